@@ -29,6 +29,9 @@ GPU) and relays rank 0's line; under torch.distributed.run (WORLD_SIZE set) it i
 round (C3), meta-tasks/s with ONE task per rank (the configs[3] / [4] shape: meta_batch_size = ranks) and with
 `--tasks-per-rank` in flight, each with its all-reduce time, and the same iteration in the other matrix modes.
 
+The timed region is exactly `--steps` steps, run once; `ms_per_step` is its duration / steps.  `--dump-outputs DIR`
+writes what the last timed step computed (`dump_outputs`) as DIR/<name>.npy, read back before anything else runs.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -37,9 +40,7 @@ import os
 import sys
 import time
 
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '24')     # before the HIP runtime initialises: see e-osvos_amd/__init__.py
-
-import torch  # noqa: E402
+import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -53,6 +54,27 @@ PMC_FILES = [os.path.join(ROOT, 'profiles', n) for n in ('r06_pmc_dominant_kerne
 
 
 MFMAS_PER_FMA = {'f16x3': 3, 'bf16x6': 6}      # 16-bit MFMA issues per fp32 multiply-accumulate
+DUMP_SAMPLE = 1 << 23                           # --dump-outputs: weight vectors are written as a fixed sample of this many values
+
+
+def param_sample(flat):
+    """A fixed sample of a flat weight vector for --dump-outputs: DUMP_SAMPLE positions drawn with seed 0 (in index order),
+    the same positions in every run; the whole vector when it is not larger."""
+    flat = flat.detach().float().cpu()
+    if flat.numel() <= DUMP_SAMPLE:
+        return flat
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+    return flat[idx]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: one DIR/<name>.npy per array, float32 or float64 (about 37 MB in all)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t, dtype=np.float64)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def matrix_peak(mode):
@@ -286,8 +308,13 @@ def bench_meta(a, eng, dist, rank, world, sd, lrs, x, y, xg, yg, barrier, dev, m
         step()                                                                  # (the collective range-guard verdict falls in the first)
     from eosvos_amd import engine as engine_mod
     mode = mode_of(mt.eng, engine_mod)                                           # the mode the timed meta-iterations run in
-    dt, samples = timed_median(step, a.steps, barrier, dist, dev)
+    dt = timed(step, a.steps, barrier, dist, dev)
+    samples = [dt]
     ms_per_step = 1e3 * dt / a.steps
+    if a.dump_outputs and rank == 0:
+        # the last timed meta-iteration: its tasks' meta losses and the learned state (lrs + model init) after its outer step
+        dump_outputs(a.dump_outputs, {'meta_losses': torch.tensor([float(l) for l in losses], dtype=torch.float64),
+                                      'state_sample': param_sample(mt.state)})
     if mode_of(mt.eng, engine_mod) != mode:
         raise SystemExit(f'bench.py: the matrix mode changed inside the timed region ({mode} -> {mode_of(mt.eng, engine_mod)})')
     mt.profile = {}
@@ -331,6 +358,9 @@ def main(argv=None, engine_factory=None, device=None, backend='nccl'):
     ap.add_argument('--steps', type=int, default=None, help='timed steps (default: 200 fine-tune iterations / 40 '
                                                              'meta-iterations, a timed region of about 2 s)')
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (fine-tune: loss, logits and a fixed sample '
+                         'of the updated weights; meta: the meta losses and a fixed sample of the learned state)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-meta', action='store_true')
     ap.add_argument('--no-ab', action='store_true', help='skip the fp32-MFMA-mode comparison in extra')
@@ -396,21 +426,18 @@ def main(argv=None, engine_factory=None, device=None, backend='nccl'):
     # the mode the TIMED steps run in: read after the warm-up, in which the guard may have moved the engine to bf16x6
     mode = mode_of(eng, engine_mod)
     guard_log0 = list(engine_mod.GUARD_LOG)
-    dt, samples = timed_median(step, a.steps, barrier, dist, dev)
+    dt = timed(step, a.steps, barrier, dist, dev)    # exactly the K steps the caller asked for, one region
+    samples = [dt]
     ms_per_step = 1e3 * dt / a.steps
     value = world * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        # what the last timed step computed: its loss, the logits of its forward pass and the weights after its update
+        dump_outputs(a.dump_outputs, {'loss': eng.last_loss(), 'logits': eng.debug_tensor('logits'),
+                                      'params_sample': param_sample(eng.get_params())})
     last_loss = eng.finetune_step(xg, yg)           # sanity: still finite after K steps
     if mode_of(eng, engine_mod) != mode or list(engine_mod.GUARD_LOG) != guard_log0:
         raise SystemExit(f'bench.py: the matrix mode changed inside the timed region ({mode} -> {mode_of(eng, engine_mod)}, guard log '
                          f'{engine_mod.GUARD_LOG}): the line would name a mode it did not time')
-    # `value` is the EXACT K steps the caller asked for (median of 3 when K < 100); a short K is a 0.2 s region, so the same
-    # step is also timed over >= 100 steps (one region, about 2 s) and both are reported
-    long_run = None
-    if a.steps < 100:
-        nl = 200
-        dtl = timed(step, nl, barrier, dist, dev)
-        long_run = {'steps': nl, 'ms_per_step': 1e3 * dtl / nl, 'value': world * nl / dtl,
-                    'note': f'the same step over one timed region of {nl} steps (the caller asked for {a.steps})'}
 
     # dominant kernel: the same steps once more with HIP events around every matrix-core launch
     psteps = min(a.steps, 20)
@@ -632,7 +659,7 @@ def main(argv=None, engine_factory=None, device=None, backend='nccl'):
             'config': {'workload': 'e-OSVOS-50 fine-tune iteration (BASELINE configs[1]): DeepLabV3+-ResNet50, '
                                    f'batch {BATCH}, {H}x{W}, BCE, per-neuron-lr SGD; one (sequence, object) per rank',
                        'batch': BATCH, 'height': H, 'width': W, 'parallelism': f'replicas x{world}'},
-            'roofline': roofline, 'cpu_baseline': cpu, 'configs': configs, 'long_run': long_run, 'extra': extra,
+            'roofline': roofline, 'cpu_baseline': cpu, 'configs': configs, 'extra': extra,
         }
         print(json.dumps(out), flush=True)
     eng.close()

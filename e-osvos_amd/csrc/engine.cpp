@@ -1637,7 +1637,7 @@ int eosvos_set_side_stream(eosvos_engine* e, int on) {
   if (hipSetDevice(e->dev) != hipSuccess) { fail("hipSetDevice"); return -1; }
   if (!on && e->s2) {
     // The stream is DESTROYED, not parked: an idle second stream per engine still costs the engines that run side by side
-    // a quarter of their throughput once every stream has a hardware queue of its own (GPU_MAX_HW_QUEUES >= 6; measured
+    // a quarter of their throughput once every stream has a hardware queue of its own (six queues or more; measured
     // 41 -> 29 meta-tasks/s with four engines, profiles/r03_hw_queue_sweep.txt).
     (void)hipStreamSynchronize(e->s);
     (void)hipStreamSynchronize(e->s2);

@@ -72,7 +72,7 @@ _POOL_WARMED = []
 
 
 def warm_stream_pool(device):
-    """ROCm deals HIP streams onto GPU_MAX_HW_QUEUES (4) hardware queues: the first streams get a queue each, later ones
+    """ROCm deals HIP streams onto a few hardware queues (four by default): the first streams get a queue each, later ones
     the least-referenced queue, and engines that run side by side lose a quarter of their rate when two of their streams
     share a queue (tools/stream_queue_probe.py, profiles/r03_stream_queue_probe.txt: 4 engines at batch 1, 207 vs 263
     iterations/s).  torch hands out its 32 pooled streams in order; four consecutive ones sit on four different queues
@@ -435,6 +435,14 @@ class Engine:
             return l.value
         _ffi.check(self.lib.eosvos_finetune_step(self.h, _ptr(images), _ptr(masks), b, int(accumulate), None))
         return None
+
+    def last_loss(self):
+        """Loss of the last forward + loss (a `finetune_step` included) as a 1-element device tensor."""
+        out = torch.empty(1, device=self.device)
+        _ffi.check(self.lib.eosvos_last_loss(self.h, _ptr(out)))
+        if torch.cuda.current_stream(self.device) != self.stream:
+            self.synchronize()
+        return out
 
     def keep_grads(self, on=True):
         _ffi.check(self.lib.eosvos_keep_grads(self.h, int(on)))

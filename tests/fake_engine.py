@@ -192,6 +192,14 @@ class FakeEngine:
     def mfma_probe(self, iters=0):
         return 0.0
 
+    def last_loss(self):
+        lg = self._logits
+        return F.binary_cross_entropy_with_logits(lg, self.last_masks.float()).view(1)
+
+    def debug_tensor(self, name):
+        assert name == 'logits', name
+        return self._logits.clone()
+
 
 class FakeDeepLab(networks.DeepLabV3Plus):
     """The product's DeepLabV3Plus drop-in class with its engine replaced by the stand-in (CPU tensors accepted)."""

@@ -74,7 +74,54 @@ def test_bench_control_flow_two_ranks(tmp_path, metric):
         c = line['configs']
         assert c['meta_tasks_per_sec_tpr1'] > 0 and c['meta_tasks_per_sec_tpr4'] == line['extra']['meta_tasks_per_sec']
         assert c['meta_tpr1_allreduce_ms'] >= 0 and c['c1_b1_ms'] > 0 and c['c3_round_ms'] > 0
-        assert line['long_run']['steps'] >= 100 and line['long_run']['value'] > 0
+    # the headline is ONE timed region of exactly --steps steps (no repeats, no longer region beside it)
+    (dt,) = line['extra']['timed_region_samples_s']
+    assert 'long_run' not in line and abs(line['ms_per_step'] - 1e3 * dt / 2) < 1e-9 * line['ms_per_step']
+
+
+@pytest.mark.parametrize('metric', ['finetune', 'meta'])
+def test_bench_dump_outputs_of_the_last_timed_step(tmp_path, monkeypatch, metric):
+    """`--dump-outputs DIR` (stand-in engine, one process): float32 / float64 arrays of at most 64 MB in all, identical in two
+    runs with the same arguments, and -- fine-tune metric -- the loss of the last timed step (warm-up + K steps from the
+    loaded state), not of a step run after the timed region."""
+    import contextlib
+    import importlib.util
+    import io
+
+    import numpy as np
+    from fake_engine import FakeEngine
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
+        monkeypatch.delenv(k, raising=False)
+    spec = importlib.util.spec_from_file_location('bench_under_test3', os.path.join(os.path.dirname(HERE), 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, 'H', 16)
+    monkeypatch.setattr(bench, 'W', 24)
+    runs = []
+    for r in range(2):
+        d = tmp_path / f'run{r}'
+        with contextlib.redirect_stdout(io.StringIO()) as buf:
+            bench.main(['--steps', '3', '--warmup', '2', '--metric', metric, '--no-cpu-baseline', '--no-ab', '--no-meta',
+                        '--dump-outputs', str(d)], engine_factory=FakeEngine, device='cpu', backend='gloo')
+        assert json.loads(buf.getvalue().strip().splitlines()[-1])['steps'] == 3
+        arrays = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert all(f.endswith('.npy') for f in os.listdir(d))
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+        runs.append(arrays)
+    assert runs[0].keys() == runs[1].keys()
+    assert all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
+    if metric == 'finetune':
+        assert set(runs[0]) == {'loss', 'logits', 'params_sample'} and runs[0]['logits'].shape == (3, 1, 16, 24)
+        from eosvos_amd import synthetic
+        e = FakeEngine('resnet50', 16, 24, max_batch=3)
+        e.load_model_state(synthetic.synthetic_state('resnet50'), synthetic.synthetic_lrs('resnet50'))
+        x, y = synthetic.synthetic_frames(3, 16, 24, seed=7)
+        losses = [e.finetune_step(x, y) for _ in range(2 + 3)]
+        assert float(runs[0]['loss'][0]) == np.float32(losses[-1])
+        assert np.array_equal(runs[0]['params_sample'], bench.param_sample(e.get_params()).numpy())
+    else:
+        assert set(runs[0]) == {'meta_losses', 'state_sample'} and runs[0]['meta_losses'].shape == (4,)
 
 
 def test_bench_gpus_flag_must_match_the_world_size(tmp_path):

@@ -217,16 +217,24 @@ HIER_CASES = [('SINGLE', False), ('TENSOR', False), ('TENSOR', True), ('NEURON',
 
 @pytest.mark.parametrize('level,use_log', HIER_CASES)
 def test_g13_lr_hierarchy(golden_dir, level, use_log):
-    """lr_hierarchy_level / use_log_init_lr (meta_optim.py:27-67,157-163,180-185) vs the reference's autograd."""
-    g = np.load(os.path.join(golden_dir, 'g13_lr_hierarchy.npz'))
+    """lr_hierarchy_level / use_log_init_lr (meta_optim.py:27-67,157-163,180-185) vs the reference's autograd.
+    Gradients are compared in float64 on both sides (fixture G13-f64: the reference run in float64 on the inputs of G13):
+    in fp32 the rounding of the two inner steps moves the sums of some init gradients by more than the fingerprint
+    tolerance, by an amount that depends on the CPU's convolution kernels -- the fp32 fixture's own rounding is that
+    large.  The losses are held to both fixtures."""
+    g32 = np.load(os.path.join(golden_dir, 'g13_lr_hierarchy.npz'))
+    g = np.load(os.path.join(golden_dir, 'g13_lr_hierarchy_f64.npz'))
     tag = f'{level}_{int(use_log)}'
-    sd = synthetic.synthetic_state('resnet50')
+    sd = {k: v.double() if v.is_floating_point() else v for k, v in synthetic.synthetic_state('resnet50').items()}
     store = synthetic.synthetic_lr_state('resnet50', level, use_log)
+    store = [s.double() for s in store] if isinstance(store, list) else store.double()
     x, y = synthetic.synthetic_frames(1, *SMALL, seed=1302)
+    x, y = x.double(), y.double()
     xm, ym = torch.flip(x, dims=[3]), torch.flip(y, dims=[3])
     out = meta.meta_task_hier(sd, store, level, use_log, [(x, y)] * 2, (xm, ym))
-    np.testing.assert_allclose(out['train_losses'], g[tag + '_train_losses'], rtol=2e-4)
-    assert abs(out['meta_loss'] - g[tag + '_meta_loss'][0]) < 2e-4 * abs(g[tag + '_meta_loss'][0])
+    for ref in (g32, g):
+        np.testing.assert_allclose(out['train_losses'], ref[tag + '_train_losses'], rtol=2e-4)
+        assert abs(out['meta_loss'] - ref[tag + '_meta_loss'][0]) < 2e-4 * abs(ref[tag + '_meta_loss'][0])
     if level == 'PARAM':
         for a, b in zip(np.stack([fp(t) for t in out['g_lr']]), g[tag + '_lr_grad_fp']):
             fp_close(a, b, rtol=2e-3, atol=1e-4 * abs(b[1]) + 1e-12)
