@@ -105,6 +105,16 @@ _SIGNATURES = {
                                              ctypes.c_int] + [ctypes.c_int] * 9 + [c_float_p]),
     'eosvos_test_conv_bwd_algo': (ctypes.c_int, [_E, ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p] +
                                   [ctypes.c_int] * 9 + [c_float_p, c_float_p]),
+    'eosvos_test_groupnorm': (ctypes.c_int, [_E, ctypes.c_int, c_float_p, ctypes.c_int, c_float_p, ctypes.c_int, c_float_p,
+                                             c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_float, c_float_p, ctypes.c_int, c_float_p, ctypes.c_void_p,
+                                             ctypes.c_int]),
+    'eosvos_test_maxpool': (ctypes.c_int, [_E, c_float_p] + [ctypes.c_int] * 4 + [c_float_p, ctypes.c_void_p, c_float_p, c_float_p]),
+    'eosvos_test_resize': (ctypes.c_int, [_E] + [ctypes.c_int] * 7 + [c_float_p, ctypes.c_int] * 5),
+    'eosvos_test_aspp_pool': (ctypes.c_int, [_E] + [ctypes.c_int] * 4 + [c_float_p] * 4 + [ctypes.c_int] + [c_float_p] * 3 +
+                              [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, c_float_p, ctypes.c_int] + [c_float_p] * 4 +
+                              [ctypes.c_int]),
+    'eosvos_test_head': (ctypes.c_int, [_E, c_float_p, c_float_p, c_float_p, ctypes.c_int64, ctypes.c_int] + [c_float_p] * 4),
     'eosvos_test_conv_presplit': (ctypes.c_int, [c_float_p] * 9 + [ctypes.c_int] * 10 + [ctypes.c_void_p]),
     'eosvos_test_wgrad_presplit': (ctypes.c_int, [c_float_p] * 8 + [ctypes.c_int] * 15 + [ctypes.c_void_p]),
 }

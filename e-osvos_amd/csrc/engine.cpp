@@ -621,6 +621,15 @@ inline void plan_mix(uint64_t v) {
   for (int i = 0; i < 8; ++i) { h ^= (v >> (8 * i)) & 0xffu; h *= 0x100000001b3ull; }
 }
 inline void plan_begin(eosvos_engine* e, int phase) { tl_plan_engine = e; tl_plan_phase = phase; e->plan_fp[phase] = 0xcbf29ce484222325ull; }
+// One forward_impl / backward_impl records into its engine's fingerprint and nothing else does: the scope clears the
+// thread's recording engine on every exit (error returns included), so later launches -- a scratch engine of a test entry
+// point, eosvos_bench_conv -- neither mix into a live engine's plan nor write into a destroyed one.
+struct PlanScope {
+  PlanScope(eosvos_engine* e, int phase) { plan_begin(e, phase); }
+  ~PlanScope() { tl_plan_engine = nullptr; }
+  PlanScope(const PlanScope&) = delete;
+  PlanScope& operator=(const PlanScope&) = delete;
+};
 void trace(const char* kind, int ci, long M, long N, long K, int splits, double frac = 1.0) {
   plan_mix((uint64_t)(unsigned char)kind[0] | ((uint64_t)(unsigned char)kind[1] << 8) | ((uint64_t)strlen(kind) << 16));
   plan_mix((uint64_t)ci); plan_mix((uint64_t)M); plan_mix((uint64_t)N); plan_mix((uint64_t)K); plan_mix((uint64_t)splits);
@@ -1918,6 +1927,7 @@ int eosvos_create_ex(eosvos_engine** out, int arch, int norm_mode, int height, i
 static int unalias_impl(eosvos_engine* e);
 int eosvos_destroy(eosvos_engine* e) {
   if (!e) return 0;
+  if (tl_plan_engine == e) tl_plan_engine = nullptr;      // (PlanScope already clears it; this thread only)
   // engines that read this engine's learned state get their own copy back before its memory goes; an alias leaves its source's list
   while (!e->aliased_by.empty()) (void)unalias_impl(e->aliased_by.back());
   if (e->alias_src) {
@@ -2158,7 +2168,7 @@ static int forward_impl(eosvos_engine* e, const float* images, int B) {
   if (B != e->lastB) pair_reset(e);          // another batch size: a new trajectory for the pre-split producers' scales
   if (e->fwd_masks) ++e->pair_iter;          // training forward: the iteration the pre-split siblings belong to
   plans_match_mode(e);
-  plan_begin(e, 0);
+  PlanScope plan_scope(e, 0);
   amax_new_phase(e, 0);
   if (h3_mode() && amax_init(e)) return fail("f16x3 matrix mode: no room for the absmax slots of this topology");
   if (h3_mode()) {
@@ -2301,7 +2311,7 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
   if (!e->mask8.empty() && !e->masks_valid)
     return fail("backward after eosvos_infer: an inference forward keeps no ReLU masks (run eosvos_forward / eosvos_finetune_step)");
   plans_match_mode(e);
-  plan_begin(e, 1);
+  PlanScope plan_scope(e, 1);
   const int64_t P4 = (int64_t)B * e->h4 * e->w4;
   const int P16 = e->h16 * e->w16;
   amax_new_phase(e, 1);
@@ -2457,7 +2467,6 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
   }
   if (flush_updates(e, B, update, accumulate, 1, e->s)) return 1;
   for (size_t ci = 0; ci < e->upd_splits.size(); ++ci) plan_mix((uint64_t)e->upd_splits[ci]);     // slabs per conv (incl. grouped launches)
-  tl_plan_engine = nullptr;
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(std::string("backward launch: ") + hipGetErrorString(err));
   return 0;
@@ -3188,6 +3197,123 @@ int eosvos_test_conv_bwd(eosvos_engine* e, const float* x, const float* w_oihw, 
   ModeScope mode_scope(e);
   return eosvos_test_conv_bwd_algo(e, EOSVOS_ALGO_DIRECT, x, w_oihw, g, nullptr, nullptr, B, H, W, Cin, Cout, k, stride, dil, pad, dx,
                                    dw_oihw);
+}
+
+// ---- op-level entry points of the other kernels (misc_kernels.hip) --------------------------------------------------
+// Each runs the production launcher with the engine's own geometry helpers (gn_geom inside launch_gn_*, make_resize +
+// upload_resize, COLSUM_CHUNKS, last_bwd_chunks) on caller DEVICE tensors, on the engine's stream; scratch lives for one call.
+namespace {
+struct OpScratch {
+  eosvos_engine t;                 // only its allocator and stream (upload_resize allocates through an engine)
+  explicit OpScratch(eosvos_engine* e) { t.s = e->s; t.s2 = nullptr; t.dev = e->dev; }
+  ~OpScratch() {
+    (void)hipStreamSynchronize(t.s);
+    for (void* q : t.allocs) (void)hipFree(q);
+  }
+};
+}  // namespace
+
+int eosvos_test_groupnorm(eosvos_engine* e, int bwd, float* z, int ldz, const float* g, int ldg, const float* gamma,
+                          const float* beta, const float* res, int ldres, int relu, int B, int P, int C, float eps, float* y,
+                          int ldy, float* stats, uint8_t* m8, int ldm8) {
+  ModeScope mode_scope(e);
+  if (!e || !z || !gamma || !stats) return fail("null argument");
+  if (B < 1 || P < 1 || C < 16 || C % 16 || ldz < C || ldz % 4) return fail("bad GroupNorm geometry");
+  const int C4 = C / 4, colblocks = (C4 + 255) / 256, ncol = C4 / colblocks;
+  if (ncol * colblocks != C4 || (ncol * 4) % (C / 16)) return fail("channel count not supported by the GroupNorm kernels");
+  OpScratch sc(e);
+  float* partial = sc.t.falloc(gn_partial_floats(B));
+  if (!partial) return fail("hipMalloc GroupNorm partials");
+  if (bwd) {
+    if (!g || ldg < C || ldg % 4) return fail("bad gradient argument");
+    launch_gn_backward(z, ldz, g, ldg, gamma, stats, partial, B, P, C, e->s);
+  } else {
+    if (!beta || !y || ldy < C || ldy % 4 || (res && (ldres < C || ldres % 4))) return fail("bad forward argument");
+    if (m8 && (!relu || ldm8 < C4)) return fail("the ReLU mask needs relu and ldm8 >= C / 4");
+    launch_gn_forward(z, ldz, gamma, beta, res, ldres, y, ldy, stats, partial, B, P, C, eps, relu, e->s, nullptr, m8, ldm8);
+  }
+  HIPOK(hipStreamSynchronize(e->s));
+  HIPOK(hipGetLastError());
+  return 0;
+}
+int eosvos_test_maxpool(eosvos_engine* e, const float* x, int B, int H, int W, int C, float* y, uint8_t* idx, const float* gy,
+                        float* gx) {
+  ModeScope mode_scope(e);
+  if (!e || !x || !y || !idx) return fail("null argument");
+  if (B < 1 || H < 1 || W < 1 || C < 4 || C % 4) return fail("bad max-pool geometry");
+  if ((gy == nullptr) != (gx == nullptr)) return fail("gy and gx go together");
+  const int Ho = conv_out(H, 3, 2, 1, 1), Wo = conv_out(W, 3, 2, 1, 1);
+  launch_maxpool_fwd(x, y, idx, B, H, W, C, Ho, Wo, e->s);
+  if (gy) launch_maxpool_bwd(gy, idx, gx, B, H, W, C, Ho, Wo, e->s);
+  HIPOK(hipStreamSynchronize(e->s));
+  HIPOK(hipGetLastError());
+  return 0;
+}
+int eosvos_test_resize(eosvos_engine* e, int align_corners, int hin, int win, int hout, int wout, int B, int C, const float* x,
+                       int ldx, float* y, int ldy, const float* gy, int ldgy, float* gx, int ldgx, const float* mask, int ldmask) {
+  ModeScope mode_scope(e);
+  if (!e) return fail("null engine");
+  if (hin < 1 || win < 1 || hout < 1 || wout < 1 || B < 1 || C < 1) return fail("bad resize geometry");
+  if ((x == nullptr) != (y == nullptr) || (gy == nullptr) != (gx == nullptr)) return fail("x / y and gy / gx go together");
+  if ((x && (ldx < C || ldy < C)) || (gy && (ldgy < C || ldgx < C)) || (mask && ldmask < C)) return fail("bad leading dimension");
+  OpScratch sc(e);
+  ResizeTab th, tw;
+  if (upload_resize(&sc.t, make_resize(hin, hout, align_corners != 0), hin, hout, th)) return 1;
+  if (upload_resize(&sc.t, make_resize(win, wout, align_corners != 0), win, wout, tw)) return 1;
+  if (x) launch_resize_fwd(x, ldx, y, ldy, B, C, th, tw, e->s);
+  if (gy) launch_resize_bwd(gy, ldgy, gx, ldgx, mask, ldmask, B, C, th, tw, e->s);
+  HIPOK(hipStreamSynchronize(e->s));
+  HIPOK(hipGetLastError());
+  return 0;
+}
+int eosvos_test_aspp_pool(eosvos_engine* e, int B, int P, int K, int N, const float* w, const float* a, const float* bias,
+                          const float* x, int ldx, float* v, float* pool, float* y, int ldy, uint8_t* m8, int ldm8,
+                          const float* gy, int ldgy, float* gpool, float* gv, float* dw, float* gx, int ldgx) {
+  ModeScope mode_scope(e);
+  if (!e || !w || !x || !v || !pool || !y) return fail("null argument");
+  if (B < 1 || P < 1 || K < 4 || K % 4 || N < 4 || N % 4 || ldx < K || ldx % 4 || ldy < N || ldy % 4) return fail("bad pooling geometry");
+  if ((a == nullptr) != (bias == nullptr)) return fail("a and bias go together (folded norm)");
+  if (m8 && ldm8 < N / 4) return fail("ldm8 < N / 4");
+  if (gy && (!gpool || !gv || !dw || !gx || ldgy < N || ldgy % 4 || ldgx < K || ldgx % 4)) return fail("bad backward argument");
+  OpScratch sc(e);
+  float* colscratch = sc.t.falloc((int64_t)B * 64 * (K > N ? K : N));      // COLSUM_CHUNKS partial sums, as the engine sizes it
+  float* slab = gy ? sc.t.falloc((int64_t)N * K) : nullptr;
+  if (!colscratch || (gy && !slab)) return fail("hipMalloc pooling scratch");
+  // forward (engine.cpp forward_impl, pool_branch): mean over pixels -> relu?(a * W v + b) -> every pixel of the channel slice
+  launch_colsum(x, ldx, v, B, P, K, 1.0f / (float)P, colscratch, e->s);
+  launch_gemv_fwd(w, v, a, bias, pool, B, N, K, e->s);
+  launch_bcast_pixels(pool, y, ldy, B, P, N, 1.f, e->s, m8, ldm8);
+  if (gy) {
+    // backward (backward_impl): the slice's gradient summed over pixels (the ReLU mask is the consumer's: its data gradient
+    // applies it) -> gv = a W^T gp, dW = gp v^T -> gv / P to every pixel
+    launch_colsum(gy, ldgy, gpool, B, P, N, 1.f, colscratch, e->s);
+    launch_gemv_bwd(w, v, gpool, a, gv, slab, B, N, K, e->s);
+    launch_bcast_pixels(gv, gx, ldgx, B, P, K, 1.0f / (float)P, e->s);
+    // the weight update's reduction (apply_update): the slab times the folded-norm scale of each output channel
+    launch_sgd_update(dw, slab, 1, (int64_t)N * K, a, nullptr, nullptr, dw, K, (int64_t)N * K, e->s);
+  }
+  HIPOK(hipStreamSynchronize(e->s));
+  HIPOK(hipGetLastError());
+  return 0;
+}
+int eosvos_test_head(eosvos_engine* e, const float* x, const float* w, const float* bias, int64_t P, int C, float* y,
+                     const float* g, float* gx, float* dw) {
+  ModeScope mode_scope(e);
+  if (!e || !x || !w || !bias || !y) return fail("null argument");
+  if (P < 1 || C < 4 || C % 4) return fail("bad head geometry");
+  if (g && (!gx || !dw)) return fail("the backward needs gx and dw");
+  OpScratch sc(e);
+  launch_last_fwd(x, w, bias, y, P, C, e->s);
+  if (g) {
+    const int chunks = last_bwd_chunks(P);
+    float* ws = sc.t.falloc((int64_t)chunks * (C + 1));
+    if (!ws) return fail("hipMalloc head weight-gradient slabs");
+    launch_last_bwd(x, w, g, gx, ws, P, C, chunks, e->s);
+    launch_sgd_update(dw, ws, chunks, C + 1, nullptr, nullptr, nullptr, dw, C + 1, C + 1, e->s);      // slab sum, as apply_update
+  }
+  HIPOK(hipStreamSynchronize(e->s));
+  HIPOK(hipGetLastError());
+  return 0;
 }
 
 // Weight gradient on pre-split operands (presplit_kernels.hip), stand-alone: no engine.  Device pointers; g / x NHWC fp32,

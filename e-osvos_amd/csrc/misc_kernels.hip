@@ -380,7 +380,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restric
         const float vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (first || vv[j] > m[j]) { m[j] = vv[j]; mi[j] = (unsigned char)(ky * 3 + kx); }
+          if (first || vv[j] > m[j] || isnan(vv[j])) { m[j] = vv[j]; mi[j] = (unsigned char)(ky * 3 + kx); }   // NaN wins, as in torch
         first = false;
       }
     }
@@ -1209,7 +1209,12 @@ __device__ __forceinline__ void gn_reduce_groups(float (&s1)[4], float (&s2)[4],
     partial[((size_t)b * 16 + g0 + tid) * chunks + chunk] = make_float2(a, q);
   }
 }
-// forward: (u, v) = (z, z^2);  backward: (gamma g, gamma g zhat)
+// The forward sums are shifted by a pivot per (image, group), the group's first channel at pixel 0 (gn_pivot): E[d^2] - E[d]^2
+// of d = z - pivot loses no precision to a mean far from zero (unshifted fp32 sums of z^2 cancel like (mean / std)^2).
+__device__ __forceinline__ float gn_pivot(const float* __restrict__ z, int ldz, int b, int P, int ch, int cg) {
+  return z[(size_t)b * P * ldz + (ch / cg) * cg];
+}
+// forward: (u, v) = (d, d^2), d = z - pivot;  backward: (gamma g, gamma g zhat)
 template <bool BWD>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ z, int ldz, const float* __restrict__ g, int ldg,
                                                         const float* __restrict__ gamma, const float* __restrict__ stats,
@@ -1231,6 +1236,9 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
       const int bg = b * 16 + (c + j) / cg;
       ga[j] = gamma[c + j]; mu[j] = stats[bg * 2]; rs[j] = stats[bg * 2 + 1];
     }
+  } else if (act) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) mu[j] = gn_pivot(z, ldz, b, P, c + j, cg);     // forward: mu = the pivot
   }
   if (act) {
     const float* zp = z + (size_t)b * P * ldz + c;
@@ -1250,7 +1258,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           if (BWD) { const float t = ga[j] * gg[j]; s1[j] += t; s2[j] += t * ((zz[j] - mu[j]) * rs[j]); }
-          else { s1[j] += zz[j]; s2[j] += zz[j] * zz[j]; }
+          else { const float d = zz[j] - mu[j]; s1[j] += d; s2[j] += d * d; }
         }
       }
     }
@@ -1263,7 +1271,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (BWD) { const float t = ga[j] * gg[j]; s1[j] += t; s2[j] += t * ((zz[j] - mu[j]) * rs[j]); }
-        else { s1[j] += zz[j]; s2[j] += zz[j] * zz[j]; }
+        else { const float d = zz[j] - mu[j]; s1[j] += d; s2[j] += d * d; }
       }
     }
   }
@@ -1272,9 +1280,10 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
 // The (image, group) totals of this workgroup's groups from the per-chunk partials, summed in double in a fixed order by 16
 // lanes per group (every workgroup of the launch computes the same bits; round 5: this replaces a 5 us launch per pass, 124
 // per iteration).  st[g] = {mean, rstd} (forward; also written to `stats_out` by the chunk-0 workgroups: the backward pass
-// reads it) or {S1 / n, S2 / n} (backward).
+// reads it) or {S1 / n, S2 / n} (backward).  Forward: the partials are shifted by gn_pivot of z.
 __device__ __forceinline__ void gn_finish_groups(const float2* __restrict__ partial, int chunks, int b, int g0, int ng, double inv_n,
-                                                 float eps, bool bwd, float* __restrict__ stats_out, float (*st)[2]) {
+                                                 float eps, bool bwd, float* __restrict__ stats_out, float (*st)[2],
+                                                 const float* __restrict__ z, int ldz, int P, int cg) {
   const int gi = threadIdx.x >> 4, l = threadIdx.x & 15;
   double a = 0.0, q = 0.0;
   if (gi < ng) {
@@ -1290,10 +1299,10 @@ __device__ __forceinline__ void gn_finish_groups(const float2* __restrict__ part
   if (gi < ng && l == 0) {
     if (bwd) { st[gi][0] = (float)(a * inv_n); st[gi][1] = (float)(q * inv_n); }
     else {
-      const double mean = a * inv_n;
-      double var = q * inv_n - mean * mean;
+      const double dm = a * inv_n;
+      double var = q * inv_n - dm * dm;
       if (var < 0.0) var = 0.0;
-      st[gi][0] = (float)mean;
+      st[gi][0] = (float)((double)gn_pivot(z, ldz, b, P, (g0 + gi) * cg, cg) + dm);
       st[gi][1] = (float)(1.0 / sqrt(var + (double)eps));
       if (stats_out && blockIdx.x == 0) { stats_out[(b * 16 + g0 + gi) * 2] = st[gi][0]; stats_out[(b * 16 + g0 + gi) * 2 + 1] = st[gi][1]; }
     }
@@ -1313,7 +1322,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(float* __restrict__ z, in
   const int tid = threadIdx.x, chunk = blockIdx.x, b = blockIdx.y, col0 = blockIdx.z * gm.ncol;
   const int cg = C >> 4;
   const int g0 = col0 * 4 / cg;
-  gn_finish_groups(partial, gm.chunks, b, g0, gm.ncol * 4 / cg, inv_n, eps, BWD, BWD ? nullptr : stats, st);
+  gn_finish_groups(partial, gm.chunks, b, g0, gm.ncol * 4 / cg, inv_n, eps, BWD, BWD ? nullptr : stats, st, z, ldz, P, cg);
   const int col = tid % gm.ncol, row = tid / gm.ncol;
   const bool act = row < gm.rows;
   const int c = (col0 + col) * 4;

@@ -16,6 +16,18 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _optr(t):
+    return _ptr(t) if t is not None else None
+
+
+def _ld(t):
+    """Leading dimension (elements per pixel) of a pixel-major view with unit channel stride whose images are P pixels apart."""
+    if t is None:
+        return 0
+    assert t.stride(-1) == 1 and t.stride(0) == t[0].numel() // t.shape[-1] * t.stride(-2), 'not a pixel-major view'
+    return t.stride(-2)
+
+
 def _dev_f32(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
@@ -684,6 +696,71 @@ class Engine:
         _ffi.check(self.lib.eosvos_test_conv_bwd(self.h, _ptr(x_nhwc), _ptr(w_oihw), _ptr(g_nhwc), B, H, W, Cin,
                                                  Cout, k, stride, dil, pad, _ptr(dx), _ptr(dw)))
         return dx, dw
+
+    # Op-level entries of misc_kernels.hip (include/eosvos.h) on device tensors.  Pixel-major (B, P, C) / (B, H, W, C) views with
+    # unit channel stride; the pixel stride is the leading dimension, so a channel slice of a wider buffer may be passed.
+    def test_groupnorm(self, z, gamma, beta, eps=1e-5, res=None, relu=False, y=None, m8=None):
+        """GroupNorm(16, C) forward of z (B, P, C) into y (default: a new (B, P, C)); returns (y, stats (B, 16, 2) = mean /
+        rstd).  m8 (uint8 (B, P, >= C / 4)) receives the ReLU mask bits (relu only)."""
+        B, P, C = z.shape
+        y = torch.empty(B, P, C, device=self.device) if y is None else y
+        stats = torch.empty(B, 16, 2, device=self.device)
+        _ffi.check(self.lib.eosvos_test_groupnorm(self.h, 0, _ptr(z), _ld(z), None, 0, _ptr(gamma), _ptr(beta), _optr(res),
+                                                  _ld(res), int(relu), B, P, C, float(eps), _ptr(y), _ld(y), _ptr(stats), _optr(m8),
+                                                  _ld(m8)))
+        return y, stats
+
+    def test_groupnorm_bwd(self, z, g, gamma, stats):
+        """dL/dz of that forward (without ReLU / residual) given g = dL/d(gn output) (B, P, C); overwrites z and returns it."""
+        B, P, C = z.shape
+        _ffi.check(self.lib.eosvos_test_groupnorm(self.h, 1, _ptr(z), _ld(z), _ptr(g), _ld(g), _ptr(gamma), None, None, 0, 0,
+                                                  B, P, C, 0.0, None, 0, _ptr(stats), None, 0))
+        return z
+
+    def test_maxpool(self, x, gy=None):
+        """max_pool2d(3, 2, 1) of a dense x (B, H, W, C): (y, argmax bytes, gx or None)."""
+        B, H, W, C = x.shape
+        assert x.is_contiguous() and (gy is None or gy.is_contiguous())
+        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        y = torch.empty(B, Ho, Wo, C, device=self.device)
+        idx = torch.empty(B, Ho, Wo, C, dtype=torch.uint8, device=self.device)
+        gx = torch.empty_like(x) if gy is not None else None
+        _ffi.check(self.lib.eosvos_test_maxpool(self.h, _ptr(x), B, H, W, C, _ptr(y), _ptr(idx), _optr(gy), _optr(gx)))
+        return y, idx, gx
+
+    def test_resize(self, align_corners, x=None, y=None, gy=None, gx=None, mask=None):
+        """Bilinear resize x (B, hin, win, C) -> y (B, hout, wout, C) and / or its backward gy -> gx (zero where mask <= 0);
+        the caller provides every tensor."""
+        (B, hin, win, C), (hout, wout) = (x if x is not None else gx).shape, (y if y is not None else gy).shape[1:3]
+        _ffi.check(self.lib.eosvos_test_resize(self.h, int(align_corners), hin, win, hout, wout, B, C, _optr(x), _ld(x), _optr(y),
+                                               _ld(y), _optr(gy), _ld(gy), _optr(gx), _ld(gx), _optr(mask), _ld(mask)))
+
+    def test_aspp_pool(self, x, w, a=None, bias=None, y=None, m8=None, gy=None):
+        """ASPP image pooling of x (B, P, K) with w (N, K): dict of v, pool, y (default (B, P, N)) and, given gy (B, P, N),
+        gpool, gv, dw, gx."""
+        B, P, K = x.shape
+        N = w.shape[0]
+        dev = self.device
+        r = {'v': torch.empty(B, K, device=dev), 'pool': torch.empty(B, N, device=dev),
+             'y': y if y is not None else torch.empty(B, P, N, device=dev)}
+        if gy is not None:
+            r.update(gpool=torch.empty(B, N, device=dev), gv=torch.empty(B, K, device=dev), dw=torch.empty(N, K, device=dev),
+                     gx=torch.empty(B, P, K, device=dev))
+        q = lambda k: _optr(r.get(k))
+        _ffi.check(self.lib.eosvos_test_aspp_pool(self.h, B, P, K, N, _ptr(w), _optr(a), _optr(bias), _ptr(x), _ld(x), q('v'),
+                                                  q('pool'), q('y'), _ld(r['y']), _optr(m8), _ld(m8), _optr(gy), _ld(gy),
+                                                  q('gpool'), q('gv'), q('dw'), q('gx'), K))
+        return r
+
+    def test_head(self, x, w, bias, g=None):
+        """1-channel classifier of a dense x (P, C): (y (P,), gx or None, dw (C + 1,) = weight and bias gradient, or None)."""
+        P, C = x.shape
+        assert x.is_contiguous()
+        y = torch.empty(P, device=self.device)
+        gx = torch.empty_like(x) if g is not None else None
+        dw = torch.empty(C + 1, device=self.device) if g is not None else None
+        _ffi.check(self.lib.eosvos_test_head(self.h, _ptr(x), _ptr(w), _ptr(bias), P, C, _ptr(y), _optr(g), _optr(gx), _optr(dw)))
+        return y, gx, dw
 
 
 class RcclComm:

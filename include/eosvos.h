@@ -390,6 +390,38 @@ int eosvos_test_conv_bwd(eosvos_engine* e, const float* x_nhwc, const float* w_o
                          const float* g_nhwc, int B, int H, int W, int Cin, int Cout, int k,
                          int stride, int dil, int pad, float* dx_nhwc, float* dw_oihw);
 
+/* Op-level entries of the other kernels (misc_kernels.hip) for the parity tests: the production launchers with the engine's
+ * own geometry, on caller DEVICE tensors (NHWC, `ld*` = floats per pixel, so a channel slice of a wider buffer works), on the
+ * engine's stream; they synchronise before returning.
+ *
+ * GroupNorm(16, C) with frozen affine, torch.nn.GroupNorm (deeplabv3plus.py:180-191).  bwd = 0: y = relu?(group_norm(z) *
+ * gamma + beta (+ res)), stats [B][16][2] = {mean, rstd} out, m8 (may be NULL; needs relu): bit j of byte [p][q] = (y of
+ * channel 4q + j > 0), row pitch ldm8 bytes.  bwd = 1: z <- dL/dz of that forward without the ReLU / residual, given
+ * g = dL/d(group_norm output) and the forward's stats (y, beta, res, m8 unused). */
+int eosvos_test_groupnorm(eosvos_engine* e, int bwd, float* z, int ldz, const float* g, int ldg, const float* gamma,
+                          const float* beta, const float* res, int ldres, int relu, int B, int P, int C, float eps, float* y,
+                          int ldy, float* stats, uint8_t* m8, int ldm8);
+/* F.max_pool2d(x, 3, 2, 1) of the stem (torchvision resnet maxpool), dense NHWC x [B][H][W][C] -> y [B][Ho][Wo][C] with the
+ * argmax bytes idx (tap | 0x80 when the maximum is > 0).  gy, gx (both or neither): gx = max_pool2d backward(gy) * (x > 0)
+ * (x being the ReLU output that was pooled). */
+int eosvos_test_maxpool(eosvos_engine* e, const float* x, int B, int H, int W, int C, float* y, uint8_t* idx, const float* gy,
+                        float* gx);
+/* F.interpolate(mode='bilinear', align_corners) from hin x win to hout x wout (deeplabv3plus.py:144, :161): x -> y when both are
+ * given, and gx = (mask ? mask > 0 : 1) * backward(gy) when gy / gx are given. */
+int eosvos_test_resize(eosvos_engine* e, int align_corners, int hin, int win, int hout, int wout, int B, int C, const float* x,
+                       int ldx, float* y, int ldy, const float* gy, int ldgy, float* gx, int ldgx, const float* mask, int ldmask);
+/* The ASPP image-pooling branch (ASPPPooling, deeplabv3plus.py:100-112): v = mean over P pixels of x [B][P][K], pool =
+ * relu(a * (w v) + bias) (a = bias = NULL: w v without affine, the GroupNorm engine's form), broadcast to y [B][P][N] (+ the ReLU
+ * mask bytes m8 when not NULL).  With gy: gpool = sum over pixels of gy [B][P][N] (already ReLU-masked, as the consumer's data
+ * gradient leaves it), gv = a * w^T gpool, dw [N][K] = a * gpool^T v (the slab after the update's scaling), gx [B][P][K] = gv / P at every pixel. */
+int eosvos_test_aspp_pool(eosvos_engine* e, int B, int P, int K, int N, const float* w, const float* a, const float* bias,
+                          const float* x, int ldx, float* v, float* pool, float* y, int ldy, uint8_t* m8, int ldm8,
+                          const float* gy, int ldgy, float* gpool, float* gv, float* dw, float* gx, int ldgx);
+/* The 1-channel classifier (Conv2d(256, 1, 1) with bias, deeplabv3plus.py:163): y [P] = x [P][C] . w + bias.  With g: gx =
+ * g w^T * (x > 0) (x is a ReLU output) and dw [C + 1] = {sum_p g x, sum_p g} after the reduction of the per-chunk slabs. */
+int eosvos_test_head(eosvos_engine* e, const float* x, const float* w, const float* bias, int64_t P, int C, float* y,
+                     const float* g, float* gx, float* dw);
+
 /* Op-level entry of the pre-split operand path (round 6; e-osvos_amd/csrc/presplit_kernels.hip): the weight gradient of one
  * convolution -- dL/dW of `/root/reference/src/networks/deeplabv3plus.py:32-53`'s convs as autograd computes it -- from operands
  * stored as fp16 (hi, lo) pairs under one power-of-two scale per tensor.  Stand-alone (no engine); device pointers.
