@@ -201,6 +201,8 @@ struct eosvos_engine {
   int loss_kind = EOSVOS_LOSS_BCE;      // loss of the fused entry points (eosvos_set_loss)
   int* aug_tab = nullptr;               // eosvos_warp_affine: adelta[W] bdelta[W] X0[H] Y0[H], then the nonzero counter
   float* aug_ctab = nullptr;            // bicubic coefficients at 1/32 pixel: [32][4]
+  void* davis_buf = nullptr;            // eosvos_davis_counts: counts + bit-packed boundary maps (grow-only, freed by destroy)
+  size_t davis_cap = 0;
   int lr_level = EOSVOS_LR_NEURON, lr_log = 0;
   float *lr_elem = nullptr, *glr_tmp = nullptr, *ptmp = nullptr;
   int *row_tensor = nullptr, *tensor_row0 = nullptr, *all_row0 = nullptr;
@@ -1942,6 +1944,7 @@ int eosvos_destroy(eosvos_engine* e) {
   if (e->s3) { (void)hipStreamSynchronize(e->s3); (void)hipStreamDestroy(e->s3); }
   if (e->ev_s3) (void)hipEventDestroy(e->ev_s3);
   for (void* p : e->allocs) (void)hipFree(p);
+  if (e->davis_buf) (void)hipFree(e->davis_buf);
   delete e;
   return 0;
 }
@@ -2641,6 +2644,46 @@ int eosvos_warp_affine_hw(eosvos_engine* e, const float* src, int channels, int 
     HIPOK(hipMemcpyAsync(nonzero_host, counter, sizeof(int), hipMemcpyDeviceToHost, e->s));
     HIPOK(hipStreamSynchronize(e->s));
   }
+  return 0;
+}
+
+// ---- DAVIS-2017 evaluation counts (evaluate.py:345-359, helper_func.py:444-458) -------------------------------------
+int eosvos_davis_counts(eosvos_engine* e, const uint8_t* pred, const uint8_t* gt, int n_frames, int height, int width, int n_obj,
+                        int bound_pix, int64_t* counts_out) {
+  if (!e || !pred || !gt || !counts_out) return fail("davis_counts: null argument");
+  if (n_frames < 0 || height < 1 || width < 1) return fail("davis_counts: bad frame geometry");
+  if (width > 64 * 64) return fail("davis_counts: frames wider than 4096 pixels are not supported");
+  if (n_obj < 1 || n_obj > 255) return fail("davis_counts: n_obj must be in [1, 255]");
+  if (bound_pix < 0 || bound_pix > 63) return fail("davis_counts: the dilation radius must be in [0, 63] pixels");
+  if (n_frames == 0) return 0;
+  // frames go through in chunks whose boundary maps take at most 64 MB (at least one frame per chunk)
+  const size_t nw = (size_t)(width + 63) / 64;
+  const size_t map_words = (size_t)n_obj * height * nw;          // one frame, one of the two maps
+  const size_t count_bytes = (size_t)n_frames * n_obj * 6 * sizeof(int64_t);
+  size_t chunk = (size_t)(64 << 20) / (2 * map_words * 8);
+  chunk = std::max<size_t>(1, std::min<size_t>({chunk, (size_t)n_frames, 65535}));
+  const size_t need = count_bytes + 2 * chunk * map_words * 8;
+  if (need > e->davis_cap) {
+    HIPOK(hipStreamSynchronize(e->s));                            // earlier calls' launches may still read the old buffer
+    if (e->davis_buf) HIPOK(hipFree(e->davis_buf));
+    e->davis_buf = nullptr;
+    e->davis_cap = 0;
+    HIPOK(hipMalloc(&e->davis_buf, need));
+    e->davis_cap = need;
+  }
+  int64_t* counts = (int64_t*)e->davis_buf;
+  unsigned long long* bmp = (unsigned long long*)((char*)e->davis_buf + count_bytes);     // count_bytes is a multiple of 8
+  unsigned long long* bmg = bmp + chunk * map_words;
+  HIPOK(hipMemsetAsync(counts, 0, count_bytes, e->s));
+  const size_t plane = (size_t)height * width;
+  for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += chunk) {
+    const int nf = (int)std::min<size_t>(chunk, (size_t)n_frames - f0);
+    launch_davis_counts(pred + f0 * plane, gt + f0 * plane, nf, height, width, n_obj, bound_pix, bmp, bmg,
+                        counts + f0 * n_obj * 6, e->s);
+    HIPOK(hipGetLastError());
+  }
+  HIPOK(hipMemcpyAsync(counts_out, counts, count_bytes, hipMemcpyDeviceToHost, e->s));
+  HIPOK(hipStreamSynchronize(e->s));
   return 0;
 }
 

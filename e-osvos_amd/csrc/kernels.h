@@ -390,6 +390,10 @@ void launch_merge_labels(const float* probs, int n_obj, int64_t n_pix, uint8_t* 
 // cv2.warpAffine (+ optional horizontal flip of the source) of C planes; tables = adelta[W] bdelta[W] X0[H] Y0[H]
 void launch_warp_affine(const float* src, float* dst, int C, int H, int W, const double* inv_matrix, int round_delta,
                         const float* ctab, int cubic, int flip, int* nonzero, hipStream_t s);
+// DAVIS counts (metrics_kernels.hip) of `frames` uint8 label-map pairs: counts [frames][n_obj][6] int64, zeroed by the caller,
+// receive atomic sums; bmp / bmg: frames * n_obj * H * ceil(W/64) words each.  W <= 4096, r <= 63, 1 <= n_obj <= 255
+void launch_davis_counts(const uint8_t* pred, const uint8_t* gt, int frames, int H, int W, int n_obj, int r,
+                         unsigned long long* bmp, unsigned long long* bmg, int64_t* counts, hipStream_t s);
 
 // theta' = theta - lr[cout]*g, g = rowscale[cout] * sum_z ws[z][...]; optional gsum += g; g_out = g
 void launch_sgd_update(float* w, const float* ws, int splits, int64_t slab, const float* rowscale,

@@ -337,3 +337,149 @@ def sequence_J(labels, gt_labels, num_objects):
     for o in range(1, num_objects + 1):
         js.append(np.mean([jaccard(labels[f] == o, gt_labels[f] == o) for f in range(1, len(labels) - 1)]))
     return float(np.mean(js))
+
+
+# ---- DAVIS-2017 J and F measures (the `davis` package as evaluate.py:345-359 -> eval_davis_seq, helper_func.py:444-458) ----
+# Restated from the public DAVIS-2017 evaluation code.  Per object o and evaluated frame f, P = (pred == o), G = (gt == o):
+#   J = |P & G| / |P | G|, 1 if both are empty (`jaccard`).
+#   F: bmap(S) is seg2bmap, b = S^E | S^Sd | S^SE with E, Sd, SE = S shifted one pixel from the right, below and
+#      below-right (zero-filled); b[-1, :] = S[-1, :] ^ E[-1, :], then b[:, -1] = S[:, -1] ^ Sd[:, -1], then b[-1, -1] = 0.
+#      r = bound_th if bound_th >= 1 else ceil(bound_th * sqrt(H^2 + W^2)); dilate = binary dilation by the disk
+#      dx^2 + dy^2 <= r^2, outside the frame being 0.  fg_match = |bmap(P) & dilate(bmap(G))|, gt_match =
+#      |bmap(G) & dilate(bmap(P))|, n_fg = |bmap(P)|, n_gt = |bmap(G)|.  precision, recall = fg_match / n_fg,
+#      gt_match / n_gt, except (1, 0) when only n_fg = 0, (0, 1) when only n_gt = 0, (1, 1) when both are 0;
+#      F = 2PR / (P + R), 0 when P + R = 0.
+#   Frames 1 .. N-2 (as `sequence_J`).  Statistics of one object's per-frame values X (`davis_statistics`): mean, recall =
+#   mean(X > 0.5), decay = mean(bin 0) - mean(bin 3) over four bins of frames.
+# The integer counts (inter, union, n_fg, n_gt, fg_match, gt_match) come from the device (`Engine.davis_counts`) or from
+# `boundary_counts_host`; every ratio and statistic is float64 on the host.
+COUNT_FIELDS = ('inter', 'union', 'n_fg', 'n_gt', 'fg_match', 'gt_match')
+
+
+def davis_bound_pix(bound_th, height, width):
+    """Dilation radius in pixels of the F measure: bound_th itself when >= 1, else ceil(bound_th * frame diagonal)."""
+    if bound_th >= 1:
+        if bound_th != int(bound_th):
+            raise ValueError(f'bound_th >= 1 is a radius in pixels and must be whole: {bound_th}')
+        return int(bound_th)
+    return int(np.ceil(bound_th * np.sqrt(float(height) ** 2 + float(width) ** 2)))
+
+
+def seg2bmap(seg):
+    """Boundary pixels of a binary mask (the `davis` package's seg2bmap, as restated above)."""
+    seg = np.asarray(seg).astype(bool)
+    e, s, se = np.zeros_like(seg), np.zeros_like(seg), np.zeros_like(seg)
+    e[:, :-1] = seg[:, 1:]
+    s[:-1, :] = seg[1:, :]
+    se[:-1, :-1] = seg[1:, 1:]
+    b = (seg ^ e) | (seg ^ s) | (seg ^ se)
+    b[-1, :] = seg[-1, :] ^ e[-1, :]
+    b[:, -1] = seg[:, -1] ^ s[:, -1]
+    b[-1, -1] = False
+    return b
+
+
+def _dilate_disk(b, r):
+    """Binary dilation of a 2-D mask by the disk dx^2 + dy^2 <= r^2 (zero outside): per row offset dy a horizontal
+    dilation by floor(sqrt(r^2 - dy^2)), from running sums."""
+    h, w = b.shape
+    cs = np.zeros((h, w + 1), dtype=np.int32)
+    np.cumsum(b, axis=1, out=cs[:, 1:])
+    x = np.arange(w)
+    out = np.zeros_like(b, dtype=bool)
+    rows = {}
+    for dy in range(-min(r, h - 1), min(r, h - 1) + 1):          # rows further away than the frame is tall add nothing
+        k = int(np.sqrt(r * r - dy * dy))
+        while k * k > r * r - dy * dy:
+            k -= 1
+        while (k + 1) * (k + 1) <= r * r - dy * dy:
+            k += 1
+        if k not in rows:
+            rows[k] = (cs[:, np.minimum(x + k + 1, w)] - cs[:, np.maximum(x - k, 0)]) > 0
+        hd = rows[k]
+        if dy >= 0:
+            out[:h - dy] |= hd[dy:]
+        else:
+            out[-dy:] |= hd[:h + dy]
+    return out
+
+
+def boundary_counts_host(pred, gt, n_obj, bound_th=0.008):
+    """Host (numpy) twin of `Engine.davis_counts`: (N, H, W) label maps -> (N, n_obj, 6) int64 counts (`COUNT_FIELDS`) of
+    every frame and object 1..n_obj.  Label values above n_obj belong to no object."""
+    pred, gt = np.asarray(pred), np.asarray(gt)
+    if pred.ndim != 3 or pred.shape != gt.shape:
+        raise ValueError('boundary_counts_host: pred and gt must be (N, H, W) label maps of one shape')
+    n, h, w = pred.shape
+    r = davis_bound_pix(bound_th, h, w)
+    out = np.zeros((n, n_obj, 6), dtype=np.int64)
+    for f in range(n):
+        for o in range(1, n_obj + 1):
+            p, g = pred[f] == o, gt[f] == o
+            bp, bg = seg2bmap(p), seg2bmap(g)
+            out[f, o - 1] = (np.logical_and(p, g).sum(), np.logical_or(p, g).sum(), bp.sum(), bg.sum(),
+                             np.logical_and(bp, _dilate_disk(bg, r)).sum(), np.logical_and(bg, _dilate_disk(bp, r)).sum())
+    return out
+
+
+def _mean_or_nan(x):
+    return float(np.mean(x)) if len(x) else float('nan')
+
+
+def davis_statistics(values):
+    """(mean, recall, decay) of one object's per-frame values, as the `davis` package's db_statistics: recall =
+    mean(X > 0.5); decay = mean(bin 0) - mean(bin 3) with bin i = X[ids[i] : ids[i+1] + 1] and
+    ids = round(linspace(1, n, 5) + 1e-10) - 1.  The published code casts ids to uint8, and ids[i+1] + 1 stays uint8: for
+    n > 256 the bin bounds wrap modulo 256 (bin 3 is then usually empty and the decay NaN).  That cast is kept as it is,
+    wrapped explicitly (a float-to-uint8 cast of an out-of-range value is platform-dependent in numpy)."""
+    x = np.asarray(values, dtype=np.float64)
+    if len(x) == 0:
+        return float('nan'), float('nan'), float('nan')
+    ids = [int(v) % 256 for v in np.round(np.linspace(1, len(x), 5) + 1e-10) - 1]
+    bins = [x[ids[i]:(ids[i + 1] + 1) % 256] for i in range(4)]
+    return float(np.mean(x)), float(np.mean(x > 0.5)), _mean_or_nan(bins[0]) - _mean_or_nan(bins[3])
+
+
+def measures_from_counts(counts):
+    """Counts of the evaluated frames, (n_frames, n_obj, 6) -> {'J': {'mean', 'recall', 'decay'}, 'F': {...}}, one float
+    per object in each list (the shape of the reference's eval_davis_seq)."""
+    counts = np.asarray(counts, dtype=np.int64)
+    out = {m: {'mean': [], 'recall': [], 'decay': []} for m in ('J', 'F')}
+    for o in range(counts.shape[1]):
+        js, fs = [], []
+        for inter, union, n_fg, n_gt, fg_match, gt_match in counts[:, o].tolist():
+            js.append(1.0 if union == 0 else float(inter) / float(union))      # exactly `jaccard`
+            if n_fg == 0 and n_gt > 0:
+                prec, rec = 1.0, 0.0
+            elif n_fg > 0 and n_gt == 0:
+                prec, rec = 0.0, 1.0
+            elif n_fg == 0 and n_gt == 0:
+                prec, rec = 1.0, 1.0
+            else:
+                prec, rec = float(fg_match) / float(n_fg), float(gt_match) / float(n_gt)
+            fs.append(0.0 if prec + rec == 0 else 2 * prec * rec / (prec + rec))
+        for m, vals in (('J', js), ('F', fs)):
+            mean, recall, decay = davis_statistics(vals)
+            out[m]['mean'].append(mean)
+            out[m]['recall'].append(recall)
+            out[m]['decay'].append(decay)
+    return out
+
+
+def davis_counts(engine, pred, gt, n_obj, bound_th=0.008):
+    """Counts of all frames: on the engine's device when it has `davis_counts` (label maps are moved there), else on the
+    host (the stand-in engines of the CPU tests)."""
+    if engine is not None and hasattr(engine, 'davis_counts'):
+        dev = engine.device
+        pred = torch.as_tensor(pred).to(device=dev, dtype=torch.uint8)
+        gt = torch.as_tensor(gt).to(device=dev, dtype=torch.uint8)
+        return engine.davis_counts(pred, gt, n_obj, bound_th)
+    as_np = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    return boundary_counts_host(as_np(pred), as_np(gt), n_obj, bound_th)
+
+
+def sequence_measures(labels, gt_labels, num_objects, engine=None, bound_th=0.008):
+    """J and F statistics per object over frames 1..N-2, in the reference's shape:
+    {'J': {'mean': [...], 'recall': [...], 'decay': [...]}, 'F': {...}}.  J means equal `sequence_J`'s per-object values."""
+    counts = davis_counts(engine, labels, gt_labels, num_objects, bound_th)
+    return measures_from_counts(counts[1:len(counts) - 1])

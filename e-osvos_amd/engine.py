@@ -482,6 +482,23 @@ class Engine:
         _ffi.check(self.lib.eosvos_merge_labels(self.h, _ptr(probs), n_obj, n_pix, _ptr(out)))
         return out
 
+    def davis_counts(self, pred, gt, n_obj, bound_th=0.008):
+        """DAVIS J / F counts of label maps (`eosvos_davis_counts`; evaluate.py:345-359, helper_func.py:444-458).
+        pred, gt: (N, H, W) uint8 tensors on the engine's device, any H and W (W <= 4096).  Returns an (N, n_obj, 6) int64
+        numpy array: inter, union, n_fg, n_gt, fg_match, gt_match per frame and object (`data.measures_from_counts`)."""
+        import numpy as np
+        from .data import davis_bound_pix
+        if pred.dtype != torch.uint8 or gt.dtype != torch.uint8 or pred.dim() != 3 or pred.shape != gt.shape:
+            raise ValueError('davis_counts: pred and gt must be (N, H, W) uint8 tensors of one shape')
+        if pred.device != self.device or gt.device != self.device:
+            raise ValueError(f'davis_counts: the label maps must be on {self.device}')
+        n, h, w = pred.shape
+        pred, gt = pred.contiguous(), gt.contiguous()
+        counts = np.empty((n, n_obj, 6), dtype=np.int64)
+        _ffi.check(self.lib.eosvos_davis_counts(self.h, _ptr(pred), _ptr(gt), n, h, w, n_obj, davis_bound_pix(bound_th, h, w),
+                                                counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return counts
+
     # ---- meta-training ----------------------------------------------------------------
     def meta_task_begin(self):
         _ffi.check(self.lib.eosvos_meta_task_begin(self.h))

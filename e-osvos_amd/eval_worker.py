@@ -74,7 +74,8 @@ def run(cfg, run_dir, device, data_root='data', height=480, width=854, num_frame
                                        vis_win_names=info.get('vis_win_names'))
                 best[key] = res['best_mean_J']
                 line = {'dataset': key, 'meta_iter': info['meta_iter'], 'mean_J': res['mean_J'], 'best_mean_J': best[key],
-                        'J_seq': res['J_seq'], 'time_per_frame': res['time_per_frame']}
+                        'J_seq': res['J_seq'], 'time_per_frame': res['time_per_frame'], 'mean_F': res['mean_F'],
+                        'mean_JF': res['mean_JF']}
                 with open(os.path.join(run_dir, 'eval_log.jsonl'), 'a') as f:
                     f.write(json.dumps(line) + '\n')
                 log(json.dumps(dict(line, mode='concurrent_eval')))

@@ -278,9 +278,13 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
     grouped): budget and grouping change the split-K partition, i.e. the order of fp32 partial sums, so the last
     bits of a result (not its parity margins, `profiles/*parity_margins*`) depend on how many objects of the sequence
     landed on this rank.  EOSVOS_OBJECTS_IN_FLIGHT=1 gives one schedule-independent order.
-    Returns dict(J_seq, mean_J, best_mean_J, time_per_frame, labels={seq: (N,H,W) uint8})."""
+    Returns dict(J_seq, mean_J, best_mean_J, time_per_frame, labels={seq: (N,H,W) uint8}) and the DAVIS J / F statistics
+    of `eval_davis_seq` (`evaluate.py:345-359`), one entry per object in sequence order: J_obj (the per-object J means the
+    reference calls J_seq), J_recall_seq, J_decay_seq, F_seq, F_recall_seq, F_decay_seq, with mean_F and
+    mean_JF = (mean J_obj + mean_F) / 2.  Their counts are taken on the device from the merged label maps
+    (`data.davis_counts`); J_seq, mean_J and the best-checkpoint choice stay per sequence, from `sequence_J`."""
     from .checkpoint import save_meta_checkpoint
-    from .data import sequence_J
+    from .data import davis_counts, measures_from_counts, sequence_J
     rank = dist.get_rank() if dist is not None else 0
     world = dist.get_world_size() if dist is not None else 1
     ds_cfg = cfg['datasets'][dataset_key]
@@ -340,30 +344,40 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
             return ds.sequence_tensors(sq, dev, with_frame_ids=True)
         fr, gs = ds.sequence_tensors(sq, dev)
         return fr, gs, [0] * len(gs)
-    load = lambda sq: read(copy.copy(dataset), sq, 'cpu')
+
+    def read_gt(ds, sq):
+        """Ground-truth label maps of the J / F measures (none in test mode)."""
+        return None if ds.test_mode else ds.label_maps(sq)
+
+    def load(sq):
+        ds = copy.copy(dataset)
+        return read(ds, sq, 'cpu') + (read_gt(ds, sq),)
     budget_before = getattr(model, 'wg_budget', 0)
     ahead = pool.submit(load, seqs[0]) if pool else None
     finishing = []
 
-    def finish(ds, sq, labels, n_obj):
-        """PNG files + J of one finished sequence (host only)."""
+    def finish(ds, sq, labels, n_obj, gt_maps, counts):
+        """PNG files, J and the J / F statistics of one finished sequence (host only)."""
         if rank == 0 and preds_dir is not None:
             names = ds.frame_names(sq)
             for f in range(labels.shape[0]):
                 if getattr(ds, 'all_frames', False) and not ds.has_label_file(sq, names[f]):
                     continue                                                    # evaluate.py:334-335
                 save_label_png(os.path.join(preds_dir, sq, names[f] + '.png'), labels[f].numpy())
-        return 0.0 if ds.test_mode else sequence_J(labels.numpy(), ds.label_maps(sq), n_obj)     # evaluate.py:344-346
+        if ds.test_mode:                                                        # evaluate.py:344-347
+            return 0.0, {m: {'mean': [0.0], 'recall': [0.0], 'decay': [0.0]} for m in ('J', 'F')}
+        return sequence_J(labels.numpy(), gt_maps, n_obj), measures_from_counts(counts[1:len(counts) - 1])
 
     for k, seq in enumerate(seqs):
         tp = time.perf_counter()
         if pool:
-            frames, gts, fids = ahead.result()
+            frames, gts, fids, gt_maps = ahead.result()
             frames, gts = frames.to(device or model.device), [g.to(device or model.device) for g in gts]
             if k + 1 < len(seqs):
                 ahead = pool.submit(load, seqs[k + 1])
         else:
             frames, gts, fids = read(dataset, seq, device or model.device)
+            gt_maps = read_gt(dataset, seq)
         tp = tick('read_s', tp)
         n = frames.shape[0]
         probs = torch.zeros(len(gts), n, *frames.shape[-2:], device=frames.device)
@@ -391,16 +405,25 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
         num_frames += n * len(gts)                                              # per (object, frame), evaluate.py:320
         if model.engine is None:                                                # this rank had no item yet
             model._ensure_engine(frames.shape[2], frames.shape[3], 1)
-        labels = merge_objects(model.engine, [probs[o] for o in range(len(gts))]).cpu()
+        labels = merge_objects(model.engine, [probs[o] for o in range(len(gts))])
+        counts = None
+        if not dataset.test_mode:                                               # J / F counts where the labels are
+            gt_dev = torch.from_numpy(np.ascontiguousarray(gt_maps, dtype=np.uint8)).to(labels.device)
+            counts = davis_counts(model.engine, labels, gt_dev, len(gts))
+        labels = labels.cpu()
         labels_out[seq] = labels
         tp = tick('merge_s', tp)
         if pool:
-            finishing.append(pool.submit(finish, copy.copy(dataset), seq, labels, len(gts)))
+            finishing.append(pool.submit(finish, copy.copy(dataset), seq, labels, len(gts), gt_maps, counts))
         else:
-            finishing.append(finish(dataset, seq, labels, len(gts)))
+            finishing.append(finish(dataset, seq, labels, len(gts), gt_maps, counts))
         tp = tick('finish_s', tp)
+    stats = {k: [] for k in ('J_obj', 'J_recall_seq', 'J_decay_seq', 'F_seq', 'F_recall_seq', 'F_decay_seq')}
     for seq, j in zip(seqs, finishing):
-        J_seq.append(j.result() if pool else j)
+        j_seq, ev = j.result() if pool else j
+        J_seq.append(j_seq)
+        for key, (m, st) in zip(stats, [(m, st) for m in ('J', 'F') for st in ('mean', 'recall', 'decay')]):
+            stats[key].extend(ev[m][st])                                        # evaluate.py:354-359
         if log is not None and rank == 0:
             log(f"{dataset_key}: {seq} [{J_seq[-1]}]")
     if pool:
@@ -413,6 +436,8 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
         if hasattr(m, 'close_parked_engines'):
             m.close_parked_engines()
     mean_J = float(np.mean(J_seq)) if J_seq else 0.0
+    mean_F = float(np.mean(stats['F_seq'])) if stats['F_seq'] else 0.0
+    mean_JF = (float(np.mean(stats['J_obj'])) + mean_F) / 2 if stats['J_obj'] else 0.0
     out_best = best_mean_J
     if rank == 0 and save_dir is not None and not dataset.test_mode:
         save_meta_checkpoint(os.path.join(save_dir, f'last_{dataset_key}_meta_iter.model'), meta_optim_state_dict,
@@ -423,4 +448,5 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
             save_meta_checkpoint(os.path.join(save_dir, f'best_{dataset_key}_meta_iter.model'), meta_optim_state_dict,
                                  meta_iter, meta_epoch, vis_win_names)
     return {'J_seq': J_seq, 'mean_J': mean_J, 'best_mean_J': out_best, 'labels': labels_out,
-            'time_per_frame': eval_time / max(num_frames, 1), 'meta_iter': meta_iter, 'phases': phases}
+            'time_per_frame': eval_time / max(num_frames, 1), 'meta_iter': meta_iter, 'phases': phases,
+            'mean_F': mean_F, 'mean_JF': mean_JF, **stats}

@@ -208,6 +208,7 @@ def _run(cfg, run, run_dir, meta_mode, eval_proc, height, width, num_frames, num
         if rank == 0:
             print(json.dumps({'mode': 'eval', 'data': data_tag, 'seconds': time.time() - t0,
                               'datasets': {k: {'mean_J': r['mean_J'], 'J_seq': r['J_seq'], 'time_per_frame': r['time_per_frame'],
+                                               'mean_F': r['mean_F'], 'mean_JF': r['mean_JF'],
                                                'labels_present': sorted({int(v) for l in r['labels'].values() for v in l.unique().tolist()})}
                                            for k, r in results.items()}}))
         if dist is not None:

@@ -242,6 +242,18 @@ int eosvos_warp_affine(eosvos_engine* e, const float* src, int channels, int fli
 int eosvos_warp_affine_hw(eosvos_engine* e, const float* src, int channels, int height, int width, int flip, double rot_deg,
                           double scale, int interp, float* dst, int* nonzero_host);
 
+/* ---- DAVIS-2017 evaluation counts (evaluate.py:345-359 -> eval_davis_seq, helper_func.py:444-458) ---------------- */
+/* The integer counts behind the `davis` package's region (J) and contour (F) measures, for every frame of a sequence and
+ * every object o in 1..n_obj, with P = (pred == o), G = (gt == o) (label values above n_obj belong to no object):
+ * counts_out[(f * n_obj + o - 1) * 6 + k], k = 0 inter |P & G|, 1 union |P | G|, 2 n_fg |bmap(P)|, 3 n_gt |bmap(G)|,
+ * 4 fg_match |bmap(P) & dilate(bmap(G))|, 5 gt_match |bmap(G) & dilate(bmap(P))|.  bmap is seg2bmap (boundary pixels), dilate
+ * a binary dilation by the disk dx^2 + dy^2 <= bound_pix^2 (outside the frame is 0).  Ratios and statistics are the
+ * caller's (data.sequence_measures).  pred / gt: device uint8 label maps [n_frames][height][width] of any size (`e` lends
+ * its stream and scratch memory only); counts_out: host memory.  Synchronises the engine's stream.  Rejected without a
+ * launch: a null pointer, bound_pix outside [0, 63], n_obj outside [1, 255], width > 4096. */
+int eosvos_davis_counts(eosvos_engine* e, const uint8_t* pred, const uint8_t* gt, int n_frames, int height, int width, int n_obj,
+                        int bound_pix, int64_t* counts_out);
+
 /* ---- learning-rate hierarchy (meta_optim.py:27-67) ------------------------------------ */
 /* `lr_hierarchy_level`: how the learned lr state is stored.  NEURON (cfgs/meta.yaml:36) one
  * value per output channel; TENSOR one per trainable tensor (`log_init_lr` of shape
