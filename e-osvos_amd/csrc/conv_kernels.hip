@@ -28,15 +28,10 @@ namespace eosvos {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#ifndef EOSVOS_BK
 #define EOSVOS_BK 32
-#endif
-#ifndef EOSVOS_EB
 #define EOSVOS_EB 4   // epilogue rows whose global operands are requested together
-#endif
-#ifndef EOSVOS_OCC
+#define EOSVOS_EB128 EOSVOS_EB      // rows per batch in the 128-wide kernels (their accumulators are dead here: registers to spare)
 #define EOSVOS_OCC 2
-#endif
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 // Blocks are dealt round-robin over the 8 XCDs; give each XCD a contiguous range of tiles
@@ -48,24 +43,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 __device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-// streaming (non-temporal) forms for epilogue operands that are touched once per launch (experiment: -DEOSVOS_NT_EPILOGUE)
-typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ldg4_stream(const float* p) {
-#ifdef EOSVOS_NT_EPILOGUE
-  const nt_f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f32x4*>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-#else
-  return ldg4(p);
-#endif
-}
-__device__ __forceinline__ void stg4_stream(float* p, const float4& v) {
-#ifdef EOSVOS_NT_EPILOGUE
-  nt_f32x4 q = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(q, reinterpret_cast<nt_f32x4*>(p));
-#else
-  *reinterpret_cast<float4*>(p) = v;
-#endif
-}
 // 16-byte buffer load; offsets past the descriptor's size return 0 (hardware range check)
 __device__ __forceinline__ float4 bufld4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
   auto v = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
@@ -127,9 +104,7 @@ __device__ __forceinline__ void pair_store4(unsigned char* y2, size_t pix, int l
 // conv_plan selects it per launch (ConvArgs::deep).  DEEP = 1: one LDS stage of K = 32 (two barriers per K
 // step); DEEP = 2: two stages of K = 16, for channel counts that are not a multiple of 32 (304: no padded step).
 #define EOSVOS_BK_DEEP 16
-#ifndef EOSVOS_DEEP_TILES
 #define EOSVOS_DEEP_TILES 1024
-#endif
 template <int BN, bool KMAJOR, int DEEP = 0>
 __global__ __launch_bounds__(256, DEEP ? 3 : EOSVOS_OCC) void conv_igemm_kernel(const ConvArgs p) {
   constexpr int BM = 128, BK = DEEP == 2 ? EOSVOS_BK_DEEP : EOSVOS_BK;
@@ -254,13 +229,8 @@ __global__ __launch_bounds__(256, DEEP ? 3 : EOSVOS_OCC) void conv_igemm_kernel(
     }
     int cur_tap = -1;
     auto load_tiles = [&](int ks) {
-#ifdef EOSVOS_DEEP_CHUNK_MAJOR      // experiment: taps innermost (the 9 taps of a channel chunk re-read nearly the same rows)
-      const int vt = DEEP ? ks % T : ks / chunks;
-      const int c0 = DEEP ? (ks / T) * BK : (ks - vt * chunks) * BK;
-#else
       const int vt = ks / chunks;
       const int c0 = (ks - vt * chunks) * BK;
-#endif
       const int tap = p.tprefix ? (int)((tappack >> (4 * vt)) & 15) : vt;
       if (tap != cur_tap) {          // wave-uniform
         cur_tap = tap;
@@ -540,23 +510,19 @@ __global__ __launch_bounds__(256) void conv_fixup_kernel(const ConvArgs p) {
   if (p.amax_y) amax_block_commit(ymax, p.amax_y);
 }
 
-static int env_int(const char* name, int dflt);
-
 // Tile width in N.  128 x 64 tiles (half the bytes of every parked partial tile, twice the tiles, 1.5x the LDS reads per
 // MFMA) pay for launches that have few tiles AND a short K: per-layer A/B in the f16x3 mode (tools/layer_times.py,
 // profiles/r03_bn64_layer_times.txt) -- the 1x1 convs of layer2-4 / ASPP at batch 1 gain 5-30 %, long-K 3x3 convs and
 // everything with >= 256 tiles lose.  Batch 1 only: at batch 3 the same rule makes the two-stream iteration 1.4 % slower
 // (9.97 -> 10.12 ms) although the single-stream per-layer times predict a small gain; batch 1: 5.46 -> 5.33 ms.
-// EOSVOS_TUNE_BN64_TILES / _KSTEPS move the two thresholds (0 tiles: never).
 int conv_bn(const ConvArgs& a) {
   if (a.nseg > 0) return 128;                     // the K-concatenated kernel exists for 128-wide tiles only
   if (a.N <= 64) return 64;
-  static const int thr = env_int("EOSVOS_TUNE_BN64_TILES", 256), kthr = env_int("EOSVOS_TUNE_BN64_KSTEPS", 16);      // (40 until the streaming kernels took the short-K launches; re-measured: 4.55 -> 4.50 ms)
-  static const int kthr_anyb = env_int("EOSVOS_TUNE_BN64_ANYB_KSTEPS", 0);     // experiment: the rule at any batch for K steps <= this
-  if (thr > 0 && conv_mfma_mode() == 2 && !a.plane_rows) {
+  constexpr long kMaxTiles = 256, kMaxKSteps = 16;      // (K steps: 40 until the streaming kernels took the short-K launches; re-measured: 4.55 -> 4.50 ms)
+  if (a.B == 1 && conv_mfma_mode() == 2 && !a.plane_rows) {
     const long tiles = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
     const long ksteps = (long)a.KH * a.KW * ((a.Kc + 31) / 32);
-    if (tiles < thr && ksteps <= (a.B == 1 ? kthr : kthr_anyb)) return 64;
+    if (tiles < kMaxTiles && ksteps <= kMaxKSteps) return 64;
   }
   return 128;
 }
@@ -676,17 +642,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 #define X6_ROWB 96
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-// Two fp32 values -> bf16 pieces, packed (e1 << 16 | e0).  Default: the truncated top 16 bits (one v_perm_b32; the
-// 3-way split of a 24-bit significand is then exact).  -DEOSVOS_X6_RNE rounds to nearest even instead
-// (v_cvt_pk_bf16_f32): same parity margins (profiles/r02_parity_margins.txt), 4 % slower step on the same box.
+// Two fp32 values -> bf16 pieces, packed (e1 << 16 | e0): the truncated top 16 bits (one v_perm_b32; the 3-way split of
+// a 24-bit significand is then exact).  Rounding to nearest even instead (v_cvt_pk_bf16_f32) was measured: same parity
+// margins (profiles/r02_parity_margins.txt), 4 % slower step on the same box.
 __device__ __forceinline__ unsigned x6_pack(float e0, float e1) {
-#ifdef EOSVOS_X6_RNE
-  bf16x2 v = {(__bf16)e0, (__bf16)e1};
-  return *reinterpret_cast<unsigned*>(&v);
-#else
   return __builtin_amdgcn_perm(__float_as_uint(e1), __float_as_uint(e0), 0x07060302u);
-#endif
 }
 __device__ __forceinline__ float x6_lo(unsigned pk) { return __uint_as_float(pk << 16); }          // piece of e0 as fp32
 __device__ __forceinline__ float x6_hi(unsigned pk) { return __uint_as_float(pk & 0xffff0000u); }  // piece of e1 as fp32
@@ -759,30 +719,14 @@ __device__ __forceinline__ float h3_scale_bits(unsigned w1, bool two, unsigned w
   inv = __uint_as_float((unsigned)(254 - f) << 23);
   return __uint_as_float((unsigned)f << 23);
 }
-// The 2-way fp16 split of two values.  Experiment (EOSVOS_MIX_SPLIT=1): both halves of each piece register written in place
-// by v_fma_mixlo / mixhi_f16 -- hi = f16(x * s), lo = f16(fma(x, s, -hi)), 2 VALU instructions per value against 4 for
-// multiply / v_cvt_pk_f16_f32 / convert back / subtract / v_cvt_pk_f16_f32.  Bit-identical pieces (tools/probes/
-// mixsplit_probe.cpp: 2^24 values at four scales; only x = -0 differs, hi = +0 / lo = -0 instead of -0 / +0) -- and SLOWER:
-// iteration 9.07 against 8.87 ms, batch 1 4.80 against 4.71 (same box).  Half the instructions is not half the issue time:
-// the mix forms run at a lower rate than the conversions they replace.
-#ifndef EOSVOS_LATE_SCALES
-#define EOSVOS_LATE_SCALES 1
-#endif
-#ifndef EOSVOS_MIX_SPLIT
-#define EOSVOS_MIX_SPLIT 0
-#endif
+// The 2-way fp16 split of two values.  Writing both halves of each piece register in place with v_fma_mixlo / mixhi_f16
+// (2 VALU instructions per value against 4) was measured with an A/B switch since removed: bit-identical pieces
+// (tools/probes/mixsplit_probe.cpp) -- and slower, iteration 9.07 against 8.87 ms: the mix forms run at a lower rate.
 __device__ __forceinline__ void h3_split_pair(float x0, float x1, float s, unsigned& hi, unsigned& lo) {
-#if EOSVOS_MIX_SPLIT
-  asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel_hi:[0,0,0]" : "=v"(hi) : "v"(x0), "v"(s));
-  asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel_hi:[0,0,0]" : "+v"(hi) : "v"(x1), "v"(s));
-  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x0), "v"(s), "v"(hi));
-  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(x1), "v"(s), "v"(hi));
-#else
   const float a = x0 * s, b = x1 * s;
   hi = h3_pack(a, b);
   const f32x2v u = h3_unpack(hi);
   lo = h3_pack(a - u.x, b - u.y);
-#endif
 }
 // four consecutive-k values -> NP pieces of 4 x 16 bit (8 bytes) each.  NP = 3: exact bf16 split (s unused); NP = 2: fp16.
 template <int NP>
@@ -874,9 +818,6 @@ __device__ __forceinline__ void x6_mma_step(const unsigned char* As, const unsig
   }
 }
 
-#ifndef EOSVOS_H3_MB2
-#define EOSVOS_H3_MB2 0      // 1: the f16x3 conv kernel re-reads the B fragments per A pair like the bf16x6 one (fewer registers, 1.5x the LDS reads)
-#endif
 constexpr int xs_max(int a, int b) { return a > b ? a : b; }
 // LDS of a conv workgroup: NP operand planes, or the C tile that the epilogue stages through the same bytes
 template <int BN, int NP> constexpr int conv_xs_smem() { return xs_max(NP * (128 + BN) * X6_ROWB, 128 * (BN + 4) * 4); }
@@ -927,13 +868,6 @@ __device__ __forceinline__ void conv_xs_body(const ConvArgs& p, unsigned char* s
   if (NP == 2 && !MULTI) {
     h3_ax = amax_issue(p.amax_x); h3_ak = amax_issue(KMAJOR ? p.amax_ks : nullptr); h3_aw = amax_issue(p.amax_w);
     h3_pending = true;
-#if !EOSVOS_LATE_SCALES
-    float ia, ib;
-    sa = h3_scale_bits(h3_ax, KMAJOR && p.amax_ks, h3_ak, ia);
-    sb = h3_scale_bits(h3_aw, false, 0u, ib);
-    inv_ab = ia * ib;
-    h3_pending = false;
-#endif
   }
   auto scales_late = [&]() {
     if (h3_pending) {                                 // wave-uniform; true once per workgroup
@@ -1166,7 +1100,7 @@ __device__ __forceinline__ void conv_xs_body(const ConvArgs& p, unsigned char* s
       const bool more = (ks + 1) < ks_end;
       if (more) load_tiles(ks + 1);          // global loads in flight behind the MFMAs below
       __builtin_amdgcn_s_setprio(1);
-      x6_mma_step<TM, TN, ((BN == 128 && (NP == 3 || EOSVOS_H3_MB2)) ? 2 : TM), NP>(As, Bs, BM, BN, wm * 64, wn * (BN / 2), fr, fq, acc);
+      x6_mma_step<TM, TN, ((BN == 128 && NP == 3) ? 2 : TM), NP>(As, Bs, BM, BN, wm * 64, wn * (BN / 2), fr, fq, acc);
       __builtin_amdgcn_s_setprio(0);
       __syncthreads();                       // every wave is done reading the stage
       if (more) store_tiles();
@@ -1214,9 +1148,6 @@ __device__ __forceinline__ void conv_xs_body(const ConvArgs& p, unsigned char* s
       __syncthreads();
       if (full) {
         if (n < p.N) {
-#ifndef EOSVOS_EB128
-#define EOSVOS_EB128 EOSVOS_EB      // rows per batch in the 128-wide kernels (their accumulators are dead here: registers to spare)
-#endif
           constexpr int NIT = BM / CROWS, EB = BN == 128 ? EOSVOS_EB128 : EOSVOS_EB;
           // the tensor added to the tile: the residual / skip gradient (res) or the destination's previous contents (accum).
           // One register set serves both; a launch with both (none in the network) reads the second one row by row.
@@ -1237,7 +1168,7 @@ __device__ __forceinline__ void conv_xs_body(const ConvArgs& p, unsigned char* s
             }
             if (adp) {
 #pragma unroll
-              for (int j = 0; j < EB; ++j) ad[j] = ldg4_stream(adp + md[j] * adld + n);
+              for (int j = 0; j < EB; ++j) ad[j] = ldg4(adp + md[j] * adld + n);
             }
             if (use_mask8) {
 #pragma unroll
@@ -1256,7 +1187,7 @@ __device__ __forceinline__ void conv_xs_body(const ConvArgs& p, unsigned char* s
               if (p.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
               if (use_mask8 || use_mask) relu_mask8(v, mk8[j]);
               if (ok[j]) {
-                stg4_stream(p.y + md[j] * p.ldy + n, v);
+                *reinterpret_cast<float4*>(p.y + md[j] * p.ldy + n) = v;
                 if (write_m8) p.mask8_out[md[j] * p.ldm8_out + (n >> 2)] = relu_bits(v);
                 if (NP == 2 && p.y2) pair_store4(p.y2, md[j], p.ldy, n, v, y2s);
                 if (NP == 2) ymax = amax_f4(ymax, v);
@@ -1281,9 +1212,7 @@ __global__ __launch_bounds__(256, 2) void conv_x6_kernel(const ConvArgs p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[conv_xs_smem<BN, 3>()];
   conv_xs_body<BN, KMAJOR, 3>(p, smem);
 }
-#ifndef EOSVOS_H3_OCC64
-#define EOSVOS_H3_OCC64 2       // workgroups per CU the 64-wide f16x3 kernels are compiled for (experiment: 3 / 4 for short-K launches)
-#endif
+#define EOSVOS_H3_OCC64 2       // workgroups per CU the 64-wide f16x3 kernels are compiled for (3 / 4 for short-K launches were tried)
 template <int BN, bool KMAJOR>
 __global__ __launch_bounds__(256, BN == 64 ? EOSVOS_H3_OCC64 : 2) void conv_h3_kernel(const ConvArgs p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[conv_xs_smem<BN, 2>()];
@@ -1345,15 +1274,8 @@ __device__ __forceinline__ void s1_split8(const float4& lo, const float4& hi, fl
 // fragment read was a 2-way conflict (SQ_LDS_BANK_CONFLICT 42 % of the LDS cycles of conv3x3_stream_kernel) and the LDS, not
 // the matrix cores, paced the K loop.
 constexpr int frag_pitch(int row_bytes) { return row_bytes % 64 == 32 ? row_bytes : row_bytes + (96 - row_bytes % 64) % 64; }
-#ifndef EOSVOS_STREAM3X3_WPRE
-#define EOSVOS_STREAM3X3_WPRE 0       // weight fragments one K step ahead of their MFMAs: measured, no difference (9.00 vs 9.01 ms)
-#endif
-#ifndef EOSVOS_STREAM3X3_D
 #define EOSVOS_STREAM3X3_D 6       // K steps the activation ring of the 3x3 streaming kernel runs ahead (a divisor of 18)
-#endif
-#ifndef EOSVOS_STREAM_OCC
 #define EOSVOS_STREAM_OCC 1        // workgroups per CU the K <= 128 variants are compiled for (2: 128 VGPRs, 4 fragments per pass)
-#endif
 template <int K, int NC>
 __global__ __launch_bounds__(512, (K <= 128 ? EOSVOS_STREAM_OCC : 1)) void conv1x1_stream_kernel(const ConvArgs p) {
   constexpr int WAVES = 8;
@@ -1488,14 +1410,8 @@ __global__ __launch_bounds__(512, (K <= 128 ? EOSVOS_STREAM_OCC : 1)) void conv1
   };
   unsigned ymax = 0;
   int strip = gw;
-  // With one pass over the column range (NF == FH) the addend rows and mask bytes of a strip are requested ONE STRIP AHEAD,
-  // together with its activations: an HBM round trip (1-2 us) is several times a strip's MFMA time.
-#ifndef EOSVOS_STREAM_AHEAD
-#define EOSVOS_STREAM_AHEAD 0      // measured: per launch +-10 % either way, the iteration 9.50 (ahead) vs 9.45 ms: off
-#endif
-  constexpr bool AHEAD = EOSVOS_STREAM_AHEAD && NF == FH;
-  float4 adn[FH];
-  unsigned mkn[FH];
+  // (Requesting a strip's addend rows and mask bytes one strip ahead, together with its activations, was measured with an
+  // A/B switch since removed: per launch +-10 % either way, the iteration 9.50 (ahead) vs 9.45 ms.)
   auto load_ad = [&](int st, float4 (&ad)[FH], unsigned (&mk)[FH], int half) {
     const long m = rbase + (long)st * 16 + fr;
     const size_t r = (size_t)(m < rend ? m : rend - 1);
@@ -1508,10 +1424,7 @@ __global__ __launch_bounds__(512, (K <= 128 ? EOSVOS_STREAM_OCC : 1)) void conv1
       for (int f = 0; f < FH; ++f) mk[f] = p.mask8[r * p.ldm8 + ((n0 + (half + f) * 16) >> 2) + fq];
     }
   };
-  if (strip < nstrips) {
-    load_x(strip);
-    if (AHEAD) load_ad(strip, adn, mkn, 0);
-  }
+  if (strip < nstrips) load_x(strip);
   // epilogue of one 16-channel fragment: scale / shift / addend / ReLU / mask, float4 store + mask byte, absmax
   auto finish = [&](const f32x4& a4, int f16, const float4& adv, unsigned mkv, size_t row, bool ok) {
     const int n = n0 + f16 * 16 + 4 * fq;
@@ -1596,21 +1509,14 @@ __global__ __launch_bounds__(512, (K <= 128 ? EOSVOS_STREAM_OCC : 1)) void conv1
     }
     float4 ad[FH];
     unsigned mk[FH];
-    if (AHEAD) {
-#pragma unroll
-      for (int f = 0; f < FH; ++f) { ad[f] = adn[f]; mk[f] = mkn[f]; }
-    }
     const int nxt = strip + gstride;
-    if (nxt < nstrips) {                              // the next strip's operands in flight behind this strip's work
-      load_x(nxt);
-      if (AHEAD) load_ad(nxt, adn, mkn, 0);
-    }
+    if (nxt < nstrips) load_x(nxt);                   // the next strip's operands in flight behind this strip's work
     const long m = rbase + (long)strip * 16 + fr;
     const bool ok = m < rend;
     const size_t row = (size_t)(ok ? m : rend - 1);
 #pragma unroll 1
     for (int half = 0; half < NF; half += FH) {
-      if (!AHEAD) load_ad(strip, ad, mk, half);
+      load_ad(strip, ad, mk, half);
       f32x4 acc[FH];
 #pragma unroll
       for (int f = 0; f < FH; ++f) {
@@ -1782,17 +1688,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_stream_kernel(const ConvArgs p
 #pragma unroll
     for (int f = 0; f < NF; ++f) acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
     const bool border = __any(cur.ok != 0x3fu);          // wave-uniform
-#if EOSVOS_STREAM3X3_WPRE
-    // weight fragments one K step ahead of the MFMAs that use them (a K step's ds_reads would otherwise sit exposed in front
-    // of its MFMAs: two waves per SIMD do not cover an LDS round trip)
-    uint4 wn0[NF], wn1[NF];
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      const unsigned char* wp = s3_smem + (f * 16 + fr) * PITCH + fq * 16;
-      wn0[f] = *reinterpret_cast<const uint4*>(wp);
-      wn1[f] = *reinterpret_cast<const uint4*>(wp + NC * PITCH);
-    }
-#endif
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       // the slot is split in place and refilled afterwards (a copy of its 8 registers per K step otherwise); only strips that
@@ -1810,35 +1705,21 @@ __global__ __launch_bounds__(512, 1) void conv3x3_stream_kernel(const ConvArgs p
       s1_split8(a, b, sx, x0, x1);
       if (ks + D < KS) load_k(cur, ks + D, ring[ks % D]);          // the ring runs D K steps ahead, across the strip boundary
       else load_k(nx, ks + D - KS, ring[ks % D]);                  // (past the last strip: the strip's own pixels once more)
+      // (reading the weight fragments one K step ahead of their MFMAs was measured: no difference, 9.00 vs 9.01 ms)
       uint4 w0[NF], w1[NF];
-#if EOSVOS_STREAM3X3_WPRE
-#pragma unroll
-      for (int f = 0; f < NF; ++f) { w0[f] = wn0[f]; w1[f] = wn1[f]; }
-      if (ks + 1 < KS) {
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-          const unsigned char* wp = s3_smem + (f * 16 + fr) * PITCH + (ks + 1) * 64 + fq * 16;
-          wn0[f] = *reinterpret_cast<const uint4*>(wp);
-          wn1[f] = *reinterpret_cast<const uint4*>(wp + NC * PITCH);
-        }
-      }
-#else
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
         const unsigned char* wp = s3_smem + (f * 16 + fr) * PITCH + ks * 64 + fq * 16;
         w0[f] = *reinterpret_cast<const uint4*>(wp);
         w1[f] = *reinterpret_cast<const uint4*>(wp + NC * PITCH);
       }
-#endif
 #pragma unroll
       for (int f = 0; f < NF; ++f) acc[f] = MFMA_F16(__builtin_bit_cast(f16x8, w1[f]), __builtin_bit_cast(f16x8, x0), acc[f]);
 #pragma unroll
       for (int f = 0; f < NF; ++f) acc[f] = MFMA_F16(__builtin_bit_cast(f16x8, w0[f]), __builtin_bit_cast(f16x8, x1), acc[f]);
 #pragma unroll
       for (int f = 0; f < NF; ++f) acc[f] = MFMA_F16(__builtin_bit_cast(f16x8, w0[f]), __builtin_bit_cast(f16x8, x0), acc[f]);
-#ifndef EOSVOS_STREAM3X3_NOSB
       __builtin_amdgcn_sched_barrier(0);
-#endif
     }
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
@@ -1861,8 +1742,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_stream_kernel(const ConvArgs p
   if (p.amax_y) amax_block_commit8(ymax, p.amax_y);
 }
 static bool stream3x3_ok(const ConvArgs& a) {
-  static const int on = env_int("EOSVOS_TUNE_STREAM3X3", 1), min_m = env_int("EOSVOS_TUNE_STREAM3X3_MINM", 16384);
-  if (!on || conv_mfma_mode() != 2 || a.nseg > 0 || a.plane_rows || a.KH != 3 || a.KW != 3 || a.upshift || a.dst_up || a.par ||
+  constexpr int min_m = 16384;
+  if (conv_mfma_mode() != 2 || a.nseg > 0 || a.plane_rows || a.KH != 3 || a.KW != 3 || a.upshift || a.dst_up || a.par ||
       a.tprefix || a.mul != 1 || a.M < min_m)
     return false;
   if (a.Kc != 64 || a.N != 64 || a.wK != 64) return false;
@@ -1877,46 +1758,38 @@ static void launch_stream3x3(const ConvArgs& a, hipStream_t s) {
   constexpr int lds = 2 * NC * frag_pitch(9 * KC * 2) + (2 * NC + KC) * 4;
   static bool attr = false;
   if (!attr) { (void)hipFuncSetAttribute((const void*)conv3x3_stream_kernel<KC, NC, D>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; }
-  static const int wgs = env_int("EOSVOS_TUNE_STREAM3X3_WGS", 256);
-  hipLaunchKernelGGL((conv3x3_stream_kernel<KC, NC, D>), dim3(wgs), dim3(512), lds, s, a);
+  hipLaunchKernelGGL((conv3x3_stream_kernel<KC, NC, D>), dim3(256), dim3(512), lds, s, a);
 }
 // the launches the streaming kernel takes (f16x3 mode): 1x1, stride 1, K in {64, 128, 256}, whole column ranges, many pixels
 static int stream1x1_nc(const ConvArgs& a) {
   // pixels from which on: 16 384 at batch 3 (below: +-0 in the iteration), 1 024 at batch 1 (layer2's 6 420 and layer3 / 4's
   // 1 620 pixels: 4.68 -> 4.65 ms; batch 3 8.86 -> 8.88 with the same rule)
-  static const int on = env_int("EOSVOS_TUNE_STREAM1X1", 1), min_m_env = env_int("EOSVOS_TUNE_STREAM1X1_MINM", 0);
-  const int min_m = min_m_env > 0 ? min_m_env : (a.B == 1 && !a.plane_rows ? 1024 : 16384);
-  if (!on || conv_mfma_mode() != 2 || a.nseg > 0 || a.KH != 1 || a.KW != 1 || a.upshift || a.dst_up || a.par ||
+  const int min_m = a.B == 1 && !a.plane_rows ? 1024 : 16384;
+  if (conv_mfma_mode() != 2 || a.nseg > 0 || a.KH != 1 || a.KW != 1 || a.upshift || a.dst_up || a.par ||
       a.tprefix || a.mul != 1 || a.off0 != 0 || a.M < min_m)
     return 0;
   if (a.plane_rows) {
     // batched GEMMs of the Winograd-domain convs (decoder), K = 256: 128-channel column ranges (the rows are re-read by the
     // two ranges of a group from one XCD's L2), or the 48-channel tail of the 304-wide data gradient.  Measured at batch 3
     // (one stream): 139 -> 122 us forward, 149 / 153 -> 110 / 113 us data gradients, tail 64 -> 46 us; iteration 9.20 -> 9.07 ms.
-    // 64-channel ranges (EOSVOS_TUNE_STREAM1X1_PLANE_NC=64; they also take K = 304 in the 320 variant) are slower than the
-    // tiled kernel: 4 x 36 workgroups per row chunk leave either 56 % of the CUs busy or a second round (195 / 232 us).
-    static const int planes_on = env_int("EOSVOS_TUNE_STREAM1X1_PLANES", 1);
-    if (!planes_on || a.mask || a.mask8 || a.res || a.accum || a.scale || a.bias || a.relu || a.kscale || a.amax_y) return 0;
+    // 64-channel ranges (measured with an A/B switch since removed; they also take K = 304 in the 320 variant) are slower than
+    // the tiled kernel: 4 x 36 workgroups per row chunk leave either 56 % of the CUs busy or a second round (195 / 232 us).
+    if (a.mask || a.mask8 || a.res || a.accum || a.scale || a.bias || a.relu || a.kscale || a.amax_y) return 0;
     if ((a.ldx & 3) || (a.ldy & 3) || (a.plane_rows & 15)) return 0;
     if (a.Kc != 256 && !(a.Kc == 304 && !a.kmajor)) return 0;
-    static const int plane_nc = env_int("EOSVOS_TUNE_STREAM1X1_PLANE_NC", 128), k304 = env_int("EOSVOS_TUNE_STREAM1X1_K304", 1);
-    if (a.Kc == 304 && !k304) return 0;
-    if (plane_nc == 128 && a.N % 128 == 0) return 128;
+    if (a.N % 128 == 0) return 128;
     if (a.N % 64 == 0) return 64;
     if (a.N == 48 && a.Kc == 256) return 48;
     return 0;
   }
-  static const int k512 = env_int("EOSVOS_TUNE_STREAM1X1_K512", 1), n48 = env_int("EOSVOS_TUNE_STREAM1X1_N48", 1);
-  if (a.Kc != 64 && a.Kc != 128 && a.Kc != 256 && !(a.Kc == 512 && k512)) return 0;
+  if (a.Kc != 64 && a.Kc != 128 && a.Kc != 256 && a.Kc != 512) return 0;
   if (a.mask && !a.mask8) return 0;                   // (the fp32-mask form stays with the tiled kernel)
   if ((a.mask_c0 & 15) || (a.ldx & 3) || (a.ldy & 3) || (a.N & 15)) return 0;
   if (a.Hi != a.Ho || a.Wi != a.Wo) return 0;
-  static const int nc256 = env_int("EOSVOS_TUNE_STREAM1X1_NC256", 0);     // experiment: whole 256-channel rows per workgroup
   if (a.Kc == 512) return a.N % 64 == 0 && a.N <= 128 ? 64 : 0;     // (weights of 64 channels x 512: 133 KB of LDS)
-  if (nc256 && a.N % 256 == 0 && a.Kc <= 128) return 256;
   if (a.N % 128 == 0) return 128;
   if (a.N == 64) return 64;
-  if (a.N == 48 && n48 && a.Kc == 256) return 48;
+  if (a.N == 48 && a.Kc == 256) return 48;
   return 0;
 }
 template <int K, int NC>
@@ -1926,7 +1799,7 @@ static void launch_stream1x1(ConvArgs& a, hipStream_t s) {
   if (!attr) { (void)hipFuncSetAttribute((const void*)conv1x1_stream_kernel<K, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; }
   if (a.plane_rows) {
     // groups = planes x row chunks, each with one workgroup per column range; about `target` workgroups in all
-    static const int target = env_int("EOSVOS_TUNE_STREAM1X1_PLANE_WGS", 216);      // measured: 144 / 216 / 256
+    constexpr int target = 216;      // measured: 144 / 216 / 256
     const int ranges = a.N / NC;
     int chunks = (target + a.nplanes * ranges - 1) / (a.nplanes * ranges);
     const int max_chunks = a.plane_rows / 128 > 0 ? a.plane_rows / 128 : 1;      // >= one strip per wave
@@ -1938,7 +1811,7 @@ static void launch_stream1x1(ConvArgs& a, hipStream_t s) {
   }
   // one workgroup per CU over all column ranges together (a workgroup's 8 waves take the strips of its range round-robin):
   // measured per shape with 128 / 256 / 512 / 1024 workgroups per range, 256 in all is the fastest or within 2 % of it
-  static const int total = env_int("EOSVOS_TUNE_STREAM1X1_WGS", 256 * (K <= 128 ? EOSVOS_STREAM_OCC : 1));
+  constexpr int total = 256 * (K <= 128 ? EOSVOS_STREAM_OCC : 1);
   const int ranges = a.N / NC;
   const int wgs = total / ranges > 0 ? total / ranges : 1;
   hipLaunchKernelGGL((conv1x1_stream_kernel<K, NC>), dim3(wgs, ranges), dim3(512), lds, s, a);
@@ -2489,10 +2362,6 @@ void launch_absmax_segments(const float* base, const long* dev_off, const int* d
 }
 
 // Matrix mode: 2 = f16x3 (default), 1 = bf16x6, 0 = fp32 MFMA; EOSVOS_MFMA=f16x3|bf16x6|f32 picks the initial one
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && v[0]) ? atoi(v) : dflt;
-}
 static int g_mfma_mode = -1;
 static thread_local int tl_mfma_mode = -1;          // an engine with a mode of its own, for the duration of one C-ABI call
 void conv_set_thread_mfma_mode(int mode) { tl_mfma_mode = mode < 0 ? -1 : (mode == 2 ? 2 : (mode ? 1 : 0)); }
@@ -2611,12 +2480,12 @@ int conv_clamp_wg_budget(int n) {
   return n >= CONV_MAX_WG ? 0 : n;
 }
 static int conv_wg_budget(int requested) {
-  static const int env = conv_clamp_wg_budget(env_int("EOSVOS_TUNE_WG_BUDGET", 0));
-  const int b = requested > 0 ? conv_clamp_wg_budget(requested) : env;
+  const int b = conv_clamp_wg_budget(requested);
   return b > 0 ? b : CONV_MAX_WG;
 }
 int conv_wg_budget_of(int requested) { return conv_wg_budget(requested); }
 #define CONV_MAX_WG_DEEP (256 * 3)
+#define EOSVOS_MINK 3      // K steps a streamed workgroup takes at least
 // (1024: the pre-split 256 x 256 kernel parks up to 1024 partial 128 x 128 tiles, launch_conv_p)
 int64_t conv_ws_floats() { return (int64_t)(CONV_MAX_WG_DEEP > 1024 ? CONV_MAX_WG_DEEP : 1024) * 2 * 128 * 128; }
 // the fix-up pass of a uniform split-K launch whose partial tiles another kernel parked (presplit_kernels.hip): a.splitk chunks
@@ -2636,22 +2505,15 @@ int conv_plan(ConvArgs& a) {
   long ksteps = (long)T * ((a.Kc + EOSVOS_BK - 1) / EOSVOS_BK);
   const long tiles = (long)((a.M + 127) / 128) * ((a.N + bn - 1) / bn);
   const bool x6 = conv_mfma_mode() >= 1;
-#ifndef EOSVOS_NO_DEEP
-  // 3-workgroups-per-CU kernel for long-K layers with many tiles (measured: decoder 3x3 fwd/dgrad at batch >= 2)
-#ifndef EOSVOS_DEEP_BATCHED
-#define EOSVOS_DEEP_BATCHED 2      // 0: never, 1: batched GEMMs with K % 32 != 0 use the K-step-16 variant, 2: all batched GEMMs
-#endif
-  const bool batched_deep = a.plane_rows != 0 && (EOSVOS_DEEP_BATCHED == 2 || (EOSVOS_DEEP_BATCHED == 1 && (a.Kc & 31)));
+  // 3-workgroups-per-CU kernel for long-K layers with many tiles (measured: decoder 3x3 fwd/dgrad at batch >= 2); all
+  // batched GEMMs take the K-step-16 variant
+  const bool batched_deep = a.plane_rows != 0;
   const bool deep_ok = ksteps >= 64 || batched_deep;
   a.deep = (!x6 && bn == 128 && tiles >= EOSVOS_DEEP_TILES && deep_ok && a.total_units <= 0)
                ? (((a.Kc & 31) || batched_deep) ? 2 : 1) : 0;
-#else
-  a.deep = 0;
-#endif
   if (a.deep == 2) ksteps = (long)T * ((a.Kc + EOSVOS_BK_DEEP - 1) / EOSVOS_BK_DEEP);
   long nwg = a.deep ? CONV_MAX_WG_DEEP : conv_wg_budget(a.wg_budget), q = 0, per = 0;
-  static const int tap_whole = env_int("EOSVOS_TUNE_TAP_WHOLE", 1);
-  if (tap_whole && x6 && a.total_units > 0 && a.torder && tiles >= nwg && ksteps * EOSVOS_BK <= 1536) {
+  if (x6 && a.total_units > 0 && a.torder && tiles >= nwg && ksteps * EOSVOS_BK <= 1536) {
     // uneven tiles (tap table), at least one per workgroup: whole tiles, longest first, no parked partial tiles and no
     // fix-up pass (the stride-2 3x3 data gradient at batch 3: 602 tiles of 4 / 8 / 8 / 16 K steps; streamed, nearly every
     // workgroup parked two slabs: 70 + 20 us).  Short K only: the 608-tile, K = 2304 data gradients of the dilated ASPP convs
@@ -2662,41 +2524,31 @@ int conv_plan(ConvArgs& a) {
     const long rem = tiles - q * nwg;
     // a leftover that nearly fills another round: whole tiles for it too (q + 1 per workgroup, fewer workgroups) -- the
     // streamed form parks two slabs per workgroup and needs the fix-up pass (batch-1 decoder: 936 tiles = 512 + 424 streamed,
-    // fix-up 17 us; as 468 workgroups x 2 whole tiles none)
-    static const int rem_whole = env_int("EOSVOS_TUNE_REM_WHOLE", 1);      // percent of the budget from which on; 0 = never
-    if (rem > 0 && rem_whole > 0 && rem * 100 >= (long)rem_whole * nwg) {
+    // fix-up 17 us; as 468 workgroups x 2 whole tiles none); from 1 % of the budget on
+    if (rem > 0 && rem * 100 >= nwg) {
       q = q + 1; per = 0;
       nwg = (tiles + q - 1) / q;
     } else if (rem > 0) {
       per = (rem * ksteps + nwg - 1) / nwg;
-      if (per < 2) {                                   // tiny K: whole tiles only
-        // EOSVOS_TUNE_TINYK_ONE_TILE: one workgroup per tile (more workgroups than resident slots: the dispatcher refills a
-        // slot the moment a workgroup retires) instead of <= one resident round of workgroups walking several tiles each
-        static const int one = env_int("EOSVOS_TUNE_TINYK_ONE_TILE", 0);
+      if (per < 2) {                                   // tiny K: whole tiles only, <= one resident round of workgroups
         per = 0;
-        if (one) { q = 1; nwg = tiles; }
-        else { q = (tiles + nwg - 1) / nwg; nwg = (tiles + q - 1) / q; }
+        q = (tiles + nwg - 1) / nwg; nwg = (tiles + q - 1) / q;
       }
     }
   } else {
     const long U = a.total_units > 0 ? a.total_units : tiles * ksteps;
-#ifndef EOSVOS_MINK
-#define EOSVOS_MINK 3
-#endif
     // short K, or at least one tile per CU and a K so short that the fix-up pass (a second launch, >= 10 us)
     // costs more than the idle second slot of some CUs: one whole tile per workgroup
     // (f16x3 mode, where a K step costs less against the fix-up pass: from a quarter of the budget in tiles and up to K = 512
     // -- batch 1 5.23 -> 5.12 ms, batch 3 9.89 -> 9.79; tools/budget_sweep.py showed layer3's 208-tile K = 256 launches at 22 us
     // streamed against 16 us as whole tiles)
-    static const int dps_div_env = env_int("EOSVOS_TUNE_DPSMALL_DIV", 0), dps_k_env = env_int("EOSVOS_TUNE_DPSMALL_K", 0);
-    const int dps_div = dps_div_env > 0 ? dps_div_env : (conv_mfma_mode() == 2 ? 4 : 2);
-    const int dps_k = dps_k_env > 0 ? dps_k_env : (conv_mfma_mode() == 2 ? 512 : 256);
+    const int dps_div = conv_mfma_mode() == 2 ? 4 : 2;
+    const int dps_k = conv_mfma_mode() == 2 ? 512 : 256;
     const bool dp_small = tiles >= conv_wg_budget(a.wg_budget) / dps_div && ksteps * EOSVOS_BK <= dps_k;
     if ((ksteps <= EOSVOS_MINK + 1 || dp_small) && a.total_units <= 0) {
       per = ksteps; nwg = tiles;                       // no fix-up
     } else {
-      static const int mink = env_int("EOSVOS_TUNE_MINK", EOSVOS_MINK);
-      if (U / nwg < mink) nwg = U / mink > 0 ? U / mink : 1;   // >= MINK K-steps per workgroup
+      if (U / nwg < EOSVOS_MINK) nwg = U / EOSVOS_MINK > 0 ? U / EOSVOS_MINK : 1;   // >= MINK K-steps per workgroup
       per = (U + nwg - 1) / nwg;
       nwg = (U + per - 1) / per;
     }
@@ -2709,22 +2561,14 @@ int conv_plan(ConvArgs& a) {
     // Measured per launch (tools/layer_times.py, batch 3, one stream): the 3x3 convs of layer2 / layer3 - 7...10 %, layer4's
     // K = 2048 1x1 convs - 5...10 %, the d = 6 ASPP conv 187 -> 140 us; tap-table launches whose tiles keep very different
     // numbers of taps (d = 18: 100 -> 135 us) stay with stream-K, which balances them exactly.
-    static const int on = env_int("EOSVOS_TUNE_SPLITK", 1), min_avg = env_int("EOSVOS_TUNE_SPLITK_MINK", 16);
-    static const int min_chunk = env_int("EOSVOS_TUNE_SPLITK_MINCHUNK", 12), min_fill = env_int("EOSVOS_TUNE_SPLITK_MINFILL", 60);      // (85 in round 3; re-measured in round 4: batch 1 4.50 -> 4.46 ms, batch 3 +-0)
+    constexpr long min_avg = 16, min_chunk = 12, min_fill = 60;      // (fill: 85 in round 3; re-measured in round 4: batch 1 4.50 -> 4.46 ms, batch 3 +-0)
     const bool even_taps = a.total_units <= 0 || a.total_units * 100 >= 85L * tiles * ksteps;
     const long budget = conv_wg_budget(a.wg_budget);
     const long avg = a.total_units > 0 ? a.total_units / tiles : ksteps;
     const long S = tiles > 0 ? budget / tiles : 0;
-    if (on && conv_mfma_mode() == 2 && !a.deep && even_taps && q == 0 && per > 0 && per < avg && S >= 2 && avg >= min_avg && avg / S >= min_chunk &&
-        tiles * S * 100 >= (long)min_fill * budget) {
+    if (conv_mfma_mode() == 2 && !a.deep && even_taps && q == 0 && per > 0 && per < avg && S >= 2 && avg >= min_avg && avg / S >= min_chunk &&
+        tiles * S * 100 >= min_fill * budget) {
       a.splitk = (int)S; nwg = tiles * S; per = 0;
-    } else {
-      // experiment: one whole tile per workgroup (no slabs, no fix-up) when the tiles alone fill s1_fill % of the budget
-      static const int s1_fill = env_int("EOSVOS_TUNE_SPLITK_S1_FILL", 0);
-      if (s1_fill > 0 && on && conv_mfma_mode() == 2 && !a.deep && a.total_units <= 0 && q == 0 && per > 0 && per < avg && S == 1 &&
-          tiles * 100 >= (long)s1_fill * budget) {
-        per = ksteps; nwg = tiles;
-      }
     }
   }
   a.dp_q = (int)q; a.per = (int)per; a.nwg = (int)nwg;
@@ -2741,10 +2585,7 @@ void launch_conv(ConvArgs& a, hipStream_t s) {
   if (const int nc = stream1x1_nc(a)) {               // short-K 1x1 convs on the large maps: the streaming kernel
     a.dp_q = 0; a.per = 0; a.nwg = 0; a.splitk = 0;
     ProfScope ps(nc >= 128 ? 35 : 36, 2.0 * a.M * a.N * a.Kc, s);
-    if (nc == 256) {
-      if (a.Kc == 64) launch_stream1x1<64, 256>(a, s);
-      else launch_stream1x1<128, 256>(a, s);
-    } else if (nc == 128) {
+    if (nc == 128) {
       if (a.Kc == 64) launch_stream1x1<64, 128>(a, s);
       else if (a.Kc == 128) launch_stream1x1<128, 128>(a, s);
       else if (a.Kc == 304) launch_stream1x1<304, 128>(a, s);
@@ -2819,12 +2660,8 @@ void launch_conv(ConvArgs& a, hipStream_t s) {
 // so tiles are staged as [pixel][channel] rows and fragments are read with ds_read_b32
 // (consecutive lanes -> consecutive channels: conflict free).
 // ---------------------------------------------------------------------------------------
-#ifndef EOSVOS_WG_BKP
 #define EOSVOS_WG_BKP 32
-#endif
-#ifndef EOSVOS_WG_OCC
 #define EOSVOS_WG_OCC 2
-#endif
 template <int BMO, int BNI>
 __global__ __launch_bounds__(256, EOSVOS_WG_OCC) void wgrad_kernel(const WgradArgs p) {
   constexpr int BKP = EOSVOS_WG_BKP;
@@ -2986,17 +2823,14 @@ static int wg_tile(int c) {
   const int padded = (c + 127) / 128 * 128;
   return (padded - c) * 100 > 15 * c ? 64 : 128;
 }
-#ifndef EOSVOS_WG_SMALLP
 #define EOSVOS_WG_SMALLP 2500        // pixel count below which 64x64 tiles are used (more tiles, fewer K splits)
-#endif
 // few pixels AND few tiles (stride-16 layers at batch 1): 64x64 tiles give more tiles and fewer K splits
 // (f16x3 mode: never -- with the faster K loop the 64x64 tiles' extra operand staging costs more than their fewer K
 // splits save: batch 1 5.31 -> 5.23 ms without them, batch 3 unchanged)
 static bool wg_small(int P, int Cout, int Cin, int T, int mode = -1) {
   const int t128 = ((Cout + wg_tile(Cout) - 1) / wg_tile(Cout)) * ((Cin + wg_tile(Cin) - 1) / wg_tile(Cin)) * T;
-  static const int smallp_env = env_int("EOSVOS_TUNE_WG_SMALLP", -1), smallt = env_int("EOSVOS_TUNE_WG_SMALLT", 256);
-  const int smallp = smallp_env >= 0 ? smallp_env : ((mode < 0 ? conv_mfma_mode() : mode) == 2 ? 0 : EOSVOS_WG_SMALLP);
-  return P < smallp && t128 < (P < EOSVOS_WG_SMALLP ? 256 : smallt);
+  const int smallp = (mode < 0 ? conv_mfma_mode() : mode) == 2 ? 0 : EOSVOS_WG_SMALLP;
+  return P < smallp && t128 < 256;
 }
 int wgrad_pick_splits(int P, int Cout, int Cin, int T, int wg_budget, int mode) {
   const bool small = wg_small(P, Cout, Cin, T, mode);
@@ -3007,13 +2841,13 @@ int wgrad_pick_splits(int P, int Cout, int Cin, int T, int wg_budget, int mode) 
   const int RES = conv_wg_budget(wg_budget) * EOSVOS_WG_OCC / EOSVOS_OCC;
   int best = 1;
   double best_eff = 0.0;
-  static const int minsteps = env_int("EOSVOS_TUNE_WG_MINSTEPS", 384 / EOSVOS_WG_BKP);   // 12 steps = 384 pixels per split (round 4: batch 1 4.57 -> 4.54 ms, batch 3 +-0; 8 before; 4 / 6: batch 1 +1.3 ... 2 %)
+  constexpr int minsteps = 384 / EOSVOS_WG_BKP;   // 12 steps = 384 pixels per split (round 4: batch 1 4.57 -> 4.54 ms, batch 3 +-0; 8 before; 4 / 6: batch 1 +1.3 ... 2 %)
   // the first (= smallest) split count that fills its rounds to `eff_enough`: fewer splits park fewer slabs (each one a full
   // copy of the weight gradient that the update kernel reads back)
   // (round 5: 80 instead of 93 -- e.g. layer4 conv2 with 3 splits in one round instead of 7 in two, half the slab bytes -- is 0.5 %
   // faster at batch 3 (8.79 -> 8.75 ms), but the longer fp32 accumulation chains moved the fp32-MFMA mode's 240-iteration
   // trajectory (fixture G21) from 3.6e-4 to 1.04e-3 on the logits: not adopted, parity margin before half a percent)
-  static const double eff_enough = env_int("EOSVOS_TUNE_WG_EFF", 93) / 100.0;
+  constexpr double eff_enough = 93 / 100.0;
   for (int s = 1; s <= 512 && steps / s >= minsteps; ++s) {
     const long wgs = (long)tiles * s;
     const long rounds = (wgs + RES - 1) / RES;

@@ -184,9 +184,6 @@ struct eosvos_engine {
   int arch, H, W, maxB, dev;
   hipStream_t s;
   hipStream_t s2 = nullptr;            // side stream: weight-gradient kernels run beside the dgrad chain
-  hipStream_t s3 = nullptr;            // EOSVOS_TUNE_SIDE_STREAMS=2 (experiment): weight gradients alternate between s2 and s3
-  hipEvent_t ev_s3 = nullptr;
-  unsigned wg_rr = 0;
   std::vector<hipEvent_t> ev;          // one fork event per conv + a join event
   bool side_used = false;
   std::vector<std::function<void()>> side_q;   // weight-gradient launches waiting for the next fork (see side_flush)
@@ -296,7 +293,6 @@ struct eosvos_engine {
   std::map<long, std::vector<std::pair<int, int>>> wgp_splits;    // (stage, batch, budget) -> (K chunks, workgroups per tile) of every eligible conv of the stage (fixed membership)
   struct WgPPending { int ci; WgradPArgs a; WgradArgs legacy; bool covered; };
   std::vector<WgPPending> wgp_pending;
-  std::vector<int> wgp_forced;
   // launch-plan fingerprint (eosvos_plan_fingerprint): FNV-1a over (kind, conv, M, N, K, workgroups / K splits) of every matrix
   // launch of the last forward [0] / backward [1] and the slab counts the update consumed -- the split plan fixes the fp32
   // summation order, i.e. which rounding a long trajectory accumulates (tests/test_gpu_plan_fingerprint.py)
@@ -442,8 +438,7 @@ void pair_reset(eosvos_engine* e);
 // a kernel with the fused absmax is about to write the tensor at `key` (full = every element): returns the slot to pass
 unsigned* twrite_fused(eosvos_engine* e, int phase, const float* key, bool full) {
   pair_uncover(e, phase, key);
-  static const bool off = getenv("EOSVOS_TUNE_NO_FUSED_AMAX") != nullptr;      // A/B: every consumer runs its own absmax pass
-  if (off || !h3_mode() || amax_init(e)) return nullptr;
+  if (!h3_mode() || amax_init(e)) return nullptr;
   unsigned* sl = tslot(e, phase, key);
   if (sl && full) e->treg[phase][key].valid = true;
   return sl;
@@ -570,11 +565,7 @@ int upload_resize(eosvos_engine* e, const HostResize& h, int in, int out, Resize
 void attach_tap_table(eosvos_engine* e, int ci, int kind, int B, ConvArgs& a) {
   const ConvL& c = e->t.convs[ci];
   const bool dilated = c.k == 3 && c.dil >= 2 && a.upshift == 0;
-#ifdef EOSVOS_NO_PARITY            // A/B switch (tools/build_variant.sh)
-  const bool s2_dgrad = false;
-#else
   const bool s2_dgrad = c.k == 3 && kind == 1 && a.upshift == 1 && !a.dst_up;    // 2.25 of 9 taps per pixel on average
-#endif
   if (!dilated && !s2_dgrad) return;
   const int bn = conv_bn(a);
   const long tiles = (long)((a.M + 127) / 128) * ((a.N + bn - 1) / bn);
@@ -644,23 +635,13 @@ void trace(const char* kind, int ci, long M, long N, long K, int splits, double 
 struct WinoGeom { int th, tw, d, tm, np; long ntile, prow; };
 // F(4x4,3x3) (36 positions, 2.25 MACs per output) for undilated convs on maps of >= 64 x 64 outputs -- the decoder --
 // where 4x4 tiles waste little at the border; F(2x2,3x3) (16 positions, 4 MACs per output) otherwise.
-#ifndef EOSVOS_WINO_F4_MINDIM
 #define EOSVOS_WINO_F4_MINDIM 64
-#endif
-#ifndef EOSVOS_WINO_F4_DIL
-#define EOSVOS_WINO_F4_DIL 1
-#endif
 bool wino_f4(const eosvos_engine* e, const ConvL& c, int Ho, int Wo) {
-#ifdef EOSVOS_NO_WINO_F4
-  (void)e; (void)c; (void)Ho; (void)Wo;
-  return false;
-#else
   if (e->force_algo == EOSVOS_ALGO_WINO_F2) return false;
   if (e->force_algo == EOSVOS_ALGO_WINO_F4) return true;
-  // large undilated maps (the decoder), or -- EOSVOS_WINO_F4_DIL -- dilated convs whose sub-grids tile well with 4x4
+  // large undilated maps (the decoder), or dilated convs whose sub-grids tile well with 4x4
   if (c.dil == 1) return Ho >= EOSVOS_WINO_F4_MINDIM && Wo >= EOSVOS_WINO_F4_MINDIM;
-  return EOSVOS_WINO_F4_DIL && (c.dil == 2 || c.dil == 4 || c.dil == 8);
-#endif
+  return c.dil == 2 || c.dil == 4 || c.dil == 8;
 }
 WinoGeom wino_geom(const eosvos_engine* e, const ConvL& c, int B, int Ho, int Wo) {
   WinoGeom g;
@@ -673,17 +654,11 @@ WinoGeom wino_geom(const eosvos_engine* e, const ConvL& c, int B, int Ho, int Wo
   g.prow = (g.ntile + 127) / 128 * 128;                  // plane rows padded to the GEMM tile
   return g;
 }
-#ifndef EOSVOS_WINO_MINWORK
 #define EOSVOS_WINO_MINWORK 100000000LL                // measured: layer4 conv2 and the d = 6 ASPP conv gain, layer2/3 conv2 do not
-#endif
 bool wino_shape(const ConvL& c) {
   return c.k == 3 && c.stride == 1 && c.pad == c.dil && c.dil >= 1 && c.dil <= 8 && (c.cin & 3) == 0 && (c.cout & 3) == 0;
 }
 bool wino_on(const eosvos_engine* e, int ci, int B, int Ho, int Wo) {
-#ifdef EOSVOS_NO_WINO
-  (void)e; (void)ci; (void)B; (void)Ho; (void)Wo;
-  return false;
-#else
   const ConvL& c = e->t.convs[ci];
   if (e->force_algo == EOSVOS_ALGO_DIRECT) return false;
   if (!wino_shape(c)) return false;
@@ -694,7 +669,6 @@ bool wino_on(const eosvos_engine* e, int ci, int B, int Ho, int Wo) {
   // conv no longer gain (same box, batch 1: 5.62 -> 5.45 ms without them, batch 3: 9.97 -> 9.93); the decoder keeps its F(4,3)
   if (conv_mfma_mode() == 2) return false;
   return (long long)B * Ho * Wo / 4 * c.cin * c.cout >= EOSVOS_WINO_MINWORK;      // MACs of one F(2,3) position
-#endif
 }
 // The batched GEMM of a Winograd forward: rows = 16 planes x prow tiles of V, weights U[p] per plane -> M planes
 ConvArgs wino_fwd_gemm(eosvos_engine* e, int ci, const WinoGeom& wg, float* ws) {
@@ -912,9 +886,7 @@ void conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int 
 // backward pass, so it can start a few layers late.
 // Measured: at batch 1 (launch-bound layers) forking every 4 layers gains 1.8 %; at batch 3 the later start of the
 // weight gradients costs more than the bubbles (+1.7 %), so there every layer forks at once.
-#ifndef EOSVOS_SIDE_BATCH
 #define EOSVOS_SIDE_BATCH 4
-#endif
 // ---- pre-split operand path ---------------------------------------------------------------------------------------------
 // Weight gradients whose channel counts are multiples of 256 (layer3, layer4, ASPP) run on wgrad_p_kernel (presplit_kernels.hip)
 // in the f16x3 mode: 1.3-1.7x the register-staged kernel per launch (profiles/r06_wgrad_p_probe.txt).  EOSVOS_PRESPLIT=0: off.
@@ -929,13 +901,12 @@ bool presplit_switch() {
 // block each other -- measured end to end on a two-object 70-frame sequence with the objects in flight
 // (profiles/r06_eval_sequence_time.txt): e-OSVOS-50 0.505 -> 0.617 s per object with the path, e-OSVOS-100-OnA 1.85 -> 1.95.
 bool presplit_enabled(const eosvos_engine* e) {
-  return presplit_switch() && h3_mode() && e->force_algo == 0 && !e->s3 && (e->s2 || e->presplit_inflight);
+  return presplit_switch() && h3_mode() && e->force_algo == 0 && (e->s2 || e->presplit_inflight);
 }
 bool presplit_wgrad_shape(const ConvL& c, int P, int ldg, int ldx) {
   // (minimum pixel count: at batch 1 -- 1620 pixels on the stride-16 map, 50 K steps for 256 x 256 tiles -- the path is 4 % slower
   // than the register-staged kernels, profiles/r06_ab_log.txt; batch 3 = 4860 pixels)
-  static const int minp_env = getenv("EOSVOS_TUNE_PRESPLIT_MINP") ? atoi(getenv("EOSVOS_TUNE_PRESPLIT_MINP")) : 4000;
-  const int minp = g_presplit == 2 ? 1 : minp_env;          // eosvos_set_presplit(2): every eligible shape (tests on small maps)
+  const int minp = g_presplit == 2 ? 1 : 4000;          // eosvos_set_presplit(2): every eligible shape (tests on small maps)
   // (stride 1 only: the inputs of the strided convs are the large maps of the previous stage, whose producers -- the streaming
   // kernels -- write no siblings: a split pass over 40-80 MB per step costs more than the kernel gains)
   return c.cout % 256 == 0 && c.cin % 256 == 0 && c.stride == 1 && ldg % 8 == 0 && ldx % 8 == 0 && P >= minp;
@@ -973,8 +944,7 @@ void pair_uncover(eosvos_engine* e, int phase, const float* key) {
 // conv epilogue / fix-up about to write the whole tensor at `key` through the view y: hand it the sibling if one is wanted
 void pair_attach(eosvos_engine* e, int phase, const float* key, const float* y, bool full, ConvArgs& a) {
   a.y2 = nullptr; a.y2_sc = nullptr; a.y2_done = 0;
-  static const bool noattach = getenv("EOSVOS_TUNE_PRESPLIT_NOATTACH") != nullptr;     // A/B: the pre-split PLAN on the register-staged kernels
-  if (noattach || !presplit_enabled(e) || e->gn() || !full || a.dst_up || a.par || a.plane_rows) return;
+  if (!presplit_enabled(e) || e->gn() || !full || a.dst_up || a.par || a.plane_rows) return;
   if (phase == 0 && !e->fwd_masks) return;                  // inference forward: no backward pass will read it
   auto it = e->pairs[phase].find(key);
   if (it == e->pairs[phase].end() || !it->second.want || it->second.fresh || !it->second.p || (a.ldy & 7) || (a.N & 7)) return;
@@ -1005,26 +975,10 @@ void pair_reset(eosvos_engine* e) {
 // covers too few runs long after the chain has ended.  Measured at batch 3, three interleaved rounds (profiles/r06_ab_log.txt):
 // 100 % 8.89 ms, 88 % 8.75, 75 % 8.67, 63 % 8.65, 50 % 8.75, 25 % 9.37; the register-staged kernels 8.83.
 int wgp_budget(const eosvos_engine* e, int ci, int B) {
-  static const int share = getenv("EOSVOS_TUNE_WGRAD_P_SIDE_SHARE") ? atoi(getenv("EOSVOS_TUNE_WGRAD_P_SIDE_SHARE")) : 75;
+  constexpr int share = 75;          // percent
   int b = conv_wg_budget_of(e->budget_for(ci, 2, B));
   if (e->s2) b = conv_clamp_wg_budget(std::max(64, b * share / 100 / 64 * 64));
   return b;
-}
-// EOSVOS_TUNE_PRESPLIT_LEGACY_SPLITS=1 (A/B, off by default): the K chunks of the pre-split weight gradients follow the
-// register-staged plan (a multiple of the workgroups per tile, at least that plan's count) instead of one chunk per workgroup.
-// Measured (profiles/r06_ab_log.txt item 8): 9.08 ms against 8.85 -- more slabs, and a workgroup that walks several chunks
-// restarts its DMA pipeline at every boundary -- with no effect on the drift of the full-length fixtures.
-bool presplit_legacy_splits() {
-  static const bool on = getenv("EOSVOS_TUNE_PRESPLIT_LEGACY_SPLITS") && atoi(getenv("EOSVOS_TUNE_PRESPLIT_LEGACY_SPLITS")) == 1;
-  return on;
-}
-// K chunks of a pre-split weight gradient whose tiles are shared by `groups` workgroups: a multiple of `groups` (every workgroup
-// walks the same number of chunks) that is at least the register-staged plan's count `sl` -- no chain of fp32 sums gets longer
-// than it was -- with at least 4 K steps per chunk
-int presplit_chunks(int sl, int groups, int steps) {
-  int m = (sl + groups - 1) / groups;
-  while (m > 1 && steps / (groups * m) < 4) --m;
-  return groups * std::max(1, m);
 }
 int pair_margin(int phase) {
   static const int margin_x = getenv("EOSVOS_TUNE_PAIR_MARGIN_X") ? atoi(getenv("EOSVOS_TUNE_PAIR_MARGIN_X")) : 2;
@@ -1046,7 +1000,6 @@ void side_flush(eosvos_engine* e) {
   if (e->side_q.empty()) return;
   (void)hipEventRecord(e->ev[0], e->s);            // everything the queued launches read is complete here
   (void)hipStreamWaitEvent(e->s2, e->ev[0], 0);
-  if (e->s3) (void)hipStreamWaitEvent(e->s3, e->ev[0], 0);
   for (auto& f : e->side_q) f();
   e->side_q.clear();
   e->side_used = true;
@@ -1083,9 +1036,7 @@ std::vector<int> plan_wgrad_splits(const std::vector<WgGroupItem>& items, int wg
         }
         return n;
       };
-      static const int rounds = getenv("EOSVOS_TUNE_WGRAD_GROUP_ROUNDS") ? atoi(getenv("EOSVOS_TUNE_WGRAD_GROUP_ROUNDS")) : 1;
-      if (rounds > 1) tau = std::max<long>(4, tau / rounds);
-      while (count(tau) > (long)RES * rounds && tau < (1L << 20)) tau += std::max<long>(1, tau / 32);
+      while (count(tau) > (long)RES && tau < (1L << 20)) tau += std::max<long>(1, tau / 32);
       for (size_t k = 0; k < items.size(); ++k) {
         const auto& it = items[k];
         if (wgrad_group_tile(it.cout) != bm || wgrad_group_tile(it.cin) != bn) continue;
@@ -1098,7 +1049,6 @@ std::vector<int> plan_wgrad_splits(const std::vector<WgGroupItem>& items, int wg
   return splits;
 }
 bool wgrad_groupable(const eosvos_engine* e, int ci, int B) {
-  static const bool off = getenv("EOSVOS_NO_WGRAD_GROUP") != nullptr;
   // Measured at batch 3 (profiles/r03_ab_wgrad_group.txt): grouping layer3 (30 / 14 splits per conv -> 2, 578 -> 57 MB of
   // slabs) leaves the two-stream step time unchanged; grouping layer2 / layer1 as well makes it 1 % LONGER although the
   // summed kernel time drops by 0.3 ms -- their grouped launches start only after the stage's data-gradient chain and
@@ -1107,9 +1057,8 @@ bool wgrad_groupable(const eosvos_engine* e, int ci, int B) {
   // 8.82 ms; with layer1 as well 8.91), every stage at batch 1 (4.65 -> 4.60 ms; layer2 + layer3 4.62).
   // An engine WITHOUT a side stream (it runs beside other engines, eosvos_set_side_stream) has no such overlap to lose:
   // every stage is grouped (4 tasks in flight at batch 1: 41.0 -> 41.9 meta-tasks/s).
-  static const int env_stage = getenv("EOSVOS_TUNE_WGRAD_GROUP_MINSTAGE") ? atoi(getenv("EOSVOS_TUNE_WGRAD_GROUP_MINSTAGE")) : -1;
-  const int min_stage = env_stage >= 0 ? env_stage : (e->s2 ? (B == 1 ? 0 : 1) : 0);
-  return !off && e->wg_group_on && conv_mfma_mode() >= 1 && e->force_algo == 0 && ci < (int)e->t.stage.size() &&
+  const int min_stage = e->s2 && B != 1 ? 1 : 0;
+  return e->wg_group_on && conv_mfma_mode() >= 1 && e->force_algo == 0 && ci < (int)e->t.stage.size() &&
          e->t.stage[ci] >= min_stage && e->t.stage[ci] <= 2 && !e->conv_hin.empty();
 }
 // Launch the queued weight gradients (all of one stage) -- on the side stream when there is one.
@@ -1137,10 +1086,7 @@ int flush_wgrad_p_group(eosvos_engine* e, int stage, int B) {
     std::vector<std::pair<int, int>> v;
     for (size_t k = 0; k < e->wgp_pending.size(); ++k) {
       const int g = splits_of(e->wgp_pending[k].a, tau);
-      // workgroups per tile: this plan's; chunks: a multiple of them, at least the register-staged plan's count (conv_wgrad)
-      const WgradPArgs& qa = e->wgp_pending[k].a;
-      if (e->wgp_forced.size() == e->wgp_pending.size()) v.push_back({presplit_chunks(e->wgp_forced[k], g, (qa.B * qa.Ho * qa.Wo + 31) / 32), g});
-      else v.push_back({g, g});
+      v.push_back({g, g});                            // one K chunk per workgroup
     }
     sp = e->wgp_splits.emplace(key, v).first;
   }
@@ -1207,19 +1153,6 @@ int flush_wgrad_p_group(eosvos_engine* e, int stage, int B) {
   return 0;
 }
 int flush_wgrad_group(eosvos_engine* e, int stage, int B) {
-  // The register-staged plan over the WHOLE stage (pre-split members included): with EOSVOS_TUNE_PRESPLIT_LEGACY_SPLITS (default)
-  // every conv keeps the K splits it has without the pre-split path, whichever kernel runs it
-  std::vector<int> full_splits;
-  const size_t n_legacy = e->wg_pending.size();
-  if (presplit_legacy_splits() && !e->wgp_pending.empty()) {
-    std::vector<WgGroupItem> full;
-    for (auto& pa : e->wg_pending) full.push_back({pa.first, pa.second.B * pa.second.Ho * pa.second.Wo, pa.second.Cout, pa.second.Cin, pa.second.KH * pa.second.KW});
-    for (auto& q : e->wgp_pending) full.push_back({q.ci, q.a.B * q.a.Ho * q.a.Wo, q.a.Cout, q.a.Cin, q.a.KH * q.a.KW});
-    full_splits = plan_wgrad_splits(full, e->wg_budget);
-    e->wgp_forced.assign(full_splits.begin() + n_legacy, full_splits.end());
-  } else {
-    e->wgp_forced.clear();
-  }
   if (int rc = flush_wgrad_p_group(e, stage, B)) return rc;
   if (e->wg_pending.empty()) { if (e->s2) side_flush(e); return 0; }
   const long key = ((long)stage * 64 + B) * 1024 + e->wg_budget;
@@ -1231,9 +1164,7 @@ int flush_wgrad_group(eosvos_engine* e, int stage, int B) {
       items.push_back({pa.first, a.B * a.Ho * a.Wo, a.Cout, a.Cin, a.KH * a.KW});
     }
     eosvos_engine::WgGroupPlan plan;
-    static const int gb_env = getenv("EOSVOS_TUNE_WGRAD_GROUP_BUDGET") ? atoi(getenv("EOSVOS_TUNE_WGRAD_GROUP_BUDGET")) : 0;     // A/B: the grouped launches' workgroup budget beside the data-gradient chain
-    const int gbud = (gb_env > 0 && e->s2 && e->wg_budget == 0) ? conv_clamp_wg_budget(gb_env) : e->wg_budget;
-    plan.splits = full_splits.empty() ? plan_wgrad_splits(items, gbud) : std::vector<int>(full_splits.begin(), full_splits.begin() + n_legacy);
+    plan.splits = plan_wgrad_splits(items, e->wg_budget);
     for (int bm : {128, 64})
       for (int bn : {128, 64}) {
         std::vector<WgradArgs> tab;
@@ -1321,8 +1252,7 @@ int conv_wgrad(eosvos_engine* e, int ci, const float* g, int ldg, const float* x
     // the 16 / 36 planes already give hundreds of tiles, and every K split parks a full Winograd-domain slab that the finish
     // kernel re-reads: plan the splits for half the workgroup budget (tools/budget_sweep.py: decoder conv at batch 3 247 -> 198 us,
     // batch 1 90 -> 72 us)
-    static const bool wino_half = getenv("EOSVOS_TUNE_WINO_WGRAD_FULL_BUDGET") == nullptr;
-    const int wbud = wino_half ? conv_wg_budget_of(e->budget_for(ci, 2, B)) / 2 : e->budget_for(ci, 2, B);
+    const int wbud = conv_wg_budget_of(e->budget_for(ci, 2, B)) / 2;
     a.splits = wgrad_pick_splits((int)ntile, c.cout, c.cin, wg.np, wbud);
     trace("wgrad", ci, c.cout, (long)c.cin * wg.np, ntile, a.splits);
     const int cin = c.cin, cout = c.cout;
@@ -1363,12 +1293,7 @@ int conv_wgrad(eosvos_engine* e, int ci, const float* g, int ldg, const float* x
     }
     // pre-split operand path: 256 x 256 tiles on the pair8 siblings of g and x when this iteration's producers wrote both;
     // otherwise the register-staged kernel with the same K splits, which leaves the scales for the next iteration's producers
-    static const bool p_nogroup = getenv("EOSVOS_TUNE_PRESPLIT_NO_GROUP") && atoi(getenv("EOSVOS_TUNE_PRESPLIT_NO_GROUP")) == 1;
-    static const int p_maxcout = getenv("EOSVOS_TUNE_PRESPLIT_MAXCOUT") ? atoi(getenv("EOSVOS_TUNE_PRESPLIT_MAXCOUT")) : 1 << 30;
-    static const int p_mink = getenv("EOSVOS_TUNE_PRESPLIT_MINTAPS") ? atoi(getenv("EOSVOS_TUNE_PRESPLIT_MINTAPS")) : 1;
-    static const long p_maxn = getenv("EOSVOS_TUNE_PRESPLIT_MAXN") ? atol(getenv("EOSVOS_TUNE_PRESPLIT_MAXN")) : (1L << 40);
-    if (presplit_enabled(e) && !e->gn() && a.amax_g && a.amax_x && presplit_wgrad_shape(c, B * Ho * Wo, ldg, ldx) &&
-        !(p_nogroup && wgrad_groupable(e, ci, B)) && c.cout <= p_maxcout && c.T() >= p_mink && (long)c.cin * c.T() <= p_maxn) {
+    if (presplit_enabled(e) && !e->gn() && a.amax_g && a.amax_x && presplit_wgrad_shape(c, B * Ho * Wo, ldg, ldx)) {
       const long rows_g = (long)B * Ho * Wo, rows_x = (long)B * Hin * Win;
       eosvos_engine::PairBuf *xb = nullptr, *gb = nullptr;
       const bool covx = pair_operand(e, 0, xkey, x, rows_x, c.cin, ldx, xb);
@@ -1395,15 +1320,9 @@ int conv_wgrad(eosvos_engine* e, int ci, const float* g, int ldg, const float* x
         }
         // K chunks (= slabs) and workgroups per tile: one chunk per workgroup, as many as fill the launch's share of the chip
         // (wgrad_p_pick_splits).  The kernel can also walk several chunks per workgroup (WgradPArgs::groups < splits: any K partition
-        // with any number of workgroups, bit-identical slabs -- tests/test_gpu_presplit.py); used only by the A/B switch below.
-        if (presplit_legacy_splits()) {
-          const int sl = wgrad_pick_splits(B * Ho * Wo, c.cout, c.cin, c.T(), e->budget_for(ci, 2, B));
-          pa.groups = std::max(1, wgrad_p_pick_splits(B * Ho * Wo, c.cout, c.cin, c.T(), wgp_budget(e, ci, B)));
-          pa.splits = a.splits = presplit_chunks(sl, pa.groups, (B * Ho * Wo + 31) / 32);
-        } else {
-          pa.splits = a.splits = wgrad_p_pick_splits(B * Ho * Wo, c.cout, c.cin, c.T(), wgp_budget(e, ci, B));
-          pa.groups = pa.splits;
-        }
+        // with any number of workgroups, bit-identical slabs -- tests/test_gpu_presplit.py).
+        pa.splits = a.splits = wgrad_p_pick_splits(B * Ho * Wo, c.cout, c.cin, c.T(), wgp_budget(e, ci, B));
+        pa.groups = pa.splits;
         trace(cov ? "wgrad_p" : "wgrad", ci, c.cout, (long)c.cin * c.T(), (long)B * Ho * Wo, pa.splits, wgrad_exec_frac(a));
         if (cov) go = [=](hipStream_t ws) { launch_wgrad_p(pa, ws); };
         else go = [=](hipStream_t ws) { launch_wgrad(a, ws); };
@@ -1422,7 +1341,7 @@ int conv_wgrad(eosvos_engine* e, int ci, const float* g, int ldg, const float* x
   }
 enqueue:
   if (e->s2) {
-    hipStream_t s2 = (e->s3 && !wino && (e->wg_rr++ & 1)) ? e->s3 : e->s2;
+    hipStream_t s2 = e->s2;
     e->side_q.push_back([go, s2]() { go(s2); });
     if ((int)e->side_q.size() >= (B == 1 ? EOSVOS_SIDE_BATCH : 1)) side_flush(e);
   } else {
@@ -1490,9 +1409,8 @@ int flush_updates(eosvos_engine* e, int B, bool update, bool accumulate, int par
 // read-modify-write between the branches, one fix-up pass.  Returns false when this engine / mode has to run them one by
 // one (GroupNorm mode: the gradients w.r.t. the raw conv outputs live in separate buffers; fp32-MFMA mode: no such kernel).
 bool aspp_dgrad_merged(eosvos_engine* e, int B, float* g_l4, const float* l4) {
-  static const bool off = getenv("EOSVOS_TUNE_NO_ASPP_MERGE") != nullptr;
   const Topo& t = e->t;
-  if (off || e->gn() || !conv_multi_supported() || e->force_algo != 0) return false;
+  if (e->gn() || !conv_multi_supported() || e->force_algo != 0) return false;
   for (int i = 0; i < 4; ++i) {
     const ConvL& c = t.convs[t.aspp[i]];
     if (c.cout != 256 || c.cin != t.convs[t.aspp[0]].cin || c.stride != 1 || t.aspp[i] != t.aspp[0] + i) return false;
@@ -1636,8 +1554,6 @@ int eosvos_set_launch_budget(eosvos_engine* e, int conv_idx, int kind, int batch
   return 0;
 }
 static hipError_t create_side_stream(hipStream_t* out) {
-  const char* prio = getenv("EOSVOS_TUNE_SIDE_PRIO");
-  if (prio && !strcmp(prio, "normal")) return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
   int plo = 0, phi = 0;
   const hipError_t rc = hipDeviceGetStreamPriorityRange(&plo, &phi);       // plo = least, phi = greatest priority
   if (rc != hipSuccess) return rc;
@@ -1769,11 +1685,8 @@ int eosvos_create_ex(eosvos_engine** out, int arch, int norm_mode, int height, i
     for (int b = 1; b <= B; ++b)
       for (int wb = 0; wb <= 512; wb += 64)          // every budget eosvos_set_wg_budget accepts
         slabs[ci] = max64(slabs[ci], (int64_t)wgrad_max_splits(b * Ho * Wo, c.cout, c.cin, c.T(), wb) * c.wsize());
-    bool reserve = false;
-#ifndef EOSVOS_NO_WINO
-    reserve = wino_shape(c) && (ci == t.dec_a || ci == t.dec_b ||
-                                (long long)B * Ho * Wo / 4 * c.cin * c.cout >= EOSVOS_WINO_MINWORK);
-#endif
+    const bool reserve = wino_shape(c) && (ci == t.dec_a || ci == t.dec_b ||
+                                           (long long)B * Ho * Wo / 4 * c.cin * c.cout >= EOSVOS_WINO_MINWORK);
     if (reserve) {                     // [final 9-tap slab][Winograd-domain slabs: splits x cout x 16 x cin]
       for (int b = 1; b <= B; ++b) {
         const WinoGeom gb = wino_geom(e, c, b, Ho, Wo);
@@ -1830,7 +1743,7 @@ int eosvos_create_ex(eosvos_engine** out, int arch, int norm_mode, int height, i
   ALLOC(e->lowlog, n4); ALLOC(e->g_low, n4);
   ALLOC(e->logits, (int64_t)B * H * W); ALLOC(e->dlogits, (int64_t)B * H * W);
   ALLOC(e->loss_dev, 4); ALLOC(e->bce_partial, 4 * 1024 + 16);
-  if (!getenv("EOSVOS_TUNE_NO_MASK8")) {          // (A/B switch: data gradients read the fp32 activations as masks)
+  {                                               // ReLU mask bytes of the tensors the data gradients read as masks
     // (GroupNorm mode, round 5: the apply pass that writes y = relu(gn(z) (+ res)) writes the bytes)
     auto m8alloc = [&](const float* key, int64_t floats) {     // one byte per 4 floats
       float* p = e->falloc((floats / 4 + 3) / 4);
@@ -1899,15 +1812,11 @@ int eosvos_create_ex(eosvos_engine** out, int arch, int norm_mode, int height, i
       // The side stream (weight gradients, early update, independent forward branches) yields to the main stream, whose
       // forward / data-gradient chain is the critical path: least stream priority.  Scheduling only -- results are bit-identical.
       // Round 5, three interleaved rounds: batch 3 8.81 -> 8.77 ms, batch 1 4.48 -> 4.47 (round 1 had found no gain with the
-      // fp32-MFMA kernels).  EOSVOS_TUNE_SIDE_PRIO=normal restores the default priority.
+      // fp32-MFMA kernels).
       HIPOK(create_side_stream(&e->s2));
       e->ev.resize(t.convs.size() + 2);
       for (auto& evt : e->ev) HIPOK(hipEventCreateWithFlags(&evt, hipEventDisableTiming));
       HIPOK(hipEventCreateWithFlags(&e->ev_wino_w, hipEventDisableTiming));
-      if (getenv("EOSVOS_TUNE_SIDE_STREAMS") && atoi(getenv("EOSVOS_TUNE_SIDE_STREAMS")) >= 2) {
-        HIPOK(hipStreamCreateWithFlags(&e->s3, hipStreamNonBlocking));
-        HIPOK(hipEventCreateWithFlags(&e->ev_s3, hipEventDisableTiming));
-      }
       e->ws_conv2 = e->falloc(conv_ws_floats());
       if (!e->ws_conv2) { eosvos_destroy(e); return fail("hipMalloc side workspace"); }
     }
@@ -1941,8 +1850,6 @@ int eosvos_destroy(eosvos_engine* e) {
   if (e->s2) { (void)hipStreamSynchronize(e->s2); (void)hipStreamDestroy(e->s2); }
   for (auto& evt : e->ev) (void)hipEventDestroy(evt);
   if (e->ev_wino_w) (void)hipEventDestroy(e->ev_wino_w);
-  if (e->s3) { (void)hipStreamSynchronize(e->s3); (void)hipStreamDestroy(e->s3); }
-  if (e->ev_s3) (void)hipEventDestroy(e->ev_s3);
   for (void* p : e->allocs) (void)hipFree(p);
   if (e->davis_buf) (void)hipFree(e->davis_buf);
   delete e;
@@ -2018,8 +1925,7 @@ static int ensure_meta_tabs(eosvos_engine* e) {
   return 0;
 }
 static void export_params(eosvos_engine* e, const float* src, float* flat, float alpha, int add) {
-  static const bool one = getenv("EOSVOS_TUNE_NO_META_BATCHED") == nullptr;
-  if (one && !ensure_meta_tabs(e)) {                  // one launch for the whole arena (64 before)
+  if (!ensure_meta_tabs(e)) {                         // one launch for the whole arena (64 before)
     launch_ohwi_to_oihw_all(src, flat, e->mt_toff, e->mt_tit, e->mt_nent, e->t.nparam, alpha, add, e->s);
     return;
   }
@@ -2184,8 +2090,7 @@ static int forward_impl(eosvos_engine* e, const float* images, int B) {
     }
   }
   // f16x3 mode: the stem runs on the fp16 matrix cores too (the frame's absmax comes from the layout pass)
-  static const bool stem_h3_off = getenv("EOSVOS_TUNE_NO_STEM_H3") != nullptr;
-  unsigned* ax = (h3_mode() && !stem_h3_off) ? amax_fused_slot(e, AM_X, 0, e->xpad, s) : nullptr;
+  unsigned* ax = h3_mode() ? amax_fused_slot(e, AM_X, 0, e->xpad, s) : nullptr;
   launch_nchw_to_nhwc_pad(images, e->xpad, B, 3, e->H, e->W, 3, s, ax);
   auto stem_fwd = [&](const float* a, const float* b, float* y) {
     if (ax) launch_stem_fwd_h3(e->xpad, e->W_(0), a, b, y, B, e->H, e->W, e->h2, e->w2, ax, s);
@@ -2200,11 +2105,7 @@ static int forward_impl(eosvos_engine* e, const float* images, int B) {
   }
   launch_maxpool_fwd(e->c1, e->p1, e->p1idx, B, e->h2, e->w2, 64, e->h4, e->w4, s, twrite_fused(e, 0, e->p1, true));
   // independent forward branches go to the side stream (frozen-BN mode; the GroupNorm kernels share scratch)
-#ifdef EOSVOS_NO_FWD_SIDE          // A/B switch
-  const bool fside = false;
-#else
   const bool fside = e->s2 != nullptr && !e->gn();
-#endif
   auto fork = [&](int ci) {      // the side stream continues from this point of the main stream
     (void)hipEventRecord(e->ev[ci], s);
     (void)hipStreamWaitEvent(e->s2, e->ev[ci], 0);
@@ -2254,10 +2155,8 @@ static int forward_impl(eosvos_engine* e, const float* images, int B) {
   const int P16 = e->h16 * e->w16;
   // The image-pooling branch (column sums, GEMV, broadcast, absmax: five small latency-bound launches) reads layer4's output
   // only: with a side stream it runs there, beside the four ASPP convs, and joins in front of the projection.
-  static const bool pool_side_off = getenv("EOSVOS_TUNE_NO_POOL_SIDE") != nullptr;
-  const bool pside = fside && !pool_side_off;
-  hipStream_t ps = pside ? e->s2 : s;
-  if (pside) fork(t.pool);
+  hipStream_t ps = fside ? e->s2 : s;
+  if (fside) fork(t.pool);
   auto pool_branch = [&]() {
     launch_colsum(l4, 2048, e->vec, B, P16, 2048, 1.0f / (float)P16, e->colscratch, ps);
     if (e->gn()) {
@@ -2269,15 +2168,15 @@ static int forward_impl(eosvos_engine* e, const float* images, int B) {
     }
     launch_bcast_pixels(e->poolout, e->cat + 1024, 1280, B, P16, 256, 1.f, ps, e->m8w(e->cat) ? e->m8w(e->cat) + 1024 / 4 : nullptr, 1280 / 4);
   };
-  if (pside) pool_branch();
+  if (fside) pool_branch();
   for (int i = 0; i < 4; ++i)
     conv_fwd(e, t.aspp[i], l4, 2048, e->h16, e->w16, e->cat + 256 * i, 1280, B, nullptr, 0, true, false, nullptr, e->cat);
-  if (!pside) pool_branch();
+  if (!fside) pool_branch();
   if (h3_mode() && !amax_init(e)) {
     // cat = 4 conv outputs (their epilogues fed the tensor's slot) + the broadcast pooling branch (its B x 256 values here)
     if (unsigned* cs = tslot(e, 0, e->cat)) { launch_absmax(e->poolout, 1, B * 256, B * 256, cs, ps); tmark_valid(e, 0, e->cat); }
   }
-  if (pside) { (void)hipEventRecord(e->ev[t.pool], e->s2); (void)hipStreamWaitEvent(s, e->ev[t.pool], 0); }
+  if (fside) { (void)hipEventRecord(e->ev[t.pool], e->s2); (void)hipStreamWaitEvent(s, e->ev[t.pool], 0); }
   conv_fwd(e, t.project, e->cat, 1280, e->h16, e->w16, e->proj, 256, B, nullptr, 0, true);
   const ConvL& lc = t.convs[t.last];
   if (t.v3) {
@@ -2382,17 +2281,12 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
   }
   {
     int sp[4];
-    static const int wg_after = getenv("EOSVOS_TUNE_ASPP_WGRAD_AFTER") ? atoi(getenv("EOSVOS_TUNE_ASPP_WGRAD_AFTER")) : 0;
-    if (!wg_after)
-      for (int i = 0; i < 4; ++i) sp[i] = conv_wgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, l4, 2048, e->h16, e->w16, B, e->g_cat);
+    for (int i = 0; i < 4; ++i) sp[i] = conv_wgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, l4, 2048, e->h16, e->w16, B, e->g_cat);
     if (!aspp_dgrad_merged(e, B, g_l4, l4)) {
-      if (wg_after) return fail("EOSVOS_TUNE_ASPP_WGRAD_AFTER needs the merged ASPP data gradient");
       for (int i = 0; i < 4; ++i)
         conv_dgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, e->h16, e->w16, g_l4, 2048, B, true, i == 3 ? l4 : nullptr, 2048, 0, nullptr, 0,
                    e->g_cat);
     }
-    if (wg_after)
-      for (int i = 0; i < 4; ++i) sp[i] = conv_wgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, l4, 2048, e->h16, e->w16, B, e->g_cat);
     for (int i = 0; i < 4; ++i) apply_update(e, t.aspp[i], sp[i], update, accumulate);
   }
   // bottlenecks, last to first.  g_out of each block = dL/d(pre-ReLU block output).
@@ -2404,7 +2298,6 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
         side_flush(e);
         (void)hipEventRecord(e->ev[t.convs.size()], e->s);      // their dgrads were the last readers of W
         (void)hipStreamWaitEvent(e->s2, e->ev[t.convs.size()], 0);
-        if (e->s3) { (void)hipEventRecord(e->ev_s3, e->s3); (void)hipStreamWaitEvent(e->s2, e->ev_s3, 0); }   // slabs written on s3
         if (flush_updates(e, B, update, accumulate, 0, e->s2)) return 1;
         e->side_used = true;
       } else if (flush_updates(e, B, update, accumulate, 0, e->s)) return 1;
@@ -2444,9 +2337,8 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
   // stem
   // f16x3 mode (frozen norm): the stem's weight gradient on the fp16 matrix cores; the absmax of its gradient operand comes
   // from the pooling backward, the frame's from this iteration's forward (slot (X, conv 0))
-  static const bool stem_h3_off = getenv("EOSVOS_TUNE_NO_STEM_H3") != nullptr;
   const auto& xrec = amax_rec_of(e, AM_X, 0);
-  const bool stem_h3 = h3_mode() && !stem_h3_off && e->amax && xrec.epoch == e->fwd_epoch && xrec.ptr == e->xpad;
+  const bool stem_h3 = h3_mode() && e->amax && xrec.epoch == e->fwd_epoch && xrec.ptr == e->xpad;
   // (GroupNorm mode, round 5: the gradient operand is dz of the stem's GroupNorm, whose apply pass reduces its absmax)
   unsigned* ag = stem_h3 ? amax_fused_slot(e, AM_G, 0, e->gn() ? e->zbuf[0] : e->g_c1, s) : nullptr;
   launch_maxpool_bwd(e->g_p1, e->p1idx, e->g_c1, B, e->h2, e->w2, 64, e->h4, e->w4, s, e->gn() ? nullptr : ag);
@@ -2462,7 +2354,6 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     apply_update(e, 0, chunks, update, accumulate);
   }
   if (e->s2) side_flush(e);
-  if (e->s3 && e->side_used) { (void)hipEventRecord(e->ev_s3, e->s3); (void)hipStreamWaitEvent(e->s, e->ev_s3, 0); }
   if (e->s2 && e->side_used) {           // join: the update reads every slab
     (void)hipEventRecord(e->ev.back(), e->s2);
     (void)hipStreamWaitEvent(e->s, e->ev.back(), 0);
@@ -2727,8 +2618,7 @@ int eosvos_meta_grad_ex(eosvos_engine* e, const float* images, const float* mask
       if (ensure_lr_maps(e)) return 1;
       HIPOK(hipMemsetAsync(e->glr_tmp, 0, (size_t)t.nlr * 4, e->s));
     }
-    static const bool one = getenv("EOSVOS_TUNE_NO_META_BATCHED") == nullptr;
-    if (one && !ensure_meta_tabs(e)) {                // every tensor's rows in one launch (64 before)
+    if (!ensure_meta_tabs(e)) {                       // every tensor's rows in one launch (64 before)
       launch_meta_lr_grad_all(e->gsum, e->gout, gl, e->mt_rbase, e->mt_rlen, (int)t.nlr, weight, e->s);
     } else {
       for (const ConvL& c : t.convs) {

@@ -421,10 +421,7 @@ struct UpdEntry {
   int blk0;        // first workgroup of this entry (UPD_CHUNKS x 1024 elements per workgroup)
   int amax_idx;    // f16x3 mode: index of the tensor's absmax word in `amax_w` (the conv index), -1: none
 };
-#ifndef UPD_CHUNKS
-#define UPD_CHUNKS 1
-#endif
-// UPD_CHUNKS: 1024-element chunks per workgroup of the update kernel (UpdEntry::blk0 counts those)
+#define UPD_CHUNKS 1      // 1024-element chunks per workgroup of the update kernel (UpdEntry::blk0 counts those)
 void launch_sgd_update_all(const UpdEntry* tab, int nent, int nblocks, float* W, const float* ws, const float* na,
                            const float* lr, const float* lr_elem, float* gsum, float* gout, hipStream_t s,
                            unsigned* amax_w = nullptr);   // amax_w: max|w| of the updated weights, per UpdEntry::amax_idx

@@ -75,7 +75,7 @@ int eosvos_get_matrix_mode(void);
 /* Pre-split operand path of the F16X3 mode (round 6, presplit_kernels.hip): weight gradients whose channel counts are multiples
  * of 256 read their operands as fp16 (hi, lo) pair tensors made by a split pass (same two pieces, same products, same fp32
  * accumulation as the on-the-fly split) on 256 x 256 tiles staged by LDS-DMA.  Process-wide switch, default on
- * (EOSVOS_PRESPLIT=0: off; on = 2: also for maps below the 1024-pixel minimum, for tests on small frames); returns the previous
+ * (EOSVOS_PRESPLIT=0: off; on = 2: also for maps below the 4000-pixel minimum, for tests on small frames); returns the previous
  * setting.  Live engines re-plan at their next call. */
 int eosvos_set_presplit(int on);
 /* Launch-plan fingerprint of the engine's last forward (out2[0]) and backward (out2[1]) pass: a 64-bit FNV-1a hash over (kind,

@@ -1,7 +1,7 @@
 """The launch plan the full-length parity fixtures were cleared with (round 6).
 
 The K-split / tile plan of every matrix launch fixes the fp32 summation order.  Round 5 measured that an equally valid other plan
-(`EOSVOS_TUNE_WG_EFF=80`) moves the fp32-MFMA mode's 240-iteration trajectory (fixture G21) from 3.6e-4 to 1.04e-3 on the logits --
+(weight-gradient K splits that fill 80 % of a round instead of 93 %, an A/B switch since removed) moves the fp32-MFMA mode's 240-iteration trajectory (fixture G21) from 3.6e-4 to 1.04e-3 on the logits --
 so G20 / G21 / G22 / G23 pin ONE plan per (mode, batch), and a change of the plan rules must re-clear them
 (`tests/test_gpu_fulllength.py`) and then refresh `tests/golden/plan_fingerprint.json` with `tools/plan_fingerprint.py --write`.
 This test fails when the plan differs from the recorded one (reference loop: `/root/reference/src/util/evaluate.py:207-281`).

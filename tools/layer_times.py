@@ -1,6 +1,7 @@
 """Per-launch time of every conv (fwd / dgrad / wgrad incl. fix-ups and transforms, one stream) under the current
 environment -> JSON on stdout: {"ci:kind": us}.   python tools/layer_times.py [batch]
-Run it under different EOSVOS_TUNE_* settings and diff the outputs (tools/layer_times_diff.py)."""
+Run it under two settings (e.g. EOSVOS_MFMA, EOSVOS_PRESPLIT, or two EOSVOS_LIB builds) and diff the outputs
+(tools/layer_times_diff.py)."""
 import json, sys
 sys.path.insert(0, '.')
 from eosvos_amd import synthetic
