@@ -83,6 +83,7 @@ _SIGNATURES = {
                                          ctypes.c_int, ctypes.c_int64, ctypes.c_int64]),
     'eosvos_alias_state': (ctypes.c_int, [_E, _E]),
     'eosvos_unalias_state': (ctypes.c_int, [_E]),
+    'eosvos_set_trainable_from': (ctypes.c_int, [_E, ctypes.c_int]),
     'eosvos_comm_unique_id': (ctypes.c_int, [ctypes.c_void_p]),
     'eosvos_comm_init_rank': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
     'eosvos_comm_destroy': (ctypes.c_int, [ctypes.c_void_p]),

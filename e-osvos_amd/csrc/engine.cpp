@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <functional>
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -266,6 +267,13 @@ struct eosvos_engine {
   eosvos_engine* alias_src = nullptr;
   float *own_Winit = nullptr, *own_lr = nullptr;
   std::vector<eosvos_engine*> aliased_by;
+  // eosvos_set_trainable_from: convs [0, train_from) are frozen (parent_model.train_encoder False).  The backward pass ends at
+  // the boundary, their weights are never updated, and their gradients are neither summed (gsum) nor exported (gout).
+  int train_from = 0;
+  int64_t tf_poff = 0, tf_lroff = 0;  // arena / per-neuron lr offset of the first trainable conv
+  int tf_tensor = 0;                  // trainable tensors before it
+  long* tf_toff = nullptr;            // export table of the trainable tensors, offsets relative to tf_poff (export_params)
+  std::set<const float*> m8_frozen;   // activations whose ReLU mask only a frozen conv's data gradient would read
   // pre-split operand path (presplit_kernels.hip, round 6): "pair8" siblings of fp32 tensors -- the two fp16 pieces of the
   // f16x3 product laid out for LDS-DMA.  One sibling per TENSOR (keyed like the absmax slots: first element of the
   // allocation; a view's sibling is the same offset into it).  Once a consumer has asked for a tensor's sibling (`want`), the
@@ -329,7 +337,8 @@ struct eosvos_engine {
     auto it = mask8.find(key);
     return it == mask8.end() ? nullptr : it->second;
   }
-  uint8_t* m8w(const float* key) const { return fwd_masks ? m8(key) : nullptr; }      // for the forward's writers
+  // for the forward's writers: no bytes for a mask that no backward pass of this engine reads (frozen region)
+  uint8_t* m8w(const float* key) const { return fwd_masks && !m8_frozen.count(key) ? m8(key) : nullptr; }
   int64_t max_alloc_floats = 0;      // largest single allocation (every conv operand is one of them)
   // EOSVOS_DEBUG_GUARD=1: every buffer sits between two 256 KB guard bands filled with a pattern;
   // eosvos_debug_check_guards reports bands a kernel wrote into (out-of-bounds writes)
@@ -1356,10 +1365,11 @@ void apply_update(eosvos_engine* e, int ci, int splits, bool /*update*/, bool /*
 // one launch: sum every layer's slabs, norm scale, theta <- theta - lr*g, optional gsum/gout
 // part 0: convs [split, nconv) = layer4 + ASPP + decoder (90 % of the parameters), whose backward
 // finishes first; part 1: convs [0, split).  With a side stream part 0 is launched there as soon
-// as layer4's backward is queued and hides under the layer3..1 backward.
+// as layer4's backward is queued and hides under the layer3..1 backward.  With a trainable boundary
+// (eosvos_set_trainable_from) part 0 is convs [train_from, nconv) and part 1 is never launched.
 int flush_updates(eosvos_engine* e, int B, bool update, bool accumulate, int part, hipStream_t stream) {
   const Topo& t = e->t;
-  const int split = t.blocks[t.blocks.size() - 3].c1;   // first conv of layer4
+  const int split = e->train_from > 0 ? e->train_from : t.blocks[t.blocks.size() - 3].c1;   // first conv of layer4
   const int lo = part == 0 ? split : 0, hi = part == 0 ? (int)t.convs.size() : split;
   const int slot = 2 * B + part;
   if (!e->upd_tab[slot]) {
@@ -1390,7 +1400,8 @@ int flush_updates(eosvos_engine* e, int B, bool update, bool accumulate, int par
   // the backward pass (main stream) reads only those.
   unsigned* amax_w = nullptr;
   if (update) {
-    for (auto& kv : e->wino_us_valid) kv.second = 0;
+    for (auto& kv : e->wino_us_valid)
+      if (e->train_from == 0 || kv.first >= lo) kv.second = 0;     // a frozen conv keeps its transformed weights
     if (h3_mode() && !amax_init(e) && e->w_amax_valid) {
       amax_w = amax_slot(e, AM_W, 0);
       amax_zero(amax_w + lo, (size_t)(hi - lo), stream);
@@ -1924,12 +1935,19 @@ static int ensure_meta_tabs(eosvos_engine* e) {
   HIPOK(hipMemcpy(e->mt_tit, tit.data(), tit.size() * sizeof(int2), hipMemcpyHostToDevice));
   return 0;
 }
-static void export_params(eosvos_engine* e, const float* src, float* flat, float alpha, int add) {
+// trainable_only: the tensors of convs [train_from, nconv) only (the frozen prefix of `flat` is not touched)
+static void export_params(eosvos_engine* e, const float* src, float* flat, float alpha, int add, bool trainable_only = false) {
+  const bool sub = trainable_only && e->train_from > 0;
   if (!ensure_meta_tabs(e)) {                         // one launch for the whole arena (64 before)
-    launch_ohwi_to_oihw_all(src, flat, e->mt_toff, e->mt_tit, e->mt_nent, e->t.nparam, alpha, add, e->s);
+    if (sub)
+      launch_ohwi_to_oihw_all(src + e->tf_poff, flat + e->tf_poff, e->tf_toff, e->mt_tit + e->tf_tensor, e->mt_nent - e->tf_tensor,
+                              e->t.nparam - e->tf_poff, alpha, add, e->s);
+    else
+      launch_ohwi_to_oihw_all(src, flat, e->mt_toff, e->mt_tit, e->mt_nent, e->t.nparam, alpha, add, e->s);
     return;
   }
   for (const ConvL& c : e->t.convs) {
+    if (sub && c.poff < e->tf_poff) continue;
     launch_ohwi_to_oihw(src + c.poff, flat + c.poff, c.cout, c.cin, c.T(), alpha, add, e->s);
     if (c.bias) launch_ohwi_to_oihw(src + c.poff + c.wsize(), flat + c.poff + c.wsize(), c.cout, 1, 1, alpha, add, e->s);
   }
@@ -2216,6 +2234,10 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
   PlanScope plan_scope(e, 1);
   const int64_t P4 = (int64_t)B * e->h4 * e->w4;
   const int P16 = e->h16 * e->w16;
+  // trainable boundary (eosvos_set_trainable_from): no data gradient flows into a frozen conv's output, no frozen conv's
+  // weight gradient is made; `l4_frozen`: the whole backbone is frozen, the pass ends at the ASPP
+  const bool frozen = e->train_from > 0;
+  const bool l4_frozen = frozen && e->train_from > t.blocks.back().c3;
   amax_new_phase(e, 1);
   // final resize
   launch_resize_bwd(e->dlogits, 1, e->g_low, 1, nullptr, 0, B, 1, e->fin_h, e->fin_w, s);
@@ -2252,7 +2274,8 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     float* g_low_feat = e->bb[t.layer1_last_block].g_out;
     const float* low = e->bb[t.layer1_last_block].out;
     int sp = conv_wgrad(e, t.dec1, e->g_dcat + 256, 304, low, 256, e->h4, e->w4, B, e->g_dcat);
-    conv_dgrad(e, t.dec1, e->g_dcat + 256, 304, e->h4, e->w4, g_low_feat, 256, B, false, nullptr, 0, 0, nullptr, 0, e->g_dcat);
+    if (!frozen)
+      conv_dgrad(e, t.dec1, e->g_dcat + 256, 304, e->h4, e->w4, g_low_feat, 256, B, false, nullptr, 0, 0, nullptr, 0, e->g_dcat);
     apply_update(e, t.dec1, sp, update, accumulate);
   }
   // decoder upsample backward (+ ReLU mask of the projection output)
@@ -2274,33 +2297,43 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
       launch_gn_backward(e->zbuf[t.pool], 256, e->gp, 256, e->G_(t.pool), e->gn_stats[t.pool], e->gn_partial, B, 1, 256, s);
       gpz = e->zbuf[t.pool];
     }
-    launch_gemv_bwd(e->W_(t.pool), e->vec, gpz, e->A_(t.pool), e->gvec, e->ws_wg + e->ws_off[t.pool], B, 256, 2048, s);
-    launch_bcast_pixels(e->gvec, g_l4, 2048, B, P16, 2048, 1.0f / (float)P16, s);
-    twrite_plain(e, 1, g_l4);
+    // (frozen backbone: the weight gradient only, no input gradient)
+    launch_gemv_bwd(e->W_(t.pool), e->vec, gpz, e->A_(t.pool), l4_frozen ? nullptr : e->gvec, e->ws_wg + e->ws_off[t.pool], B, 256,
+                    2048, s);
+    if (!l4_frozen) {
+      launch_bcast_pixels(e->gvec, g_l4, 2048, B, P16, 2048, 1.0f / (float)P16, s);
+      twrite_plain(e, 1, g_l4);
+    }
     apply_update(e, t.pool, 1, update, accumulate);
   }
   {
     int sp[4];
     for (int i = 0; i < 4; ++i) sp[i] = conv_wgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, l4, 2048, e->h16, e->w16, B, e->g_cat);
-    if (!aspp_dgrad_merged(e, B, g_l4, l4)) {
+    if (!l4_frozen && !aspp_dgrad_merged(e, B, g_l4, l4)) {
       for (int i = 0; i < 4; ++i)
         conv_dgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, e->h16, e->w16, g_l4, 2048, B, true, i == 3 ? l4 : nullptr, 2048, 0, nullptr, 0,
                    e->g_cat);
     }
     for (int i = 0; i < 4; ++i) apply_update(e, t.aspp[i], sp[i], update, accumulate);
   }
+  // layer4, ASPP and decoder are done: update them now (on the side stream if there is one)
+  auto flush_part0 = [&]() -> int {
+    if (e->s2) {
+      side_flush(e);
+      (void)hipEventRecord(e->ev[t.convs.size()], e->s);      // their dgrads were the last readers of W
+      (void)hipStreamWaitEvent(e->s2, e->ev[t.convs.size()], 0);
+      if (flush_updates(e, B, update, accumulate, 0, e->s2)) return 1;
+      e->side_used = true;
+    } else if (flush_updates(e, B, update, accumulate, 0, e->s)) return 1;
+    return 0;
+  };
+  if (l4_frozen && flush_part0()) return 1;
   // bottlenecks, last to first.  g_out of each block = dL/d(pre-ReLU block output).
   const int first_l4_block = (int)t.blocks.size() - 3;
-  for (int i = (int)t.blocks.size() - 1; i >= 0; --i) {
+  for (int i = l4_frozen ? -1 : (int)t.blocks.size() - 1; i >= 0; --i) {
     if (i == first_l4_block - 1) {
-      // layer4, ASPP and decoder are done: update them now (on the side stream if there is one)
-      if (e->s2) {
-        side_flush(e);
-        (void)hipEventRecord(e->ev[t.convs.size()], e->s);      // their dgrads were the last readers of W
-        (void)hipStreamWaitEvent(e->s2, e->ev[t.convs.size()], 0);
-        if (flush_updates(e, B, update, accumulate, 0, e->s2)) return 1;
-        e->side_used = true;
-      } else if (flush_updates(e, B, update, accumulate, 0, e->s)) return 1;
+      if (flush_part0()) return 1;
+      if (frozen) break;                 // layer1..3 and the stem are frozen
     }
     const Block& b = t.blocks[i];
     auto& f = e->bb[i];
@@ -2316,12 +2349,14 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     // the low-level feature already holds decoder.conv1's contribution
     bool have = !t.v3 && (i == t.layer1_last_block + 1);
     const float* inmask = is_first_block ? nullptr : f.xin;   // p1 is a max-pool output: masked in maxpool_bwd
+    // (the block's input is a frozen conv's output: weight gradients only)
+    const bool in_frozen = frozen && b.c1 == e->train_from;
     if (b.ds >= 0) {
       sp = conv_wgrad(e, b.ds, f.g_out, cout, f.xin, f.Cin, f.Hi, f.Wi, B);
-      conv_dgrad(e, b.ds, f.g_out, cout, f.Hi, f.Wi, f.g_xin, f.Cin, B, have, nullptr, 0, 0);
+      if (!in_frozen) conv_dgrad(e, b.ds, f.g_out, cout, f.Hi, f.Wi, f.g_xin, f.Cin, B, have, nullptr, 0, 0);
       apply_update(e, b.ds, sp, update, accumulate);
       sp = conv_wgrad(e, b.c1, f.g_t1, cmid, f.xin, f.Cin, f.Hi, f.Wi, B);
-      conv_dgrad(e, b.c1, f.g_t1, cmid, f.Hi, f.Wi, f.g_xin, f.Cin, B, true, inmask, f.Cin, 0);
+      if (!in_frozen) conv_dgrad(e, b.c1, f.g_t1, cmid, f.Hi, f.Wi, f.g_xin, f.Cin, B, true, inmask, f.Cin, 0);
       apply_update(e, b.c1, sp, update, accumulate);
     } else {
       // identity path: g_xin = mask * (dgrad_conv1(g_t1) + g_out)
@@ -2335,6 +2370,7 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     if (b.ds >= 0 && flush_wgrad_group(e, t.stage[b.c1], B)) return 1;
   }
   // stem
+  if (!frozen) {
   // f16x3 mode (frozen norm): the stem's weight gradient on the fp16 matrix cores; the absmax of its gradient operand comes
   // from the pooling backward, the frame's from this iteration's forward (slot (X, conv 0))
   const auto& xrec = amax_rec_of(e, AM_X, 0);
@@ -2353,13 +2389,14 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     else launch_stem_wgrad(e->xpad, gc1, e->ws_wg + e->ws_off[0], B, e->H, e->W, e->h2, e->w2, chunks, s);
     apply_update(e, 0, chunks, update, accumulate);
   }
+  }
   if (e->s2) side_flush(e);
   if (e->s2 && e->side_used) {           // join: the update reads every slab
     (void)hipEventRecord(e->ev.back(), e->s2);
     (void)hipStreamWaitEvent(e->s, e->ev.back(), 0);
     e->side_used = false;
   }
-  if (flush_updates(e, B, update, accumulate, 1, e->s)) return 1;
+  if (!frozen && flush_updates(e, B, update, accumulate, 1, e->s)) return 1;
   for (size_t ci = 0; ci < e->upd_splits.size(); ++ci) plan_mix((uint64_t)e->upd_splits[ci]);     // slabs per conv (incl. grouped launches)
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(std::string("backward launch: ") + hipGetErrorString(err));
@@ -2454,7 +2491,8 @@ int eosvos_get_grads(eosvos_engine* e, float* out) {
   ModeScope mode_scope(e);
   if (!e || !out) return fail("null argument");
   if (!e->keep_grads) return fail("gradients are only kept after eosvos_keep_grads(e, 1)");
-  export_params(e, e->gout, out, 1.f, 0);
+  if (e->train_from > 0) HIPOK(hipMemsetAsync(out, 0, (size_t)e->tf_poff * 4, e->s));     // frozen tensors: zero gradient
+  export_params(e, e->gout, out, 1.f, 0, true);
   HIPOK(hipGetLastError());
   return 0;
 }
@@ -2585,7 +2623,7 @@ int eosvos_meta_task_begin(eosvos_engine* e) {
     e->gsum = e->falloc(e->t.nparam);
     if (!e->gsum) return fail("hipMalloc gsum");
   }
-  HIPOK(hipMemsetAsync(e->gsum, 0, (size_t)e->t.nparam * 4, e->s));
+  HIPOK(hipMemsetAsync(e->gsum + e->tf_poff, 0, (size_t)(e->t.nparam - e->tf_poff) * 4, e->s));   // (frozen part: never written)
   return eosvos_reset(e);
 }
 int eosvos_meta_grad(eosvos_engine* e, const float* images, const float* masks, int batch, float* flat_meta_grad,
@@ -2607,9 +2645,12 @@ int eosvos_meta_grad_ex(eosvos_engine* e, const float* images, const float* mask
   if (rc) return 1;
   const Topo& t = e->t;
   const int64_t nstore = lr_store_count(t, e->lr_level);
+  // trainable boundary: only the trainable convs' rows / elements are made (the frozen ones of the caller's buffer are left as
+  // they are: zero for a zeroed buffer); gsum / gout hold nothing for the frozen convs
+  const int64_t p0 = e->tf_poff, r0 = e->tf_lroff;
   if (e->lr_level == EOSVOS_LR_PARAM) {
-    launch_meta_lr_grad_elem(e->gsum, e->gout, e->lr_log ? e->lr_elem : nullptr, e->ptmp, t.nparam, e->s);
-    export_params(e, e->ptmp, flat_meta_grad, weight, 1);
+    launch_meta_lr_grad_elem(e->gsum + p0, e->gout + p0, e->lr_log ? e->lr_elem + p0 : nullptr, e->ptmp + p0, t.nparam - p0, e->s);
+    export_params(e, e->ptmp, flat_meta_grad, weight, 1, true);
   } else {
     // per-neuron d/d lr first (into the caller's buffer directly when that is the stored level)
     const bool direct = e->lr_level == EOSVOS_LR_NEURON && !e->lr_log;
@@ -2619,9 +2660,10 @@ int eosvos_meta_grad_ex(eosvos_engine* e, const float* images, const float* mask
       HIPOK(hipMemsetAsync(e->glr_tmp, 0, (size_t)t.nlr * 4, e->s));
     }
     if (!ensure_meta_tabs(e)) {                       // every tensor's rows in one launch (64 before)
-      launch_meta_lr_grad_all(e->gsum, e->gout, gl, e->mt_rbase, e->mt_rlen, (int)t.nlr, weight, e->s);
+      launch_meta_lr_grad_all(e->gsum, e->gout, gl + r0, e->mt_rbase + r0, e->mt_rlen + r0, (int)(t.nlr - r0), weight, e->s);
     } else {
       for (const ConvL& c : t.convs) {
+        if (c.poff < p0) continue;
         launch_meta_lr_grad(e->gsum + c.poff, e->gout + c.poff, gl + c.lroff, c.cout, (int64_t)c.T() * c.cin, weight, e->s);
         if (c.bias)
           launch_meta_lr_grad(e->gsum + c.poff + c.wsize(), e->gout + c.poff + c.wsize(), gl + c.lroff + c.cout,
@@ -2629,16 +2671,16 @@ int eosvos_meta_grad_ex(eosvos_engine* e, const float* images, const float* mask
       }
     }
     if (e->lr_level == EOSVOS_LR_NEURON) {
-      if (!direct) launch_lr_grad_neuron(gl, e->lr, flat_meta_grad, (int)t.nlr, e->lr_log, e->s);
+      if (!direct) launch_lr_grad_neuron(gl + r0, e->lr + r0, flat_meta_grad + r0, (int)(t.nlr - r0), e->lr_log, e->s);
     } else if (e->lr_level == EOSVOS_LR_TENSOR) {
       launch_lr_grad_reduce(gl, e->lr, e->tensor_row0, flat_meta_grad, e->ntensors, e->lr_log, e->s);
     } else {
       launch_lr_grad_reduce(gl, e->lr, e->all_row0, flat_meta_grad, 1, e->lr_log, e->s);
     }
   }
-  if (flags & EOSVOS_META_INIT_GRAD) export_params(e, e->gout, flat_meta_grad + nstore, weight, 1);
+  if (flags & EOSVOS_META_INIT_GRAD) export_params(e, e->gout, flat_meta_grad + nstore, weight, 1, true);
   // truncated BPTT: the next segment starts from detached parameters (meta_optim.reset(keep_state=True))
-  if (flags & EOSVOS_META_NEW_SEGMENT) HIPOK(hipMemsetAsync(e->gsum, 0, (size_t)t.nparam * 4, e->s));
+  if (flags & EOSVOS_META_NEW_SEGMENT) HIPOK(hipMemsetAsync(e->gsum + p0, 0, (size_t)(t.nparam - p0) * 4, e->s));
   HIPOK(hipGetLastError());
   if (meta_loss_host) {
     HIPOK(hipMemcpyAsync(meta_loss_host, e->loss_dev, 4, hipMemcpyDeviceToHost, e->s));
@@ -2679,6 +2721,8 @@ int eosvos_outer_step(eosvos_engine* e, float* state, float* grad, float* exp_av
   if (!e || !state || !grad || !exp_avg || !exp_avg_sq || step < 1) return fail("bad argument");
   const Topo& t = e->t;
   if (n_lr != t.nlr) return fail("eosvos_outer_step handles the NEURON lr hierarchy level only (n_lr must be eosvos_lr_count)");
+  if (e->train_from > 0)
+    return fail("eosvos_outer_step: not with a trainable boundary (the learned state is the trainable subset: eosvos_radam_step)");
   if (!e->outer_tab) {
     std::vector<OuterEnt> tab;
     int blk = 0;
@@ -2744,6 +2788,7 @@ int eosvos_alias_state(eosvos_engine* e, eosvos_engine* src) {
   if (!e || !src) return fail("null engine");
   if (e == src) return 0;
   if (e->dev != src->dev || e->arch != src->arch) return fail("eosvos_alias_state: engines of different devices / architectures");
+  if (e->train_from != src->train_from) return fail("eosvos_alias_state: engines with different trainable boundaries");
   if (src->alias_src) return fail("eosvos_alias_state: the source engine is itself an alias (alias its source instead)");
   if (!e->aliased_by.empty()) return fail("eosvos_alias_state: other engines read this engine's state");
   if (e->alias_src == src) return 0;
@@ -2761,6 +2806,48 @@ int eosvos_unalias_state(eosvos_engine* e) {
   ModeScope mode_scope(e);
   if (!e) return fail("null engine");
   return unalias_impl(e);
+}
+
+int eosvos_set_trainable_from(eosvos_engine* e, int conv_idx) {
+  if (!e) return fail("null engine");
+  const Topo& t = e->t;
+  const int l4 = t.blocks[t.blocks.size() - 3].c1;
+  if (conv_idx != 0 && conv_idx != l4 && conv_idx != t.aspp[0])
+    return fail("eosvos_set_trainable_from: the boundary must be 0, the first conv of layer4 or the first ASPP conv");
+  if (conv_idx == e->train_from) return 0;
+  if (e->alias_src || !e->aliased_by.empty())
+    return fail("eosvos_set_trainable_from: not on an engine that shares its learned state (eosvos_alias_state)");
+  int tens = 0;
+  for (int ci = 0; ci < conv_idx; ++ci) tens += t.convs[ci].bias ? 2 : 1;
+  const ConvL& c0 = t.convs[conv_idx];
+  if (conv_idx > 0) {                       // export table of the trainable tensors (offsets relative to the first of them)
+    std::vector<long> toff;
+    for (size_t ci = conv_idx; ci < t.convs.size(); ++ci) {
+      const ConvL& c = t.convs[ci];
+      toff.push_back((long)(c.poff - c0.poff));
+      if (c.bias) toff.push_back((long)(c.poff + c.wsize() - c0.poff));
+    }
+    long* d = (long*)e->falloc((int64_t)toff.size() * 2);
+    if (!d) return fail("hipMalloc trainable export table");
+    HIPOK(hipMemcpy(d, toff.data(), toff.size() * sizeof(long), hipMemcpyHostToDevice));
+    e->tf_toff = d;
+  }
+  HIPOK(hipStreamSynchronize(e->s));        // launches queued under the old boundary finish before the tables change
+  e->train_from = conv_idx;
+  e->tf_poff = conv_idx > 0 ? c0.poff : 0;
+  e->tf_lroff = conv_idx > 0 ? c0.lroff : 0;
+  e->tf_tensor = conv_idx > 0 ? tens : 0;
+  for (auto& tab : e->upd_tab) tab = nullptr;       // the update's part 0 covers another conv range
+  if (e->gsum) HIPOK(hipMemsetAsync(e->gsum, 0, (size_t)t.nparam * 4, e->s));
+  // ReLU masks that only a frozen conv's data gradient reads: the activations of the frozen blocks
+  e->m8_frozen.clear();
+  if (conv_idx > 0)
+    for (size_t i = 0; i < t.blocks.size(); ++i) {
+      if (t.blocks[i].c1 >= conv_idx) break;
+      e->m8_frozen.insert({e->bb[i].t1, e->bb[i].t2, e->bb[i].out});
+    }
+  e->masks_valid = false;                   // a backward pass needs a forward made under this boundary
+  return 0;
 }
 
 // ---- RCCL: the one exchange of the meta-training path ------------------------------------------------------------------

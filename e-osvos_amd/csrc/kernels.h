@@ -366,7 +366,7 @@ void launch_colsum(const float* x, int ldx, float* out /*[B][C]*/, int B, int P,
 // y[b][n] = relu(a[n]*sum_k W[n][k]*v[b][k] + b[n])
 void launch_gemv_fwd(const float* W, const float* v, const float* a, const float* b, float* y, int B,
                      int N, int K, hipStream_t s);
-// gv[b][k] = sum_n gp[b][n]*a[n]*W[n][k] ;  dW[n][k] = sum_b gp[b][n]*v[b][k]
+// gv[b][k] = sum_n gp[b][n]*a[n]*W[n][k] ;  dW[n][k] = sum_b gp[b][n]*v[b][k]  (gv may be nullptr: dW only)
 void launch_gemv_bwd(const float* W, const float* v, const float* gp, const float* a, float* gv,
                      float* dW, int B, int N, int K, hipStream_t s);
 void launch_bcast_pixels(const float* v /*[B][C]*/, float* y, int ldy, int B, int P, int C, float alpha,

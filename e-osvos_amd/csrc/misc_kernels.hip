@@ -630,7 +630,7 @@ void launch_gemv_fwd(const float* W, const float* v, const float* a, const float
 __global__ void gemv_bwd_kernel(const float* __restrict__ W, const float* __restrict__ v,
                                 const float* __restrict__ gp, const float* __restrict__ a,
                                 float* __restrict__ gv, float* __restrict__ dW, int B, int N, int K) {
-  const long nv = (long)B * K, nw = (long)N * K;
+  const long nv = gv ? (long)B * K : 0, nw = (long)N * K;      // gv == nullptr: the weight gradient only
   GRID_STRIDE(e, nv + nw) {
     if (e < nv) {
       const int k = (int)(e % K), b = (int)(e / K);
@@ -649,7 +649,7 @@ __global__ void gemv_bwd_kernel(const float* __restrict__ W, const float* __rest
 }
 void launch_gemv_bwd(const float* W, const float* v, const float* gp, const float* a, float* gv, float* dW,
                      int B, int N, int K, hipStream_t s) {
-  const long n = (long)B * K + (long)N * K;
+  const long n = (gv ? (long)B * K : 0) + (long)N * K;
   hipLaunchKernelGGL(gemv_bwd_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, W, v, gp, a, gv, dW, B, N, K);
 }
 __global__ void bcast_pixels_kernel(const float* __restrict__ v, float* __restrict__ y, int ldy, int B, int P,

@@ -123,6 +123,7 @@ class Engine:
                                              self.device.index or 0, ctypes.c_void_p(self.stream.cuda_stream),
                                              0 if side_stream else 1))          # EOSVOS_CREATE_NO_SIDE_STREAM
         self.h = h
+        self.train_from = 0                # eosvos_set_trainable_from
         self._loss = torch.zeros(1, device=self.device)
         # host-side view of the engine's state (networks.DeepLabV3Plus carries it across an engine re-creation)
         self.steps_since_reset, self.has_snapshot, self.in_meta_task = 0, False, False
@@ -552,6 +553,12 @@ class Engine:
         self.lr_level, self.lr_log, self.n_lr_store = 'NEURON', bool(use_log), self.n_lr
         if learn_model_init:
             self.steps_since_reset = 0
+
+    def set_trainable_from(self, conv_idx):
+        """`eosvos_set_trainable_from`: convs [0, conv_idx) are frozen (`topology.trainable_from`; 0 trains everything).  Weight
+        entries keep the full layout; the frozen part of the meta-gradient / gradients is left untouched / zero."""
+        _ffi.check(self.lib.eosvos_set_trainable_from(self.h, int(conv_idx)))
+        self.train_from = int(conv_idx)
 
     def alias_state(self, src):
         """`eosvos_alias_state`: this engine reads `src`'s learned init and per-neuron lr from now on (engines that run the

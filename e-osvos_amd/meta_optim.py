@@ -18,6 +18,8 @@ Reference semantics kept:
     (`meta_optim.py:27-67,157-163,180-185`): the learned state keeps the reference's tensors
     (`log_init_lr` (1,1) / (G,1), or one `log_init_lr_<name>` per tensor); the engine expands it to the
     effective lr of the step and returns d/d(state) in the same layout (`eosvos_set_lr_state`).
+  * a frozen encoder (`train_encoder=False`): only the `requires_grad` tensors are learned (`meta_optim.py:46-78`,
+    `meta_model.py:29-60`), so every level above covers that subset (TENSOR: G = 21 for DeepLabV3+, 9 for DeepLabV3).
 Unsupported reference options raise NotImplementedError exactly like the reference does for
 unknown hierarchy levels (`meta_optim.py:68-69`).
 """
@@ -41,7 +43,7 @@ class _MetaModelShim:
 
     @property
     def num_param_groups(self):
-        return len(self.model._names)
+        return len(self.model._train_names)
 
 
 class MetaOptimizer:
@@ -65,7 +67,8 @@ class MetaOptimizer:
         self.meta_model = _MetaModelShim(model)
         self.state = {'num_steps': 0}
         self._train_loss = None
-        names, shapes = model._names, model._shapes
+        names = model._train_names
+        shapes = [model._shapes[model._names.index(n)] for n in names]
         self._lr_views = OrderedDict()
         lvl = lr_hierarchy_level
         if lvl == 'SINGLE':                               # meta_optim.py:27-31
@@ -95,6 +98,7 @@ class MetaOptimizer:
         for k, v in learned:
             self._params[k] = _Param(k, v, True)
         self._grad_flat = None
+        self._n_init = sum(v.numel() for v in self._init_views.values())     # (the trainable suffix of the model's flat init)
         model._lr_flat = self._lr_flat
         model._lr_mode = (lvl, self._use_log_init_lr)
         model._dirty = True
@@ -137,6 +141,13 @@ class MetaOptimizer:
         missing = [k for k in self._params if k not in sd]
         if missing:
             raise KeyError(f'missing keys: {missing[:4]}...')
+        if self.model._train_from:
+            # strict `load_state_dict` of the reference module: a checkpoint of the whole network (train_encoder True) does
+            # not load into a frozen-encoder optimizer
+            unexpected = [k for k in sd if k not in self._params]
+            if unexpected:
+                raise RuntimeError(f'Error(s) in loading state_dict for MetaOptimizer: Unexpected key(s) in state_dict: '
+                                   f'{", ".join(repr(k) for k in unexpected[:4])}{", ..." if len(unexpected) > 4 else ""}')
         # The evaluation loop reloads the SAME learned state for every object and every adaptation round
         # (evaluate.py:196,200): when neither the source tensors nor this optimizer's own storage changed since the last
         # load (same storages, same in-place version counters) the 161 MB copy and the engine upload it triggers are skipped.
@@ -158,7 +169,7 @@ class MetaOptimizer:
     def init_zero_grad(self):
         eng = self.model.engine
         dev = eng.device if eng is not None else self.model.device
-        n = self._lr_flat.numel() + (self.model._flat.numel() if self._learn_model_init else 0)
+        n = self._lr_flat.numel() + (self._n_init if self._learn_model_init else 0)
         self._grad_flat = torch.zeros(n, device=dev)
         off = 0
         for p in self._params.values():
@@ -228,10 +239,14 @@ class MetaOptimizer:
         if not getattr(self, '_first_segment', True):
             eng.forward(meta_inputs.contiguous(), want_logits=False)
             return float(eng.loss(loss_func, meta_gts.contiguous().float()))
-        task = torch.zeros(self._lr_flat.numel() + self.model._flat.numel(), device=self._grad_flat.device)
+        n_lr, n_store = self._lr_flat.numel(), eng.n_lr_store
+        task = torch.zeros(n_store + self.model._flat.numel(), device=self._grad_flat.device)
         loss = eng.meta_grad(meta_inputs.contiguous(), meta_gts.contiguous(), task, weight=weight,
                              init_grad=self._learn_model_init)
         if not math.isnan(loss):
-            n = self._grad_flat.numel()             # learn_model_init False: only the lr slice is a Parameter
-            self._grad_flat.add_(task[:n])
+            # the learned tensors are the suffix of each part of the engine's layout (all of it without a frozen encoder);
+            # learn_model_init False: only the lr slice is a Parameter
+            self._grad_flat[:n_lr].add_(task[n_store - n_lr:n_store])
+            if self._learn_model_init:
+                self._grad_flat[n_lr:].add_(task[task.numel() - self._n_init:])
         return loss

@@ -10,7 +10,10 @@ Replaces the reference's worker/main split:
   * outer step         `src/train_meta.py:361-373` (average by meta_batch_size, optional
                        clip, RAdam with per-tensor groups `:110-127`, `clamp_init_lr`)
 The flat state vector is [log_init_lr_* | model_init_*] in `MetaOptimizer.named_parameters()`
-order (`meta_optim.py:65-66,78`), the reference's OIHW layout.
+order (`meta_optim.py:65-66,78`), the reference's OIHW layout.  With a frozen encoder (the engine's
+`train_from`, `train_encoder=False`) it holds the trainable tensors only -- the suffix of each part of the
+engine's layout -- and so do the gradient, the all-reduce and the RAdam moments; the frozen init stays the
+parent's weights.
 """
 import math
 import os
@@ -57,7 +60,25 @@ class MetaTrainer:
         self.wg_budget = int(os.environ.get('EOSVOS_META_WG_BUDGET', CONCURRENT_WG_BUDGET.get(min(len(self.engines), 4), 0)))
         self._apply_wg_budget()
         self.level, self.use_log = lr_hierarchy_level, bool(use_log_init_lr)
-        self.n_lr = engine.lr_store_count(lr_hierarchy_level)        # NotImplementedError for unknown levels
+        self.n_lr_full = engine.lr_store_count(lr_hierarchy_level)   # NotImplementedError for unknown levels
+        # frozen encoder: the learned tensors are tr[nf:] (topology.frozen_tensors); nf = 0 without one
+        self.train_from = int(getattr(engine, 'train_from', 0))
+        tr_all = trainable(engine.encoder)
+        nf = self.train_from
+        self._tr = tr_all[nf:]
+        self.n_param = sum(math.prod(s) for _, s in self._tr) if nf else engine.n_param
+        self._frozen_init = None
+        for e in self.engines[1:]:                 # the extra engines of a frozen-encoder model end their backward where it does
+            if int(getattr(e, 'train_from', 0)) != self.train_from:
+                e.set_trainable_from(self.train_from)
+        if lr_hierarchy_level == 'NEURON':
+            self.n_lr = sum(math.prod(neuron_lr_shape(s)) for _, s in self._tr)
+        elif lr_hierarchy_level == 'TENSOR':
+            self.n_lr = len(self._tr)
+        elif lr_hierarchy_level == 'PARAM':
+            self.n_lr = self.n_param
+        if not nf or lr_hierarchy_level == 'SINGLE':
+            self.n_lr = self.n_lr_full
         engine.set_loss(loss_func)
         self.loss_func = loss_func
         self.dist = dist
@@ -68,7 +89,7 @@ class MetaTrainer:
         # step, not in the state dict.  `freeze_encoder` (train_meta.py:120-121): lr = 0 for every learned tensor whose
         # name contains 'backbone' (log_init_lr_backbone-* and model_init_backbone-*).
         self.learn_model_init, self.freeze_encoder = bool(learn_model_init), bool(freeze_encoder)
-        tr = trainable(engine.encoder)
+        tr = self._tr
         nb = sum(1 for n_, _ in tr if n_.startswith('backbone'))
         assert all(n_.startswith('backbone') for n_, _ in tr[:nb])      # the backbone tensors come first
         self._backbone_param = sum(math.prod(s) for _, s in tr[:nb])
@@ -78,11 +99,11 @@ class MetaTrainer:
             self._backbone_lr = self._backbone_param
         else:
             self._backbone_lr = 0            # one `log_init_lr` Parameter: its name has no 'backbone'
-        n = self.n_lr + engine.n_param
+        n = self.n_lr + self.n_param
         dev = engine.device
         self.state = torch.zeros(n, device=dev)
         self.grad = torch.zeros(n, device=dev)
-        self.task_grad = torch.zeros(n, device=dev)
+        self.task_grad = torch.zeros(self.n_lr_full + engine.n_param, device=dev)    # engine layout (eosvos_meta_grad)
         self.exp_avg = torch.zeros(n, device=dev)
         self.exp_avg_sq = torch.zeros(n, device=dev)
         self.step = 0
@@ -91,7 +112,8 @@ class MetaTrainer:
         # vector holding the init part (learn_model_init) or only the lr state.  The extra engines then READ the first
         # engine's learned init / lr (`eosvos_alias_state`): nothing is uploaded per engine after a step.
         # EOSVOS_NO_FUSED_OUTER=1: the separate RAdam / clamp / zero / upload calls (A/B, and what the CPU stand-in runs).
-        self.fused_outer = (hasattr(engine, 'outer_step') and lr_hierarchy_level == 'NEURON' and
+        # (not with a frozen encoder: the fused step keeps the engine's full layout, the subset goes through eosvos_radam_step)
+        self.fused_outer = (hasattr(engine, 'outer_step') and lr_hierarchy_level == 'NEURON' and not self.train_from and
                             os.environ.get('EOSVOS_NO_FUSED_OUTER', '0') != '1')
         if self.fused_outer:
             for e in self.engines[1:]:
@@ -102,24 +124,26 @@ class MetaTrainer:
         """model_state: reference-style model state dict; lrs: the learned lr state in the reference's
         layout for the hierarchy level (list of per-tensor tensors for NEURON / PARAM, one (G,1) / (1,1)
         tensor for TENSOR / SINGLE; log values with `use_log_init_lr`)."""
-        names = [n for n, _ in trainable(self.eng.encoder)]
+        names = [n for n, _ in self._tr]
         dev = self.eng.device
         lrs = list(lrs) if isinstance(lrs, (list, tuple)) else [lrs]
         self.state[:self.n_lr] = torch.cat([l.reshape(-1).float() for l in lrs]).to(dev)
         self.state[self.n_lr:] = torch.cat([model_state[n].reshape(-1).float() for n in names]).to(dev)
+        frozen = trainable(self.eng.encoder)[:self.train_from]
+        self._frozen_init = (torch.cat([model_state[n].reshape(-1).float() for n, _ in frozen]).to(dev) if frozen else None)
         self._model_state = model_state          # (frozen norm statistics + the init of engines built later for other frame sizes)
         self._drop_pool()
         for e in self.engines:
             with _on_stream(e):
                 e.set_loss(self.loss_func)
                 e.load_model_state(model_state)
-                e.set_lr_state(self.level, self.use_log, self.state[:self.n_lr])
+                e.set_lr_state(self.level, self.use_log, self._engine_lr())
         self._mode_check_pending = True      # the first meta-iteration decides the matrix mode for every rank's engines together
 
     def state_dict(self):
         """`meta_optim_state_dict` of the reference checkpoints (train_meta.py:277-286)."""
         out, off = {}, 0
-        tr = trainable(self.eng.encoder)
+        tr = self._tr
         if self.level in ('SINGLE', 'TENSOR'):              # one `log_init_lr` Parameter, meta_optim.py:27-42
             out['log_init_lr'] = self.state[:self.n_lr].view(self.n_lr, 1)
             off = self.n_lr
@@ -166,14 +190,16 @@ class MetaTrainer:
             if on_gpu:
                 e.stream.wait_stream(eng.stream)
             e.set_loss(self.loss_func)
+            if self.train_from:
+                e.set_trainable_from(self.train_from)
             e.load_model_state(self._model_state)
-            e.set_lr_state(self.level, self.use_log, self.state[:self.n_lr])
+            e.set_lr_state(self.level, self.use_log, self._engine_lr())
             if self.fused_outer:
                 e.alias_state(eng)
             elif getattr(e, 'verify_matrix_mode', None) is not None:
-                e.set_init(self.state[self.n_lr:], verify=False)
+                e.set_init(self._engine_init(), verify=False)
             else:
-                e.set_init(self.state[self.n_lr:])
+                e.set_init(self._engine_init())
             if getattr(e, 'verify_matrix_mode', None) is not None:      # one matrix mode per trainer (the first engine's verdict)
                 e.set_engine_matrix_mode(getattr(eng, '_own_mode', None))
                 e._verify_pending = e._step_check_pending = False
@@ -216,11 +242,32 @@ class MetaTrainer:
             with _on_stream(e):
                 if k and getattr(e, 'stream', None) is not None:
                     e.stream.wait_stream(self.eng.stream)       # the outer step wrote the state on the first engine's stream
-                e.set_lr_state(self.level, self.use_log, self.state[:self.n_lr])
+                e.set_lr_state(self.level, self.use_log, self._engine_lr())
                 if getattr(e, 'verify_matrix_mode', None) is not None:
-                    e.set_init(self.state[self.n_lr:], verify=False)      # one outer step away from a state the guard has seen
+                    e.set_init(self._engine_init(), verify=False)      # one outer step away from a state the guard has seen
                 else:
-                    e.set_init(self.state[self.n_lr:])
+                    e.set_init(self._engine_init())
+
+    def _engine_lr(self):
+        """The lr state in the engine's layout (frozen encoder: the learned lrs are its suffix; the frozen rows are inert)."""
+        lr = self.state[:self.n_lr]
+        if self.n_lr == self.n_lr_full:
+            return lr
+        return torch.cat([torch.zeros(self.n_lr_full - self.n_lr, device=lr.device), lr])
+
+    def _engine_init(self):
+        """The init in the engine's layout: the parent's frozen weights, then the learned ones."""
+        init = self.state[self.n_lr:]
+        return init if self._frozen_init is None else torch.cat([self._frozen_init, init])
+
+    def _add_task(self, tg):
+        """self.grad += the learned part of a task gradient in the engine's layout."""
+        if not self.train_from:
+            self.grad.add_(tg)
+            return
+        nl, nlf = self.n_lr, self.n_lr_full
+        self.grad[:nl].add_(tg[nlf - nl:nlf])
+        self.grad[nl:].add_(tg[tg.numel() - self.n_param:])
 
     # ---- one task ---------------------------------------------------------------------
     def run_task(self, x_train, y_train, x_meta, y_meta, inner_steps=5, bptt_epochs=None, multi_step_bptt_loss=None, eng=None):
@@ -263,7 +310,7 @@ class MetaTrainer:
         if math.isnan(meta_loss):
             self.skipped_tasks += 1
         else:
-            self.grad.add_(self.task_grad)
+            self._add_task(self.task_grad)
         return meta_loss
 
     # ---- one meta-iteration --------------------------------------------------------------
@@ -284,7 +331,7 @@ class MetaTrainer:
         n = len(engines)
         self._apply_wg_budget()
         if len(getattr(self, '_task_grads', [])) < n:
-            self._task_grads = [torch.zeros_like(self.grad) for _ in range(n)]
+            self._task_grads = [torch.zeros_like(self.task_grad) for _ in range(n)]
         losses = []
         for base in range(0, len(tasks), n):
             group = tasks[base:base + n]
@@ -308,7 +355,7 @@ class MetaTrainer:
                 if math.isnan(l):
                     self.skipped_tasks += 1
                 else:
-                    self.grad.add_(tg)
+                    self._add_task(tg)
                 losses.append(l)
         return losses
 

@@ -10,7 +10,10 @@ re-created when the frame size changes (DAVIS 480p frames are not all 854 wide).
 
 Only the mode the fine-tuning loops use is implemented: BatchNorm in eval mode with frozen
 affine (`batch_norm.accum_stats False`, `cfgs/meta.yaml:72-75`) and Dropout off; anything
-else raises NotImplementedError (no silent fallback).
+else raises NotImplementedError (no silent fallback).  `train_encoder=False` (`cfgs/meta.yaml:71`)
+freezes the backbone as the reference does (V3+: all but layer4, `deeplabv3plus.py:144-146`; V3: all of it,
+`deeplabv3.py:53-54`): those tensors report `requires_grad == False` and every engine of the model ends its
+backward pass at the boundary (`eosvos_set_trainable_from`).
 """
 from collections import OrderedDict
 
@@ -18,7 +21,7 @@ import torch
 
 from . import _ffi
 from .engine import Engine
-from .topology import conv_infos, model_state_keys, norm_layers, trainable
+from .topology import conv_infos, frozen_tensors, model_state_keys, norm_layers, trainable, trainable_from
 
 
 class _Param:
@@ -49,8 +52,6 @@ class DeepLabV3Plus:
             raise NotImplementedError('plain DeepLabV3 has no GroupNorm variant (networks/deeplabv3.py)')
         if num_classes != 1:
             raise NotImplementedError('num_classes != 1')
-        if not train_encoder:
-            raise NotImplementedError('train_encoder=False')
         if batch_norm is not None and (batch_norm.get('accum_stats') or batch_norm.get('learn_weight')
                                        or batch_norm.get('learn_bias')):
             raise NotImplementedError('only frozen BatchNorm (accum_stats/learn_* False) is implemented')
@@ -84,7 +85,10 @@ class DeepLabV3Plus:
                 self._norm[p + '.running_mean'] = torch.zeros(c)
                 self._norm[p + '.running_var'] = torch.ones(c)
                 self._norm[p + '.num_batches_tracked'] = torch.zeros((), dtype=torch.long)
-        self._params = OrderedDict((n, _Param(n, v, True)) for n, v in self._views.items())
+        self._train_from = trainable_from(backbone, train_encoder)         # first trainable conv (0: all of them)
+        nf = frozen_tensors(backbone, train_encoder)
+        self._params = OrderedDict((n, _Param(n, v, i >= nf)) for i, (n, v) in enumerate(self._views.items()))
+        self._train_names = self._names[nf:]       # what MetaOptimizer learns (`meta_optim.py:46-78`): the requires_grad tensors
 
     # ---- nn.Module-like surface ---------------------------------------------------------
     def to(self, device):
@@ -219,6 +223,8 @@ class DeepLabV3Plus:
                     cache.clear()
                     self.engine = Engine(self.encoder, height, width, max(batch, self.max_batch), str(self.device), norm=self.norm, **kw)
                 self.engine._built_with_side = want_side
+                if self._train_from:
+                    self.engine.set_trainable_from(self._train_from)
             if getattr(self, 'wg_budget', 0) and hasattr(self.engine, 'set_wg_budget'):
                 self.engine.set_wg_budget(self.wg_budget)
             if not getattr(self, 'side_stream', True) and hasattr(self.engine, 'set_side_stream'):
@@ -277,7 +283,10 @@ class DeepLabV3Plus:
             e.set_norm(cat('.weight'), cat('.bias'), cat('.running_mean'), cat('.running_var'))
         if self._lr_flat is not None:
             level, use_log = getattr(self, '_lr_mode', ('NEURON', False))
-            e.set_lr_state(level, use_log, self._lr_flat)
+            lr = self._lr_flat
+            if self._train_from:          # the learned lrs of the trainable tensors are the suffix of the engine's layout
+                lr = torch.cat([torch.zeros(e.lr_store_count(level) - lr.numel(), dtype=lr.dtype, device=lr.device), lr])
+            e.set_lr_state(level, use_log, lr)
         self._dirty = False
 
     def __call__(self, inputs):

@@ -74,6 +74,21 @@ def trainable(encoder='resnet50'):
     return out
 
 
+def trainable_from(encoder='resnet50', train_encoder=True):
+    """Index (in `conv_infos` order) of the first trainable conv: 0 when the encoder trains, else the first conv of layer4
+    for DeepLabV3+ (`deeplabv3plus.py:144-146`: backbone frozen, layer4 trainable again) and the first ASPP conv for plain
+    DeepLabV3 (`deeplabv3.py:53-54`: the whole backbone frozen).  Convs before it are frozen (`eosvos_set_trainable_from`)."""
+    if train_encoder:
+        return 0
+    names = [c.name for c in conv_infos(encoder)]
+    return names.index('classifier.0.convs.0.0' if is_v3(encoder) else 'backbone.layer4.0.conv1')
+
+
+def frozen_tensors(encoder='resnet50', train_encoder=True):
+    """Number of leading `trainable(encoder)` tensors the boundary freezes (every conv before it has a weight only)."""
+    return trainable_from(encoder, train_encoder)
+
+
 def norm_layers(encoder='resnet50'):
     """[(prefix, channels)] of the 62 (R50) norm layers in module order."""
     return [(c.norm, c.cout) for c in conv_infos(encoder) if c.norm is not None]

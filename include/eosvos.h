@@ -332,6 +332,26 @@ int eosvos_alias_state(eosvos_engine* e, eosvos_engine* src);
  * the lr level / log flag of its aliases. */
 int eosvos_unalias_state(eosvos_engine* e);
 
+/* ---- frozen encoder (`parent_model.train_encoder: False`, cfgs/meta.yaml:71) --------------------------------------------
+ * Convs [0, conv_idx) of the reference order (eosvos_conv_info) are frozen, the rest are trained.  The reference freezes
+ * the backbone except layer4 for DeepLabV3+ (networks/deeplabv3plus.py:144-146: conv_idx = first conv of layer4) and the
+ * whole backbone for DeepLabV3 (networks/deeplabv3.py:53-54: conv_idx = first ASPP conv); 0 trains everything (the
+ * default).  Other values are rejected.  Under a boundary:
+ *  - the backward pass ends at it: no data gradient into a frozen conv's output, no weight gradient of a frozen conv, no
+ *    update of its weights (they keep the value of the last eosvos_set_init / eosvos_set_params);
+ *  - entries that carry model weights keep the full layout: eosvos_set_init, eosvos_get_params, eosvos_set_params,
+ *    eosvos_snapshot_params / eosvos_restore_params;
+ *  - entries that carry learned state keep the full layout too, and the frozen part is inert: eosvos_lr_store_count and
+ *    eosvos_set_lr_state are unchanged (the lr values of frozen tensors are read by nothing), eosvos_meta_grad[_ex] adds
+ *    into the trainable part only (it leaves the frozen lr / init entries of the caller's buffer as they are) and
+ *    eosvos_get_grads writes zeros for the frozen tensors.  The trainable subset -- the reference's
+ *    MetaOptimizer.named_parameters() (meta_optim.py:46-78, meta_model.py:29-60) -- is the SUFFIX of every part of the full
+ *    layout: lr rows / tensors / elements and init elements from the first trainable conv on;
+ *  - eosvos_outer_step fails (the caller keeps the RAdam moments of the subset only: eosvos_radam_step on the suffixes);
+ *  - eosvos_alias_state requires both engines to have the same boundary, and an aliased engine cannot change it.
+ * Call between steps (it synchronises the engine's stream); a backward pass needs a forward made under the boundary. */
+int eosvos_set_trainable_from(eosvos_engine* e, int conv_idx);
+
 /* ---- the exchange step of meta-training over RCCL (SURVEY 8b `allreduce_sum(flat, n, comm)`) ------------------------
  * Replaces the reference's hand-off of per-process gradients into shared CPU tensors (src/util/meta_run.py:237-238) +
  * the main process's sum (src/train_meta.py:361-366) by ONE in-place all-reduce(sum) of the flat meta-gradient
