@@ -32,6 +32,12 @@ round (C3), meta-tasks/s with ONE task per rank (the configs[3] / [4] shape: met
 The timed region is exactly `--steps` steps, run once; `ms_per_step` is its duration / steps.  `--dump-outputs DIR`
 writes what the last timed step computed (`dump_outputs`) as DIR/<name>.npy, read back before anything else runs.
 
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, `--dump-outputs`, the result line
+(headline fields, `config`, and in `extra` the matrix mode, guard log, library version and timed-region sample).
+`--full` also measures everything else the line has carried: `roofline` (its profiled pass and the one-stream engine),
+`cpu_baseline`, `configs` and the rest of `extra` (C1 / C3 shapes, the meta metric beside the fine-tune one, the other
+matrix modes, 3 objects in flight, GroupNorm mode); `--no-cpu-baseline` / `--no-meta` / `--no-ab` leave parts of that out.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -317,6 +323,27 @@ def bench_meta(a, eng, dist, rank, world, sd, lrs, x, y, xg, yg, barrier, dev, m
                                       'state_sample': param_sample(mt.state)})
     if mode_of(mt.eng, engine_mod) != mode:
         raise SystemExit(f'bench.py: the matrix mode changed inside the timed region ({mode} -> {mode_of(mt.eng, engine_mod)})')
+    head = {
+        'metric': 'meta_tasks_per_sec', 'value': world * tpr * a.steps / dt, 'unit': 'meta_tasks/s', 'n_gpus': world,
+        'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': ms_per_step, 'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None, 'dtype': dtype_name(mode), 'data': 'synthetic',
+        'config': {'workload': f'meta-train iteration (BASELINE configs[3..4]): meta_batch_size = {tpr} x ranks, {tpr} tasks per '
+                               f'rank in flight together (one engine each), a task = 5 inner fine-tune steps + 1 meta frame at '
+                               f'batch 1, {H}x{W}, BCE; one all-reduce(sum) of the 40.3 M-float meta-gradient, RAdam + lr clamp '
+                               'on every rank',
+                   'meta_batch_size': world * tpr, 'tasks_per_rank': tpr, 'inner_steps': 5, 'height': H, 'width': W,
+                   'parallelism': f'tasks sharded x{world}'},
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(dict(head, extra={'matrix_mode': mode, 'guard_log': [list(g) for g in engine_mod.GUARD_LOG],
+                                               'lib_version': lib_version, 'timed_region_samples_s': samples})), flush=True)
+        for e in extra:
+            e.close()
+        eng.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     mt.profile = {}
     for _ in range(2):
         step()                                                                  # all-reduce / outer-step split (drains the GPU per phase)
@@ -330,20 +357,9 @@ def bench_meta(a, eng, dist, rank, world, sd, lrs, x, y, xg, yg, barrier, dev, m
     for e in extra:
         e.close()
     if rank == 0:
-        out = {
-            'metric': 'meta_tasks_per_sec', 'value': world * tpr * a.steps / dt, 'unit': 'meta_tasks/s', 'n_gpus': world,
-            'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': ms_per_step, 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': dtype_name(mode), 'data': 'synthetic',
-            'config': {'workload': f'meta-train iteration (BASELINE configs[3..4]): meta_batch_size = {tpr} x ranks, {tpr} tasks per '
-                                   f'rank in flight together (one engine each), a task = 5 inner fine-tune steps + 1 meta frame at '
-                                   f'batch 1, {H}x{W}, BCE; one all-reduce(sum) of the 40.3 M-float meta-gradient, RAdam + lr clamp '
-                                   'on every rank',
-                       'meta_batch_size': world * tpr, 'tasks_per_rank': tpr, 'inner_steps': 5, 'height': H, 'width': W,
-                       'parallelism': f'tasks sharded x{world}'},
-            'roofline': roof, 'cpu_baseline': cpu,
-            'extra': {'last_meta_loss': losses[-1], 'matrix_mode': mode, 'guard_log': [list(g) for g in engine_mod.GUARD_LOG], 'lib_version': lib_version,
-                      'timed_region_samples_s': samples, 'phase_ms_per_meta_iteration': split},
-        }
+        out = dict(head, roofline=roof, cpu_baseline=cpu,
+                   extra={'last_meta_loss': losses[-1], 'matrix_mode': mode, 'guard_log': [list(g) for g in engine_mod.GUARD_LOG],
+                          'lib_version': lib_version, 'timed_region_samples_s': samples, 'phase_ms_per_meta_iteration': split})
         print(json.dumps(out), flush=True)
     eng.close()
     if dist is not None:
@@ -361,9 +377,12 @@ def main(argv=None, engine_factory=None, device=None, backend='nccl'):
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed step computed to DIR/<name>.npy (fine-tune: loss, logits and a fixed sample '
                          'of the updated weights; meta: the meta losses and a fixed sample of the learned state)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-meta', action='store_true')
-    ap.add_argument('--no-ab', action='store_true', help='skip the fp32-MFMA-mode comparison in extra')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also measure the roofline, CPU baseline, other shapes, modes and configurations '
+                         '(a plain run does only set-up, warm-up, the timed steps, --dump-outputs and the result line)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-meta', action='store_true', help='--full: skip the meta metric in extra')
+    ap.add_argument('--no-ab', action='store_true', help='--full: skip the other matrix modes and engine configurations in extra')
     ap.add_argument('--tasks-per-rank', type=int, default=4,
                     help='meta metric: tasks per GPU per meta-iteration, run concurrently on one engine each (default 4: '
                          'measured 26.8 / 31.0 / 34.2 / 34.2 tasks/s with 1 / 3 / 4 / 6 in flight)')
@@ -434,10 +453,28 @@ def main(argv=None, engine_factory=None, device=None, backend='nccl'):
         # what the last timed step computed: its loss, the logits of its forward pass and the weights after its update
         dump_outputs(a.dump_outputs, {'loss': eng.last_loss(), 'logits': eng.debug_tensor('logits'),
                                       'params_sample': param_sample(eng.get_params())})
-    last_loss = eng.finetune_step(xg, yg)           # sanity: still finite after K steps
+    if a.full:
+        last_loss = eng.finetune_step(xg, yg)       # sanity: still finite after K steps
     if mode_of(eng, engine_mod) != mode or list(engine_mod.GUARD_LOG) != guard_log0:
         raise SystemExit(f'bench.py: the matrix mode changed inside the timed region ({mode} -> {mode_of(eng, engine_mod)}, guard log '
                          f'{engine_mod.GUARD_LOG}): the line would name a mode it did not time')
+    head = {
+        'metric': 'finetune_iters_per_sec', 'value': value, 'unit': 'finetune_iters/s', 'n_gpus': world,
+        'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': ms_per_step, 'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None, 'dtype': dtype_name(mode), 'data': 'synthetic',
+        'config': {'workload': 'e-OSVOS-50 fine-tune iteration (BASELINE configs[1]): DeepLabV3+-ResNet50, '
+                               f'batch {BATCH}, {H}x{W}, BCE, per-neuron-lr SGD; one (sequence, object) per rank',
+                   'batch': BATCH, 'height': H, 'width': W, 'parallelism': f'replicas x{world}'},
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(dict(head, extra={'matrix_mode': mode, 'guard_log': [list(g) for g in engine_mod.GUARD_LOG],
+                                               'guard_enabled': engine_mod._guard_enabled(), 'lib_version': lib_version,
+                                               'timed_region_samples_s': samples})), flush=True)
+        eng.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # dominant kernel: the same steps once more with HIP events around every matrix-core launch
     psteps = min(a.steps, 20)
@@ -652,16 +689,7 @@ def main(argv=None, engine_factory=None, device=None, backend='nccl'):
     if mode_of(eng, engine_mod) != mode:
         raise SystemExit(f'bench.py: the headline engine left the matrix mode it was timed in ({mode} -> {mode_of(eng, engine_mod)})')
     if rank == 0:
-        out = {
-            'metric': 'finetune_iters_per_sec', 'value': value, 'unit': 'finetune_iters/s', 'n_gpus': world,
-            'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': ms_per_step, 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': dtype_name(mode), 'data': 'synthetic',
-            'config': {'workload': 'e-OSVOS-50 fine-tune iteration (BASELINE configs[1]): DeepLabV3+-ResNet50, '
-                                   f'batch {BATCH}, {H}x{W}, BCE, per-neuron-lr SGD; one (sequence, object) per rank',
-                       'batch': BATCH, 'height': H, 'width': W, 'parallelism': f'replicas x{world}'},
-            'roofline': roofline, 'cpu_baseline': cpu, 'configs': configs, 'extra': extra,
-        }
-        print(json.dumps(out), flush=True)
+        print(json.dumps(dict(head, roofline=roofline, cpu_baseline=cpu, configs=configs, extra=extra)), flush=True)
     eng.close()
     if dist is not None:
         dist.destroy_process_group()

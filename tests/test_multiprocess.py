@@ -124,6 +124,47 @@ def test_bench_dump_outputs_of_the_last_timed_step(tmp_path, monkeypatch, metric
         assert set(runs[0]) == {'meta_losses', 'state_sample'} and runs[0]['meta_losses'].shape == (4,)
 
 
+@pytest.mark.parametrize('metric', ['finetune', 'meta'])
+def test_bench_plain_run_measures_only_the_headline(monkeypatch, metric):
+    """Without `--full` (stand-in engine, one process): the warm-up and the timed steps are all that run -- no profiled
+    pass, no CPU baseline, no further engines or shapes -- and the line carries the headline fields only."""
+    import contextlib
+    import importlib.util
+    import io
+
+    from fake_engine import FakeEngine
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
+        monkeypatch.delenv(k, raising=False)
+    spec = importlib.util.spec_from_file_location('bench_under_test4', os.path.join(os.path.dirname(HERE), 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, 'H', 16)
+    monkeypatch.setattr(bench, 'W', 24)
+
+    def refuse(*args, **kwargs):
+        raise AssertionError('a plain run must not measure the CPU baseline')
+    monkeypatch.setattr(bench, 'cpu_baseline_finetune', refuse)
+    monkeypatch.setattr(bench, 'cpu_baseline_meta', refuse)
+    FakeEngine.instances.clear()
+    with contextlib.redirect_stdout(io.StringIO()) as buf:
+        bench.main(['--steps', '3', '--warmup', '2', '--metric', metric], engine_factory=FakeEngine, device='cpu', backend='gloo')
+    line = json.loads(buf.getvalue().strip().splitlines()[-1])
+    assert line['metric'] == ('meta_tasks_per_sec' if metric == 'meta' else 'finetune_iters_per_sec')
+    assert line['steps'] == 3 and line['warmup'] == 2 and line['higher_is_better'] is True and line['dtype'].startswith('f32')
+    per_step = 4 if metric == 'meta' else 1                            # meta: 4 tasks in flight per GPU
+    (dt,) = line['extra']['timed_region_samples_s']
+    assert abs(line['ms_per_step'] - 1e3 * dt / 3) < 1e-9 * line['ms_per_step']
+    assert abs(line['value'] - per_step * 3 / dt) < 1e-6 * line['value']
+    assert not {'roofline', 'cpu_baseline', 'configs'} & set(line)
+    assert set(line['extra']) <= {'matrix_mode', 'guard_log', 'guard_enabled', 'lib_version', 'timed_region_samples_s'}
+    assert all(getattr(e, '_prof', None) is None for e in FakeEngine.instances)      # no profiled pass
+    if metric == 'finetune':
+        (e,) = FakeEngine.instances
+        assert e.log.count('step') == 2 + 3                            # warm-up + timed steps, nothing after them
+    else:
+        assert len(FakeEngine.instances) == 4
+
+
 def test_bench_gpus_flag_must_match_the_world_size(tmp_path):
     """`--gpus N` is the contract, not a hint: a rank started with another WORLD_SIZE refuses to run (and N > 1 without
     WORLD_SIZE self-launches N ranks, which needs N GPUs: here it must fail loudly, there being none)."""

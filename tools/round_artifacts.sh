@@ -6,14 +6,14 @@
 R=${1:-r06}
 O=$PWD/gpurun_out/$R; mkdir -p $O
 export TMPDIR=/tmp
-python3 bench.py --steps 20 --no-cpu-baseline --no-meta --no-ab > $O/bench_quick.json 2> $O/bench_quick.err
+python3 bench.py --full --steps 20 --no-cpu-baseline --no-meta --no-ab > $O/bench_quick.json 2> $O/bench_quick.err
 K=$(python3 -c "import json;print(json.load(open('$O/bench_quick.json'))['roofline']['kernel'])")
 echo "dominant kernel: $K"
 tools/pmc_dominant.sh $R "$K" 3
 cp $O/pmc_dominant_kernel.json profiles/${R}_pmc_dominant_kernel.json
-python3 bench.py > $O/bench_b3.json 2> $O/bench.err; tail -c 400 $O/bench_b3.json
-python3 bench.py --metric meta > $O/bench_meta_b1.json 2> $O/bench_meta.err; tail -c 300 $O/bench_meta_b1.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --no-cpu-baseline --no-meta --no-ab > $O/prof_bench.json 2> $O/prof.err
+python3 bench.py --full > $O/bench_b3.json 2> $O/bench.err; tail -c 400 $O/bench_b3.json
+python3 bench.py --full --metric meta > $O/bench_meta_b1.json 2> $O/bench_meta.err; tail -c 300 $O/bench_meta_b1.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --full --no-cpu-baseline --no-meta --no-ab > $O/prof_bench.json 2> $O/prof.err
 find $O/prof -name '*kernel_stats.csv' | head -1 | xargs -I{} cp {} $O/bench_b3_kernel_stats.csv
 head -6 $O/bench_b3_kernel_stats.csv
 rm -rf $O/prof
