@@ -25,7 +25,6 @@ _SIGNATURES = {
     'eosvos_get_engine_matrix_mode': (ctypes.c_int, [_E]),
     'eosvos_set_wg_budget': (ctypes.c_int, [_E, ctypes.c_int]),
     'eosvos_set_side_stream': (ctypes.c_int, [_E, ctypes.c_int]),
-    'eosvos_set_launch_budget': (ctypes.c_int, [_E, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     'eosvos_num_convs': (ctypes.c_int, [ctypes.c_int]),
     'eosvos_conv_info': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     'eosvos_param_count': (ctypes.c_int64, [ctypes.c_int]),
@@ -118,7 +117,6 @@ _SIGNATURES = {
                               [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, c_float_p, ctypes.c_int] + [c_float_p] * 4 +
                               [ctypes.c_int]),
     'eosvos_test_head': (ctypes.c_int, [_E, c_float_p, c_float_p, c_float_p, ctypes.c_int64, ctypes.c_int] + [c_float_p] * 4),
-    'eosvos_test_conv_presplit': (ctypes.c_int, [c_float_p] * 9 + [ctypes.c_int] * 10 + [ctypes.c_void_p]),
     'eosvos_test_wgrad_presplit': (ctypes.c_int, [c_float_p] * 8 + [ctypes.c_int] * 15 + [ctypes.c_void_p]),
 }
 

@@ -2399,7 +2399,7 @@ const char* const kProfNames[] = {
     "conv_h3_multi_kernel", "conv_x6_multi_kernel", "conv1x1_stream_kernel<*, 128>", "conv1x1_stream_kernel<*, 64>",
     "conv3x3_stream_kernel",
     // pre-split operand path (presplit_kernels.hip), indices kProfPresplit0 ...
-    "wgrad_p_kernel<256, 256>", "wgrad_p_group_kernel<256, 256>", "conv_p_kernel<256, false>", "conv_p_kernel<256, true>"};
+    "wgrad_p_kernel<256, 256>", "wgrad_p_group_kernel<256, 256>"};
 constexpr int kProfKernels = sizeof(kProfNames) / sizeof(kProfNames[0]);
 hipEvent_t prof_event() {
   if (!g_prof_pool.empty()) { hipEvent_t e = g_prof_pool.back(); g_prof_pool.pop_back(); return e; }
@@ -2486,14 +2486,13 @@ static int conv_wg_budget(int requested) {
 int conv_wg_budget_of(int requested) { return conv_wg_budget(requested); }
 #define CONV_MAX_WG_DEEP (256 * 3)
 #define EOSVOS_MINK 3      // K steps a streamed workgroup takes at least
-// (1024: the pre-split 256 x 256 kernel parks up to 1024 partial 128 x 128 tiles, launch_conv_p)
-int64_t conv_ws_floats() { return (int64_t)(CONV_MAX_WG_DEEP > 1024 ? CONV_MAX_WG_DEEP : 1024) * 2 * 128 * 128; }
-// the fix-up pass of a uniform split-K launch whose partial tiles another kernel parked (presplit_kernels.hip): a.splitk chunks
-void launch_conv_fixup_splitk(const ConvArgs& a, hipStream_t s) {
-  const long tiles = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-  ProfScope ps(16, 0.0, s);
-  hipLaunchKernelGGL((conv_fixup_kernel<128>), dim3((unsigned)tiles, 8), dim3(256), 0, s, a);
-}
+// ConvArgs::ws: workgroup bid < nwg of a launch parks at most two BM x BN <= 128 x 128 partial tiles, ws[2 bid] and
+// ws[2 bid + 1] (conv_igemm_kernel, conv_xs_body).  conv_plan starts from CONV_MAX_WG_DEEP workgroups (deep kernels) or the
+// budget (<= CONV_MAX_WG), and no branch raises nwg above that start: whole tiles per workgroup take ceil(tiles / q) with
+// tiles < q x start, or one per tile when tiles < start; streamed launches only lower it; uniform split-K takes
+// tiles x (budget / tiles).
+static_assert(CONV_MAX_WG <= CONV_MAX_WG_DEEP, "conv_ws_floats");
+int64_t conv_ws_floats() { return (int64_t)CONV_MAX_WG_DEEP * 2 * 128 * 128; }
 
 // returns the number of workgroups; fills a.dp_q / a.per / a.nwg.
 //   tiles >= 512: each workgroup takes dp_q = tiles/512 whole tiles (no workspace traffic) and

@@ -254,14 +254,6 @@ struct eosvos_engine {
   std::map<int, MultiTab> aspp_multi;
   OuterEnt* outer_tab = nullptr;      // eosvos_outer_step: device table of the trainable tensors
   int outer_blocks = 0;
-  // per-launch workgroup budgets found by Engine.autotune (eosvos_set_launch_budget): (conv, kind 0 fwd / 1 dgrad / 2 wgrad,
-  // batch) -> budget; consulted only while the engine plans for the whole chip (wg_budget == 0)
-  std::map<long, int> tuned_budget;
-  int budget_for(int ci, int kind, int B) const {
-    if (wg_budget != 0 || tuned_budget.empty()) return wg_budget;
-    auto it = tuned_budget.find(((long)ci * 4 + kind) * 4096 + B);
-    return it == tuned_budget.end() ? wg_budget : it->second;
-  }
   // eosvos_alias_state: this engine reads `alias_src`'s learned init / per-neuron lr (own_* keep its own buffers for
   // eosvos_unalias_state and for the day the source goes first); `aliased_by` = the engines that read THIS engine's
   eosvos_engine* alias_src = nullptr;
@@ -605,7 +597,6 @@ void attach_tap_table(eosvos_engine* e, int ci, int kind, int B, ConvArgs& a) {
   a.par = s2_dgrad ? 1 : 0;
 }
 
-int ksteps_of(int T, int kc) { return T * ((kc + 31) / 32); }
 // EOSVOS_TRACE=1: one stderr line per MFMA launch (joined with rocprofv3's kernel trace by
 // tools/layer_report.py to get per-layer TFLOP/s)
 bool trace_on() {
@@ -702,7 +693,7 @@ void conv_fwd(eosvos_engine* e, int ci, const float* x, int ldx, int Hi, int Wi,
   const ConvL& c = e->t.convs[ci];
   ConvArgs a;
   memset(&a, 0, sizeof(a));
-  a.wg_budget = e->budget_for(ci, 0, B);
+  a.wg_budget = e->wg_budget;
   hipStream_t st = side ? e->s2 : e->s;
   a.x = x; a.w = e->W_(ci); a.y = y; a.ws = side ? e->ws_conv2 : e->ws_conv;
   a.B = B; a.Hi = Hi; a.Wi = Wi; a.ldx = ldx; a.Kc = c.cin;
@@ -785,7 +776,7 @@ void conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int 
   const ConvL& c = e->t.convs[ci];
   ConvArgs a;
   memset(&a, 0, sizeof(a));
-  a.wg_budget = e->budget_for(ci, 1, B);
+  a.wg_budget = e->wg_budget;
   if (!gkey) gkey = g;
   if (!gxkey) gxkey = gx;
   if (e->gn() && c.norm) { g = e->zbuf[ci]; ldg = c.cout; gkey = g; }   // gradient w.r.t. the raw conv output (conv_wgrad made it)
@@ -983,9 +974,9 @@ void pair_reset(eosvos_engine* e) {
 // covers every CU makes the main stream's next data gradient wait for whole weight-gradient workgroups to finish, and one that
 // covers too few runs long after the chain has ended.  Measured at batch 3, three interleaved rounds (profiles/r06_ab_log.txt):
 // 100 % 8.89 ms, 88 % 8.75, 75 % 8.67, 63 % 8.65, 50 % 8.75, 25 % 9.37; the register-staged kernels 8.83.
-int wgp_budget(const eosvos_engine* e, int ci, int B) {
+int wgp_budget(const eosvos_engine* e) {
   constexpr int share = 75;          // percent
-  int b = conv_wg_budget_of(e->budget_for(ci, 2, B));
+  int b = conv_wg_budget_of(e->wg_budget);
   if (e->s2) b = conv_clamp_wg_budget(std::max(64, b * share / 100 / 64 * 64));
   return b;
 }
@@ -1080,7 +1071,7 @@ int flush_wgrad_p_group(eosvos_engine* e, int stage, int B) {
   const long key = (((long)stage * 64 + B) * 1024 + e->wg_budget) * 2 + (e->s2 ? 1 : 0);
   auto sp = e->wgp_splits.find(key);
   if (sp == e->wgp_splits.end()) {
-    const int res = wgrad_p_resident(wgp_budget(e, e->wgp_pending[0].ci, B));
+    const int res = wgrad_p_resident(wgp_budget(e));
     long work = 0;
     for (auto& q : e->wgp_pending) work += (long)wgrad_p_tiles(q.a) * ((q.a.B * q.a.Ho * q.a.Wo + 31) / 32);
     long tau = std::max<long>(4, (work + res - 1) / res);
@@ -1261,7 +1252,7 @@ int conv_wgrad(eosvos_engine* e, int ci, const float* g, int ldg, const float* x
     // the 16 / 36 planes already give hundreds of tiles, and every K split parks a full Winograd-domain slab that the finish
     // kernel re-reads: plan the splits for half the workgroup budget (tools/budget_sweep.py: decoder conv at batch 3 247 -> 198 us,
     // batch 1 90 -> 72 us)
-    const int wbud = conv_wg_budget_of(e->budget_for(ci, 2, B)) / 2;
+    const int wbud = conv_wg_budget_of(e->wg_budget) / 2;
     a.splits = wgrad_pick_splits((int)ntile, c.cout, c.cin, wg.np, wbud);
     trace("wgrad", ci, c.cout, (long)c.cin * wg.np, ntile, a.splits);
     const int cin = c.cin, cout = c.cout;
@@ -1330,7 +1321,7 @@ int conv_wgrad(eosvos_engine* e, int ci, const float* g, int ldg, const float* x
         // K chunks (= slabs) and workgroups per tile: one chunk per workgroup, as many as fill the launch's share of the chip
         // (wgrad_p_pick_splits).  The kernel can also walk several chunks per workgroup (WgradPArgs::groups < splits: any K partition
         // with any number of workgroups, bit-identical slabs -- tests/test_gpu_presplit.py).
-        pa.splits = a.splits = wgrad_p_pick_splits(B * Ho * Wo, c.cout, c.cin, c.T(), wgp_budget(e, ci, B));
+        pa.splits = a.splits = wgrad_p_pick_splits(B * Ho * Wo, c.cout, c.cin, c.T(), wgp_budget(e));
         pa.groups = pa.splits;
         trace(cov ? "wgrad_p" : "wgrad", ci, c.cout, (long)c.cin * c.T(), (long)B * Ho * Wo, pa.splits, wgrad_exec_frac(a));
         if (cov) go = [=](hipStream_t ws) { launch_wgrad_p(pa, ws); };
@@ -1343,7 +1334,7 @@ int conv_wgrad(eosvos_engine* e, int ci, const float* g, int ldg, const float* x
       e->wg_pending.push_back({ci, a});
       return -1;
     }
-    a.splits = wgrad_pick_splits(B * a.Ho * a.Wo, c.cout, c.cin, c.T(), e->budget_for(ci, 2, B));
+    a.splits = wgrad_pick_splits(B * a.Ho * a.Wo, c.cout, c.cin, c.T(), e->wg_budget);
     trace("wgrad", ci, c.cout, (long)c.cin * c.T(), (long)B * a.Ho * a.Wo, a.splits, wgrad_exec_frac(a));
     go = [=](hipStream_t ws) { launch_wgrad(a, ws); };
     nslabs = a.splits;
@@ -1553,17 +1544,6 @@ int eosvos_set_wg_budget(eosvos_engine* e, int workgroups) {
   return e->wg_budget;
 }
 
-int eosvos_set_launch_budget(eosvos_engine* e, int conv_idx, int kind, int batch, int workgroups) {
-  if (!e) return fail("null engine");
-  if (conv_idx < 0 || conv_idx >= (int)e->t.convs.size() || kind < 0 || kind > 2 || batch < 1 || batch > e->maxB) return fail("bad launch key");
-  const long key = ((long)conv_idx * 4 + kind) * 4096 + batch;      // (batch < 4096: eosvos_create refuses larger engines' operands anyway)
-  if (batch >= 4096) return fail("bad launch key");
-  if (workgroups < 0) e->tuned_budget.erase(key);
-  else e->tuned_budget[key] = conv_clamp_wg_budget(workgroups);
-  for (auto& tab : e->upd_tab) tab = nullptr;      // weight-gradient split counts follow the budget
-  e->wg_plans.clear();                             // ... and so do the grouped launches' tables
-  return 0;
-}
 static hipError_t create_side_stream(hipStream_t* out) {
   int plo = 0, phi = 0;
   const hipError_t rc = hipDeviceGetStreamPriorityRange(&plo, &phi);       // plo = least, phi = greatest priority
@@ -3375,49 +3355,6 @@ int eosvos_test_wgrad_presplit(const float* g, const float* x, float* ws, void* 
     launch_wgrad(a, s);
     conv_set_thread_mfma_mode(keep);
   }
-  HIPOK(hipGetLastError());
-  return 0;
-}
-
-// Forward conv / data gradient on the pre-split 256 x 256 kernel (presplit_kernels.hip conv_p_kernel), stand-alone.  Stride 1,
-// padding dil * (k / 2).  kmajor 0: x [B][H][W][Cin] -> y [B][H][W][Cout]; kmajor 1: x = the gradient [B][H][W][Cout] -> y [B][H][W][Cin]
-// (times kscale[cout] when given).  w: engine layout [Cout][k*k][Cin].  x2: scratch of x's size; ws: conv_ws_floats() floats; amax:
-// 32 * 2048 zeroed words; sc: 4 floats; zero: 2048 zero bytes.  which: 0 = absmax -> split pass -> kernel + fix-up; 1 = kernel + fix-up
-// only; 2 = the register-staged f16x3 kernels; 4 = without a producer scale (the A operand staged from the fp32 tensor).
-int eosvos_test_conv_presplit(const float* x, const float* w, const float* kscale, float* y, void* x2, float* ws, unsigned* amax,
-                              float* sc, const void* zero, int B, int H, int W, int Cin, int Cout, int k, int dil, int kmajor,
-                              int splits, int which, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!x || !w || !y || !x2 || !ws || !amax || !sc || !zero) return fail("null argument");
-  const int pad = dil * (k / 2), T = k * k;
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.w = w; a.y = y; a.ws = ws;
-  a.B = B; a.Hi = H; a.Wi = W; a.Ho = H; a.Wo = W; a.KH = a.KW = k; a.M = B * H * W; a.wN = Cout; a.wK = Cin;
-  if (!kmajor) { a.ldx = Cin; a.Kc = Cin; a.N = Cout; a.ldy = Cout; a.mul = 1; a.off0 = -pad; a.kstep = dil; }
-  else { a.ldx = Cout; a.Kc = Cout; a.N = Cin; a.ldy = Cin; a.mul = 1; a.off0 = pad; a.kstep = -dil; a.kmajor = 1; a.kscale = kscale; }
-  a.amax_x = amax; a.amax_w = amax + 1; a.amax_ks = kscale ? amax + 2 : nullptr;
-  const long rows = (long)B * H * W;
-  if (which == 0 || which == 2 || which == 4) {
-    launch_absmax(x, rows, a.ldx, a.ldx, amax + 0, s);
-    launch_absmax(w, (long)Cout * T, Cin, Cin, amax + 1, s);
-    if (kscale) launch_absmax(kscale, 1, Cout, Cout, amax + 2, s);
-  }
-  if (which == 0) launch_pair_split(x, x2, rows, a.ldx, a.ldx, amax + 0, 0, sc + 0, s);
-  const int keep = conv_thread_mfma_mode();
-  conv_set_thread_mfma_mode(2);
-  if (which == 2) {
-    launch_conv(a, s);
-  } else {
-    if (!conv_p_supported(a)) { conv_set_thread_mfma_mode(keep); return fail("conv_p: unsupported shape"); }
-    ConvPExtra q;
-    q.x2 = (const unsigned char*)x2; q.scp_x = sc; q.zero = (const unsigned char*)zero;
-    q.splits = splits > 0 ? splits : conv_p_pick_splits(a);
-    if (q.splits < 1) { conv_set_thread_mfma_mode(keep); return fail("conv_p: the launch is too small for the 256 x 256 kernel"); }
-    if (which == 4) HIPOK(hipMemsetAsync(sc, 0, 16, s));
-    launch_conv_p(a, q, s);
-  }
-  conv_set_thread_mfma_mode(keep);
   HIPOK(hipGetLastError());
   return 0;
 }

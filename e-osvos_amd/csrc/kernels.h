@@ -186,7 +186,7 @@ void conv_prof_enable(int on);
 int conv_prof_read(int max, const char** names, long* counts, double* ms, double* flops);
 void conv_prof_mark_begin(int kernel, double flops, hipStream_t s);   // launchers outside conv_kernels.hip; kernel = index into the name table
 void conv_prof_mark_end(hipStream_t s);
-enum { kProfPresplit0 = 38 };    // first pre-split kernel in the name table: wgrad_p, wgrad_p_group, conv_p fwd, conv_p dgrad
+enum { kProfPresplit0 = 38 };    // first pre-split kernel in the name table: wgrad_p, wgrad_p_group
 double conv_exec_frac(const struct ConvArgs& a);
 double wgrad_exec_frac(const struct WgradArgs& a);
 int conv_mfma_mode();                // 1: bf16x6 split kernels (default), 0: fp32 MFMA kernels (EOSVOS_MFMA=f32), 2: f16x3 (EOSVOS_MFMA=f16x3)
@@ -199,7 +199,6 @@ void launch_absmax_segments(const float* base, const long* dev_off, const int* d
 // calibration: back-to-back fp32 MFMAs, returns the FLOPs the launch performs
 double launch_mfma_probe(float* scratch, int iters, hipStream_t s);
 int64_t conv_ws_floats();
-void launch_conv_fixup_splitk(const ConvArgs& a, hipStream_t s);
 }  // namespace eosvos
 #include <vector>
 namespace eosvos {
@@ -262,19 +261,6 @@ struct WgradPArgs {
   const float* g; const float* x;
 };
 #define PAIR_HEADROOM 10      // spare bits a producer's scale may have over the tensor's absmax before the operand is re-split
-// Forward conv / data gradient on 256 x 256 tiles: the gathered operand (activation / gradient rows) comes from its pair8
-// sibling by LDS-DMA, the weights are staged through registers with the split done on the fly (they are shared by every row
-// tile and stay in L2; no sibling of the weights has to be maintained).  K is split `splits` ways; the partial tiles are parked
-// in conv_fixup_kernel's slab layout and that kernel applies the epilogue (ConvArgs::splitk).
-struct ConvPExtra {
-  const unsigned char* x2;   // pair8 sibling of ConvArgs::x (same view, same addressing)
-  const float* scp_x;        // the scale its producer used (checked against ConvArgs::amax_x; misfit: staged from ConvArgs::x)
-  const unsigned char* zero; // >= 2 KB of zero bytes
-  int splits;
-};
-bool conv_p_supported(const ConvArgs& a);
-int conv_p_pick_splits(const ConvArgs& a);          // 0: the launch is too small / too short for the 256 x 256 kernel
-void launch_conv_p(ConvArgs& a, const ConvPExtra& q, hipStream_t s);
 bool wgrad_p_supported(const WgradPArgs& a);
 int wgrad_p_tiles(const WgradPArgs& a);
 void launch_wgrad_p(const WgradPArgs& a, hipStream_t s);

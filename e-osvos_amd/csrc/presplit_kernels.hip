@@ -102,10 +102,6 @@ __device__ __forceinline__ void p_glds16(const unsigned char* sbase, unsigned vo
 __device__ __forceinline__ unsigned p_lds_addr(const void* p) {
   return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) const char*)p);
 }
-// fragment of a row-major image: 8 consecutive k of one row = one 16-byte chunk
-__device__ __forceinline__ pf16x8 p_lds_frag(unsigned addr) {
-  return *(__attribute__((address_space(3))) const pf16x8*)(size_t)addr;
-}
 // fragment of a K-major [pixel][channel] image: 8 k of one channel per lane = two transposed reads 4 pixel rows apart
 __device__ __forceinline__ pf16x8 p_tr_frag(unsigned addr, int rowb) {
   const ph4 a = __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) ph4*)addr);
@@ -325,293 +321,6 @@ __global__ __launch_bounds__(512, 1) void wgrad_p_group_kernel(const WgradPArgs*
   const int ent = __builtin_amdgcn_readfirstlane(m.x), bid = __builtin_amdgcn_readfirstlane(m.y);
   const WgradPArgs p = tab[ent];
   wgrad_p_body<BM, BN>(p, bid, smem);
-}
-
-// ---- forward conv / data gradient on 256 x 256 tiles ------------------------------------------------------------------------------
-// out[m][n] = sum_{tap, k} A[src(m, tap)][k] * Wt[(tap, k)][n]   (ConvArgs semantics, conv_xs_body of conv_kernels.hip; the
-// contraction of `/root/reference/src/networks/deeplabv3plus.py:32-53`'s convs and of their autograd data gradient).
-//   A: pair8 sibling of the gather source, LDS-DMA: an instruction copies 8 rows x 128 B (32 channels: 4 x [hi8 | lo8]); lane l
-//      -> tile row 8 i + l / 8, 16-byte chunk (l % 8) ^ ((row >> 1) & 7) (bank swizzle on the source address); rows whose source
-//      pixel lies in the padding (or past M) read a page of zeros.  Fragments by ds_read_b128.
-//   B: the fp32 weights through registers, split on the fly under their fresh absmax scale (one K step ahead): n-major
-//      (forward: W[n][tap][k] rows, the A image layout) or k-major (data gradient: W[k][tap][n] rows times the frozen-norm
-//      scale a[k], the [k][channel] image of wgrad_p_body read by ds_read_b64_tr_b16).
-//   K units = (taps that touch the image for at least one row of the tile) x (Kc / 32), split p.splitk ways (workgroup b =
-//   chunk * tiles + tile); the 128 x 128 quarters of a chunk's tile are parked where conv_fixup_kernel<128> expects the slabs
-//   of a uniform split-K launch, and that kernel sums them in chunk order and applies the epilogue.
-template <bool KMAJOR>
-__global__ __launch_bounds__(512, 1) void conv_p_kernel(const ConvArgs p, const ConvPExtra q) {
-  constexpr int STAGE = 65536, A_BYTES = 32768;
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * STAGE];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;                    // 2 x 4 waves of 128 (rows) x 64 (columns)
-  const int T = p.KH * p.KW;
-  const int nt = p.N >> 8, mtl = (p.M + 255) >> 8;
-  const int tiles = mtl * nt;
-  const int bid = p_xcd_remap(blockIdx.x, gridDim.x);
-  const int chunk = bid / tiles, tile = bid - chunk * tiles;
-  const int m0 = (tile / nt) << 8, n0 = (tile % nt) << 8;
-  const int kcs = p.Kc >> 5;                                  // K steps per tap
-
-  // scales: A -- the producer's (stale) scale checked against this iteration's absmax; B -- fresh, as conv_xs_body
-  const unsigned mx = amax_read(p.amax_x);
-  float sa = *q.scp_x;
-  const bool oka = pair_scale_fits(mx, sa);
-  if (!oka) sa = pair_scale_of(mx, 0);
-  float mw = __uint_as_float(amax_read(p.amax_w));
-  if (KMAJOR && p.kscale) mw *= __uint_as_float(amax_read(p.amax_ks));
-  const float sb = pair_scale_of(__float_as_uint(mw), 0);
-  const float inv = 1.0f / (sa * sb);
-
-  // gather rows of this lane's 4 DMA slots: tile row r_j = 8 (4 wave + j) + lane / 8
-  const int hwo = p.Ho * p.Wo;
-  long abase[4];                                             // byte offset of the row's source pixel at tap (0, 0) + its chunk
-  unsigned vmask[4];                                         // bit t: tap t reads inside the image
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int r = 8 * (4 * wave + j) + (lane >> 3);
-    const int m = m0 + r;
-    const int c = (lane & 7) ^ ((r >> 1) & 7);
-    unsigned vm = 0;
-    long pix0 = 0;
-    if (m < p.M) {
-      const int b = m / hwo, rem = m - b * hwo;
-      const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-      const int sy0 = oy * p.mul + p.off0, sx0 = ox * p.mul + p.off0;
-      pix0 = ((long)b * p.Hi + sy0) * p.Wi + sx0;
-      for (int ky = 0; ky < p.KH; ++ky)
-        for (int kx = 0; kx < p.KW; ++kx) {
-          const int sy = sy0 + ky * p.kstep, sx = sx0 + kx * p.kstep;
-          if ((unsigned)sy < (unsigned)p.Hi && (unsigned)sx < (unsigned)p.Wi) vm |= 1u << (ky * p.KW + kx);
-        }
-    }
-    vmask[j] = vm;
-    abase[j] = pix0 * p.ldx * 4 + c * 16;
-  }
-  // taps that touch the image for at least one row of the tile (the same set in every workgroup of the tile)
-  unsigned* const red = reinterpret_cast<unsigned*>(smem);
-  {
-    const unsigned any = vmask[0] | vmask[1] | vmask[2] | vmask[3];
-    unsigned wv = 0;
-    for (int t = 0; t < T; ++t) wv |= (__builtin_amdgcn_ballot_w64((any >> t) & 1u) != 0ull) ? (1u << t) : 0u;
-    if (lane == 0) red[wave] = wv;
-    __syncthreads();
-  }
-  unsigned tmask = 0;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) tmask |= red[w];
-  tmask = __builtin_amdgcn_readfirstlane(tmask);
-  __syncthreads();
-  unsigned long long tapcode = 0;                            // valid taps, 4 bits each
-  int nv = 0;
-  for (int t = 0; t < T; ++t)
-    if ((tmask >> t) & 1u) { tapcode |= (unsigned long long)t << (4 * nv); ++nv; }
-  const int U = nv * kcs;
-  const int u0 = (int)(((long)U * chunk) / p.splitk), u1 = (int)(((long)U * (chunk + 1)) / p.splitk);
-
-  const unsigned lds0 = p_lds_addr(smem);
-  auto unit_tap = [&](int u, int& kc) { const int vi = u / kcs; kc = u - vi * kcs; return (int)((tapcode >> (4 * vi)) & 15ull); };
-  // A: DMA of unit u into stage buf (or the fp32 path when the producer's scale does not fit)
-  auto issueA = [&](int u, int buf) {
-    int kc;
-    const int tap = unit_tap(u, kc);
-    const int ky = tap / p.KW, kx = tap - ky * p.KW;
-    const long toff = ((long)(ky * p.kstep) * p.Wi + kx * p.kstep) * p.ldx * 4 + kc * 128;
-    if (oka) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool ok = (vmask[j] >> tap) & 1u;
-        const unsigned char* src = ok ? q.x2 + abase[j] + toff : q.zero + (lane & 7) * 16;
-        unsigned keep;
-        const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + buf * STAGE + (4 * wave + j) * 1024);
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-      }
-    } else {
-      // 1024 (row, 8-channel group) items, two per thread
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int idx = tid + 512 * i;
-        const int r = idx >> 2, G = idx & 3;
-        const int m = m0 + r;
-        uint4 hi = make_uint4(0u, 0u, 0u, 0u), lo = hi;
-        if (m < p.M) {
-          const int b = m / hwo, rem = m - b * hwo;
-          const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-          const int sy = oy * p.mul + p.off0 + ky * p.kstep, sx = ox * p.mul + p.off0 + kx * p.kstep;
-          if ((unsigned)sy < (unsigned)p.Hi && (unsigned)sx < (unsigned)p.Wi) {
-            const float* a = p.x + (((long)b * p.Hi + sy) * p.Wi + sx) * p.ldx + kc * 32 + 8 * G;
-            p_split8(*reinterpret_cast<const float4*>(a), *reinterpret_cast<const float4*>(a + 4), sa, hi, lo);
-          }
-        }
-        unsigned char* row = smem + buf * STAGE + r * 128;
-        const int sw = (r >> 1) & 7;
-        *reinterpret_cast<uint4*>(row + (((2 * G) ^ sw) << 4)) = hi;
-        *reinterpret_cast<uint4*>(row + (((2 * G + 1) ^ sw) << 4)) = lo;
-      }
-    }
-  };
-  // B: the unit's weights into registers (16 floats per thread), and from registers into stage buf
-  float4 wb[4];
-  auto loadB = [&](int u) {
-    int kc;
-    const int tap = unit_tap(u, kc);
-    const float* src;
-    if (!KMAJOR) src = p.w + ((size_t)(n0 + (tid >> 1)) * T + tap) * p.wK + kc * 32 + 16 * (tid & 1);
-    else src = p.w + ((size_t)(kc * 32 + (tid >> 4)) * T + tap) * p.wK + n0 + 16 * (tid & 15);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) wb[i] = *reinterpret_cast<const float4*>(src + 4 * i);
-  };
-  auto storeB = [&](int u, int buf) {
-    unsigned char* const Bs = smem + buf * STAGE + A_BYTES;
-    if (!KMAJOR) {
-      const int r = tid >> 1, h = tid & 1, sw = (r >> 1) & 7;
-      unsigned char* row = Bs + r * 128;
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        uint4 hi, lo;
-        p_split8(wb[2 * g], wb[2 * g + 1], sb, hi, lo);
-        const int c = 2 * (2 * h + g);
-        *reinterpret_cast<uint4*>(row + ((c ^ sw) << 4)) = hi;
-        *reinterpret_cast<uint4*>(row + (((c + 1) ^ sw) << 4)) = lo;
-      }
-    } else {
-      int kc;
-      (void)unit_tap(u, kc);
-      const int k = tid >> 4, ng = tid & 15;
-      const float a = p.kscale ? p.kscale[kc * 32 + k] : 1.f;
-      const int f = (k & 1) | (((k >> 1) & 1) << 2) | (((k >> 3) & 1) << 3);
-      unsigned char* row = Bs + k * 1024;
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {
-        float4 v0 = wb[2 * g], v1 = wb[2 * g + 1];
-        v0.x *= a; v0.y *= a; v0.z *= a; v0.w *= a; v1.x *= a; v1.y *= a; v1.z *= a; v1.w *= a;
-        uint4 hi, lo;
-        p_split8(v0, v1, sb, hi, lo);
-        const int c = 2 * (2 * ng + g);
-        *reinterpret_cast<uint4*>(row + ((c ^ f) << 4)) = hi;
-        *reinterpret_cast<uint4*>(row + (((c + 1) ^ f) << 4)) = lo;
-      }
-    }
-  };
-
-  // fragment read addresses (stage 0; the stage toggles by XOR with STAGE)
-  const int fr = lane & 15, fq = lane >> 4;
-  unsigned aoff[2], boffr[2], bofft[4][2];
-#pragma unroll
-  for (int pc = 0; pc < 2; ++pc) {
-    const unsigned sw = (unsigned)(((2 * fq + pc) ^ ((fr >> 1) & 7)) << 4);
-    aoff[pc] = lds0 + (unsigned)(wm * 128 + fr) * 128u + sw;
-    boffr[pc] = lds0 + A_BYTES + (unsigned)(wn * 64 + fr) * 128u + sw;
-  }
-  {
-    const int q4 = fr >> 2, pp = fr & 3, h = pp >> 1;
-    const int fl = (q4 & 1) | (((q4 >> 1) & 1) << 2) | ((fq & 1) << 3);
-    const unsigned kbase = (unsigned)((8 * fq + q4) * 1024 + 8 * (pp & 1));
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int pc = 0; pc < 2; ++pc) {
-        const unsigned phys = (unsigned)((((a ^ (fl >> 2)) & 3) << 2) | (h << 1) | (pc ^ (fl & 1)));
-        bofft[a][pc] = lds0 + A_BYTES + kbase + (phys << 4) + (unsigned)wn * 256u;
-      }
-  }
-
-  pf32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.f;
-
-  if (u0 < u1) { issueA(u0, 0); loadB(u0); }
-  for (int u = u0; u < u1; ++u) {
-    const int buf = (u - u0) & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    storeB(u, buf);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (u + 1 < u1) { issueA(u + 1, buf ^ 1); loadB(u + 1); }
-    pf16x8 fb[4][2];
-#pragma unroll
-    for (int tn = 0; tn < 4; ++tn)
-#pragma unroll
-      for (int pc = 0; pc < 2; ++pc) {
-        if (!KMAJOR) fb[tn][pc] = p_lds_frag(boffr[pc] + tn * 2048u);
-        else fb[tn][pc] = p_tr_frag(bofft[tn][pc], 1024);
-      }
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int tm = 0; tm < 8; ++tm) {
-      pf16x8 fa[2];
-#pragma unroll
-      for (int pc = 0; pc < 2; ++pc)
-        fa[pc] = p_lds_frag(aoff[pc] + tm * 2048u);
-#pragma unroll
-      for (int tn = 0; tn < 4; ++tn) {
-        pf32x4 c = acc[tm][tn];
-        c = P_MFMA(fa[1], fb[tn][0], c);                   // smallest terms first (as conv_xs_body)
-        c = P_MFMA(fa[0], fb[tn][1], c);
-        c = P_MFMA(fa[0], fb[tn][0], c);
-        acc[tm][tn] = c;
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-    for (int pc = 0; pc < 2; ++pc) {
-      aoff[pc] ^= (unsigned)STAGE; boffr[pc] ^= (unsigned)STAGE;
-#pragma unroll
-      for (int a = 0; a < 4; ++a) bofft[a][pc] ^= (unsigned)STAGE;
-    }
-  }
-
-  // the chunk's partial tile: four 128 x 128 slabs in conv_fixup_kernel<128>'s layout (ws[(gi * 2 + 0)][128][128], gi = chunk *
-  // tiles128 + tile128).  D row (pixel) = 4 * (lane >> 4) + e, column (channel) = lane & 15.
-  const int mt128 = (p.M + 127) >> 7, nt128 = p.N >> 7;
-  const int tm128 = (m0 >> 7) + wm, tn128 = (n0 >> 7) + (wn >> 1);
-  if (tm128 < mt128) {
-    float* slab = p.ws + ((size_t)chunk * mt128 * nt128 + (size_t)tm128 * nt128 + tn128) * 2 * 16384;
-#pragma unroll
-    for (int tm = 0; tm < 8; ++tm)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float* row = slab + (tm * 16 + 4 * fq + e) * 128 + (wn & 1) * 64 + fr;
-#pragma unroll
-        for (int tn = 0; tn < 4; ++tn) row[tn * 16] = acc[tm][tn][e] * inv;
-      }
-  }
-}
-
-bool conv_p_supported(const ConvArgs& a) {
-  return a.N % 256 == 0 && a.Kc % 32 == 0 && a.ldx % 8 == 0 && a.upshift == 0 && !a.par && !a.dst_up && !a.plane_rows && a.nseg == 0 &&
-         a.KH * a.KW <= 9 && a.wK % 4 == 0;
-}
-// K chunks: one resident round of the 256 one-per-CU workgroups; at least 2 (the epilogue lives in the fix-up pass), at most 16,
-// at least 10 K steps each -- 0 when the launch does not give that
-int conv_p_pick_splits(const ConvArgs& a) {
-  const long tiles = (long)((a.M + 255) / 256) * (a.N / 256);
-  const long units = (long)a.KH * a.KW * (a.Kc / 32);
-  const int res = conv_wg_budget_of(a.wg_budget) / 2;
-  long s = tiles > 0 ? res / tiles : 0;
-  if (s > 16) s = 16;
-  while (s >= 2 && units / s < 10) --s;
-  if (s < 2 || tiles * s * 100 < 70L * res) return 0;
-  const long tiles128 = (long)((a.M + 127) / 128) * (a.N / 128);
-  if (s * tiles128 > 1024) return 0;
-  return (int)s;
-}
-void launch_conv_p(ConvArgs& a, const ConvPExtra& q, hipStream_t s) {
-  const int tiles = ((a.M + 255) / 256) * (a.N / 256);
-  a.splitk = q.splits; a.dp_q = 0; a.per = 0; a.nwg = tiles * q.splits; a.deep = 0;
-  conv_prof_mark_begin(kProfPresplit0 + 2 + (a.kmajor ? 1 : 0), 2.0 * a.M * a.N * a.KH * a.KW * a.Kc * conv_exec_frac(a), s);
-  if (a.kmajor) hipLaunchKernelGGL((conv_p_kernel<true>), dim3(a.nwg), dim3(512), 0, s, a, q);
-  else hipLaunchKernelGGL((conv_p_kernel<false>), dim3(a.nwg), dim3(512), 0, s, a, q);
-  conv_prof_mark_end(s);
-  a.y2_done = a.y2 ? 1 : 0;
-  launch_conv_fixup_splitk(a, s);
 }
 
 bool wgrad_p_supported(const WgradPArgs& a) {

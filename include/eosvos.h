@@ -103,11 +103,6 @@ int eosvos_get_engine_matrix_mode(eosvos_engine* e);
  * No reference counterpart (the reference runs one task per process and lets cuDNN choose). */
 int eosvos_set_wg_budget(eosvos_engine* e, int workgroups);
 
-/* Per-launch override of the workgroup budget (see eosvos_set_wg_budget): the forward (kind 0), data-gradient (1) or
- * weight-gradient (2) launch of conv `conv_idx` at batch size `batch` plans for `workgroups` workgroups (0 = the whole chip,
- * < 0 removes the override) while the engine's own budget is 0.  `Engine.autotune` times every launch under a few budgets
- * and keeps the fastest.  A budget only changes how a reduction is split, i.e. the fp32 summation order. */
-int eosvos_set_launch_budget(eosvos_engine* e, int conv_idx, int kind, int batch, int workgroups);
 /* An engine alone on the GPU runs its weight-gradient launches on a second (side) stream beside the data-gradient chain
  * (on = 1, the default).  Engines that run side by side -- the tasks of a meta-batch in flight on one GPU, the objects of
  * a sequence (evaluate.py:132) -- are better off with ONE queue each (on = 0): the other engines fill the chip, and the
@@ -465,17 +460,6 @@ int eosvos_test_head(eosvos_engine* e, const float* x, const float* w, const flo
 int eosvos_test_wgrad_presplit(const float* g, const float* x, float* ws, void* g2, void* x2, unsigned* amax, float* sc,
                                const void* zero, int B, int Ho, int Wo, int Cout, int Hi, int Wi, int Cin, int k, int stride,
                                int pad, int dil, int splits, int groups, int margin, int which, void* stream);
-
-/* The same for the forward convolution (kmajor 0) and the data gradient (kmajor 1) of one stride-1 convolution with padding
- * dil * (k / 2): conv_p_kernel (presplit_kernels.hip) -- the gathered operand from its fp16-pair sibling by LDS-DMA, the weights
- * through registers -- followed by the split-K fix-up pass.  x: [B][H][W][Cin] (kmajor 1: the gradient [B][H][W][Cout]); w: engine
- * layout [Cout][k*k][Cin]; kscale: per-output-channel factor of the data gradient (frozen-norm scale) or NULL; y: [B][H][W][Cout]
- * ([..][Cin]); x2: scratch of x's size; ws: 1024 * 2 * 128 * 128 floats; amax: 32 * 2048 zeroed words; sc: 4 floats; zero: 2048
- * zero bytes.  splits: K chunks (0: planned).  which: 0 = absmax -> split pass -> kernel; 1 = kernel only; 2 = the register-staged
- * f16x3 kernels; 4 = without a producer scale (operand staged from the fp32 tensor). */
-int eosvos_test_conv_presplit(const float* x, const float* w, const float* kscale, float* y, void* x2, float* ws, unsigned* amax,
-                              float* sc, const void* zero, int B, int H, int W, int Cin, int Cout, int k, int dil, int kmajor,
-                              int splits, int which, void* stream);
 
 #ifdef __cplusplus
 }
