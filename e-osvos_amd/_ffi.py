@@ -105,14 +105,14 @@ _SIGNATURES = {
                              [c_float_p, c_float_p]),
     'eosvos_test_conv_algo': (ctypes.c_int, [_E, ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
                                              ctypes.c_int] + [ctypes.c_int] * 9 + [c_float_p]),
-    'eosvos_test_conv_bwd_algo': (ctypes.c_int, [_E, ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p] +
+    'eosvos_test_conv_bwd_algo': (ctypes.c_int, [_E, ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p] +
                                   [ctypes.c_int] * 9 + [c_float_p, c_float_p]),
     'eosvos_test_groupnorm': (ctypes.c_int, [_E, ctypes.c_int, c_float_p, ctypes.c_int, c_float_p, ctypes.c_int, c_float_p,
                                              c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_float, c_float_p, ctypes.c_int, c_float_p, ctypes.c_void_p,
                                              ctypes.c_int]),
     'eosvos_test_maxpool': (ctypes.c_int, [_E, c_float_p] + [ctypes.c_int] * 4 + [c_float_p, ctypes.c_void_p, c_float_p, c_float_p]),
-    'eosvos_test_resize': (ctypes.c_int, [_E] + [ctypes.c_int] * 7 + [c_float_p, ctypes.c_int] * 5),
+    'eosvos_test_resize': (ctypes.c_int, [_E] + [ctypes.c_int] * 7 + [c_float_p, ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_int]),
     'eosvos_test_aspp_pool': (ctypes.c_int, [_E] + [ctypes.c_int] * 4 + [c_float_p] * 4 + [ctypes.c_int] + [c_float_p] * 3 +
                               [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, c_float_p, ctypes.c_int] + [c_float_p] * 4 +
                               [ctypes.c_int]),

@@ -63,20 +63,6 @@ __device__ __forceinline__ size_t dst_pixel(const ConvArgs& p, int m) {
   return ((size_t)b * p.Hf + (oy << 1)) * p.Wf + (ox << 1);
 }
 
-// ---- fused epilogue on 4 consecutive output channels ---------------------------------------
-__device__ __forceinline__ float4 conv_epilogue4(const ConvArgs& p, float4 v, size_t m, int n) {
-  if (p.scale) { const float4 s = ldg4(p.scale + n); v.x *= s.x; v.y *= s.y; v.z *= s.z; v.w *= s.w; }
-  if (p.bias) { const float4 s = ldg4(p.bias + n); v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w; }
-  if (p.res) { const float4 s = ldg4(p.res + m * p.ldres + n); v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w; }
-  if (p.accum) { const float4 s = ldg4(p.y + m * p.ldy + n); v.x += s.x; v.y += s.y; v.z += s.z; v.w += s.w; }
-  if (p.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-  if (p.mask && n >= p.mask_c0) {
-    const float4 s = ldg4(p.mask + m * p.ldmask + n);
-    v.x = s.x > 0.f ? v.x : 0.f; v.y = s.y > 0.f ? v.y : 0.f; v.z = s.z > 0.f ? v.z : 0.f; v.w = s.w > 0.f ? v.w : 0.f;
-  }
-  return v;
-}
-
 // pre-split operand path: 4 consecutive channels n .. n + 3 of pixel `pix` into the destination's pair8 sibling
 // (presplit_kernels.hip: per 8 channels [8 x fp16 hi | 8 x fp16 lo]; same two pieces as h3_split_pair)
 __device__ __forceinline__ void pair_store4(unsigned char* y2, size_t pix, int ldy, int n, const float4& v, float s) {
@@ -345,7 +331,6 @@ __global__ __launch_bounds__(256, DEEP ? 3 : EOSVOS_OCC) void conv_igemm_kernel(
       if (p.bias) bi = ldg4(p.bias + n);
     }
     const bool use_mask8 = p.mask8 && n >= p.mask_c0;
-    const bool use_mask = !use_mask8 && p.mask && n >= p.mask_c0;
     const bool write_m8 = p.mask8_out && p.relu;
 #pragma unroll
     for (int ep = 0; ep < EPASS; ++ep) {
@@ -373,7 +358,7 @@ __global__ __launch_bounds__(256, DEEP ? 3 : EOSVOS_OCC) void conv_igemm_kernel(
             size_t md[EB];
             bool ok[EB];
             float4 rs[EB], ac[EB];
-            unsigned mk8[EB];                 // ReLU mask bits of the row's 4 channels (from mask bytes, or from the fp32 activation)
+            unsigned mk8[EB];                 // ReLU mask bits of the row's 4 channels
 #pragma unroll
             for (int j = 0; j < EB; ++j) {
               const int m = m0 + trow(c_r + (it0 + j) * CROWS);
@@ -391,9 +376,6 @@ __global__ __launch_bounds__(256, DEEP ? 3 : EOSVOS_OCC) void conv_igemm_kernel(
             if (use_mask8) {
 #pragma unroll
               for (int j = 0; j < EB; ++j) mk8[j] = p.mask8[md[j] * p.ldm8 + (n >> 2)];
-            } else if (use_mask) {
-#pragma unroll
-              for (int j = 0; j < EB; ++j) mk8[j] = relu_bits(ldg4(p.mask + md[j] * p.ldmask + n));
             }
 #pragma unroll
             for (int j = 0; j < EB; ++j) {
@@ -403,7 +385,7 @@ __global__ __launch_bounds__(256, DEEP ? 3 : EOSVOS_OCC) void conv_igemm_kernel(
               if (p.res) { v.x += rs[j].x; v.y += rs[j].y; v.z += rs[j].z; v.w += rs[j].w; }
               if (p.accum) { v.x += ac[j].x; v.y += ac[j].y; v.z += ac[j].z; v.w += ac[j].w; }
               if (p.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-              if (use_mask8 || use_mask) relu_mask8(v, mk8[j]);
+              if (use_mask8) relu_mask8(v, mk8[j]);
               if (ok[j]) {
                 *reinterpret_cast<float4*>(p.y + md[j] * p.ldy + n) = v;
                 if (write_m8) p.mask8_out[md[j] * p.ldm8_out + (n >> 2)] = relu_bits(v);
@@ -455,7 +437,6 @@ __global__ __launch_bounds__(256) void conv_fixup_kernel(const ConvArgs p) {
   if (p.bias) bi = ldg4(p.bias + n);
   const float y2s = p.y2 ? *p.y2_sc : 0.f;       // requested with the other operands, consumed after the slab sums
   const bool use_mask8 = p.mask8 && n >= p.mask_c0;
-  const bool use_mask = !use_mask8 && p.mask && n >= p.mask_c0;
   size_t md[RPB];
   unsigned mk8[RPB];
   bool ok[RPB];
@@ -470,7 +451,6 @@ __global__ __launch_bounds__(256) void conv_fixup_kernel(const ConvArgs p) {
     sum[j] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (p.res) rs[j] = ldg4(p.res + md[j] * p.ldres + n);
     if (p.accum) ac[j] = ldg4(p.y + md[j] * p.ldy + n);
-    if (use_mask) mk8[j] = relu_bits(ldg4(p.mask + md[j] * p.ldmask + n));
     if (use_mask8) mk8[j] = p.mask8[md[j] * p.ldm8 + (n >> 2)];
   }
   for (int g = g0; g <= g1; g += 4) {
@@ -501,7 +481,7 @@ __global__ __launch_bounds__(256) void conv_fixup_kernel(const ConvArgs p) {
     if (p.res) { v.x += rs[j].x; v.y += rs[j].y; v.z += rs[j].z; v.w += rs[j].w; }
     if (p.accum) { v.x += ac[j].x; v.y += ac[j].y; v.z += ac[j].z; v.w += ac[j].w; }
     if (p.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-    if (use_mask8 || use_mask) relu_mask8(v, mk8[j]);
+    if (use_mask8) relu_mask8(v, mk8[j]);
     *reinterpret_cast<float4*>(p.y + md[j] * p.ldy + n) = v;
     if (p.mask8_out && p.relu) p.mask8_out[md[j] * p.ldm8_out + (n >> 2)] = relu_bits(v);
     if (p.y2) pair_store4(p.y2, md[j], p.ldy, n, v, y2s);
@@ -1131,7 +1111,6 @@ __device__ __forceinline__ void conv_xs_body(const ConvArgs& p, unsigned char* s
       if (p.bias) bi = ldg4(p.bias + n);
     }
     const bool use_mask8 = p.mask8 && n >= p.mask_c0;
-    const bool use_mask = !use_mask8 && p.mask && n >= p.mask_c0;
     const bool write_m8 = p.mask8_out && p.relu;
     const float y2s = (NP == 2 && p.y2) ? *p.y2_sc : 0.f;
     {
@@ -1159,7 +1138,7 @@ __device__ __forceinline__ void conv_xs_body(const ConvArgs& p, unsigned char* s
             size_t md[EB];
             bool ok[EB];
             float4 ad[EB];
-            unsigned mk8[EB];                 // ReLU mask bits of the row's 4 channels (from mask bytes, or from the fp32 activation)
+            unsigned mk8[EB];                 // ReLU mask bits of the row's 4 channels
 #pragma unroll
             for (int j = 0; j < EB; ++j) {
               const int m = m0 + c_r + (it0 + j) * CROWS;
@@ -1173,9 +1152,6 @@ __device__ __forceinline__ void conv_xs_body(const ConvArgs& p, unsigned char* s
             if (use_mask8) {
 #pragma unroll
               for (int j = 0; j < EB; ++j) mk8[j] = p.mask8[md[j] * p.ldm8 + (n >> 2)];
-            } else if (use_mask) {
-#pragma unroll
-              for (int j = 0; j < EB; ++j) mk8[j] = relu_bits(ldg4(p.mask + md[j] * p.ldmask + n));
             }
 #pragma unroll
             for (int j = 0; j < EB; ++j) {
@@ -1185,7 +1161,7 @@ __device__ __forceinline__ void conv_xs_body(const ConvArgs& p, unsigned char* s
               if (adp) { v.x += ad[j].x; v.y += ad[j].y; v.z += ad[j].z; v.w += ad[j].w; }
               if (both) { const float4 a2 = ldg4(p.y + md[j] * p.ldy + n); v.x += a2.x; v.y += a2.y; v.z += a2.z; v.w += a2.w; }
               if (p.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-              if (use_mask8 || use_mask) relu_mask8(v, mk8[j]);
+              if (use_mask8) relu_mask8(v, mk8[j]);
               if (ok[j]) {
                 *reinterpret_cast<float4*>(p.y + md[j] * p.ldy + n) = v;
                 if (write_m8) p.mask8_out[md[j] * p.ldm8_out + (n >> 2)] = relu_bits(v);
@@ -1747,7 +1723,6 @@ static bool stream3x3_ok(const ConvArgs& a) {
       a.tprefix || a.mul != 1 || a.M < min_m)
     return false;
   if (a.Kc != 64 || a.N != 64 || a.wK != 64) return false;
-  if (a.mask && !a.mask8) return false;
   if ((a.mask_c0 & 15) || (a.ldx & 3) || (a.ldy & 3)) return false;
   if (a.Hi != a.Ho || a.Wi != a.Wo) return false;
   if (!(a.kstep == 1 || a.kstep == -1) || a.off0 != -a.kstep) return false;      // pad 1, dilation 1 (forward: -1 / +1, data gradient: +1 / -1)
@@ -1774,7 +1749,7 @@ static int stream1x1_nc(const ConvArgs& a) {
     // (one stream): 139 -> 122 us forward, 149 / 153 -> 110 / 113 us data gradients, tail 64 -> 46 us; iteration 9.20 -> 9.07 ms.
     // 64-channel ranges (measured with an A/B switch since removed; they also take K = 304 in the 320 variant) are slower than
     // the tiled kernel: 4 x 36 workgroups per row chunk leave either 56 % of the CUs busy or a second round (195 / 232 us).
-    if (a.mask || a.mask8 || a.res || a.accum || a.scale || a.bias || a.relu || a.kscale || a.amax_y) return 0;
+    if (a.mask8 || a.res || a.accum || a.scale || a.bias || a.relu || a.kscale || a.amax_y) return 0;
     if ((a.ldx & 3) || (a.ldy & 3) || (a.plane_rows & 15)) return 0;
     if (a.Kc != 256 && !(a.Kc == 304 && !a.kmajor)) return 0;
     if (a.N % 128 == 0) return 128;
@@ -1783,7 +1758,6 @@ static int stream1x1_nc(const ConvArgs& a) {
     return 0;
   }
   if (a.Kc != 64 && a.Kc != 128 && a.Kc != 256 && a.Kc != 512) return 0;
-  if (a.mask && !a.mask8) return 0;                   // (the fp32-mask form stays with the tiled kernel)
   if ((a.mask_c0 & 15) || (a.ldx & 3) || (a.ldy & 3) || (a.N & 15)) return 0;
   if (a.Hi != a.Ho || a.Wi != a.Wo) return 0;
   if (a.Kc == 512) return a.N % 64 == 0 && a.N <= 128 ? 64 : 0;     // (weights of 64 channels x 512: 133 KB of LDS)

@@ -320,8 +320,8 @@ struct eosvos_engine {
   static constexpr int TSLOTS = 384;   // per phase
 
   // ReLU masks as bytes (ConvArgs::mask8): one buffer per activation tensor a data gradient masks with, written by the
-  // forward epilogue that applies the ReLU (frozen-BN mode: every producer has the fused write; GroupNorm mode has none and
-  // keeps reading the fp32 activation)
+  // forward pass that applies the ReLU (conv epilogue, fix-up, Winograd output transform, GroupNorm apply pass, pooling
+  // broadcast).  They are the only form of the mask the backward pass reads.
   std::map<const float*, uint8_t*> mask8;
   bool fwd_masks = true;             // false during eosvos_infer: no backward pass will read the masks of this forward
   bool masks_valid = false;          // the mask bytes belong to the activations of the last forward
@@ -769,10 +769,14 @@ void conv_fwd(eosvos_engine* e, int ci, const float* x, int ldx, int Hi, int Wi,
                       a.Ho * a.Wo, c.cout, 1e-5f, relu ? 1 : 0, st, gn ? gn_yslot : nullptr,
                       (relu && e->m8w(ykey)) ? e->m8w(ykey) + (y - ykey) / 4 : nullptr, ldy / 4);
 }
-// gx[B,Hin,Win,cin] (ld ldgx) (+)= dgrad of conv ci applied to g[B,Ho,Wo,cout] (ld ldg)
-void conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int Win, float* gx, int ldgx, int B,
-                bool accum, const float* mask, int ldmask, int mask_c0, const float* add = nullptr, int ldadd = 0,
-                const float* gkey = nullptr, const float* gxkey = nullptr) {
+// gx[B,Hin,Win,cin] (ld ldgx) (+)= dgrad of conv ci applied to g[B,Ho,Wo,cout] (ld ldg), zero in channels >= mask_c0
+// where the ReLU mask of `relu_x` (the forward activation gx is the gradient of: same layout) is clear.  relu_x must
+// have mask bytes (eosvos_engine::mask8); a masked gradient without them is an error, never an unmasked result.
+int conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int Win, float* gx, int ldgx, int B,
+               bool accum, const float* relu_x, int mask_c0, const float* add = nullptr, int ldadd = 0,
+               const float* gkey = nullptr, const float* gxkey = nullptr) {
+  const uint8_t* mask8 = relu_x ? e->m8(relu_x) : nullptr;
+  if (relu_x && !mask8) return fail("internal: a masked data gradient of conv " + std::to_string(ci) + " has no ReLU mask bytes");
   const ConvL& c = e->t.convs[ci];
   ConvArgs a;
   memset(&a, 0, sizeof(a));
@@ -787,9 +791,7 @@ void conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int 
   a.mul = 1; a.off0 = c.pad; a.kstep = -c.dil; a.upshift = c.stride == 2 ? 1 : 0;
   a.M = B * Hin * Win; a.wN = c.cout; a.wK = c.cin; a.kmajor = 1;
   a.kscale = e->A_(ci);
-  a.mask = mask; a.ldmask = ldmask; a.mask_c0 = mask_c0; a.accum = accum ? 1 : 0;
-  const uint8_t* mask8 = mask ? e->m8(mask) : nullptr;      // the byte form of the same mask, when its producer wrote one
-  a.mask8 = mask8; a.ldm8 = ldmask / 4;
+  a.mask8 = mask8; a.ldm8 = ldgx / 4; a.mask_c0 = mask_c0; a.accum = accum ? 1 : 0;
   a.res = add; a.ldres = ldadd;
   const bool wino_dg = !add && wino_on(e, ci, B, Hin, Win);
   if (h3_mode() && !wino_dg && !amax_init(e)) {
@@ -844,12 +846,10 @@ void conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int 
       launch_conv(m, e->s);
     }
     if (wg.tm == 4)
-      launch_wino4_dgrad_output(e->wino_dv, prow, c.cin, B, Hin, Win, th, tw, wg.d, mask, ldmask, mask_c0, accum ? 1 : 0, gx, ldgx, e->s, gxs,
-                                mask8, ldmask / 4);
+      launch_wino4_dgrad_output(e->wino_dv, prow, c.cin, B, Hin, Win, th, tw, wg.d, mask8, a.ldm8, mask_c0, accum ? 1 : 0, gx, ldgx, e->s, gxs);
     else
-      launch_wino_dgrad_output(e->wino_dv, prow, c.cin, B, Hin, Win, th, tw, wg.d, mask, ldmask, mask_c0, accum ? 1 : 0, gx, ldgx, e->s, gxs,
-                               mask8, ldmask / 4);
-    return;
+      launch_wino_dgrad_output(e->wino_dv, prow, c.cin, B, Hin, Win, th, tw, wg.d, mask8, a.ldm8, mask_c0, accum ? 1 : 0, gx, ldgx, e->s, gxs);
+    return 0;
   }
   if (c.k == 1 && c.stride == 2 && !add) {
     // only the even pixels of the finer grid receive a contribution: run the GEMM on the
@@ -867,18 +867,18 @@ void conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int 
     trace("dgrad", ci, a.M, a.N, (long)c.T() * c.cout, conv_plan(a));
     launch_conv(a, e->s);
     b.N = tail; b.w += a.N; b.y += a.N;
-    if (b.mask) { b.mask += a.N; b.mask_c0 = b.mask_c0 > a.N ? b.mask_c0 - a.N : 0; }
-    if (b.mask8) b.mask8 += a.N / 4;
+    if (b.mask8) { b.mask8 += a.N / 4; b.mask_c0 = b.mask_c0 > a.N ? b.mask_c0 - a.N : 0; }
     if (b.res) b.res += a.N;
     trace("dgrad", ci, b.M, b.N, (long)c.T() * c.cout, conv_plan(b));
     launch_conv(b, e->s);
-    return;
+    return 0;
   }
   attach_tap_table(e, ci, 1, B, a);
   pair_attach(e, 1, gxkey, gx, ldgx == c.cin, a);
   trace("dgrad", ci, a.M, a.N, (long)c.T() * c.cout, conv_plan(a), conv_exec_frac(a));
   launch_conv(a, e->s);
   pair_covered(e, 1, gxkey, a);
+  return 0;
 }
 // Weight-gradient launches are queued and forked onto the side stream a few layers at a time: every
 // hipEventRecord / hipStreamWaitEvent pair costs the main stream a ~6 us bubble (measured: 57 gaps per batch-1
@@ -1428,8 +1428,8 @@ bool aspp_dgrad_merged(eosvos_engine* e, int B, float* g_l4, const float* l4) {
   a.mul = 1; a.off0 = 0; a.kstep = 0; a.upshift = 0;
   a.M = B * e->h16 * e->w16; a.wN = 256; a.wK = c0.cin; a.kmajor = 1;
   a.kscale = e->A_(t.aspp[0]);
-  a.mask = l4; a.ldmask = c0.cin; a.mask_c0 = 0; a.accum = 1;
-  a.mask8 = e->m8(l4); a.ldm8 = c0.cin / 4;
+  a.mask8 = e->m8(l4); a.ldm8 = c0.cin / 4; a.mask_c0 = 0; a.accum = 1;
+  if (!a.mask8) return false;                      // (conv_dgrad reports the missing mask bytes)
   a.nseg = 4;
   a.w_floats = 0;
   ConvSegHost segs[4];
@@ -1748,7 +1748,7 @@ int eosvos_create_ex(eosvos_engine** out, int arch, int norm_mode, int height, i
       const int64_t nm = (int64_t)B * f.Hm * f.Wm, no = (int64_t)B * f.Ho * f.Wo;
       ok = ok && m8alloc(f.t1, nm * t.convs[b.c1].cout) && m8alloc(f.t2, no * t.convs[b.c2].cout) && m8alloc(f.out, no * t.convs[b.c3].cout);
     }
-    ok = ok && m8alloc(e->cat, n16 * 1280) && m8alloc(e->dcat, n4 * 304) && m8alloc(e->d1, n4 * 256);
+    ok = ok && m8alloc(e->cat, n16 * 1280) && m8alloc(e->proj, n16 * 256) && m8alloc(e->dcat, n4 * 304) && m8alloc(e->d1, n4 * 256);
     if (!ok) { eosvos_destroy(e); return fail("hipMalloc ReLU mask bytes"); }
   }
   for (int i = 0; i < 4; ++i) track(t.aspp[i], e->h16, e->w16);
@@ -2208,7 +2208,7 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
   const int B = e->lastB;
   if (B < 1 || !e->have_loss_grad) return fail("backward without forward + loss");
   if (accumulate && !e->gsum) return fail("accumulate without eosvos_meta_task_begin");
-  if (!e->mask8.empty() && !e->masks_valid)
+  if (!e->masks_valid)
     return fail("backward after eosvos_infer: an inference forward keeps no ReLU masks (run eosvos_forward / eosvos_finetune_step)");
   plans_match_mode(e);
   PlanScope plan_scope(e, 1);
@@ -2229,7 +2229,7 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     twrite_plain(e, 1, e->g_d1);
     apply_update(e, t.last, chunks, update, accumulate);
     int sp = conv_wgrad(e, t.head3, e->g_d1, 256, e->proj, 256, e->h16, e->w16, B);
-    conv_dgrad(e, t.head3, e->g_d1, 256, e->h16, e->w16, e->g_proj, 256, B, false, e->proj, 256, 0);
+    if (conv_dgrad(e, t.head3, e->g_d1, 256, e->h16, e->w16, e->g_proj, 256, B, false, e->proj, 0)) return 1;
     apply_update(e, t.head3, sp, update, accumulate);
   } else {
   // classifier conv (Cout = 1)
@@ -2242,11 +2242,11 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
   // decoder 3x3 convs
   {
     int sp = conv_wgrad(e, t.dec_b, e->g_d2, 256, e->d1, 256, e->h4, e->w4, B);
-    conv_dgrad(e, t.dec_b, e->g_d2, 256, e->h4, e->w4, e->g_d1, 256, B, false, e->d1, 256, 0);
+    if (conv_dgrad(e, t.dec_b, e->g_d2, 256, e->h4, e->w4, e->g_d1, 256, B, false, e->d1, 0)) return 1;
     apply_update(e, t.dec_b, sp, update, accumulate);
     sp = conv_wgrad(e, t.dec_a, e->g_d1, 256, e->dcat, 304, e->h4, e->w4, B);
     // channels [0,256) of dcat are the (unclamped) upsampled ASPP output: no ReLU mask there
-    conv_dgrad(e, t.dec_a, e->g_d1, 256, e->h4, e->w4, e->g_dcat, 304, B, false, e->dcat, 304, 256);
+    if (conv_dgrad(e, t.dec_a, e->g_d1, 256, e->h4, e->w4, e->g_dcat, 304, B, false, e->dcat, 256)) return 1;
     apply_update(e, t.dec_a, sp, update, accumulate);
   }
   // decoder.conv1 on the low-level feature: raw gradient into g_out of layer1's last block
@@ -2254,17 +2254,18 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     float* g_low_feat = e->bb[t.layer1_last_block].g_out;
     const float* low = e->bb[t.layer1_last_block].out;
     int sp = conv_wgrad(e, t.dec1, e->g_dcat + 256, 304, low, 256, e->h4, e->w4, B, e->g_dcat);
-    if (!frozen)
-      conv_dgrad(e, t.dec1, e->g_dcat + 256, 304, e->h4, e->w4, g_low_feat, 256, B, false, nullptr, 0, 0, nullptr, 0, e->g_dcat);
+    if (!frozen && conv_dgrad(e, t.dec1, e->g_dcat + 256, 304, e->h4, e->w4, g_low_feat, 256, B, false, nullptr, 0, nullptr, 0, e->g_dcat))
+      return 1;
     apply_update(e, t.dec1, sp, update, accumulate);
   }
   // decoder upsample backward (+ ReLU mask of the projection output)
-  launch_resize_bwd(e->g_dcat, 304, e->g_proj, 256, e->proj, 256, B, 256, e->up_h, e->up_w, s, twrite_fused(e, 1, e->g_proj, true));
+  if (!e->m8(e->proj)) return fail("internal: the projection output has no ReLU mask bytes");
+  launch_resize_bwd(e->g_dcat, 304, e->g_proj, 256, e->m8(e->proj), 256 / 4, B, 256, e->up_h, e->up_w, s, twrite_fused(e, 1, e->g_proj, true));
   }
   // ASPP projection
   {
     int sp = conv_wgrad(e, t.project, e->g_proj, 256, e->cat, 1280, e->h16, e->w16, B);
-    conv_dgrad(e, t.project, e->g_proj, 256, e->h16, e->w16, e->g_cat, 1280, B, false, e->cat, 1280, 0);
+    if (conv_dgrad(e, t.project, e->g_proj, 256, e->h16, e->w16, e->g_cat, 1280, B, false, e->cat, 0)) return 1;
     apply_update(e, t.project, sp, update, accumulate);
   }
   float* g_l4 = e->bb.back().g_out;
@@ -2291,8 +2292,9 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     for (int i = 0; i < 4; ++i) sp[i] = conv_wgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, l4, 2048, e->h16, e->w16, B, e->g_cat);
     if (!l4_frozen && !aspp_dgrad_merged(e, B, g_l4, l4)) {
       for (int i = 0; i < 4; ++i)
-        conv_dgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, e->h16, e->w16, g_l4, 2048, B, true, i == 3 ? l4 : nullptr, 2048, 0, nullptr, 0,
-                   e->g_cat);
+        if (conv_dgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, e->h16, e->w16, g_l4, 2048, B, true, i == 3 ? l4 : nullptr, 0, nullptr, 0,
+                       e->g_cat))
+          return 1;
     }
     for (int i = 0; i < 4; ++i) apply_update(e, t.aspp[i], sp[i], update, accumulate);
   }
@@ -2319,10 +2321,10 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     auto& f = e->bb[i];
     const int cmid = t.convs[b.c1].cout, cout = t.convs[b.c3].cout;
     int sp = conv_wgrad(e, b.c3, f.g_out, cout, f.t2, cmid, f.Ho, f.Wo, B);
-    conv_dgrad(e, b.c3, f.g_out, cout, f.Ho, f.Wo, f.g_t2, cmid, B, false, f.t2, cmid, 0);
+    if (conv_dgrad(e, b.c3, f.g_out, cout, f.Ho, f.Wo, f.g_t2, cmid, B, false, f.t2, 0)) return 1;
     apply_update(e, b.c3, sp, update, accumulate);
     sp = conv_wgrad(e, b.c2, f.g_t2, cmid, f.t1, cmid, f.Hm, f.Wm, B);
-    conv_dgrad(e, b.c2, f.g_t2, cmid, f.Hm, f.Wm, f.g_t1, cmid, B, false, f.t1, cmid, 0);
+    if (conv_dgrad(e, b.c2, f.g_t2, cmid, f.Hm, f.Wm, f.g_t1, cmid, B, false, f.t1, 0)) return 1;
     apply_update(e, b.c2, sp, update, accumulate);
     // gradient w.r.t. the block input: conv1 path + identity / downsample path
     const bool is_first_block = i == 0;
@@ -2333,16 +2335,16 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     const bool in_frozen = frozen && b.c1 == e->train_from;
     if (b.ds >= 0) {
       sp = conv_wgrad(e, b.ds, f.g_out, cout, f.xin, f.Cin, f.Hi, f.Wi, B);
-      if (!in_frozen) conv_dgrad(e, b.ds, f.g_out, cout, f.Hi, f.Wi, f.g_xin, f.Cin, B, have, nullptr, 0, 0);
+      if (!in_frozen && conv_dgrad(e, b.ds, f.g_out, cout, f.Hi, f.Wi, f.g_xin, f.Cin, B, have, nullptr, 0)) return 1;
       apply_update(e, b.ds, sp, update, accumulate);
       sp = conv_wgrad(e, b.c1, f.g_t1, cmid, f.xin, f.Cin, f.Hi, f.Wi, B);
-      if (!in_frozen) conv_dgrad(e, b.c1, f.g_t1, cmid, f.Hi, f.Wi, f.g_xin, f.Cin, B, true, inmask, f.Cin, 0);
+      if (!in_frozen && conv_dgrad(e, b.c1, f.g_t1, cmid, f.Hi, f.Wi, f.g_xin, f.Cin, B, true, inmask, 0)) return 1;
       apply_update(e, b.c1, sp, update, accumulate);
     } else {
       // identity path: g_xin = mask * (dgrad_conv1(g_t1) + g_out)
       if (have) return fail("internal: identity block after the low-level tap is unsupported");
       sp = conv_wgrad(e, b.c1, f.g_t1, cmid, f.xin, f.Cin, f.Hi, f.Wi, B);
-      conv_dgrad(e, b.c1, f.g_t1, cmid, f.Hi, f.Wi, f.g_xin, f.Cin, B, false, inmask, f.Cin, 0, f.g_out, cout);
+      if (conv_dgrad(e, b.c1, f.g_t1, cmid, f.Hi, f.Wi, f.g_xin, f.Cin, B, false, inmask, 0, f.g_out, cout)) return 1;
       apply_update(e, b.c1, sp, update, accumulate);
     }
     // first block of a ResNet layer: its data-gradient chain is queued, every operand of the stage's weight gradients
@@ -2997,7 +2999,7 @@ int eosvos_bench_conv(eosvos_engine* e, int ci, int kind, int batch, int reps, f
   const int Ho = conv_out(Hi, c.k, c.stride, c.dil, c.pad), Wo = conv_out(Wi, c.k, c.stride, c.dil, c.pad);
   auto run = [&]() {
     if (kind == 0) conv_fwd(e, ci, x, ldx, Hi, Wi, y, ldy, batch, nullptr, 0, true);
-    else if (kind == 1) conv_dgrad(e, ci, g, ldy, Hi, Wi, gx, ldx, batch, false, x, ldx, 0);
+    else if (kind == 1) (void)conv_dgrad(e, ci, g, ldy, Hi, Wi, gx, ldx, batch, false, e->m8(x) ? x : nullptr, 0);   // (p1 has no bytes)
     else conv_wgrad(e, ci, g, ldy, x, ldx, Hi, Wi, batch);
   };
   hipEvent_t a, b;
@@ -3160,7 +3162,7 @@ int eosvos_test_conv_algo(eosvos_engine* e, int algo, const float* x, const floa
   return 0;
 }
 int eosvos_test_conv_bwd_algo(eosvos_engine* e, int algo, const float* x, const float* w_oihw, const float* g,
-                              const float* scale, const float* mask, int B, int H, int W, int Cin, int Cout, int k, int stride,
+                              const float* scale, const uint8_t* m8, int B, int H, int W, int Cin, int Cout, int k, int stride,
                               int dil, int pad, float* dx, float* dw_oihw) {
   ModeScope mode_scope(e);
   if (!e || !x || !w_oihw || !g || !dx || !dw_oihw) return fail("null argument");
@@ -3176,7 +3178,8 @@ int eosvos_test_conv_bwd_algo(eosvos_engine* e, int algo, const float* x, const 
   if (scale) HIPOK(hipMemcpyAsync(t->na, scale, (size_t)Cout * 4, hipMemcpyDeviceToDevice, t->s));
   // the order of the backward pass: weight gradient first (it makes the shared Winograd-domain dM), then data gradient
   const int nslabs = conv_wgrad(t, 0, g, Cout, x, Cin, H, W, B);
-  conv_dgrad(t, 0, g, Cout, H, W, dx, Cin, B, false, mask, Cin, 0);
+  if (m8) t->mask8[x] = const_cast<uint8_t*>(m8);        // the mask bytes of x, as the forward pass would have left them
+  if (conv_dgrad(t, 0, g, Cout, H, W, dx, Cin, B, false, m8 ? x : nullptr, 0)) return 1;
   float* dw = t->falloc((int64_t)Cout * Cin * T);
   if (!dw) return fail("hipMalloc dw");
   const int64_t n = (int64_t)Cout * Cin * T;
@@ -3250,18 +3253,19 @@ int eosvos_test_maxpool(eosvos_engine* e, const float* x, int B, int H, int W, i
   return 0;
 }
 int eosvos_test_resize(eosvos_engine* e, int align_corners, int hin, int win, int hout, int wout, int B, int C, const float* x,
-                       int ldx, float* y, int ldy, const float* gy, int ldgy, float* gx, int ldgx, const float* mask, int ldmask) {
+                       int ldx, float* y, int ldy, const float* gy, int ldgy, float* gx, int ldgx, const uint8_t* m8, int ldm8) {
   ModeScope mode_scope(e);
   if (!e) return fail("null engine");
   if (hin < 1 || win < 1 || hout < 1 || wout < 1 || B < 1 || C < 1) return fail("bad resize geometry");
   if ((x == nullptr) != (y == nullptr) || (gy == nullptr) != (gx == nullptr)) return fail("x / y and gy / gx go together");
-  if ((x && (ldx < C || ldy < C)) || (gy && (ldgy < C || ldgx < C)) || (mask && ldmask < C)) return fail("bad leading dimension");
+  if ((x && (ldx < C || ldy < C)) || (gy && (ldgy < C || ldgx < C)) || (m8 && ldm8 < C / 4)) return fail("bad leading dimension");
+  if (m8 && C % 4) return fail("a masked resize backward needs C % 4 == 0 (one mask byte per 4 channels)");
   OpScratch sc(e);
   ResizeTab th, tw;
   if (upload_resize(&sc.t, make_resize(hin, hout, align_corners != 0), hin, hout, th)) return 1;
   if (upload_resize(&sc.t, make_resize(win, wout, align_corners != 0), win, wout, tw)) return 1;
   if (x) launch_resize_fwd(x, ldx, y, ldy, B, C, th, tw, e->s);
-  if (gy) launch_resize_bwd(gy, ldgy, gx, ldgx, mask, ldmask, B, C, th, tw, e->s);
+  if (gy) launch_resize_bwd(gy, ldgy, gx, ldgx, m8, ldm8, B, C, th, tw, e->s);
   HIPOK(hipStreamSynchronize(e->s));
   HIPOK(hipGetLastError());
   return 0;

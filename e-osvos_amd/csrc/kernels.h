@@ -93,14 +93,12 @@ struct ConvArgs {
   const float* kscale;  // per-k multiply on A (dgrad: norm a of the conv), may be null
   const float* res;     // fwd: residual added before ReLU; NHWC with ldres
   int ldres;
-  const float* mask;    // dgrad: out = 0 where mask[m][n] <= 0 for n >= mask_c0
-  int ldmask, mask_c0;
   // ReLU masks as bytes: one byte per 4 consecutive channels of a pixel, bit j = (channel 4q + j of the forward activation
   // > 0), ldm8 bytes per pixel (= the tensor's floats per pixel / 4).  The forward epilogue that applies the ReLU writes
-  // them (mask8_out), the data gradient reads them (mask8, used instead of `mask` when set): 1/16 of the fp32 activation
-  // the mask used to be read from.  Pointers carry the same channel offset (/ 4) as the views they describe.
+  // them (mask8_out), the data gradient reads them (mask8: out = 0 where the bit is clear, for n >= mask_c0): 1/16 of the
+  // fp32 activation.  Pointers carry the same channel offset (/ 4) as the views they describe.
   const uint8_t* mask8;
-  int ldm8;
+  int ldm8, mask_c0;
   uint8_t* mask8_out;
   int ldm8_out;
   int relu;
@@ -289,11 +287,11 @@ void launch_wino4_output(const float* M, long prow, int C, int B, int H, int W, 
                          uint8_t* mask8_out = nullptr, int ldm8 = 0);
 void launch_wino4_wgrad_finish(const float* ws, int splits, int Cout, int Cin, float* dst, hipStream_t s);
 void launch_wino4_dgrad_output(const float* dV, long prow, int C, int B, int H, int W, int th, int tw, int dil,
-                               const float* mask, int ldmask, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s, unsigned* amax = nullptr,
-                               const uint8_t* mask8 = nullptr, int ldm8 = 0);   // U = G (rowscale*w) G^T
+                               const uint8_t* mask8, int ldm8, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s,
+                               unsigned* amax = nullptr);   // dX = mask8?(B dV B^T, overlapped)
 void launch_wino_dgrad_output(const float* dV, long prow, int C, int B, int H, int W, int th, int tw, int dil,
-                              const float* mask, int ldmask, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s, unsigned* amax = nullptr,
-                              const uint8_t* mask8 = nullptr, int ldm8 = 0);   // dX = mask?(B dV B^T, overlapped)
+                              const uint8_t* mask8, int ldm8, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s,
+                              unsigned* amax = nullptr);   // dX = mask8?(B dV B^T, overlapped)
 void launch_wino_output(const float* M, long prow, int C, int B, int H, int W, int th, int tw, int dil, const float* scale,
                         const float* bias, int relu, float* y, int ldy, hipStream_t s, unsigned* amax = nullptr,
                         uint8_t* mask8_out = nullptr, int ldm8 = 0);        // y = epilogue(A^T M A)
@@ -342,8 +340,9 @@ struct ResizeTab {
 };
 void launch_resize_fwd(const float* x, int ldx, float* y, int ldy, int B, int C, ResizeTab th,
                        ResizeTab tw, hipStream_t s);
-// gx = (mask? mask>0 : 1) * resize_backward(gy)
-void launch_resize_bwd(const float* gy, int ldgy, float* gx, int ldgx, const float* mask, int ldmask,
+// gx = resize_backward(gy), zero where the ReLU mask byte's bit is clear (m8 / ldm8 as ConvArgs::mask8; C % 4 == 0 only --
+// the 1-channel form takes no mask)
+void launch_resize_bwd(const float* gy, int ldgy, float* gx, int ldgx, const uint8_t* m8, int ldm8,
                        int B, int C, ResizeTab th, ResizeTab tw, hipStream_t s, unsigned* amax = nullptr);   // amax: absmax slot of gx
 
 // ASPP image-pooling branch

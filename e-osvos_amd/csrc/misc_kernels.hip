@@ -483,7 +483,7 @@ void launch_resize_fwd(const float* x, int ldx, float* y, int ldy, int B, int C,
 }
 template <int V>
 __global__ __launch_bounds__(256) void resize_bwd_kernel(const float* __restrict__ gy, int ldgy, float* __restrict__ gx, int ldgx,
-                                  const float* __restrict__ mask, int ldmask, int B, int C, ResizeTab th,
+                                  const uint8_t* __restrict__ m8, int ldm8, int B, int C, ResizeTab th,
                                   ResizeTab tw, unsigned* __restrict__ amax) {
   const int CV = C / V;
   const long n = (long)B * th.in * tw.in * CV;
@@ -541,26 +541,28 @@ __global__ __launch_bounds__(256) void resize_bwd_kernel(const float* __restrict
       }
     }
     float* d = gx + pix * ldgx + cv * V;
-    if (mask) {
-      const float* mk = mask + pix * ldmask + cv * V;
+    if (V == 4 && m8) {
+      // ReLU mask byte of channels cv * 4 .. + 3, addressed through their float offset (= pix * ldm8 + cv): this form
+      // shares the channel offset the gradient's own address holds (one VGPR fewer than indexing by cv)
+      const unsigned bits = m8[(pix * 4 * ldm8 + cv * V) >> 2];
 #pragma unroll
-      for (int j = 0; j < V; ++j) acc[j] = mk[j] > 0.f ? acc[j] : 0.f;
+      for (int j = 0; j < V; ++j) acc[j] = (bits & (1u << j)) ? acc[j] : 0.f;
     }
 #pragma unroll
     for (int j = 0; j < V; ++j) { d[j] = acc[j]; const unsigned q = amax_f1(acc[j]); am = am > q ? am : q; }
   }
   if (amax) amax_block_commit(am, amax);
 }
-void launch_resize_bwd(const float* gy, int ldgy, float* gx, int ldgx, const float* mask, int ldmask, int B,
+void launch_resize_bwd(const float* gy, int ldgy, float* gx, int ldgx, const uint8_t* m8, int ldm8, int B,
                        int C, ResizeTab th, ResizeTab tw, hipStream_t s, unsigned* amax) {
   if ((C & 3) == 0) {
     const long n = (long)B * th.in * tw.in * (C / 4);
     hipLaunchKernelGGL((resize_bwd_kernel<4>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, gy, ldgy, gx,
-                       ldgx, mask, ldmask, B, C, th, tw, amax);
+                       ldgx, m8, ldm8, B, C, th, tw, amax);
   } else {
     const long n = (long)B * th.in * tw.in * C;
     hipLaunchKernelGGL((resize_bwd_kernel<1>), dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, gy, ldgy, gx,
-                       ldgx, mask, ldmask, B, C, th, tw, amax);
+                       ldgx, nullptr, 0, B, C, th, tw, amax);
   }
 }
 
@@ -1840,9 +1842,8 @@ void launch_wino_weight(const float* w, int Cout, int Cin, const float* rowscale
 // (columns likewise), B = [[1,0,0,0],[0,1,-1,1],[-1,1,1,0],[0,0,0,-1]]; gather form, no atomics: deterministic.
 __global__ __launch_bounds__(256) void wino_dgrad_output_kernel(const float* __restrict__ dV, long prow, int C, int B, int H,
                                                                  int W, int th, int tw, int dil,
-                                                                 const float* __restrict__ mask, int ldmask, int mask_c0,
-                                                                 int accum, float* __restrict__ gx, int ldgx, unsigned* __restrict__ amax,
-                                                                 const uint8_t* __restrict__ mask8, int ldm8) {
+                                                                 const uint8_t* __restrict__ mask8, int ldm8, int mask_c0,
+                                                                 int accum, float* __restrict__ gx, int ldgx, unsigned* __restrict__ amax) {
   const int C4 = C >> 2;
   const long n = (long)B * dil * dil * th * tw * C4;      // one 2x2 block of a sub-grid per tile position
   unsigned am = 0;
@@ -1917,12 +1918,7 @@ __global__ __launch_bounds__(256) void wino_dgrad_output_kernel(const float* __r
           const float4 o = *reinterpret_cast<const float4*>(gx + pix * ldgx + c4 * 4);
           v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
         }
-        if (mask8 && c4 * 4 >= mask_c0) {
-          relu_mask8(v, mask8[pix * ldm8 + c4]);
-        } else if (mask && c4 * 4 >= mask_c0) {
-          const float4 m = *reinterpret_cast<const float4*>(mask + pix * ldmask + c4 * 4);
-          v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
-        }
+        if (mask8 && c4 * 4 >= mask_c0) relu_mask8(v, mask8[pix * ldm8 + c4]);
         am = amax_f4(am, v);
         *reinterpret_cast<float4*>(gx + pix * ldgx + c4 * 4) = v;
       }
@@ -1931,11 +1927,11 @@ __global__ __launch_bounds__(256) void wino_dgrad_output_kernel(const float* __r
   if (amax) amax_block_commit(am, amax);
 }
 void launch_wino_dgrad_output(const float* dV, long prow, int C, int B, int H, int W, int th, int tw, int dil,
-                              const float* mask, int ldmask, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s, unsigned* amax,
-                              const uint8_t* mask8, int ldm8) {
+                              const uint8_t* mask8, int ldm8, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s,
+                              unsigned* amax) {
   const long n = (long)B * dil * dil * th * tw * (C / 4);
   hipLaunchKernelGGL(wino_dgrad_output_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, dV, prow, C, B, H, W, th, tw,
-                     dil, mask, ldmask, mask_c0, accum, gx, ldgx, amax, mask8, ldm8);
+                     dil, mask8, ldm8, mask_c0, accum, gx, ldgx, amax);
 }
 // y (NHWC, ld ldy) = relu?(scale * (A^T M A) + bias) from M[p][tile][c], A^T = [[1,1,1,0],[0,1,-1,-1]]
 __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restrict__ M, long prow, int C, int B, int H, int W,
@@ -2253,9 +2249,8 @@ __global__ __launch_bounds__(256) void wino4_wgrad_finish_kernel(const float* __
 // (its row 3); columns likewise.  B[i][a] = BT[a][i].
 __global__ __launch_bounds__(256) void wino4_dgrad_output_kernel(const float* __restrict__ dV, long prow, int C, int B, int H,
                                                                   int W, int th, int tw, int dil,
-                                                                  const float* __restrict__ mask, int ldmask, int mask_c0,
-                                                                  int accum, float* __restrict__ gx, int ldgx, unsigned* __restrict__ amax,
-                                                                  const uint8_t* __restrict__ mask8, int ldm8) {
+                                                                  const uint8_t* __restrict__ mask8, int ldm8, int mask_c0,
+                                                                  int accum, float* __restrict__ gx, int ldgx, unsigned* __restrict__ amax) {
   const int C4 = C >> 2;
   const long n = (long)B * dil * dil * th * tw * C4;
   unsigned am = 0;
@@ -2339,12 +2334,7 @@ __global__ __launch_bounds__(256) void wino4_dgrad_output_kernel(const float* __
           const float4 o = *reinterpret_cast<const float4*>(gx + pix * ldgx + c4 * 4);
           v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
         }
-        if (mask8 && c4 * 4 >= mask_c0) {
-          relu_mask8(v, mask8[pix * ldm8 + c4]);
-        } else if (mask && c4 * 4 >= mask_c0) {
-          const float4 m = *reinterpret_cast<const float4*>(mask + pix * ldmask + c4 * 4);
-          v.x = m.x > 0.f ? v.x : 0.f; v.y = m.y > 0.f ? v.y : 0.f; v.z = m.z > 0.f ? v.z : 0.f; v.w = m.w > 0.f ? v.w : 0.f;
-        }
+        if (mask8 && c4 * 4 >= mask_c0) relu_mask8(v, mask8[pix * ldm8 + c4]);
         am = amax_f4(am, v);
         *reinterpret_cast<float4*>(gx + pix * ldgx + c4 * 4) = v;
       }
@@ -2378,10 +2368,10 @@ void launch_wino4_wgrad_finish(const float* ws, int splits, int Cout, int Cin, f
   hipLaunchKernelGGL(wino4_wgrad_finish_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, ws, splits, Cout, Cin, dst);
 }
 void launch_wino4_dgrad_output(const float* dV, long prow, int C, int B, int H, int W, int th, int tw, int dil,
-                               const float* mask, int ldmask, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s, unsigned* amax,
-                               const uint8_t* mask8, int ldm8) {
+                               const uint8_t* mask8, int ldm8, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s,
+                               unsigned* amax) {
   const long n = (long)B * dil * dil * th * tw * (C / 4);
   hipLaunchKernelGGL(wino4_dgrad_output_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, dV, prow, C, B, H, W, th, tw,
-                     dil, mask, ldmask, mask_c0, accum, gx, ldgx, amax, mask8, ldm8);
+                     dil, mask8, ldm8, mask_c0, accum, gx, ldgx, amax);
 }
 }  // namespace eosvos

@@ -20,6 +20,14 @@ def _optr(t):
     return _ptr(t) if t is not None else None
 
 
+def _relu_bits(t):
+    """ReLU mask bytes of t (..., C), the form the engine's data gradients read: bit j of byte q = (channel 4q + j > 0)."""
+    if t is None:
+        return None
+    m = (t > 0).to(torch.uint8).reshape(*t.shape[:-1], -1, 4)
+    return (m[..., 0] | (m[..., 1] << 1) | (m[..., 2] << 2) | (m[..., 3] << 3)).contiguous()
+
+
 def _ld(t):
     """Leading dimension (elements per pixel) of a pixel-major view with unit channel stride whose images are P pixels apart."""
     if t is None:
@@ -671,14 +679,15 @@ class Engine:
         return y
 
     def test_conv_bwd_algo(self, algo, x_nhwc, w_oihw, g_nhwc, stride, dil, pad, scale=None, mask=None):
-        """(dx, dw) through the production weight- / data-gradient paths with the algorithm forced."""
+        """(dx, dw) through the production weight- / data-gradient paths with the algorithm forced; dx = 0 where mask (NHWC
+        like x) is <= 0, passed to the engine as mask bytes."""
         B, H, W, Cin = x_nhwc.shape
         Cout, _, k, _ = w_oihw.shape
         dx = torch.empty_like(x_nhwc)
         dw = torch.empty_like(w_oihw)
-        p = lambda t: _ptr(t) if t is not None else None
+        m8 = _relu_bits(mask)
         _ffi.check(self.lib.eosvos_test_conv_bwd_algo(self.h, self.ALGOS[algo], _ptr(x_nhwc), _ptr(w_oihw), _ptr(g_nhwc),
-                                                      p(scale), p(mask), B, H, W, Cin, Cout, k, stride, dil, pad, _ptr(dx),
+                                                      _optr(scale), _optr(m8), B, H, W, Cin, Cout, k, stride, dil, pad, _ptr(dx),
                                                       _ptr(dw)))
         return dx, dw
 
@@ -723,11 +732,12 @@ class Engine:
         return y, idx, gx
 
     def test_resize(self, align_corners, x=None, y=None, gy=None, gx=None, mask=None):
-        """Bilinear resize x (B, hin, win, C) -> y (B, hout, wout, C) and / or its backward gy -> gx (zero where mask <= 0);
-        the caller provides every tensor."""
+        """Bilinear resize x (B, hin, win, C) -> y (B, hout, wout, C) and / or its backward gy -> gx (zero where mask <= 0,
+        passed to the engine as mask bytes: C % 4 == 0); the caller provides every tensor."""
         (B, hin, win, C), (hout, wout) = (x if x is not None else gx).shape, (y if y is not None else gy).shape[1:3]
+        m8 = _relu_bits(mask)
         _ffi.check(self.lib.eosvos_test_resize(self.h, int(align_corners), hin, win, hout, wout, B, C, _optr(x), _ld(x), _optr(y),
-                                               _ld(y), _optr(gy), _ld(gy), _optr(gx), _ld(gx), _optr(mask), _ld(mask)))
+                                               _ld(y), _optr(gy), _ld(gy), _optr(gx), _ld(gx), _optr(m8), _ld(m8)))
 
     def test_aspp_pool(self, x, w, a=None, bias=None, y=None, m8=None, gy=None):
         """ASPP image pooling of x (B, P, K) with w (N, K): dict of v, pool, y (default (B, P, N)) and, given gy (B, P, N),

@@ -406,10 +406,10 @@ int eosvos_test_conv_algo(eosvos_engine* e, int algo, const float* x_nhwc, const
                           int B, int H, int W, int Cin, int Cout, int k, int stride, int dil, int pad,
                           float* y_nhwc);
 /* dx = mask?(dgrad(scale*g)), dw = scale * wgrad(g, x) through the production backward paths; `scale` (per cout,
- * the folded norm scale) and `mask` (NHWC like x: dx = 0 where mask <= 0, the ReLU mask of the conv input) may be
- * NULL. */
+ * the folded norm scale) and `m8` (the ReLU mask bytes of the conv input, Cin / 4 per pixel: dx of channel 4q + j = 0
+ * where bit j of byte [p][q] is clear) may be NULL. */
 int eosvos_test_conv_bwd_algo(eosvos_engine* e, int algo, const float* x_nhwc, const float* w_oihw,
-                              const float* g_nhwc, const float* scale, const float* mask_nhwc, int B, int H, int W,
+                              const float* g_nhwc, const float* scale, const uint8_t* m8, int B, int H, int W,
                               int Cin, int Cout, int k, int stride, int dil, int pad, float* dx_nhwc,
                               float* dw_oihw);
 /* dx = conv_dgrad(g), dw = conv_wgrad(g, x) for the same geometry (no norm scale), ALGO_DIRECT. */
@@ -434,9 +434,10 @@ int eosvos_test_groupnorm(eosvos_engine* e, int bwd, float* z, int ldz, const fl
 int eosvos_test_maxpool(eosvos_engine* e, const float* x, int B, int H, int W, int C, float* y, uint8_t* idx, const float* gy,
                         float* gx);
 /* F.interpolate(mode='bilinear', align_corners) from hin x win to hout x wout (deeplabv3plus.py:144, :161): x -> y when both are
- * given, and gx = (mask ? mask > 0 : 1) * backward(gy) when gy / gx are given. */
+ * given, and gx = backward(gy) when gy / gx are given, zero in channel 4q + j where bit j of the ReLU mask byte m8[p][q] is
+ * clear (m8 may be NULL; row pitch ldm8 bytes; needs C % 4 == 0). */
 int eosvos_test_resize(eosvos_engine* e, int align_corners, int hin, int win, int hout, int wout, int B, int C, const float* x,
-                       int ldx, float* y, int ldy, const float* gy, int ldgy, float* gx, int ldgx, const float* mask, int ldmask);
+                       int ldx, float* y, int ldy, const float* gy, int ldgy, float* gx, int ldgx, const uint8_t* m8, int ldm8);
 /* The ASPP image-pooling branch (ASPPPooling, deeplabv3plus.py:100-112): v = mean over P pixels of x [B][P][K], pool =
  * relu(a * (w v) + bias) (a = bias = NULL: w v without affine, the GroupNorm engine's form), broadcast to y [B][P][N] (+ the ReLU
  * mask bytes m8 when not NULL).  With gy: gpool = sum over pixels of gy [B][P][N] (already ReLU-masked, as the consumer's data
