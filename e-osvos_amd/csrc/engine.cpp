@@ -187,7 +187,7 @@ struct eosvos_engine {
   hipStream_t s2 = nullptr;            // side stream: weight-gradient kernels run beside the dgrad chain
   std::vector<hipEvent_t> ev;          // one fork event per conv + a join event
   bool side_used = false;
-  std::vector<std::function<void()>> side_q;   // weight-gradient launches waiting for the next fork (see side_flush)
+  std::vector<std::function<void(hipStream_t)>> side_q;   // weight-gradient launches waiting for the next fork (see side_flush)
   int h2, w2, h4, w4, h8, w8, h16, w16;
   std::vector<void*> allocs;
 
@@ -231,12 +231,21 @@ struct eosvos_engine {
   float *gn_sums = nullptr, *gn_partial = nullptr;
   struct TapTab { int* prefix; int* mask; long total; int* order; };
   std::map<long, TapTab> tap_tabs;    // (conv, fwd/dgrad, batch) -> compacted K-step table of a dilated conv
-  // Grouped weight gradients: the convs of ResNet layer1..3 only queue their WgradArgs; when the stage's data-gradient
-  // chain is queued, one launch per tile shape computes all of them (plan_wgrad_group)
-  struct WgGroupLaunch { WgradArgs* dtab; int* dmap; int nwg, bm, bn; double flops; int first_ci; };
-  struct WgGroupPlan { std::vector<WgGroupLaunch> launches; std::vector<int> splits; };
-  std::vector<std::pair<int, WgradArgs>> wg_pending;
-  std::map<long, WgGroupPlan> wg_plans;           // (stage, batch, budget) -> device tables
+  // Grouped weight gradients: the convs of ResNet layer1..3 only queue their arguments; when the stage's data-gradient
+  // chain is queued, flush_wgrad_group computes all of them: one launch per tile shape of the register-staged kernel and
+  // one of the pre-split kernel (`presplit` entries carry `p`; `covered`: this iteration's producers wrote both siblings)
+  struct WgPending { int ci; WgradArgs a; bool presplit; WgradPArgs p; bool covered; };
+  std::vector<WgPending> wg_pending;
+  // dtab: WgradArgs[] of bm x bn register-staged tiles in dtab[0], or WgradPArgs[] of 256 x 256 pre-split tiles in
+  // dtab[parity of the iteration] (the scale words alternate)
+  struct WgGroupLaunch { const void* dtab[2] = {nullptr, nullptr}; int* dmap = nullptr; int nwg = 0, bm = 0, bn = 0; double flops = 0; int first_ci = -1; };
+  struct WgGroupPlan {
+    std::vector<int> splits;                         // K splits (= slabs) of every queued conv (fixed membership: the update tables are built once)
+    size_t npresplit = 0;                            // pre-split members among them
+    std::vector<WgGroupLaunch> launches;             // the register-staged members: one launch per tile shape
+    std::map<std::string, WgGroupLaunch> presplit;   // covered subset of the pre-split members -> their one launch
+  };
+  std::map<long, WgGroupPlan> wg_plans;           // (stage, batch, budget, side stream) -> split counts and device tables
   bool wg_group_on = true;
   std::vector<int> conv_hin, conv_win;            // per conv: input map size (grouped-plan slab sizing)
   std::vector<int64_t> ws_off;       // per conv: offset of its weight-gradient slabs in ws_wg
@@ -288,11 +297,6 @@ struct eosvos_engine {
   unsigned char* pair_zero = nullptr;             // 4 KB of zeros: K rows past the last contributing pixel
   float* pair_sc_pool = nullptr;
   int pair_sc_used = 0;
-  struct WgPGroupPlan { WgradPArgs* dtab[2] = {nullptr, nullptr}; int* dmap = nullptr; int nwg = 0; double flops = 0; };   // dtab[parity of the iteration]: the scale words alternate
-  std::map<std::pair<long, std::string>, WgPGroupPlan> wgp_plans;   // ((stage, batch, budget), covered subset) -> device tables of the grouped pre-split launch
-  std::map<long, std::vector<std::pair<int, int>>> wgp_splits;    // (stage, batch, budget) -> (K chunks, workgroups per tile) of every eligible conv of the stage (fixed membership)
-  struct WgPPending { int ci; WgradPArgs a; WgradArgs legacy; bool covered; };
-  std::vector<WgPPending> wgp_pending;
   // launch-plan fingerprint (eosvos_plan_fingerprint): FNV-1a over (kind, conv, M, N, K, workgroups / K splits) of every matrix
   // launch of the last forward [0] / backward [1] and the slab counts the update consumed -- the split plan fixes the fp32
   // summation order, i.e. which rounding a long trajectory accumulates (tests/test_gpu_plan_fingerprint.py)
@@ -623,10 +627,15 @@ struct PlanScope {
   PlanScope(const PlanScope&) = delete;
   PlanScope& operator=(const PlanScope&) = delete;
 };
+// the line alone, not mixed into the plan fingerprint: launches that cover several convs and sum their flops themselves (grouped
+// weight gradients: conv = the first member, M x N = the tile, splits = workgroups; the merged ASPP data gradient)
+void trace_line(const char* kind, int ci, long M, long N, long K, int splits, double flops) {
+  if (trace_on()) fprintf(stderr, "EOSVOS_TRACE %s conv=%d M=%ld N=%ld K=%ld splits=%d flops=%.0f\n", kind, ci, M, N, K, splits, flops);
+}
 void trace(const char* kind, int ci, long M, long N, long K, int splits, double frac = 1.0) {
   plan_mix((uint64_t)(unsigned char)kind[0] | ((uint64_t)(unsigned char)kind[1] << 8) | ((uint64_t)strlen(kind) << 16));
   plan_mix((uint64_t)ci); plan_mix((uint64_t)M); plan_mix((uint64_t)N); plan_mix((uint64_t)K); plan_mix((uint64_t)splits);
-  if (trace_on()) fprintf(stderr, "EOSVOS_TRACE %s conv=%d M=%ld N=%ld K=%ld splits=%d flops=%.0f\n", kind, ci, M, N, K, splits, 2.0 * M * N * K * frac);
+  trace_line(kind, ci, M, N, K, splits, 2.0 * M * N * K * frac);
 }
 // Winograd F(2x2,3x3) path (forward, data gradient, weight gradient) of 3x3 / stride 1 convs: 2.25x fewer MACs,
 // paid for with HBM-bound transform passes.  Always on for the decoder's two convs on the stride-4 map (27 % of a
@@ -924,14 +933,15 @@ eosvos_engine::PairBuf* pair_buf(eosvos_engine* e, int phase, const float* key, 
     (void)hipMemsetAsync(e->pair_sc_pool, 0, PAIR_SC_POOL * 4, e->s);
   }
   if (pb.floats < need) {
+    // (the scale words first: a sibling is committed, and with that handed out by later calls, only together with them)
+    if (!pb.sc && e->pair_sc_used + 3 > PAIR_SC_POOL) return nullptr;
     pb.p = (unsigned char*)e->falloc(need);
     if (!pb.p) { pb.floats = 0; return nullptr; }
-    pb.floats = need; pb.covered = false; pb.fresh = true;
     if (!pb.sc) {
-      if (e->pair_sc_used + 3 > PAIR_SC_POOL) return nullptr;
       pb.sc = e->pair_sc_pool + e->pair_sc_used;
       e->pair_sc_used += 3;
     }
+    pb.floats = need; pb.covered = false; pb.fresh = true;
   }
   return &pb;
 }
@@ -1000,51 +1010,62 @@ void side_flush(eosvos_engine* e) {
   if (e->side_q.empty()) return;
   (void)hipEventRecord(e->ev[0], e->s);            // everything the queued launches read is complete here
   (void)hipStreamWaitEvent(e->s2, e->ev[0], 0);
-  for (auto& f : e->side_q) f();
+  for (auto& f : e->side_q) f(e->s2);
   e->side_q.clear();
   e->side_used = true;
 }
+// a weight-gradient launch: queued for the next fork onto the side stream (side_flush) when the engine has one, else at
+// once on the main stream
+template <class F>
+void side_enqueue(eosvos_engine* e, F&& launch) {
+  if (e->s2) e->side_q.emplace_back(std::forward<F>(launch));
+  else launch(e->s);
+}
 // ---- grouped weight gradients ------------------------------------------------------------------------
-// K splits of the weight gradients of one group: every launch (one per tile shape) should fill the chip with
-// workgroups of about equal K length.  tau = (sum of tiles x K steps of the shape class) / workgroups the launch plans
-// for; a conv with `steps` K steps of 32 pixels is cut into ceil(steps / tau) splits (>= 4 steps each).
+// K splits of weight gradients that share ONE launch of equal tiles: the launch should fill the chip with workgroups of
+// about equal K length.  tau = (sum of tiles x K steps) / workgroups the launch plans for; an item with `steps` K steps
+// of 32 pixels is cut into ceil(steps / tau) splits (>= 4 steps each, at most 512).
+struct KItem { long tiles, steps; };
+std::vector<int> plan_equal_k(const std::vector<KItem>& items, long resident) {
+  auto splits_of = [](const KItem& it, long tau) {
+    const long sp = (it.steps + tau - 1) / tau;
+    return sp > it.steps / 4 ? std::max<long>(1, it.steps / 4) : sp;
+  };
+  long work = 0;
+  for (const auto& it : items) work += it.tiles * it.steps;
+  // smallest tau whose workgroups all fit one resident round (a launch a little over one round would run its
+  // last workgroups alone: measured 556 workgroups at 113 TFLOP/s against 864 = 1.7 rounds at 163)
+  long tau = std::max<long>(4, (work + resident - 1) / resident);
+  auto count = [&](long t) {
+    long n = 0;
+    for (const auto& it : items) n += it.tiles * splits_of(it, t);
+    return n;
+  };
+  while (count(tau) > resident && tau < (1L << 20)) tau += std::max<long>(1, tau / 32);
+  // (the cap of 512 plays no part in the search: an item cut more often is by itself more than a resident round, <= 512)
+  std::vector<int> splits;
+  for (const auto& it : items) splits.push_back((int)std::min<long>(splits_of(it, tau), 512));
+  return splits;
+}
+// the register-staged kernels: one launch, hence one plan, per tile shape wgrad_group_tile(cout) x wgrad_group_tile(cin)
 struct WgGroupItem { int ci, P, cout, cin, T; };
+long wgrad_group_tiles(const WgGroupItem& it) {
+  const int bm = wgrad_group_tile(it.cout), bn = wgrad_group_tile(it.cin);
+  return (long)((it.cout + bm - 1) / bm) * ((it.cin + bn - 1) / bn) * it.T;
+}
 std::vector<int> plan_wgrad_splits(const std::vector<WgGroupItem>& items, int wg_budget) {
-  const int RES = conv_wg_budget_of(wg_budget);
   std::vector<int> splits(items.size(), 1);
   for (int bm : {128, 64})
     for (int bn : {128, 64}) {
-      long work = 0;
-      for (const auto& it : items) {
-        if (wgrad_group_tile(it.cout) != bm || wgrad_group_tile(it.cin) != bn) continue;
-        const long tiles = (long)((it.cout + bm - 1) / bm) * ((it.cin + bn - 1) / bn) * it.T;
-        work += tiles * ((it.P + 31) / 32);
-      }
-      if (!work) continue;
-      // smallest tau whose workgroups all fit one resident round (a launch a little over one round would run its
-      // last workgroups alone: measured 556 workgroups at 113 TFLOP/s against 864 = 1.7 rounds at 163)
-      long tau = std::max<long>(4, (work + RES - 1) / RES);
-      auto count = [&](long t) {
-        long n = 0;
-        for (const auto& it : items) {
-          if (wgrad_group_tile(it.cout) != bm || wgrad_group_tile(it.cin) != bn) continue;
-          const long tiles = (long)((it.cout + bm - 1) / bm) * ((it.cin + bn - 1) / bn) * it.T;
-          const long steps = (it.P + 31) / 32;
-          long sp = (steps + t - 1) / t;
-          if (sp > steps / 4) sp = std::max<long>(1, steps / 4);
-          n += tiles * sp;
-        }
-        return n;
-      };
-      while (count(tau) > (long)RES && tau < (1L << 20)) tau += std::max<long>(1, tau / 32);
+      std::vector<KItem> shape;
+      std::vector<size_t> at;                      // shape[j] is items[at[j]]
       for (size_t k = 0; k < items.size(); ++k) {
-        const auto& it = items[k];
-        if (wgrad_group_tile(it.cout) != bm || wgrad_group_tile(it.cin) != bn) continue;
-        const long steps = (it.P + 31) / 32;
-        long sp = (steps + tau - 1) / tau;
-        if (sp > steps / 4) sp = std::max<long>(1, steps / 4);
-        splits[k] = (int)std::min<long>(sp, 512);
+        if (wgrad_group_tile(items[k].cout) != bm || wgrad_group_tile(items[k].cin) != bn) continue;
+        shape.push_back({wgrad_group_tiles(items[k]), (items[k].P + 31) / 32});
+        at.push_back(k);
       }
+      const std::vector<int> sp = plan_equal_k(shape, conv_wg_budget_of(wg_budget));
+      for (size_t j = 0; j < at.size(); ++j) splits[at[j]] = sp[j];
     }
   return splits;
 }
@@ -1061,297 +1082,253 @@ bool wgrad_groupable(const eosvos_engine* e, int ci, int B) {
   return e->wg_group_on && conv_mfma_mode() >= 1 && e->force_algo == 0 && ci < (int)e->t.stage.size() &&
          e->t.stage[ci] >= min_stage && e->t.stage[ci] <= 2 && !e->conv_hin.empty();
 }
+// device copy of a host table of a grouped launch (its entries, its (entry, workgroup) map)
+template <class T>
+int upload_table(eosvos_engine* e, const std::vector<T>& tab, T*& dev) {
+  dev = (T*)e->falloc((int64_t)(tab.size() * sizeof(T) + 3) / 4);
+  if (!dev) return fail("hipMalloc grouped weight-gradient tables");
+  HIPOK(hipMemcpy(dev, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
 // Launch the queued weight gradients (all of one stage) -- on the side stream when there is one.
-// The pre-split members of a stage's group.  K splits are planned over ALL eligible convs of the stage (fixed membership: the
-// update tables are built once) so that the 256 x 256 workgroups fit one resident round (one per CU) at equal K length.  The
-// convs whose operand siblings were written this iteration run as ONE launch; the others (first iteration of a trajectory)
-// on the register-staged kernel with the same split counts.
-int flush_wgrad_p_group(eosvos_engine* e, int stage, int B) {
-  if (e->wgp_pending.empty()) return 0;
+// The register-staged members run as one launch per tile shape, planned for the engine's workgroup budget.
+// The pre-split members: K splits are planned over ALL eligible convs of the stage (fixed membership: the update tables are
+// built once) so that the 256 x 256 workgroups fit one resident round (one per CU of wgp_budget's share) at equal K length.
+// The convs whose operand siblings were written this iteration run as ONE launch; the others (first iteration of a
+// trajectory) on the register-staged kernel with the same split counts.
+int flush_wgrad_group(eosvos_engine* e, int stage, int B) {
+  auto& Q = e->wg_pending;
+  if (Q.empty()) { side_flush(e); return 0; }
   const long key = (((long)stage * 64 + B) * 1024 + e->wg_budget) * 2 + (e->s2 ? 1 : 0);
-  auto sp = e->wgp_splits.find(key);
-  if (sp == e->wgp_splits.end()) {
-    const int res = wgrad_p_resident(wgp_budget(e));
-    long work = 0;
-    for (auto& q : e->wgp_pending) work += (long)wgrad_p_tiles(q.a) * ((q.a.B * q.a.Ho * q.a.Wo + 31) / 32);
-    long tau = std::max<long>(4, (work + res - 1) / res);
-    auto splits_of = [&](const WgradPArgs& a, long t) {
-      const long steps = (a.B * a.Ho * a.Wo + 31) / 32;
-      long n = (steps + t - 1) / t;
-      if (n > steps / 4) n = std::max<long>(1, steps / 4);
-      return (int)std::min<long>(n, 512);
-    };
-    auto count = [&](long t) { long n = 0; for (auto& q : e->wgp_pending) n += (long)wgrad_p_tiles(q.a) * splits_of(q.a, t); return n; };
-    while (count(tau) > res && tau < (1L << 20)) tau += std::max<long>(1, tau / 32);
-    std::vector<std::pair<int, int>> v;
-    for (size_t k = 0; k < e->wgp_pending.size(); ++k) {
-      const int g = splits_of(e->wgp_pending[k].a, tau);
-      v.push_back({g, g});                            // one K chunk per workgroup
+  auto it = e->wg_plans.find(key);
+  if (it == e->wg_plans.end()) {
+    eosvos_engine::WgGroupPlan plan;
+    std::vector<WgGroupItem> items;
+    std::vector<KItem> pitems;
+    std::vector<size_t> at, pat;                   // items[j] is Q[at[j]], pitems[j] is Q[pat[j]]
+    for (size_t k = 0; k < Q.size(); ++k) {
+      const WgradArgs& a = Q[k].a;
+      const int P = a.B * a.Ho * a.Wo;
+      if (Q[k].presplit) { pitems.push_back({wgrad_p_tiles(Q[k].p), (P + 31) / 32}); pat.push_back(k); }
+      else { items.push_back({Q[k].ci, P, a.Cout, a.Cin, a.KH * a.KW}); at.push_back(k); }
     }
-    sp = e->wgp_splits.emplace(key, v).first;
+    const std::vector<int> sp = plan_wgrad_splits(items, e->wg_budget);
+    const std::vector<int> psp = plan_equal_k(pitems, wgrad_p_resident(wgp_budget(e)));
+    plan.splits.assign(Q.size(), 1);
+    plan.npresplit = pat.size();
+    for (size_t j = 0; j < at.size(); ++j) plan.splits[at[j]] = sp[j];
+    for (size_t j = 0; j < pat.size(); ++j) plan.splits[pat[j]] = psp[j];
+    for (int bm : {128, 64})
+      for (int bn : {128, 64}) {
+        eosvos_engine::WgGroupLaunch L;
+        std::vector<WgradArgs> tab;
+        std::vector<int> map;
+        for (size_t j = 0; j < items.size(); ++j) {
+          const auto& im = items[j];
+          if (wgrad_group_tile(im.cout) != bm || wgrad_group_tile(im.cin) != bn) continue;
+          WgradArgs a = Q[at[j]].a;
+          a.splits = sp[j];
+          // workgroups of an entry in launch_wgrad's order: split-major, the taps of a (cout, cin) tile pair adjacent
+          for (int w = 0; w < wgrad_group_tiles(im) * a.splits; ++w) { map.push_back((int)tab.size()); map.push_back(w); }
+          L.flops += 2.0 * im.cout * im.cin * im.T * (double)im.P * wgrad_exec_frac(a);
+          if (L.first_ci < 0) L.first_ci = im.ci;
+          tab.push_back(a);
+        }
+        if (tab.empty()) continue;
+        WgradArgs* dtab = nullptr;
+        if (upload_table(e, tab, dtab) || upload_table(e, map, L.dmap)) return 1;
+        L.dtab[0] = dtab; L.nwg = (int)(map.size() / 2); L.bm = bm; L.bn = bn;
+        plan.launches.push_back(L);
+      }
+    it = e->wg_plans.emplace(key, plan).first;
   }
-  const std::vector<std::pair<int, int>>& splits = sp->second;
-  if (splits.size() != e->wgp_pending.size()) return fail("internal: grouped pre-split weight-gradient plan does not match the queue");
-  std::string mask(e->wgp_pending.size(), '0');            // which members' siblings were written this iteration (ResNet-101's layer3: 69 members)
-  bool any = false;
-  for (size_t k = 0; k < e->wgp_pending.size(); ++k) if (e->wgp_pending[k].covered) { mask[k] = '1'; any = true; }
-  std::vector<std::function<void(hipStream_t)>> launches;
-  if (any) {
-    auto it = e->wgp_plans.find({key, mask});
-    if (it == e->wgp_plans.end()) {
-      eosvos_engine::WgPGroupPlan plan;
+  eosvos_engine::WgGroupPlan& plan = it->second;
+  std::string covered;             // which pre-split members' siblings were written this iteration (ResNet-101's layer3: 69 members)
+  int first_p = -1;
+  for (const auto& q : Q)
+    if (q.presplit) { covered += q.covered ? '1' : '0'; if (first_p < 0) first_p = q.ci; }
+  if (plan.splits.size() != Q.size() || plan.npresplit != covered.size()) return fail("internal: grouped weight-gradient plan does not match the queue");
+  if (covered.find('1') != std::string::npos) {
+    const int par = (int)(e->pair_iter & 1);
+    auto pl = plan.presplit.find(covered);
+    if (pl == plan.presplit.end()) {
+      eosvos_engine::WgGroupLaunch L;
       std::vector<WgradPArgs> tab;
       std::vector<int> map;
-      for (size_t k = 0; k < e->wgp_pending.size(); ++k) {
-        if (!e->wgp_pending[k].covered) continue;
-        WgradPArgs a = e->wgp_pending[k].a;
-        a.splits = splits[k].first; a.groups = splits[k].second;
-        const int tiles = wgrad_p_tiles(a);
-        for (int w = 0; w < tiles * a.groups; ++w) { map.push_back((int)tab.size()); map.push_back(w); }
-        plan.flops += 2.0 * a.Cout * a.Cin * a.KH * a.KW * (double)a.B * a.Ho * a.Wo * wgrad_exec_frac(e->wgp_pending[k].legacy);
+      for (size_t k = 0; k < Q.size(); ++k) {
+        if (!Q[k].presplit || !Q[k].covered) continue;
+        WgradPArgs a = Q[k].p;
+        a.splits = a.groups = plan.splits[k];            // one K chunk per workgroup
+        for (int w = 0; w < wgrad_p_tiles(a) * a.groups; ++w) { map.push_back((int)tab.size()); map.push_back(w); }
+        L.flops += 2.0 * a.Cout * a.Cin * a.KH * a.KW * (double)a.B * a.Ho * a.Wo * wgrad_exec_frac(Q[k].a);
         tab.push_back(a);
       }
-      const int par = (int)(e->pair_iter & 1);
-      plan.dmap = (int*)e->falloc((int64_t)map.size());
       for (int q = 0; q < 2; ++q) {
-        plan.dtab[par ^ q] = (WgradPArgs*)e->falloc((int64_t)(tab.size() * sizeof(WgradPArgs) + 3) / 4);
-        if (!plan.dtab[par ^ q] || !plan.dmap) return fail("hipMalloc grouped pre-split weight-gradient tables");
-        HIPOK(hipMemcpy(plan.dtab[par ^ q], tab.data(), tab.size() * sizeof(WgradPArgs), hipMemcpyHostToDevice));
+        WgradPArgs* dtab = nullptr;
+        if (upload_table(e, tab, dtab)) return 1;
+        L.dtab[par ^ q] = dtab;
         for (auto& a : tab) {        // the other parity: the producers' word and the next iteration's word trade places
           const float* pg = a.scp_g; const float* px = a.scp_x;
           a.scp_g = a.scn_g; a.scp_x = a.scn_x;
           a.scn_g = const_cast<float*>(pg); a.scn_x = const_cast<float*>(px);
         }
       }
-      HIPOK(hipMemcpy(plan.dmap, map.data(), map.size() * 4, hipMemcpyHostToDevice));
-      plan.nwg = (int)(map.size() / 2);
-      it = e->wgp_plans.emplace(std::make_pair(key, mask), plan).first;
+      if (upload_table(e, map, L.dmap)) return 1;
+      L.nwg = (int)(map.size() / 2); L.bm = L.bn = 256; L.first_ci = first_p;
+      pl = plan.presplit.emplace(covered, L).first;
     }
-    const eosvos_engine::WgPGroupPlan PL = it->second;
-    if (trace_on()) fprintf(stderr, "EOSVOS_TRACE wgrad conv=%d M=%d N=%d K=%d splits=%d flops=%.0f\n", e->wgp_pending[0].ci, 256, 256, 0, PL.nwg, PL.flops);
-    const int par = (int)(e->pair_iter & 1);
-    launches.push_back([PL, par](hipStream_t ws) { launch_wgrad_p_group(PL.dtab[par], PL.dmap, PL.nwg, PL.flops, ws); });
+    const eosvos_engine::WgGroupLaunch L = pl->second;
+    trace_line("wgrad", L.first_ci, L.bm, L.bn, 0, L.nwg, L.flops);
+    side_enqueue(e, [L, par](hipStream_t ws) { launch_wgrad_p_group((const WgradPArgs*)L.dtab[par], L.dmap, L.nwg, L.flops, ws); });
   }
-  for (size_t k = 0; k < e->wgp_pending.size(); ++k) {
-    auto& pd = e->wgp_pending[k];
-    e->upd_splits[pd.ci] = splits[k].first;
-    if (pd.covered) continue;
-    WgradArgs la = pd.legacy;
-    la.splits = splits[k].first;
-    trace("wgrad", pd.ci, la.Cout, (long)la.Cin * la.KH * la.KW, (long)la.B * la.Ho * la.Wo, la.splits, wgrad_exec_frac(la));
-    launches.push_back([la](hipStream_t ws) { launch_wgrad(la, ws); });
+  for (size_t k = 0; k < Q.size(); ++k) {
+    e->upd_splits[Q[k].ci] = plan.splits[k];
+    if (!Q[k].presplit || Q[k].covered) continue;
+    WgradArgs a = Q[k].a;            // siblings not written: the register-staged kernel, which leaves the scales for the next iteration
+    a.splits = plan.splits[k];
+    trace("wgrad", Q[k].ci, a.Cout, (long)a.Cin * a.KH * a.KW, (long)a.B * a.Ho * a.Wo, a.splits, wgrad_exec_frac(a));
+    side_enqueue(e, [a](hipStream_t ws) { launch_wgrad(a, ws); });
   }
-  e->wgp_pending.clear();
-  for (auto& go : launches) {
-    if (e->s2) {
-      hipStream_t s2 = e->s2;
-      e->side_q.push_back([go, s2]() { go(s2); });
-    } else {
-      go(e->s);
-    }
+  for (const eosvos_engine::WgGroupLaunch& L : plan.launches) {
+    trace_line("wgrad", L.first_ci, L.bm, L.bn, 0, L.nwg, L.flops);
+    side_enqueue(e, [L](hipStream_t ws) { launch_wgrad_group((const WgradArgs*)L.dtab[0], L.dmap, L.nwg, L.bm, L.bn, L.flops, ws); });
   }
+  Q.clear();
+  side_flush(e);
   return 0;
 }
-int flush_wgrad_group(eosvos_engine* e, int stage, int B) {
-  if (int rc = flush_wgrad_p_group(e, stage, B)) return rc;
-  if (e->wg_pending.empty()) { if (e->s2) side_flush(e); return 0; }
-  const long key = ((long)stage * 64 + B) * 1024 + e->wg_budget;
-  auto it = e->wg_plans.find(key);
-  if (it == e->wg_plans.end()) {
-    std::vector<WgGroupItem> items;
-    for (auto& pa : e->wg_pending) {
-      const WgradArgs& a = pa.second;
-      items.push_back({pa.first, a.B * a.Ho * a.Wo, a.Cout, a.Cin, a.KH * a.KW});
-    }
-    eosvos_engine::WgGroupPlan plan;
-    plan.splits = plan_wgrad_splits(items, e->wg_budget);
-    for (int bm : {128, 64})
-      for (int bn : {128, 64}) {
-        std::vector<WgradArgs> tab;
-        std::vector<int> map;
-        double flops = 0;
-        int first = -1;
-        for (size_t k = 0; k < items.size(); ++k) {
-          const auto& im = items[k];
-          if (wgrad_group_tile(im.cout) != bm || wgrad_group_tile(im.cin) != bn) continue;
-          WgradArgs a = e->wg_pending[k].second;
-          a.splits = plan.splits[k];
-          a.ws = e->ws_wg + e->ws_off[im.ci];
-          const int tiles = ((im.cout + bm - 1) / bm) * ((im.cin + bn - 1) / bn) * im.T;
-          // workgroups of an entry in launch_wgrad's order: split-major, the taps of a (cout, cin) tile pair adjacent
-          for (int w = 0; w < tiles * a.splits; ++w) { map.push_back((int)tab.size()); map.push_back(w); }
-          flops += 2.0 * im.cout * im.cin * im.T * (double)im.P * wgrad_exec_frac(a);
-          if (first < 0) first = im.ci;
-          tab.push_back(a);
-        }
-        if (tab.empty()) continue;
-        eosvos_engine::WgGroupLaunch L;
-        L.dtab = (WgradArgs*)e->falloc((int64_t)(tab.size() * sizeof(WgradArgs) + 3) / 4);
-        L.dmap = (int*)e->falloc((int64_t)map.size());
-        if (!L.dtab || !L.dmap) return fail("hipMalloc grouped weight-gradient tables");
-        HIPOK(hipMemcpy(L.dtab, tab.data(), tab.size() * sizeof(WgradArgs), hipMemcpyHostToDevice));
-        HIPOK(hipMemcpy(L.dmap, map.data(), map.size() * 4, hipMemcpyHostToDevice));
-        L.nwg = (int)(map.size() / 2); L.bm = bm; L.bn = bn; L.flops = flops; L.first_ci = first;
-        plan.launches.push_back(L);
-      }
-    it = e->wg_plans.emplace(key, plan).first;
+// ---- one conv's weight gradient -------------------------------------------------------------------------
+// wgrad_wino / wgrad_direct enqueue on the main stream what the operands need first (transform, absmax passes), fill the
+// arguments, record the slab count in upd_splits and return the launch for conv_wgrad to place.
+using WgLaunch = std::function<void(hipStream_t)>;
+// Winograd domain: dM = A dY A^T feeds this weight gradient (side stream) and the data gradient (main stream)
+WgLaunch wgrad_wino(eosvos_engine* e, int ci, const float* g, int ldg, const float* x, int ldx, int Hin, int Win, int B, int Ho, int Wo) {
+  const ConvL& c = e->t.convs[ci];
+  const WinoGeom wg = wino_geom(e, c, B, Ho, Wo);
+  unsigned* dms = amax_fused_slot(e, AM_DM, ci, e->wino_dM[ci], e->s);
+  if (wg.tm == 4) launch_wino4_grad(g, ldg, c.cout, B, Ho, Wo, wg.th, wg.tw, wg.d, wg.prow, e->wino_dM[ci], e->s, dms);
+  else launch_wino_grad(g, ldg, c.cout, B, Ho, Wo, wg.th, wg.tw, wg.d, wg.prow, e->wino_dM[ci], e->s, dms);
+  e->wino_dm_batch[ci] = B;
+  const long ntile = wg.ntile, prow = wg.prow;
+  float* V = e->wino_V[ci];
+  const bool need_v = e->wino_v_batch[ci] != B;       // else: V comes from the forward pass
+  float* final_slab = e->ws_wg + e->ws_off[ci];
+  WgradArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g = e->wino_dM[ci]; a.x = V; a.ws = final_slab + c.wsize();
+  a.B = 1; a.Ho = 1; a.Wo = (int)ntile; a.ldg = c.cout; a.Cout = c.cout; a.Hi = 1; a.Wi = (int)ntile; a.ldx = c.cin; a.Cin = c.cin;
+  a.KH = a.KW = wg.tm + 2; a.stride = 1; a.pad = 0; a.dil = 0;  // the "taps" are the Winograd positions, no pixel shift
+  a.g_tap_stride = prow * c.cout; a.x_tap_stride = prow * c.cin;
+  // the 16 / 36 planes already give hundreds of tiles, and every K split parks a full Winograd-domain slab that the finish
+  // kernel re-reads: plan the splits for half the workgroup budget (tools/budget_sweep.py: decoder conv at batch 3 247 -> 198 us,
+  // batch 1 90 -> 72 us)
+  const int wbud = conv_wg_budget_of(e->wg_budget) / 2;
+  a.splits = wgrad_pick_splits((int)ntile, c.cout, c.cin, wg.np, wbud);
+  trace("wgrad", ci, c.cout, (long)c.cin * wg.np, ntile, a.splits);
+  const int cin = c.cin, cout = c.cout;
+  const bool h3 = h3_mode() && !amax_init(e);
+  if (h3) {
+    a.amax_g = amax_get(e, AM_DM, ci, e->wino_dM[ci], (long)wg.np * prow, c.cout, c.cout, e->s);
+    a.amax_x = amax_slot(e, AM_V, ci);
+    if (!need_v && amax_rec_of(e, AM_V, ci).epoch != e->fwd_epoch)      // V of a forward in another mode
+      a.amax_x = amax_get(e, AM_V, ci, V, (long)wg.np * prow, c.cin, c.cin, e->s);
   }
-  const eosvos_engine::WgGroupPlan& plan = it->second;
-  if (plan.splits.size() != e->wg_pending.size()) return fail("internal: grouped weight-gradient plan does not match the queue");
-  for (size_t k = 0; k < e->wg_pending.size(); ++k) e->upd_splits[e->wg_pending[k].first] = plan.splits[k];
-  e->wg_pending.clear();
-  for (const auto& L : plan.launches) {
-    if (trace_on()) fprintf(stderr, "EOSVOS_TRACE wgrad conv=%d M=%d N=%d K=%d splits=%d flops=%.0f\n", L.first_ci, L.bm, L.bn, 0, L.nwg, L.flops);
-    const eosvos_engine::WgGroupLaunch LL = L;
-    if (e->s2) {
-      hipStream_t s2 = e->s2;
-      e->side_q.push_back([LL, s2]() { launch_wgrad_group(LL.dtab, LL.dmap, LL.nwg, LL.bm, LL.bn, LL.flops, s2); });
-    } else {
-      launch_wgrad_group(LL.dtab, LL.dmap, LL.nwg, LL.bm, LL.bn, LL.flops, e->s);
+  unsigned* vslot = h3 ? amax_slot(e, AM_V, ci) : nullptr;
+  e->upd_splits[ci] = 1;           // the finish kernel sums the Winograd-domain slabs into ONE 9-tap slab
+  return [=](hipStream_t ws) {
+    if (need_v) {
+      if (h3) amax_zero(vslot, 1, ws);
+      if (wg.tm == 4) launch_wino4_input(x, ldx, cin, B, Hin, Win, wg.th, wg.tw, wg.d, prow, V, ws, vslot);
+      else launch_wino_input(x, ldx, cin, B, Hin, Win, wg.th, wg.tw, wg.d, prow, V, ws, vslot);
     }
-  }
-  if (e->s2) side_flush(e);
-  return 0;
+    launch_wgrad(a, ws);
+    if (wg.tm == 4) launch_wino4_wgrad_finish(a.ws, a.splits, cout, cin, final_slab, ws);
+    else launch_wino_wgrad_finish(a.ws, a.splits, cout, cin, final_slab, ws);
+  };
 }
-// slabs of dW into ws_wg; returns the number of slabs (-1: queued for the stage's grouped launch, flush_wgrad_group)
-int conv_wgrad(eosvos_engine* e, int ci, const float* g, int ldg, const float* x, int ldx, int Hin, int Win, int B,
-               const float* gkey = nullptr, const float* xkey = nullptr) {
+// Pre-split operand path: 256 x 256 tiles on the pair8 siblings of g and x when this iteration's producers wrote both
+// (`covered`); otherwise the register-staged kernel with the same K splits, which leaves the scales for the next iteration's
+// producers (a.scn_*).  false: the conv does not take the path.
+bool wgrad_presplit_args(eosvos_engine* e, const ConvL& c, const float* gkey, const float* xkey, WgradArgs& a, WgradPArgs& pa, bool& covered) {
+  if (!presplit_enabled(e) || e->gn() || !a.amax_g || !a.amax_x || !presplit_wgrad_shape(c, a.B * a.Ho * a.Wo, a.ldg, a.ldx)) return false;
+  const long rows_g = (long)a.B * a.Ho * a.Wo, rows_x = (long)a.B * a.Hi * a.Wi;
+  eosvos_engine::PairBuf *xb = nullptr, *gb = nullptr;
+  const bool covx = pair_operand(e, 0, xkey, a.x, rows_x, c.cin, a.ldx, xb);
+  const bool covg = pair_operand(e, 1, gkey, a.g, rows_g, c.cout, a.ldg, gb);
+  if (!xb || !gb) return false;
+  const int par = (int)(e->pair_iter & 1);
+  memset(&pa, 0, sizeof(pa));
+  pa.g2 = gb->p + (a.g - gkey) * 4; pa.x2 = xb->p + (a.x - xkey) * 4; pa.ws = a.ws;
+  pa.B = a.B; pa.Ho = a.Ho; pa.Wo = a.Wo; pa.ldg = a.ldg; pa.Cout = c.cout; pa.Hi = a.Hi; pa.Wi = a.Wi; pa.ldx = a.ldx; pa.Cin = c.cin;
+  pa.KH = pa.KW = c.k; pa.stride = c.stride; pa.pad = c.pad; pa.dil = c.dil;
+  pa.zero = e->pair_zero;
+  pa.scp_g = gb->sc + 1 + par; pa.scp_x = xb->sc + 1 + par;
+  pa.scn_g = gb->sc + 1 + (par ^ 1); pa.scn_x = xb->sc + 1 + (par ^ 1);
+  pa.slot_g = a.amax_g; pa.slot_x = a.amax_x;
+  pa.margin_g = pair_margin(1); pa.margin_x = pair_margin(0);
+  pa.g = a.g; pa.x = a.x;
+  a.scn_g = pa.scn_g; a.scn_x = pa.scn_x; a.margin_g = pa.margin_g; a.margin_x = pa.margin_x;
+  xb->fresh = false; gb->fresh = false;        // from the next iteration on their producers have a scale to write with
+  covered = covx && covg;
+  return true;
+}
+// direct form; an empty launch: queued for the stage's grouped launch (flush_wgrad_group records the slab count)
+WgLaunch wgrad_direct(eosvos_engine* e, int ci, const float* g, int ldg, const float* x, int ldx, int Hin, int Win, int B, int Ho, int Wo,
+                      const float* gkey, const float* xkey) {
+  const ConvL& c = e->t.convs[ci];
+  WgradArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g = g; a.x = x; a.ws = e->ws_wg + e->ws_off[ci];
+  a.B = B; a.Ho = Ho; a.Wo = Wo;
+  a.ldg = ldg; a.Cout = c.cout; a.Hi = Hin; a.Wi = Win; a.ldx = ldx; a.Cin = c.cin;
+  a.KH = a.KW = c.k; a.stride = c.stride; a.pad = c.pad; a.dil = c.dil;
+  if (h3_mode() && !amax_init(e)) {
+    a.amax_g = tlookup(e, 1, gkey);
+    if (!a.amax_g) a.amax_g = amax_get(e, AM_G, ci, g, (long)B * Ho * Wo, c.cout, ldg, e->s);
+    // the input activation: the slot of its tensor or of this conv's view from the forward pass, else it is made now
+    a.amax_x = tlookup(e, 0, xkey);
+    if (!a.amax_x) {
+      unsigned* xs = amax_slot(e, AM_X, ci);
+      auto& r = amax_rec_of(e, AM_X, ci);
+      a.amax_x = (r.epoch == e->fwd_epoch && r.ptr == x) ? xs : amax_get(e, AM_X, ci, x, (long)B * Hin * Win, c.cin, ldx, e->s);
+    }
+  }
+  WgradPArgs pa{};
+  bool covered = false;
+  const bool presplit = wgrad_presplit_args(e, c, gkey, xkey, a, pa, covered);
+  if (wgrad_groupable(e, ci, B)) {
+    e->wg_pending.push_back({ci, a, presplit, pa, covered});
+    return nullptr;
+  }
+  // Pre-split: K chunks (= slabs) and workgroups per tile: one chunk per workgroup, as many as fill the launch's share of the chip
+  // (wgrad_p_pick_splits).  The kernel can also walk several chunks per workgroup (WgradPArgs::groups < splits: any K partition
+  // with any number of workgroups, bit-identical slabs -- tests/test_gpu_presplit.py).
+  if (presplit) pa.splits = pa.groups = a.splits = wgrad_p_pick_splits(B * Ho * Wo, c.cout, c.cin, c.T(), wgp_budget(e));
+  else a.splits = wgrad_pick_splits(B * Ho * Wo, c.cout, c.cin, c.T(), e->wg_budget);
+  e->upd_splits[ci] = a.splits;
+  const bool on_pairs = presplit && covered;
+  trace(on_pairs ? "wgrad_p" : "wgrad", ci, c.cout, (long)c.cin * c.T(), (long)B * Ho * Wo, a.splits, wgrad_exec_frac(a));
+  if (on_pairs) return [pa](hipStream_t ws) { launch_wgrad_p(pa, ws); };
+  return [a](hipStream_t ws) { launch_wgrad(a, ws); };
+}
+// slabs of dW into ws_wg (their number: upd_splits[ci]; of a conv queued for its stage's grouped launch: set by flush_wgrad_group)
+void conv_wgrad(eosvos_engine* e, int ci, const float* g, int ldg, const float* x, int ldx, int Hin, int Win, int B,
+                const float* gkey = nullptr, const float* xkey = nullptr) {
   const ConvL& c = e->t.convs[ci];
   if (!gkey) gkey = g;
   if (!xkey) xkey = x;
+  const int Ho = conv_out(Hin, c.k, c.stride, c.dil, c.pad), Wo = conv_out(Win, c.k, c.stride, c.dil, c.pad);
   if (e->gn() && c.norm) {        // dz = GroupNorm backward of G_u, written over the stored raw output
-    const int Ho = conv_out(Hin, c.k, c.stride, c.dil, c.pad), Wo = conv_out(Win, c.k, c.stride, c.dil, c.pad);
     // (round 5: the apply pass reduces max|dz| itself -- the consumers below, weight and data gradient, read the slot)
     launch_gn_backward(e->zbuf[ci], c.cout, g, ldg, e->G_(ci), e->gn_stats[ci], e->gn_partial, B, Ho * Wo, c.cout,
                        e->s, twrite_fused(e, 1, e->zbuf[ci], true));
     g = e->zbuf[ci]; ldg = c.cout; gkey = g;
   }
-  const int Ho = conv_out(Hin, c.k, c.stride, c.dil, c.pad), Wo = conv_out(Win, c.k, c.stride, c.dil, c.pad);
-  const bool wino = wino_on(e, ci, B, Ho, Wo);
-  if (wino) {                       // dM feeds this weight gradient (side stream) and the data gradient (main stream)
-    const WinoGeom wg = wino_geom(e, c, B, Ho, Wo);
-    unsigned* dms = amax_fused_slot(e, AM_DM, ci, e->wino_dM[ci], e->s);
-    if (wg.tm == 4) launch_wino4_grad(g, ldg, c.cout, B, Ho, Wo, wg.th, wg.tw, wg.d, wg.prow, e->wino_dM[ci], e->s, dms);
-    else launch_wino_grad(g, ldg, c.cout, B, Ho, Wo, wg.th, wg.tw, wg.d, wg.prow, e->wino_dM[ci], e->s, dms);
-    e->wino_dm_batch[ci] = B;
-  }
-  WgradArgs a;
-  memset(&a, 0, sizeof(a));
-  int nslabs;
-  std::function<void(hipStream_t)> go;
-  if (wino) {
-    const WinoGeom wg = wino_geom(e, c, B, Ho, Wo);
-    const long ntile = wg.ntile, prow = wg.prow;
-    float* V = e->wino_V[ci];
-    const bool need_v = e->wino_v_batch[ci] != B;       // else: V comes from the forward pass
-    float* final_slab = e->ws_wg + e->ws_off[ci];
-    a.g = e->wino_dM[ci]; a.x = V; a.ws = final_slab + c.wsize();
-    a.B = 1; a.Ho = 1; a.Wo = (int)ntile; a.ldg = c.cout; a.Cout = c.cout; a.Hi = 1; a.Wi = (int)ntile; a.ldx = c.cin; a.Cin = c.cin;
-    a.KH = a.KW = wg.tm + 2; a.stride = 1; a.pad = 0; a.dil = 0;  // the "taps" are the Winograd positions, no pixel shift
-    a.g_tap_stride = prow * c.cout; a.x_tap_stride = prow * c.cin;
-    // the 16 / 36 planes already give hundreds of tiles, and every K split parks a full Winograd-domain slab that the finish
-    // kernel re-reads: plan the splits for half the workgroup budget (tools/budget_sweep.py: decoder conv at batch 3 247 -> 198 us,
-    // batch 1 90 -> 72 us)
-    const int wbud = conv_wg_budget_of(e->wg_budget) / 2;
-    a.splits = wgrad_pick_splits((int)ntile, c.cout, c.cin, wg.np, wbud);
-    trace("wgrad", ci, c.cout, (long)c.cin * wg.np, ntile, a.splits);
-    const int cin = c.cin, cout = c.cout;
-    const bool h3 = h3_mode() && !amax_init(e);
-    if (h3) {
-      a.amax_g = amax_get(e, AM_DM, ci, e->wino_dM[ci], (long)wg.np * prow, c.cout, c.cout, e->s);
-      a.amax_x = amax_slot(e, AM_V, ci);
-      if (!need_v && amax_rec_of(e, AM_V, ci).epoch != e->fwd_epoch)      // V of a forward in another mode
-        a.amax_x = amax_get(e, AM_V, ci, V, (long)wg.np * prow, c.cin, c.cin, e->s);
-    }
-    unsigned* vslot = h3 ? amax_slot(e, AM_V, ci) : nullptr;
-    go = [=](hipStream_t ws) {
-      if (need_v) {
-        if (h3) amax_zero(vslot, 1, ws);
-        if (wg.tm == 4) launch_wino4_input(x, ldx, cin, B, Hin, Win, wg.th, wg.tw, wg.d, prow, V, ws, vslot);
-        else launch_wino_input(x, ldx, cin, B, Hin, Win, wg.th, wg.tw, wg.d, prow, V, ws, vslot);
-      }
-      launch_wgrad(a, ws);
-      if (wg.tm == 4) launch_wino4_wgrad_finish(a.ws, a.splits, cout, cin, final_slab, ws);
-      else launch_wino_wgrad_finish(a.ws, a.splits, cout, cin, final_slab, ws);
-    };
-    nslabs = 1;
-  } else {
-    a.g = g; a.x = x; a.ws = e->ws_wg + e->ws_off[ci];
-    a.B = B; a.Ho = Ho; a.Wo = Wo;
-    a.ldg = ldg; a.Cout = c.cout; a.Hi = Hin; a.Wi = Win; a.ldx = ldx; a.Cin = c.cin;
-    a.KH = a.KW = c.k; a.stride = c.stride; a.pad = c.pad; a.dil = c.dil;
-    if (h3_mode() && !amax_init(e)) {
-      a.amax_g = tlookup(e, 1, gkey);
-      if (!a.amax_g) a.amax_g = amax_get(e, AM_G, ci, g, (long)B * Ho * Wo, c.cout, ldg, e->s);
-      // the input activation: the slot of its tensor or of this conv's view from the forward pass, else it is made now
-      a.amax_x = tlookup(e, 0, xkey);
-      if (!a.amax_x) {
-        unsigned* xs = amax_slot(e, AM_X, ci);
-        auto& r = amax_rec_of(e, AM_X, ci);
-        a.amax_x = (r.epoch == e->fwd_epoch && r.ptr == x) ? xs : amax_get(e, AM_X, ci, x, (long)B * Hin * Win, c.cin, ldx, e->s);
-      }
-    }
-    // pre-split operand path: 256 x 256 tiles on the pair8 siblings of g and x when this iteration's producers wrote both;
-    // otherwise the register-staged kernel with the same K splits, which leaves the scales for the next iteration's producers
-    if (presplit_enabled(e) && !e->gn() && a.amax_g && a.amax_x && presplit_wgrad_shape(c, B * Ho * Wo, ldg, ldx)) {
-      const long rows_g = (long)B * Ho * Wo, rows_x = (long)B * Hin * Win;
-      eosvos_engine::PairBuf *xb = nullptr, *gb = nullptr;
-      const bool covx = pair_operand(e, 0, xkey, x, rows_x, c.cin, ldx, xb);
-      const bool covg = pair_operand(e, 1, gkey, g, rows_g, c.cout, ldg, gb);
-      if (xb && gb) {
-        const int par = (int)(e->pair_iter & 1);
-        WgradPArgs pa;
-        memset(&pa, 0, sizeof(pa));
-        pa.g2 = gb->p + (g - gkey) * 4; pa.x2 = xb->p + (x - xkey) * 4; pa.ws = a.ws;
-        pa.B = B; pa.Ho = Ho; pa.Wo = Wo; pa.ldg = ldg; pa.Cout = c.cout; pa.Hi = Hin; pa.Wi = Win; pa.ldx = ldx; pa.Cin = c.cin;
-        pa.KH = pa.KW = c.k; pa.stride = c.stride; pa.pad = c.pad; pa.dil = c.dil;
-        pa.zero = e->pair_zero;
-        pa.scp_g = gb->sc + 1 + par; pa.scp_x = xb->sc + 1 + par;
-        pa.scn_g = gb->sc + 1 + (par ^ 1); pa.scn_x = xb->sc + 1 + (par ^ 1);
-        pa.slot_g = a.amax_g; pa.slot_x = a.amax_x;
-        pa.margin_g = pair_margin(1); pa.margin_x = pair_margin(0);
-        pa.g = g; pa.x = x;
-        a.scn_g = pa.scn_g; a.scn_x = pa.scn_x; a.margin_g = pa.margin_g; a.margin_x = pa.margin_x;
-        xb->fresh = false; gb->fresh = false;        // from the next iteration on their producers have a scale to write with
-        const bool cov = covx && covg;
-        if (wgrad_groupable(e, ci, B)) {
-          e->wgp_pending.push_back({ci, pa, a, cov});
-          return -1;
-        }
-        // K chunks (= slabs) and workgroups per tile: one chunk per workgroup, as many as fill the launch's share of the chip
-        // (wgrad_p_pick_splits).  The kernel can also walk several chunks per workgroup (WgradPArgs::groups < splits: any K partition
-        // with any number of workgroups, bit-identical slabs -- tests/test_gpu_presplit.py).
-        pa.splits = a.splits = wgrad_p_pick_splits(B * Ho * Wo, c.cout, c.cin, c.T(), wgp_budget(e));
-        pa.groups = pa.splits;
-        trace(cov ? "wgrad_p" : "wgrad", ci, c.cout, (long)c.cin * c.T(), (long)B * Ho * Wo, pa.splits, wgrad_exec_frac(a));
-        if (cov) go = [=](hipStream_t ws) { launch_wgrad_p(pa, ws); };
-        else go = [=](hipStream_t ws) { launch_wgrad(a, ws); };
-        nslabs = pa.splits;
-        goto enqueue;
-      }
-    }
-    if (wgrad_groupable(e, ci, B)) {
-      e->wg_pending.push_back({ci, a});
-      return -1;
-    }
-    a.splits = wgrad_pick_splits(B * a.Ho * a.Wo, c.cout, c.cin, c.T(), e->wg_budget);
-    trace("wgrad", ci, c.cout, (long)c.cin * c.T(), (long)B * a.Ho * a.Wo, a.splits, wgrad_exec_frac(a));
-    go = [=](hipStream_t ws) { launch_wgrad(a, ws); };
-    nslabs = a.splits;
-  }
-enqueue:
-  if (e->s2) {
-    hipStream_t s2 = e->s2;
-    e->side_q.push_back([go, s2]() { go(s2); });
-    if ((int)e->side_q.size() >= (B == 1 ? EOSVOS_SIDE_BATCH : 1)) side_flush(e);
-  } else {
-    go(e->s);
-  }
-  return nslabs;
-}
-// reduce slabs, scale by the frozen-norm a[cout], (optionally) theta <- theta - lr*g
-void apply_update(eosvos_engine* e, int ci, int splits, bool /*update*/, bool /*accumulate*/) {
-  if (splits >= 0) e->upd_splits[ci] = splits;     // the slabs stay parked; flush_updates() consumes them
+  WgLaunch go = wino_on(e, ci, B, Ho, Wo) ? wgrad_wino(e, ci, g, ldg, x, ldx, Hin, Win, B, Ho, Wo)
+                                         : wgrad_direct(e, ci, g, ldg, x, ldx, Hin, Win, B, Ho, Wo, gkey, xkey);
+  if (!go) return;
+  side_enqueue(e, std::move(go));
+  if (e->s2 && (int)e->side_q.size() >= (B == 1 ? EOSVOS_SIDE_BATCH : 1)) side_flush(e);
 }
 // one launch: sum every layer's slabs, norm scale, theta <- theta - lr*g, optional gsum/gout
 // part 0: convs [split, nconv) = layer4 + ASPP + decoder (90 % of the parameters), whose backward
@@ -1469,8 +1446,8 @@ bool aspp_dgrad_merged(eosvos_engine* e, int B, float* g_l4, const float* l4) {
   double fl = 0;
   for (int i = 0; i < 4; ++i) fl += 2.0 * a.M * a.N * t.convs[t.aspp[i]].T() * 256.0;
   if (trace_on())
-    fprintf(stderr, "EOSVOS_TRACE dgrad conv=%d M=%d N=%d K=%ld splits=%d flops=%.0f\n", t.aspp[0], a.M, a.N, (long)(a.total_units * 32 / (((a.M + 127) / 128) * ((a.N + 127) / 128))), conv_plan(a),
-            2.0 * 128 * 128 * 32 * (double)a.total_units);
+    trace_line("dgrad", t.aspp[0], a.M, a.N, (long)(a.total_units * 32 / (((a.M + 127) / 128) * ((a.N + 127) / 128))), conv_plan(a),
+               2.0 * 128 * 128 * 32 * (double)a.total_units);
   (void)fl;
   pair_attach(e, 1, g_l4, g_l4, true, a);
   launch_conv(a, e->s);
@@ -1485,8 +1462,6 @@ void plans_match_mode(eosvos_engine* e) {
   if (e->plan_mode == mode) return;
   e->plan_mode = mode;
   e->wg_plans.clear();                             // (the device tables stay allocated until the engine goes: a few KB per switch)
-  e->wgp_plans.clear();
-  e->wgp_splits.clear();
   for (auto& tab : e->upd_tab) tab = nullptr;
   e->wino_v_batch.clear();                         // Winograd selection differs per mode: V / dM of the other mode are stale
   for (auto& kv : e->wino_dm_batch) kv.second = 0;
@@ -2227,36 +2202,32 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     const int chunks = last_bwd_chunks(PA);
     launch_last_bwd(e->d1, e->W_(t.last), e->g_low, e->g_d1, e->ws_wg + e->ws_off[t.last], PA, 256, chunks, s);
     twrite_plain(e, 1, e->g_d1);
-    apply_update(e, t.last, chunks, update, accumulate);
-    int sp = conv_wgrad(e, t.head3, e->g_d1, 256, e->proj, 256, e->h16, e->w16, B);
+    e->upd_splits[t.last] = chunks;
+    conv_wgrad(e, t.head3, e->g_d1, 256, e->proj, 256, e->h16, e->w16, B);
     if (conv_dgrad(e, t.head3, e->g_d1, 256, e->h16, e->w16, e->g_proj, 256, B, false, e->proj, 0)) return 1;
-    apply_update(e, t.head3, sp, update, accumulate);
   } else {
   // classifier conv (Cout = 1)
   {
     const int chunks = last_bwd_chunks(P4);
     launch_last_bwd(e->d2, e->W_(t.last), e->g_low, e->g_d2, e->ws_wg + e->ws_off[t.last], P4, 256, chunks, s);
     twrite_plain(e, 1, e->g_d2);
-    apply_update(e, t.last, chunks, update, accumulate);
+    e->upd_splits[t.last] = chunks;
   }
   // decoder 3x3 convs
   {
-    int sp = conv_wgrad(e, t.dec_b, e->g_d2, 256, e->d1, 256, e->h4, e->w4, B);
+    conv_wgrad(e, t.dec_b, e->g_d2, 256, e->d1, 256, e->h4, e->w4, B);
     if (conv_dgrad(e, t.dec_b, e->g_d2, 256, e->h4, e->w4, e->g_d1, 256, B, false, e->d1, 0)) return 1;
-    apply_update(e, t.dec_b, sp, update, accumulate);
-    sp = conv_wgrad(e, t.dec_a, e->g_d1, 256, e->dcat, 304, e->h4, e->w4, B);
+    conv_wgrad(e, t.dec_a, e->g_d1, 256, e->dcat, 304, e->h4, e->w4, B);
     // channels [0,256) of dcat are the (unclamped) upsampled ASPP output: no ReLU mask there
     if (conv_dgrad(e, t.dec_a, e->g_d1, 256, e->h4, e->w4, e->g_dcat, 304, B, false, e->dcat, 256)) return 1;
-    apply_update(e, t.dec_a, sp, update, accumulate);
   }
   // decoder.conv1 on the low-level feature: raw gradient into g_out of layer1's last block
   {
     float* g_low_feat = e->bb[t.layer1_last_block].g_out;
     const float* low = e->bb[t.layer1_last_block].out;
-    int sp = conv_wgrad(e, t.dec1, e->g_dcat + 256, 304, low, 256, e->h4, e->w4, B, e->g_dcat);
+    conv_wgrad(e, t.dec1, e->g_dcat + 256, 304, low, 256, e->h4, e->w4, B, e->g_dcat);
     if (!frozen && conv_dgrad(e, t.dec1, e->g_dcat + 256, 304, e->h4, e->w4, g_low_feat, 256, B, false, nullptr, 0, nullptr, 0, e->g_dcat))
       return 1;
-    apply_update(e, t.dec1, sp, update, accumulate);
   }
   // decoder upsample backward (+ ReLU mask of the projection output)
   if (!e->m8(e->proj)) return fail("internal: the projection output has no ReLU mask bytes");
@@ -2264,9 +2235,8 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
   }
   // ASPP projection
   {
-    int sp = conv_wgrad(e, t.project, e->g_proj, 256, e->cat, 1280, e->h16, e->w16, B);
+    conv_wgrad(e, t.project, e->g_proj, 256, e->cat, 1280, e->h16, e->w16, B);
     if (conv_dgrad(e, t.project, e->g_proj, 256, e->h16, e->w16, e->g_cat, 1280, B, false, e->cat, 0)) return 1;
-    apply_update(e, t.project, sp, update, accumulate);
   }
   float* g_l4 = e->bb.back().g_out;
   const float* l4 = e->bb.back().out;
@@ -2285,18 +2255,16 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
       launch_bcast_pixels(e->gvec, g_l4, 2048, B, P16, 2048, 1.0f / (float)P16, s);
       twrite_plain(e, 1, g_l4);
     }
-    apply_update(e, t.pool, 1, update, accumulate);
+    e->upd_splits[t.pool] = 1;
   }
   {
-    int sp[4];
-    for (int i = 0; i < 4; ++i) sp[i] = conv_wgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, l4, 2048, e->h16, e->w16, B, e->g_cat);
+    for (int i = 0; i < 4; ++i) conv_wgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, l4, 2048, e->h16, e->w16, B, e->g_cat);
     if (!l4_frozen && !aspp_dgrad_merged(e, B, g_l4, l4)) {
       for (int i = 0; i < 4; ++i)
         if (conv_dgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, e->h16, e->w16, g_l4, 2048, B, true, i == 3 ? l4 : nullptr, 0, nullptr, 0,
                        e->g_cat))
           return 1;
     }
-    for (int i = 0; i < 4; ++i) apply_update(e, t.aspp[i], sp[i], update, accumulate);
   }
   // layer4, ASPP and decoder are done: update them now (on the side stream if there is one)
   auto flush_part0 = [&]() -> int {
@@ -2320,12 +2288,10 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     const Block& b = t.blocks[i];
     auto& f = e->bb[i];
     const int cmid = t.convs[b.c1].cout, cout = t.convs[b.c3].cout;
-    int sp = conv_wgrad(e, b.c3, f.g_out, cout, f.t2, cmid, f.Ho, f.Wo, B);
+    conv_wgrad(e, b.c3, f.g_out, cout, f.t2, cmid, f.Ho, f.Wo, B);
     if (conv_dgrad(e, b.c3, f.g_out, cout, f.Ho, f.Wo, f.g_t2, cmid, B, false, f.t2, 0)) return 1;
-    apply_update(e, b.c3, sp, update, accumulate);
-    sp = conv_wgrad(e, b.c2, f.g_t2, cmid, f.t1, cmid, f.Hm, f.Wm, B);
+    conv_wgrad(e, b.c2, f.g_t2, cmid, f.t1, cmid, f.Hm, f.Wm, B);
     if (conv_dgrad(e, b.c2, f.g_t2, cmid, f.Hm, f.Wm, f.g_t1, cmid, B, false, f.t1, 0)) return 1;
-    apply_update(e, b.c2, sp, update, accumulate);
     // gradient w.r.t. the block input: conv1 path + identity / downsample path
     const bool is_first_block = i == 0;
     // the low-level feature already holds decoder.conv1's contribution
@@ -2334,18 +2300,15 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     // (the block's input is a frozen conv's output: weight gradients only)
     const bool in_frozen = frozen && b.c1 == e->train_from;
     if (b.ds >= 0) {
-      sp = conv_wgrad(e, b.ds, f.g_out, cout, f.xin, f.Cin, f.Hi, f.Wi, B);
+      conv_wgrad(e, b.ds, f.g_out, cout, f.xin, f.Cin, f.Hi, f.Wi, B);
       if (!in_frozen && conv_dgrad(e, b.ds, f.g_out, cout, f.Hi, f.Wi, f.g_xin, f.Cin, B, have, nullptr, 0)) return 1;
-      apply_update(e, b.ds, sp, update, accumulate);
-      sp = conv_wgrad(e, b.c1, f.g_t1, cmid, f.xin, f.Cin, f.Hi, f.Wi, B);
+      conv_wgrad(e, b.c1, f.g_t1, cmid, f.xin, f.Cin, f.Hi, f.Wi, B);
       if (!in_frozen && conv_dgrad(e, b.c1, f.g_t1, cmid, f.Hi, f.Wi, f.g_xin, f.Cin, B, true, inmask, 0)) return 1;
-      apply_update(e, b.c1, sp, update, accumulate);
     } else {
       // identity path: g_xin = mask * (dgrad_conv1(g_t1) + g_out)
       if (have) return fail("internal: identity block after the low-level tap is unsupported");
-      sp = conv_wgrad(e, b.c1, f.g_t1, cmid, f.xin, f.Cin, f.Hi, f.Wi, B);
+      conv_wgrad(e, b.c1, f.g_t1, cmid, f.xin, f.Cin, f.Hi, f.Wi, B);
       if (conv_dgrad(e, b.c1, f.g_t1, cmid, f.Hi, f.Wi, f.g_xin, f.Cin, B, false, inmask, 0, f.g_out, cout)) return 1;
-      apply_update(e, b.c1, sp, update, accumulate);
     }
     // first block of a ResNet layer: its data-gradient chain is queued, every operand of the stage's weight gradients
     // is final -> one grouped launch per tile shape
@@ -2369,7 +2332,7 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     }
     if (ag) launch_stem_wgrad_h3(e->xpad, gc1, e->ws_wg + e->ws_off[0], B, e->H, e->W, e->h2, e->w2, chunks, ag, amax_slot(e, AM_X, 0), s);
     else launch_stem_wgrad(e->xpad, gc1, e->ws_wg + e->ws_off[0], B, e->H, e->W, e->h2, e->w2, chunks, s);
-    apply_update(e, 0, chunks, update, accumulate);
+    e->upd_splits[0] = chunks;
   }
   }
   if (e->s2) side_flush(e);
@@ -3009,6 +2972,7 @@ int eosvos_bench_conv(eosvos_engine* e, int ci, int kind, int batch, int reps, f
   e->s2 = nullptr;                 // time everything on the main stream
   const bool group_was = e->wg_group_on;
   e->wg_group_on = false;          // one layer at a time: its own launch
+  const int splits_was = e->upd_splits[ci];      // (conv_wgrad records the slab count of that launch)
   run();
   HIPOK(hipEventRecord(a, e->s));
   for (int i = 0; i < reps; ++i) run();
@@ -3016,6 +2980,7 @@ int eosvos_bench_conv(eosvos_engine* e, int ci, int kind, int batch, int reps, f
   HIPOK(hipEventSynchronize(b));
   e->s2 = side;
   e->wg_group_on = group_was;
+  e->upd_splits[ci] = splits_was;
   float ms = 0.f;
   HIPOK(hipEventElapsedTime(&ms, a, b));
   *ms_host = ms / reps;
@@ -3177,13 +3142,13 @@ int eosvos_test_conv_bwd_algo(eosvos_engine* e, int algo, const float* x, const 
   launch_oihw_to_ohwi(w_oihw, t->Wp, Cout, Cin, T, t->s);
   if (scale) HIPOK(hipMemcpyAsync(t->na, scale, (size_t)Cout * 4, hipMemcpyDeviceToDevice, t->s));
   // the order of the backward pass: weight gradient first (it makes the shared Winograd-domain dM), then data gradient
-  const int nslabs = conv_wgrad(t, 0, g, Cout, x, Cin, H, W, B);
+  conv_wgrad(t, 0, g, Cout, x, Cin, H, W, B);
   if (m8) t->mask8[x] = const_cast<uint8_t*>(m8);        // the mask bytes of x, as the forward pass would have left them
   if (conv_dgrad(t, 0, g, Cout, H, W, dx, Cin, B, false, m8 ? x : nullptr, 0)) return 1;
   float* dw = t->falloc((int64_t)Cout * Cin * T);
   if (!dw) return fail("hipMalloc dw");
   const int64_t n = (int64_t)Cout * Cin * T;
-  launch_sgd_update(dw, t->ws_wg, nslabs, n, scale ? t->na : nullptr, nullptr, nullptr, dw, (int64_t)T * Cin, n, t->s);
+  launch_sgd_update(dw, t->ws_wg, t->upd_splits[0], n, scale ? t->na : nullptr, nullptr, nullptr, dw, (int64_t)T * Cin, n, t->s);
   launch_ohwi_to_oihw(dw, dw_oihw, Cout, Cin, T, 1.f, 0, t->s);
   HIPOK(hipStreamSynchronize(t->s));
   HIPOK(hipGetLastError());
@@ -3293,7 +3258,7 @@ int eosvos_test_aspp_pool(eosvos_engine* e, int B, int P, int K, int N, const fl
     launch_colsum(gy, ldgy, gpool, B, P, N, 1.f, colscratch, e->s);
     launch_gemv_bwd(w, v, gpool, a, gv, slab, B, N, K, e->s);
     launch_bcast_pixels(gv, gx, ldgx, B, P, K, 1.0f / (float)P, e->s);
-    // the weight update's reduction (apply_update): the slab times the folded-norm scale of each output channel
+    // the weight update's reduction (flush_updates): the slab times the folded-norm scale of each output channel
     launch_sgd_update(dw, slab, 1, (int64_t)N * K, a, nullptr, nullptr, dw, K, (int64_t)N * K, e->s);
   }
   HIPOK(hipStreamSynchronize(e->s));
@@ -3313,7 +3278,7 @@ int eosvos_test_head(eosvos_engine* e, const float* x, const float* w, const flo
     float* ws = sc.t.falloc((int64_t)chunks * (C + 1));
     if (!ws) return fail("hipMalloc head weight-gradient slabs");
     launch_last_bwd(x, w, g, gx, ws, P, C, chunks, e->s);
-    launch_sgd_update(dw, ws, chunks, C + 1, nullptr, nullptr, nullptr, dw, C + 1, C + 1, e->s);      // slab sum, as apply_update
+    launch_sgd_update(dw, ws, chunks, C + 1, nullptr, nullptr, nullptr, dw, C + 1, C + 1, e->s);      // slab sum, as flush_updates
   }
   HIPOK(hipStreamSynchronize(e->s));
   HIPOK(hipGetLastError());
