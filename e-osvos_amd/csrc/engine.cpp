@@ -197,6 +197,7 @@ struct eosvos_engine {
   bool keep_grads = false;
   // learned-lr storage level (meta_optim.py:27-67): the update consumes `lr` (per neuron) or `lr_elem`
   int loss_kind = EOSVOS_LOSS_BCE;      // loss of the fused entry points (eosvos_set_loss)
+  float* lovasz_scratch = nullptr;      // sort buffers of the Lovasz hinge kinds, allocated when one is first selected or used
   int* aug_tab = nullptr;               // eosvos_warp_affine: adelta[W] bdelta[W] X0[H] Y0[H], then the nonzero counter
   float* aug_ctab = nullptr;            // bicubic coefficients at 1/32 pixel: [32][4]
   void* davis_buf = nullptr;            // eosvos_davis_counts: counts + bit-packed boundary maps (grow-only, freed by destroy)
@@ -2367,10 +2368,36 @@ int eosvos_loss_bce(eosvos_engine* e, const float* masks, int batch, float* loss
   HIPOK(hipGetLastError());
   return 0;
 }
+namespace {
+inline bool lovasz_kind(int kind) { return kind == EOSVOS_LOSS_LOVASZ_HINGE || kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT; }
+// the Lovasz kinds' sort scratch, sized for the engine's largest batch; 0 on success
+int lovasz_ensure(eosvos_engine* e) {
+  if (e->lovasz_scratch) return 0;
+  const int64_t n = (int64_t)e->maxB * e->H * e->W;
+  if (n >= ((int64_t)1 << 30)) return fail("lovasz hinge: too many pixels for 32-bit sort values");
+  e->lovasz_scratch = e->falloc(lovasz_scratch_floats(n, e->maxB));
+  if (!e->lovasz_scratch) {
+    (void)hipGetLastError();              // the failed hipMalloc must not surface in a later call's launch check
+    return fail("lovasz hinge: out of device memory for the sort scratch");
+  }
+  return 0;
+}
+}  // namespace
+
 int eosvos_loss(eosvos_engine* e, int kind, const float* masks, int batch, float* loss_out) {
   ModeScope mode_scope(e);
   if (kind == EOSVOS_LOSS_BCE) return eosvos_loss_bce(e, masks, batch, loss_out);
   if (!e || !masks) return fail("null argument");
+  if (lovasz_kind(kind)) {
+    if (batch != e->lastB) return fail("loss batch differs from the last forward");
+    if (lovasz_ensure(e)) return 1;
+    launch_lovasz(e->logits, masks, e->dlogits, e->loss_dev, e->lovasz_scratch, (int64_t)e->H * e->W, batch,
+                  kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT, e->s);
+    e->have_loss_grad = true;
+    if (loss_out) HIPOK(hipMemcpyAsync(loss_out, e->loss_dev, 4, hipMemcpyDeviceToDevice, e->s));
+    HIPOK(hipGetLastError());
+    return 0;
+  }
   if (kind != EOSVOS_LOSS_DICE && kind != EOSVOS_LOSS_BCE_DICE && kind != EOSVOS_LOSS_CLASS_BALANCED_BCE)
     return fail("unknown loss kind");
   if (batch != e->lastB) return fail("loss batch differs from the last forward");
@@ -2387,7 +2414,8 @@ int eosvos_last_loss(eosvos_engine* e, float* loss_out) {
 }
 int eosvos_set_loss(eosvos_engine* e, int kind) {
   if (!e) return fail("null engine");
-  if (kind < EOSVOS_LOSS_BCE || kind > EOSVOS_LOSS_CLASS_BALANCED_BCE) return fail("unknown loss kind");
+  if (kind < EOSVOS_LOSS_BCE || kind > EOSVOS_LOSS_LOVASZ_HINGE_FLAT) return fail("unknown loss kind");
+  if (lovasz_kind(kind) && lovasz_ensure(e)) return 1;
   e->loss_kind = kind;
   return 0;
 }
@@ -2407,6 +2435,14 @@ int eosvos_loss_tensors(eosvos_engine* e, int kind, const float* logits, const f
   ModeScope mode_scope(e);
   if (kind == EOSVOS_LOSS_BCE) return eosvos_bce(e, logits, masks, n, loss_out, nullptr);
   if (!e || !logits || !masks || !loss_out || n < 1) return fail("bad argument");
+  if (lovasz_kind(kind)) {                  // the n elements are one set for either kind
+    if (n > (int64_t)e->maxB * e->H * e->W) return fail("n exceeds the engine's scratch");
+    if (lovasz_ensure(e)) return 1;
+    e->have_loss_grad = false;              // the gradient scratch is overwritten
+    launch_lovasz(logits, masks, e->dlogits, loss_out, e->lovasz_scratch, n, 1, 1, e->s);
+    HIPOK(hipGetLastError());
+    return 0;
+  }
   if (kind != EOSVOS_LOSS_DICE && kind != EOSVOS_LOSS_BCE_DICE && kind != EOSVOS_LOSS_CLASS_BALANCED_BCE)
     return fail("unknown loss kind");
   if (n > (int64_t)e->maxB * e->H * e->W) return fail("n exceeds the engine's scratch");

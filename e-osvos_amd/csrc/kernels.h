@@ -370,6 +370,13 @@ void launch_bce(const float* logits, const float* gt, float* dlogits, float* los
 // dice (kind 1) / BCE - log(1 - dice) (kind 2), whole batch flattened; partial >= 4*1024+4 floats
 void launch_dice(const float* logits, const float* gt, float* dlogits, float* loss, float* partial, int64_t n, int kind,
                  hipStream_t s);
+// Lovasz hinge (lovasz_kernels.hip; loss_lovasz.py:78-111): `images` sets of n_per_image pixels, the loss their mean and each
+// gradient scaled by 1 / images -- or, with `flat`, the whole batch as one set.  A per-image stable radix sort of the
+// positive errors, a scan of the label bits and a scatter of the gradient; bit-reproducible.  scratch: lovasz_scratch_floats
+// (n_per_image * images, images) floats; n_per_image * images < 2^31.
+int64_t lovasz_scratch_floats(int64_t n_total, int max_images);
+void launch_lovasz(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_image,
+                   int images, int flat, hipStream_t s);
 void launch_sigmoid(const float* x, float* y, int64_t n, hipStream_t s);
 void launch_merge_labels(const float* probs, int n_obj, int64_t n_pix, uint8_t* labels, hipStream_t s);
 // cv2.warpAffine (+ optional horizontal flip of the source) of C planes; tables = adelta[W] bdelta[W] X0[H] Y0[H]

@@ -49,7 +49,8 @@ def _touched(*tensors):
 
 
 LR_LEVELS = {'NEURON': 0, 'TENSOR': 1, 'SINGLE': 2, 'PARAM': 3}      # include/eosvos.h EOSVOS_LR_*
-LOSS_KINDS = {'cross_entropy': 0, 'dice': 1, 'cross_entropy_and_dice': 2, 'class_balanced_cross_entropy': 3}
+LOSS_KINDS = {'cross_entropy': 0, 'dice': 1, 'cross_entropy_and_dice': 2, 'class_balanced_cross_entropy': 3,
+              'lovasz_hinge': 4, 'lovasz_hinge_flat': 5}      # the last two: networks/loss_lovasz.py:78-111, per_image True / False
 
 
 def set_matrix_mode(mode):

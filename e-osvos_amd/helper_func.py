@@ -8,8 +8,9 @@
   EpochSampler        `helper_func.py:521-545`
   set_random_seeds    `helper_func.py:515-518`
 `dice` (`networks/loss_dice.py:4-40`), `cross_entropy_and_dice` (`:45-54`) and
-`class_balanced_cross_entropy` (`networks/loss_ce.py:15-60`) run as fused HIP kernels too; unknown
-names raise NotImplementedError as in the reference (`:55-56`).
+`class_balanced_cross_entropy` (`networks/loss_ce.py:15-60`) run as fused HIP kernels too, and so does the
+Lovasz hinge of `networks/loss_lovasz.py:78-111` as `lovasz_hinge` (`per_image=True`, the reference default) and
+`lovasz_hinge_flat` (`per_image=False`); unknown names raise NotImplementedError as in the reference (`:55-56`).
 """
 import random
 
@@ -23,8 +24,11 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
     """`compute_loss(loss_func, outputs, gts, loss_kwargs=None)`, helper_func.py:28-56.  The returned
     0-dim loss carries the engine handle so `MetaOptimizer.step(loss)` can run the backward."""
     loss_kwargs = loss_kwargs or {}
-    if loss_func not in ('cross_entropy', 'dice', 'cross_entropy_and_dice', 'class_balanced_cross_entropy'):
+    if loss_func not in ('cross_entropy', 'dice', 'cross_entropy_and_dice', 'class_balanced_cross_entropy',
+                         'lovasz_hinge', 'lovasz_hinge_flat'):
         raise NotImplementedError(f"loss_func='{loss_func}'")
+    if loss_func == 'lovasz_hinge' and not loss_kwargs.get('per_image', True):
+        loss_func = 'lovasz_hinge_flat'                    # loss_lovasz.py:89-90: the whole batch as one set
     if loss_func == 'class_balanced_cross_entropy' and not loss_kwargs.get('size_average', True):
         raise NotImplementedError('class_balanced_cross_entropy with size_average=False')
     eng = getattr(outputs, '_eosvos_engine', None)

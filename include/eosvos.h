@@ -178,6 +178,15 @@ int eosvos_loss_bce(eosvos_engine* e, const float* masks, int batch, float* loss
 #define EOSVOS_LOSS_DICE 1
 #define EOSVOS_LOSS_BCE_DICE 2
 #define EOSVOS_LOSS_CLASS_BALANCED_BCE 3 /* `class_balanced_cross_entropy`, networks/loss_ce.py:15-60 */
+/* Lovasz hinge, the Jaccard hinge (networks/loss_lovasz.py:78-111): errors e = 1 - x * (2 * (t >= .5) - 1) ranked in
+ * descending order (ties by ascending pixel index), weighted by the increments of the Jaccard loss along that order.
+ * EOSVOS_LOSS_LOVASZ_HINGE = `per_image=True` (the reference default): the mean over the images of the batch;
+ * EOSVOS_LOSS_LOVASZ_HINGE_FLAT = `per_image=False`: the whole batch is one set.  Through eosvos_loss_tensors the n
+ * elements are one set for either kind.  A non-finite logit makes the loss NaN.  The first use of either kind allocates
+ * the sort scratch (16 bytes per pixel of the largest batch) once; a failed allocation is reported and leaves the
+ * engine usable with the other kinds. */
+#define EOSVOS_LOSS_LOVASZ_HINGE 4
+#define EOSVOS_LOSS_LOVASZ_HINGE_FLAT 5
 int eosvos_loss(eosvos_engine* e, int kind, const float* masks, int batch, float* loss_out);
 /* The value of the last loss evaluated by eosvos_loss* / eosvos_finetune_step / eosvos_meta_grad*, copied to a DEVICE
  * float on the engine's stream without synchronising (several engines in flight on one GPU: concurrent meta tasks). */
