@@ -638,7 +638,7 @@ void trace(const char* kind, int ci, long M, long N, long K, int splits, double 
   plan_mix((uint64_t)ci); plan_mix((uint64_t)M); plan_mix((uint64_t)N); plan_mix((uint64_t)K); plan_mix((uint64_t)splits);
   trace_line(kind, ci, M, N, K, splits, 2.0 * M * N * K * frac);
 }
-// Winograd F(2x2,3x3) path (forward, data gradient, weight gradient) of 3x3 / stride 1 convs: 2.25x fewer MACs,
+// Winograd F(2x2,3x3) / F(4x4,3x3) path (forward, data gradient, weight gradient) of 3x3 / stride 1 convs: 2.25x / 4x fewer MACs,
 // paid for with HBM-bound transform passes.  Always on for the decoder's two convs on the stride-4 map (27 % of a
 // batch-3 iteration's FLOPs); for the dilated / undilated conv2 of layer3 / layer4 only when the launch is large
 // enough for the extra passes to pay (EOSVOS_WINO_MINWORK multiply-accumulates per Winograd position).
@@ -680,18 +680,28 @@ bool wino_on(const eosvos_engine* e, int ci, int B, int Ho, int Wo) {
   if (conv_mfma_mode() == 2) return false;
   return (long long)B * Ho * Wo / 4 * c.cin * c.cout >= EOSVOS_WINO_MINWORK;      // MACs of one F(2,3) position
 }
-// The batched GEMM of a Winograd forward: rows = 16 planes x prow tiles of V, weights U[p] per plane -> M planes
-ConvArgs wino_fwd_gemm(eosvos_engine* e, int ci, const WinoGeom& wg, float* ws) {
-  const ConvL& c = e->t.convs[ci];
-  const long prow = wg.prow;
+// The batched plane GEMM of a Winograd pass: rows = np planes x prow tiles of x, one [cout][cin] weight matrix per plane.
+// Forward (kmajor 0): V x U -> M planes, K = cin, N = cout; data gradient (kmajor 1): dM x Us -> dV planes, K = cout, N = cin
+ConvArgs wino_plane_gemm(const eosvos_engine* e, const ConvL& c, const WinoGeom& wg, const float* x, const float* w, float* y,
+                         float* ws, int kmajor) {
+  const int K = kmajor ? c.cout : c.cin, N = kmajor ? c.cin : c.cout;
   ConvArgs m;
   memset(&m, 0, sizeof(m));
   m.wg_budget = e->wg_budget;
-  m.x = e->wino_V[ci]; m.w = e->wino_U[ci]; m.y = e->wino_m; m.ws = ws; m.nplanes = wg.np;
-  m.B = 1; m.Hi = 1; m.Wi = (int)(wg.np * prow); m.ldx = c.cin; m.Kc = c.cin;
-  m.Ho = 1; m.Wo = m.Wi; m.N = c.cout; m.ldy = c.cout; m.KH = m.KW = 1; m.mul = 1;
-  m.M = m.Wi; m.wN = c.cout; m.wK = c.cin; m.plane_rows = (int)prow; m.w_plane = (long)c.cout * c.cin;
+  m.x = x; m.w = w; m.y = y; m.ws = ws; m.nplanes = wg.np;
+  m.B = 1; m.Hi = 1; m.Wi = (int)(wg.np * wg.prow); m.ldx = K; m.Kc = K;
+  m.Ho = 1; m.Wo = m.Wi; m.N = N; m.ldy = N; m.KH = m.KW = 1; m.mul = 1;
+  m.M = m.Wi; m.wN = c.cout; m.wK = c.cin; m.kmajor = kmajor; m.plane_rows = (int)wg.prow; m.w_plane = (long)c.cout * c.cin;
   return m;
+}
+// U = G w G^T and Us = a[cout] * U (the data gradient's copy) of conv ci: remade on stream st when the weights changed
+// since they were last made
+void wino_ensure_weights(eosvos_engine* e, int ci, int tm, hipStream_t st) {
+  if (e->wino_us_valid[ci]) return;
+  const ConvL& c = e->t.convs[ci];
+  unsigned* us = amax_wino_weights(e, ci, st);
+  launch_wino_weight(tm, e->W_(ci), c.cout, c.cin, e->A_(ci), e->wino_U[ci], e->wino_Us[ci], st, us, us ? us + e->t.convs.size() : nullptr);
+  e->wino_us_valid[ci] = 1;
 }
 // `side`: launch on the side stream with its own stream-K workspace (forward branches that do not depend on
 // each other: downsample convs, decoder.conv1)
@@ -721,18 +731,11 @@ void conv_fwd(eosvos_engine* e, int ci, const float* x, int ldx, int Hi, int Wi,
     // U = G w G^T (and a[cout] * U for the data gradient) only when the weights changed since it was last made; a
     // forward with a side stream has already queued all of them there (forward_impl), beside layer1..3
     if (e->wino_w_wait) { (void)hipStreamWaitEvent(st, e->ev_wino_w, 0); e->wino_w_wait = false; }
-    if (!e->wino_us_valid[ci]) {
-      unsigned* us = amax_wino_weights(e, ci, st);
-      if (wg.tm == 4) launch_wino4_weight(e->W_(ci), c.cout, c.cin, e->A_(ci), e->wino_U[ci], e->wino_Us[ci], st, us, us ? us + e->t.convs.size() : nullptr);
-      else launch_wino_weight(e->W_(ci), c.cout, c.cin, e->A_(ci), e->wino_U[ci], e->wino_Us[ci], st, us, us ? us + e->t.convs.size() : nullptr);
-      e->wino_us_valid[ci] = 1;
-    }
+    wino_ensure_weights(e, ci, wg.tm, st);
     unsigned* vslot = amax_fused_slot(e, AM_V, ci, e->wino_V[ci], st);   // the input transform accumulates max|V| itself
-    if (wg.tm == 4) launch_wino4_input(x, ldx, c.cin, B, Hi, Wi, th, tw, wg.d, prow, e->wino_V[ci], st, vslot);
-    else launch_wino_input(x, ldx, c.cin, B, Hi, Wi, th, tw, wg.d, prow, e->wino_V[ci], st, vslot);
+    launch_wino_input(wg.tm, x, ldx, c.cin, B, Hi, Wi, th, tw, wg.d, prow, e->wino_V[ci], st, vslot);
     e->wino_v_batch[ci] = B;
-    ConvArgs m = wino_fwd_gemm(e, ci, wg, a.ws);
-    m.wg_budget = a.wg_budget;
+    ConvArgs m = wino_plane_gemm(e, c, wg, e->wino_V[ci], e->wino_U[ci], e->wino_m, a.ws, 0);
     if (vslot) { m.amax_x = vslot; m.amax_w = amax_slot(e, AM_U, ci); }
     // the output transform writes y (directly, or the raw conv output of the GroupNorm mode)
     // (GroupNorm mode: the output transform writes the raw conv output; y and its absmax come from the GroupNorm apply pass)
@@ -741,12 +744,8 @@ void conv_fwd(eosvos_engine* e, int ci, const float* x, int ldx, int Hi, int Wi,
     uint8_t* ym8 = (gn || !e->m8w(ykey)) ? nullptr : e->m8w(ykey) + (y - ykey) / 4;
     trace("fwd", ci, m.M, m.N, c.cin, conv_plan(m));
     launch_conv(m, st);
-    if (wg.tm == 4)
-      launch_wino4_output(e->wino_m, prow, c.cout, B, a.Ho, a.Wo, th, tw, wg.d, gn ? nullptr : e->A_(ci), gn ? nullptr : e->B_(ci),
-                          (!gn && relu) ? 1 : 0, gn ? e->zbuf[ci] : y, gn ? c.cout : ldy, st, yslot, ym8, ldy / 4);
-    else
-      launch_wino_output(e->wino_m, prow, c.cout, B, a.Ho, a.Wo, th, tw, wg.d, gn ? nullptr : e->A_(ci), gn ? nullptr : e->B_(ci),
-                         (!gn && relu) ? 1 : 0, gn ? e->zbuf[ci] : y, gn ? c.cout : ldy, st, yslot, ym8, ldy / 4);
+    launch_wino_output(wg.tm, e->wino_m, prow, c.cout, B, a.Ho, a.Wo, th, tw, wg.d, gn ? nullptr : e->A_(ci), gn ? nullptr : e->B_(ci),
+                       (!gn && relu) ? 1 : 0, gn ? e->zbuf[ci] : y, gn ? c.cout : ldy, st, yslot, ym8, ldy / 4);
     if (gn)
       launch_gn_forward(e->zbuf[ci], c.cout, e->G_(ci), e->nb + c.noff, res, ldres, y, ldy, e->gn_stats[ci], e->gn_partial, B,
                         a.Ho * a.Wo, c.cout, 1e-5f, relu ? 1 : 0, st, yslot_any, (relu && e->m8w(ykey)) ? e->m8w(ykey) + (y - ykey) / 4 : nullptr, ldy / 4);
@@ -778,6 +777,22 @@ void conv_fwd(eosvos_engine* e, int ci, const float* x, int ldx, int Hi, int Wi,
     launch_gn_forward(e->zbuf[ci], c.cout, e->G_(ci), e->nb + c.noff, res, ldres, y, ldy, e->gn_stats[ci], e->gn_partial, B,
                       a.Ho * a.Wo, c.cout, 1e-5f, relu ? 1 : 0, st, gn ? gn_yslot : nullptr,
                       (relu && e->m8w(ykey)) ? e->m8w(ykey) + (y - ykey) / 4 : nullptr, ldy / 4);
+}
+// A data-gradient GEMM whose N leaves a tail of <= 64 columns over whole 128-wide column tiles, e.g. the decoder's 304
+// input channels: 2 column tiles of 128 + a 64-wide launch instead of 3 x 128 (the 128-wide kernel would spend a third of
+// its MFMAs on 80 padding columns)
+bool dgrad_has_tail(const ConvArgs& a) { return a.N > 128 && a.N % 128 > 0 && a.N % 128 <= 64; }
+void launch_dgrad_tail_split(eosvos_engine* e, int ci, ConvArgs a, long K) {
+  const int tail = a.N % 128;
+  ConvArgs b = a;
+  a.N -= tail;
+  trace("dgrad", ci, a.M, a.N, K, conv_plan(a));
+  launch_conv(a, e->s);
+  b.N = tail; b.w += a.N; b.y += a.N;
+  if (b.mask8) { b.mask8 += a.N / 4; b.mask_c0 = b.mask_c0 > a.N ? b.mask_c0 - a.N : 0; }      // (the Winograd plane GEMM has neither)
+  if (b.res) b.res += a.N;
+  trace("dgrad", ci, b.M, b.N, K, conv_plan(b));
+  launch_conv(b, e->s);
 }
 // gx[B,Hin,Win,cin] (ld ldgx) (+)= dgrad of conv ci applied to g[B,Ho,Wo,cout] (ld ldg), zero in channels >= mask_c0
 // where the ReLU mask of `relu_x` (the forward activation gx is the gradient of: same layout) is clear.  relu_x must
@@ -813,52 +828,30 @@ int conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int W
     a.amax_y = twrite_fused(e, 1, gxkey, ldgx == c.cin);
   }
   if (wino_dg) {
-    // Winograd data gradient: dV[p] = dM[p] (a[cout] U[p]), 16 GEMMs [tiles x cout] x [cout x cin] in one batched
-    // launch, then dX = mask(B dV B^T) gathered per 2x2 pixel block
+    // Winograd data gradient: dV[p] = dM[p] (a[cout] U[p]), 16 / 36 GEMMs [tiles x cout] x [cout x cin] in one batched
+    // launch, then dX = mask(B dV B^T) gathered per 2x2 / 4x4 pixel block
     const WinoGeom wg = wino_geom(e, c, B, Hin, Win);
     const int th = wg.th, tw = wg.tw;
     const long prow = wg.prow;
     if (e->wino_dm_batch[ci] != B) {
       unsigned* dms = amax_fused_slot(e, AM_DM, ci, e->wino_dM[ci], e->s);
-      if (wg.tm == 4) launch_wino4_grad(g, ldg, c.cout, B, Hin, Win, th, tw, wg.d, prow, e->wino_dM[ci], e->s, dms);
-      else launch_wino_grad(g, ldg, c.cout, B, Hin, Win, th, tw, wg.d, prow, e->wino_dM[ci], e->s, dms);
+      launch_wino_grad(wg.tm, g, ldg, c.cout, B, Hin, Win, th, tw, wg.d, prow, e->wino_dM[ci], e->s, dms);
     }
     e->wino_dm_batch[ci] = 0;
-    if (!e->wino_us_valid[ci]) {                     // no forward since the weights changed: rebuild a[cout] * U
-      unsigned* us = amax_wino_weights(e, ci, e->s);
-      if (wg.tm == 4) launch_wino4_weight(e->W_(ci), c.cout, c.cin, e->A_(ci), e->wino_U[ci], e->wino_Us[ci], e->s, us, us ? us + e->t.convs.size() : nullptr);
-      else launch_wino_weight(e->W_(ci), c.cout, c.cin, e->A_(ci), e->wino_U[ci], e->wino_Us[ci], e->s, us, us ? us + e->t.convs.size() : nullptr);
-      e->wino_us_valid[ci] = 1;
-    }
-    ConvArgs m;
-    memset(&m, 0, sizeof(m));
-    m.wg_budget = a.wg_budget;
+    wino_ensure_weights(e, ci, wg.tm, e->s);         // no forward since the weights changed: rebuild a[cout] * U
+    ConvArgs m = wino_plane_gemm(e, c, wg, e->wino_dM[ci], e->wino_Us[ci], e->wino_dv, e->ws_conv, 1);
     if (h3_mode() && !amax_init(e)) {
       m.amax_x = amax_get(e, AM_DM, ci, e->wino_dM[ci], (long)wg.np * prow, c.cout, c.cout, e->s);   // made by the transform
       m.amax_w = amax_slot(e, AM_US, ci);
     }
     unsigned* gxs = twrite_fused(e, 1, gxkey, ldgx == c.cin);
-    m.x = e->wino_dM[ci]; m.w = e->wino_Us[ci]; m.y = e->wino_dv; m.ws = e->ws_conv; m.nplanes = wg.np;
-    m.B = 1; m.Hi = 1; m.Wi = (int)(wg.np * prow); m.ldx = c.cout; m.Kc = c.cout;
-    m.Ho = 1; m.Wo = m.Wi; m.N = c.cin; m.ldy = c.cin; m.KH = m.KW = 1; m.mul = 1;
-    m.M = m.Wi; m.wN = c.cout; m.wK = c.cin; m.kmajor = 1; m.plane_rows = (int)prow; m.w_plane = (long)c.cout * c.cin;
-    const int tailw = m.N % 128;
-    if (m.N > 128 && tailw > 0 && tailw <= 64) {      // 304 = 2 x 128-wide column tiles + a 64-wide launch
-      ConvArgs b = m;
-      m.N -= tailw;
-      trace("dgrad", ci, m.M, m.N, c.cout, conv_plan(m));
-      launch_conv(m, e->s);
-      b.N = tailw; b.w += m.N; b.y += m.N;
-      trace("dgrad", ci, b.M, b.N, c.cout, conv_plan(b));
-      launch_conv(b, e->s);
+    if (dgrad_has_tail(m)) {
+      launch_dgrad_tail_split(e, ci, m, c.cout);
     } else {
       trace("dgrad", ci, m.M, m.N, c.cout, conv_plan(m));
       launch_conv(m, e->s);
     }
-    if (wg.tm == 4)
-      launch_wino4_dgrad_output(e->wino_dv, prow, c.cin, B, Hin, Win, th, tw, wg.d, mask8, a.ldm8, mask_c0, accum ? 1 : 0, gx, ldgx, e->s, gxs);
-    else
-      launch_wino_dgrad_output(e->wino_dv, prow, c.cin, B, Hin, Win, th, tw, wg.d, mask8, a.ldm8, mask_c0, accum ? 1 : 0, gx, ldgx, e->s, gxs);
+    launch_wino_dgrad_output(wg.tm, e->wino_dv, prow, c.cin, B, Hin, Win, th, tw, wg.d, mask8, a.ldm8, mask_c0, accum ? 1 : 0, gx, ldgx, e->s, gxs);
     return 0;
   }
   if (c.k == 1 && c.stride == 2 && !add) {
@@ -868,19 +861,8 @@ int conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int W
     a.Ho = a.Hi; a.Wo = a.Wi; a.mul = 1; a.off0 = 0; a.kstep = 0; a.upshift = 0;
     a.M = B * a.Ho * a.Wo; a.dst_up = 1; a.Hf = Hin; a.Wf = Win;
   }
-  const int tail = a.N % 128;
-  if (a.N > 128 && tail > 0 && tail <= 64 && !a.dst_up && !(c.k == 3 && c.dil >= 2)) {
-    // e.g. the decoder's 304 input channels: 2 column tiles of 128 + one of 64 instead of 3 x 128
-    // (the 128-wide kernel would spend a third of its MFMAs on 80 padding columns)
-    ConvArgs b = a;
-    a.N -= tail;
-    trace("dgrad", ci, a.M, a.N, (long)c.T() * c.cout, conv_plan(a));
-    launch_conv(a, e->s);
-    b.N = tail; b.w += a.N; b.y += a.N;
-    if (b.mask8) { b.mask8 += a.N / 4; b.mask_c0 = b.mask_c0 > a.N ? b.mask_c0 - a.N : 0; }
-    if (b.res) b.res += a.N;
-    trace("dgrad", ci, b.M, b.N, (long)c.T() * c.cout, conv_plan(b));
-    launch_conv(b, e->s);
+  if (dgrad_has_tail(a) && !a.dst_up && !(c.k == 3 && c.dil >= 2)) {
+    launch_dgrad_tail_split(e, ci, a, (long)c.T() * c.cout);
     return 0;
   }
   attach_tap_table(e, ci, 1, B, a);
@@ -1207,8 +1189,7 @@ WgLaunch wgrad_wino(eosvos_engine* e, int ci, const float* g, int ldg, const flo
   const ConvL& c = e->t.convs[ci];
   const WinoGeom wg = wino_geom(e, c, B, Ho, Wo);
   unsigned* dms = amax_fused_slot(e, AM_DM, ci, e->wino_dM[ci], e->s);
-  if (wg.tm == 4) launch_wino4_grad(g, ldg, c.cout, B, Ho, Wo, wg.th, wg.tw, wg.d, wg.prow, e->wino_dM[ci], e->s, dms);
-  else launch_wino_grad(g, ldg, c.cout, B, Ho, Wo, wg.th, wg.tw, wg.d, wg.prow, e->wino_dM[ci], e->s, dms);
+  launch_wino_grad(wg.tm, g, ldg, c.cout, B, Ho, Wo, wg.th, wg.tw, wg.d, wg.prow, e->wino_dM[ci], e->s, dms);
   e->wino_dm_batch[ci] = B;
   const long ntile = wg.ntile, prow = wg.prow;
   float* V = e->wino_V[ci];
@@ -1239,12 +1220,10 @@ WgLaunch wgrad_wino(eosvos_engine* e, int ci, const float* g, int ldg, const flo
   return [=](hipStream_t ws) {
     if (need_v) {
       if (h3) amax_zero(vslot, 1, ws);
-      if (wg.tm == 4) launch_wino4_input(x, ldx, cin, B, Hin, Win, wg.th, wg.tw, wg.d, prow, V, ws, vslot);
-      else launch_wino_input(x, ldx, cin, B, Hin, Win, wg.th, wg.tw, wg.d, prow, V, ws, vslot);
+      launch_wino_input(wg.tm, x, ldx, cin, B, Hin, Win, wg.th, wg.tw, wg.d, prow, V, ws, vslot);
     }
     launch_wgrad(a, ws);
-    if (wg.tm == 4) launch_wino4_wgrad_finish(a.ws, a.splits, cout, cin, final_slab, ws);
-    else launch_wino_wgrad_finish(a.ws, a.splits, cout, cin, final_slab, ws);
+    launch_wino_wgrad_finish(wg.tm, a.ws, a.splits, cout, cin, final_slab, ws);
   };
 }
 // Pre-split operand path: 256 x 256 tiles on the pair8 siblings of g and x when this iteration's producers wrote both
@@ -2095,10 +2074,7 @@ static int forward_impl(eosvos_engine* e, const float* images, int B) {
       const int Ho = conv_out(e->conv_hin[ci], c.k, c.stride, c.dil, c.pad), Wo = conv_out(e->conv_win[ci], c.k, c.stride, c.dil, c.pad);
       if (!wino_on(e, ci, B, Ho, Wo)) continue;
       if (!any) { fork(0); any = true; }
-      unsigned* us = amax_wino_weights(e, ci, e->s2);
-      if (wino_geom(e, c, B, Ho, Wo).tm == 4) launch_wino4_weight(e->W_(ci), c.cout, c.cin, e->A_(ci), e->wino_U[ci], e->wino_Us[ci], e->s2, us, us ? us + t.convs.size() : nullptr);
-      else launch_wino_weight(e->W_(ci), c.cout, c.cin, e->A_(ci), e->wino_U[ci], e->wino_Us[ci], e->s2, us, us ? us + t.convs.size() : nullptr);
-      kv.second = 1;
+      wino_ensure_weights(e, ci, wino_geom(e, c, B, Ho, Wo).tm, e->s2);
     }
     if (any) { (void)hipEventRecord(e->ev_wino_w, e->s2); e->wino_w_wait = true; }
   }
@@ -2943,7 +2919,7 @@ int eosvos_time_hot_kernel(eosvos_engine* e, int batch, int reps, float* ms_host
     // conv_igemm launch of an iteration, against the GEMM's own FLOPs
     const WinoGeom wg = wino_geom(e, c, batch, e->h4, e->w4);
     const long ntile = wg.ntile;
-    ConvArgs m = wino_fwd_gemm(e, t.dec_a, wg, e->ws_conv);
+    ConvArgs m = wino_plane_gemm(e, c, wg, e->wino_V[t.dec_a], e->wino_U[t.dec_a], e->wino_m, e->ws_conv, 0);
     HIPOK(hipEventRecord(a, e->s));
     for (int i = 0; i < reps; ++i) { ConvArgs k = m; launch_conv(k, e->s); }
     HIPOK(hipEventRecord(b, e->s));

@@ -270,32 +270,23 @@ void launch_wgrad_p_group(const WgradPArgs* dev_tab, const int* dev_map, int nwg
 void launch_pair_split(const float* x, void* out, long rows, int C, int ld, const unsigned* slot, int margin, float* sc, hipStream_t s);
 int conv_wg_budget_of(int requested);   // workgroups a launch plans for under eosvos_set_wg_budget(requested)
 int conv_clamp_wg_budget(int n);     // the budgets the slab arenas are sized for: 0 (default) or a multiple of 64 in [64, 512]
-// Winograd F(2x2,3x3) weight gradient pieces (misc_kernels.hip): V = B^T d B, dM = A dY A^T, dW = G^T sum_z dU_z G
-// planes are [16][prow][C] with prow >= B*th*tw rows (padded to the GEMM tile so that a row tile never straddles planes)
-// dil: dilation of the 3x3 conv = dil*dil interleaved sub-grids; tiles are (image, sy, sx, ty, tx), th x tw per sub-grid
-void launch_wino_input(const float* x, int ldx, int C, int B, int H, int W, int th, int tw, int dil, long prow, float* V, hipStream_t s, unsigned* amax = nullptr);
-void launch_wino_grad(const float* g, int ldg, int C, int B, int H, int W, int th, int tw, int dil, long prow, float* M, hipStream_t s, unsigned* amax = nullptr);
-void launch_wino_weight(const float* w, int Cout, int Cin, const float* rowscale, float* U, float* Us, hipStream_t s, unsigned* amax_u = nullptr, unsigned* amax_us = nullptr);   // U = G w G^T, Us = rowscale*U
-// Winograd F(4x4,3x3): 36 planes, th x tw tiles of 4x4 outputs per sub-grid
-void launch_wino4_input(const float* x, int ldx, int C, int B, int H, int W, int th, int tw, int dil, long prow, float* V,
-                        hipStream_t s, unsigned* amax = nullptr);
-void launch_wino4_grad(const float* g, int ldg, int C, int B, int H, int W, int th, int tw, int dil, long prow, float* M,
+// Winograd F(tm x tm, 3x3) transform passes (misc_kernels.hip), tm = 2 or 4: V = B^T d B, dM = A dY A^T, U = G w G^T,
+// y = epilogue(A^T M A), dX = mask8?(B dV B^T, overlapped), dW = G^T sum_z dU_z G
+// planes are [(tm+2)^2][prow][C] with prow >= B*dil*dil*th*tw rows (padded to the GEMM tile so that a row tile never straddles planes)
+// dil: dilation of the 3x3 conv = dil*dil interleaved sub-grids; tiles are (image, sy, sx, ty, tx), th x tw tiles of tm x tm outputs per sub-grid
+void launch_wino_input(int tm, const float* x, int ldx, int C, int B, int H, int W, int th, int tw, int dil, long prow, float* V,
                        hipStream_t s, unsigned* amax = nullptr);
-void launch_wino4_weight(const float* w, int Cout, int Cin, const float* rowscale, float* U, float* Us, hipStream_t s, unsigned* amax_u = nullptr, unsigned* amax_us = nullptr);
-void launch_wino4_output(const float* M, long prow, int C, int B, int H, int W, int th, int tw, int dil, const float* scale,
-                         const float* bias, int relu, float* y, int ldy, hipStream_t s, unsigned* amax = nullptr,
-                         uint8_t* mask8_out = nullptr, int ldm8 = 0);
-void launch_wino4_wgrad_finish(const float* ws, int splits, int Cout, int Cin, float* dst, hipStream_t s);
-void launch_wino4_dgrad_output(const float* dV, long prow, int C, int B, int H, int W, int th, int tw, int dil,
-                               const uint8_t* mask8, int ldm8, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s,
-                               unsigned* amax = nullptr);   // dX = mask8?(B dV B^T, overlapped)
-void launch_wino_dgrad_output(const float* dV, long prow, int C, int B, int H, int W, int th, int tw, int dil,
-                              const uint8_t* mask8, int ldm8, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s,
-                              unsigned* amax = nullptr);   // dX = mask8?(B dV B^T, overlapped)
-void launch_wino_output(const float* M, long prow, int C, int B, int H, int W, int th, int tw, int dil, const float* scale,
+void launch_wino_grad(int tm, const float* g, int ldg, int C, int B, int H, int W, int th, int tw, int dil, long prow, float* M,
+                      hipStream_t s, unsigned* amax = nullptr);
+void launch_wino_weight(int tm, const float* w, int Cout, int Cin, const float* rowscale, float* U, float* Us, hipStream_t s,
+                        unsigned* amax_u = nullptr, unsigned* amax_us = nullptr);   // Us = rowscale * U
+void launch_wino_output(int tm, const float* M, long prow, int C, int B, int H, int W, int th, int tw, int dil, const float* scale,
                         const float* bias, int relu, float* y, int ldy, hipStream_t s, unsigned* amax = nullptr,
-                        uint8_t* mask8_out = nullptr, int ldm8 = 0);        // y = epilogue(A^T M A)
-void launch_wino_wgrad_finish(const float* ws, int splits, int Cout, int Cin, float* dst, hipStream_t s);
+                        uint8_t* mask8_out = nullptr, int ldm8 = 0);
+void launch_wino_wgrad_finish(int tm, const float* ws, int splits, int Cout, int Cin, float* dst, hipStream_t s);
+void launch_wino_dgrad_output(int tm, const float* dV, long prow, int C, int B, int H, int W, int th, int tw, int dil,
+                              const uint8_t* mask8, int ldm8, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s,
+                              unsigned* amax = nullptr);
 
 // ---------------------------------------------------------------------------------
 // misc_kernels.hip

@@ -2,8 +2,11 @@
 // 7x7 stem, max-pool, bilinear resize (+ gather-form backward), the ASPP image-pooling
 // branch, the 1-channel classifier conv, fused BCE loss + gradient, the fused
 // per-neuron-lr SGD update (split-K slab reduction included), meta-gradient reduction,
-// RAdam.  64-lane waves, 16-byte accesses where the layout allows, deterministic
-// (atomic-free) reductions everywhere so fine-tuning trajectories are reproducible.
+// RAdam, the Winograd transform passes (one templated family, at the end of the file).
+// 64-lane waves, 16-byte accesses where the layout allows, deterministic (atomic-free)
+// reductions everywhere so fine-tuning trajectories are reproducible.
+#include <cassert>
+
 #include "kernels.h"
 
 namespace eosvos {
@@ -1635,113 +1638,316 @@ void launch_warp_affine(const float* src, float* dst, int C, int H, int W, const
 }
 }  // namespace eosvos
 
-// ---- Winograd F(2x2, 3x3) weight gradient of the decoder's 3x3 convs ----------------------------------------
-// Y = A^T [ (G w G^T) (.) (B^T d B) ] A per 2x2 output tile and (cin, cout) pair, so with U = G w G^T:
-//   dU[p] = sum_tiles dM[p][tile][cout] * V[p][tile][cin]   (16 positions p: 16 GEMMs with K = tiles, 2.25x fewer
-//   MACs than the 9-tap form),  V = B^T d B,  dM = A dY A^T,  dW = G^T dU G.
-// V / dM are stored plane by plane ([p][tile][channel]) so the batched GEMM runs on wgrad_kernel with the 16
-// positions as "taps" (plane strides instead of pixel shifts).
+// ---- Winograd F(m x m, 3x3) transform passes of the 3x3 / stride-1 convs: one kernel family for the two tile
+// sizes m = TM = 2 and 4:  Y = A^T [ (G w G^T) (.) (B^T d B) ] A per TM x TM output tile and (cin, cout) pair.  With
+// NP = TM + 2 and U = G w G^T:
+//   forward          V = B^T d B (input), M[p] = V[p] U[p] (batched GEMM, conv_kernels.hip), y = epilogue(A^T M A) (output)
+//   data gradient    dM = A dY A^T (grad), dV[p] = dM[p] (a U[p])^T (batched GEMM), dX = mask(B dV B^T, overlap-added)
+//   weight gradient  dU[p] = sum_tiles dM[p][tile][cout] * V[p][tile][cin] (wgrad_kernel, the NP*NP positions as "taps"),
+//                    dW = G^T dU G (wgrad finish)
+// V / dM / M / dV are stored plane by plane ([p][tile][channel], prow >= ntile rows per plane, padded to the GEMM tile so
+// that a row tile never straddles planes).  F(2,3): 16 positions, 4 MACs per output instead of 9; F(4,3): 36 positions,
+// 2.25 MACs, transform-domain tensors 0.56x the F(2,3) size, interpolation points 0, +-1, +-2, inf (Lavin & Gray); fp32
+// rounding error of one conv ~2e-6 rms of the output scale (direct fp32: 1e-7, F(2,3): 3e-7) -- far inside the 1e-3
+// logit tolerance.  Stride 1, pad = dilation only.
+// The transforms are driven by the constexpr matrices of WinoMat<TM>: zero entries are skipped at compile time, every
+// other entry is one fmaf, in the order of the matrix row (for F(2,3), whose entries are 0, +-1 and +-1/2, that is the
+// plain sum / difference chain).  Two F(2,3) kernels are explicit specialisations because their summation order is not
+// the separable one of the template: wino_wgrad_finish_kernel<2> and wino_dgrad_output_kernel<2> (see there).
 namespace eosvos {
-// V[p][tile][c] from X (NHWC, ld ldx): 4x4 patch rows 2ty-1..2ty+2, cols 2tx-1..2tx+2, zero outside the image
+// BT, G, AT of both sizes; tests/test_winograd_math.py parses them from this file and checks the Winograd identities
+template <int TM> struct WinoMat;
+template <> struct WinoMat<2> {
+  static __device__ constexpr float BT[4][4] = {{1, 0, -1, 0}, {0, 1, 1, 0}, {0, -1, 1, 0}, {0, 1, 0, -1}};
+  static __device__ constexpr float G[4][3] = {{1, 0, 0}, {0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f}, {0, 0, 1}};
+  static __device__ constexpr float AT[2][4] = {{1, 1, 1, 0}, {0, 1, -1, -1}};
+};
+template <> struct WinoMat<4> {
+  static __device__ constexpr float BT[6][6] = {{4, 0, -5, 0, 1, 0}, {0, -4, -4, 1, 1, 0}, {0, 4, -4, -1, 1, 0},
+                                                {0, -2, -1, 2, 1, 0}, {0, 2, -1, -2, 1, 0}, {0, 4, 0, -5, 0, 1}};
+  static __device__ constexpr float G[6][3] = {{0.25f, 0, 0}, {-1.f / 6, -1.f / 6, -1.f / 6}, {-1.f / 6, 1.f / 6, -1.f / 6},
+                                               {1.f / 24, 1.f / 12, 1.f / 6}, {1.f / 24, -1.f / 12, 1.f / 6}, {0, 0, 1}};
+  static __device__ constexpr float AT[4][6] = {{1, 1, 1, 1, 1, 0}, {0, 1, -1, 2, -2, 0}, {0, 1, 1, 4, 4, 0}, {0, 1, -1, 8, -8, 1}};
+};
+__device__ __forceinline__ void fma4(float4& acc, float c, const float4& v) {
+  acc.x = fmaf(c, v.x, acc.x); acc.y = fmaf(c, v.y, acc.y); acc.z = fmaf(c, v.z, acc.z); acc.w = fmaf(c, v.w, acc.w);
+}
+__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ float4 scaled4(float s, const float4& v) { return make_float4(s * v.x, s * v.y, s * v.z, s * v.w); }
+
+// element e of a transform pass = (tile, 4 channels); tile = (image b, sy, sx, ty, tx): th x tw tiles of TM x TM outputs
+// per sub-grid of a dilated conv (dil * dil interleaved sub-grids, each an ordinary 3x3 convolution; dil = 1: the image)
+struct WinoTile { int c4; long tile; int tx, ty, sx, sy, b; };
+__device__ __forceinline__ WinoTile wino_tile(long e, int C4, int th, int tw, int dil) {
+  WinoTile t;
+  t.c4 = (int)(e % C4);
+  t.tile = e / C4;
+  t.tx = (int)(t.tile % tw); t.ty = (int)((t.tile / tw) % th);
+  t.sx = (int)((t.tile / ((long)tw * th)) % dil); t.sy = (int)((t.tile / ((long)tw * th * dil)) % dil);
+  t.b = (int)(t.tile / ((long)tw * th * dil * dil));
+  return t;
+}
+
+// V[p][tile][c] = B^T d B from X (NHWC, ld ldx), d = NP x NP patch rows TM*ty-1 .. TM*ty+TM, cols likewise (zero outside)
+template <int TM>
 __global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict__ x, int ldx, int C, int B, int H, int W,
                                                           int th, int tw, int dil, long prow, float* __restrict__ V, unsigned* __restrict__ amax) {
+  using Mt = WinoMat<TM>;
+  constexpr int NP = TM + 2;
   const int C4 = C >> 2;
-  const long ntile = (long)B * dil * dil * th * tw, n = ntile * C4;
+  const long n = (long)B * dil * dil * th * tw * C4;
   unsigned am = 0;
   GRID_STRIDE(e, n) {
-    const int c4 = (int)(e % C4);
-    const long tile = e / C4;
-    // dilation d: d*d interleaved sub-grids, each an ordinary 3x3 convolution; tile = (image, sy, sx, ty, tx)
-    const int tx = (int)(tile % tw), ty = (int)((tile / tw) % th);
-    const int sx = (int)((tile / ((long)tw * th)) % dil), sy = (int)((tile / ((long)tw * th * dil)) % dil);
-    const int b = (int)(tile / ((long)tw * th * dil * dil));
-    float4 d[4][4];
+    const WinoTile t = wino_tile(e, C4, th, tw, dil);
+    float4 d[NP][NP];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int yy = sy + dil * (2 * ty - 1 + i);
+    for (int i = 0; i < NP; ++i) {
+      const int yy = t.sy + dil * (TM * t.ty - 1 + i);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int xx = sx + dil * (2 * tx - 1 + j);
+      for (int j = 0; j < NP; ++j) {
+        const int xx = t.sx + dil * (TM * t.tx - 1 + j);
         d[i][j] = ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)
-                      ? *reinterpret_cast<const float4*>(x + (((long)b * H + yy) * W + xx) * ldx + c4 * 4)
-                      : make_float4(0.f, 0.f, 0.f, 0.f);
+                      ? *reinterpret_cast<const float4*>(x + (((long)t.b * H + yy) * W + xx) * ldx + t.c4 * 4)
+                      : zero4();
       }
     }
-#define F4OP(r, a, op, b) r.x = a.x op b.x; r.y = a.y op b.y; r.z = a.z op b.z; r.w = a.w op b.w
-    float4 t[4][4];                        // t = B^T d : rows (d0-d2, d1+d2, d2-d1, d1-d3)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      F4OP(t[0][j], d[0][j], -, d[2][j]); F4OP(t[1][j], d[1][j], +, d[2][j]);
-      F4OP(t[2][j], d[2][j], -, d[1][j]); F4OP(t[3][j], d[1][j], -, d[3][j]);
+    for (int j = 0; j < NP; ++j) {         // columns: d[:, j] <- B^T d[:, j]
+      float4 c[NP];
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        c[i] = zero4();
+#pragma unroll
+        for (int a = 0; a < NP; ++a)
+          if (Mt::BT[i][a] != 0.f) fma4(c[i], Mt::BT[i][a], d[a][j]);
+      }
+#pragma unroll
+      for (int i = 0; i < NP; ++i) d[i][j] = c[i];
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {          // V = t B : columns (t0-t2, t1+t2, t2-t1, t1-t3)
-      float4 v0, v1, v2, v3;
-      F4OP(v0, t[i][0], -, t[i][2]); F4OP(v1, t[i][1], +, t[i][2]);
-      F4OP(v2, t[i][2], -, t[i][1]); F4OP(v3, t[i][1], -, t[i][3]);
-      float* o = V + ((long)(i * 4) * prow + tile) * C + c4 * 4;
-      am = amax_f4(amax_f4(amax_f4(amax_f4(am, v0), v1), v2), v3);
-      *reinterpret_cast<float4*>(o) = v0;
-      *reinterpret_cast<float4*>(o + prow * C) = v1;
-      *reinterpret_cast<float4*>(o + 2 * prow * C) = v2;
-      *reinterpret_cast<float4*>(o + 3 * prow * C) = v3;
+    for (int i = 0; i < NP; ++i) {         // rows: V[i, :] = B^T applied along the row
+#pragma unroll
+      for (int j = 0; j < NP; ++j) {
+        float4 v = zero4();
+#pragma unroll
+        for (int bb = 0; bb < NP; ++bb)
+          if (Mt::BT[j][bb] != 0.f) fma4(v, Mt::BT[j][bb], d[i][bb]);
+        am = amax_f4(am, v);
+        *reinterpret_cast<float4*>(V + ((long)(i * NP + j) * prow + t.tile) * C + t.c4 * 4) = v;
+      }
     }
   }
   if (amax) amax_block_commit(am, amax);
 }
-// dM[p][tile][c] = A dY A^T from dY (NHWC, ld ldg): 2x2 outputs of the tile (zero outside), A = [[1,0],[1,1],[1,-1],[0,-1]]
+// dM[p][tile][c] = A dY A^T from dY (NHWC, ld ldg): the tile's TM x TM outputs (zero outside), A = AT^T
+template <int TM>
 __global__ __launch_bounds__(256) void wino_grad_kernel(const float* __restrict__ g, int ldg, int C, int B, int H, int W,
                                                          int th, int tw, int dil, long prow, float* __restrict__ M, unsigned* __restrict__ amax) {
+  using Mt = WinoMat<TM>;
+  constexpr int NP = TM + 2;
   const int C4 = C >> 2;
-  const long ntile = (long)B * dil * dil * th * tw, n = ntile * C4;
+  const long n = (long)B * dil * dil * th * tw * C4;
   unsigned am = 0;
   GRID_STRIDE(e, n) {
-    const int c4 = (int)(e % C4);
-    const long tile = e / C4;
-    const int tx = (int)(tile % tw), ty = (int)((tile / tw) % th);
-    const int sx = (int)((tile / ((long)tw * th)) % dil), sy = (int)((tile / ((long)tw * th * dil)) % dil);
-    const int b = (int)(tile / ((long)tw * th * dil * dil));
-    float4 d[2][2];
+    const WinoTile tl = wino_tile(e, C4, th, tw, dil);
+    float4 d[TM][TM];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int yy = sy + dil * (2 * ty + i), xx = sx + dil * (2 * tx + j);
-        d[i][j] = (yy < H && xx < W) ? *reinterpret_cast<const float4*>(g + (((long)b * H + yy) * W + xx) * ldg + c4 * 4)
-                                     : make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int j = 0; j < TM; ++j) {
+        const int yy = tl.sy + dil * (TM * tl.ty + i), xx = tl.sx + dil * (TM * tl.tx + j);
+        d[i][j] = (yy < H && xx < W) ? *reinterpret_cast<const float4*>(g + (((long)tl.b * H + yy) * W + xx) * ldg + tl.c4 * 4)
+                                     : zero4();
       }
-    float4 t[4][2];                        // t = A d : rows (d0, d0+d1, d0-d1, -d1)
+    float4 t[NP][TM];                      // t = A d : t[a][j] = sum_r AT[r][a] d[r][j]
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      t[0][j] = d[0][j];
-      F4OP(t[1][j], d[0][j], +, d[1][j]); F4OP(t[2][j], d[0][j], -, d[1][j]);
-      t[3][j] = make_float4(-d[1][j].x, -d[1][j].y, -d[1][j].z, -d[1][j].w);
-    }
+    for (int a = 0; a < NP; ++a)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {          // M = t A^T : columns (t0, t0+t1, t0-t1, -t1)
-      float4 m1, m2;
-      F4OP(m1, t[i][0], +, t[i][1]); F4OP(m2, t[i][0], -, t[i][1]);
-      const float4 m3 = make_float4(-t[i][1].x, -t[i][1].y, -t[i][1].z, -t[i][1].w);
-      float* o = M + ((long)(i * 4) * prow + tile) * C + c4 * 4;
-      am = amax_f4(amax_f4(amax_f4(amax_f4(am, t[i][0]), m1), m2), m3);
-      *reinterpret_cast<float4*>(o) = t[i][0];
-      *reinterpret_cast<float4*>(o + prow * C) = m1;
-      *reinterpret_cast<float4*>(o + 2 * prow * C) = m2;
-      *reinterpret_cast<float4*>(o + 3 * prow * C) = m3;
+      for (int j = 0; j < TM; ++j) {
+        t[a][j] = zero4();
+#pragma unroll
+        for (int r = 0; r < TM; ++r)
+          if (Mt::AT[r][a] != 0.f) fma4(t[a][j], Mt::AT[r][a], d[r][j]);
+      }
+#pragma unroll
+    for (int a = 0; a < NP; ++a)
+#pragma unroll
+      for (int bb = 0; bb < NP; ++bb) {    // dM[a][bb] = sum_r t[a][r] AT[r][bb]
+        float4 v = zero4();
+#pragma unroll
+        for (int r = 0; r < TM; ++r)
+          if (Mt::AT[r][bb] != 0.f) fma4(v, Mt::AT[r][bb], t[a][r]);
+        am = amax_f4(am, v);
+        *reinterpret_cast<float4*>(M + ((long)(a * NP + bb) * prow + tl.tile) * C + tl.c4 * 4) = v;
+      }
+  }
+  if (amax) amax_block_commit(am, amax);
+}
+// U[p][cout][cin] = G w G^T from W[cout][3x3][cin]; Us (optional) = rowscale[cout] * U, the copy the data gradient
+// multiplies with (the frozen-norm scale a[cout] folded in)
+template <int TM>
+__global__ __launch_bounds__(256) void wino_weight_kernel(const float* __restrict__ w, int Cout, int Cin,
+                                                           const float* __restrict__ rowscale, float* __restrict__ U,
+                                                           float* __restrict__ Us, unsigned* __restrict__ amax_u, unsigned* __restrict__ amax_us) {
+  using Mt = WinoMat<TM>;
+  constexpr int NP = TM + 2;
+  const int C4 = Cin >> 2;
+  const long n = (long)Cout * C4;
+  unsigned am = 0, ams = 0;
+  GRID_STRIDE(e, n) {
+    const int c4 = (int)(e % C4), co = (int)(e / C4);
+    const float rs = rowscale ? rowscale[co] : 1.f;
+    float4 g[3][3];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) g[t / 3][t % 3] = *reinterpret_cast<const float4*>(w + ((size_t)co * 9 + t) * Cin + c4 * 4);
+    float4 t[NP][3];
+#pragma unroll
+    for (int a = 0; a < NP; ++a)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        t[a][j] = zero4();
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+          if (Mt::G[a][r] != 0.f) fma4(t[a][j], Mt::G[a][r], g[r][j]);
+      }
+    const size_t ps = (size_t)Cout * Cin;
+#pragma unroll
+    for (int a = 0; a < NP; ++a)
+#pragma unroll
+      for (int bb = 0; bb < NP; ++bb) {
+        float4 v = zero4();
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+          if (Mt::G[bb][r] != 0.f) fma4(v, Mt::G[bb][r], t[a][r]);
+        am = amax_f4(am, v);
+        ams = amax_f4(ams, scaled4(rs, v));
+        *reinterpret_cast<float4*>(U + (size_t)(a * NP + bb) * ps + (size_t)co * Cin + c4 * 4) = v;
+        if (Us) *reinterpret_cast<float4*>(Us + (size_t)(a * NP + bb) * ps + (size_t)co * Cin + c4 * 4) = scaled4(rs, v);
+      }
+  }
+  if (amax_u) amax_block_commit(am, amax_u);
+  if (amax_us) amax_block_commit(ams, amax_us);
+}
+// y (NHWC, ld ldy) = relu?(scale * (A^T M A) + bias) from M[p][tile][c], TM x TM outputs per tile
+template <int TM>
+__global__ __launch_bounds__(256) void wino_output_kernel(const float* __restrict__ M, long prow, int C, int B, int H, int W,
+                                                           int th, int tw, int dil, const float* __restrict__ scale,
+                                                           const float* __restrict__ bias, int relu, float* __restrict__ y,
+                                                           int ldy, unsigned* __restrict__ amax, uint8_t* __restrict__ mask8_out, int ldm8) {
+  using Mt = WinoMat<TM>;
+  constexpr int NP = TM + 2;
+  const int C4 = C >> 2;
+  const long n = (long)B * dil * dil * th * tw * C4;
+  unsigned am = 0;
+  GRID_STRIDE(e, n) {
+    const WinoTile tl = wino_tile(e, C4, th, tw, dil);
+    float4 t[TM][NP];                      // t = A^T m, streamed over the rows a of m
+#pragma unroll
+    for (int r = 0; r < TM; ++r)
+#pragma unroll
+      for (int j = 0; j < NP; ++j) t[r][j] = zero4();
+#pragma unroll
+    for (int a = 0; a < NP; ++a)
+#pragma unroll
+      for (int j = 0; j < NP; ++j) {
+        const float4 m = *reinterpret_cast<const float4*>(M + ((long)(a * NP + j) * prow + tl.tile) * C + tl.c4 * 4);
+#pragma unroll
+        for (int r = 0; r < TM; ++r)
+          if (Mt::AT[r][a] != 0.f) fma4(t[r][j], Mt::AT[r][a], m);
+      }
+    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), bi = zero4();
+    if (scale) sc = *reinterpret_cast<const float4*>(scale + tl.c4 * 4);
+    if (bias) bi = *reinterpret_cast<const float4*>(bias + tl.c4 * 4);
+#pragma unroll
+    for (int r = 0; r < TM; ++r) {
+      const int yy = tl.sy + dil * (TM * tl.ty + r);
+      if (yy >= H) continue;
+#pragma unroll
+      for (int q = 0; q < TM; ++q) {
+        const int xx = tl.sx + dil * (TM * tl.tx + q);
+        if (xx >= W) continue;
+        float4 v = zero4();
+#pragma unroll
+        for (int j = 0; j < NP; ++j)
+          if (Mt::AT[q][j] != 0.f) fma4(v, Mt::AT[q][j], t[r][j]);
+        if (scale) { v.x *= sc.x; v.y *= sc.y; v.z *= sc.z; v.w *= sc.w; }
+        if (bias) { v.x += bi.x; v.y += bi.y; v.z += bi.z; v.w += bi.w; }
+        if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        am = amax_f4(am, v);
+        *reinterpret_cast<float4*>(y + (((long)tl.b * H + yy) * W + xx) * ldy + tl.c4 * 4) = v;
+        if (mask8_out) mask8_out[(((long)tl.b * H + yy) * W + xx) * ldm8 + tl.c4] = relu_bits(v);
+      }
     }
   }
   if (amax) amax_block_commit(am, amax);
 }
-// dW[cout][3x3][cin] = G^T (sum_z dU_z[cout][4x4][cin]) G,  G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
+// dW[cout][3x3][cin] = G^T (sum_z dU_z[cout][NP x NP][cin]) G.  One thread per (cout, cin): the decoder convs have only
+// 256 x 304 of them, and a float4-per-thread version (64 workgroups of long dependent load chains) ran at 2 TB/s.
+template <int TM> constexpr int wino_finish_cin_per_thread = 1;      // input channels one thread finishes (the launcher's grid)
+template <int TM>
 __global__ __launch_bounds__(256) void wino_wgrad_finish_kernel(const float* __restrict__ ws, int splits, int Cout, int Cin,
                                                                  float* __restrict__ dst) {
+  using Mt = WinoMat<TM>;
+  constexpr int NP = TM + 2;
+  const long n = (long)Cout * Cin;
+  GRID_STRIDE(e, n) {
+    const int ci = (int)(e % Cin), co = (int)(e / Cin);
+    float t[3][NP];                        // t = G^T u, streamed over the rows a of u (each summed over the splits)
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int j = 0; j < NP; ++j) t[r][j] = 0.f;
+#pragma unroll
+    for (int a = 0; a < NP; ++a) {
+      float u[NP];                         // one row of dU, its NP loads per split in flight together
+#pragma unroll
+      for (int j = 0; j < NP; ++j) u[j] = 0.f;
+      for (int z = 0; z < splits; ++z) {
+        float v[NP];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) v[j] = ws[(((size_t)z * Cout + co) * (NP * NP) + (a * NP + j)) * Cin + ci];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) u[j] += v[j];
+      }
+#pragma unroll
+      for (int j = 0; j < NP; ++j)
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+          if (Mt::G[a][r] != 0.f) t[r][j] = fmaf(Mt::G[a][r], u[j], t[r][j]);
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        float v = 0.f;
+#pragma unroll
+        for (int j = 0; j < NP; ++j)
+          if (Mt::G[j][q] != 0.f) v = fmaf(Mt::G[j][q], t[r][j], v);
+        dst[((size_t)co * 9 + r * 3 + q) * Cin + ci] = v;
+      }
+  }
+}
+// F(2,3) keeps its own association: (u0 + .5(u1+u2), .5(u1-u2), .5(u1+u2) + u3) with the sum u1+u2 shared by two rows,
+// which no traversal order of the fmaf chain above reproduces; its results must not move.  float4 per thread (Cin / 4).
+__device__ __forceinline__ void wino2_gt(const float4& u0, const float4& u1, const float4& u2, const float4& u3, float4& r0, float4& r1, float4& r2) {
+  const float4 s12 = make_float4(u1.x + u2.x, u1.y + u2.y, u1.z + u2.z, u1.w + u2.w);
+  const float4 d12 = make_float4(u1.x - u2.x, u1.y - u2.y, u1.z - u2.z, u1.w - u2.w);
+  r0 = make_float4(u0.x + 0.5f * s12.x, u0.y + 0.5f * s12.y, u0.z + 0.5f * s12.z, u0.w + 0.5f * s12.w);
+  r1 = scaled4(0.5f, d12);
+  r2 = make_float4(0.5f * s12.x + u3.x, 0.5f * s12.y + u3.y, 0.5f * s12.z + u3.z, 0.5f * s12.w + u3.w);
+}
+template <> constexpr int wino_finish_cin_per_thread<2> = 4;
+template <>
+__global__ __launch_bounds__(256) void wino_wgrad_finish_kernel<2>(const float* __restrict__ ws, int splits, int Cout, int Cin,
+                                                                    float* __restrict__ dst) {
+  static_assert(wino_finish_cin_per_thread<2> == 4, "this kernel finishes one float4 of input channels per thread");
   const int C4 = Cin >> 2;
   const long n = (long)Cout * C4;
   GRID_STRIDE(e, n) {
     const int c4 = (int)(e % C4), co = (int)(e / C4);
     float4 u[4][4];
 #pragma unroll
-    for (int p = 0; p < 16; ++p) u[p >> 2][p & 3] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int p = 0; p < 16; ++p) u[p >> 2][p & 3] = zero4();
     for (int z = 0; z < splits; ++z) {
       const float* sp = ws + ((size_t)z * Cout + co) * 16 * Cin + c4 * 4;
 #pragma unroll
@@ -1751,169 +1957,105 @@ __global__ __launch_bounds__(256) void wino_wgrad_finish_kernel(const float* __r
         a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
       }
     }
-    // t = G^T u (3x4): rows (u0 + .5(u1+u2), .5(u1-u2), .5(u1+u2) + u3); then w = t G (3x3), same combination on columns
-    float4 t[3][4];
+    float4 t[3][4];                        // t = G^T u (3x4); then w = t G (3x3), the same combination on columns
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float4 s12, d12;
-      F4OP(s12, u[1][j], +, u[2][j]); F4OP(d12, u[1][j], -, u[2][j]);
-      t[0][j] = make_float4(u[0][j].x + 0.5f * s12.x, u[0][j].y + 0.5f * s12.y, u[0][j].z + 0.5f * s12.z, u[0][j].w + 0.5f * s12.w);
-      t[1][j] = make_float4(0.5f * d12.x, 0.5f * d12.y, 0.5f * d12.z, 0.5f * d12.w);
-      t[2][j] = make_float4(0.5f * s12.x + u[3][j].x, 0.5f * s12.y + u[3][j].y, 0.5f * s12.z + u[3][j].z, 0.5f * s12.w + u[3][j].w);
-    }
+    for (int j = 0; j < 4; ++j) wino2_gt(u[0][j], u[1][j], u[2][j], u[3][j], t[0][j], t[1][j], t[2][j]);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      float4 s12, d12;
-      F4OP(s12, t[i][1], +, t[i][2]); F4OP(d12, t[i][1], -, t[i][2]);
+      float4 w0, w1, w2;
+      wino2_gt(t[i][0], t[i][1], t[i][2], t[i][3], w0, w1, w2);
       float* o = dst + ((size_t)co * 9 + i * 3) * Cin + c4 * 4;
-      *reinterpret_cast<float4*>(o) = make_float4(t[i][0].x + 0.5f * s12.x, t[i][0].y + 0.5f * s12.y, t[i][0].z + 0.5f * s12.z, t[i][0].w + 0.5f * s12.w);
-      *reinterpret_cast<float4*>(o + Cin) = make_float4(0.5f * d12.x, 0.5f * d12.y, 0.5f * d12.z, 0.5f * d12.w);
-      *reinterpret_cast<float4*>(o + 2 * Cin) = make_float4(0.5f * s12.x + t[i][3].x, 0.5f * s12.y + t[i][3].y, 0.5f * s12.z + t[i][3].z, 0.5f * s12.w + t[i][3].w);
+      *reinterpret_cast<float4*>(o) = w0;
+      *reinterpret_cast<float4*>(o + Cin) = w1;
+      *reinterpret_cast<float4*>(o + 2 * Cin) = w2;
     }
   }
-#undef F4OP
 }
-void launch_wino_input(const float* x, int ldx, int C, int B, int H, int W, int th, int tw, int dil, long prow, float* V,
-                       hipStream_t s, unsigned* amax) {
-  const long n = (long)B * dil * dil * th * tw * (C / 4);
-  hipLaunchKernelGGL(wino_input_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, x, ldx, C, B, H, W, th, tw, dil, prow, V, amax);
-}
-void launch_wino_grad(const float* g, int ldg, int C, int B, int H, int W, int th, int tw, int dil, long prow, float* M,
-                      hipStream_t s, unsigned* amax) {
-  const long n = (long)B * dil * dil * th * tw * (C / 4);
-  hipLaunchKernelGGL(wino_grad_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, g, ldg, C, B, H, W, th, tw, dil, prow, M, amax);
-}
-// U[p][cout][cin] = G w G^T from W[cout][3x3][cin]
-// U = G w G^T; Us (optional) = rowscale[cout] * U, the copy the data gradient multiplies with
-__global__ __launch_bounds__(256) void wino_weight_kernel(const float* __restrict__ w, int Cout, int Cin,
-                                                           const float* __restrict__ rowscale, float* __restrict__ U,
-                                                           float* __restrict__ Us, unsigned* __restrict__ amax_u, unsigned* __restrict__ amax_us) {
-  const int C4 = Cin >> 2;
-  const long n = (long)Cout * C4;
-  unsigned am = 0, ams = 0;
-  GRID_STRIDE(e, n) {
-    const int c4 = (int)(e % C4), co = (int)(e / C4);
-    const float rs = rowscale ? rowscale[co] : 1.f;      // data gradient: the frozen-norm scale a[cout] folded into Us
-    float4 g[3][3];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) g[t / 3][t % 3] = *reinterpret_cast<const float4*>(w + ((size_t)co * 9 + t) * Cin + c4 * 4);
-    float4 t4[4][3];                       // t = G g : rows (g0, .5(g0+g1+g2), .5(g0-g1+g2), g2)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const float4 a = g[0][j], b = g[1][j], c = g[2][j];
-      t4[0][j] = a;
-      t4[1][j] = make_float4(0.5f * (a.x + b.x + c.x), 0.5f * (a.y + b.y + c.y), 0.5f * (a.z + b.z + c.z), 0.5f * (a.w + b.w + c.w));
-      t4[2][j] = make_float4(0.5f * (a.x - b.x + c.x), 0.5f * (a.y - b.y + c.y), 0.5f * (a.z - b.z + c.z), 0.5f * (a.w - b.w + c.w));
-      t4[3][j] = c;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {          // U = t G^T : columns likewise
-      const float4 a = t4[i][0], b = t4[i][1], c = t4[i][2];
-      const size_t off = ((size_t)(i * 4) * Cout + co) * Cin + c4 * 4;
-      const size_t ps = (size_t)Cout * Cin;
-      const float4 u0 = a;
-      const float4 u1 = make_float4(0.5f * (a.x + b.x + c.x), 0.5f * (a.y + b.y + c.y), 0.5f * (a.z + b.z + c.z), 0.5f * (a.w + b.w + c.w));
-      const float4 u2 = make_float4(0.5f * (a.x - b.x + c.x), 0.5f * (a.y - b.y + c.y), 0.5f * (a.z - b.z + c.z), 0.5f * (a.w - b.w + c.w));
-      const float4 u3 = c;
-      am = amax_f4(amax_f4(amax_f4(amax_f4(am, u0), u1), u2), u3);
-      ams = amax_f4(amax_f4(ams, make_float4(rs * u0.x, rs * u0.y, rs * u0.z, rs * u0.w)), make_float4(rs * u1.x, rs * u1.y, rs * u1.z, rs * u1.w));
-      ams = amax_f4(amax_f4(ams, make_float4(rs * u2.x, rs * u2.y, rs * u2.z, rs * u2.w)), make_float4(rs * u3.x, rs * u3.y, rs * u3.z, rs * u3.w));
-      *reinterpret_cast<float4*>(U + off) = u0;
-      *reinterpret_cast<float4*>(U + off + ps) = u1;
-      *reinterpret_cast<float4*>(U + off + 2 * ps) = u2;
-      *reinterpret_cast<float4*>(U + off + 3 * ps) = u3;
-      if (Us) {
-        *reinterpret_cast<float4*>(Us + off) = make_float4(rs * u0.x, rs * u0.y, rs * u0.z, rs * u0.w);
-        *reinterpret_cast<float4*>(Us + off + ps) = make_float4(rs * u1.x, rs * u1.y, rs * u1.z, rs * u1.w);
-        *reinterpret_cast<float4*>(Us + off + 2 * ps) = make_float4(rs * u2.x, rs * u2.y, rs * u2.z, rs * u2.w);
-        *reinterpret_cast<float4*>(Us + off + 3 * ps) = make_float4(rs * u3.x, rs * u3.y, rs * u3.z, rs * u3.w);
-      }
-    }
-  }
-  if (amax_u) amax_block_commit(am, amax_u);
-  if (amax_us) amax_block_commit(ams, amax_us);
-}
-void launch_wino_weight(const float* w, int Cout, int Cin, const float* rowscale, float* U, float* Us, hipStream_t s, unsigned* amax_u, unsigned* amax_us) {
-  const long n = (long)Cout * (Cin / 4);
-  hipLaunchKernelGGL(wino_weight_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, w, Cout, Cin, rowscale, U, Us, amax_u, amax_us);
-}
-// dX (NHWC, ld ldgx) = mask?( sum over the covering tiles of (B dV B^T)[i][j] ), one thread per 2x2 pixel block and 4
-// channels: the block (2k..2k+1, 2l..2l+1) takes rows i = 3 of tile k-1, i = 1, 2 of tile k and i = 0 of tile k+1
-// (columns likewise), B = [[1,0,0,0],[0,1,-1,1],[-1,1,1,0],[0,0,0,-1]]; gather form, no atomics: deterministic.
+// dX (NHWC, ld ldgx) = mask?(accum + overlap-add of B dV B^T), gather form, no atomics: deterministic.  One thread per
+// TM x TM pixel block (= tile position) and 4 channels.  Block (k, l) takes patch rows i = 1..TM of tile k, i = NP-1 of
+// tile k-1 (its row 0) and i = 0 of tile k+1 (its row TM-1); columns likewise.  B[i][a] = BT[a][i].
+template <int TM>
 __global__ __launch_bounds__(256) void wino_dgrad_output_kernel(const float* __restrict__ dV, long prow, int C, int B, int H,
                                                                  int W, int th, int tw, int dil,
                                                                  const uint8_t* __restrict__ mask8, int ldm8, int mask_c0,
                                                                  int accum, float* __restrict__ gx, int ldgx, unsigned* __restrict__ amax) {
+  using Mt = WinoMat<TM>;
+  constexpr int NP = TM + 2;
   const int C4 = C >> 2;
-  const long n = (long)B * dil * dil * th * tw * C4;      // one 2x2 block of a sub-grid per tile position
+  const long n = (long)B * dil * dil * th * tw * C4;
   unsigned am = 0;
   GRID_STRIDE(e, n) {
-    const int c4 = (int)(e % C4);
-    const long blk = e / C4;
-    const int l = (int)(blk % tw), k = (int)((blk / tw) % th);
-    const int sx = (int)((blk / ((long)tw * th)) % dil), sy = (int)((blk / ((long)tw * th * dil)) % dil);
-    const int b = (int)(blk / ((long)tw * th * dil * dil));
-    float4 acc[2][2];
+    const WinoTile blk = wino_tile(e, C4, th, tw, dil);      // the block's own tile: k = ty, l = tx
+    const int c4 = blk.c4, sx = blk.sx, sy = blk.sy, b = blk.b;
+    float4 acc[TM][TM];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i >> 1][i & 1] = make_float4(0.f, 0.f, 0.f, 0.f);
-    // tile rows: (tile dk, patch row i) pairs feeding output row r of the block
-    // r = 0 (y = 2k):   (k, i = 1), (k-1, i = 3);   r = 1 (y = 2k+1): (k, i = 2), (k+1, i = 0)
+    for (int r = 0; r < TM; ++r)
+#pragma unroll
+      for (int q = 0; q < TM; ++q) acc[r][q] = zero4();
 #pragma unroll
     for (int dk = -1; dk <= 1; ++dk) {
-      const int ty = k + dk;
+      const int ty = blk.ty + dk;
       if ((unsigned)ty >= (unsigned)th) continue;
 #pragma unroll
       for (int dl = -1; dl <= 1; ++dl) {
-        const int tx = l + dl;
+        const int tx = blk.tx + dl;
         if ((unsigned)tx >= (unsigned)tw) continue;
         const long tile = ((((long)b * dil + sy) * dil + sx) * th + ty) * tw + tx;
-        // rows of B needed from this tile: dk=-1 -> {3}; dk=0 -> {1,2}; dk=+1 -> {0}; columns likewise with dl
+        // patch rows of this tile that land in the block: dk = -1 -> {NP-1}, 0 -> {1..TM}, +1 -> {0}; output row r(i)
+        const int ni = dk == 0 ? TM : 1, nj = dl == 0 ? TM : 1;
+        // t[ii][bb] = sum_a B[i][a] dV[a][bb]   for the needed i, streamed over a
+        float4 t[TM][NP];
 #pragma unroll
-        for (int ii = 0; ii < 2; ++ii) {
-          const int i = dk < 0 ? 3 : (dk > 0 ? 0 : 1 + ii);
-          if (dk != 0 && ii == 1) continue;
-          const int r = dk < 0 ? 0 : (dk > 0 ? 1 : ii);              // output row inside the block
+        for (int ii = 0; ii < TM; ++ii)
 #pragma unroll
-          for (int jj = 0; jj < 2; ++jj) {
-            const int j = dl < 0 ? 3 : (dl > 0 ? 0 : 1 + jj);
-            if (dl != 0 && jj == 1) continue;
-            const int cidx = dl < 0 ? 0 : (dl > 0 ? 1 : jj);          // output column inside the block
-            // dd[i][j] = sum_{a,bb} Bm[i][a] * dV[a][bb] * Bm[j][bb]
-            float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+          for (int bb = 0; bb < NP; ++bb) t[ii][bb] = zero4();
 #pragma unroll
-            for (int a = 0; a < 4; ++a) {
-              const float ba = (i == 0) ? (a == 0 ? 1.f : 0.f)
-                             : (i == 1) ? (a == 1 ? 1.f : (a == 2 ? -1.f : (a == 3 ? 1.f : 0.f)))
-                             : (i == 2) ? (a == 0 ? -1.f : (a == 3 ? 0.f : 1.f))
-                                        : (a == 3 ? -1.f : 0.f);
-              if (ba == 0.f) continue;
+        for (int a = 0; a < NP; ++a) {
+          // is row a needed by any of the i rows?  (i = NP-1: a = NP-1 only; i = 0: a = 0 only; centre: every a)
+          if (dk < 0 && a != NP - 1) continue;
+          if (dk > 0 && a != 0) continue;
 #pragma unroll
-              for (int bb = 0; bb < 4; ++bb) {
-                const float bj = (j == 0) ? (bb == 0 ? 1.f : 0.f)
-                               : (j == 1) ? (bb == 1 ? 1.f : (bb == 2 ? -1.f : (bb == 3 ? 1.f : 0.f)))
-                               : (j == 2) ? (bb == 0 ? -1.f : (bb == 3 ? 0.f : 1.f))
-                                          : (bb == 3 ? -1.f : 0.f);
-                if (bj == 0.f) continue;
-                const float4 v = *reinterpret_cast<const float4*>(dV + ((long)(a * 4 + bb) * prow + tile) * C + c4 * 4);
-                const float wgt = ba * bj;
-                sum.x += wgt * v.x; sum.y += wgt * v.y; sum.z += wgt * v.z; sum.w += wgt * v.w;
-              }
+          for (int bb = 0; bb < NP; ++bb) {
+            if (dl < 0 && bb != NP - 1) continue;
+            if (dl > 0 && bb != 0) continue;
+            const float4 v = *reinterpret_cast<const float4*>(dV + ((long)(a * NP + bb) * prow + tile) * C + c4 * 4);
+#pragma unroll
+            for (int ii = 0; ii < TM; ++ii) {
+              if (ii >= ni) continue;
+              const int i = dk < 0 ? NP - 1 : (dk > 0 ? 0 : 1 + ii);
+              if (Mt::BT[a][i] != 0.f) fma4(t[ii][bb], Mt::BT[a][i], v);
             }
-            acc[r][cidx].x += sum.x; acc[r][cidx].y += sum.y; acc[r][cidx].z += sum.z; acc[r][cidx].w += sum.w;
+          }
+        }
+#pragma unroll
+        for (int ii = 0; ii < TM; ++ii) {
+          if (ii >= ni) continue;
+          const int r = dk < 0 ? 0 : (dk > 0 ? TM - 1 : ii);
+#pragma unroll
+          for (int jj = 0; jj < TM; ++jj) {
+            if (jj >= nj) continue;
+            const int j = dl < 0 ? NP - 1 : (dl > 0 ? 0 : 1 + jj);
+            const int q = dl < 0 ? 0 : (dl > 0 ? TM - 1 : jj);
+#pragma unroll
+            for (int bb = 0; bb < NP; ++bb) {
+              if (dl < 0 && bb != NP - 1) continue;
+              if (dl > 0 && bb != 0) continue;
+              if (Mt::BT[bb][j] != 0.f) fma4(acc[r][q], Mt::BT[bb][j], t[ii][bb]);
+            }
           }
         }
       }
     }
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int yy = sy + dil * (2 * k + r);
+    for (int r = 0; r < TM; ++r) {
+      const int yy = sy + dil * (TM * blk.ty + r);
       if (yy >= H) continue;
 #pragma unroll
-      for (int cc = 0; cc < 2; ++cc) {
-        const int xx = sx + dil * (2 * l + cc);
+      for (int q = 0; q < TM; ++q) {
+        const int xx = sx + dil * (TM * blk.tx + q);
         if (xx >= W) continue;
         const long pix = ((long)b * H + yy) * W + xx;
-        float4 v = acc[r][cc];
+        float4 v = acc[r][q];
         if (accum) {                       // several branches feed this gradient (ASPP): add, then mask, like the GEMM epilogue
           const float4 o = *reinterpret_cast<const float4*>(gx + pix * ldgx + c4 * 4);
           v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
@@ -1926,407 +2068,67 @@ __global__ __launch_bounds__(256) void wino_dgrad_output_kernel(const float* __r
   }
   if (amax) amax_block_commit(am, amax);
 }
-void launch_wino_dgrad_output(const float* dV, long prow, int C, int B, int H, int W, int th, int tw, int dil,
-                              const uint8_t* mask8, int ldm8, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s,
-                              unsigned* amax) {
-  const long n = (long)B * dil * dil * th * tw * (C / 4);
-  hipLaunchKernelGGL(wino_dgrad_output_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, dV, prow, C, B, H, W, th, tw,
-                     dil, mask8, ldm8, mask_c0, accum, gx, ldgx, amax);
-}
-// y (NHWC, ld ldy) = relu?(scale * (A^T M A) + bias) from M[p][tile][c], A^T = [[1,1,1,0],[0,1,-1,-1]]
-__global__ __launch_bounds__(256) void wino_output_kernel(const float* __restrict__ M, long prow, int C, int B, int H, int W,
-                                                           int th, int tw, int dil, const float* __restrict__ scale,
-                                                           const float* __restrict__ bias, int relu, float* __restrict__ y,
-                                                           int ldy, unsigned* __restrict__ amax, uint8_t* __restrict__ mask8_out, int ldm8) {
-  const int C4 = C >> 2;
-  const long ntile = (long)B * dil * dil * th * tw, n = ntile * C4;
-  unsigned am = 0;
-  GRID_STRIDE(e, n) {
-    const int c4 = (int)(e % C4);
-    const long tile = e / C4;
-    const int tx = (int)(tile % tw), ty = (int)((tile / tw) % th);
-    const int sx = (int)((tile / ((long)tw * th)) % dil), sy = (int)((tile / ((long)tw * th * dil)) % dil);
-    const int b = (int)(tile / ((long)tw * th * dil * dil));
-    float4 m[4][4];
-#pragma unroll
-    for (int p = 0; p < 16; ++p) m[p >> 2][p & 3] = *reinterpret_cast<const float4*>(M + ((long)p * prow + tile) * C + c4 * 4);
-    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), bi = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (scale) sc = *reinterpret_cast<const float4*>(scale + c4 * 4);
-    if (bias) bi = *reinterpret_cast<const float4*>(bias + c4 * 4);
-    float4 t[2][4];                        // t = A^T m : rows (m0+m1+m2, m1-m2-m3)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      t[0][j] = make_float4(m[0][j].x + m[1][j].x + m[2][j].x, m[0][j].y + m[1][j].y + m[2][j].y, m[0][j].z + m[1][j].z + m[2][j].z, m[0][j].w + m[1][j].w + m[2][j].w);
-      t[1][j] = make_float4(m[1][j].x - m[2][j].x - m[3][j].x, m[1][j].y - m[2][j].y - m[3][j].y, m[1][j].z - m[2][j].z - m[3][j].z, m[1][j].w - m[2][j].w - m[3][j].w);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int yy = sy + dil * (2 * ty + i);
-      if (yy >= H) continue;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int xx = sx + dil * (2 * tx + j);
-        if (xx >= W) continue;
-        float4 v;
-        if (j == 0) v = make_float4(t[i][0].x + t[i][1].x + t[i][2].x, t[i][0].y + t[i][1].y + t[i][2].y, t[i][0].z + t[i][1].z + t[i][2].z, t[i][0].w + t[i][1].w + t[i][2].w);
-        else v = make_float4(t[i][1].x - t[i][2].x - t[i][3].x, t[i][1].y - t[i][2].y - t[i][3].y, t[i][1].z - t[i][2].z - t[i][3].z, t[i][1].w - t[i][2].w - t[i][3].w);
-        if (scale) { v.x *= sc.x; v.y *= sc.y; v.z *= sc.z; v.w *= sc.w; }
-        if (bias) { v.x += bi.x; v.y += bi.y; v.z += bi.z; v.w += bi.w; }
-        if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        am = amax_f4(am, v);
-        *reinterpret_cast<float4*>(y + (((long)b * H + yy) * W + xx) * ldy + c4 * 4) = v;
-        if (mask8_out) mask8_out[(((long)b * H + yy) * W + xx) * ldm8 + c4] = relu_bits(v);
-      }
-    }
-  }
-  if (amax) amax_block_commit(am, amax);
-}
-void launch_wino_output(const float* M, long prow, int C, int B, int H, int W, int th, int tw, int dil, const float* scale,
-                        const float* bias, int relu, float* y, int ldy, hipStream_t s, unsigned* amax, uint8_t* mask8_out, int ldm8) {
-  const long n = (long)B * dil * dil * th * tw * (C / 4);
-  hipLaunchKernelGGL(wino_output_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, M, prow, C, B, H, W, th, tw, dil,
-                     scale, bias, relu, y, ldy, amax, relu ? mask8_out : nullptr, ldm8);
-}
-void launch_wino_wgrad_finish(const float* ws, int splits, int Cout, int Cin, float* dst, hipStream_t s) {
-  const long n = (long)Cout * (Cin / 4);
-  hipLaunchKernelGGL(wino_wgrad_finish_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, ws, splits, Cout, Cin, dst);
-}
-}  // namespace eosvos
-
-// ---- Winograd F(4x4, 3x3): the decoder's two 3x3 convs on the stride-4 map -------------------------------------
-// Same structure as F(2x2,3x3) above with 6x6 patches / 36 positions and 4x4 output tiles: 2.25 MACs per output
-// and (cin, cout) pair instead of 4 (and 9 for the direct form), transform-domain tensors 0.56x the F(2,3) size.
-// Interpolation points 0, +-1, +-2, inf (Lavin & Gray); fp32 rounding error of one conv ~2e-6 rms of the output
-// scale (direct fp32: 1e-7, F(2,3): 3e-7) -- far inside the 1e-3 logit tolerance.  Undilated, stride 1, pad 1 only.
-namespace eosvos {
-namespace w4 {
-__device__ constexpr float BT[6][6] = {{4, 0, -5, 0, 1, 0}, {0, -4, -4, 1, 1, 0}, {0, 4, -4, -1, 1, 0},
-                                       {0, -2, -1, 2, 1, 0}, {0, 2, -1, -2, 1, 0}, {0, 4, 0, -5, 0, 1}};
-__device__ constexpr float G[6][3] = {{0.25f, 0, 0}, {-1.f / 6, -1.f / 6, -1.f / 6}, {-1.f / 6, 1.f / 6, -1.f / 6},
-                                      {1.f / 24, 1.f / 12, 1.f / 6}, {1.f / 24, -1.f / 12, 1.f / 6}, {0, 0, 1}};
-__device__ constexpr float AT[4][6] = {{1, 1, 1, 1, 1, 0}, {0, 1, -1, 2, -2, 0}, {0, 1, 1, 4, 4, 0}, {0, 1, -1, 8, -8, 1}};
-__device__ __forceinline__ void fma4(float4& acc, float c, const float4& v) {
-  acc.x = fmaf(c, v.x, acc.x); acc.y = fmaf(c, v.y, acc.y); acc.z = fmaf(c, v.z, acc.z); acc.w = fmaf(c, v.w, acc.w);
-}
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-}  // namespace w4
-
-// tile decode shared by the F(4,3) kernels: tile = (image, sy, sx, ty, tx), th x tw tiles of 4x4 outputs per sub-grid
-// of a dilated conv (dil*dil sub-grids; dil = 1: the image itself)
-#define W4_TILE_DECODE                                                                                      \
-  const int c4 = (int)(e % C4);                                                                             \
-  const long tile = e / C4;                                                                                 \
-  const int tx = (int)(tile % tw), ty = (int)((tile / tw) % th);                                            \
-  const int sx = (int)((tile / ((long)tw * th)) % dil), sy = (int)((tile / ((long)tw * th * dil)) % dil);   \
-  const int b = (int)(tile / ((long)tw * th * dil * dil));
-
-// V[p][tile][c] = B^T d B, d = 6x6 patch rows 4ty-1..4ty+4, cols 4tx-1..4tx+4 (zero outside)
-__global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restrict__ x, int ldx, int C, int B, int H, int W,
-                                                           int th, int tw, int dil, long prow, float* __restrict__ V, unsigned* __restrict__ amax) {
+// F(2,3) keeps its own association: each (tile, i, j) term sum_a sum_bb B[i][a] B[j][bb] dV[a][bb] is summed in ONE chain
+// and then added to the block's accumulator, not in the two separable stages above; its results must not move.
+template <>
+__global__ __launch_bounds__(256) void wino_dgrad_output_kernel<2>(const float* __restrict__ dV, long prow, int C, int B, int H,
+                                                                    int W, int th, int tw, int dil,
+                                                                    const uint8_t* __restrict__ mask8, int ldm8, int mask_c0,
+                                                                    int accum, float* __restrict__ gx, int ldgx, unsigned* __restrict__ amax) {
+  using Mt = WinoMat<2>;
   const int C4 = C >> 2;
   const long n = (long)B * dil * dil * th * tw * C4;
   unsigned am = 0;
   GRID_STRIDE(e, n) {
-    W4_TILE_DECODE
-    float4 d[6][6];
+    const WinoTile blk = wino_tile(e, C4, th, tw, dil);
+    const int c4 = blk.c4, sx = blk.sx, sy = blk.sy, b = blk.b;
+    float4 acc[2][2];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const int yy = sy + dil * (4 * ty - 1 + i);
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        const int xx = sx + dil * (4 * tx - 1 + j);
-        d[i][j] = ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)
-                      ? *reinterpret_cast<const float4*>(x + (((long)b * H + yy) * W + xx) * ldx + c4 * 4)
-                      : w4::zero4();
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {          // columns: d[:, j] <- B^T d[:, j]
-      float4 t[6];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        t[i] = w4::zero4();
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-          if (w4::BT[i][a] != 0.f) w4::fma4(t[i], w4::BT[i][a], d[a][j]);
-      }
-#pragma unroll
-      for (int i = 0; i < 6; ++i) d[i][j] = t[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {          // rows: V[i, :] = B^T applied along the row
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        float4 v = w4::zero4();
-#pragma unroll
-        for (int bb = 0; bb < 6; ++bb)
-          if (w4::BT[j][bb] != 0.f) w4::fma4(v, w4::BT[j][bb], d[i][bb]);
-        am = amax_f4(am, v);
-        *reinterpret_cast<float4*>(V + ((long)(i * 6 + j) * prow + tile) * C + c4 * 4) = v;
-      }
-    }
-  }
-  if (amax) amax_block_commit(am, amax);
-}
-// dM[p][tile][c] = A dY A^T, dY = the tile's 4x4 outputs (zero outside), A = AT^T
-__global__ __launch_bounds__(256) void wino4_grad_kernel(const float* __restrict__ g, int ldg, int C, int B, int H, int W,
-                                                          int th, int tw, int dil, long prow, float* __restrict__ M, unsigned* __restrict__ amax) {
-  const int C4 = C >> 2;
-  const long n = (long)B * dil * dil * th * tw * C4;
-  unsigned am = 0;
-  GRID_STRIDE(e, n) {
-    W4_TILE_DECODE
-    float4 d[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int yy = sy + dil * (4 * ty + i), xx = sx + dil * (4 * tx + j);
-        d[i][j] = (yy < H && xx < W) ? *reinterpret_cast<const float4*>(g + (((long)b * H + yy) * W + xx) * ldg + c4 * 4)
-                                     : w4::zero4();
-      }
-    float4 t[6][4];                        // t = A d : t[a][j] = sum_r AT[r][a] d[r][j]
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        t[a][j] = w4::zero4();
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (w4::AT[r][a] != 0.f) w4::fma4(t[a][j], w4::AT[r][a], d[r][j]);
-      }
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-      for (int bb = 0; bb < 6; ++bb) {     // dM[a][bb] = sum_r t[a][r] AT[r][bb]
-        float4 v = w4::zero4();
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (w4::AT[r][bb] != 0.f) w4::fma4(v, w4::AT[r][bb], t[a][r]);
-        am = amax_f4(am, v);
-        *reinterpret_cast<float4*>(M + ((long)(a * 6 + bb) * prow + tile) * C + c4 * 4) = v;
-      }
-  }
-  if (amax) amax_block_commit(am, amax);
-}
-// U[p][cout][cin] = G (rowscale * w) G^T
-__global__ __launch_bounds__(256) void wino4_weight_kernel(const float* __restrict__ w, int Cout, int Cin,
-                                                            const float* __restrict__ rowscale, float* __restrict__ U,
-                                                            float* __restrict__ Us, unsigned* __restrict__ amax_u, unsigned* __restrict__ amax_us) {
-  const int C4 = Cin >> 2;
-  const long n = (long)Cout * C4;
-  unsigned am = 0, ams = 0;
-  GRID_STRIDE(e, n) {
-    const int c4 = (int)(e % C4), co = (int)(e / C4);
-    const float rs = rowscale ? rowscale[co] : 1.f;
-    float4 g[3][3];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) g[t / 3][t % 3] = *reinterpret_cast<const float4*>(w + ((size_t)co * 9 + t) * Cin + c4 * 4);
-    float4 t[6][3];
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        t[a][j] = w4::zero4();
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-          if (w4::G[a][r] != 0.f) w4::fma4(t[a][j], w4::G[a][r], g[r][j]);
-      }
-    const size_t ps = (size_t)Cout * Cin;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-      for (int bb = 0; bb < 6; ++bb) {
-        float4 v = w4::zero4();
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-          if (w4::G[bb][r] != 0.f) w4::fma4(v, w4::G[bb][r], t[a][r]);
-        am = amax_f4(am, v);
-        ams = amax_f4(ams, make_float4(rs * v.x, rs * v.y, rs * v.z, rs * v.w));
-        *reinterpret_cast<float4*>(U + (size_t)(a * 6 + bb) * ps + (size_t)co * Cin + c4 * 4) = v;
-        if (Us)
-          *reinterpret_cast<float4*>(Us + (size_t)(a * 6 + bb) * ps + (size_t)co * Cin + c4 * 4) =
-              make_float4(rs * v.x, rs * v.y, rs * v.z, rs * v.w);
-      }
-  }
-  if (amax_u) amax_block_commit(am, amax_u);
-  if (amax_us) amax_block_commit(ams, amax_us);
-}
-// y = relu?(scale * (A^T M A) + bias), 4x4 outputs per tile
-__global__ __launch_bounds__(256) void wino4_output_kernel(const float* __restrict__ M, long prow, int C, int B, int H, int W,
-                                                            int th, int tw, int dil, const float* __restrict__ scale,
-                                                            const float* __restrict__ bias, int relu, float* __restrict__ y,
-                                                            int ldy, unsigned* __restrict__ amax, uint8_t* __restrict__ mask8_out, int ldm8) {
-  const int C4 = C >> 2;
-  const long n = (long)B * dil * dil * th * tw * C4;
-  unsigned am = 0;
-  GRID_STRIDE(e, n) {
-    W4_TILE_DECODE
-    float4 t[4][6];                        // t = A^T m, streamed over the rows a of m
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) t[r][j] = w4::zero4();
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        const float4 m = *reinterpret_cast<const float4*>(M + ((long)(a * 6 + j) * prow + tile) * C + c4 * 4);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (w4::AT[r][a] != 0.f) w4::fma4(t[r][j], w4::AT[r][a], m);
-      }
-    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), bi = w4::zero4();
-    if (scale) sc = *reinterpret_cast<const float4*>(scale + c4 * 4);
-    if (bias) bi = *reinterpret_cast<const float4*>(bias + c4 * 4);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int yy = sy + dil * (4 * ty + r);
-      if (yy >= H) continue;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int xx = sx + dil * (4 * tx + q);
-        if (xx >= W) continue;
-        float4 v = w4::zero4();
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-          if (w4::AT[q][j] != 0.f) w4::fma4(v, w4::AT[q][j], t[r][j]);
-        if (scale) { v.x *= sc.x; v.y *= sc.y; v.z *= sc.z; v.w *= sc.w; }
-        if (bias) { v.x += bi.x; v.y += bi.y; v.z += bi.z; v.w += bi.w; }
-        if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        am = amax_f4(am, v);
-        *reinterpret_cast<float4*>(y + (((long)b * H + yy) * W + xx) * ldy + c4 * 4) = v;
-        if (mask8_out) mask8_out[(((long)b * H + yy) * W + xx) * ldm8 + c4] = relu_bits(v);
-      }
-    }
-  }
-  if (amax) amax_block_commit(am, amax);
-}
-// dW[cout][3x3][cin] = G^T (sum_z dU_z[cout][6x6][cin]) G.  One thread per (cout, cin): the decoder convs have only
-// 256 x 304 of them, and a float4-per-thread version (64 workgroups of long dependent load chains) ran at 2 TB/s.
-__global__ __launch_bounds__(256) void wino4_wgrad_finish_kernel(const float* __restrict__ ws, int splits, int Cout, int Cin,
-                                                                  float* __restrict__ dst) {
-  const long n = (long)Cout * Cin;
-  GRID_STRIDE(e, n) {
-    const int ci = (int)(e % Cin), co = (int)(e / Cin);
-    float t[3][6];                         // t = G^T u, streamed over the rows a of u (each summed over the splits)
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) t[r][j] = 0.f;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      float u[6];                          // one row of dU, its 6 loads per split in flight together
-#pragma unroll
-      for (int j = 0; j < 6; ++j) u[j] = 0.f;
-      for (int z = 0; z < splits; ++z) {
-        float v[6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) v[j] = ws[(((size_t)z * Cout + co) * 36 + (a * 6 + j)) * Cin + ci];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) u[j] += v[j];
-      }
-#pragma unroll
-      for (int j = 0; j < 6; ++j)
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-          if (w4::G[a][r] != 0.f) t[r][j] = fmaf(w4::G[a][r], u[j], t[r][j]);
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        float v = 0.f;
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-          if (w4::G[j][q] != 0.f) v = fmaf(w4::G[j][q], t[r][j], v);
-        dst[((size_t)co * 9 + r * 3 + q) * Cin + ci] = v;
-      }
-  }
-}
-// dX = mask?(accum + overlap-add of B dV B^T), gather form: one thread per 4x4 pixel block (= tile position) and 4
-// channels.  Block (k, l) takes patch rows i = 1..4 of tile k, i = 5 of tile k-1 (its row 0) and i = 0 of tile k+1
-// (its row 3); columns likewise.  B[i][a] = BT[a][i].
-__global__ __launch_bounds__(256) void wino4_dgrad_output_kernel(const float* __restrict__ dV, long prow, int C, int B, int H,
-                                                                  int W, int th, int tw, int dil,
-                                                                  const uint8_t* __restrict__ mask8, int ldm8, int mask_c0,
-                                                                  int accum, float* __restrict__ gx, int ldgx, unsigned* __restrict__ amax) {
-  const int C4 = C >> 2;
-  const long n = (long)B * dil * dil * th * tw * C4;
-  unsigned am = 0;
-  GRID_STRIDE(e, n) {
-    const int c4 = (int)(e % C4);
-    const long blk = e / C4;
-    const int l = (int)(blk % tw), k = (int)((blk / tw) % th);
-    const int sx = (int)((blk / ((long)tw * th)) % dil), sy = (int)((blk / ((long)tw * th * dil)) % dil);
-    const int b = (int)(blk / ((long)tw * th * dil * dil));
-    float4 acc[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[r][q] = w4::zero4();
+    for (int i = 0; i < 4; ++i) acc[i >> 1][i & 1] = zero4();
 #pragma unroll
     for (int dk = -1; dk <= 1; ++dk) {
-      const int ty = k + dk;
+      const int ty = blk.ty + dk;
       if ((unsigned)ty >= (unsigned)th) continue;
 #pragma unroll
       for (int dl = -1; dl <= 1; ++dl) {
-        const int tx = l + dl;
+        const int tx = blk.tx + dl;
         if ((unsigned)tx >= (unsigned)tw) continue;
         const long tile = ((((long)b * dil + sy) * dil + sx) * th + ty) * tw + tx;
-        // patch rows of this tile that land in the block: dk = -1 -> {5}, 0 -> {1..4}, +1 -> {0}; output row r(i)
-        constexpr int NI_C = 4;
-        const int ni = dk == 0 ? NI_C : 1, nj = dl == 0 ? NI_C : 1;
-        // t[ii][bb] = sum_a B[i][a] dV[a][bb]   for the needed i, streamed over a
-        float4 t[4][6];
+        // rows of B needed from this tile: dk = -1 -> {3}; dk = 0 -> {1, 2}; dk = +1 -> {0}; columns likewise with dl
 #pragma unroll
-        for (int ii = 0; ii < 4; ++ii)
+        for (int ii = 0; ii < 2; ++ii) {
+          const int i = dk < 0 ? 3 : (dk > 0 ? 0 : 1 + ii);
+          if (dk != 0 && ii == 1) continue;
+          const int r = dk < 0 ? 0 : (dk > 0 ? 1 : ii);              // output row inside the block
 #pragma unroll
-          for (int bb = 0; bb < 6; ++bb) t[ii][bb] = w4::zero4();
+          for (int jj = 0; jj < 2; ++jj) {
+            const int j = dl < 0 ? 3 : (dl > 0 ? 0 : 1 + jj);
+            if (dl != 0 && jj == 1) continue;
+            const int q = dl < 0 ? 0 : (dl > 0 ? 1 : jj);            // output column inside the block
+            float4 sum = zero4();
 #pragma unroll
-        for (int a = 0; a < 6; ++a) {
-          // is row a needed by any of the i rows?  (i = 5: a = 5 only; i = 0: a = 0 only; centre: every a)
-          if (dk < 0 && a != 5) continue;
-          if (dk > 0 && a != 0) continue;
+            for (int a = 0; a < 4; ++a) {
+              if (Mt::BT[a][i] == 0.f) continue;
 #pragma unroll
-          for (int bb = 0; bb < 6; ++bb) {
-            if (dl < 0 && bb != 5) continue;
-            if (dl > 0 && bb != 0) continue;
-            const float4 v = *reinterpret_cast<const float4*>(dV + ((long)(a * 6 + bb) * prow + tile) * C + c4 * 4);
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii) {
-              if (ii >= ni) continue;
-              const int i = dk < 0 ? 5 : (dk > 0 ? 0 : 1 + ii);
-              if (w4::BT[a][i] != 0.f) w4::fma4(t[ii][bb], w4::BT[a][i], v);
+              for (int bb = 0; bb < 4; ++bb) {
+                if (Mt::BT[bb][j] == 0.f) continue;
+                const float4 v = *reinterpret_cast<const float4*>(dV + ((long)(a * 4 + bb) * prow + tile) * C + c4 * 4);
+                const float wgt = Mt::BT[a][i] * Mt::BT[bb][j];
+                sum.x += wgt * v.x; sum.y += wgt * v.y; sum.z += wgt * v.z; sum.w += wgt * v.w;
+              }
             }
-          }
-        }
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) {
-          if (ii >= ni) continue;
-          const int r = dk < 0 ? 0 : (dk > 0 ? 3 : ii);
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            if (jj >= nj) continue;
-            const int j = dl < 0 ? 5 : (dl > 0 ? 0 : 1 + jj);
-            const int q = dl < 0 ? 0 : (dl > 0 ? 3 : jj);
-#pragma unroll
-            for (int bb = 0; bb < 6; ++bb) {
-              if (dl < 0 && bb != 5) continue;
-              if (dl > 0 && bb != 0) continue;
-              if (w4::BT[bb][j] != 0.f) w4::fma4(acc[r][q], w4::BT[bb][j], t[ii][bb]);
-            }
+            acc[r][q].x += sum.x; acc[r][q].y += sum.y; acc[r][q].z += sum.z; acc[r][q].w += sum.w;
           }
         }
       }
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int yy = sy + dil * (4 * k + r);
+    for (int r = 0; r < 2; ++r) {
+      const int yy = sy + dil * (2 * blk.ty + r);
       if (yy >= H) continue;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int xx = sx + dil * (4 * l + q);
+      for (int q = 0; q < 2; ++q) {
+        const int xx = sx + dil * (2 * blk.tx + q);
         if (xx >= W) continue;
         const long pix = ((long)b * H + yy) * W + xx;
         float4 v = acc[r][q];
@@ -2342,36 +2144,45 @@ __global__ __launch_bounds__(256) void wino4_dgrad_output_kernel(const float* __
   }
   if (amax) amax_block_commit(am, amax);
 }
-#undef W4_TILE_DECODE
-void launch_wino4_input(const float* x, int ldx, int C, int B, int H, int W, int th, int tw, int dil, long prow, float* V,
-                        hipStream_t s, unsigned* amax) {
-  const long n = (long)B * dil * dil * th * tw * (C / 4);
-  hipLaunchKernelGGL(wino4_input_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, x, ldx, C, B, H, W, th, tw, dil, prow, V, amax);
-}
-void launch_wino4_grad(const float* g, int ldg, int C, int B, int H, int W, int th, int tw, int dil, long prow, float* M,
+
+// ---- launchers: tm = 2 or 4 (WinoGeom::tm) selects the instantiation --------------------------------------------------
+#define WINO_LAUNCH(kernel, grid, s, ...)                                                              \
+  do {                                                                                                 \
+    assert(tm == 2 || tm == 4);                                                                        \
+    if (tm == 4) hipLaunchKernelGGL(kernel<4>, dim3(grid), dim3(256), 0, s, __VA_ARGS__);              \
+    else hipLaunchKernelGGL(kernel<2>, dim3(grid), dim3(256), 0, s, __VA_ARGS__);                      \
+  } while (0)
+void launch_wino_input(int tm, const float* x, int ldx, int C, int B, int H, int W, int th, int tw, int dil, long prow, float* V,
                        hipStream_t s, unsigned* amax) {
   const long n = (long)B * dil * dil * th * tw * (C / 4);
-  hipLaunchKernelGGL(wino4_grad_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, g, ldg, C, B, H, W, th, tw, dil, prow, M, amax);
+  WINO_LAUNCH(wino_input_kernel, grid_for(n, 256, 8192), s, x, ldx, C, B, H, W, th, tw, dil, prow, V, amax);
 }
-void launch_wino4_weight(const float* w, int Cout, int Cin, const float* rowscale, float* U, float* Us, hipStream_t s, unsigned* amax_u, unsigned* amax_us) {
+void launch_wino_grad(int tm, const float* g, int ldg, int C, int B, int H, int W, int th, int tw, int dil, long prow, float* M,
+                      hipStream_t s, unsigned* amax) {
+  const long n = (long)B * dil * dil * th * tw * (C / 4);
+  WINO_LAUNCH(wino_grad_kernel, grid_for(n, 256, 8192), s, g, ldg, C, B, H, W, th, tw, dil, prow, M, amax);
+}
+void launch_wino_weight(int tm, const float* w, int Cout, int Cin, const float* rowscale, float* U, float* Us, hipStream_t s,
+                        unsigned* amax_u, unsigned* amax_us) {
   const long n = (long)Cout * (Cin / 4);
-  hipLaunchKernelGGL(wino4_weight_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, w, Cout, Cin, rowscale, U, Us, amax_u, amax_us);
+  WINO_LAUNCH(wino_weight_kernel, grid_for(n, 256), s, w, Cout, Cin, rowscale, U, Us, amax_u, amax_us);
 }
-void launch_wino4_output(const float* M, long prow, int C, int B, int H, int W, int th, int tw, int dil, const float* scale,
-                         const float* bias, int relu, float* y, int ldy, hipStream_t s, unsigned* amax, uint8_t* mask8_out, int ldm8) {
+void launch_wino_output(int tm, const float* M, long prow, int C, int B, int H, int W, int th, int tw, int dil, const float* scale,
+                        const float* bias, int relu, float* y, int ldy, hipStream_t s, unsigned* amax, uint8_t* mask8_out, int ldm8) {
   const long n = (long)B * dil * dil * th * tw * (C / 4);
-  hipLaunchKernelGGL(wino4_output_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, M, prow, C, B, H, W, th, tw, dil,
-                     scale, bias, relu, y, ldy, amax, relu ? mask8_out : nullptr, ldm8);
+  WINO_LAUNCH(wino_output_kernel, grid_for(n, 256, 8192), s, M, prow, C, B, H, W, th, tw, dil, scale, bias, relu, y, ldy, amax,
+              relu ? mask8_out : nullptr, ldm8);
 }
-void launch_wino4_wgrad_finish(const float* ws, int splits, int Cout, int Cin, float* dst, hipStream_t s) {
-  const long n = (long)Cout * Cin;
-  hipLaunchKernelGGL(wino4_wgrad_finish_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, ws, splits, Cout, Cin, dst);
+void launch_wino_wgrad_finish(int tm, const float* ws, int splits, int Cout, int Cin, float* dst, hipStream_t s) {
+  const long n = (long)Cout * (Cin / (tm == 4 ? wino_finish_cin_per_thread<4> : wino_finish_cin_per_thread<2>));
+  WINO_LAUNCH(wino_wgrad_finish_kernel, grid_for(n, 256), s, ws, splits, Cout, Cin, dst);
 }
-void launch_wino4_dgrad_output(const float* dV, long prow, int C, int B, int H, int W, int th, int tw, int dil,
-                               const uint8_t* mask8, int ldm8, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s,
-                               unsigned* amax) {
+void launch_wino_dgrad_output(int tm, const float* dV, long prow, int C, int B, int H, int W, int th, int tw, int dil,
+                              const uint8_t* mask8, int ldm8, int mask_c0, int accum, float* gx, int ldgx, hipStream_t s,
+                              unsigned* amax) {
   const long n = (long)B * dil * dil * th * tw * (C / 4);
-  hipLaunchKernelGGL(wino4_dgrad_output_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, dV, prow, C, B, H, W, th, tw,
-                     dil, mask8, ldm8, mask_c0, accum, gx, ldgx, amax);
+  WINO_LAUNCH(wino_dgrad_output_kernel, grid_for(n, 256, 8192), s, dV, prow, C, B, H, W, th, tw, dil, mask8, ldm8, mask_c0, accum,
+              gx, ldgx, amax);
 }
+#undef WINO_LAUNCH
 }  // namespace eosvos

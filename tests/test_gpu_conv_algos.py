@@ -74,6 +74,10 @@ WINO_CASES = [
     ('direct', (1, 30, 54, 2048, 256, 12)),       # tap tables (d = 12, 18 keep the implicit-GEMM kernel)
     ('direct', (1, 30, 54, 2048, 256, 18)),
     ('direct', (1, 120, 214, 304, 256, 1)),
+    # (appended: the position of a case is its test id)
+    ('wino_f4', (1, 5, 7, 64, 64, 1)),            # th = 2: the data gradient's neighbour gather meets both borders at once
+    ('wino_f4', (2, 31, 55, 128, 64, 3)),         # forced F(4,3) on the odd sub-grids of an odd dilation, batch 2
+    ('wino_f2', (3, 6, 6, 64, 64, 2)),            # batch 3, 3x3 sub-grids: th = tw = 2
 ]
 # measured maxima (profiles/r02_conv_algo_margins.txt): direct 3e-7, F(2,3) 1e-6, F(4,3) 8e-6 of the output scale
 TOL = {'direct': 3e-6, 'wino_f2': 6e-6, 'wino_f4': 2.5e-5}

@@ -1,5 +1,6 @@
-"""CPU checks of the Winograd transforms the HIP kernels hard-code (csrc/misc_kernels.hip): the F(4x4,3x3) matrices are
-parsed from the source and, with the F(2x2,3x3) ones, must reproduce a direct 3x3 correlation and its adjoints."""
+"""CPU checks of the Winograd transforms the HIP kernels hard-code (csrc/misc_kernels.hip, WinoMat<2> / WinoMat<4>): the
+F(2x2,3x3) and F(4x4,3x3) matrices are parsed from the source and must reproduce a direct 3x3 correlation and its adjoints;
+the F(2x2,3x3) ones must also be the textbook matrices."""
 import os
 import re
 
@@ -17,9 +18,15 @@ def _parse(name, rows, cols):
 
 
 F4 = dict(BT=_parse('BT', 6, 6), G=_parse('G', 6, 3), AT=_parse('AT', 4, 6))
-F2 = dict(BT=np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], float),
-          G=np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], float),
-          AT=np.array([[1, 1, 1, 0], [0, 1, -1, -1]], float))
+F2 = dict(BT=_parse('BT', 4, 4), G=_parse('G', 4, 3), AT=_parse('AT', 2, 4))
+F2_REF = dict(BT=np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], float),
+              G=np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], float),
+              AT=np.array([[1, 1, 1, 0], [0, 1, -1, -1]], float))
+
+
+def test_f23_matrices_are_the_textbook_ones():
+    for k in F2_REF:
+        np.testing.assert_array_equal(F2[k], F2_REF[k])
 
 
 def _corr(d, g, m):
@@ -37,8 +44,8 @@ def test_winograd_forward_identity():
 
 
 def test_winograd_adjoints():
-    """dM = A dY A^T, dd = B dV B^T, dg = G^T dU G are the gradients of Y w.r.t. M, d and g (what wino*_grad,
-    wino*_dgrad_output and wino*_wgrad_finish compute)."""
+    """dM = A dY A^T, dd = B dV B^T, dg = G^T dU G are the gradients of Y w.r.t. M, d and g (what wino_grad_kernel,
+    wino_dgrad_output_kernel and wino_wgrad_finish_kernel compute)."""
     rng = np.random.default_rng(1)
     for F, m in ((F2, 2), (F4, 4)):
         d, g, dY = rng.standard_normal((m + 2, m + 2)), rng.standard_normal((3, 3)), rng.standard_normal((m, m))
