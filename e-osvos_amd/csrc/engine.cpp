@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <functional>
 #include <map>
 #include <set>
@@ -197,6 +198,9 @@ struct eosvos_engine {
   bool keep_grads = false;
   // learned-lr storage level (meta_optim.py:27-67): the update consumes `lr` (per neuron) or `lr_elem`
   int loss_kind = EOSVOS_LOSS_BCE;      // loss of the fused entry points (eosvos_set_loss)
+  bool loss_ignore_on = false;          // eosvos_set_loss_ignore: the fused entry points evaluate their loss with a void label
+  float loss_ignore = 0.f;
+  int* prop_count = nullptr;            // eosvos_propagation_targets: per-frame positive counts
   float* lovasz_scratch = nullptr;      // sort buffers of the Lovasz hinge kinds, allocated when one is first selected or used
   int* aug_tab = nullptr;               // eosvos_warp_affine: adelta[W] bdelta[W] X0[H] Y0[H], then the nonzero counter
   float* aug_ctab = nullptr;            // bicubic coefficients at 1/32 pixel: [32][4]
@@ -1688,7 +1692,7 @@ int eosvos_create_ex(eosvos_engine** out, int arch, int norm_mode, int height, i
   ALLOC(e->d2, n4 * 256); ALLOC(e->g_d2, n4 * 256);
   ALLOC(e->lowlog, n4); ALLOC(e->g_low, n4);
   ALLOC(e->logits, (int64_t)B * H * W); ALLOC(e->dlogits, (int64_t)B * H * W);
-  ALLOC(e->loss_dev, 4); ALLOC(e->bce_partial, 4 * 1024 + 16);
+  ALLOC(e->loss_dev, 4); ALLOC(e->bce_partial, LOSS_IGNORE_PARTIAL_FLOATS);
   {                                               // ReLU mask bytes of the tensors the data gradients read as masks
     // (GroupNorm mode, round 5: the apply pass that writes y = relu(gn(z) (+ res)) writes the bytes)
     auto m8alloc = [&](const float* key, int64_t floats) {     // one byte per 4 floats
@@ -2383,6 +2387,44 @@ int eosvos_loss(eosvos_engine* e, int kind, const float* masks, int batch, float
   HIPOK(hipGetLastError());
   return 0;
 }
+namespace {
+// a void label is a finite value no target can take
+inline bool ignore_ok(float v) { return std::isfinite(v) && (v < 0.f || v > 1.f); }
+constexpr int PROP_MAX_FRAMES = 1024;
+}  // namespace
+int eosvos_loss_ignore(eosvos_engine* e, int kind, const float* masks, int batch, float ignore, float* loss_out) {
+  ModeScope mode_scope(e);
+  if (!e || !masks) return fail("null argument");
+  if (kind < EOSVOS_LOSS_BCE || kind > EOSVOS_LOSS_LOVASZ_HINGE_FLAT) return fail("unknown loss kind");
+  if (!ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  if (batch != e->lastB) return fail("loss batch differs from the last forward");
+  if (lovasz_kind(kind)) {
+    if (lovasz_ensure(e)) return 1;
+    launch_lovasz_ignore(e->logits, masks, e->dlogits, e->loss_dev, e->lovasz_scratch, (int64_t)e->H * e->W, batch,
+                         kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT, ignore, e->s);
+  } else {
+    launch_loss_ignore(e->logits, masks, e->dlogits, e->loss_dev, e->bce_partial, (int64_t)batch * e->H * e->W, kind, ignore,
+                       e->s);
+  }
+  e->have_loss_grad = true;
+  if (loss_out) HIPOK(hipMemcpyAsync(loss_out, e->loss_dev, 4, hipMemcpyDeviceToDevice, e->s));
+  HIPOK(hipGetLastError());
+  return 0;
+}
+int eosvos_set_loss_ignore(eosvos_engine* e, int on, float ignore) {
+  if (!e) return fail("null engine");
+  if (on && !ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  e->loss_ignore_on = on != 0;
+  e->loss_ignore = on ? ignore : 0.f;
+  return 0;
+}
+namespace {
+// the loss of the fused entry points
+inline int fused_loss(eosvos_engine* e, const float* masks, int batch) {
+  return e->loss_ignore_on ? eosvos_loss_ignore(e, e->loss_kind, masks, batch, e->loss_ignore, nullptr)
+                           : eosvos_loss(e, e->loss_kind, masks, batch, nullptr);
+}
+}  // namespace
 int eosvos_last_loss(eosvos_engine* e, float* loss_out) {
   if (!e || !loss_out) return fail("null argument");
   HIPOK(hipMemcpyAsync(loss_out, e->loss_dev, 4, hipMemcpyDeviceToDevice, e->s));
@@ -2427,6 +2469,45 @@ int eosvos_loss_tensors(eosvos_engine* e, int kind, const float* logits, const f
   HIPOK(hipGetLastError());
   return 0;
 }
+int eosvos_loss_tensors_ignore(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n, float ignore,
+                               float* loss_out) {
+  ModeScope mode_scope(e);
+  if (!e || !logits || !masks || !loss_out || n < 1) return fail("bad argument");
+  if (kind < EOSVOS_LOSS_BCE || kind > EOSVOS_LOSS_LOVASZ_HINGE_FLAT) return fail("unknown loss kind");
+  if (!ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  if (n > (int64_t)e->maxB * e->H * e->W) return fail("n exceeds the engine's scratch");
+  if (lovasz_kind(kind) && lovasz_ensure(e)) return 1;
+  e->have_loss_grad = false;              // the gradient scratch is overwritten
+  if (lovasz_kind(kind)) launch_lovasz_ignore(logits, masks, e->dlogits, loss_out, e->lovasz_scratch, n, 1, 1, ignore, e->s);
+  else launch_loss_ignore(logits, masks, e->dlogits, loss_out, e->bce_partial, n, kind, ignore, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+int eosvos_propagation_targets(eosvos_engine* e, const float* probs, int n_frames, int64_t n_pix, float lo, float hi,
+                               float ignore, float* targets_out, int64_t* n_pos_host) {
+  if (!e || !probs || !targets_out) return fail("null argument");
+  if (n_frames < 1 || n_frames > PROP_MAX_FRAMES || n_pix < 1 || n_pix >= ((int64_t)1 << 31))
+    return fail("eosvos_propagation_targets: 1 .. 1024 frames of 1 .. 2^31 - 1 pixels");
+  if (!(lo >= 0.f && lo < hi && hi <= 1.f)) return fail("eosvos_propagation_targets: needs 0 <= lo < hi <= 1");
+  if (!ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  if (!e->prop_count) {
+    e->prop_count = (int*)e->falloc(PROP_MAX_FRAMES);
+    if (!e->prop_count) {
+      (void)hipGetLastError();
+      return fail("hipMalloc propagation counters");
+    }
+  }
+  HIPOK(hipMemsetAsync(e->prop_count, 0, sizeof(int) * n_frames, e->s));
+  launch_propagation_targets(probs, targets_out, e->prop_count, n_frames, n_pix, lo, hi, ignore, e->s);
+  HIPOK(hipGetLastError());
+  if (n_pos_host) {
+    std::vector<int> host(n_frames);
+    HIPOK(hipMemcpyAsync(host.data(), e->prop_count, sizeof(int) * n_frames, hipMemcpyDeviceToHost, e->s));
+    HIPOK(hipStreamSynchronize(e->s));
+    for (int f = 0; f < n_frames; ++f) n_pos_host[f] = host[f];
+  }
+  return 0;
+}
 int eosvos_backward_step(eosvos_engine* e, int accumulate) {
   ModeScope mode_scope(e);
   if (!e) return fail("null engine");
@@ -2436,7 +2517,7 @@ int eosvos_finetune_step(eosvos_engine* e, const float* images, const float* mas
                          float* loss_host) {
   ModeScope mode_scope(e);
   if (eosvos_forward(e, images, batch, nullptr)) return 1;
-  if (eosvos_loss(e, e->loss_kind, masks, batch, nullptr)) return 1;
+  if (fused_loss(e, masks, batch)) return 1;
   if (backward_impl(e, true, accumulate != 0)) return 1;
   if (loss_host) {
     HIPOK(hipMemcpyAsync(loss_host, e->loss_dev, 4, hipMemcpyDeviceToHost, e->s));
@@ -2594,7 +2675,7 @@ int eosvos_meta_grad_ex(eosvos_engine* e, const float* images, const float* mask
   if (!e || !images || !masks || !flat_meta_grad) return fail("null argument");
   if (!e->gsum) return fail("eosvos_meta_grad without eosvos_meta_task_begin");
   if (eosvos_forward(e, images, batch, nullptr)) return 1;
-  if (eosvos_loss(e, e->loss_kind, masks, batch, nullptr)) return 1;
+  if (fused_loss(e, masks, batch)) return 1;
   const bool keep = e->keep_grads;
   e->keep_grads = true;
   const int rc = backward_impl(e, false, false);

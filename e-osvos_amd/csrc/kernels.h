@@ -368,6 +368,20 @@ void launch_dice(const float* logits, const float* gt, float* dlogits, float* lo
 int64_t lovasz_scratch_floats(int64_t n_total, int max_images);
 void launch_lovasz(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_image,
                    int images, int flat, hipStream_t s);
+// The losses with a void label: a pixel with gt == ignore (a finite value outside [0, 1]) is in no sum, count or sort and its
+// gradient is +0; an empty valid set gives loss 0.  launch_loss_ignore: kind 0 BCE over the valid pixels, 1 dice, 2 BCE - log(1
+// - dice), 3 class-balanced BCE (sums and counts over the valid pixels, the trailing divisions by n); partial >=
+// LOSS_IGNORE_PARTIAL_FLOATS floats.  launch_lovasz_ignore: launch_lovasz with the void pixels dropped before the ranking
+// (flatten_binary_scores, loss_lovasz.py:114-126).  Without a void pixel both give the bits of the unmasked launches.
+constexpr int LOSS_IGNORE_PARTIAL_FLOATS = 5 * 1024 + 16;
+void launch_loss_ignore(const float* logits, const float* gt, float* dlogits, float* loss, float* partial, int64_t n, int kind,
+                        float ignore, hipStream_t s);
+void launch_lovasz_ignore(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_image,
+                          int images, int flat, float ignore, hipStream_t s);
+// targets = 1 where probs >= hi, 0 where probs < lo, `ignore` between, for n_frames maps of n_pix; n_pos[frame] (zeroed by the
+// caller) += the frame's number of 1s
+void launch_propagation_targets(const float* probs, float* targets, int* n_pos, int n_frames, int64_t n_pix, float lo, float hi,
+                                float ignore, hipStream_t s);
 void launch_sigmoid(const float* x, float* y, int64_t n, hipStream_t s);
 void launch_merge_labels(const float* probs, int n_obj, int64_t n_pix, uint8_t* labels, hipStream_t s);
 // cv2.warpAffine (+ optional horizontal flip of the source) of C planes; tables = adelta[W] bdelta[W] X0[H] Y0[H]

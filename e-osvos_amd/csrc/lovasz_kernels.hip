@@ -8,6 +8,8 @@
 //
 // Pipeline (one stream, no host round trip, no workgroup waits for another: every dependency is a kernel boundary):
 //   prep      e per pixel; per-tile counts of e > 0, of g, and a non-finite flag; dlogits <- 0
+//             (with a void label, `ignore=` of loss_lovasz.py:114-126: a pixel with t == ignore is dropped here and in compact,
+//             so the segment sizes below count valid pixels only; size 0 is legal and gives loss 0)
 //   compact   the pixels with e > 0 only, in index order, as (key = ~bits(e), value = index << 1 | g).  Pixels with e <= 0
 //             rank last and change no higher rank's counts, so they never enter the sort.
 //   4 x (hist, scan, scatter)   stable LSD radix sort, 8-bit digits, segmented by image.  The rank of an element within its
@@ -95,9 +97,14 @@ __device__ __forceinline__ long lv_elem(int tile, int j) {
   return (long)tile * LV_TILE + (threadIdx.x >> 6) * LV_WSPAN + j * 64 + (threadIdx.x & 63);
 }
 
-__global__ __launch_bounds__(LV_THREADS) void lovasz_prep_kernel(const float* __restrict__ x, const float* __restrict__ t,
-                                                                 float* __restrict__ dx, int* __restrict__ tinfo, long seg_len,
-                                                                 int tps) {
+// VOID: a pixel with t == ign is dropped here and in the compaction (flatten_binary_scores, loss_lovasz.py:114-126): it counts
+// neither as e > 0 nor as foreground, its logit may be non-finite, and dlogits stays the +0 written below.
+// The body is shared; the kernel without a void label keeps its own entry point and arguments (and, checked in the
+// disassembly, the code it had before the void form existed).
+template <bool VOID>
+__device__ __forceinline__ void lovasz_prep_body(const float* __restrict__ x, const float* __restrict__ t,
+                                                 float* __restrict__ dx, int* __restrict__ tinfo, long seg_len, int tps,
+                                                 float ign) {
   __shared__ int sh[4];
   const int seg = blockIdx.x / tps, tile = blockIdx.x % tps;
   const long seg0 = (long)seg * seg_len;
@@ -106,10 +113,11 @@ __global__ __launch_bounds__(LV_THREADS) void lovasz_prep_kernel(const float* __
   for (int j = 0; j < LV_ITEMS; ++j) {
     const long i = lv_elem(tile, j);
     if (i < seg_len) {
-      const float xv = x[seg0 + i];
+      const float xv = x[seg0 + i], tv = t[seg0 + i];
       int g;
-      const float e = lv_error(xv, t[seg0 + i], g);
+      const float e = lv_error(xv, tv, g);
       dx[seg0 + i] = 0.f;
+      if (VOID && tv == ign) continue;
       m += e > 0.f ? 1 : 0;
       G += g;
       nf |= (__float_as_uint(xv) & 0x7f800000u) == 0x7f800000u ? 1 : 0;
@@ -124,10 +132,23 @@ __global__ __launch_bounds__(LV_THREADS) void lovasz_prep_kernel(const float* __
   }
 }
 
-__global__ __launch_bounds__(LV_THREADS) void lovasz_compact_kernel(const float* __restrict__ x, const float* __restrict__ t,
-                                                                    const int* __restrict__ tinfo, int* __restrict__ sinfo,
-                                                                    unsigned* __restrict__ keys, unsigned* __restrict__ vals,
-                                                                    long seg_len, int tps) {
+__global__ __launch_bounds__(LV_THREADS) void lovasz_prep_kernel(const float* __restrict__ x, const float* __restrict__ t,
+                                                                 float* __restrict__ dx, int* __restrict__ tinfo, long seg_len,
+                                                                 int tps) {
+  lovasz_prep_body<false>(x, t, dx, tinfo, seg_len, tps, 0.f);
+}
+__global__ __launch_bounds__(LV_THREADS) void lovasz_prep_ign_kernel(const float* __restrict__ x, const float* __restrict__ t,
+                                                                     float* __restrict__ dx, int* __restrict__ tinfo,
+                                                                     long seg_len, int tps, float ign) {
+  lovasz_prep_body<true>(x, t, dx, tinfo, seg_len, tps, ign);
+}
+
+// VOID: as in prep, a pixel with t == ign is left out of the compaction.  One body for both kernels.
+template <bool VOID>
+__device__ __forceinline__ void lovasz_compact_body(const float* __restrict__ x, const float* __restrict__ t,
+                                                    const int* __restrict__ tinfo, int* __restrict__ sinfo,
+                                                    unsigned* __restrict__ keys, unsigned* __restrict__ vals, long seg_len,
+                                                    int tps, float ign) {
   __shared__ int sh[4];
   __shared__ int wtot[4];
   const int seg = blockIdx.x / tps, tile = blockIdx.x % tps;
@@ -161,7 +182,11 @@ __global__ __launch_bounds__(LV_THREADS) void lovasz_compact_kernel(const float*
   for (int j = 0; j < LV_ITEMS; ++j) {
     const long i = lv_elem(tile, j);
     e[j] = 0.f; g[j] = 0;
-    if (i < seg_len) e[j] = lv_error(x[seg0 + i], t[seg0 + i], g[j]);
+    if (i < seg_len) {
+      const float tv = t[seg0 + i];
+      e[j] = lv_error(x[seg0 + i], tv, g[j]);
+      if (VOID && tv == ign) e[j] = 0.f;           // a select: ranks with the e <= 0 pixels, i.e. never enters the sort
+    }
     bal[j] = __ballot(e[j] > 0.f);               // (a NaN error compares false: it ranks with the e <= 0 pixels)
     total += __popcll(bal[j]);
   }
@@ -179,6 +204,19 @@ __global__ __launch_bounds__(LV_THREADS) void lovasz_compact_kernel(const float*
     }
     run += __popcll(bal[j]);
   }
+}
+
+__global__ __launch_bounds__(LV_THREADS) void lovasz_compact_kernel(const float* __restrict__ x, const float* __restrict__ t,
+                                                                    const int* __restrict__ tinfo, int* __restrict__ sinfo,
+                                                                    unsigned* __restrict__ keys, unsigned* __restrict__ vals,
+                                                                    long seg_len, int tps) {
+  lovasz_compact_body<false>(x, t, tinfo, sinfo, keys, vals, seg_len, tps, 0.f);
+}
+__global__ __launch_bounds__(LV_THREADS) void lovasz_compact_ign_kernel(const float* __restrict__ x, const float* __restrict__ t,
+                                                                        const int* __restrict__ tinfo, int* __restrict__ sinfo,
+                                                                        unsigned* __restrict__ keys, unsigned* __restrict__ vals,
+                                                                        long seg_len, int tps, float ign) {
+  lovasz_compact_body<true>(x, t, tinfo, sinfo, keys, vals, seg_len, tps, ign);
 }
 
 __global__ __launch_bounds__(LV_THREADS) void lovasz_hist_kernel(const unsigned* __restrict__ keys, const int* __restrict__ sinfo,
@@ -391,8 +429,9 @@ int64_t lovasz_scratch_floats(int64_t n_total, int max_images) {
   return 4 * ((n_total + 1) / 2 * 2) + tiles * (2 + 256 + LV_TINFO) + (int64_t)LV_SINFO * max_images + 16;
 }
 
-void launch_lovasz(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_image,
-                   int images, int flat, hipStream_t s) {
+namespace {
+void lovasz_launches(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_image,
+                     int images, int flat, bool has_ign, float ign, hipStream_t s) {
   const int segs = flat ? 1 : images;
   const int64_t n_total = n_per_image * images;
   const long seg_len = (long)(flat ? n_total : n_per_image);
@@ -400,8 +439,14 @@ void launch_lovasz(const float* logits, const float* gt, float* dlogits, float* 
   const int nb = segs * tps;
   const LvScratch L = lv_carve(scratch, n_total, nb, segs);
   const dim3 grid(nb), block(LV_THREADS);
-  hipLaunchKernelGGL(lovasz_prep_kernel, grid, block, 0, s, logits, gt, dlogits, L.tinfo, seg_len, tps);
-  hipLaunchKernelGGL(lovasz_compact_kernel, grid, block, 0, s, logits, gt, L.tinfo, L.sinfo, L.key[0], L.val[0], seg_len, tps);
+  if (has_ign) {
+    hipLaunchKernelGGL(lovasz_prep_ign_kernel, grid, block, 0, s, logits, gt, dlogits, L.tinfo, seg_len, tps, ign);
+    hipLaunchKernelGGL(lovasz_compact_ign_kernel, grid, block, 0, s, logits, gt, L.tinfo, L.sinfo, L.key[0], L.val[0], seg_len,
+                       tps, ign);
+  } else {
+    hipLaunchKernelGGL(lovasz_prep_kernel, grid, block, 0, s, logits, gt, dlogits, L.tinfo, seg_len, tps);
+    hipLaunchKernelGGL(lovasz_compact_kernel, grid, block, 0, s, logits, gt, L.tinfo, L.sinfo, L.key[0], L.val[0], seg_len, tps);
+  }
   for (int pass = 0; pass < 4; ++pass) {           // (the key's top bit is always set: 31 significant bits, four 8-bit digits)
     const int in = pass & 1, out = in ^ 1;
     hipLaunchKernelGGL(lovasz_hist_kernel, grid, block, 0, s, L.key[in], L.sinfo, L.hist, seg_len, tps, 8 * pass);
@@ -413,6 +458,16 @@ void launch_lovasz(const float* logits, const float* gt, float* dlogits, float* 
   hipLaunchKernelGGL(lovasz_weights_kernel, grid, block, 0, s, L.key[0], L.val[0], L.sinfo, L.tinfo, dlogits, L.partial, seg_len,
                      tps, (long)n_total, 1.0 / (double)segs);
   hipLaunchKernelGGL(lovasz_final_kernel, dim3(1), block, 0, s, L.partial, L.sinfo, loss, segs, tps);
+}
+}  // namespace
+
+void launch_lovasz(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_image,
+                   int images, int flat, hipStream_t s) {
+  lovasz_launches(logits, gt, dlogits, loss, scratch, n_per_image, images, flat, false, 0.f, s);
+}
+void launch_lovasz_ignore(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_image,
+                          int images, int flat, float ignore, hipStream_t s) {
+  lovasz_launches(logits, gt, dlogits, loss, scratch, n_per_image, images, flat, true, ignore, s);
 }
 
 }  // namespace eosvos

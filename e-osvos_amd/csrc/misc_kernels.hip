@@ -1536,6 +1536,231 @@ void launch_dice(const float* logits, const float* gt, float* dlogits, float* lo
   hipLaunchKernelGGL(dice_grad_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, logits, gt, partial + 4 * 1024, dlogits,
                      (long)n);
 }
+
+// ---- the same four losses with a void label: a pixel with t == ign is in no sum and no count, its gradient is +0 ------
+// Kernels of their own beside the ones above (which are untouched): the same grids, the same per-thread accumulation order
+// and the same expressions, so that a map without a void pixel gives the bits of the unmasked launch.  A void pixel's
+// logit is selected away, never multiplied by 0 (it may be NaN / inf).  Every kind is partial -> final -> grad: the valid
+// count |V| is known only after the first pass.  Counts are per-block integers summed in a fixed order.
+//   partial floats: [0, 4096) per-block sums, [4096, 4112) scalars of the final kernel, [4112, 5136) per-block valid counts
+constexpr int LOSS_IGN_SCAL = 4 * 1024, LOSS_IGN_CNT = 4 * 1024 + 16;
+__device__ __forceinline__ int block_sum_256_i(int v, int* sh /*>=4 ints*/) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return sh[0] + sh[1] + sh[2] + sh[3];
+}
+// |V| from the per-block counts, valid in every thread
+__device__ __forceinline__ long valid_total(const int* __restrict__ cnt, int nb, int* shi) {
+  long c = 0;                                     // (a block counts < 2^31 pixels; the total may not fit an int)
+  for (int i = threadIdx.x; i < nb; i += 256) c += cnt[i];
+  const int lo = block_sum_256_i((int)(c & 0xffff), shi), hi = block_sum_256_i((int)(c >> 16), shi);
+  return ((long)hi << 16) + lo;
+}
+__global__ __launch_bounds__(256) void bce_ign_partial_kernel(const float* __restrict__ x, const float* __restrict__ t,
+                                                               float* __restrict__ partial, int* __restrict__ cnt, long n,
+                                                               float ign) {
+  __shared__ float sh[4];
+  __shared__ int shi[4];
+  float s = 0.f;
+  int c = 0;
+  GRID_STRIDE(i, n) {
+    const float xv = x[i], tv = t[i];
+    const bool ok = tv != ign;
+    const float e = expf(-fabsf(xv));
+    const float v = fmaxf(xv, 0.f) - xv * tv + log1pf(e);
+    s = ok ? s + v : s;
+    c += ok ? 1 : 0;
+  }
+  s = block_sum_256(s, sh);
+  c = block_sum_256_i(c, shi);
+  if (threadIdx.x == 0) { partial[blockIdx.x] = s; cnt[blockIdx.x] = c; }
+}
+// scal = {loss, 1 / |V|} (0 for an empty V)
+__global__ __launch_bounds__(256) void bce_ign_final_kernel(const float* __restrict__ partial, const int* __restrict__ cnt,
+                                                             float* __restrict__ loss, float* __restrict__ scal, int nb) {
+  __shared__ float sh[4];
+  __shared__ int shi[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) s += partial[i];
+  s = block_sum_256(s, sh);
+  const long V = valid_total(cnt, nb, shi);
+  if (threadIdx.x == 0) {
+    const float inv = V > 0 ? 1.0f / (float)V : 0.f;
+    loss[0] = V > 0 ? s * inv : 0.f;
+    scal[0] = loss[0]; scal[1] = inv;
+  }
+}
+__global__ void bce_ign_grad_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ scal,
+                                    float* __restrict__ dx, long n, float ign) {
+  const float inv_n = scal[1];
+  GRID_STRIDE(i, n) {
+    const float xv = x[i], tv = t[i];
+    const float e = expf(-fabsf(xv));
+    const float sig = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+    dx[i] = tv != ign ? (sig - tv) * inv_n : 0.f;
+  }
+}
+__global__ __launch_bounds__(256) void dice_ign_partial_kernel(const float* __restrict__ x, const float* __restrict__ t,
+                                                                float4* __restrict__ partial, int* __restrict__ cnt, long n,
+                                                                float ign) {
+  __shared__ float sh[4];
+  __shared__ int shi[4];
+  float a = 0.f, b = 0.f, c = 0.f, d = 0.f;
+  int k = 0;
+  GRID_STRIDE(i, n) {
+    const float xv = x[i], tv = t[i];
+    const bool ok = tv != ign;
+    const float e = expf(-fabsf(xv));
+    const float p = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+    const float v = fmaxf(xv, 0.f) - xv * tv + log1pf(e);
+    a = ok ? a + p * tv : a; b = ok ? b + p : b; c = ok ? c + tv : c;
+    d = ok ? d + v : d;
+    k += ok ? 1 : 0;
+  }
+  a = block_sum_256(a, sh); b = block_sum_256(b, sh); c = block_sum_256(c, sh); d = block_sum_256(d, sh);
+  k = block_sum_256_i(k, shi);
+  if (threadIdx.x == 0) { partial[blockIdx.x] = make_float4(a, b, c, d); cnt[blockIdx.x] = k; }
+}
+// dice_final_kernel with |V| in the place of n; an empty V gives num = D = 1: dice = 0, -log(1 - 0) = 0, and no BCE term
+__global__ __launch_bounds__(256) void dice_ign_final_kernel(const float4* __restrict__ partial, const int* __restrict__ cnt,
+                                                              int nb, int kind, float* __restrict__ loss,
+                                                              float* __restrict__ scal) {
+  __shared__ double sh[4][4];
+  __shared__ int shi[4];
+  double a = 0, b = 0, c = 0, d = 0;
+  for (int i = threadIdx.x; i < nb; i += 256) { const float4 v = partial[i]; a += v.x; b += v.y; c += v.z; d += v.w; }
+  for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); c += __shfl_xor(c, o, 64); d += __shfl_xor(d, o, 64); }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { sh[w][0] = a; sh[w][1] = b; sh[w][2] = c; sh[w][3] = d; }
+  const long V = valid_total(cnt, nb, shi);       // (its barriers also publish sh)
+  if (threadIdx.x == 0) {
+    double I = 0, Sp = 0, Sy = 0, Sb = 0;
+    for (int k = 0; k < 4; ++k) { I += sh[k][0]; Sp += sh[k][1]; Sy += sh[k][2]; Sb += sh[k][3]; }
+    const double num = 2.0 * I + 1.0, D = Sp + Sy + 1.0;
+    const double dice = 1.0 - num / D;
+    if (kind == 1) {
+      loss[0] = (float)dice;
+      scal[1] = (float)(-2.0 / D); scal[2] = (float)(num / (D * D)); scal[3] = 0.f;
+    } else {
+      loss[0] = V > 0 ? (float)(Sb / (double)V - log(num / D)) : 0.f;
+      scal[1] = (float)(-2.0 / num); scal[2] = (float)(1.0 / D); scal[3] = V > 0 ? (float)(1.0 / (double)V) : 0.f;
+    }
+    scal[0] = loss[0];
+  }
+}
+__global__ void dice_ign_grad_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ scal,
+                                     float* __restrict__ dx, long n, float ign) {
+  const float cy = scal[1], c1 = scal[2], bw = scal[3];
+  GRID_STRIDE(i, n) {
+    const float xv = x[i], tv = t[i];
+    const float e = expf(-fabsf(xv));
+    const float p = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+    dx[i] = tv != ign ? bw * (p - tv) + (cy * tv + c1) * p * (1.f - p) : 0.f;
+  }
+}
+// class-balanced BCE over V (loss_ce.py:42-53): N_pos, N_neg and the two sums run over V, num_total = |V|; the two trailing
+// divisions (`:55`, `:58`) stay those of the tensor's full shape, n:  L = (N_neg * S_pos + N_pos * S_neg) / (|V| * n)
+__global__ __launch_bounds__(256) void cbce_ign_partial_kernel(const float* __restrict__ x, const float* __restrict__ t,
+                                                                float4* __restrict__ partial, int* __restrict__ cnt, long n,
+                                                                float ign) {
+  __shared__ float sh[4];
+  __shared__ int shi[4];
+  float a = 0.f, b = 0.f, c = 0.f;
+  int k = 0;
+  GRID_STRIDE(i, n) {
+    const float xv = x[i], tv = t[i];
+    const bool ok = tv != ign;
+    const float l = tv >= 0.5f ? 1.f : 0.f;
+    const float v = fmaxf(xv, 0.f) - xv * l + log1pf(expf(-fabsf(xv)));
+    a = ok ? a + l : a; b = ok ? b + l * v : b; c = ok ? c + (1.f - l) * v : c;
+    k += ok ? 1 : 0;
+  }
+  a = block_sum_256(a, sh); b = block_sum_256(b, sh); c = block_sum_256(c, sh);
+  k = block_sum_256_i(k, shi);
+  if (threadIdx.x == 0) { partial[blockIdx.x] = make_float4(a, b, c, 0.f); cnt[blockIdx.x] = k; }
+}
+__global__ __launch_bounds__(256) void cbce_ign_final_kernel(const float4* __restrict__ partial, const int* __restrict__ cnt,
+                                                              int nb, long n, float* __restrict__ loss,
+                                                              float* __restrict__ scal) {
+  __shared__ double sh[4][3];
+  __shared__ int shi[4];
+  double a = 0, b = 0, c = 0;
+  for (int i = threadIdx.x; i < nb; i += 256) { const float4 v = partial[i]; a += v.x; b += v.y; c += v.z; }
+  for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); c += __shfl_xor(c, o, 64); }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { sh[w][0] = a; sh[w][1] = b; sh[w][2] = c; }
+  const long V = valid_total(cnt, nb, shi);       // (its barriers also publish sh)
+  if (threadIdx.x == 0) {
+    double Np = 0, Sp = 0, Sn = 0;
+    for (int k = 0; k < 4; ++k) { Np += sh[k][0]; Sp += sh[k][1]; Sn += sh[k][2]; }
+    const double N = (double)n, T = (double)V, Nn = T - Np;
+    loss[0] = V > 0 ? (float)((Nn * Sp + Np * Sn) / (T * N)) : 0.f;
+    scal[0] = loss[0];
+    scal[1] = V > 0 ? (float)(Nn / (T * N)) : 0.f; scal[2] = V > 0 ? (float)(Np / (T * N)) : 0.f;
+  }
+}
+__global__ void cbce_ign_grad_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ scal,
+                                     float* __restrict__ dx, long n, float ign) {
+  const float wp = scal[1], wn = scal[2];
+  GRID_STRIDE(i, n) {
+    const float xv = x[i], tv = t[i];
+    const bool pos = tv >= 0.5f;
+    const float e = expf(-fabsf(xv));
+    const float p = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+    const float g = pos ? wp * (p - 1.f) : wn * p;
+    dx[i] = tv != ign ? g : 0.f;
+  }
+}
+void launch_loss_ignore(const float* logits, const float* gt, float* dlogits, float* loss, float* partial, int64_t n, int kind,
+                        float ignore, hipStream_t s) {
+  float* scal = partial + LOSS_IGN_SCAL;
+  int* cnt = (int*)(partial + LOSS_IGN_CNT);
+  const dim3 one(1), block(256), all(grid_for(n, 256));
+  if (kind == 0) {
+    const int nb = grid_for(n, 256, BCE_BLOCKS);
+    hipLaunchKernelGGL(bce_ign_partial_kernel, dim3(nb), block, 0, s, logits, gt, partial, cnt, (long)n, ignore);
+    hipLaunchKernelGGL(bce_ign_final_kernel, one, block, 0, s, partial, cnt, loss, scal, nb);
+    hipLaunchKernelGGL(bce_ign_grad_kernel, all, block, 0, s, logits, gt, scal, dlogits, (long)n, ignore);
+    return;
+  }
+  const int nb = grid_for(n, 256, 1024);
+  if (kind == 3) {
+    hipLaunchKernelGGL(cbce_ign_partial_kernel, dim3(nb), block, 0, s, logits, gt, (float4*)partial, cnt, (long)n, ignore);
+    hipLaunchKernelGGL(cbce_ign_final_kernel, one, block, 0, s, (const float4*)partial, cnt, nb, (long)n, loss, scal);
+    hipLaunchKernelGGL(cbce_ign_grad_kernel, all, block, 0, s, logits, gt, scal, dlogits, (long)n, ignore);
+    return;
+  }
+  hipLaunchKernelGGL(dice_ign_partial_kernel, dim3(nb), block, 0, s, logits, gt, (float4*)partial, cnt, (long)n, ignore);
+  hipLaunchKernelGGL(dice_ign_final_kernel, one, block, 0, s, (const float4*)partial, cnt, nb, kind, loss, scal);
+  hipLaunchKernelGGL(dice_ign_grad_kernel, all, block, 0, s, logits, gt, scal, dlogits, (long)n, ignore);
+}
+
+// ---- pseudo-label targets of online adaptation with an uncertainty band -----------------------------------------------
+// targets = 1 where p >= hi, 0 where p < lo, `ign` between (a NaN probability is void); n_pos[frame] += the frame's count
+// of 1s: summed over the wave, one integer atomic per wave (integer adds commute: the counts do not depend on arrival order)
+__global__ __launch_bounds__(256) void propagation_targets_kernel(const float* __restrict__ probs, float* __restrict__ targets,
+                                                                   int* __restrict__ n_pos, long n_pix, float lo, float hi,
+                                                                   float ign) {
+  const long f0 = (long)blockIdx.y * n_pix;
+  int c = 0;
+  GRID_STRIDE(i, n_pix) {
+    const float p = probs[f0 + i];
+    const bool pos = p >= hi;
+    targets[f0 + i] = pos ? 1.f : (p < lo ? 0.f : ign);
+    c += pos ? 1 : 0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(n_pos + blockIdx.y, c);
+}
+void launch_propagation_targets(const float* probs, float* targets, int* n_pos, int n_frames, int64_t n_pix, float lo, float hi,
+                                float ignore, hipStream_t s) {
+  hipLaunchKernelGGL(propagation_targets_kernel, dim3(grid_for(n_pix, 256, 1024), n_frames), dim3(256), 0, s, probs, targets,
+                     n_pos, (long)n_pix, lo, hi, ignore);
+}
 }  // namespace eosvos
 
 // ---- device-side data augmentation: cv2.warpAffine restated (custom_transforms.py:41-51) -----------------

@@ -53,6 +53,15 @@ LOSS_KINDS = {'cross_entropy': 0, 'dice': 1, 'cross_entropy_and_dice': 2, 'class
               'lovasz_hinge': 4, 'lovasz_hinge_flat': 5}      # the last two: networks/loss_lovasz.py:78-111, per_image True / False
 
 
+def check_ignore(ignore):
+    """The void label of a loss (`ignore=` of networks/loss_lovasz.py:78-126) as a float: finite and outside [0, 1], so that no
+    target can take it."""
+    v = float(ignore)
+    if v != v or v in (float('inf'), float('-inf')) or 0.0 <= v <= 1.0:
+        raise ValueError(f'ignore={ignore!r}: the void label must be finite and outside [0, 1]')
+    return v
+
+
 def set_matrix_mode(mode):
     """'f16x3' (default), 'bf16x6' or 'f32': how the convolutions' fp32 contractions use the matrix cores (process-wide; include/eosvos.h)."""
     _ffi.check(_ffi.load().eosvos_set_matrix_mode({'f32': 0, 'bf16x6': 1, 'f16x3': 2}[mode]))
@@ -180,11 +189,13 @@ class Engine:
         self.lr_level, self.lr_log, self.n_lr_store = level, bool(use_log), n
         self.synchronize()
 
-    def set_loss(self, name):
-        """Loss of finetune_step / meta_grad (`loss_func`, helper_func.py:28-56)."""
+    def set_loss(self, name, ignore=None):
+        """Loss of finetune_step / meta_grad (`loss_func`, helper_func.py:28-56) and its void label (None: every pixel counts)."""
         if name not in LOSS_KINDS:
             raise NotImplementedError(name)             # helper_func.py:55-56
+        v = None if ignore is None else check_ignore(ignore)
         _ffi.check(self.lib.eosvos_set_loss(self.h, LOSS_KINDS[name]))
+        _ffi.check(self.lib.eosvos_set_loss_ignore(self.h, int(v is not None), v or 0.0))
 
     def set_norm(self, gamma, beta, mean, var, eps=1e-5):
         ts = [_dev_f32(t, self.device) for t in (gamma, beta, mean, var)]
@@ -324,8 +335,16 @@ class Engine:
             return 'f16x3'
         return self._verify_step(images, masks, loss_kind)
 
-    def _verify_step(self, images, masks, loss_kind=None):
-        """The fine-tune-step half of the guard (see verify_matrix_mode): one step in each split mode from the same weights."""
+    def _loss_call(self, kind, masks, ignore, out):
+        """eosvos_loss, or eosvos_loss_ignore with a void label, on the last forward."""
+        if ignore is None:
+            _ffi.check(self.lib.eosvos_loss(self.h, LOSS_KINDS[kind], _ptr(masks), masks.shape[0], _optr(out)))
+        else:
+            _ffi.check(self.lib.eosvos_loss_ignore(self.h, LOSS_KINDS[kind], _ptr(masks), masks.shape[0], ignore, _optr(out)))
+
+    def _verify_step(self, images, masks, loss_kind=None, ignore=None):
+        """The fine-tune-step half of the guard (see verify_matrix_mode): one step in each split mode from the same weights.
+        `loss_kind` None: the fused step with the engine's own loss and void label; otherwise that loss with `ignore`."""
         self._step_check_pending = False
         own = getattr(self, '_own_mode', None)
         b = images.shape[0]
@@ -338,7 +357,7 @@ class Engine:
                     _ffi.check(self.lib.eosvos_finetune_step(self.h, _ptr(images), _ptr(masks), b, 0, None))
                 else:
                     _ffi.check(self.lib.eosvos_forward(self.h, _ptr(images), b, None))
-                    _ffi.check(self.lib.eosvos_loss(self.h, LOSS_KINDS[loss_kind], _ptr(masks), b, None))
+                    self._loss_call(loss_kind, masks, ignore, None)
                     _ffi.check(self.lib.eosvos_backward_step(self.h, 0))
                 loss = torch.empty(1, device=self.device)
                 _ffi.check(self.lib.eosvos_last_loss(self.h, _ptr(loss)))
@@ -384,7 +403,7 @@ class Engine:
             mode = self.verify_matrix_mode(images, masks)
             if masks is None and want_step and mode == 'f16x3':
                 self._step_check_pending = True
-                self._chk_images, self._chk_masks, self._chk_kind = images, None, None
+                self._chk_images, self._chk_masks, self._chk_kind, self._chk_ignore = images, None, None, None
 
     def forward(self, images, want_logits=True):
         b = self._check_images(images)
@@ -400,27 +419,49 @@ class Engine:
         loss = torch.empty(1, device=self.device)
         _ffi.check(self.lib.eosvos_loss_bce(self.h, _ptr(masks), masks.shape[0], _ptr(loss)))
         if getattr(self, '_step_check_pending', False):
-            self._chk_masks, self._chk_kind = masks, 'cross_entropy'
+            self._chk_masks, self._chk_kind, self._chk_ignore = masks, 'cross_entropy', None
         return loss
 
-    def loss(self, kind, masks):
-        """kind: a compute_loss name (helper_func.py:28-56, see LOSS_KINDS); leaves dL/dlogits."""
-        k = LOSS_KINDS[kind]
+    def loss(self, kind, masks, ignore=None):
+        """kind: a compute_loss name (helper_func.py:28-56, see LOSS_KINDS); leaves dL/dlogits.  `ignore`: the void label --
+        pixels whose mask equals it are in no sum, count or ranking and get gradient 0 (`eosvos_loss_ignore`)."""
+        LOSS_KINDS[kind]
+        ignore = None if ignore is None else check_ignore(ignore)
         assert masks.is_cuda and masks.dtype == torch.float32 and masks.is_contiguous()
         out = torch.empty(1, device=self.device)
-        _ffi.check(self.lib.eosvos_loss(self.h, k, _ptr(masks), masks.shape[0], _ptr(out)))
+        self._loss_call(kind, masks, ignore, out)
         if getattr(self, '_step_check_pending', False):
-            self._chk_masks, self._chk_kind = masks, kind
+            self._chk_masks, self._chk_kind, self._chk_ignore = masks, kind, ignore
         return out
 
-    def loss_of(self, kind, logits, masks):
+    def loss_of(self, kind, logits, masks, ignore=None):
         """Value of a compute_loss loss on arbitrary device tensors (one sample of a batch for
-        `batch_average: False`); no gradient is kept."""
+        `batch_average: False`); no gradient is kept.  `ignore`: as in `loss` (`eosvos_loss_tensors_ignore`)."""
         logits, masks = logits.contiguous(), masks.contiguous()
         assert logits.is_cuda and masks.is_cuda and logits.numel() == masks.numel()
         out = torch.empty(1, device=self.device)
-        _ffi.check(self.lib.eosvos_loss_tensors(self.h, LOSS_KINDS[kind], _ptr(logits), _ptr(masks), logits.numel(), _ptr(out)))
+        if ignore is None:
+            _ffi.check(self.lib.eosvos_loss_tensors(self.h, LOSS_KINDS[kind], _ptr(logits), _ptr(masks), logits.numel(), _ptr(out)))
+        else:
+            _ffi.check(self.lib.eosvos_loss_tensors_ignore(self.h, LOSS_KINDS[kind], _ptr(logits), _ptr(masks), logits.numel(),
+                                                           check_ignore(ignore), _ptr(out)))
         return out
+
+    def propagation_targets(self, probs, lo, hi, ignore, counts=True):
+        """Pseudo-label targets of online adaptation with an uncertainty band (`eosvos_propagation_targets`): probs (F, ...)
+        device fp32 -> (targets of the same shape: 1 where p >= hi, 0 where p < lo, `ignore` between; the number of 1s per frame
+        as a list of ints after ONE host read, or None with counts=False)."""
+        self._check_stream()
+        probs = probs.contiguous()
+        assert probs.is_cuda and probs.dtype == torch.float32 and probs.dim() >= 2
+        if not 0.0 <= lo < hi <= 1.0:
+            raise ValueError(f'propagation_targets: needs 0 <= lo < hi <= 1, got {lo!r}, {hi!r}')
+        f = probs.shape[0]
+        out = torch.empty_like(probs)
+        n_pos = (ctypes.c_int64 * f)() if counts else None
+        _ffi.check(self.lib.eosvos_propagation_targets(self.h, _ptr(probs), f, probs[0].numel(), lo, hi, check_ignore(ignore),
+                                                       _ptr(out), n_pos))
+        return out, ([int(v) for v in n_pos] if counts else None)
 
     def bce(self, logits, masks):
         """Mean BCE-with-logits of arbitrary device tensors (no gradient kept)."""
@@ -435,12 +476,13 @@ class Engine:
             # deferred step half of the range guard (callers that go forward -> loss -> backward_step): one step per split mode
             # from the current weights, then the forward + loss of THIS step again in the mode that stays
             x, m, kind = getattr(self, '_chk_images', None), getattr(self, '_chk_masks', None), getattr(self, '_chk_kind', None)
+            ign = getattr(self, '_chk_ignore', None)      # the check repeats the caller's loss, void label included
             self._step_check_pending = False
             self._chk_images = self._chk_masks = None
             if not accumulate and x is not None and m is not None and m.shape[0] == x.shape[0] and _guard_enabled():
-                self._verify_step(x, m, kind)
+                self._verify_step(x, m, kind, ign)
                 _ffi.check(self.lib.eosvos_forward(self.h, _ptr(x), x.shape[0], None))
-                _ffi.check(self.lib.eosvos_loss(self.h, LOSS_KINDS[kind], _ptr(m), m.shape[0], None))
+                self._loss_call(kind, m, ign, None)
         _ffi.check(self.lib.eosvos_backward_step(self.h, int(accumulate)))
         self.steps_since_reset += 1
 

@@ -66,6 +66,20 @@ def _repeat_batch(frame, gt, batch, seed):
     return frame.expand(batch, -1, -1, -1).contiguous(), gt.expand(batch, -1, -1, -1).contiguous()
 
 
+PROPAGATION_IGNORE = 255.0       # the void label of the uncertainty band's targets (PASCAL's void class)
+
+
+def min_prop_band(min_prop):
+    """`eval_online_adapt.min_prop`: a scalar threshold (the reference, evaluate.py:231-240) -> None; a two-element list
+    [lo, hi] with 0 <= lo < hi <= 1 -> (lo, hi): propagated targets are 1 where p >= hi, 0 where p < lo and void between."""
+    if not isinstance(min_prop, (list, tuple)):
+        return None
+    ok = len(min_prop) == 2 and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in min_prop)
+    if not ok or not 0.0 <= float(min_prop[0]) < float(min_prop[1]) <= 1.0:
+        raise ValueError(f'eval_online_adapt.min_prop={min_prop!r}: a number, or [lo, hi] with 0 <= lo < hi <= 1')
+    return float(min_prop[0]), float(min_prop[1])
+
+
 def finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0):
     """One (sequence, object) work item of `evaluate.py:132-317`: fine-tune on the train frame, predict the following
     frames, with online adaptation re-fine-tune every `step` frames.  Returns (probs (N,H,W) with the train frame seeded
@@ -92,6 +106,7 @@ def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, 
     augment = augment or _repeat_batch
     n = frames.shape[0]
     ona = cfg['eval_online_adapt']
+    band = min_prop_band(ona['min_prop'])
     step = ona['step']
     bsz = cfg['data_cfg']['batch_sizes']['train']
     es = cfg.get('train_early_stopping_cfg', {'patience': None, 'min_loss_improv': 0.001})
@@ -114,15 +129,27 @@ def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, 
         num_epochs = cfg['num_epochs']['eval'] if r == 0 else ona['num_epochs']
         model.train_without_dropout()
         round_hist = []
+        loss_kwargs = None
         if r > 0:
             # the adaptation batch of this round: train frame + the propagated frames whose thresholded prediction is
             # not empty (evaluate.py:231-240).  The reference rebuilds it every epoch from the same masks; once is enough.
             round_inputs, round_gts = frames[train_frame_id:train_frame_id + 1], gt
-            for f in rd['propagate_frames']:
-                pg = masks[f:f + 1].ge(ona['min_prop']).float()
-                if pg.sum().item() != 0:                            # evaluate.py:239
-                    round_inputs = torch.cat([round_inputs, frames[f:f + 1]])
-                    round_gts = torch.cat([round_gts, pg])
+            if band is None:
+                for f in rd['propagate_frames']:
+                    pg = masks[f:f + 1].ge(ona['min_prop']).float()
+                    if pg.sum().item() != 0:                            # evaluate.py:239
+                        round_inputs = torch.cat([round_inputs, frames[f:f + 1]])
+                        round_gts = torch.cat([round_gts, pg])
+            elif rd['propagate_frames']:
+                # uncertainty band: one launch builds every propagated frame's targets (void between lo and hi) and counts
+                # its positives, one host read for the round; the train frame's ground truth is never void
+                fs = list(rd['propagate_frames'])
+                pg, n_pos = model.engine.propagation_targets(masks[fs], band[0], band[1], PROPAGATION_IGNORE)
+                keep = [i for i, c in enumerate(n_pos) if c != 0]
+                if keep:                                                # no surviving frame: no void pixel, the plain loss
+                    loss_kwargs = {'ignore': PROPAGATION_IGNORE}
+                    round_inputs = torch.cat([round_inputs, frames[[fs[i] for i in keep]]])
+                    round_gts = torch.cat([round_gts, pg[keep]])
             round_inputs, round_gts = round_inputs.contiguous(), round_gts.contiguous()
         for epoch in range(1, num_epochs + 1):
             set_random_seeds(cfg.get('seed', 1) + epoch + r)
@@ -131,7 +158,7 @@ def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, 
             else:
                 inputs, gts = round_inputs, round_gts
             outputs = model(inputs)
-            train_loss = compute_loss(loss_func, outputs[-1], gts)     # a device scalar: no host wait yet
+            train_loss = compute_loss(loss_func, outputs[-1], gts, loss_kwargs)     # a device scalar: no host wait yet
             model.zero_grad()
             meta_optim.set_train_loss(train_loss)
             meta_optim.step(train_loss)
@@ -237,7 +264,7 @@ def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_g
                       train_frame_id=0):
     """frames (N,3,H,W) on the GPU, object_gts: list of (1,H,W) binary masks of the train frame.
     cfg keys (names of cfgs/meta.yaml): num_epochs.eval, eval_online_adapt.{step,reset_model_mode,
-    num_epochs,min_prop}, data_cfg.batch_sizes.train, seed, loss_func, train_early_stopping_cfg.
+    num_epochs,min_prop (a threshold, or [lo, hi]: `min_prop_band`)}, data_cfg.batch_sizes.train, seed, loss_func, train_early_stopping_cfg.
     Returns (labels (N,H,W) uint8, per-object probs list, train loss history per object)."""
     probs_all, hist_all = [], []
     for gt in object_gts:

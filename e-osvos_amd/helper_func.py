@@ -11,6 +11,8 @@
 `class_balanced_cross_entropy` (`networks/loss_ce.py:15-60`) run as fused HIP kernels too, and so does the
 Lovasz hinge of `networks/loss_lovasz.py:78-111` as `lovasz_hinge` (`per_image=True`, the reference default) and
 `lovasz_hinge_flat` (`per_image=False`); unknown names raise NotImplementedError as in the reference (`:55-56`).
+`loss_kwargs={'ignore': v}` marks the pixels whose target equals `v` as void for every kind: the reference's keyword for the
+Lovasz hinge (`networks/loss_lovasz.py:78-126`), the same rule for the others (in no sum and no count, gradient 0).
 """
 import random
 
@@ -36,12 +38,13 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
         raise RuntimeError('compute_loss needs logits produced by eosvos_amd.networks.DeepLabV3Plus '
                            '(there is no CPU/eager path)')
     gts = gts.contiguous().float()
+    ign = {'ignore': loss_kwargs['ignore']} if loss_kwargs.get('ignore') is not None else {}      # void label, every kind
     if loss_kwargs.get('batch_average', True):
-        loss = eng.loss(loss_func, gts).view(())      # also leaves dL/dlogits in the engine
+        loss = eng.loss(loss_func, gts, **ign).view(())      # also leaves dL/dlogits in the engine
         loss._eosvos_engine = eng
         return loss
     # per-sample values (run_loader metrics, helper_func.py:131-137): every loss evaluated sample by sample
-    return torch.cat([eng.loss_of(loss_func, outputs[b], gts[b]) for b in range(outputs.shape[0])])
+    return torch.cat([eng.loss_of(loss_func, outputs[b], gts[b], **ign) for b in range(outputs.shape[0])])
 
 
 def init_parent_model(architecture, encoder, train_encoder, decoder_norm_layer=None,

@@ -205,6 +205,35 @@ int eosvos_bce(eosvos_engine* e, const float* logits, const float* masks, int64_
  * loss_dice.py:33-40, loss_ce.py:26-40).  No gradient is kept; a pending loss gradient is invalidated. */
 int eosvos_loss_tensors(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n,
                         float* loss_out);
+/* ---- void pixels: an ignore label for every loss ------------------------------------------------------------------------
+ * A pixel is void iff masks[p] == ignore (compared as floats); `ignore` must be finite and outside [0, 1], anything else is
+ * rejected before a launch.  A void pixel is in no sum, no count and no ranking, its logit is never read into the result (it
+ * may be NaN / inf) and its gradient is exactly +0.  With V the valid pixels of the set:
+ *   EOSVOS_LOSS_BCE                  sum_V bce / |V|                                   (helper_func.py:32-37)
+ *   EOSVOS_LOSS_DICE                 the three sums of networks/loss_dice.py:25-30 over V, smooth = 1
+ *   EOSVOS_LOSS_BCE_DICE             bce_V - log(1 - dice_V)                            (helper_func.py:45-54)
+ *   EOSVOS_LOSS_CLASS_BALANCED_BCE   num_labels_pos / _neg, loss_pos / _neg of networks/loss_ce.py:42-53 over V; the two
+ *                                    trailing divisions stay those of the tensor's full shape (OSVOS void-pixel weighting)
+ *   EOSVOS_LOSS_LOVASZ_HINGE[_FLAT]  the void pixels are removed before the ranking, per image or from the whole batch
+ *                                    (`ignore=`, flatten_binary_scores, networks/loss_lovasz.py:78-126)
+ * An empty V gives loss 0 and an all-zero gradient (an all-void image adds 0 to the per-image mean, loss_lovasz.py:101-103).
+ * Without a void pixel in `masks` the result has the bits of eosvos_loss / eosvos_loss_tensors.
+ * eosvos_loss_ignore leaves dL/dlogits for eosvos_backward_step exactly as eosvos_loss does. */
+int eosvos_loss_ignore(eosvos_engine* e, int kind, const float* masks, int batch, float ignore, float* loss_out);
+/* eosvos_loss_tensors with a void label (networks/loss_lovasz.py:78-126 and the loss files above): the n elements are one set;
+ * no gradient is kept, a pending loss gradient is invalidated. */
+int eosvos_loss_tensors_ignore(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n,
+                               float ignore, float* loss_out);
+/* The fused entry points eosvos_finetune_step / eosvos_meta_grad[_ex] evaluate their loss (eosvos_set_loss) with the void label
+ * `ignore` (networks/loss_lovasz.py:78-126) while `on` != 0.  Per engine, off by default; an engine that shares another's state
+ * (eosvos_alias_state) does not take its setting over. */
+int eosvos_set_loss_ignore(eosvos_engine* e, int on, float ignore);
+/* Pseudo-label targets of online adaptation with an uncertainty band (the thresholding of evaluate.py:231-240, whose void
+ * label the losses above skip, networks/loss_lovasz.py:78-126): for n_frames probability maps of n_pix pixels,
+ * targets_out = 1 where p >= hi, 0 where p < lo, `ignore` between (0 <= lo < hi <= 1, n_frames <= 1024).  n_pos_host (may be
+ * NULL: nothing waits) receives the number of 1s of each frame after one synchronisation. */
+int eosvos_propagation_targets(eosvos_engine* e, const float* probs, int n_frames, int64_t n_pix, float lo, float hi,
+                               float ignore, float* targets_out, int64_t* n_pos_host);
 /* autograd.grad + theta <- theta - lr (.) grad (meta_optim.py:177-214,
  * meta_model.py:78-80), using the gradient left by eosvos_loss_bce.
  * accumulate != 0 additionally adds the step's gradients into the task's sum_k g_k
