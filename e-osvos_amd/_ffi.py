@@ -72,6 +72,10 @@ _SIGNATURES = {
     'eosvos_keep_grads': (ctypes.c_int, [_E, ctypes.c_int]),
     'eosvos_get_grads': (ctypes.c_int, [_E, c_float_p]),
     'eosvos_infer': (ctypes.c_int, [_E, c_float_p, ctypes.c_int, c_float_p]),
+    'eosvos_infer_view': (ctypes.c_int, [_E, c_float_p, ctypes.c_int, ctypes.c_int]),
+    'eosvos_tta_accumulate': (ctypes.c_int, [_E, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                             c_float_p, ctypes.c_int, ctypes.c_int]),
+    'eosvos_resize_frames': (ctypes.c_int, [_E, c_float_p] + [ctypes.c_int] * 6 + [c_float_p]),
     'eosvos_merge_labels': (ctypes.c_int, [_E, c_float_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]),
     'eosvos_meta_task_begin': (ctypes.c_int, [_E]),
     'eosvos_meta_grad': (ctypes.c_int, [_E, c_float_p, c_float_p, ctypes.c_int, c_float_p,

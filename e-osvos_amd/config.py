@@ -96,6 +96,16 @@ NAMED = {
 }
 
 
+# Options beyond the reference's cfgs/meta.yaml.  They are NOT part of BASE (the reference's key set): `parse_cli` adds a group
+# only when the command line sets one of its keys (`eval_tta.flip=True eval_tta.scales=[0.75,1.0,1.25]`), consumers read them
+# with `cfg.get(...)`.
+#   eval_tta   test-time augmentation of the evaluation's inference passes (`tta.py`): mirrored and rescaled views averaged in
+#              probability space with equal weights; the value below is the neutral one (one plain view = off)
+EXTENSIONS = {
+    'eval_tta': {'flip': False, 'scales': [1.0]},
+}
+
+
 def _merge(dst, src):
     for k, v in src.items():
         if isinstance(v, dict) and isinstance(dst.get(k), dict):
@@ -141,7 +151,13 @@ def parse_cli(argv):
         else:
             raise KeyError(f'unknown named config: {a}')
     for k, v in updates:
+        group = k.split('.')[0]
+        if group in EXTENSIONS and group not in cfg:
+            cfg[group] = copy.deepcopy(EXTENSIONS[group])
         _set_dotted(cfg, k, v)
+    if 'eval_tta' in cfg:
+        from .tta import check
+        check(cfg['eval_tta'])                              # ValueError: empty list, scale <= 0, ...
     unsupported(cfg)
     return cfg
 

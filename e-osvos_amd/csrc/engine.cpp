@@ -259,6 +259,7 @@ struct eosvos_engine {
   std::vector<int> upd_blocks;
   int64_t ws_conv_n = 0, ws_wg_n = 0;
   ResizeTab up_h, up_w, fin_h, fin_w;  // decoder upsample (align_corners) and final resize
+  std::map<std::pair<int, int>, ResizeTab> frame_tabs;      // eosvos_resize_frames: (in, out) -> align_corners=False table
   int lastB = 0;
   bool have_loss_grad = false;
   int force_algo = 0;                 // EOSVOS_ALGO_*: 0 = plan by work size; the op-level parity tests force one path
@@ -2028,7 +2029,7 @@ int eosvos_restore_params(eosvos_engine* e) {
 }
 
 // ---- forward ------------------------------------------------------------------------------------
-static int forward_impl(eosvos_engine* e, const float* images, int B) {
+static int forward_impl(eosvos_engine* e, const float* images, int B, bool mirror = false) {
   const Topo& t = e->t;
   hipStream_t s = e->s;
   if (B != e->lastB) pair_reset(e);          // another batch size: a new trajectory for the pre-split producers' scales
@@ -2048,7 +2049,7 @@ static int forward_impl(eosvos_engine* e, const float* images, int B) {
   }
   // f16x3 mode: the stem runs on the fp16 matrix cores too (the frame's absmax comes from the layout pass)
   unsigned* ax = h3_mode() ? amax_fused_slot(e, AM_X, 0, e->xpad, s) : nullptr;
-  launch_nchw_to_nhwc_pad(images, e->xpad, B, 3, e->H, e->W, 3, s, ax);
+  launch_nchw_to_nhwc_pad(images, e->xpad, B, 3, e->H, e->W, 3, s, ax, mirror ? 1 : 0);
   auto stem_fwd = [&](const float* a, const float* b, float* y) {
     if (ax) launch_stem_fwd_h3(e->xpad, e->W_(0), a, b, y, B, e->H, e->W, e->h2, e->w2, ax, s);
     else launch_stem_fwd(e->xpad, e->W_(0), a, b, y, B, e->H, e->W, e->h2, e->w2, s);
@@ -2549,6 +2550,49 @@ int eosvos_infer(eosvos_engine* e, const float* images, int batch, float* probs_
   e->fwd_masks = true;
   if (rc) return 1;
   launch_sigmoid(e->logits, probs_out, (int64_t)batch * e->H * e->W, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+// ---- test-time augmentation: mirrored / rescaled views averaged in probability space ------------
+int eosvos_infer_view(eosvos_engine* e, const float* images, int batch, int mirror) {
+  ModeScope mode_scope(e);
+  if (!e || !images) return fail("null argument");
+  if (batch < 1 || batch > e->maxB) return fail("batch out of range");
+  e->fwd_masks = false;                 // inference, as eosvos_infer
+  const int rc = forward_impl(e, images, batch, mirror != 0);
+  e->fwd_masks = true;
+  return rc ? 1 : 0;
+}
+int eosvos_tta_accumulate(eosvos_engine* e_view, int h, int w, int batch, int mirror, float weight, int first, float* acc,
+                          int H, int W) {
+  if (!e_view || !acc) return fail("null argument");
+  if (batch < 1 || batch > e_view->maxB) return fail("batch out of range");
+  if (h < 1 || w < 1 || H < 1 || W < 1) return fail("eosvos_tta_accumulate: sizes must be >= 1");
+  if (h != e_view->H || w != e_view->W) return fail("eosvos_tta_accumulate: h x w is not the frame size of the view's engine");
+  if (!(weight == weight) || weight - weight != 0.f) return fail("eosvos_tta_accumulate: the weight must be finite");
+  launch_tta_accumulate(e_view->logits, acc, batch, h, w, H, W, mirror != 0, weight, first != 0, e_view->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+int eosvos_resize_frames(eosvos_engine* e, const float* src, int B, int C, int h_in, int w_in, int h_out, int w_out, float* dst) {
+  if (!e || !src || !dst) return fail("null argument");
+  if (B < 1 || C < 1) return fail("batch out of range");
+  if (h_in < 1 || w_in < 1 || h_out < 1 || w_out < 1) return fail("eosvos_resize_frames: sizes must be >= 1");
+  if ((int64_t)B * C > 0x7fffffff) return fail("eosvos_resize_frames: too many planes");
+  // the tables of a (in, out) pair stay with the engine: the frames of a sequence all take the same ones
+  auto tab = [&](int in, int out) -> const ResizeTab* {
+    auto it = e->frame_tabs.find({in, out});
+    if (it == e->frame_tabs.end()) {
+      ResizeTab t;
+      if (upload_resize(e, make_resize(in, out, false), in, out, t)) return nullptr;
+      it = e->frame_tabs.emplace(std::make_pair(in, out), t).first;
+    }
+    return &it->second;
+  };
+  const ResizeTab* th = tab(h_in, h_out);
+  const ResizeTab* tw = th ? tab(w_in, w_out) : nullptr;
+  if (!th || !tw) return 1;
+  launch_resize_fwd(src, 1, dst, 1, B * C, 1, *th, *tw, e->s);      // NCHW planes = B * C one-channel images
   HIPOK(hipGetLastError());
   return 0;
 }

@@ -292,7 +292,8 @@ void launch_wino_dgrad_output(int tm, const float* dV, long prow, int C, int B, 
 // misc_kernels.hip
 // ---------------------------------------------------------------------------------
 void launch_nchw_to_nhwc_pad(const float* src, float* dst, int B, int C, int H, int W, int pad,
-                             hipStream_t s, unsigned* amax = nullptr);      // amax: absmax slot of the frame (f16x3 mode)
+                             hipStream_t s, unsigned* amax = nullptr, int mirror = 0);      // amax: absmax slot of the frame (f16x3 mode)
+                                                                                               // mirror: source column x -> padded column W-1-x
 void launch_fill(float* p, int64_t n, float v, hipStream_t s);
 // OIHW <-> engine layout O,(kh,kw),I for one tensor
 void launch_oihw_to_ohwi(const float* src, float* dst, int O, int I, int T, hipStream_t s);
@@ -383,6 +384,9 @@ void launch_lovasz_ignore(const float* logits, const float* gt, float* dlogits, 
 void launch_propagation_targets(const float* probs, float* targets, int* n_pos, int n_frames, int64_t n_pix, float lo, float hi,
                                 float ignore, hipStream_t s);
 void launch_sigmoid(const float* x, float* y, int64_t n, hipStream_t s);
+// test-time augmentation: acc (B, H, W) = (first ? 0 : acc) + weight * sigmoid(bilinear_{align_corners=False}(unmirror(logits (B, h, w))))
+void launch_tta_accumulate(const float* logits, float* acc, int B, int h, int w, int H, int W, int mirror, float weight,
+                           int first, hipStream_t s);
 void launch_merge_labels(const float* probs, int n_obj, int64_t n_pix, uint8_t* labels, hipStream_t s);
 // cv2.warpAffine (+ optional horizontal flip of the source) of C planes; tables = adelta[W] bdelta[W] X0[H] Y0[H]
 void launch_warp_affine(const float* src, float* dst, int C, int H, int W, const double* inv_matrix, int round_delta,

@@ -36,7 +36,8 @@ static inline int grid_for(long n, int per_block, int cap = 4096) {
 
 // ---- layout ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void nchw_to_nhwc_pad_kernel(const float* __restrict__ src, float* __restrict__ dst, int B,
-                                                               int C, int H, int W, int pad, unsigned* __restrict__ amax) {
+                                                               int C, int H, int W, int pad, unsigned* __restrict__ amax,
+                                                               int mirror) {
   const long n = (long)B * H * W;
   const int Wp = W + 2 * pad, Hp = H + 2 * pad;
   unsigned am = 0;
@@ -44,7 +45,8 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_pad_kernel(const float* __re
     const int x = (int)(i % W);
     const int y = (int)((i / W) % H);
     const int b = (int)(i / ((long)W * H));
-    float* d = dst + (((long)b * Hp + y + pad) * Wp + x + pad) * C;
+    const int xd = mirror ? W - 1 - x : x;            // mirrored view (test-time augmentation): the frame is flipped on its way in
+    float* d = dst + (((long)b * Hp + y + pad) * Wp + xd + pad) * C;
     for (int c = 0; c < C; ++c) {
       const float v = src[(((long)b * C + c) * H + y) * W + x];
       d[c] = v;
@@ -55,10 +57,10 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_pad_kernel(const float* __re
   if (amax) amax_block_commit(am, amax);            // f16x3 mode: absmax of the frame for the stem on the matrix cores
 }
 void launch_nchw_to_nhwc_pad(const float* src, float* dst, int B, int C, int H, int W, int pad,
-                             hipStream_t s, unsigned* amax) {
+                             hipStream_t s, unsigned* amax, int mirror) {
   const long n = (long)B * H * W;
   hipLaunchKernelGGL(nchw_to_nhwc_pad_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, src, dst, B, C, H,
-                     W, pad, amax);
+                     W, pad, amax, mirror);
 }
 
 __global__ void fill_kernel(float* p, long n, float v) { GRID_STRIDE(i, n) p[i] = v; }
@@ -774,6 +776,52 @@ __global__ void sigmoid_kernel(const float* __restrict__ x, float* __restrict__ 
 }
 void launch_sigmoid(const float* x, float* y, int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(sigmoid_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, x, y, (long)n);
+}
+// Test-time augmentation, one view into the frame's accumulator: acc (B, H, W) (+)= weight * sigmoid(resize(unmirror(logits)))
+// with logits (B, h, w).  The resize is torch's bilinear align_corners=False rule (source coordinate
+// max(0, (in / out) * (o + 0.5) - 0.5), upper neighbour clamped at the edge; the arithmetic of resize_fwd_kernel) with the
+// coordinates computed in place: a view is resampled once, so a table would cost more than it saves.  h == H and w == W
+// reads the logit itself.  One thread per output pixel, one writer per pixel: no LDS, no atomics, order-free.
+__device__ __forceinline__ void tta_src(int o, float scale, int in, int& i0, int& i1, float& lam) {
+  float src = scale * ((float)o + 0.5f) - 0.5f;
+  if (src < 0.f) src = 0.f;
+  i0 = (int)src;
+  if (i0 > in - 1) i0 = in - 1;
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  lam = src - (float)i0;
+}
+__global__ __launch_bounds__(256) void tta_accumulate_kernel(const float* __restrict__ logits, float* __restrict__ acc, int B,
+                                                             int h, int w, int H, int W, float sy, float sx, int mirror,
+                                                             float weight, int first) {
+  const long n = (long)B * H * W;
+  const bool same = h == H && w == W;
+  GRID_STRIDE(i, n) {
+    const int ox = (int)(i % W), oy = (int)((i / W) % H);
+    const float* src = logits + (i / ((long)W * H)) * ((long)h * w);
+    float xv;
+    if (same) {
+      xv = src[(long)oy * w + (mirror ? w - 1 - ox : ox)];
+    } else {
+      int y0, y1, x0, x1;
+      float ly, lx;
+      tta_src(oy, sy, h, y0, y1, ly);
+      tta_src(ox, sx, w, x0, x1, lx);
+      if (mirror) { x0 = w - 1 - x0; x1 = w - 1 - x1; }      // column x of the un-mirrored view is column w - 1 - x of the logits
+      const float hy = 1.f - ly, hx = 1.f - lx;
+      const float v00 = src[(long)y0 * w + x0], v01 = src[(long)y0 * w + x1];
+      const float v10 = src[(long)y1 * w + x0], v11 = src[(long)y1 * w + x1];
+      xv = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+    }
+    const float e = expf(-fabsf(xv));
+    const float p = weight * (xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e));
+    acc[i] = first ? p : acc[i] + p;
+  }
+}
+void launch_tta_accumulate(const float* logits, float* acc, int B, int h, int w, int H, int W, int mirror, float weight,
+                           int first, hipStream_t s) {
+  const long n = (long)B * H * W;
+  hipLaunchKernelGGL(tta_accumulate_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, logits, acc, B, h, w, H, W,
+                     (float)h / (float)H, (float)w / (float)W, mirror, weight, first);
 }
 __global__ void merge_labels_kernel(const float* __restrict__ probs, int n_obj, long n_pix,
                                     uint8_t* __restrict__ labels) {

@@ -525,6 +525,33 @@ class Engine:
         _ffi.check(self.lib.eosvos_infer(self.h, _ptr(images), b, _ptr(out)))
         return out
 
+    # ---- test-time augmentation (mirrored / rescaled views, see tta.py) ------------------------
+    def infer_view(self, images, mirror=False):
+        """`eosvos_infer_view`: the inference forward of `infer` on the frames as they are or mirrored left-right (the layout
+        pass flips them on the way in); the logits stay in the engine for `tta_accumulate`."""
+        b = self._check_images(images)
+        self._guard(images)
+        _ffi.check(self.lib.eosvos_infer_view(self.h, _ptr(images), b, int(bool(mirror))))
+        return b
+
+    def tta_accumulate(self, acc, weight, mirror=False, first=False):
+        """`eosvos_tta_accumulate`: acc (B, 1, H, W) (+)= weight * sigmoid(bilinear_{align_corners=False}(un-mirrored logits of
+        this engine's last forward)), one launch; `first` stores instead of adding.  Returns acc."""
+        self._check_stream()
+        assert acc.is_cuda and acc.dtype == torch.float32 and acc.is_contiguous() and acc.dim() == 4 and acc.shape[1] == 1, acc.shape
+        _ffi.check(self.lib.eosvos_tta_accumulate(self.h, self.height, self.width, acc.shape[0], int(bool(mirror)), float(weight),
+                                                  int(bool(first)), _ptr(acc), acc.shape[2], acc.shape[3]))
+        return acc
+
+    def resize_frames(self, frames, height, width):
+        """`eosvos_resize_frames`: (B, C, h, w) device fp32 -> (B, C, height, width), bilinear with align_corners=False."""
+        self._check_stream()
+        assert frames.is_cuda and frames.dtype == torch.float32 and frames.is_contiguous() and frames.dim() == 4, frames.shape
+        b, c, h, w = frames.shape
+        out = torch.empty(b, c, int(height), int(width), device=self.device)
+        _ffi.check(self.lib.eosvos_resize_frames(self.h, _ptr(frames), b, c, h, w, int(height), int(width), _ptr(out)))
+        return out
+
     def merge_labels(self, probs):
         """probs: (n_obj, H, W) device fp32 -> (H, W) uint8.  `evaluate.py:322-326`."""
         probs = probs.contiguous()

@@ -20,6 +20,7 @@ import time
 import numpy as np
 import torch
 
+from . import tta as tta_views
 from .helper_func import compute_loss, early_stopping, set_random_seeds
 
 
@@ -80,11 +81,17 @@ def min_prop_band(min_prop):
     return float(min_prop[0]), float(min_prop[1])
 
 
-def finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0):
+def finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None):
     """One (sequence, object) work item of `evaluate.py:132-317`: fine-tune on the train frame, predict the following
     frames, with online adaptation re-fine-tune every `step` frames.  Returns (probs (N,H,W) with the train frame seeded
-    as 2*GT (`:167-168`), train-loss history per round)."""
-    return _drain(finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id))
+    as 2*GT (`:167-168`), train-loss history per round).  `tta`: test-time augmentation of every inference call (`tta.py`)."""
+    return _drain(finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id,
+                                        **_tta_kw(tta)))
+
+
+def _tta_kw(tta):
+    """`tta` travels as a keyword, and only when it is set: without it every call below is the one made before it existed."""
+    return {} if tta is None else {'tta': tta}
 
 
 def _drain(gen):
@@ -95,7 +102,7 @@ def _drain(gen):
         return stop.value
 
 
-def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0):
+def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None):
     """`finetune_object` as a generator: it yields each time a fine-tune iteration (or a few inference frames) has been
     ENQUEUED on the model's engine and before the host waits for its loss, so that a caller holding several objects
     (one model / engine / stream each, `run_objects_in_flight`) can queue the others' work in between.  Everything
@@ -104,6 +111,9 @@ def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, 
     if augment is None and cfg['data_cfg'].get('random_train_transform'):
         augment = device_augment(model)
     augment = augment or _repeat_batch
+    # test-time augmentation: the frames' probabilities (the propagated targets of the adaptation rounds included: they are the
+    # frames' prediction) are the mean over the views; off = the plain inference call below
+    view_set = tta_views.ViewSet(model, frames.shape[2], frames.shape[3], tta) if tta_views.active(tta) else None
     n = frames.shape[0]
     ona = cfg['eval_online_adapt']
     band = min_prop_band(ona['min_prop'])
@@ -174,9 +184,14 @@ def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, 
         # the reference predicts frame by frame (`test` batch size 1, evaluate.py:293-314); frozen normalisation makes
         # the frames of a batch independent, and at 480x854 a batch of 3 costs 1.40 ms per frame, one of 8 1.16, one 2.30
         nb = max(1, min(int(getattr(model.engine, 'max_batch', 1)), INFER_BATCH))
+        if view_set is not None and rd['eval_min'] < rd['eval_max']:
+            view_set.sync()                     # the view engines of other sizes take this round's weights
         for f in range(rd['eval_min'], rd['eval_max'], nb):
             g = min(f + nb, rd['eval_max'])
-            masks[f:g] = model.engine.infer(frames[f:g].contiguous())
+            if view_set is not None:
+                masks[f:g] = view_set.infer(frames[f:g].contiguous())
+            else:
+                masks[f:g] = model.engine.infer(frames[f:g].contiguous())
             yield
     return masks[:, 0], hist
 
@@ -219,7 +234,7 @@ def object_workers(model, meta_optim, meta_optim_cfg, n, wg_budget=256):
     return ws
 
 
-def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augment=None, train_frame_id=0):
+def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augment=None, train_frame_id=0, tta=None):
     """[(probs, hist)] for the objects `gts` of one sequence, up to len(workers) of them in flight together; results are
     those of `finetune_object` one after the other (same engine arithmetic at the same workgroup budget).
     `train_frame_id`: one frame for all objects, or one per object (YouTube-VOS objects that appear later)."""
@@ -239,7 +254,7 @@ def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augm
             if wi not in active and pending:
                 oi = pending.pop(0)
                 active[wi] = (oi, finetune_object_steps(w.model, w.meta_optim, meta_optim_state_dict, frames, gts[oi], cfg,
-                                                        augment, tfid[oi]))
+                                                        augment, tfid[oi], **_tta_kw(tta)))
         for wi in sorted(active):
             oi, gen = active[wi]
             w = workers[wi]
@@ -261,14 +276,16 @@ def merge_objects(engine, probs_all):
 
 
 def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_gts, cfg, augment=None,
-                      train_frame_id=0):
+                      train_frame_id=0, tta=None):
     """frames (N,3,H,W) on the GPU, object_gts: list of (1,H,W) binary masks of the train frame.
     cfg keys (names of cfgs/meta.yaml): num_epochs.eval, eval_online_adapt.{step,reset_model_mode,
     num_epochs,min_prop (a threshold, or [lo, hi]: `min_prop_band`)}, data_cfg.batch_sizes.train, seed, loss_func, train_early_stopping_cfg.
+    `tta` ({'flip': bool, 'scales': [floats]}, `tta.py`): every inference call averages the mirrored / rescaled views.
     Returns (labels (N,H,W) uint8, per-object probs list, train loss history per object)."""
     probs_all, hist_all = [], []
     for gt in object_gts:
-        probs, hist = finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id)
+        probs, hist = finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id,
+                                      **_tta_kw(tta))
         probs_all.append(probs)
         hist_all.append(hist)
     return merge_objects(model.engine, probs_all), probs_all, hist_all
@@ -288,7 +305,7 @@ def save_label_png(path, labels_hw):
 
 def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dataset_key, save_dir=None,
                      meta_iter=None, meta_epoch=None, best_mean_J=0.0, dist=None, device=None, vis_win_names=None,
-                     log=None, objects_in_flight=None):
+                     log=None, objects_in_flight=None, tta=None):
     """The evaluation worker of `src/util/evaluate.py:111-382` for the DeepLab path: every sequence of `dataset`
     (an `eosvos_amd.data` reader), every object, fine-tune / online adaptation / inference / merge; prediction PNGs
     under `{save_dir}/best_eval_preds/{name}/{split}/{seq}/{frame}.png`, J per sequence, and the
@@ -305,6 +322,8 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
     grouped): budget and grouping change the split-K partition, i.e. the order of fp32 partial sums, so the last
     bits of a result (not its parity margins, `profiles/*parity_margins*`) depend on how many objects of the sequence
     landed on this rank.  EOSVOS_OBJECTS_IN_FLIGHT=1 gives one schedule-independent order.
+    `tta` ({'flip': bool, 'scales': [floats]}, `tta.py`): test-time augmentation of every inference call; the view engines
+    it builds are released with the parked ones at the end.
     Returns dict(J_seq, mean_J, best_mean_J, time_per_frame, labels={seq: (N,H,W) uint8}) and the DAVIS J / F statistics
     of `eval_davis_seq` (`evaluate.py:345-359`), one entry per object in sequence order: J_obj (the per-object J means the
     reference calls J_seq), J_recall_seq, J_decay_seq, F_seq, F_recall_seq, F_decay_seq, with mean_F and
@@ -416,7 +435,7 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
             item += 1
         if workers is not None and len(mine) > 1:
             res = run_objects_in_flight(workers, meta_optim_state_dict, frames, [gts[o] for o in mine], cfg,
-                                        train_frame_id=[fids[o] for o in mine])
+                                        train_frame_id=[fids[o] for o in mine], **_tta_kw(tta))
             for o, (p, _) in zip(mine, res):
                 probs[o] = p
         else:
@@ -424,7 +443,7 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
                 model.set_wg_budget(0)                                          # alone on the GPU
             for o in mine:
                 probs[o], _ = finetune_object(model, meta_optim, meta_optim_state_dict, frames, gts[o], cfg,
-                                              train_frame_id=fids[o])
+                                              train_frame_id=fids[o], **_tta_kw(tta))
         if world > 1:
             dist.all_reduce(probs)
         eval_time += time.perf_counter() - t0

@@ -19,6 +19,7 @@ import random
 import numpy as np
 import torch
 
+from . import tta as tta_views
 from .networks import DeepLabV3, DeepLabV3Plus
 
 
@@ -68,19 +69,29 @@ def init_parent_model(architecture, encoder, train_encoder, decoder_norm_layer=N
     return model, parent_states
 
 
-def run_frames(model, frames, gts=None, loss_func='cross_entropy'):
+def run_frames(model, frames, gts=None, loss_func='cross_entropy', tta=None):
     """Inference over frames (N,3,H,W) one at a time (batch 1, `test` batch size of the configs):
     returns (`loss_func` per frame or None, acc per frame or None, probs (N,1,H,W)) -- `run_loader`,
-    helper_func.py:131-142, evaluates the configured loss with `batch_average: False`."""
+    helper_func.py:131-142, evaluates the configured loss with `batch_average: False`.
+    `tta` ({'flip': bool, 'scales': [floats]}, `tta.py`): probs are the mean over the mirrored / rescaled views, and the
+    loss is that of the averaged prediction (of its logit, log(p / (1 - p))); None or the neutral dictionary: one plain view."""
     model.eval()
     probs, losses, accs = [], [], []
+    use_tta = tta_views.active(tta)
+    view_set = None
     for i in range(frames.shape[0]):
         x = frames[i:i + 1].contiguous()
         eng = model._ensure_engine(x.shape[2], x.shape[3], 1)
-        p = eng.infer(x)
+        if use_tta:
+            if view_set is None or (view_set.height, view_set.width) != tuple(x.shape[2:]):
+                view_set = tta_views.ViewSet(model, x.shape[2], x.shape[3], tta)
+                view_set.sync()                               # the weights do not change while this function runs
+            p = view_set.infer(x)
+        else:
+            p = eng.infer(x)
         probs.append(p)
         if gts is not None:
-            logits = eng.debug_tensor('logits')[:1]
+            logits = torch.logit(p, eps=1e-7) if use_tta else eng.debug_tensor('logits')[:1]
             losses.append(eng.loss_of(loss_func, logits, gts[i:i + 1].contiguous()))
             pred = p.ge(0.5)
             accs.append(pred.eq(gts[i:i + 1].bool()).float().mean().view(1))

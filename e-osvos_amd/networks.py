@@ -257,11 +257,48 @@ class DeepLabV3Plus:
         while len(cache) > self.ENGINE_CACHE:
             cache.pop(next(iter(cache))).close()
 
+    def _build_view_engine(self, height, width, batch):
+        kw = {} if getattr(self, 'side_stream', True) else {'side_stream': False}
+        return Engine(self.encoder, height, width, batch, str(self.device), norm=self.norm, **kw)
+
+    def _view_engine(self, height, width, batch):
+        """The engine that scores the height x width views of test-time augmentation (`tta.ViewSet`).  It lives BESIDE the live
+        engine (`_ensure_engine` would replace that one, and refuses to while a first-step snapshot is held, which online
+        adaptation always has): built on first use with this model's norm statistics, kept per size, and released by
+        `close_parked_engines`.  Its weights are the caller's business (`ViewSet.sync`: the live engine's current ones)."""
+        views = self.__dict__.setdefault('_view_engines', {})
+        v = views.get((height, width))
+        if v is not None and (v.max_batch < batch or getattr(v, 'h', True) is None):
+            v.close()
+            v = None
+        if v is None:
+            v = views[(height, width)] = self._build_view_engine(height, width, batch)
+            v._norm_pushes = None
+            if self._train_from and hasattr(v, 'set_trainable_from'):
+                v.set_trainable_from(self._train_from)
+            if getattr(self, 'wg_budget', 0) and hasattr(v, 'set_wg_budget'):
+                v.set_wg_budget(self.wg_budget)
+        pushes = self.__dict__.get('_push_count', 0)
+        if v._norm_pushes != pushes:          # norm statistics as of the last push_state (the weights come from ViewSet.sync)
+            nl = norm_layers(self.encoder)
+            cat = lambda suf: torch.cat([self._norm[p + suf].reshape(-1).float() for p, _ in nl])
+            if self.norm == 'gn':
+                g = cat('.weight')
+                v.set_norm(g, cat('.bias'), torch.zeros_like(g), torch.ones_like(g))
+            else:
+                v.set_norm(cat('.weight'), cat('.bias'), cat('.running_mean'), cat('.running_var'))
+            v._norm_pushes = pushes
+        return v
+
     def close_parked_engines(self):
-        """Release the engines parked for other frame sizes (keeps the live one)."""
+        """Release the engines parked for other frame sizes and the view engines of test-time augmentation (keeps the live
+        one)."""
         for e in self.__dict__.get('_engine_cache', {}).values():
             e.close()
         self.__dict__['_engine_cache'] = {}
+        for e in self.__dict__.get('_view_engines', {}).values():
+            e.close()
+        self.__dict__['_view_engines'] = {}
 
     def close_engines(self):
         self.close_parked_engines()
@@ -288,6 +325,7 @@ class DeepLabV3Plus:
                 lr = torch.cat([torch.zeros(e.lr_store_count(level) - lr.numel(), dtype=lr.dtype, device=lr.device), lr])
             e.set_lr_state(level, use_log, lr)
         self._dirty = False
+        self.__dict__['_push_count'] = self.__dict__.get('_push_count', 0) + 1
 
     def __call__(self, inputs):
         if self.training and not self._dropout_off:

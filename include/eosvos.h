@@ -255,6 +255,31 @@ int eosvos_infer(eosvos_engine* e, const float* images, int batch, float* probs_
 int eosvos_merge_labels(eosvos_engine* e, const float* probs, int n_obj, int64_t n_pix,
                         uint8_t* labels_out);
 
+/* ---- test-time augmentation: mirrored and rescaled views averaged in probability space ---------
+ * (the test-time ensemble of the OSVOS / OnAVOS family; the reference scores one view, helper_func.py:131-142.)
+ * One frame's prediction = sum over views of weight_v * sigmoid(resize_to_frame(unmirror(logits_v))), weights summing
+ * to 1, so the accumulator IS the probability map (no finishing pass; eosvos_merge_labels reads it as it is).
+ * Per view: eosvos_resize_frames (views of another size) -> eosvos_infer_view on the engine of that size ->
+ * eosvos_tta_accumulate. */
+/* Forward only, in the inference mode of eosvos_infer (no ReLU masks kept: no backward step may follow); the logits
+ * stay in the engine.  mirror != 0 feeds the frame mirrored left-right: the layout pass writes source column x to
+ * column W-1-x, the padded input is byte for byte that of the flipped frame and no flipped copy is made.  The launch
+ * plan (eosvos_plan_fingerprint) is that of eosvos_infer. */
+int eosvos_infer_view(eosvos_engine* e, const float* images, int batch, int mirror);
+/* acc (batch x H x W) = (first ? 0 : acc) + weight * sigmoid(R(U(logits))) in one launch, where logits (batch x h x w)
+ * are those of e_view's last forward (h, w must be e_view's frame size), U un-mirrors them when mirror != 0 and R is
+ * torch.nn.functional.interpolate(mode='bilinear', align_corners=False) to H x W: source coordinate
+ * max(0, (in / out) * (o + 0.5) - 0.5) in fp32, upper neighbour clamped at the edge.  h == H and w == W takes the
+ * logit itself (weight 1, first 1 then gives eosvos_infer's bits).  One writer per pixel: deterministic.  Runs on
+ * e_view's stream; acc is the caller's. */
+int eosvos_tta_accumulate(eosvos_engine* e_view, int h, int w, int batch, int mirror, float weight, int first, float* acc,
+                          int H, int W);
+/* dst (B x C x h_out x w_out) = bilinear align_corners=False resize of src (B x C x h_in x w_in), the rule above (the
+ * engine's resize kernel on B * C one-channel planes); any sizes >= 1, not tied to e's frame size.  The index tables
+ * of a size pair are built on first use and stay with e. */
+int eosvos_resize_frames(eosvos_engine* e, const float* src, int B, int C, int h_in, int w_in, int h_out, int w_out,
+                         float* dst);
+
 /* ---- data augmentation (data/custom_transforms.py:9-92,189-213; helper_func.py:255-261) --- */
 /* One RandomHorizontalFlip + RandomScaleNRotate application on the device: dst = cv2.warpAffine(
  * cv2.flip(src) if flip else src, cv2.getRotationMatrix2D((W/2, H/2), rot_deg, scale), (W, H),
