@@ -56,6 +56,8 @@ _SIGNATURES = {
                                              ctypes.c_double, ctypes.c_int, c_float_p, ctypes.POINTER(ctypes.c_int)]),
     'eosvos_davis_counts': (ctypes.c_int, [_E, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    'eosvos_crf_labels': (ctypes.c_int, [_E, c_float_p, c_float_p] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 +
+                          [ctypes.c_void_p, c_float_p]),
     'eosvos_set_norm': (ctypes.c_int, [_E, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_float]),
     'eosvos_reset': (ctypes.c_int, [_E]),
     'eosvos_get_params': (ctypes.c_int, [_E, c_float_p]),

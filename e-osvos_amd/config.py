@@ -106,6 +106,16 @@ EXTENSIONS = {
 }
 
 
+# Post-processing of the evaluation's label maps, handled like EXTENSIONS (not part of BASE, added by `parse_cli` only when the
+# command line sets one of its keys: `eval_crf.iterations=5 eval_crf.w_appearance=10`, read with `cfg.get(...)`).
+#   eval_crf   local dense-CRF refinement of the final merge (`crf.py`); the value below is the neutral one (0 iterations = the plain
+#              merge), the other keys hold `crf.DEFAULTS` -- customary values, not tuned on data
+POSTPROCESS = {
+    'eval_crf': {'iterations': 0, 'radius': 5, 'dilation': 2, 'w_appearance': 10.0, 'w_smooth': 3.0,
+                 'theta_alpha': 8.0, 'theta_beta': 0.05, 'theta_gamma': 3.0},
+}
+
+
 def _merge(dst, src):
     for k, v in src.items():
         if isinstance(v, dict) and isinstance(dst.get(k), dict):
@@ -152,12 +162,16 @@ def parse_cli(argv):
             raise KeyError(f'unknown named config: {a}')
     for k, v in updates:
         group = k.split('.')[0]
-        if group in EXTENSIONS and group not in cfg:
-            cfg[group] = copy.deepcopy(EXTENSIONS[group])
+        for groups in (EXTENSIONS, POSTPROCESS):
+            if group in groups and group not in cfg:
+                cfg[group] = copy.deepcopy(groups[group])
         _set_dotted(cfg, k, v)
     if 'eval_tta' in cfg:
         from .tta import check
         check(cfg['eval_tta'])                              # ValueError: empty list, scale <= 0, ...
+    if 'eval_crf' in cfg:
+        from .crf import check as check_crf
+        check_crf(cfg['eval_crf'])                          # ValueError: radius 0, a negative weight, ...
     unsupported(cfg)
     return cfg
 

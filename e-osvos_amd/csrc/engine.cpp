@@ -206,6 +206,8 @@ struct eosvos_engine {
   float* aug_ctab = nullptr;            // bicubic coefficients at 1/32 pixel: [32][4]
   void* davis_buf = nullptr;            // eosvos_davis_counts: counts + bit-packed boundary maps (grow-only, freed by destroy)
   size_t davis_cap = 0;
+  void* crf_buf = nullptr;              // eosvos_crf_labels: unary + the two Q planes of the mean field (grow-only, freed by destroy)
+  size_t crf_cap = 0;
   int lr_level = EOSVOS_LR_NEURON, lr_log = 0;
   float *lr_elem = nullptr, *glr_tmp = nullptr, *ptmp = nullptr;
   int *row_tensor = nullptr, *tensor_row0 = nullptr, *all_row0 = nullptr;
@@ -1803,6 +1805,7 @@ int eosvos_destroy(eosvos_engine* e) {
   if (e->ev_wino_w) (void)hipEventDestroy(e->ev_wino_w);
   for (void* p : e->allocs) (void)hipFree(p);
   if (e->davis_buf) (void)hipFree(e->davis_buf);
+  if (e->crf_buf) (void)hipFree(e->crf_buf);
   delete e;
   return 0;
 }
@@ -2695,6 +2698,65 @@ int eosvos_davis_counts(eosvos_engine* e, const uint8_t* pred, const uint8_t* gt
   }
   HIPOK(hipMemcpyAsync(counts_out, counts, count_bytes, hipMemcpyDeviceToHost, e->s));
   HIPOK(hipStreamSynchronize(e->s));
+  return 0;
+}
+
+// ---- local dense-CRF refinement of the merged label maps (beside evaluate.py:322-326) -------------------------------
+int eosvos_crf_labels(eosvos_engine* e, const float* images, const float* probs, int n_frames, int n_obj, int height, int width,
+                      int iterations, int radius, int dilation, float w_appearance, float w_smooth, float theta_alpha,
+                      float theta_beta, float theta_gamma, uint8_t* labels_out, float* q_out) {
+  if (!e || !images || !probs || !labels_out) return fail("crf_labels: null argument");
+  if (n_frames < 0 || height < 1 || width < 1) return fail("crf_labels: bad frame geometry");
+  if (n_obj < 1 || n_obj > 255) return fail("crf_labels: n_obj must be in [1, 255]");
+  if (iterations < 0 || iterations > 20) return fail("crf_labels: iterations must be in [0, 20]");
+  if (radius < 1 || radius > 7) return fail("crf_labels: radius must be in [1, 7]");
+  if (dilation < 1 || dilation > 4) return fail("crf_labels: dilation must be in [1, 4]");
+  if (radius * dilation > 16) return fail("crf_labels: radius * dilation must be at most 16");
+  if (!std::isfinite(w_appearance) || !std::isfinite(w_smooth) || w_appearance < 0.f || w_smooth < 0.f)
+    return fail("crf_labels: the weights must be finite and >= 0");
+  if (!std::isfinite(theta_alpha) || !std::isfinite(theta_beta) || !std::isfinite(theta_gamma) || theta_alpha <= 0.f ||
+      theta_beta <= 0.f || theta_gamma <= 0.f)
+    return fail("crf_labels: every theta must be finite and > 0");
+  if (n_frames > 65535) return fail("crf_labels: at most 65535 frames per call");
+  if (n_frames == 0) return 0;
+  const int n_lab = n_obj + 1;
+  const int64_t n_pix = (int64_t)height * width;
+  if (iterations == 0) {                // the plain merge; Q^0 only on request, straight into q_out
+    launch_crf_prepare(probs, n_frames, n_obj, n_pix, q_out, nullptr, labels_out, e->s);
+    HIPOK(hipGetLastError());
+    return 0;
+  }
+  const size_t plane = (size_t)n_frames * n_lab * n_pix;           // floats of one of the three buffers
+  const size_t need = 3 * plane * sizeof(float);
+  if (need > ((size_t)512 << 20))
+    return fail("crf_labels: " + std::to_string(need >> 20) + " MB of scratch for " + std::to_string(n_frames) +
+                " frames exceeds the 512 MB cap of one call: pass fewer frames per call");
+  if (need > e->crf_cap) {
+    HIPOK(hipStreamSynchronize(e->s));                              // earlier calls' launches may still read the old buffer
+    if (e->crf_buf) HIPOK(hipFree(e->crf_buf));
+    e->crf_buf = nullptr;
+    e->crf_cap = 0;
+    if (hipMalloc(&e->crf_buf, need) != hipSuccess) {
+      (void)hipGetLastError();                                      // the failed allocation is reported here, not by a later call
+      e->crf_buf = nullptr;
+      return fail("crf_labels: hipMalloc of " + std::to_string(need >> 20) + " MB of scratch failed");
+    }
+    e->crf_cap = need;
+    static const char* fill = getenv("EOSVOS_DEBUG_FILL");          // as falloc: the buffer starts out as that word
+    if (fill) { (void)hipMemsetD32((hipDeviceptr_t)e->crf_buf, (int)strtoul(fill, nullptr, 16), need / 4); (void)hipDeviceSynchronize(); }
+  }
+  float* unary = (float*)e->crf_buf;
+  float* q[2] = {unary + plane, unary + 2 * plane};
+  CrfTables tab;
+  crf_fill_tables(tab, radius, dilation, theta_alpha, theta_gamma);
+  launch_crf_prepare(probs, n_frames, n_obj, n_pix, q[0], unary, nullptr, e->s);
+  HIPOK(hipGetLastError());
+  for (int t = 0; t < iterations; ++t) {
+    const bool last = t + 1 == iterations;
+    launch_crf_iteration(images, unary, q[t & 1], last && q_out ? q_out : q[(t + 1) & 1], last ? labels_out : nullptr, n_frames,
+                         n_lab, height, width, radius, dilation, w_appearance, w_smooth, theta_beta, tab, e->s);
+    HIPOK(hipGetLastError());
+  }
   return 0;
 }
 

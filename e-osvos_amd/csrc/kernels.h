@@ -1,4 +1,4 @@
-// Launcher declarations of the gfx950 kernels (conv_kernels.hip, misc_kernels.hip).
+// Launcher declarations of the gfx950 kernels (conv_kernels.hip, misc_kernels.hip, crf_kernels.hip, ...).
 // Host code (engine.cpp) only sees these plain-C++ functions; every launcher enqueues on
 // the given stream and never synchronises or allocates.
 #pragma once
@@ -395,6 +395,20 @@ void launch_warp_affine(const float* src, float* dst, int C, int H, int W, const
 // receive atomic sums; bmp / bmg: frames * n_obj * H * ceil(W/64) words each.  W <= 4096, r <= 63, 1 <= n_obj <= 255
 void launch_davis_counts(const uint8_t* pred, const uint8_t* gt, int frames, int H, int W, int n_obj, int r,
                          unsigned long long* bmp, unsigned long long* bmg, int64_t* counts, hipStream_t s);
+// Locally connected dense CRF over the merged probabilities (crf_kernels.hip; the model: include/eosvos.h, eosvos_crf_labels).
+// Planes are [frame][label][H][W] fp32 with n_lab = n_obj + 1 labels, label maps [frame][H][W].
+// launch_crf_prepare: probs [frame][n_obj][n_pix] -> q0 = Q^0 and u = -log Q^0 (both may be null: nothing of the model is
+// computed), labels (may be null) = merge_labels_kernel's decision on probs.
+// launch_crf_iteration: one mean-field update q_out = softmax(-unary + messages(q_in)), q_in != q_out; labels (may be null)
+// receives the decision on q_out.  1 <= r <= 7, 1 <= d <= 4, r * d <= 16, n_frames <= 65535; `tab` from crf_fill_tables.
+#define CRF_MAX_SIDE 15      // 2 * 7 + 1 offsets per axis
+struct CrfTables { float wa[CRF_MAX_SIDE * CRF_MAX_SIDE], ws[CRF_MAX_SIDE * CRF_MAX_SIDE]; };   // exp(-|delta|^2 / (2 theta^2)), [(dy + r) * (2r + 1) + dx + r]
+void crf_fill_tables(CrfTables& tab, int r, int d, float theta_alpha, float theta_gamma);
+void launch_crf_prepare(const float* probs, int n_frames, int n_obj, int64_t n_pix, float* q0, float* u, uint8_t* labels,
+                        hipStream_t s);
+void launch_crf_iteration(const float* images, const float* unary, const float* q_in, float* q_out, uint8_t* labels,
+                          int n_frames, int n_lab, int H, int W, int r, int d, float w_a, float w_s, float theta_beta,
+                          const CrfTables& tab, hipStream_t s);
 
 // theta' = theta - lr[cout]*g, g = rowscale[cout] * sum_z ws[z][...]; optional gsum += g; g_out = g
 void launch_sgd_update(float* w, const float* ws, int splits, int64_t slab, const float* rowscale,

@@ -578,6 +578,32 @@ class Engine:
                                                 counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return counts
 
+    def crf_labels(self, images, probs, iterations=5, radius=5, dilation=2, w_appearance=10.0, w_smooth=3.0, theta_alpha=8.0,
+                   theta_beta=0.05, theta_gamma=3.0, return_q=False):
+        """Local dense-CRF refinement of the merge (`eosvos_crf_labels`; beside evaluate.py:322-326, the model: `crf.py`).
+        images (N, 3, H, W), probs (N, n_obj, H, W): device fp32 of any H and W -> label maps (N, H, W) uint8, with `return_q`
+        also Q^T (N, n_obj + 1, H, W).  iterations = 0 is `merge_labels`.  Nothing waits for the GPU; the frames go through in
+        chunks that keep the engine's scratch under `crf.SCRATCH_CAP`."""
+        from . import crf
+        p = crf.check(dict(iterations=iterations, radius=radius, dilation=dilation, w_appearance=w_appearance, w_smooth=w_smooth,
+                           theta_alpha=theta_alpha, theta_beta=theta_beta, theta_gamma=theta_gamma))
+        crf._check_tensors(images, probs)
+        self._check_stream()
+        for t in (images, probs):
+            if t.device != self.device or t.dtype != torch.float32:
+                raise ValueError(f'crf_labels: images and probs must be fp32 tensors on {self.device}')
+        images, probs = images.contiguous(), probs.contiguous()
+        n, n_obj, h, w = probs.shape
+        out = torch.empty(n, h, w, dtype=torch.uint8, device=self.device)
+        q = torch.empty(n, n_obj + 1, h, w, device=self.device) if return_q else None
+        step = crf.frames_per_call(n_obj, h, w)
+        for f in range(0, n, step):
+            g = min(f + step, n)
+            _ffi.check(self.lib.eosvos_crf_labels(self.h, _ptr(images[f:g]), _ptr(probs[f:g]), g - f, n_obj, h, w, p['iterations'],
+                                                  p['radius'], p['dilation'], p['w_appearance'], p['w_smooth'], p['theta_alpha'],
+                                                  p['theta_beta'], p['theta_gamma'], _ptr(out[f:g]), _optr(q[f:g] if return_q else None)))
+        return (out, q) if return_q else out
+
     # ---- meta-training ----------------------------------------------------------------
     def meta_task_begin(self):
         _ffi.check(self.lib.eosvos_meta_task_begin(self.h))

@@ -312,6 +312,44 @@ int eosvos_warp_affine_hw(eosvos_engine* e, const float* src, int channels, int 
 int eosvos_davis_counts(eosvos_engine* e, const uint8_t* pred, const uint8_t* gt, int n_frames, int height, int width, int n_obj,
                         int bound_pix, int64_t* counts_out);
 
+/* ---- local dense-CRF refinement of the merged label maps (stands beside src/util/evaluate.py:322-326) ----------- */
+/* The reference merges the per-object probabilities by threshold + arg-max (`:322-326`, eosvos_merge_labels) and never
+ * looks at the frame.  This is the appearance-aware form of that step the OSVOS family uses (OnAVOS, DeepLab v1/v2): the
+ * locally connected dense CRF -- mean field with Gaussian position / colour kernels on a dilated (2r+1)^2 window, the
+ * "ConvCRF" restriction of Kraehenbuehl-Koltun.  An opt-in extension; with iterations = 0 it IS eosvos_merge_labels.
+ * Per frame, labels l = 0 (background), 1..n_obj, p_o = clamp(probs[o - 1], 0, 1) (the train frame holds 2 * GT):
+ *   unary     m = max_o p_o; s_0 = 1 - m, s_o = p_o; s_l <- max(s_l, 1e-5); q0_l = s_l / sum_l s_l; U_l = -log q0_l
+ *   window    offsets D = dilation * (dy, dx), dy, dx in [-radius, radius], (dy, dx) != (0, 0), neighbours inside the frame only
+ *   kernels   k_a(p, q) = exp(-|D|^2 / (2 theta_alpha^2) - |I_p - I_q|^2 / (2 theta_beta^2))   (squared difference summed
+ *             over the 3 channels; only colour differences enter, so the frames' normalisation does not matter)
+ *             k_s(p, q) = exp(-|D|^2 / (2 theta_gamma^2))
+ *   norms     N_a(p) = sum_q exp(-|D|^2 / (2 theta_alpha^2)), N_s(p) = sum_q k_s: position only (they differ from the interior
+ *             constant only near the border), deliberately not sum_q k_a, which underflows to 0 in fp32 at a pixel unlike all
+ *             its neighbours; a term whose normaliser is 0 (no neighbour inside the frame) contributes 0
+ *   update    Q^0 = q0; t = 1..iterations, all of Q^{t-1} read before any of Q^t is written:
+ *             msg_l(p) = w_appearance * sum_q k_a Q^{t-1}_l(q) / N_a(p) + w_smooth * sum_q k_s Q^{t-1}_l(q) / N_s(p)
+ *             Q^t(p) = softmax_l(-U_l(p) + msg_l(p))        (Potts compatibility; the label-independent part cancels)
+ *   decision  0 if Q^T_0 > max_o Q^T_o (strict), else the lowest o attaining the maximum.  iterations = 0 takes
+ *             eosvos_merge_labels' decision (max_o probs < 0.5 ? 0 : first arg-max + 1) on probs as given, bit for bit:
+ *             1 - m > m <=> m < 0.5 holds in fp32 without exception, and the clamp moves no decision on [0, 1] and 2 * GT.
+ * images [n_frames][3][height][width], probs [n_frames][n_obj][height][width], labels_out [n_frames][height][width],
+ * q_out (may be NULL) receives Q^T as [n_frames][n_obj + 1][height][width]; all device memory, frames of any size (`e`
+ * lends its stream and scratch memory only).  Asynchronous on the engine's stream.  Launches: one to prepare (unary, Q^0),
+ * one per iteration (the last one also decides); no matrix kernel, eosvos_plan_fingerprint is untouched.  One writer per
+ * element and a fixed summation order: two calls give the same bits, and a frame's result does not depend on the frames
+ * beside it.  Scratch: 3 * n_frames * (n_obj + 1) * height * width floats (none with iterations = 0), allocated on first
+ * use, growing only, at most 512 MB per call -- a call that needs more is rejected (pass fewer frames per call); a
+ * failed allocation is reported and leaves the engine usable.
+ * Rejected without a launch: a null pointer (q_out excepted), height or width < 1, n_obj outside [1, 255], iterations
+ * outside [0, 20], radius outside [1, 7], dilation outside [1, 4], radius * dilation > 16, a weight < 0 or non-finite,
+ * a theta <= 0 or non-finite, more than 65535 frames.  The customary defaults (iterations 5, radius 5, dilation 2,
+ * w_appearance 10, w_smooth 3, theta_alpha 8 px, theta_beta 0.05 on [0, 1] RGB, theta_gamma 3 px: eosvos_amd/crf.py)
+ * are pydensecrf's rescaled to this normalisation and are not tuned on data. */
+int eosvos_crf_labels(eosvos_engine* e, const float* images, const float* probs, int n_frames, int n_obj,
+                      int height, int width, int iterations, int radius, int dilation, float w_appearance,
+                      float w_smooth, float theta_alpha, float theta_beta, float theta_gamma,
+                      uint8_t* labels_out, float* q_out);
+
 /* ---- learning-rate hierarchy (meta_optim.py:27-67) ------------------------------------ */
 /* `lr_hierarchy_level`: how the learned lr state is stored.  NEURON (cfgs/meta.yaml:36) one
  * value per output channel; TENSOR one per trainable tensor (`log_init_lr` of shape
