@@ -13,6 +13,25 @@ LIB_PATH = os.environ.get('EOSVOS_LIB') or os.path.join(_HERE, 'libeosvos.so')  
 c_float_p = ctypes.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 _E = ctypes.c_void_p
 
+
+class View(ctypes.Structure):
+    """include/eosvos.h eosvos_view: a pixel-major view (first element, floats per pixel) and the tensor it is a slice of."""
+    _fields_ = [('p', ctypes.c_void_p), ('ld', ctypes.c_int), ('key', ctypes.c_void_p), ('ldkey', ctypes.c_int)]
+
+
+class ConvViews(ctypes.Structure):
+    """include/eosvos.h eosvos_conv_views."""
+    _fields_ = ([(n, ctypes.c_int) for n in ('algo', 'B', 'H', 'W', 'Cin', 'Cout', 'k', 'stride', 'dil', 'pad')] +
+                [('w_oihw', ctypes.c_void_p), ('scale', ctypes.c_void_p), ('bias', ctypes.c_void_p), ('passes', ctypes.c_int),
+                 ('x', View), ('y', View), ('res', View), ('relu', ctypes.c_int), ('y_m8', ctypes.c_void_p),
+                 ('g', View), ('gx', View), ('add', View), ('accum', ctypes.c_int), ('mask_c0', ctypes.c_int),
+                 ('gx_m8', ctypes.c_void_p), ('dw_oihw', ctypes.c_void_p),
+                 ('slot_bits', ctypes.c_uint * 2), ('slot_valid', ctypes.c_int * 2),
+                 ('src_slot_bits', ctypes.c_uint * 2), ('src_slot_valid', ctypes.c_int * 2), ('fwd_slices', ctypes.c_int)])
+
+
+VIEWS_FWD, VIEWS_DGRAD, VIEWS_WGRAD = 1, 2, 4
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     'eosvos_version': (ctypes.c_char_p, []),
@@ -119,6 +138,10 @@ _SIGNATURES = {
                                              ctypes.c_int] + [ctypes.c_int] * 9 + [c_float_p]),
     'eosvos_test_conv_bwd_algo': (ctypes.c_int, [_E, ctypes.c_int, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_void_p] +
                                   [ctypes.c_int] * 9 + [c_float_p, c_float_p]),
+    'eosvos_test_conv_views': (ctypes.c_int, [_E, ctypes.POINTER(ConvViews)]),
+    'eosvos_test_aspp_dgrad': (ctypes.c_int, [_E, ctypes.c_int, c_float_p, ctypes.c_void_p, c_float_p, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint),
+                                              ctypes.POINTER(ctypes.c_int)]),
     'eosvos_test_groupnorm': (ctypes.c_int, [_E, ctypes.c_int, c_float_p, ctypes.c_int, c_float_p, ctypes.c_int, c_float_p,
                                              c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_float, c_float_p, ctypes.c_int, c_float_p, ctypes.c_void_p,

@@ -1442,6 +1442,21 @@ bool aspp_dgrad_merged(eosvos_engine* e, int B, float* g_l4, const float* l4) {
   return true;
 }
 
+// g_l4 (holding the pooling branch's broadcast) += the four ASPP branches' data gradients, masked with the ReLU mask of l4: the
+// K-concatenated launch, or -- where it declines, or `force_fallback` (parity tests) -- one accumulating conv_dgrad per branch,
+// the mask applied by the last.  *merged (may be null): which of the two ran.
+int aspp_dgrad(eosvos_engine* e, int B, float* g_l4, const float* l4, bool force_fallback, bool* merged) {
+  const Topo& t = e->t;
+  const bool m = !force_fallback && aspp_dgrad_merged(e, B, g_l4, l4);
+  if (merged) *merged = m;
+  if (m) return 0;
+  for (int i = 0; i < 4; ++i)
+    if (conv_dgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, e->h16, e->w16, g_l4, 2048, B, true, i == 3 ? l4 : nullptr, 0, nullptr, 0,
+                   e->g_cat))
+      return 1;
+  return 0;
+}
+
 // The grouped weight-gradient tables (WgradArgs with or without absmax slots, split counts) and the update tables (slab
 // counts per conv) depend on the process-wide matrix mode: a mode switch on a live engine drops them.
 void plans_match_mode(eosvos_engine* e) {
@@ -2244,12 +2259,7 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
   }
   {
     for (int i = 0; i < 4; ++i) conv_wgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, l4, 2048, e->h16, e->w16, B, e->g_cat);
-    if (!l4_frozen && !aspp_dgrad_merged(e, B, g_l4, l4)) {
-      for (int i = 0; i < 4; ++i)
-        if (conv_dgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, e->h16, e->w16, g_l4, 2048, B, true, i == 3 ? l4 : nullptr, 0, nullptr, 0,
-                       e->g_cat))
-          return 1;
-    }
+    if (!l4_frozen && aspp_dgrad(e, B, g_l4, l4, false, nullptr)) return 1;
   }
   // layer4, ASPP and decoder are done: update them now (on the side stream if there is one)
   auto flush_part0 = [&]() -> int {
@@ -3364,6 +3374,144 @@ int eosvos_test_conv_bwd(eosvos_engine* e, const float* x, const float* w_oihw, 
   ModeScope mode_scope(e);
   return eosvos_test_conv_bwd_algo(e, EOSVOS_ALGO_DIRECT, x, w_oihw, g, nullptr, nullptr, B, H, W, Cin, Cout, k, stride, dil, pad, dx,
                                    dw_oihw);
+}
+
+// ---- the same convolution in the forms the network's passes use: channel slices of wider tensors (absmax slot, mask bytes
+// and pitch of the TENSOR), accumulating / adding / partially masked data gradients ------------------------------------
+namespace {
+// the absmax slot of the tensor at `key` as a consumer would read it: maximum of its words; valid = tlookup would return it
+int read_tslot(eosvos_engine* t, int phase, const float* key, unsigned* bits, int* valid) {
+  *bits = 0; *valid = 0;
+  if (!h3_mode() || !t->amax) return 0;
+  auto it = t->treg[phase].find(key);
+  if (it == t->treg[phase].end()) return 0;
+  unsigned w[AMAX_SUB];
+  HIPOK(hipMemcpy2D(w, sizeof(unsigned), t->amax + amax_tcol(t, phase, it->second.idx), (size_t)AMAX_ROW * sizeof(unsigned),
+                    sizeof(unsigned), AMAX_SUB, hipMemcpyDeviceToHost));
+  for (int i = 0; i < AMAX_SUB; ++i) *bits = w[i] > *bits ? w[i] : *bits;
+  *valid = it->second.valid ? 1 : 0;
+  return 0;
+}
+// a producer's part for a source tensor that the caller filled: max|tensor| over ALL its channels into its slot, trusted
+int seed_tslot(eosvos_engine* t, int phase, const float* key, long rows, int C) {
+  if (!h3_mode()) return 0;
+  if (amax_init(t)) return fail("absmax arena");
+  unsigned* sl = tslot(t, phase, key);
+  if (!sl) return fail("no absmax slot left for the source tensor");
+  launch_absmax(key, rows, C, C, sl, t->s);
+  tmark_valid(t, phase, key);
+  return 0;
+}
+bool view_ok(const eosvos_view& v, int C) {
+  if (!v.p || v.ld < C || (v.ld & 3)) return false;
+  if (!v.key) return true;
+  const long off = v.p - v.key;
+  return v.ldkey == v.ld && off >= 0 && !(off & 3) && off + C <= v.ldkey;
+}
+}  // namespace
+
+int eosvos_test_conv_views(eosvos_engine* e, eosvos_conv_views* v) {
+  ModeScope mode_scope(e);
+  if (!e || !v || !v->w_oihw) return fail("null argument");
+  const int B = v->B, H = v->H, W = v->W, Cin = v->Cin, Cout = v->Cout, k = v->k;
+  if (B < 1 || H < 1 || W < 1 || Cin < 4 || Cout < 4 || (Cin % 4) || (Cout % 4)) return fail("bad geometry (channels must be multiples of 4)");
+  if (v->algo < EOSVOS_ALGO_AUTO || v->algo > EOSVOS_ALGO_WINO_F4) return fail("unknown conv algorithm");
+  const bool fwd = v->passes & EOSVOS_VIEWS_FWD, dg = v->passes & EOSVOS_VIEWS_DGRAD, wg = v->passes & EOSVOS_VIEWS_WGRAD;
+  if (!fwd && !dg && !wg) return fail("no pass selected");
+  if (fwd && (v->scale == nullptr) != (v->bias == nullptr)) return fail("scale and bias go together (folded norm)");
+  if (fwd && (!view_ok(v->x, Cin) || !view_ok(v->y, Cout) || (v->res.p && !view_ok(v->res, Cout)))) return fail("bad forward view");
+  const int nsl = v->fwd_slices > 1 ? v->fwd_slices : 1;
+  if (nsl > 1) {      // slice i reads x.p + i * Cin and writes y.p + i * Cout: both must be slices of keyed tensors wide enough for all
+    if (!fwd || dg || wg || v->res.p || !v->x.key || !v->y.key) return fail("fwd_slices: forward only, keyed x and y, no residual");
+    if ((v->x.p - v->x.key) + (long)nsl * Cin > v->x.ldkey || (v->y.p - v->y.key) + (long)nsl * Cout > v->y.ldkey) return fail("fwd_slices: past the tensor");
+  }
+  if ((dg || wg) && !view_ok(v->g, Cout)) return fail("bad gradient view");
+  if (dg && (!view_ok(v->gx, Cin) || (v->add.p && !view_ok(v->add, Cin)) || v->mask_c0 < 0 || (v->mask_c0 & 3))) return fail("bad data-gradient view");
+  if (wg && (!view_ok(v->x, Cin) || !v->dw_oihw)) return fail("bad weight-gradient view");
+  ScratchEngine se(e, v->algo, B, H, W, Cin, Cout, k, v->stride, v->dil, v->pad, v->scale != nullptr);
+  if (!se.ok) return fail("scratch engine: shape not eligible for the requested algorithm, or out of memory");
+  eosvos_engine* t = &se.t;
+  const int T = k * k;
+  const int Ho = conv_out(H, k, v->stride, v->dil, v->pad), Wo = conv_out(W, k, v->stride, v->dil, v->pad);
+  const long Pin = (long)B * H * W, Pout = (long)B * Ho * Wo;
+  launch_oihw_to_ohwi(v->w_oihw, t->Wp, Cout, Cin, T, t->s);
+  if (v->scale) HIPOK(hipMemcpyAsync(t->na, v->scale, (size_t)Cout * 4, hipMemcpyDeviceToDevice, t->s));
+  if (v->bias) HIPOK(hipMemcpyAsync(t->nb, v->bias, (size_t)Cout * 4, hipMemcpyDeviceToDevice, t->s));
+  const float* xkey = v->x.key ? v->x.key : v->x.p;
+  v->slot_bits[0] = v->slot_bits[1] = v->src_slot_bits[0] = v->src_slot_bits[1] = 0;
+  v->slot_valid[0] = v->slot_valid[1] = v->src_slot_valid[0] = v->src_slot_valid[1] = 0;
+  amax_new_phase(t, 0);
+  if ((fwd || wg) && v->x.key && seed_tslot(t, 0, v->x.key, Pin, v->x.ldkey)) return 1;
+  if (fwd) {
+    if (v->res.p && wino_on(t, 0, B, Ho, Wo)) return fail("the Winograd output transform has no residual input (the network never needs one)");
+    const float* ykey = v->y.key ? v->y.key : v->y.p;
+    if (v->y_m8) t->mask8[ykey] = v->y_m8;
+    for (int i = 0; i < nsl; ++i)
+      conv_fwd(t, 0, v->x.p + (long)i * Cin, v->x.ld, H, W, v->y.p + (long)i * Cout, v->y.ld, B, v->res.p, v->res.ld, v->relu != 0, false, xkey, ykey);
+    HIPOK(hipStreamSynchronize(t->s));
+    HIPOK(hipGetLastError());
+    t->mask8.erase(ykey);
+    if (read_tslot(t, 0, ykey, &v->slot_bits[0], &v->slot_valid[0])) return 1;
+  }
+  if ((fwd || wg) && v->x.key && read_tslot(t, 0, v->x.key, &v->src_slot_bits[0], &v->src_slot_valid[0])) return 1;
+  if (dg || wg) {
+    amax_new_phase(t, 1);
+    const float* gkey = v->g.key ? v->g.key : v->g.p;
+    if (v->g.key && seed_tslot(t, 1, v->g.key, Pout, v->g.ldkey)) return 1;
+    // the order of the backward pass: weight gradient first (it makes the shared Winograd-domain dM), then data gradient
+    if (wg) conv_wgrad(t, 0, v->g.p, v->g.ld, v->x.p, v->x.ld, H, W, B, gkey, xkey);
+    if (dg) {
+      const float* gxkey = v->gx.key ? v->gx.key : v->gx.p;
+      if (v->gx_m8) t->mask8[v->gx.p] = const_cast<uint8_t*>(v->gx_m8);      // the mask bytes of the activation gx is the gradient of
+      if (conv_dgrad(t, 0, v->g.p, v->g.ld, H, W, v->gx.p, v->gx.ld, B, v->accum != 0, v->gx_m8 ? v->gx.p : nullptr, v->mask_c0,
+                     v->add.p, v->add.ld, gkey, gxkey))
+        return 1;
+      HIPOK(hipStreamSynchronize(t->s));
+      HIPOK(hipGetLastError());
+      if (read_tslot(t, 1, gxkey, &v->slot_bits[1], &v->slot_valid[1])) return 1;
+    }
+    if (wg) {
+      const int64_t n = (int64_t)Cout * Cin * T;
+      float* dw = t->falloc(n);
+      if (!dw) return fail("hipMalloc dw");
+      launch_sgd_update(dw, t->ws_wg, t->upd_splits[0], n, v->scale ? t->na : nullptr, nullptr, nullptr, dw, (int64_t)T * Cin, n, t->s);
+      launch_ohwi_to_oihw(dw, v->dw_oihw, Cout, Cin, T, 1.f, 0, t->s);
+    }
+  }
+  HIPOK(hipStreamSynchronize(t->s));
+  HIPOK(hipGetLastError());
+  if ((dg || wg) && v->g.key && read_tslot(t, 1, v->g.key, &v->src_slot_bits[1], &v->src_slot_valid[1])) return 1;
+  return 0;
+}
+
+int eosvos_test_aspp_dgrad(eosvos_engine* e, int batch, const float* g_cat, const uint8_t* l4_m8, float* g_l4_inout,
+                           int force_fallback, int* merged_ran, unsigned* slot_bits, int* slot_valid) {
+  ModeScope mode_scope(e);
+  if (!e || !g_cat || !l4_m8 || !g_l4_inout || !merged_ran || !slot_bits || !slot_valid) return fail("null argument");
+  if (batch < 1 || batch > e->maxB) return fail("batch out of range");
+  const Topo& t = e->t;
+  float* g_l4 = e->bb.back().g_out;
+  const float* l4 = e->bb.back().out;
+  const int cin = t.convs[t.aspp[0]].cin;
+  uint8_t* m8 = e->m8(l4);
+  if (cin != 2048 || e->gn() || !m8) return fail("eosvos_test_aspp_dgrad needs the frozen-norm ResNet-50/101 ASPP with mask bytes");
+  const size_t P = (size_t)batch * e->h16 * e->w16;
+  plans_match_mode(e);
+  e->masks_valid = false;                         // the mask bytes of l4 and the gradient buffers no longer belong to a forward
+  e->have_loss_grad = false;
+  HIPOK(hipMemcpyAsync(e->g_cat, g_cat, P * 1280 * sizeof(float), hipMemcpyDeviceToDevice, e->s));
+  HIPOK(hipMemcpyAsync(m8, l4_m8, P * (cin / 4), hipMemcpyDeviceToDevice, e->s));
+  HIPOK(hipMemcpyAsync(g_l4, g_l4_inout, P * cin * sizeof(float), hipMemcpyDeviceToDevice, e->s));
+  amax_new_phase(e, 1);
+  if (seed_tslot(e, 1, e->g_cat, (long)P, 1280)) return 1;      // as the projection's data gradient, the writer of g_cat, leaves it
+  twrite_plain(e, 1, g_l4);                       // the pooling branch's broadcast has no fused absmax
+  bool merged = false;
+  if (aspp_dgrad(e, batch, g_l4, l4, force_fallback != 0, &merged)) return 1;
+  *merged_ran = merged ? 1 : 0;
+  HIPOK(hipMemcpyAsync(g_l4_inout, g_l4, P * cin * sizeof(float), hipMemcpyDeviceToDevice, e->s));
+  HIPOK(hipStreamSynchronize(e->s));
+  HIPOK(hipGetLastError());
+  return read_tslot(e, 1, g_l4, slot_bits, slot_valid);
 }
 
 // ---- op-level entry points of the other kernels (misc_kernels.hip) --------------------------------------------------

@@ -796,6 +796,91 @@ class Engine:
                                                  Cout, k, stride, dil, pad, _ptr(dx), _ptr(dw)))
         return dx, dw
 
+    @staticmethod
+    def _view(t, C, shape):
+        """eosvos_view of `t`: a (B, h, w, C) NHWC tensor, or (view, base) with `view` a channel slice of the contiguous NHWC
+        tensor `base` (the key: absmax slot and mask bytes are kept per tensor).  Refuses anything that is not inside its base."""
+        v = _ffi.View()
+        if t is None:
+            return v
+        view, base = t if isinstance(t, tuple) else (t, None)
+        B, h, w = shape
+        ld = view.stride(2)
+        assert view.dtype == torch.float32 and tuple(view.shape) == (B, h, w, C), (tuple(view.shape), (B, h, w, C))
+        assert view.stride() == (h * w * ld, w * ld, ld, 1) and ld >= C and ld % 4 == 0, view.stride()
+        v.p, v.ld = view.data_ptr(), ld
+        if base is None:
+            assert view.is_contiguous() or view._base is not None, 'a strided view needs its base tensor'
+            if view._base is not None:
+                b0 = view._base
+                off = (view.data_ptr() - b0.data_ptr()) // 4
+                assert 0 <= off and off + (B * h * w - 1) * ld + C <= b0.numel(), 'view outside its storage'
+        else:
+            assert base.dtype == torch.float32 and base.is_contiguous() and tuple(base.shape) == (B, h, w, ld), tuple(base.shape)
+            off = (view.data_ptr() - base.data_ptr()) // 4
+            assert 0 <= off <= ld - C and off % 4 == 0, off
+            v.key, v.ldkey = base.data_ptr(), ld
+        return v
+
+    def test_conv_views(self, algo, w_oihw, stride, dil, pad, shape, scale=None, bias=None, x=None, y=None, res=None, relu=False,
+                        y_m8=None, g=None, gx=None, add=None, accum=False, mask_c0=0, gx_m8=None, want_dw=False, fwd_slices=1):
+        """One conv through the production conv_fwd / conv_dgrad / conv_wgrad with every operand a view (include/eosvos.h
+        eosvos_test_conv_views): `shape` = (B, H, W) of the conv input; an operand is an NHWC tensor (its pixel stride is the
+        pitch) or a (view, base) pair.  Passes: forward when `y` is given (written in place; y_m8 = uint8 (B, Ho, Wo, ld / 4) mask
+        bytes of the whole y tensor), data gradient when `gx` is given (in place; gx_m8 = uint8 (B, H, W, ld / 4)), weight
+        gradient when want_dw.  fwd_slices = n > 1: n forwards in one absmax phase, the i-th reading the next Cin channels of x's
+        base and writing the next Cout channels of y's.  Returns {'dw', 'y_slot', 'gx_slot', 'x_slot', 'g_slot'}: slots as (bit
+        pattern of the committed max, trusted); x_slot / g_slot: the whole-tensor slot a keyed source view ran under."""
+        B, H, W = shape
+        Cout, Cin, k, _ = w_oihw.shape
+        Ho = (H + 2 * pad - dil * (k - 1) - 1) // stride + 1
+        Wo = (W + 2 * pad - dil * (k - 1) - 1) // stride + 1
+        a = _ffi.ConvViews()
+        a.algo, a.B, a.H, a.W, a.Cin, a.Cout, a.k, a.stride, a.dil, a.pad = self.ALGOS[algo], B, H, W, Cin, Cout, k, stride, dil, pad
+        assert w_oihw.is_contiguous() and w_oihw.dtype == torch.float32
+        a.w_oihw = w_oihw.data_ptr()
+        for name, t in (('scale', scale), ('bias', bias)):
+            if t is not None:
+                assert t.is_contiguous() and t.dtype == torch.float32 and t.numel() == Cout
+                setattr(a, name, t.data_ptr())
+        a.passes = (_ffi.VIEWS_FWD if y is not None else 0) | (_ffi.VIEWS_DGRAD if gx is not None else 0) | (_ffi.VIEWS_WGRAD if want_dw else 0)
+        a.x, a.y, a.res = self._view(x, Cin, (B, H, W)), self._view(y, Cout, (B, Ho, Wo)), self._view(res, Cout, (B, Ho, Wo))
+        a.g, a.gx, a.add = self._view(g, Cout, (B, Ho, Wo)), self._view(gx, Cin, (B, H, W)), self._view(add, Cin, (B, H, W))
+        a.relu, a.accum, a.mask_c0, a.fwd_slices = int(relu), int(accum), int(mask_c0), int(fwd_slices)
+        if fwd_slices > 1:
+            for vw, C in ((a.x, Cin), (a.y, Cout)):
+                assert vw.key and (vw.p - vw.key) // 4 + fwd_slices * C <= vw.ldkey, 'fwd_slices: past the base tensor'
+        if y_m8 is not None:
+            assert y_m8.dtype == torch.uint8 and y_m8.is_contiguous() and tuple(y_m8.shape) == (B, Ho, Wo, a.y.ld // 4), tuple(y_m8.shape)
+            a.y_m8 = y_m8.data_ptr()
+        if gx_m8 is not None:
+            assert gx_m8.dtype == torch.uint8 and gx_m8.is_contiguous() and tuple(gx_m8.shape) == (B, H, W, a.gx.ld // 4), tuple(gx_m8.shape)
+            a.gx_m8 = gx_m8.data_ptr()
+        dw = torch.empty_like(w_oihw) if want_dw else None
+        if dw is not None:
+            a.dw_oihw = dw.data_ptr()
+        torch.cuda.synchronize(self.device)
+        _ffi.check(self.lib.eosvos_test_conv_views(self.h, ctypes.byref(a)))
+        return {'dw': dw, 'y_slot': (int(a.slot_bits[0]), bool(a.slot_valid[0])), 'gx_slot': (int(a.slot_bits[1]), bool(a.slot_valid[1])),
+                'x_slot': (int(a.src_slot_bits[0]), bool(a.src_slot_valid[0])), 'g_slot': (int(a.src_slot_bits[1]), bool(a.src_slot_valid[1]))}
+
+    def test_aspp_dgrad(self, g_cat, l4_m8, g_l4, force_fallback=False):
+        """The ASPP branches' data gradient into d(layer4 output) as the backward pass runs it (include/eosvos.h
+        eosvos_test_aspp_dgrad), with this engine's weights: g_cat (B, h16, w16, 1280), l4_m8 uint8 (B, h16, w16, 512), g_l4
+        (B, h16, w16, 2048) updated in place.  Returns (merged_ran, (slot bits, trusted))."""
+        B, h, w, _ = g_cat.shape
+        ptr, dims = ctypes.c_void_p(), (ctypes.c_int64 * 4)()
+        _ffi.check(self.lib.eosvos_debug_tensor(self.h, b'g_cat', ctypes.byref(ptr), dims))
+        assert (h, w) == (int(dims[1]), int(dims[2])) and 1 <= B <= self.max_batch, ((B, h, w), list(dims))      # the engine's own buffers
+        assert g_cat.is_contiguous() and g_cat.dtype == torch.float32 and g_cat.shape[3] == 1280
+        assert g_l4.is_contiguous() and g_l4.dtype == torch.float32 and tuple(g_l4.shape) == (B, h, w, 2048)
+        assert l4_m8.is_contiguous() and l4_m8.dtype == torch.uint8 and tuple(l4_m8.shape) == (B, h, w, 512)
+        merged, bits, valid = ctypes.c_int(), ctypes.c_uint(), ctypes.c_int()
+        torch.cuda.synchronize(self.device)
+        _ffi.check(self.lib.eosvos_test_aspp_dgrad(self.h, B, _ptr(g_cat), _ptr(l4_m8), _ptr(g_l4), int(force_fallback),
+                                                   ctypes.byref(merged), ctypes.byref(bits), ctypes.byref(valid)))
+        return bool(merged.value), (int(bits.value), bool(valid.value))
+
     # Op-level entries of misc_kernels.hip (include/eosvos.h) on device tensors.  Pixel-major (B, P, C) / (B, H, W, C) views with
     # unit channel stride; the pixel stride is the leading dimension, so a channel slice of a wider buffer may be passed.
     def test_groupnorm(self, z, gamma, beta, eps=1e-5, res=None, relu=False, y=None, m8=None):

@@ -518,6 +518,59 @@ int eosvos_test_conv_bwd(eosvos_engine* e, const float* x_nhwc, const float* w_o
                          const float* g_nhwc, int B, int H, int W, int Cin, int Cout, int k,
                          int stride, int dil, int pad, float* dx_nhwc, float* dw_oihw);
 
+/* One convolution through the production conv_fwd / conv_dgrad / conv_wgrad in the forms the network's passes use: every
+ * tensor operand is a VIEW -- `p` first element (device), `ld` floats per pixel, and, when it is a channel slice of a wider
+ * tensor, `key` / `ldkey`: first element and pixel pitch (= channel count) of that tensor (key NULL: the view is the tensor).
+ * The f16x3 absmax slots, the mask bytes and the pair8 siblings are kept per TENSOR, i.e. per key. */
+typedef struct eosvos_view {
+  float* p;
+  int ld;
+  float* key;
+  int ldkey;
+} eosvos_view;
+#define EOSVOS_VIEWS_FWD 1
+#define EOSVOS_VIEWS_DGRAD 2
+#define EOSVOS_VIEWS_WGRAD 4
+typedef struct eosvos_conv_views {
+  /* geometry as eosvos_test_conv_algo: x [B][H][W][Cin], y / g [B][Ho][Wo][Cout]; scale / bias (per cout) may be NULL */
+  int algo, B, H, W, Cin, Cout, k, stride, dil, pad;
+  const float* w_oihw;
+  const float* scale;
+  const float* bias;
+  int passes;                 /* EOSVOS_VIEWS_*; in one call the weight gradient runs before the data gradient */
+  /* forward: y = relu?(a * conv(x) + b (+ res)).  y_m8 (may be NULL): the mask bytes of the WHOLE y tensor, y.ldkey / 4 (or
+   * y.ld / 4) bytes per pixel; a ReLU forward writes bit j of byte [p][q] = (channel 4q + j of the tensor > 0) for the view */
+  eosvos_view x, y, res;
+  int relu;
+  uint8_t* y_m8;
+  /* data gradient: gx = M * ((accum ? gx : 0) + add + dgrad(a * g)); M from gx_m8 (may be NULL; gx.ld / 4 bytes per pixel,
+   * byte [p][q] bit j = channel 4q + j of the view) for channels >= mask_c0, 1 below */
+  eosvos_view g, gx, add;
+  int accum, mask_c0;
+  const uint8_t* gx_m8;
+  /* weight gradient of g and x: dw [Cout][Cin][k][k] = a * wgrad(g, x) */
+  float* dw_oihw;
+  /* out, f16x3 mode (0 in the others): the absmax slot of the destination tensor after the pass -- [0] y, [1] gx -- as the
+   * maximum of its words (the bit pattern of max |value| the writers committed), and whether a consumer would trust it.  A
+   * keyed SOURCE view runs under the slot of its whole tensor, which the entry fills first, as the tensor's producer would. */
+  unsigned slot_bits[2];
+  int slot_valid[2];
+  /* the same for the whole-tensor slots the keyed SOURCE views ran under: [0] x, [1] g (0 when the view has no key) */
+  unsigned src_slot_bits[2];
+  int src_slot_valid[2];
+  /* forward only, > 1: that many launches in ONE absmax phase, launch i reading x.p + i * Cin and writing y.p + i * Cout
+   * (x and y keyed and wide enough) -- all slices of a tensor written one after the other; slot [0] is read after the last */
+  int fwd_slices;
+} eosvos_conv_views;
+int eosvos_test_conv_views(eosvos_engine* e, eosvos_conv_views* v);
+/* The ASPP branches' data gradient into d(layer4 output) on a loaded engine -- the step backward_impl runs (aspp_dgrad: the
+ * K-concatenated launch, or four accumulating conv_dgrad calls when it declines or force_fallback is set):
+ * g_l4 = M * (g_l4 + sum_i dgrad_i(a_i * g_cat[..., 256 i : 256 i + 256])).  g_cat [B][h16][w16][1280], l4_m8 [B][h16][w16][Cin / 4]
+ * mask bytes of the layer4 output, g_l4 [B][h16][w16][Cin] in / out (device).  merged_ran: which path ran; slot_bits /
+ * slot_valid: g_l4's f16x3 absmax slot as in eosvos_conv_views. */
+int eosvos_test_aspp_dgrad(eosvos_engine* e, int batch, const float* g_cat, const uint8_t* l4_m8, float* g_l4_inout,
+                           int force_fallback, int* merged_ran, unsigned* slot_bits, int* slot_valid);
+
 /* Op-level entries of the other kernels (misc_kernels.hip) for the parity tests: the production launchers with the engine's
  * own geometry, on caller DEVICE tensors (NHWC, `ld*` = floats per pixel, so a channel slice of a wider buffer works), on the
  * engine's stream; they synchronise before returning.
