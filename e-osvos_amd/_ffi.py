@@ -77,6 +77,9 @@ _SIGNATURES = {
                                            ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     'eosvos_crf_labels': (ctypes.c_int, [_E, c_float_p, c_float_p] + [ctypes.c_int] * 7 + [ctypes.c_float] * 5 +
                           [ctypes.c_void_p, c_float_p]),
+    'eosvos_label_components': (ctypes.c_int, [_E, ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+    'eosvos_filter_components': (ctypes.c_int, [_E, ctypes.c_void_p] + [ctypes.c_int] * 8 +
+                                 [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'eosvos_set_norm': (ctypes.c_int, [_E, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_float]),
     'eosvos_reset': (ctypes.c_int, [_E]),
     'eosvos_get_params': (ctypes.c_int, [_E, c_float_p]),

@@ -116,6 +116,16 @@ POSTPROCESS = {
 }
 
 
+# Region-level clean-up of the evaluation's label maps, handled like EXTENSIONS and POSTPROCESS (not part of BASE, added by
+# `parse_cli` only when the command line sets one of its keys: `eval_components.gate=24 eval_components.min_rel_area=0.05
+# eval_components.largest_only=True` -- example values, untuned; read with `cfg.get(...)`).
+#   eval_components   connected-component filter after the merge and the CRF (`components.py`); the value below is the neutral
+#                     one (`components.DEFAULTS`: nothing is filtered, nothing new is called)
+CLEANUP = {
+    'eval_components': {'connectivity': 8, 'min_area': 0, 'min_rel_area': 0.0, 'largest_only': False, 'gate': 0},
+}
+
+
 def _merge(dst, src):
     for k, v in src.items():
         if isinstance(v, dict) and isinstance(dst.get(k), dict):
@@ -162,7 +172,7 @@ def parse_cli(argv):
             raise KeyError(f'unknown named config: {a}')
     for k, v in updates:
         group = k.split('.')[0]
-        for groups in (EXTENSIONS, POSTPROCESS):
+        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP):
             if group in groups and group not in cfg:
                 cfg[group] = copy.deepcopy(groups[group])
         _set_dotted(cfg, k, v)
@@ -172,6 +182,9 @@ def parse_cli(argv):
     if 'eval_crf' in cfg:
         from .crf import check as check_crf
         check_crf(cfg['eval_crf'])                          # ValueError: radius 0, a negative weight, ...
+    if 'eval_components' in cfg:
+        from .components import check as check_components
+        check_components(cfg['eval_components'])            # ValueError: gate 64, connectivity 6, ...
     unsupported(cfg)
     return cfg
 

@@ -208,6 +208,8 @@ struct eosvos_engine {
   size_t davis_cap = 0;
   void* crf_buf = nullptr;              // eosvos_crf_labels: unary + the two Q planes of the mean field (grow-only, freed by destroy)
   size_t crf_cap = 0;
+  void* ccl_buf = nullptr;              // eosvos_label_components / eosvos_filter_components: union-find, ids, areas, flags (grow-only, freed by destroy)
+  size_t ccl_cap = 0;
   int lr_level = EOSVOS_LR_NEURON, lr_log = 0;
   float *lr_elem = nullptr, *glr_tmp = nullptr, *ptmp = nullptr;
   int *row_tensor = nullptr, *tensor_row0 = nullptr, *all_row0 = nullptr;
@@ -1821,6 +1823,7 @@ int eosvos_destroy(eosvos_engine* e) {
   for (void* p : e->allocs) (void)hipFree(p);
   if (e->davis_buf) (void)hipFree(e->davis_buf);
   if (e->crf_buf) (void)hipFree(e->crf_buf);
+  if (e->ccl_buf) (void)hipFree(e->ccl_buf);
   delete e;
   return 0;
 }
@@ -2766,6 +2769,104 @@ int eosvos_crf_labels(eosvos_engine* e, const float* images, const float* probs,
     launch_crf_iteration(images, unary, q[t & 1], last && q_out ? q_out : q[(t + 1) & 1], last ? labels_out : nullptr, n_frames,
                          n_lab, height, width, radius, dilation, w_appearance, w_smooth, theta_beta, tab, e->s);
     HIPOK(hipGetLastError());
+  }
+  return 0;
+}
+
+// ---- connected-component clean-up of the merged label maps (after evaluate.py:322-326 and the CRF) --------------------
+// argument checks shared by the two entry points; `who` names the entry point in the message
+static int ccl_check(const char* who, int n_frames, int height, int width, int connectivity) {
+  const std::string w(who);
+  if (n_frames < 0 || height < 1 || width < 1) return fail(w + ": bad frame geometry");
+  if (height > 4096 || width > 4096) return fail(w + ": frames larger than 4096 pixels a side are not supported");
+  if ((int64_t)height * width >= ((int64_t)1 << 24)) return fail(w + ": frames of 2^24 pixels or more are not supported");
+  if (connectivity != 4 && connectivity != 8) return fail(w + ": connectivity must be 4 or 8");
+  if (n_frames > 65535) return fail(w + ": at most 65535 frames per call");
+  return 0;
+}
+static int ccl_scratch(eosvos_engine* e, const char* who, size_t need, int n_frames) {
+  const std::string w(who);
+  if (need > ((size_t)512 << 20))
+    return fail(w + ": " + std::to_string(need >> 20) + " MB of scratch for " + std::to_string(n_frames) +
+                " frames exceeds the 512 MB cap of one call: pass fewer frames per call");
+  if (need > e->ccl_cap) {
+    HIPOK(hipStreamSynchronize(e->s));                              // earlier calls' launches may still read the old buffer
+    if (e->ccl_buf) HIPOK(hipFree(e->ccl_buf));
+    e->ccl_buf = nullptr;
+    e->ccl_cap = 0;
+    if (hipMalloc(&e->ccl_buf, need) != hipSuccess) {
+      (void)hipGetLastError();
+      e->ccl_buf = nullptr;
+      return fail(w + ": hipMalloc of " + std::to_string(need >> 20) + " MB of scratch failed");
+    }
+    e->ccl_cap = need;
+    static const char* fill = getenv("EOSVOS_DEBUG_FILL");          // as falloc: the buffer starts out as that word
+    if (fill) { (void)hipMemsetD32((hipDeviceptr_t)e->ccl_buf, (int)strtoul(fill, nullptr, 16), need / 4); (void)hipDeviceSynchronize(); }
+  }
+  return 0;
+}
+
+int eosvos_label_components(eosvos_engine* e, const uint8_t* labels, int n_frames, int height, int width, int connectivity,
+                            int32_t* ids_out) {
+  if (!e || !labels || !ids_out) return fail("label_components: null argument");
+  if (ccl_check("label_components", n_frames, height, width, connectivity)) return 1;
+  if (n_frames == 0) return 0;
+  const size_t np = (size_t)n_frames * height * width;
+  if (ccl_scratch(e, "label_components", ((2 * np * sizeof(int)) + 3) / 4 * 4, n_frames)) return 1;
+  int* parent = (int*)e->ccl_buf;
+  launch_ccl_label(labels, n_frames, height, width, connectivity, parent, parent + np, ids_out, nullptr, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+
+int eosvos_filter_components(eosvos_engine* e, const uint8_t* labels, int n_frames, int height, int width, int connectivity,
+                             int min_area, int rel_q16, int largest_only, int gate, const uint8_t* prev, const uint8_t* keep,
+                             uint8_t* out, int64_t* removed_out) {
+  if (!e || !labels || !out) return fail("filter_components: null argument");
+  if (ccl_check("filter_components", n_frames, height, width, connectivity)) return 1;
+  if (gate < 0 || gate > 63) return fail("filter_components: gate must be in [0, 63] pixels");
+  if (min_area < 0) return fail("filter_components: min_area must be >= 0");
+  if (rel_q16 < 0 || rel_q16 > 65536) return fail("filter_components: rel_q16 must be in [0, 65536]");
+  if (n_frames == 0) return 0;
+  const size_t P = (size_t)height * width, np = (size_t)n_frames * P;
+  // [parent | tarea | ids | area] ints, [best: 256 per frame | removed: 1 per frame] 64-bit words, [cand: 1 per pixel |
+  // pres: 256 per frame and 256 for `prev`] bytes; everything from `area` on starts out as 0
+  const size_t words = (size_t)n_frames * 257, bytes = np + ((size_t)n_frames + 1) * 256;
+  const size_t need = (4 * np * sizeof(int) + words * 8 + bytes + 3) / 4 * 4;
+  if (ccl_scratch(e, "filter_components", need, n_frames)) return 1;
+  int* parent = (int*)e->ccl_buf;
+  int *tarea = parent + np, *ids = tarea + np, *area = ids + np;
+  unsigned long long* best = (unsigned long long*)(area + np);     // 16 * np bytes in: 8-byte aligned
+  unsigned long long* removed = best + (size_t)n_frames * 256;
+  uint8_t* cand = (uint8_t*)(removed + n_frames);
+  uint8_t* pres = cand + np;
+  HIPOK(hipMemsetAsync(area, 0, np * sizeof(int) + words * 8 + bytes, e->s));
+  launch_ccl_label(labels, n_frames, height, width, connectivity, parent, tarea, ids, area, e->s);
+  HIPOK(hipGetLastError());
+  auto kept = [&](int f) { return keep && keep[f] ? 1 : 0; };
+  if (gate > 0) {                        // frame by frame: the gate of a frame reads the filtered frame before it
+    if (prev) launch_ccl_presence(prev, (int)P, pres, e->s);
+    for (int f = 0; f < n_frames; ++f) {
+      const uint8_t* R = f == 0 ? prev : out + (size_t)(f - 1) * P;
+      const uint8_t* pres_f = R ? pres + (size_t)f * 256 : nullptr;
+      if (R && !kept(f)) launch_ccl_gate(labels + f * P, R, pres_f, ids + f * P, height, width, gate, cand + f * P, e->s);
+      launch_ccl_filter(labels + f * P, ids + f * P, area + f * P, pres_f, cand + f * P, kept(f), 1, (int)P, min_area,
+                        (unsigned)rel_q16, largest_only != 0, best + (size_t)f * 256, out + f * P, pres + (size_t)(f + 1) * 256,
+                        removed + f, e->s);
+      HIPOK(hipGetLastError());
+    }
+  } else {                               // no frame depends on another: one launch per run of frames with the same `keep` flag
+    for (int f = 0, g; f < n_frames; f = g) {
+      for (g = f + 1; g < n_frames && kept(g) == kept(f); ++g) {}
+      launch_ccl_filter(labels + f * P, ids + f * P, area + f * P, nullptr, cand + f * P, kept(f), g - f, (int)P, min_area,
+                        (unsigned)rel_q16, largest_only != 0, best + (size_t)f * 256, out + f * P, pres + (size_t)(f + 1) * 256,
+                        removed + f, e->s);
+      HIPOK(hipGetLastError());
+    }
+  }
+  if (removed_out) {
+    HIPOK(hipMemcpyAsync(removed_out, removed, (size_t)n_frames * sizeof(int64_t), hipMemcpyDeviceToHost, e->s));
+    HIPOK(hipStreamSynchronize(e->s));
   }
   return 0;
 }

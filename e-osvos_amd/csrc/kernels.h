@@ -1,4 +1,4 @@
-// Launcher declarations of the gfx950 kernels (conv_kernels.hip, misc_kernels.hip, crf_kernels.hip, ...).
+// Launcher declarations of the gfx950 kernels (conv_kernels.hip, misc_kernels.hip, crf_kernels.hip, ccl_kernels.hip, ...).
 // Host code (engine.cpp) only sees these plain-C++ functions; every launcher enqueues on
 // the given stream and never synchronises or allocates.
 #pragma once
@@ -409,6 +409,25 @@ void launch_crf_prepare(const float* probs, int n_frames, int n_obj, int64_t n_p
 void launch_crf_iteration(const float* images, const float* unary, const float* q_in, float* q_out, uint8_t* labels,
                           int n_frames, int n_lab, int H, int W, int r, int d, float w_a, float w_s, float theta_beta,
                           const CrfTables& tab, hipStream_t s);
+
+// Connected components of uint8 label maps and the component filter (ccl_kernels.hip; the rules: include/eosvos.h,
+// eosvos_label_components / eosvos_filter_components).  Maps are [frame][H][W]; H, W <= 4096, H * W < 2^24, frames <= 65535.
+// launch_ccl_label: ids [frame][H * W] = 1 + the smallest frame-local pixel index of the pixel's component (0: background);
+// parent / tarea: scratch of the same size; area (may be null; zeroed by the caller) receives at [root] the pixel count.
+// launch_ccl_presence: pres[256] (zeroed by the caller) = 1 for every non-zero value of `map`.
+// launch_ccl_gate (one frame): cand [H * W] (zeroed by the caller) = 1 at the root of every component with a pixel within
+// Chebyshev distance gate <= 63 of a pixel of R with its label, for the labels R contains (pres).
+// launch_ccl_filter: the area rules over the candidates (pres null: every component is one; pres is per launch, so with pres
+// the launch takes one frame) -> out, pres_out [frame][256] and removed [frame] (both zeroed by the caller); best
+// [frame][256] is zeroed scratch.  keep_all: the frames are copied unchanged (pres_out is still written).
+void launch_ccl_label(const uint8_t* labels, int n_frames, int H, int W, int connectivity, int* parent, int* tarea, int* ids,
+                      int* area, hipStream_t s);
+void launch_ccl_presence(const uint8_t* map, int n_pix, uint8_t* pres, hipStream_t s);
+void launch_ccl_gate(const uint8_t* labels, const uint8_t* R, const uint8_t* pres, const int* ids, int H, int W, int gate,
+                     uint8_t* cand, hipStream_t s);
+void launch_ccl_filter(const uint8_t* labels, const int* ids, const int* area, const uint8_t* pres, const uint8_t* cand,
+                       int keep_all, int n_frames, int n_pix, int min_area, unsigned rel_q16, int largest_only,
+                       unsigned long long* best, uint8_t* out, uint8_t* pres_out, unsigned long long* removed, hipStream_t s);
 
 // theta' = theta - lr[cout]*g, g = rowscale[cout] * sum_z ws[z][...]; optional gsum += g; g_out = g
 void launch_sgd_update(float* w, const float* ws, int splits, int64_t slab, const float* rowscale,

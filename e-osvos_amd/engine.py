@@ -604,6 +604,63 @@ class Engine:
                                                   p['theta_beta'], p['theta_gamma'], _ptr(out[f:g]), _optr(q[f:g] if return_q else None)))
         return (out, q) if return_q else out
 
+    def _check_label_maps(self, who, labels, prev=None):
+        from . import components
+        components._check_maps(who, labels, prev)
+        for t in (labels, prev):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.uint8):
+                raise ValueError(f'{who}: the label maps must be uint8 tensors on {self.device}')
+
+    def label_components(self, labels, connectivity=8):
+        """Component ids of label maps (`eosvos_label_components`; the rules: `components.py`).  labels (N, H, W) uint8 on the
+        engine's device, any H and W within the limits -> (N, H, W) int32: 1 + the smallest y * W + x of the pixel's component,
+        0 on background.  Nothing waits for the GPU; the frames go through in chunks under `components.SCRATCH_CAP`."""
+        from . import components
+        if connectivity not in (4, 8):
+            raise ValueError(f'label_components: connectivity={connectivity!r}: 4 or 8')
+        self._check_label_maps('label_components', labels)
+        self._check_stream()
+        labels = labels.contiguous()
+        n, h, w = labels.shape
+        ids = torch.empty(n, h, w, dtype=torch.int32, device=self.device)
+        step = components.frames_per_call(h, w)
+        for f in range(0, n, step):
+            g = min(f + step, n)
+            _ffi.check(self.lib.eosvos_label_components(self.h, _ptr(labels[f:g]), g - f, h, w, connectivity, _ptr(ids[f:g])))
+        return ids
+
+    def filter_components(self, labels, connectivity=8, min_area=0, min_rel_area=0.0, largest_only=False, gate=0, prev=None,
+                          keep=(), return_removed=False):
+        """The component filter of `components.py` (`eosvos_filter_components`).  labels (N, H, W) uint8 on the engine's
+        device in frame order, prev (H, W) uint8 or None, keep: frame indices copied unchanged -> filtered maps (N, H, W) uint8;
+        with `return_removed` also the pixels zeroed per frame as an (N,) int64 numpy array (this waits for the GPU).  The frames
+        go through in chunks under `components.SCRATCH_CAP`; a chunk's last filtered frame is the `prev` of the next."""
+        import numpy as np
+        from . import components
+        p = components.check(dict(connectivity=connectivity, min_area=min_area, min_rel_area=min_rel_area,
+                                  largest_only=largest_only, gate=gate))
+        self._check_label_maps('filter_components', labels, prev)
+        self._check_stream()
+        labels = labels.contiguous()
+        n, h, w = labels.shape
+        flags = bytearray(n)
+        for f in keep:
+            if 0 <= int(f) < n:
+                flags[int(f)] = 1
+        out = torch.empty_like(labels)
+        removed = np.zeros(n, dtype=np.int64)
+        rem_p = ctypes.POINTER(ctypes.c_int64)
+        step = components.frames_per_call(h, w)
+        prev = prev.contiguous() if prev is not None else None
+        for f in range(0, n, step):
+            g = min(f + step, n)
+            _ffi.check(self.lib.eosvos_filter_components(
+                self.h, _ptr(labels[f:g]), g - f, h, w, p['connectivity'], p['min_area'], components.rel_q16(p['min_rel_area']),
+                int(p['largest_only']), p['gate'], _optr(prev), bytes(flags[f:g]), _ptr(out[f:g]),
+                removed[f:g].ctypes.data_as(rem_p) if return_removed else None))
+            prev = out[g - 1]
+        return (out, removed) if return_removed else out
+
     # ---- meta-training ----------------------------------------------------------------
     def meta_task_begin(self):
         _ffi.check(self.lib.eosvos_meta_task_begin(self.h))

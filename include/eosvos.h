@@ -350,6 +350,48 @@ int eosvos_crf_labels(eosvos_engine* e, const float* images, const float* probs,
                       float w_smooth, float theta_alpha, float theta_beta, float theta_gamma,
                       uint8_t* labels_out, float* q_out);
 
+/* ---- connected-component clean-up of the merged label maps (after src/util/evaluate.py:322-326 and the CRF) ------ */
+/* The reference has no such step; the OSVOS family removes confident blobs on look-alikes after the fact (small components,
+ * all but the dominant component, components that do not continue the previous frame's mask).  An opt-in extension.
+ * labels: device uint8 maps [n_frames][height][width] of one sequence in frame order; 0 is background, every non-zero value
+ * an object label (no object count is needed).
+ *   components  two pixels of a frame are connected when they hold the same non-zero label and are neighbours under
+ *               `connectivity`: 4 = edge neighbours, 8 = edge and corner neighbours.  Pixels with different labels never
+ *               connect, frames never connect.  The id of a component is 1 + min(y * width + x) over its pixels, background
+ *               has id 0: the id map is unique.
+ *   filter      for frame f in ascending order, for every label o present in it:
+ *     1. gate (g = `gate` in 0..63, 0 = off).  R is the FILTERED output of frame f - 1; for the first frame of the call R is
+ *        `prev` (may be NULL: no R).  The gate is active for (f, o) when g > 0, R exists and R has at least one pixel equal
+ *        to o.  When active, a component is a candidate only if one of its pixels p has a pixel q with R[q] == o and
+ *        max(|px - qx|, |py - qy|) <= g (Chebyshev distance; outside the frame R counts as 0).  When inactive, every
+ *        component of o is a candidate.
+ *     2. area rules over the candidates of (f, o) only; A = a candidate's pixel count, Amax = the largest candidate count of
+ *        (f, o).  The candidate is kept iff  A >= min_area,  and  A * 65536 >= rel_q16 * Amax  (64-bit integers; rel_q16 =
+ *        round(min_rel_area * 65536) with min_rel_area in [0, 1], computed once by the caller),  and, if largest_only,
+ *        A == Amax and among those the candidate has the smallest id.
+ *     3. pixels of components that are not kept become 0, everything else is copied.
+ *   keep        (HOST memory, n_frames flags, may be NULL) frames flagged there -- the train frames, whose map is the seeded
+ *               ground truth -- are copied unchanged; they still serve as R of the frame after them.
+ * eosvos_label_components writes the id map (device int32 [n_frames][height][width]); eosvos_filter_components writes the
+ * filtered maps to `out` (device, not overlapping `labels`) and, if removed_out (HOST memory, n_frames values) is not NULL,
+ * the number of pixels zeroed per frame -- it then synchronises the engine's stream; otherwise both are asynchronous on
+ * the engine's stream.  `e` lends its stream and scratch memory only; frames of any size within the limits.
+ * Launches (csrc/ccl_kernels.hip): union-find labelling in three (64 x 16 tiles in LDS, tile seams by atomicMin, flatten
+ * + areas with one atomic per tile-local root); then with the gate per frame gate flags / largest candidate / apply, without
+ * it one such pair for all frames.  No launch is cooperative and no workgroup waits for another; parent[i] <= i holds at
+ * all times, so every loop walks strictly downward and ends.  Integer arithmetic only: results are exact and independent
+ * of arrival order.  Scratch: 8 bytes per pixel for the id map, 17 bytes per pixel (+ 2312 per frame) for the filter,
+ * allocated on first use, growing only, at most 512 MB per call -- a call that needs more is rejected (pass fewer
+ * frames per call and the last filtered frame as `prev` of the next).
+ * Rejected without a launch: a null pointer (prev, keep, removed_out excepted), height or width < 1 or > 4096,
+ * height * width >= 2^24, connectivity not 4 or 8, gate outside [0, 63], min_area < 0, rel_q16 outside [0, 65536], more
+ * than 65535 frames. */
+int eosvos_label_components(eosvos_engine* e, const uint8_t* labels, int n_frames, int height, int width, int connectivity,
+                            int32_t* ids_out);
+int eosvos_filter_components(eosvos_engine* e, const uint8_t* labels, int n_frames, int height, int width, int connectivity,
+                             int min_area, int rel_q16, int largest_only, int gate, const uint8_t* prev, const uint8_t* keep,
+                             uint8_t* out, int64_t* removed_out);
+
 /* ---- learning-rate hierarchy (meta_optim.py:27-67) ------------------------------------ */
 /* `lr_hierarchy_level`: how the learned lr state is stored.  NEURON (cfgs/meta.yaml:36) one
  * value per output channel; TENSOR one per trainable tensor (`log_init_lr` of shape
