@@ -80,6 +80,8 @@ _SIGNATURES = {
     'eosvos_label_components': (ctypes.c_int, [_E, ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
     'eosvos_filter_components': (ctypes.c_int, [_E, ctypes.c_void_p] + [ctypes.c_int] * 8 +
                                  [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
+    'eosvos_fill_holes': (ctypes.c_int, [_E, ctypes.c_void_p] + [ctypes.c_int] * 7 +
+                          [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'eosvos_set_norm': (ctypes.c_int, [_E, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_float]),
     'eosvos_reset': (ctypes.c_int, [_E]),
     'eosvos_get_params': (ctypes.c_int, [_E, c_float_p]),

@@ -126,6 +126,16 @@ CLEANUP = {
 }
 
 
+# Hole filling of the evaluation's label maps, handled like EXTENSIONS, POSTPROCESS and CLEANUP (not part of BASE, added by
+# `parse_cli` only when the command line sets one of its keys: `eval_holes.max_area=64 eval_holes.prev_overlap=0.5` -- example
+# values, untuned; read with `cfg.get(...)`).
+#   eval_holes        enclosed background islands are filled after the component filter (`holes.py`); the value below is the
+#                     neutral one (`holes.DEFAULTS`: max_area 0, nothing is filled, nothing new is called)
+FILL = {
+    'eval_holes': {'connectivity': 8, 'max_area': 0, 'max_rel_area': 1.0, 'prev_overlap': 0.0},
+}
+
+
 def _merge(dst, src):
     for k, v in src.items():
         if isinstance(v, dict) and isinstance(dst.get(k), dict):
@@ -172,7 +182,7 @@ def parse_cli(argv):
             raise KeyError(f'unknown named config: {a}')
     for k, v in updates:
         group = k.split('.')[0]
-        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP):
+        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL):
             if group in groups and group not in cfg:
                 cfg[group] = copy.deepcopy(groups[group])
         _set_dotted(cfg, k, v)
@@ -185,6 +195,9 @@ def parse_cli(argv):
     if 'eval_components' in cfg:
         from .components import check as check_components
         check_components(cfg['eval_components'])            # ValueError: gate 64, connectivity 6, ...
+    if 'eval_holes' in cfg:
+        from .holes import check as check_holes
+        check_holes(cfg['eval_holes'])                      # ValueError: max_area -1, prev_overlap 1.5, ...
     unsupported(cfg)
     return cfg
 

@@ -18,6 +18,12 @@
 //   ccl_best_kernel     best[o] = max over the candidates of (area << 32) | ~id : the largest area, ties to the smallest id
 //   ccl_apply_kernel    the three area rules; writes the filtered map, the labels it contains (the next frame's `pres`) and the
 //                       number of pixels zeroed
+// and, for the hole filler (eosvos_fill_holes, eosvos_amd/holes.py: fill_host), the same three labelling kernels over the ZERO
+// pixels under the dual connectivity, then
+//   hole_scan_kernel    every zero pixel merges its border flag and its non-zero neighbours into its root's record; the frame's
+//                       label histogram
+//   hole_overlap_kernel per frame, only with the previous-frame rule: how many pixels of a candidate hole were its label in R
+//   hole_apply_kernel   the size and overlap rules; writes the filled map, the labels it contains and the pixels filled
 // No launch is cooperative, no workgroup waits for another, no loop's exit depends on another workgroup's progress: other
 // workgroups can only LOWER a parent slot, and every loop below makes progress by reading a strictly smaller index than
 // before.  The bound of every loop is stated at the loop.  All sums, maxima and flags are integers: arrival order cannot
@@ -75,7 +81,13 @@ __device__ __forceinline__ u64 ccl_spread(u64 lo, u64 c, u64 hi, int k) {
 }
 
 // ---- labelling --------------------------------------------------------------------------------------------------------
+// ZERO: the hole filler's labelling of the BACKGROUND -- a pixel counts as label 1 where the map holds 0 and as background where
+// it holds an object label; the three kernels are otherwise the same code, and the <false> instances are the ones they were.
+template <bool ZERO>
+__device__ __forceinline__ int ccl_value(int raw) { return ZERO ? (raw == 0 ? 1 : 0) : raw; }
+
 // grid (ceil(W / 64), ceil(H / 16), frames), block 256
+template <bool ZERO>
 __global__ __launch_bounds__(256) void ccl_tile_kernel(const uint8_t* __restrict__ labels, int H, int W, int conn8,
                                                         int* __restrict__ parent, int* __restrict__ tarea) {
   __shared__ int s_par[CCL_TILE];
@@ -94,7 +106,7 @@ __global__ __launch_bounds__(256) void ccl_tile_kernel(const uint8_t* __restrict
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int r = wave + 4 * k, y = y0 + r;
-    const int L = (x < W && y < H) ? labels[(size_t)y * W + x] : 0;          // 0 outside the frame: joins nothing
+    const int L = (x < W && y < H) ? ccl_value<ZERO>(labels[(size_t)y * W + x]) : 0;   // 0 outside the frame: joins nothing
     const int left = __shfl_up(L, 1);
     const u64 m = __ballot(lane > 0 && L != 0 && L == left);
     const u64 upto = lane == 63 ? ~0ull : ((2ull << lane) - 1);               // bits 0 .. lane
@@ -146,6 +158,7 @@ __global__ __launch_bounds__(256) void ccl_tile_kernel(const uint8_t* __restrict
 }
 
 // grid (ceil(H * W / 256), frames), block 256.  Pixels whose neighbour to the left / above / at an upper corner lies in another tile.
+template <bool ZERO>
 __global__ __launch_bounds__(256) void ccl_seam_kernel(const uint8_t* __restrict__ labels, int H, int W, int conn8,
                                                         int* __restrict__ parent) {
   const int n_pix = H * W;
@@ -156,23 +169,24 @@ __global__ __launch_bounds__(256) void ccl_seam_kernel(const uint8_t* __restrict
   if (!(col0 || row0 || (conn8 && col63))) return;
   labels += (size_t)blockIdx.y * n_pix;
   parent += (size_t)blockIdx.y * n_pix;
-  const int L = labels[p];
+  const int L = ccl_value<ZERO>(labels[p]);
   if (L == 0) return;
-  if (col0 && x > 0 && labels[p - 1] == L) ccl_union(parent, p, p - 1);
+  if (col0 && x > 0 && ccl_value<ZERO>(labels[p - 1]) == L) ccl_union(parent, p, p - 1);
   if (y == 0) return;
-  if (row0 && labels[p - W] == L) ccl_union(parent, p, p - W);
+  if (row0 && ccl_value<ZERO>(labels[p - W]) == L) ccl_union(parent, p, p - W);
   if (!conn8) return;
-  if ((col0 || row0) && x > 0 && labels[p - W - 1] == L) ccl_union(parent, p, p - W - 1);
-  if ((col63 || row0) && x + 1 < W && labels[p - W + 1] == L) ccl_union(parent, p, p - W + 1);
+  if ((col0 || row0) && x > 0 && ccl_value<ZERO>(labels[p - W - 1]) == L) ccl_union(parent, p, p - W - 1);
+  if ((col63 || row0) && x + 1 < W && ccl_value<ZERO>(labels[p - W + 1]) == L) ccl_union(parent, p, p - W + 1);
 }
 
 // grid (ceil(H * W / 256), frames), block 256.  area: zeroed by the caller.
+template <bool ZERO>
 __global__ __launch_bounds__(256) void ccl_flatten_kernel(const uint8_t* __restrict__ labels, int n_pix, const int* __restrict__ parent,
                                                            const int* __restrict__ tarea, int* __restrict__ ids, int* __restrict__ area) {
   const int p = (int)(blockIdx.x * 256u + threadIdx.x);
   if (p >= n_pix) return;
   const size_t base = (size_t)blockIdx.y * n_pix;
-  if (labels[base + p] == 0) { ids[base + p] = 0; return; }
+  if (ccl_value<ZERO>(labels[base + p]) == 0) { ids[base + p] = 0; return; }
   const int root = ccl_find(parent + base, p);
   ids[base + p] = root + 1;
   if (area) {
@@ -281,16 +295,202 @@ __global__ __launch_bounds__(256) void ccl_apply_kernel(const uint8_t* __restric
   __syncthreads();
   if (threadIdx.x == 0 && s_removed) atomicAdd(removed + f, (u64)s_removed);
 }
+
+// ---- hole filling (eosvos_fill_holes; the rules: include/eosvos.h, the numpy twin: eosvos_amd/holes.py) ------------------
+// The background is labelled by the three kernels above in their ZERO form under the dual connectivity; ids[p] - 1 is then the
+// root of a zero pixel's background component and area[root] its pixel count A.  Per root one 32-bit record:
+//   bit 16       a pixel of the component lies on the frame border
+//   bits 8..15   255 - the smallest non-zero neighbour label seen
+//   bits 0..7    the largest non-zero neighbour label seen (0: none yet)
+// All three fields only grow, and merging two records is the field-wise maximum.  A record is DEAD once the border bit is set or
+// the two labels differ: the component is then no candidate whatever else arrives, and nobody stores to it any more.
+constexpr unsigned HOLE_BORDER = 1u << 16;
+
+__device__ __forceinline__ unsigned hole_merge(unsigned a, unsigned b) {
+  const unsigned hi = max(a & 0xffu, b & 0xffu), lo = max(a & 0xff00u, b & 0xff00u);
+  return ((a | b) & HOLE_BORDER) | lo | hi;
+}
+__device__ __forceinline__ unsigned hole_word(int label) { return ((255u - (unsigned)label) << 8) | (unsigned)label; }   // label != 0
+__device__ __forceinline__ bool hole_dead(unsigned r) {
+  return (r & HOLE_BORDER) || ((r & 0xffu) && 255u - ((r >> 8) & 0xffu) != (r & 0xffu));
+}
+// the label a finished record makes its component a candidate for; 0: none (border, several labels)
+__device__ __forceinline__ int hole_label(unsigned r) { return hole_dead(r) ? 0 : (int)(r & 0xffu); }
+
+// Merges v into *slot.  The plain read first spares the atomic where the stored record is dead or already dominates v (both are
+// monotone, so a stale read can only cost a spared atomic, never a result).  Loop bound: a retry happens only when another
+// thread's compare-and-swap changed the word in between; a live word has seen at most one label, so it changes at most twice
+// (first label; border bit or second label, after which it is dead and nobody stores): at most 3 passes.  A retry is another
+// thread's completed store, never a wait for one.
+__device__ __forceinline__ void hole_update(unsigned* slot, unsigned v) {
+  unsigned cur = __atomic_load_n(slot, __ATOMIC_RELAXED);
+  for (;;) {
+    if (hole_dead(cur)) return;
+    const unsigned nw = hole_merge(cur, v);
+    if (nw == cur) return;
+    const unsigned old = atomicCAS(slot, cur, nw);
+    if (old == cur) return;
+    cur = old;
+  }
+}
+
+__device__ __forceinline__ bool hole_size_ok(int A, unsigned S, int max_area, unsigned rel_q16) {
+  return A <= max_area && (u64)(unsigned)A * 65536ull <= (u64)rel_q16 * (u64)S;
+}
+
+// (a) grid (ceil(H * W / 256), frames), block 256.  rec [frame][H * W] and hist [frame][256]: zeroed by the caller.  Every zero
+// pixel merges its border flag and its non-zero neighbours (under the background's connectivity, bg8) into its root's record;
+// every non-zero pixel counts in the frame's label histogram (S of the size rule).  No thread leaves before the end: the
+// ballots and shuffles below see whole waves.
+__global__ __launch_bounds__(256) void hole_scan_kernel(const uint8_t* __restrict__ labels, const int* __restrict__ ids, int H, int W,
+                                                         int bg8, unsigned* __restrict__ rec, unsigned* __restrict__ hist) {
+  __shared__ unsigned s_hist[256];
+  s_hist[threadIdx.x] = 0;
+  __syncthreads();
+  const int n_pix = H * W, lane = threadIdx.x & 63;
+  const int p = (int)(blockIdx.x * 256u + threadIdx.x);
+  const size_t base = (size_t)blockIdx.y * n_pix;
+  labels += base;
+  int L = -1, root = -1;
+  unsigned c = 0;
+  if (p < n_pix) {
+    L = labels[p];
+    if (L == 0) {
+      const int y = p / W, x = p - y * W;
+      root = ids[base + p] - 1;
+      if (x == 0 || y == 0 || x == W - 1 || y == H - 1) c = HOLE_BORDER;
+      const bool l = x > 0, r = x + 1 < W, u = y > 0, d = y + 1 < H;      // every read below is inside the frame
+      int v;
+      if (l && (v = labels[p - 1])) c = hole_merge(c, hole_word(v));
+      if (r && (v = labels[p + 1])) c = hole_merge(c, hole_word(v));
+      if (u && (v = labels[p - W])) c = hole_merge(c, hole_word(v));
+      if (d && (v = labels[p + W])) c = hole_merge(c, hole_word(v));
+      if (bg8) {
+        if (u && l && (v = labels[p - W - 1])) c = hole_merge(c, hole_word(v));
+        if (u && r && (v = labels[p - W + 1])) c = hole_merge(c, hole_word(v));
+        if (d && l && (v = labels[p + W - 1])) c = hole_merge(c, hole_word(v));
+        if (d && r && (v = labels[p + W + 1])) c = hole_merge(c, hole_word(v));
+      }
+    }
+  }
+  // histogram: one LDS add per (wave, distinct label), not one per pixel -- an object fills whole waves with one label.
+  // Loop bound: every pass clears at least the bit it took the label from: <= 64 passes.
+  u64 rem = __ballot(L > 0);
+  while (rem) {
+    const int o = __shfl(L, __ffsll((long long)rem) - 1);
+    const u64 mine = __ballot(L == o);
+    rem &= ~mine;
+    if (lane == 0) atomicAdd(s_hist + o, (unsigned)__popcll(mine));
+  }
+  // records: lanes whose root's record is dead or dominates their word already drop out on a plain read -- almost every pixel
+  // of the "outside" component, whose record dies with the first border pixel that arrives; the rest go one atomic per
+  // (wave, distinct root), the lanes of a root merged by a butterfly first.  Loop bound: as above, <= 64 passes of 6 shuffles.
+  bool todo = root >= 0 && c != 0;
+  if (todo) {
+    const unsigned cur = __atomic_load_n(rec + base + root, __ATOMIC_RELAXED);
+    if (hole_dead(cur) || hole_merge(cur, c) == cur) todo = false;
+  }
+  rem = __ballot(todo);
+  while (rem) {
+    const int r0 = __shfl(root, __ffsll((long long)rem) - 1);
+    const bool mine = todo && root == r0;
+    const u64 m = __ballot(mine);
+    rem &= ~m;
+    unsigned v = mine ? c : 0u;
+#pragma unroll
+    for (int sft = 32; sft; sft >>= 1) v = hole_merge(v, (unsigned)__shfl_xor((int)v, sft));
+    if (lane == __ffsll((long long)m) - 1) hole_update(rec + base + r0, v);
+  }
+  __syncthreads();
+  const unsigned h = s_hist[threadIdx.x];                                // one global atomic per (workgroup, label present in it)
+  if (h) atomicAdd(hist + (size_t)blockIdx.y * 256 + threadIdx.x, h);
+}
+
+// (b) one frame; grid (ceil(H * W / 256)), block 256.  Launched only where the previous-frame rule can be active (overlap_q16 > 0
+// and R exists).  cnt [H * W]: zeroed by the caller; cnt[root] = C, the pixels p of the hole with R[p] == o, for the holes that
+// are candidates of a label o that R contains (pres) and that pass the size rule -- the others are never read.  One atomic per
+// (wave, distinct root) with the wave's count: a hole receives one add per wave it has a pixel in, not one per pixel.
+// Loop bound: every pass clears at least one bit: <= 64 passes.
+__global__ __launch_bounds__(256) void hole_overlap_kernel(const uint8_t* __restrict__ labels, const uint8_t* __restrict__ R,
+                                                            const uint8_t* __restrict__ pres, const int* __restrict__ ids,
+                                                            const int* __restrict__ area, const unsigned* __restrict__ rec,
+                                                            const unsigned* __restrict__ hist, int n_pix, int max_area,
+                                                            unsigned rel_q16, unsigned* __restrict__ cnt) {
+  const int p = (int)(blockIdx.x * 256u + threadIdx.x), lane = threadIdx.x & 63;
+  int root = -1;
+  bool hit = false;
+  if (p < n_pix && labels[p] == 0) {
+    root = ids[p] - 1;
+    const int o = hole_label(rec[root]);
+    hit = o != 0 && pres[o] && R[p] == o && hole_size_ok(area[root], hist[o], max_area, rel_q16);
+  }
+  u64 rem = __ballot(hit);
+  while (rem) {
+    const int r0 = __shfl(root, __ffsll((long long)rem) - 1);
+    const u64 m = __ballot(hit && root == r0);
+    rem &= ~m;
+    if (lane == __ffsll((long long)m) - 1) atomicAdd(cnt + r0, (unsigned)__popcll(m));
+  }
+}
+
+// (c) grid (ceil(H * W / 256), frames), block 256.  pres: the labels R contains, null where the previous-frame rule is inactive
+// for every label (overlap_q16 == 0 or no R; only then may frames > 1).  keep_all: the frames are copied unchanged.  pres_out
+// [frame][256] and filled [frame]: zeroed by the caller.  Pixels filled: one LDS add per wave, one global atomic per workgroup.
+__global__ __launch_bounds__(256) void hole_apply_kernel(const uint8_t* __restrict__ labels, const int* __restrict__ ids,
+                                                          const int* __restrict__ area, const unsigned* __restrict__ rec,
+                                                          const unsigned* __restrict__ hist, const unsigned* __restrict__ cnt,
+                                                          const uint8_t* __restrict__ pres, int keep_all, int n_pix, int max_area,
+                                                          unsigned rel_q16, unsigned overlap_q16, uint8_t* __restrict__ out,
+                                                          uint8_t* __restrict__ pres_out, u64* __restrict__ filled) {
+  __shared__ unsigned s_filled;
+  if (threadIdx.x == 0) s_filled = 0;
+  __syncthreads();
+  const int p = (int)(blockIdx.x * 256u + threadIdx.x);
+  const int f = blockIdx.y;
+  const size_t base = (size_t)f * n_pix;
+  bool fill = false;
+  if (p < n_pix) {
+    int v = labels[base + p];
+    if (v == 0 && !keep_all) {
+      const int root = ids[base + p] - 1;
+      const int o = hole_label(rec[base + root]);
+      if (o != 0) {
+        const int A = area[base + root];
+        bool ok = hole_size_ok(A, hist[(size_t)f * 256 + o], max_area, rel_q16);
+        if (ok && pres != nullptr && pres[o])
+          ok = (u64)cnt[base + root] * 65536ull >= (u64)overlap_q16 * (u64)(unsigned)A;
+        if (ok) { v = o; fill = true; }
+      }
+    }
+    out[base + p] = (uint8_t)v;
+    if (v && !pres_out[(size_t)f * 256 + v]) pres_out[(size_t)f * 256 + v] = 1;
+  }
+  const u64 z = __ballot(fill);
+  if ((threadIdx.x & 63) == 0 && z) atomicAdd(&s_filled, (unsigned)__popcll(z));
+  __syncthreads();
+  if (threadIdx.x == 0 && s_filled) atomicAdd(filled + f, (u64)s_filled);
+}
 }  // namespace
 
-void launch_ccl_label(const uint8_t* labels, int n_frames, int H, int W, int connectivity, int* parent, int* tarea, int* ids,
+template <bool ZERO>
+static void ccl_label(const uint8_t* labels, int n_frames, int H, int W, int connectivity, int* parent, int* tarea, int* ids,
                       int* area, hipStream_t s) {
   const int conn8 = connectivity == 8, n_pix = H * W;
   const dim3 per_pixel((n_pix + 255) / 256, n_frames);
-  hipLaunchKernelGGL(ccl_tile_kernel, dim3((W + CCL_TW - 1) / CCL_TW, (H + CCL_TH - 1) / CCL_TH, n_frames), dim3(256), 0, s,
+  hipLaunchKernelGGL(ccl_tile_kernel<ZERO>, dim3((W + CCL_TW - 1) / CCL_TW, (H + CCL_TH - 1) / CCL_TH, n_frames), dim3(256), 0, s,
                      labels, H, W, conn8, parent, tarea);
-  hipLaunchKernelGGL(ccl_seam_kernel, per_pixel, dim3(256), 0, s, labels, H, W, conn8, parent);
-  hipLaunchKernelGGL(ccl_flatten_kernel, per_pixel, dim3(256), 0, s, labels, n_pix, (const int*)parent, (const int*)tarea, ids, area);
+  hipLaunchKernelGGL(ccl_seam_kernel<ZERO>, per_pixel, dim3(256), 0, s, labels, H, W, conn8, parent);
+  hipLaunchKernelGGL(ccl_flatten_kernel<ZERO>, per_pixel, dim3(256), 0, s, labels, n_pix, (const int*)parent, (const int*)tarea, ids, area);
+}
+
+void launch_ccl_label(const uint8_t* labels, int n_frames, int H, int W, int connectivity, int* parent, int* tarea, int* ids,
+                      int* area, hipStream_t s) {
+  ccl_label<false>(labels, n_frames, H, W, connectivity, parent, tarea, ids, area, s);
+}
+
+void launch_ccl_label_zero(const uint8_t* labels, int n_frames, int H, int W, int connectivity, int* parent, int* tarea, int* ids,
+                           int* area, hipStream_t s) {
+  ccl_label<true>(labels, n_frames, H, W, connectivity, parent, tarea, ids, area, s);
 }
 
 void launch_ccl_presence(const uint8_t* map, int n_pix, uint8_t* pres, hipStream_t s) {
@@ -309,5 +509,26 @@ void launch_ccl_filter(const uint8_t* labels, const int* ids, const int* area, c
   if (!keep_all) hipLaunchKernelGGL(ccl_best_kernel, grid, dim3(256), 0, s, labels, ids, area, pres, cand, n_pix, best);
   hipLaunchKernelGGL(ccl_apply_kernel, grid, dim3(256), 0, s, labels, ids, area, pres, cand, (const u64*)best, keep_all, n_pix, min_area,
                      rel_q16, largest_only, out, pres_out, removed);
+}
+
+void launch_hole_scan(const uint8_t* labels, const int* ids, int n_frames, int H, int W, int connectivity, unsigned* rec,
+                      unsigned* hist, hipStream_t s) {
+  hipLaunchKernelGGL(hole_scan_kernel, dim3((H * W + 255) / 256, n_frames), dim3(256), 0, s, labels, ids, H, W,
+                     connectivity == 4 ? 1 : 0, rec, hist);       // objects 4-connected: the background is 8-connected
+}
+
+void launch_hole_overlap(const uint8_t* labels, const uint8_t* R, const uint8_t* pres, const int* ids, const int* area,
+                         const unsigned* rec, const unsigned* hist, int n_pix, int max_area, unsigned rel_q16, unsigned* cnt,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(hole_overlap_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, s, labels, R, pres, ids, area, rec, hist, n_pix,
+                     max_area, rel_q16, cnt);
+}
+
+void launch_hole_apply(const uint8_t* labels, const int* ids, const int* area, const unsigned* rec, const unsigned* hist,
+                       const unsigned* cnt, const uint8_t* pres, int keep_all, int n_frames, int n_pix, int max_area,
+                       unsigned rel_q16, unsigned overlap_q16, uint8_t* out, uint8_t* pres_out, unsigned long long* filled,
+                       hipStream_t s) {
+  hipLaunchKernelGGL(hole_apply_kernel, dim3((n_pix + 255) / 256, n_frames), dim3(256), 0, s, labels, ids, area, rec, hist, cnt, pres,
+                     keep_all, n_pix, max_area, rel_q16, overlap_q16, out, pres_out, filled);
 }
 }  // namespace eosvos

@@ -208,7 +208,7 @@ struct eosvos_engine {
   size_t davis_cap = 0;
   void* crf_buf = nullptr;              // eosvos_crf_labels: unary + the two Q planes of the mean field (grow-only, freed by destroy)
   size_t crf_cap = 0;
-  void* ccl_buf = nullptr;              // eosvos_label_components / eosvos_filter_components: union-find, ids, areas, flags (grow-only, freed by destroy)
+  void* ccl_buf = nullptr;              // eosvos_label_components / eosvos_filter_components / eosvos_fill_holes: union-find, ids, areas, flags (grow-only, freed by destroy)
   size_t ccl_cap = 0;
   int lr_level = EOSVOS_LR_NEURON, lr_log = 0;
   float *lr_elem = nullptr, *glr_tmp = nullptr, *ptmp = nullptr;
@@ -2866,6 +2866,65 @@ int eosvos_filter_components(eosvos_engine* e, const uint8_t* labels, int n_fram
   }
   if (removed_out) {
     HIPOK(hipMemcpyAsync(removed_out, removed, (size_t)n_frames * sizeof(int64_t), hipMemcpyDeviceToHost, e->s));
+    HIPOK(hipStreamSynchronize(e->s));
+  }
+  return 0;
+}
+
+// ---- hole filling of the merged label maps (after the component filter) ------------------------------------------------
+int eosvos_fill_holes(eosvos_engine* e, const uint8_t* labels, int n_frames, int height, int width, int connectivity,
+                      int max_area, int rel_q16, int overlap_q16, const uint8_t* prev, const uint8_t* keep, uint8_t* out,
+                      int64_t* filled_out) {
+  if (!e || !labels || !out) return fail("fill_holes: null argument");
+  if (ccl_check("fill_holes", n_frames, height, width, connectivity)) return 1;
+  if (max_area < 0 || max_area > (1 << 24)) return fail("fill_holes: max_area must be in [0, 2^24]");
+  if (rel_q16 < 0 || rel_q16 > 65536) return fail("fill_holes: rel_q16 must be in [0, 65536]");
+  if (overlap_q16 < 0 || overlap_q16 > 65536) return fail("fill_holes: overlap_q16 must be in [0, 65536]");
+  if (n_frames == 0) return 0;
+  const size_t P = (size_t)height * width, np = (size_t)n_frames * P;
+  // [parent | tarea | ids | area | rec | cnt] 32-bit words per pixel, [hist: 256 per frame] 32-bit words, pad to 8 bytes,
+  // [filled: 1 per frame] 64-bit words, [pres: 256 per frame and 256 for `prev`] bytes; everything from `area` on starts out as 0
+  const size_t words = 6 * np + (size_t)n_frames * 256;
+  const size_t filled_at = (words * 4 + 7) / 8 * 8;
+  const size_t need = filled_at + (size_t)n_frames * 8 + ((size_t)n_frames + 1) * 256;
+  if (ccl_scratch(e, "fill_holes", need, n_frames)) return 1;
+  int* parent = (int*)e->ccl_buf;
+  int *tarea = parent + np, *ids = tarea + np, *area = ids + np;
+  unsigned *rec = (unsigned*)(area + np), *cnt = rec + np, *hist = cnt + np;
+  unsigned long long* filled = (unsigned long long*)((char*)e->ccl_buf + filled_at);
+  uint8_t* pres = (uint8_t*)(filled + n_frames);
+  HIPOK(hipMemsetAsync(area, 0, need - 3 * np * sizeof(int), e->s));
+  auto kept = [&](int f) { return keep && keep[f] ? 1 : 0; };
+  const bool off = max_area == 0 || rel_q16 == 0;                  // no hole can pass the size rule: every frame is copied
+  if (!off) {
+    launch_ccl_label_zero(labels, n_frames, height, width, connectivity == 8 ? 4 : 8, parent, tarea, ids, area, e->s);
+    launch_hole_scan(labels, ids, n_frames, height, width, connectivity, rec, hist, e->s);
+    HIPOK(hipGetLastError());
+  }
+  if (!off && overlap_q16 > 0) {         // frame by frame: the rule of a frame reads the filled frame before it
+    if (prev) launch_ccl_presence(prev, (int)P, pres, e->s);
+    for (int f = 0; f < n_frames; ++f) {
+      const uint8_t* R = f == 0 ? prev : out + (size_t)(f - 1) * P;
+      const uint8_t* pres_f = R ? pres + (size_t)f * 256 : nullptr;
+      if (R && !kept(f))
+        launch_hole_overlap(labels + f * P, R, pres_f, ids + f * P, area + f * P, rec + f * P, hist + (size_t)f * 256, (int)P, max_area,
+                            (unsigned)rel_q16, cnt + f * P, e->s);
+      launch_hole_apply(labels + f * P, ids + f * P, area + f * P, rec + f * P, hist + (size_t)f * 256, cnt + f * P, pres_f, kept(f), 1,
+                        (int)P, max_area, (unsigned)rel_q16, (unsigned)overlap_q16, out + f * P, pres + (size_t)(f + 1) * 256,
+                        filled + f, e->s);
+      HIPOK(hipGetLastError());
+    }
+  } else {                               // no frame depends on another: one launch per run of frames with the same `keep` flag
+    for (int f = 0, g; f < n_frames; f = g) {
+      for (g = f + 1; g < n_frames && (off || kept(g) == kept(f)); ++g) {}
+      launch_hole_apply(labels + f * P, ids + f * P, area + f * P, rec + f * P, hist + (size_t)f * 256, cnt + f * P, nullptr,
+                        off || kept(f), g - f, (int)P, max_area, (unsigned)rel_q16, 0u, out + f * P, pres + (size_t)(f + 1) * 256,
+                        filled + f, e->s);
+      HIPOK(hipGetLastError());
+    }
+  }
+  if (filled_out) {
+    HIPOK(hipMemcpyAsync(filled_out, filled, (size_t)n_frames * sizeof(int64_t), hipMemcpyDeviceToHost, e->s));
     HIPOK(hipStreamSynchronize(e->s));
   }
   return 0;

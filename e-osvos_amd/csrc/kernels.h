@@ -429,6 +429,27 @@ void launch_ccl_filter(const uint8_t* labels, const int* ids, const int* area, c
                        int keep_all, int n_frames, int n_pix, int min_area, unsigned rel_q16, int largest_only,
                        unsigned long long* best, uint8_t* out, uint8_t* pres_out, unsigned long long* removed, hipStream_t s);
 
+// Hole filling of uint8 label maps (ccl_kernels.hip; the rules: include/eosvos.h, eosvos_fill_holes).
+// launch_ccl_label_zero: launch_ccl_label over the pixels that hold 0 (one label; object pixels are its background): ids =
+// 1 + root of a zero pixel's background component, area[root] = its pixel count.  Pass the BACKGROUND's connectivity.
+// launch_hole_scan: rec [frame][H * W] (per root: border bit, smallest and largest non-zero neighbour label) and hist
+// [frame][256] (pixels per label), both zeroed by the caller; `connectivity` is the OBJECTS' (4: corner neighbours count).
+// launch_hole_overlap (one frame): cnt [H * W] (zeroed by the caller) at [root] = pixels of the hole that hold its label in R,
+// for holes that are candidates of a label R contains (pres) and pass the size rule.
+// launch_hole_apply: the size rule and, with pres (per launch, so one frame), the overlap rule -> out, pres_out [frame][256]
+// and filled [frame] (both zeroed by the caller).  keep_all: the frames are copied unchanged (pres_out is still written).
+void launch_ccl_label_zero(const uint8_t* labels, int n_frames, int H, int W, int connectivity, int* parent, int* tarea, int* ids,
+                           int* area, hipStream_t s);
+void launch_hole_scan(const uint8_t* labels, const int* ids, int n_frames, int H, int W, int connectivity, unsigned* rec,
+                      unsigned* hist, hipStream_t s);
+void launch_hole_overlap(const uint8_t* labels, const uint8_t* R, const uint8_t* pres, const int* ids, const int* area,
+                         const unsigned* rec, const unsigned* hist, int n_pix, int max_area, unsigned rel_q16, unsigned* cnt,
+                         hipStream_t s);
+void launch_hole_apply(const uint8_t* labels, const int* ids, const int* area, const unsigned* rec, const unsigned* hist,
+                       const unsigned* cnt, const uint8_t* pres, int keep_all, int n_frames, int n_pix, int max_area,
+                       unsigned rel_q16, unsigned overlap_q16, uint8_t* out, uint8_t* pres_out, unsigned long long* filled,
+                       hipStream_t s);
+
 // theta' = theta - lr[cout]*g, g = rowscale[cout] * sum_z ws[z][...]; optional gsum += g; g_out = g
 void launch_sgd_update(float* w, const float* ws, int splits, int64_t slab, const float* rowscale,
                        const float* lr, float* gsum, float* gout, int64_t rowlen, int64_t n,

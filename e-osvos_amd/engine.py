@@ -661,6 +661,37 @@ class Engine:
             prev = out[g - 1]
         return (out, removed) if return_removed else out
 
+    def fill_holes(self, labels, connectivity=8, max_area=0, max_rel_area=1.0, prev_overlap=0.0, prev=None, keep=(),
+                   return_filled=False):
+        """The hole filler of `holes.py` (`eosvos_fill_holes`).  labels (N, H, W) uint8 on the engine's device in frame order,
+        prev (H, W) uint8 or None, keep: frame indices copied unchanged -> filled maps (N, H, W) uint8; with `return_filled`
+        also the pixels filled per frame as an (N,) int64 numpy array (this waits for the GPU).  The frames go through in chunks
+        under `holes.SCRATCH_CAP`; a chunk's last filled frame is the `prev` of the next."""
+        import numpy as np
+        from . import holes
+        p = holes.check(dict(connectivity=connectivity, max_area=max_area, max_rel_area=max_rel_area, prev_overlap=prev_overlap))
+        self._check_label_maps('fill_holes', labels, prev)
+        self._check_stream()
+        labels = labels.contiguous()
+        n, h, w = labels.shape
+        flags = bytearray(n)
+        for f in keep:
+            if 0 <= int(f) < n:
+                flags[int(f)] = 1
+        out = torch.empty_like(labels)
+        filled = np.zeros(n, dtype=np.int64)
+        fill_p = ctypes.POINTER(ctypes.c_int64)
+        step = holes.frames_per_call(h, w)
+        prev = prev.contiguous() if prev is not None else None
+        for f in range(0, n, step):
+            g = min(f + step, n)
+            _ffi.check(self.lib.eosvos_fill_holes(
+                self.h, _ptr(labels[f:g]), g - f, h, w, p['connectivity'], p['max_area'], holes.rel_q16(p['max_rel_area']),
+                holes.overlap_q16(p['prev_overlap']), _optr(prev), bytes(flags[f:g]), _ptr(out[f:g]),
+                filled[f:g].ctypes.data_as(fill_p) if return_filled else None))
+            prev = out[g - 1]
+        return (out, filled) if return_filled else out
+
     # ---- meta-training ----------------------------------------------------------------
     def meta_task_begin(self):
         _ffi.check(self.lib.eosvos_meta_task_begin(self.h))

@@ -22,6 +22,7 @@ import torch
 
 from . import components as component_filter
 from . import crf as crf_refine
+from . import holes as hole_filler
 from . import tta as tta_views
 from .helper_func import compute_loss, early_stopping, set_random_seeds
 
@@ -271,21 +272,26 @@ def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augm
     return out
 
 
-def merge_objects(engine, probs_all, frames=None, crf=None, keep=(), components=None):
+def merge_objects(engine, probs_all, frames=None, crf=None, keep=(), components=None, holes=None):
     """Per-object probabilities [(N,H,W)] -> label maps (N,H,W) uint8 (`evaluate.py:322-326`).
     `crf` (`crf.py`; None or iterations 0: off, the code below as it always was): the local dense CRF refines the merge against
     `frames` (N,3,H,W), one `crf_labels` call per chunk of frames.  The frames listed in `keep` -- the train frame of EVERY
     object of the sequence, whose prediction is the seeded ground truth -- take the plain merge and stay it.
     `components` (`components.py`; None or neutral values: off, nothing new is called): after the merge and the CRF, the
     connected-component filter zeroes small / non-dominant / ungated components frame by frame; the `keep` frames pass
-    unchanged and anchor the gate of the frame after them."""
+    unchanged and anchor the gate of the frame after them.
+    `holes` (`holes.py`; None or max_area 0: off, nothing new is called): last, enclosed background islands that are small
+    and were object in the previous frame's filled map are filled; the `keep` frames pass unchanged and anchor that chain."""
     stack = torch.stack(list(probs_all), dim=1)                       # (N, n_obj, H, W)
     clean = component_filter.active(components)
+    fill = hole_filler.active(holes)
     if crf_refine.active(crf):
         labels = _merge_refined(engine, stack, frames, crf, keep)
     else:
         labels = torch.stack([engine.merge_labels(stack[f].contiguous()) for f in range(stack.shape[0])])
-    return component_filter.filter(engine, labels, components, keep=keep) if clean else labels
+    if clean:
+        labels = component_filter.filter(engine, labels, components, keep=keep)
+    return hole_filler.fill(engine, labels, holes, keep=keep) if fill else labels
 
 
 def _merge_refined(engine, stack, frames, crf, keep):
@@ -315,8 +321,14 @@ def _components_kw(components):
     return {} if components is None else {'components': components}
 
 
+def _holes_kw(holes):
+    """As `_tta_kw`: `holes` travels as a keyword, and only when it is set to something that fills (`holes.active`, which
+    also validates it)."""
+    return {'holes': holes} if hole_filler.active(holes) else {}
+
+
 def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_gts, cfg, augment=None,
-                      train_frame_id=0, tta=None, crf=None, components=None):
+                      train_frame_id=0, tta=None, crf=None, components=None, holes=None):
     """frames (N,3,H,W) on the GPU, object_gts: list of (1,H,W) binary masks of the train frame.
     cfg keys (names of cfgs/meta.yaml): num_epochs.eval, eval_online_adapt.{step,reset_model_mode,
     num_epochs,min_prop (a threshold, or [lo, hi]: `min_prop_band`)}, data_cfg.batch_sizes.train, seed, loss_func, train_early_stopping_cfg.
@@ -324,6 +336,7 @@ def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_g
     `crf` (`crf.py`): the final merge is refined by the local dense CRF; the train frame keeps the plain merge.
     `components` (`components.py`): the connected-component filter cleans the merged (and refined) maps; the train frame passes
     unchanged and anchors the gate.
+    `holes` (`holes.py`): the hole filler runs after the component filter, with the same train frame kept.
     Returns (labels (N,H,W) uint8, per-object probs list, train loss history per object)."""
     probs_all, hist_all = [], []
     for gt in object_gts:
@@ -331,9 +344,10 @@ def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_g
                                       **_tta_kw(tta))
         probs_all.append(probs)
         hist_all.append(hist)
-    if crf is None and components is None:
+    if crf is None and components is None and not _holes_kw(holes):
         return merge_objects(model.engine, probs_all), probs_all, hist_all
-    return merge_objects(model.engine, probs_all, frames, crf, keep=(train_frame_id,), **_components_kw(components)), probs_all, hist_all
+    return merge_objects(model.engine, probs_all, frames, crf, keep=(train_frame_id,), **_components_kw(components),
+                         **_holes_kw(holes)), probs_all, hist_all
 
 
 def prediction_paths(save_dir, dataset_name, split):
@@ -350,7 +364,7 @@ def save_label_png(path, labels_hw):
 
 def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dataset_key, save_dir=None,
                      meta_iter=None, meta_epoch=None, best_mean_J=0.0, dist=None, device=None, vis_win_names=None,
-                     log=None, objects_in_flight=None, tta=None, crf=None, components=None):
+                     log=None, objects_in_flight=None, tta=None, crf=None, components=None, holes=None):
     """The evaluation worker of `src/util/evaluate.py:111-382` for the DeepLab path: every sequence of `dataset`
     (an `eosvos_amd.data` reader), every object, fine-tune / online adaptation / inference / merge; prediction PNGs
     under `{save_dir}/best_eval_preds/{name}/{split}/{seq}/{frame}.png`, J per sequence, and the
@@ -373,6 +387,7 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
     CRF; a frame that is the train frame of every object of its sequence keeps the plain merge (its seeded ground truth).
     `components` (`components.py`): the connected-component filter cleans the merged (and refined) label maps before the PNGs,
     J_seq and the J / F counts see them; the same train frame passes unchanged.
+    `holes` (`holes.py`): the hole filler runs after the component filter; the PNGs, J_seq and the J / F counts see the filled maps.
     Returns dict(J_seq, mean_J, best_mean_J, time_per_frame, labels={seq: (N,H,W) uint8}) and the DAVIS J / F statistics
     of `eval_davis_seq` (`evaluate.py:345-359`), one entry per object in sequence order: J_obj (the per-object J means the
     reference calls J_seq), J_recall_seq, J_decay_seq, F_seq, F_recall_seq, F_decay_seq, with mean_F and
@@ -500,11 +515,12 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
         num_frames += n * len(gts)                                              # per (object, frame), evaluate.py:320
         if model.engine is None:                                                # this rank had no item yet
             model._ensure_engine(frames.shape[2], frames.shape[3], 1)
-        keep = {'keep': tuple(set(fids)) if len(set(fids)) == 1 else ()} if crf is not None or components is not None else {}
+        keep = {'keep': tuple(set(fids)) if len(set(fids)) == 1 else ()} \
+            if crf is not None or components is not None or holes is not None else {}
         if crf is not None:
             keep = dict(frames=frames, **keep)
         labels = merge_objects(model.engine, [probs[o] for o in range(len(gts))], **keep, **_crf_kw(crf),
-                               **_components_kw(components))
+                               **_components_kw(components), **_holes_kw(holes))
         counts = None
         if not dataset.test_mode:                                               # J / F counts where the labels are
             gt_dev = torch.from_numpy(np.ascontiguousarray(gt_maps, dtype=np.uint8)).to(labels.device)

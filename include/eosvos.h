@@ -392,6 +392,50 @@ int eosvos_filter_components(eosvos_engine* e, const uint8_t* labels, int n_fram
                              int min_area, int rel_q16, int largest_only, int gate, const uint8_t* prev, const uint8_t* keep,
                              uint8_t* out, int64_t* removed_out);
 
+/* ---- hole filling of the merged label maps (after the component filter) ------------------------------------------- */
+/* The reference has no such step; the OSVOS family fills the background islands a few sub-threshold pixels leave inside an
+ * object.  Real holes (a bicycle frame, the gap between legs) are in the ground truth, so a hole is filled only if it is small
+ * and most of it was object in the previous frame's FILLED map -- the chain the component filter's gate uses, anchored at the
+ * train frame.  An opt-in extension.
+ * labels: device uint8 maps [n_frames][height][width] of one sequence in frame order; 0 is background, every non-zero value
+ * an object label.
+ *   1. background components  two pixels of a frame that hold 0 are connected when they are neighbours under the DUAL of
+ *        `connectivity`: connectivity 8 (objects join over corners) = the background joins over edges only; connectivity 4 =
+ *        the background joins over edges and corners.  Frames never connect.
+ *   2. holes  a background component is a hole when none of its pixels lies on the frame border (x = 0, y = 0, x = width - 1,
+ *        y = height - 1).  Its bordering labels are the non-zero labels among the neighbours (under the background's
+ *        connectivity) of its pixels.  A hole with exactly one bordering label o is a candidate for o; with two or more it is
+ *        left alone; it cannot have none.
+ *   3. size  A = the hole's pixel count, S = the number of pixels equal to o in the frame's INPUT map.  The candidate passes
+ *        iff  A <= max_area  and  A * 65536 <= rel_q16 * S  (64-bit integers; rel_q16 = round(max_rel_area * 65536) with
+ *        max_rel_area in [0, 1], computed once by the caller).
+ *   4. previous frame  R is the FILLED output of frame f - 1; for the first frame of the call R is `prev` (may be NULL: no R).
+ *        The rule is active for a candidate of o when overlap_q16 = round(prev_overlap * 65536) > 0, R exists and R has a pixel
+ *        equal to o.  When active, C = the number of the hole's pixels p with R[p] == o, and the candidate passes iff
+ *        C * 65536 >= overlap_q16 * A.  When inactive, it passes.
+ *   5. fill  pixels of holes that pass become o, everything else is copied.
+ *   6. independence  every decision in a frame is taken on the frame's input map: holes of a frame never influence each other.
+ *   7. keep  (HOST memory, n_frames flags, may be NULL) frames flagged there -- the train frames -- are copied unchanged and
+ *        still serve as R of the frame after them.
+ *   8. off  max_area == 0 or rel_q16 == 0: no hole can pass, every frame is copied.
+ * Writes the filled maps to `out` (device, not overlapping `labels`) and, if filled_out (HOST memory, n_frames values) is not
+ * NULL, the number of pixels filled per frame -- it then synchronises the engine's stream; otherwise the call is asynchronous
+ * on the engine's stream.  `e` lends its stream and scratch memory only; frames of any size within the limits.
+ * Launches (csrc/ccl_kernels.hip): the three union-find launches of eosvos_label_components over the zero pixels; a scan (per
+ * root: border flag, smallest and largest neighbour label -- one label <=> they are equal -- and the frame's label histogram);
+ * with overlap_q16 > 0 per frame in order an overlap count and the apply, without it one apply for all frames.  Integer
+ * atomics only: results are exact and independent of arrival order.  No launch is cooperative, no workgroup waits for another.
+ * Scratch (shared with the component filter): 24 bytes per pixel (parent, tile count, id, area, record, overlap count as
+ * 32-bit words) + 1288 per frame (histogram, pixels filled, labels present) + 264, allocated on first use, growing only, at
+ * most 512 MB per call -- a call that needs more is rejected (pass fewer frames per call and the last filled frame as `prev`
+ * of the next).
+ * Rejected without a launch: a null pointer (prev, keep, filled_out excepted), height or width < 1 or > 4096,
+ * height * width >= 2^24, connectivity not 4 or 8, max_area outside [0, 2^24], rel_q16 or overlap_q16 outside [0, 65536], more
+ * than 65535 frames. */
+int eosvos_fill_holes(eosvos_engine* e, const uint8_t* labels, int n_frames, int height, int width, int connectivity,
+                      int max_area, int rel_q16, int overlap_q16, const uint8_t* prev, const uint8_t* keep, uint8_t* out,
+                      int64_t* filled_out);
+
 /* ---- learning-rate hierarchy (meta_optim.py:27-67) ------------------------------------ */
 /* `lr_hierarchy_level`: how the learned lr state is stored.  NEURON (cfgs/meta.yaml:36) one
  * value per output channel; TENSOR one per trainable tensor (`log_init_lr` of shape
