@@ -1712,7 +1712,7 @@ int eosvos_create_ex(eosvos_engine** out, int arch, int norm_mode, int height, i
   ALLOC(e->d2, n4 * 256); ALLOC(e->g_d2, n4 * 256);
   ALLOC(e->lowlog, n4); ALLOC(e->g_low, n4);
   ALLOC(e->logits, (int64_t)B * H * W); ALLOC(e->dlogits, (int64_t)B * H * W);
-  ALLOC(e->loss_dev, 4); ALLOC(e->bce_partial, LOSS_IGNORE_PARTIAL_FLOATS);
+  ALLOC(e->loss_dev, 4); ALLOC(e->bce_partial, LOSS_PARTIAL_FLOATS);
   {                                               // ReLU mask bytes of the tensors the data gradients read as masks
     // (GroupNorm mode, round 5: the apply pass that writes y = relu(gn(z) (+ res)) writes the bytes)
     auto m8alloc = [&](const float* key, int64_t floats) {     // one byte per 4 floats
@@ -2355,18 +2355,12 @@ int eosvos_forward(eosvos_engine* e, const float* images, int batch, float* logi
     HIPOK(hipMemcpyAsync(logits_out, e->logits, (size_t)batch * e->H * e->W * 4, hipMemcpyDeviceToDevice, e->s));
   return 0;
 }
-int eosvos_loss_bce(eosvos_engine* e, const float* masks, int batch, float* loss_out) {
-  ModeScope mode_scope(e);
-  if (!e || !masks) return fail("null argument");
-  if (batch != e->lastB) return fail("loss batch differs from the last forward");
-  launch_bce(e->logits, masks, e->dlogits, e->loss_dev, e->bce_partial, (int64_t)batch * e->H * e->W, e->s);
-  e->have_loss_grad = true;
-  if (loss_out) HIPOK(hipMemcpyAsync(loss_out, e->loss_dev, 4, hipMemcpyDeviceToDevice, e->s));
-  HIPOK(hipGetLastError());
-  return 0;
-}
 namespace {
 inline bool lovasz_kind(int kind) { return kind == EOSVOS_LOSS_LOVASZ_HINGE || kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT; }
+inline bool loss_kind_ok(int kind) { return kind >= EOSVOS_LOSS_BCE && kind <= EOSVOS_LOSS_LOVASZ_HINGE_FLAT; }
+// a void label is a finite value no target can take
+inline bool ignore_ok(float v) { return std::isfinite(v) && (v < 0.f || v > 1.f); }
+constexpr int PROP_MAX_FRAMES = 1024;
 // the Lovasz kinds' sort scratch, sized for the engine's largest batch; 0 on success
 int lovasz_ensure(eosvos_engine* e) {
   if (e->lovasz_scratch) return 0;
@@ -2379,54 +2373,62 @@ int lovasz_ensure(eosvos_engine* e) {
   }
   return 0;
 }
-}  // namespace
-
-int eosvos_loss(eosvos_engine* e, int kind, const float* masks, int batch, float* loss_out) {
-  ModeScope mode_scope(e);
-  if (kind == EOSVOS_LOSS_BCE) return eosvos_loss_bce(e, masks, batch, loss_out);
-  if (!e || !masks) return fail("null argument");
+// Loss `kind` (checked by the caller) of `images` maps of n_per_image pixels -- the Lovasz kinds: per map, or with `flat` over
+// all of them as one set -- with its gradient, into the device pointers loss / dlogits.  `ignore`: the void label, or null.
+int loss_eval(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n_per_image, int images, int flat,
+              const float* ignore, float* dlogits, float* loss) {
   if (lovasz_kind(kind)) {
-    if (batch != e->lastB) return fail("loss batch differs from the last forward");
     if (lovasz_ensure(e)) return 1;
-    launch_lovasz(e->logits, masks, e->dlogits, e->loss_dev, e->lovasz_scratch, (int64_t)e->H * e->W, batch,
-                  kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT, e->s);
-    e->have_loss_grad = true;
-    if (loss_out) HIPOK(hipMemcpyAsync(loss_out, e->loss_dev, 4, hipMemcpyDeviceToDevice, e->s));
-    HIPOK(hipGetLastError());
-    return 0;
+    launch_lovasz(logits, masks, dlogits, loss, e->lovasz_scratch, n_per_image, images, flat, ignore, e->s);
+  } else {
+    launch_loss(kind, logits, masks, dlogits, loss, e->bce_partial, n_per_image * images, ignore, e->s);
   }
-  if (kind != EOSVOS_LOSS_DICE && kind != EOSVOS_LOSS_BCE_DICE && kind != EOSVOS_LOSS_CLASS_BALANCED_BCE)
-    return fail("unknown loss kind");
-  if (batch != e->lastB) return fail("loss batch differs from the last forward");
-  launch_dice(e->logits, masks, e->dlogits, e->loss_dev, e->bce_partial, (int64_t)batch * e->H * e->W, kind, e->s);
-  e->have_loss_grad = true;
-  if (loss_out) HIPOK(hipMemcpyAsync(loss_out, e->loss_dev, 4, hipMemcpyDeviceToDevice, e->s));
   HIPOK(hipGetLastError());
   return 0;
 }
-namespace {
-// a void label is a finite value no target can take
-inline bool ignore_ok(float v) { return std::isfinite(v) && (v < 0.f || v > 1.f); }
-constexpr int PROP_MAX_FRAMES = 1024;
-}  // namespace
-int eosvos_loss_ignore(eosvos_engine* e, int kind, const float* masks, int batch, float ignore, float* loss_out) {
-  ModeScope mode_scope(e);
+// on the logits of the last forward: leaves dL/dlogits for eosvos_backward_step
+int loss_on_forward(eosvos_engine* e, int kind, const float* masks, int batch, const float* ignore, float* loss_out) {
   if (!e || !masks) return fail("null argument");
-  if (kind < EOSVOS_LOSS_BCE || kind > EOSVOS_LOSS_LOVASZ_HINGE_FLAT) return fail("unknown loss kind");
-  if (!ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  if (!loss_kind_ok(kind)) return fail("unknown loss kind");
+  if (ignore && !ignore_ok(*ignore)) return fail("the ignore label must be finite and outside [0, 1]");
   if (batch != e->lastB) return fail("loss batch differs from the last forward");
-  if (lovasz_kind(kind)) {
-    if (lovasz_ensure(e)) return 1;
-    launch_lovasz_ignore(e->logits, masks, e->dlogits, e->loss_dev, e->lovasz_scratch, (int64_t)e->H * e->W, batch,
-                         kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT, ignore, e->s);
-  } else {
-    launch_loss_ignore(e->logits, masks, e->dlogits, e->loss_dev, e->bce_partial, (int64_t)batch * e->H * e->W, kind, ignore,
-                       e->s);
-  }
+  if (loss_eval(e, kind, e->logits, masks, (int64_t)e->H * e->W, batch, kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT, ignore,
+                e->dlogits, e->loss_dev))
+    return 1;
   e->have_loss_grad = true;
   if (loss_out) HIPOK(hipMemcpyAsync(loss_out, e->loss_dev, 4, hipMemcpyDeviceToDevice, e->s));
-  HIPOK(hipGetLastError());
   return 0;
+}
+// on caller tensors, the n elements one set.  Without a caller buffer the gradient goes to the engine's own dlogits scratch,
+// which bounds n and invalidates a pending eosvos_loss* gradient.
+int loss_on_tensors(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n, const float* ignore,
+                    float* loss_out, float* dlogits_out) {
+  if (!e || !logits || !masks || !loss_out || n < 1) return fail("bad argument");
+  if (!loss_kind_ok(kind)) return fail("unknown loss kind");
+  if (ignore && !ignore_ok(*ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  if (!dlogits_out) {
+    if (n > (int64_t)e->maxB * e->H * e->W) return fail("n exceeds the engine's scratch");
+    e->have_loss_grad = false;
+  }
+  return loss_eval(e, kind, logits, masks, n, 1, 1, ignore, dlogits_out ? dlogits_out : e->dlogits, loss_out);
+}
+// the loss of the fused entry points
+inline int fused_loss(eosvos_engine* e, const float* masks, int batch) {
+  return loss_on_forward(e, e->loss_kind, masks, batch, e->loss_ignore_on ? &e->loss_ignore : nullptr, nullptr);
+}
+}  // namespace
+
+int eosvos_loss_bce(eosvos_engine* e, const float* masks, int batch, float* loss_out) {
+  ModeScope mode_scope(e);
+  return loss_on_forward(e, EOSVOS_LOSS_BCE, masks, batch, nullptr, loss_out);
+}
+int eosvos_loss(eosvos_engine* e, int kind, const float* masks, int batch, float* loss_out) {
+  ModeScope mode_scope(e);
+  return loss_on_forward(e, kind, masks, batch, nullptr, loss_out);
+}
+int eosvos_loss_ignore(eosvos_engine* e, int kind, const float* masks, int batch, float ignore, float* loss_out) {
+  ModeScope mode_scope(e);
+  return loss_on_forward(e, kind, masks, batch, &ignore, loss_out);
 }
 int eosvos_set_loss_ignore(eosvos_engine* e, int on, float ignore) {
   if (!e) return fail("null engine");
@@ -2435,13 +2437,6 @@ int eosvos_set_loss_ignore(eosvos_engine* e, int on, float ignore) {
   e->loss_ignore = on ? ignore : 0.f;
   return 0;
 }
-namespace {
-// the loss of the fused entry points
-inline int fused_loss(eosvos_engine* e, const float* masks, int batch) {
-  return e->loss_ignore_on ? eosvos_loss_ignore(e, e->loss_kind, masks, batch, e->loss_ignore, nullptr)
-                           : eosvos_loss(e, e->loss_kind, masks, batch, nullptr);
-}
-}  // namespace
 int eosvos_last_loss(eosvos_engine* e, float* loss_out) {
   if (!e || !loss_out) return fail("null argument");
   HIPOK(hipMemcpyAsync(loss_out, e->loss_dev, 4, hipMemcpyDeviceToDevice, e->s));
@@ -2449,7 +2444,7 @@ int eosvos_last_loss(eosvos_engine* e, float* loss_out) {
 }
 int eosvos_set_loss(eosvos_engine* e, int kind) {
   if (!e) return fail("null engine");
-  if (kind < EOSVOS_LOSS_BCE || kind > EOSVOS_LOSS_LOVASZ_HINGE_FLAT) return fail("unknown loss kind");
+  if (!loss_kind_ok(kind)) return fail("unknown loss kind");
   if (lovasz_kind(kind) && lovasz_ensure(e)) return 1;
   e->loss_kind = kind;
   return 0;
@@ -2457,48 +2452,16 @@ int eosvos_set_loss(eosvos_engine* e, int kind) {
 int eosvos_bce(eosvos_engine* e, const float* logits, const float* masks, int64_t n, float* loss_out,
                float* dlogits_out) {
   ModeScope mode_scope(e);
-  if (!e || !logits || !masks || !loss_out || n < 1) return fail("bad argument");
-  if (!dlogits_out && n > (int64_t)e->maxB * e->H * e->W) return fail("n exceeds the engine's scratch");
-  // without a caller buffer the gradient goes to the engine's own dlogits scratch, which
-  // invalidates a pending eosvos_loss_bce gradient
-  if (!dlogits_out) e->have_loss_grad = false;
-  launch_bce(logits, masks, dlogits_out ? dlogits_out : e->dlogits, loss_out, e->bce_partial, n, e->s);
-  HIPOK(hipGetLastError());
-  return 0;
+  return loss_on_tensors(e, EOSVOS_LOSS_BCE, logits, masks, n, nullptr, loss_out, dlogits_out);
 }
 int eosvos_loss_tensors(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n, float* loss_out) {
   ModeScope mode_scope(e);
-  if (kind == EOSVOS_LOSS_BCE) return eosvos_bce(e, logits, masks, n, loss_out, nullptr);
-  if (!e || !logits || !masks || !loss_out || n < 1) return fail("bad argument");
-  if (lovasz_kind(kind)) {                  // the n elements are one set for either kind
-    if (n > (int64_t)e->maxB * e->H * e->W) return fail("n exceeds the engine's scratch");
-    if (lovasz_ensure(e)) return 1;
-    e->have_loss_grad = false;              // the gradient scratch is overwritten
-    launch_lovasz(logits, masks, e->dlogits, loss_out, e->lovasz_scratch, n, 1, 1, e->s);
-    HIPOK(hipGetLastError());
-    return 0;
-  }
-  if (kind != EOSVOS_LOSS_DICE && kind != EOSVOS_LOSS_BCE_DICE && kind != EOSVOS_LOSS_CLASS_BALANCED_BCE)
-    return fail("unknown loss kind");
-  if (n > (int64_t)e->maxB * e->H * e->W) return fail("n exceeds the engine's scratch");
-  e->have_loss_grad = false;              // the gradient scratch is overwritten
-  launch_dice(logits, masks, e->dlogits, loss_out, e->bce_partial, n, kind, e->s);
-  HIPOK(hipGetLastError());
-  return 0;
+  return loss_on_tensors(e, kind, logits, masks, n, nullptr, loss_out, nullptr);
 }
 int eosvos_loss_tensors_ignore(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n, float ignore,
                                float* loss_out) {
   ModeScope mode_scope(e);
-  if (!e || !logits || !masks || !loss_out || n < 1) return fail("bad argument");
-  if (kind < EOSVOS_LOSS_BCE || kind > EOSVOS_LOSS_LOVASZ_HINGE_FLAT) return fail("unknown loss kind");
-  if (!ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
-  if (n > (int64_t)e->maxB * e->H * e->W) return fail("n exceeds the engine's scratch");
-  if (lovasz_kind(kind) && lovasz_ensure(e)) return 1;
-  e->have_loss_grad = false;              // the gradient scratch is overwritten
-  if (lovasz_kind(kind)) launch_lovasz_ignore(logits, masks, e->dlogits, loss_out, e->lovasz_scratch, n, 1, 1, ignore, e->s);
-  else launch_loss_ignore(logits, masks, e->dlogits, loss_out, e->bce_partial, n, kind, ignore, e->s);
-  HIPOK(hipGetLastError());
-  return 0;
+  return loss_on_tensors(e, kind, logits, masks, n, &ignore, loss_out, nullptr);
 }
 int eosvos_propagation_targets(eosvos_engine* e, const float* probs, int n_frames, int64_t n_pix, float lo, float hi,
                                float ignore, float* targets_out, int64_t* n_pos_host) {

@@ -61,6 +61,19 @@ __device__ __forceinline__ unsigned amax_read(const unsigned* slot) {
   }
   return m;
 }
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// integer sum over a 256-thread block, valid in every thread
+__device__ __forceinline__ int block_sum_i(int v, int* sh /*4*/) {
+  v = wave_sum_i(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return sh[0] + sh[1] + sh[2] + sh[3];
+}
 #endif
 
 // ---------------------------------------------------------------------------------
@@ -356,29 +369,25 @@ void launch_last_bwd(const float* x, const float* w, const float* g, float* gx, 
                      int64_t P, int C, int chunks, hipStream_t s);
 int last_bwd_chunks(int64_t P);
 
-// BCE-with-logits mean + gradient; loss accumulates deterministically through `partial`
-void launch_bce(const float* logits, const float* gt, float* dlogits, float* loss, float* partial,
-                int64_t n, hipStream_t s);
-// dice (kind 1) / BCE - log(1 - dice) (kind 2), whole batch flattened; partial >= 4*1024+4 floats
-void launch_dice(const float* logits, const float* gt, float* dlogits, float* loss, float* partial, int64_t n, int kind,
-                 hipStream_t s);
+// The device losses.  `ignore`: null, or a host pointer to the void label (finite, outside [0, 1]): a pixel with gt == *ignore is in no
+// sum, count or sort and its gradient is +0; an empty valid set gives loss 0; without a void pixel the result has the bits of
+// the launch without a label (each kernel is one `template <bool VOID>` source, the label compiled out of the plain instance).
+// launch_loss, the whole batch flattened, sums in a fixed order through `partial` (LOSS_PARTIAL_FLOATS floats): kind 0 BCE-with-
+// logits mean (gradient fused into the loss pass; with a label a third launch, 1 / |V| being known only after the count),
+// 1 dice, 2 BCE - log(1 - dice), 3 class-balanced BCE (sums and counts over the valid pixels, the trailing divisions by n).
+constexpr int LOSS_BLOCKS = 1024;                 // cap of the partial grids
+// partial: [0, LOSS_SCAL) per-block sums (up to a float4 each), 16 scalars of the final kernel, per-block valid counts
+constexpr int LOSS_SCAL = 4 * LOSS_BLOCKS, LOSS_CNT = LOSS_SCAL + 16, LOSS_PARTIAL_FLOATS = LOSS_CNT + LOSS_BLOCKS;
+void launch_loss(int kind, const float* logits, const float* gt, float* dlogits, float* loss, float* partial, int64_t n,
+                 const float* ignore, hipStream_t s);
 // Lovasz hinge (lovasz_kernels.hip; loss_lovasz.py:78-111): `images` sets of n_per_image pixels, the loss their mean and each
 // gradient scaled by 1 / images -- or, with `flat`, the whole batch as one set.  A per-image stable radix sort of the
-// positive errors, a scan of the label bits and a scatter of the gradient; bit-reproducible.  scratch: lovasz_scratch_floats
+// positive errors, a scan of the label bits and a scatter of the gradient; bit-reproducible.  The void pixels are dropped
+// before the ranking (flatten_binary_scores, loss_lovasz.py:114-126).  scratch: lovasz_scratch_floats
 // (n_per_image * images, images) floats; n_per_image * images < 2^31.
 int64_t lovasz_scratch_floats(int64_t n_total, int max_images);
 void launch_lovasz(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_image,
-                   int images, int flat, hipStream_t s);
-// The losses with a void label: a pixel with gt == ignore (a finite value outside [0, 1]) is in no sum, count or sort and its
-// gradient is +0; an empty valid set gives loss 0.  launch_loss_ignore: kind 0 BCE over the valid pixels, 1 dice, 2 BCE - log(1
-// - dice), 3 class-balanced BCE (sums and counts over the valid pixels, the trailing divisions by n); partial >=
-// LOSS_IGNORE_PARTIAL_FLOATS floats.  launch_lovasz_ignore: launch_lovasz with the void pixels dropped before the ranking
-// (flatten_binary_scores, loss_lovasz.py:114-126).  Without a void pixel both give the bits of the unmasked launches.
-constexpr int LOSS_IGNORE_PARTIAL_FLOATS = 5 * 1024 + 16;
-void launch_loss_ignore(const float* logits, const float* gt, float* dlogits, float* loss, float* partial, int64_t n, int kind,
-                        float ignore, hipStream_t s);
-void launch_lovasz_ignore(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_image,
-                          int images, int flat, float ignore, hipStream_t s);
+                   int images, int flat, const float* ignore, hipStream_t s);
 // targets = 1 where probs >= hi, 0 where probs < lo, `ignore` between, for n_frames maps of n_pix; n_pos[frame] (zeroed by the
 // caller) += the frame's number of 1s
 void launch_propagation_targets(const float* probs, float* targets, int* n_pos, int n_frames, int64_t n_pix, float lo, float hi,

@@ -54,19 +54,6 @@ inline LvScratch lv_carve(float* scratch, int64_t n_total, int64_t tiles, int se
 }
 
 __device__ __forceinline__ unsigned long long lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// integer sum over the 256 threads, valid in every thread
-__device__ __forceinline__ int block_sum_i(int v, int* sh /*4*/) {
-  v = wave_sum_i(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
 // fp64 sum over the 256 threads in a fixed order, valid in every thread
 __device__ __forceinline__ double block_sum_d(double v, double* sh /*4*/) {
 #pragma unroll
@@ -98,13 +85,12 @@ __device__ __forceinline__ long lv_elem(int tile, int j) {
 }
 
 // VOID: a pixel with t == ign is dropped here and in the compaction (flatten_binary_scores, loss_lovasz.py:114-126): it counts
-// neither as e > 0 nor as foreground, its logit may be non-finite, and dlogits stays the +0 written below.
-// The body is shared; the kernel without a void label keeps its own entry point and arguments (and, checked in the
-// disassembly, the code it had before the void form existed).
+// neither as e > 0 nor as foreground, its logit may be non-finite, and dlogits stays the +0 written below.  VOID = false never
+// reads `ign`.
 template <bool VOID>
-__device__ __forceinline__ void lovasz_prep_body(const float* __restrict__ x, const float* __restrict__ t,
-                                                 float* __restrict__ dx, int* __restrict__ tinfo, long seg_len, int tps,
-                                                 float ign) {
+__global__ __launch_bounds__(LV_THREADS) void lovasz_prep_kernel(const float* __restrict__ x, const float* __restrict__ t,
+                                                                 float* __restrict__ dx, int* __restrict__ tinfo, long seg_len,
+                                                                 int tps, float ign) {
   __shared__ int sh[4];
   const int seg = blockIdx.x / tps, tile = blockIdx.x % tps;
   const long seg0 = (long)seg * seg_len;
@@ -132,23 +118,12 @@ __device__ __forceinline__ void lovasz_prep_body(const float* __restrict__ x, co
   }
 }
 
-__global__ __launch_bounds__(LV_THREADS) void lovasz_prep_kernel(const float* __restrict__ x, const float* __restrict__ t,
-                                                                 float* __restrict__ dx, int* __restrict__ tinfo, long seg_len,
-                                                                 int tps) {
-  lovasz_prep_body<false>(x, t, dx, tinfo, seg_len, tps, 0.f);
-}
-__global__ __launch_bounds__(LV_THREADS) void lovasz_prep_ign_kernel(const float* __restrict__ x, const float* __restrict__ t,
-                                                                     float* __restrict__ dx, int* __restrict__ tinfo,
-                                                                     long seg_len, int tps, float ign) {
-  lovasz_prep_body<true>(x, t, dx, tinfo, seg_len, tps, ign);
-}
-
-// VOID: as in prep, a pixel with t == ign is left out of the compaction.  One body for both kernels.
+// VOID: as in prep, a pixel with t == ign is left out of the compaction.
 template <bool VOID>
-__device__ __forceinline__ void lovasz_compact_body(const float* __restrict__ x, const float* __restrict__ t,
-                                                    const int* __restrict__ tinfo, int* __restrict__ sinfo,
-                                                    unsigned* __restrict__ keys, unsigned* __restrict__ vals, long seg_len,
-                                                    int tps, float ign) {
+__global__ __launch_bounds__(LV_THREADS) void lovasz_compact_kernel(const float* __restrict__ x, const float* __restrict__ t,
+                                                                    const int* __restrict__ tinfo, int* __restrict__ sinfo,
+                                                                    unsigned* __restrict__ keys, unsigned* __restrict__ vals,
+                                                                    long seg_len, int tps, float ign) {
   __shared__ int sh[4];
   __shared__ int wtot[4];
   const int seg = blockIdx.x / tps, tile = blockIdx.x % tps;
@@ -204,19 +179,6 @@ __device__ __forceinline__ void lovasz_compact_body(const float* __restrict__ x,
     }
     run += __popcll(bal[j]);
   }
-}
-
-__global__ __launch_bounds__(LV_THREADS) void lovasz_compact_kernel(const float* __restrict__ x, const float* __restrict__ t,
-                                                                    const int* __restrict__ tinfo, int* __restrict__ sinfo,
-                                                                    unsigned* __restrict__ keys, unsigned* __restrict__ vals,
-                                                                    long seg_len, int tps) {
-  lovasz_compact_body<false>(x, t, tinfo, sinfo, keys, vals, seg_len, tps, 0.f);
-}
-__global__ __launch_bounds__(LV_THREADS) void lovasz_compact_ign_kernel(const float* __restrict__ x, const float* __restrict__ t,
-                                                                        const int* __restrict__ tinfo, int* __restrict__ sinfo,
-                                                                        unsigned* __restrict__ keys, unsigned* __restrict__ vals,
-                                                                        long seg_len, int tps, float ign) {
-  lovasz_compact_body<true>(x, t, tinfo, sinfo, keys, vals, seg_len, tps, ign);
 }
 
 __global__ __launch_bounds__(LV_THREADS) void lovasz_hist_kernel(const unsigned* __restrict__ keys, const int* __restrict__ sinfo,
@@ -430,8 +392,9 @@ int64_t lovasz_scratch_floats(int64_t n_total, int max_images) {
 }
 
 namespace {
+template <bool VOID>
 void lovasz_launches(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_image,
-                     int images, int flat, bool has_ign, float ign, hipStream_t s) {
+                     int images, int flat, float ign, hipStream_t s) {
   const int segs = flat ? 1 : images;
   const int64_t n_total = n_per_image * images;
   const long seg_len = (long)(flat ? n_total : n_per_image);
@@ -439,14 +402,9 @@ void lovasz_launches(const float* logits, const float* gt, float* dlogits, float
   const int nb = segs * tps;
   const LvScratch L = lv_carve(scratch, n_total, nb, segs);
   const dim3 grid(nb), block(LV_THREADS);
-  if (has_ign) {
-    hipLaunchKernelGGL(lovasz_prep_ign_kernel, grid, block, 0, s, logits, gt, dlogits, L.tinfo, seg_len, tps, ign);
-    hipLaunchKernelGGL(lovasz_compact_ign_kernel, grid, block, 0, s, logits, gt, L.tinfo, L.sinfo, L.key[0], L.val[0], seg_len,
-                       tps, ign);
-  } else {
-    hipLaunchKernelGGL(lovasz_prep_kernel, grid, block, 0, s, logits, gt, dlogits, L.tinfo, seg_len, tps);
-    hipLaunchKernelGGL(lovasz_compact_kernel, grid, block, 0, s, logits, gt, L.tinfo, L.sinfo, L.key[0], L.val[0], seg_len, tps);
-  }
+  hipLaunchKernelGGL((lovasz_prep_kernel<VOID>), grid, block, 0, s, logits, gt, dlogits, L.tinfo, seg_len, tps, ign);
+  hipLaunchKernelGGL((lovasz_compact_kernel<VOID>), grid, block, 0, s, logits, gt, L.tinfo, L.sinfo, L.key[0], L.val[0], seg_len,
+                     tps, ign);
   for (int pass = 0; pass < 4; ++pass) {           // (the key's top bit is always set: 31 significant bits, four 8-bit digits)
     const int in = pass & 1, out = in ^ 1;
     hipLaunchKernelGGL(lovasz_hist_kernel, grid, block, 0, s, L.key[in], L.sinfo, L.hist, seg_len, tps, 8 * pass);
@@ -462,12 +420,9 @@ void lovasz_launches(const float* logits, const float* gt, float* dlogits, float
 }  // namespace
 
 void launch_lovasz(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_image,
-                   int images, int flat, hipStream_t s) {
-  lovasz_launches(logits, gt, dlogits, loss, scratch, n_per_image, images, flat, false, 0.f, s);
-}
-void launch_lovasz_ignore(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_image,
-                          int images, int flat, float ignore, hipStream_t s) {
-  lovasz_launches(logits, gt, dlogits, loss, scratch, n_per_image, images, flat, true, ignore, s);
+                   int images, int flat, const float* ignore, hipStream_t s) {
+  if (ignore) lovasz_launches<true>(logits, gt, dlogits, loss, scratch, n_per_image, images, flat, *ignore, s);
+  else lovasz_launches<false>(logits, gt, dlogits, loss, scratch, n_per_image, images, flat, 0.f, s);
 }
 
 }  // namespace eosvos

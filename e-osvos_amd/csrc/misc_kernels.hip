@@ -1,6 +1,7 @@
 // HBM-bound and small kernels of the e-OSVOS inner loop for gfx950: layout changes, the
 // 7x7 stem, max-pool, bilinear resize (+ gather-form backward), the ASPP image-pooling
-// branch, the 1-channel classifier conv, fused BCE loss + gradient, the fused
+// branch, the 1-channel classifier conv, the losses and their gradients (one templated kernel family each, with or without a
+// void label), the fused
 // per-neuron-lr SGD update (split-K slab reduction included), meta-gradient reduction,
 // RAdam, the Winograd transform passes (one templated family, at the end of the file).
 // 64-lane waves, 16-byte accesses where the layout allows, deterministic (atomic-free)
@@ -735,38 +736,7 @@ void launch_last_bwd(const float* x, const float* w, const float* g, float* gx, 
   hipLaunchKernelGGL(last_bwd_kernel, dim3(chunks), dim3(256), 0, s, x, w, g, gx, ws_dw, (long)P, C, chunks);
 }
 
-// ---- BCE with logits (mean) + gradient -------------------------------------------------------------
-#define BCE_BLOCKS 1024
-__global__ __launch_bounds__(256) void bce_kernel(const float* __restrict__ x, const float* __restrict__ t,
-                                                   float* __restrict__ dx, float* __restrict__ partial, long n,
-                                                   float inv_n) {
-  __shared__ float sh[4];
-  float s = 0.f;
-  GRID_STRIDE(i, n) {
-    const float xv = x[i], tv = t[i];
-    const float e = expf(-fabsf(xv));
-    s += fmaxf(xv, 0.f) - xv * tv + log1pf(e);
-    const float sig = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-    dx[i] = (sig - tv) * inv_n;
-  }
-  s = block_sum_256(s, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-__global__ __launch_bounds__(256) void bce_final_kernel(const float* __restrict__ partial, float* __restrict__ loss,
-                                                         int nb, float inv_n) {
-  __shared__ float sh[4];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < nb; i += 256) s += partial[i];
-  s = block_sum_256(s, sh);
-  if (threadIdx.x == 0) loss[0] = s * inv_n;
-}
-void launch_bce(const float* logits, const float* gt, float* dlogits, float* loss, float* partial, int64_t n,
-                hipStream_t s) {
-  const int nb = grid_for(n, 256, BCE_BLOCKS);
-  const float inv_n = 1.0f / (float)n;
-  hipLaunchKernelGGL(bce_kernel, dim3(nb), dim3(256), 0, s, logits, gt, dlogits, partial, (long)n, inv_n);
-  hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(256), 0, s, partial, loss, nb, inv_n);
-}
+// ---- sigmoid, test-time augmentation -------------------------------------------------------------------
 __global__ void sigmoid_kernel(const float* __restrict__ x, float* __restrict__ y, long n) {
   GRID_STRIDE(i, n) {
     const float xv = x[i];
@@ -1472,195 +1442,96 @@ void launch_gn_backward(float* z, int ldz, const float* g, int ldg, const float*
 }
 }  // namespace eosvos
 
-// ---- dice / BCE+dice losses (loss_dice.py:4-40, helper_func.py:43-54), batch_average=True ------------
-// stage 1: per-block partials {sum p*y, sum p, sum y, sum bce}; stage 2: scalars; stage 3: dlogits
+// ---- the device losses and their gradients (launch_loss): BCE with logits (mean), dice / BCE+dice, class-balanced BCE ----
+// One `template <bool VOID>` kernel family per loss.  VOID = true is the loss with a void label: a pixel with t == ign is in
+// no sum and no count and its gradient is +0; its logit is selected away, never multiplied by 0 (it may be NaN / inf); the
+// valid pixels are counted per block (integers, summed in a fixed order) and |V| takes the place of n.  VOID = false compiles
+// the select, the count and the |V| == 0 results out: it reads no count buffer and V = n.  Grids, per-thread accumulation order
+// and expressions are shared, so a map without a void pixel gives the bits of the plain launch.
+// Every kind is partial -> final -> grad, the scalars of `final` staying on the device, but plain BCE: its 1 / n is known on
+// the host, so the first pass writes the gradient too.  Scratch layout: LOSS_SCAL, LOSS_CNT (kernels.h).
 namespace eosvos {
-__global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restrict__ x, const float* __restrict__ t,
-                                                            float4* __restrict__ partial, long n) {
-  __shared__ float sh[4];
-  float a = 0.f, b = 0.f, c = 0.f, d = 0.f;
-  GRID_STRIDE(i, n) {
-    const float xv = x[i], tv = t[i];
-    const float e = expf(-fabsf(xv));
-    const float p = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-    a += p * tv; b += p; c += tv;
-    d += fmaxf(xv, 0.f) - xv * tv + log1pf(e);
-  }
-  a = block_sum_256(a, sh); b = block_sum_256(b, sh); c = block_sum_256(c, sh); d = block_sum_256(d, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = make_float4(a, b, c, d);
-}
-// scal = {loss, c_y, c_1, bce_w}:  dL/dx = bce_w*(p - y) + (c_y*y + c_1)*p*(1-p)
-__global__ __launch_bounds__(256) void dice_final_kernel(const float4* __restrict__ partial, int nb, long n, int kind,
-                                                          float* __restrict__ loss, float* __restrict__ scal) {
-  __shared__ double sh[4][4];
-  double a = 0, b = 0, c = 0, d = 0;
-  for (int i = threadIdx.x; i < nb; i += 256) { const float4 v = partial[i]; a += v.x; b += v.y; c += v.z; d += v.w; }
-  for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); c += __shfl_xor(c, o, 64); d += __shfl_xor(d, o, 64); }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sh[w][0] = a; sh[w][1] = b; sh[w][2] = c; sh[w][3] = d; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double I = 0, Sp = 0, Sy = 0, Sb = 0;
-    for (int k = 0; k < 4; ++k) { I += sh[k][0]; Sp += sh[k][1]; Sy += sh[k][2]; Sb += sh[k][3]; }
-    const double num = 2.0 * I + 1.0, D = Sp + Sy + 1.0;
-    const double dice = 1.0 - num / D;
-    if (kind == 1) {            // dice:  dL/dp = -(2y*D - num)/D^2
-      loss[0] = (float)dice;
-      scal[1] = (float)(-2.0 / D); scal[2] = (float)(num / (D * D)); scal[3] = 0.f;
-    } else {                    // BCE - log(1 - dice) = BCE - log(num/D):  dL/dp = -2y/num + 1/D
-      loss[0] = (float)(Sb / (double)n - log(num / D));
-      scal[1] = (float)(-2.0 / num); scal[2] = (float)(1.0 / D); scal[3] = (float)(1.0 / (double)n);
-    }
-    scal[0] = loss[0];
-  }
-}
-__global__ void dice_grad_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ scal,
-                                 float* __restrict__ dx, long n) {
-  const float cy = scal[1], c1 = scal[2], bw = scal[3];
-  GRID_STRIDE(i, n) {
-    const float xv = x[i], tv = t[i];
-    const float e = expf(-fabsf(xv));
-    const float p = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-    dx[i] = bw * (p - tv) + (cy * tv + c1) * p * (1.f - p);
-  }
-}
-// class-balanced cross entropy (loss_ce.py:15-60, batch_average = size_average = True):
-//   labels = gt >= .5;  L = (N_neg * sum_pos bce + N_pos * sum_neg bce) / N^2
-__global__ __launch_bounds__(256) void cbce_partial_kernel(const float* __restrict__ x, const float* __restrict__ t,
-                                                            float4* __restrict__ partial, long n) {
-  __shared__ float sh[4];
-  float a = 0.f, b = 0.f, c = 0.f;
-  GRID_STRIDE(i, n) {
-    const float xv = x[i];
-    const float l = t[i] >= 0.5f ? 1.f : 0.f;
-    const float v = fmaxf(xv, 0.f) - xv * l + log1pf(expf(-fabsf(xv)));
-    a += l; b += l * v; c += (1.f - l) * v;
-  }
-  a = block_sum_256(a, sh); b = block_sum_256(b, sh); c = block_sum_256(c, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = make_float4(a, b, c, 0.f);
-}
-__global__ __launch_bounds__(256) void cbce_final_kernel(const float4* __restrict__ partial, int nb, long n,
-                                                          float* __restrict__ loss, float* __restrict__ scal) {
-  __shared__ double sh[4][3];
-  double a = 0, b = 0, c = 0;
-  for (int i = threadIdx.x; i < nb; i += 256) { const float4 v = partial[i]; a += v.x; b += v.y; c += v.z; }
-  for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); c += __shfl_xor(c, o, 64); }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sh[w][0] = a; sh[w][1] = b; sh[w][2] = c; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double Np = 0, Sp = 0, Sn = 0;
-    for (int k = 0; k < 4; ++k) { Np += sh[k][0]; Sp += sh[k][1]; Sn += sh[k][2]; }
-    const double N = (double)n, Nn = N - Np;
-    loss[0] = (float)((Nn * Sp + Np * Sn) / (N * N));
-    scal[0] = loss[0]; scal[1] = (float)(Nn / (N * N)); scal[2] = (float)(Np / (N * N));
-  }
-}
-__global__ void cbce_grad_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ scal,
-                                 float* __restrict__ dx, long n) {
-  const float wp = scal[1], wn = scal[2];
-  GRID_STRIDE(i, n) {
-    const float xv = x[i];
-    const bool pos = t[i] >= 0.5f;
-    const float e = expf(-fabsf(xv));
-    const float p = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-    dx[i] = pos ? wp * (p - 1.f) : wn * p;
-  }
-}
-void launch_dice(const float* logits, const float* gt, float* dlogits, float* loss, float* partial /*>=4*1024+4*/, int64_t n,
-                 int kind, hipStream_t s) {
-  const int nb = grid_for(n, 256, 1024);
-  if (kind == 3) {
-    hipLaunchKernelGGL(cbce_partial_kernel, dim3(nb), dim3(256), 0, s, logits, gt, (float4*)partial, (long)n);
-    hipLaunchKernelGGL(cbce_final_kernel, dim3(1), dim3(256), 0, s, (const float4*)partial, nb, (long)n, loss,
-                       partial + 4 * 1024);
-    hipLaunchKernelGGL(cbce_grad_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, logits, gt, partial + 4 * 1024,
-                       dlogits, (long)n);
-    return;
-  }
-  hipLaunchKernelGGL(dice_partial_kernel, dim3(nb), dim3(256), 0, s, logits, gt, (float4*)partial, (long)n);
-  hipLaunchKernelGGL(dice_final_kernel, dim3(1), dim3(256), 0, s, (const float4*)partial, nb, (long)n, kind, loss,
-                     partial + 4 * 1024);
-  hipLaunchKernelGGL(dice_grad_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, logits, gt, partial + 4 * 1024, dlogits,
-                     (long)n);
-}
-
-// ---- the same four losses with a void label: a pixel with t == ign is in no sum and no count, its gradient is +0 ------
-// Kernels of their own beside the ones above (which are untouched): the same grids, the same per-thread accumulation order
-// and the same expressions, so that a map without a void pixel gives the bits of the unmasked launch.  A void pixel's
-// logit is selected away, never multiplied by 0 (it may be NaN / inf).  Every kind is partial -> final -> grad: the valid
-// count |V| is known only after the first pass.  Counts are per-block integers summed in a fixed order.
-//   partial floats: [0, 4096) per-block sums, [4096, 4112) scalars of the final kernel, [4112, 5136) per-block valid counts
-constexpr int LOSS_IGN_SCAL = 4 * 1024, LOSS_IGN_CNT = 4 * 1024 + 16;
-__device__ __forceinline__ int block_sum_256_i(int v, int* sh /*>=4 ints*/) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
 // |V| from the per-block counts, valid in every thread
 __device__ __forceinline__ long valid_total(const int* __restrict__ cnt, int nb, int* shi) {
   long c = 0;                                     // (a block counts < 2^31 pixels; the total may not fit an int)
   for (int i = threadIdx.x; i < nb; i += 256) c += cnt[i];
-  const int lo = block_sum_256_i((int)(c & 0xffff), shi), hi = block_sum_256_i((int)(c >> 16), shi);
+  const int lo = block_sum_i((int)(c & 0xffff), shi), hi = block_sum_i((int)(c >> 16), shi);
   return ((long)hi << 16) + lo;
 }
-__global__ __launch_bounds__(256) void bce_ign_partial_kernel(const float* __restrict__ x, const float* __restrict__ t,
-                                                               float* __restrict__ partial, int* __restrict__ cnt, long n,
-                                                               float ign) {
+__device__ __forceinline__ float bce_grad(float xv, float tv, float e /*exp(-|xv|)*/, float inv_n) {
+  const float sig = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+  return (sig - tv) * inv_n;
+}
+// VOID = false: dx = dL/dx with the host's inv_n = 1 / n
+template <bool VOID>
+__global__ __launch_bounds__(256) void bce_partial_kernel(const float* __restrict__ x, const float* __restrict__ t,
+                                                           float* __restrict__ dx, float* __restrict__ partial,
+                                                           int* __restrict__ cnt, long n, float inv_n, float ign) {
   __shared__ float sh[4];
   __shared__ int shi[4];
   float s = 0.f;
   int c = 0;
   GRID_STRIDE(i, n) {
     const float xv = x[i], tv = t[i];
-    const bool ok = tv != ign;
+    const bool ok = !VOID || tv != ign;
     const float e = expf(-fabsf(xv));
     const float v = fmaxf(xv, 0.f) - xv * tv + log1pf(e);
     s = ok ? s + v : s;
     c += ok ? 1 : 0;
+    if constexpr (!VOID) dx[i] = bce_grad(xv, tv, e, inv_n);
   }
   s = block_sum_256(s, sh);
-  c = block_sum_256_i(c, shi);
-  if (threadIdx.x == 0) { partial[blockIdx.x] = s; cnt[blockIdx.x] = c; }
+  if constexpr (VOID) c = block_sum_i(c, shi);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = s;
+    if constexpr (VOID) cnt[blockIdx.x] = c;
+  }
 }
-// scal = {loss, 1 / |V|} (0 for an empty V)
-__global__ __launch_bounds__(256) void bce_ign_final_kernel(const float* __restrict__ partial, const int* __restrict__ cnt,
-                                                             float* __restrict__ loss, float* __restrict__ scal, int nb) {
+// VOID: scal = {loss, 1 / |V|} (0 for an empty V)
+template <bool VOID>
+__global__ __launch_bounds__(256) void bce_final_kernel(const float* __restrict__ partial, const int* __restrict__ cnt,
+                                                         float* __restrict__ loss, float* __restrict__ scal, int nb,
+                                                         float inv_n) {
   __shared__ float sh[4];
   __shared__ int shi[4];
   float s = 0.f;
   for (int i = threadIdx.x; i < nb; i += 256) s += partial[i];
   s = block_sum_256(s, sh);
-  const long V = valid_total(cnt, nb, shi);
-  if (threadIdx.x == 0) {
-    const float inv = V > 0 ? 1.0f / (float)V : 0.f;
-    loss[0] = V > 0 ? s * inv : 0.f;
-    scal[0] = loss[0]; scal[1] = inv;
+  if constexpr (VOID) {
+    const long V = valid_total(cnt, nb, shi);
+    if (threadIdx.x == 0) {
+      const float inv = V > 0 ? 1.0f / (float)V : 0.f;
+      loss[0] = V > 0 ? s * inv : 0.f;
+      scal[0] = loss[0]; scal[1] = inv;
+    }
+  } else if (threadIdx.x == 0) {
+    loss[0] = s * inv_n;
   }
 }
-__global__ void bce_ign_grad_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ scal,
-                                    float* __restrict__ dx, long n, float ign) {
+// the third pass of BCE with a void label
+__global__ void bce_grad_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ scal,
+                                float* __restrict__ dx, long n, float ign) {
   const float inv_n = scal[1];
   GRID_STRIDE(i, n) {
     const float xv = x[i], tv = t[i];
     const float e = expf(-fabsf(xv));
-    const float sig = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-    dx[i] = tv != ign ? (sig - tv) * inv_n : 0.f;
+    const float g = bce_grad(xv, tv, e, inv_n);
+    dx[i] = tv != ign ? g : 0.f;
   }
 }
-__global__ __launch_bounds__(256) void dice_ign_partial_kernel(const float* __restrict__ x, const float* __restrict__ t,
-                                                                float4* __restrict__ partial, int* __restrict__ cnt, long n,
-                                                                float ign) {
+// dice / BCE+dice (loss_dice.py:4-40, helper_func.py:43-54), batch_average=True
+// stage 1: per-block partials {sum p*y, sum p, sum y, sum bce}; stage 2: scalars; stage 3: dlogits
+template <bool VOID>
+__global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restrict__ x, const float* __restrict__ t,
+                                                            float4* __restrict__ partial, int* __restrict__ cnt, long n,
+                                                            float ign) {
   __shared__ float sh[4];
   __shared__ int shi[4];
   float a = 0.f, b = 0.f, c = 0.f, d = 0.f;
   int k = 0;
   GRID_STRIDE(i, n) {
     const float xv = x[i], tv = t[i];
-    const bool ok = tv != ign;
+    const bool ok = !VOID || tv != ign;
     const float e = expf(-fabsf(xv));
     const float p = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
     const float v = fmaxf(xv, 0.f) - xv * tv + log1pf(e);
@@ -1669,13 +1540,18 @@ __global__ __launch_bounds__(256) void dice_ign_partial_kernel(const float* __re
     k += ok ? 1 : 0;
   }
   a = block_sum_256(a, sh); b = block_sum_256(b, sh); c = block_sum_256(c, sh); d = block_sum_256(d, sh);
-  k = block_sum_256_i(k, shi);
-  if (threadIdx.x == 0) { partial[blockIdx.x] = make_float4(a, b, c, d); cnt[blockIdx.x] = k; }
+  if constexpr (VOID) k = block_sum_i(k, shi);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = make_float4(a, b, c, d);
+    if constexpr (VOID) cnt[blockIdx.x] = k;
+  }
 }
-// dice_final_kernel with |V| in the place of n; an empty V gives num = D = 1: dice = 0, -log(1 - 0) = 0, and no BCE term
-__global__ __launch_bounds__(256) void dice_ign_final_kernel(const float4* __restrict__ partial, const int* __restrict__ cnt,
-                                                              int nb, int kind, float* __restrict__ loss,
-                                                              float* __restrict__ scal) {
+// scal = {loss, c_y, c_1, bce_w}:  dL/dx = bce_w*(p - y) + (c_y*y + c_1)*p*(1-p)
+// VOID: |V| in the place of n; an empty V gives num = D = 1: dice = 0, -log(1 - 0) = 0, and no BCE term
+template <bool VOID>
+__global__ __launch_bounds__(256) void dice_final_kernel(const float4* __restrict__ partial, const int* __restrict__ cnt,
+                                                          int nb, long n, int kind, float* __restrict__ loss,
+                                                          float* __restrict__ scal) {
   __shared__ double sh[4][4];
   __shared__ int shi[4];
   double a = 0, b = 0, c = 0, d = 0;
@@ -1683,56 +1559,67 @@ __global__ __launch_bounds__(256) void dice_ign_final_kernel(const float4* __res
   for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); c += __shfl_xor(c, o, 64); d += __shfl_xor(d, o, 64); }
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) { sh[w][0] = a; sh[w][1] = b; sh[w][2] = c; sh[w][3] = d; }
-  const long V = valid_total(cnt, nb, shi);       // (its barriers also publish sh)
+  long V = n;
+  if constexpr (VOID) V = valid_total(cnt, nb, shi);   // (its barriers also publish sh)
+  else __syncthreads();
   if (threadIdx.x == 0) {
     double I = 0, Sp = 0, Sy = 0, Sb = 0;
     for (int k = 0; k < 4; ++k) { I += sh[k][0]; Sp += sh[k][1]; Sy += sh[k][2]; Sb += sh[k][3]; }
     const double num = 2.0 * I + 1.0, D = Sp + Sy + 1.0;
     const double dice = 1.0 - num / D;
-    if (kind == 1) {
+    const bool any = !VOID || V > 0;
+    if (kind == 1) {            // dice:  dL/dp = -(2y*D - num)/D^2
       loss[0] = (float)dice;
       scal[1] = (float)(-2.0 / D); scal[2] = (float)(num / (D * D)); scal[3] = 0.f;
-    } else {
-      loss[0] = V > 0 ? (float)(Sb / (double)V - log(num / D)) : 0.f;
-      scal[1] = (float)(-2.0 / num); scal[2] = (float)(1.0 / D); scal[3] = V > 0 ? (float)(1.0 / (double)V) : 0.f;
+    } else {                    // BCE - log(1 - dice) = BCE - log(num/D):  dL/dp = -2y/num + 1/D
+      loss[0] = any ? (float)(Sb / (double)V - log(num / D)) : 0.f;
+      scal[1] = (float)(-2.0 / num); scal[2] = (float)(1.0 / D); scal[3] = any ? (float)(1.0 / (double)V) : 0.f;
     }
     scal[0] = loss[0];
   }
 }
-__global__ void dice_ign_grad_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ scal,
-                                     float* __restrict__ dx, long n, float ign) {
+template <bool VOID>
+__global__ void dice_grad_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ scal,
+                                 float* __restrict__ dx, long n, float ign) {
   const float cy = scal[1], c1 = scal[2], bw = scal[3];
   GRID_STRIDE(i, n) {
     const float xv = x[i], tv = t[i];
     const float e = expf(-fabsf(xv));
     const float p = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-    dx[i] = tv != ign ? bw * (p - tv) + (cy * tv + c1) * p * (1.f - p) : 0.f;
+    dx[i] = (!VOID || tv != ign) ? bw * (p - tv) + (cy * tv + c1) * p * (1.f - p) : 0.f;
   }
 }
-// class-balanced BCE over V (loss_ce.py:42-53): N_pos, N_neg and the two sums run over V, num_total = |V|; the two trailing
-// divisions (`:55`, `:58`) stay those of the tensor's full shape, n:  L = (N_neg * S_pos + N_pos * S_neg) / (|V| * n)
-__global__ __launch_bounds__(256) void cbce_ign_partial_kernel(const float* __restrict__ x, const float* __restrict__ t,
-                                                                float4* __restrict__ partial, int* __restrict__ cnt, long n,
-                                                                float ign) {
+// class-balanced cross entropy (loss_ce.py:15-60, batch_average = size_average = True):
+//   labels = gt >= .5;  L = (N_neg * sum_pos bce + N_pos * sum_neg bce) / N^2
+// VOID (loss_ce.py:42-53): N_pos, N_neg and the two sums run over V, num_total = |V|; the two trailing divisions (`:55`,
+// `:58`) stay those of the tensor's full shape, n:  L = (N_neg * S_pos + N_pos * S_neg) / (|V| * n)
+template <bool VOID>
+__global__ __launch_bounds__(256) void cbce_partial_kernel(const float* __restrict__ x, const float* __restrict__ t,
+                                                            float4* __restrict__ partial, int* __restrict__ cnt, long n,
+                                                            float ign) {
   __shared__ float sh[4];
   __shared__ int shi[4];
   float a = 0.f, b = 0.f, c = 0.f;
   int k = 0;
   GRID_STRIDE(i, n) {
     const float xv = x[i], tv = t[i];
-    const bool ok = tv != ign;
+    const bool ok = !VOID || tv != ign;
     const float l = tv >= 0.5f ? 1.f : 0.f;
     const float v = fmaxf(xv, 0.f) - xv * l + log1pf(expf(-fabsf(xv)));
     a = ok ? a + l : a; b = ok ? b + l * v : b; c = ok ? c + (1.f - l) * v : c;
     k += ok ? 1 : 0;
   }
   a = block_sum_256(a, sh); b = block_sum_256(b, sh); c = block_sum_256(c, sh);
-  k = block_sum_256_i(k, shi);
-  if (threadIdx.x == 0) { partial[blockIdx.x] = make_float4(a, b, c, 0.f); cnt[blockIdx.x] = k; }
+  if constexpr (VOID) k = block_sum_i(k, shi);
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = make_float4(a, b, c, 0.f);
+    if constexpr (VOID) cnt[blockIdx.x] = k;
+  }
 }
-__global__ __launch_bounds__(256) void cbce_ign_final_kernel(const float4* __restrict__ partial, const int* __restrict__ cnt,
-                                                              int nb, long n, float* __restrict__ loss,
-                                                              float* __restrict__ scal) {
+template <bool VOID>
+__global__ __launch_bounds__(256) void cbce_final_kernel(const float4* __restrict__ partial, const int* __restrict__ cnt,
+                                                          int nb, long n, float* __restrict__ loss,
+                                                          float* __restrict__ scal) {
   __shared__ double sh[4][3];
   __shared__ int shi[4];
   double a = 0, b = 0, c = 0;
@@ -1740,18 +1627,22 @@ __global__ __launch_bounds__(256) void cbce_ign_final_kernel(const float4* __res
   for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); c += __shfl_xor(c, o, 64); }
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) { sh[w][0] = a; sh[w][1] = b; sh[w][2] = c; }
-  const long V = valid_total(cnt, nb, shi);       // (its barriers also publish sh)
+  long V = n;
+  if constexpr (VOID) V = valid_total(cnt, nb, shi);   // (its barriers also publish sh)
+  else __syncthreads();
   if (threadIdx.x == 0) {
     double Np = 0, Sp = 0, Sn = 0;
     for (int k = 0; k < 4; ++k) { Np += sh[k][0]; Sp += sh[k][1]; Sn += sh[k][2]; }
     const double N = (double)n, T = (double)V, Nn = T - Np;
-    loss[0] = V > 0 ? (float)((Nn * Sp + Np * Sn) / (T * N)) : 0.f;
+    const bool any = !VOID || V > 0;
+    loss[0] = any ? (float)((Nn * Sp + Np * Sn) / (T * N)) : 0.f;
     scal[0] = loss[0];
-    scal[1] = V > 0 ? (float)(Nn / (T * N)) : 0.f; scal[2] = V > 0 ? (float)(Np / (T * N)) : 0.f;
+    scal[1] = any ? (float)(Nn / (T * N)) : 0.f; scal[2] = any ? (float)(Np / (T * N)) : 0.f;
   }
 }
-__global__ void cbce_ign_grad_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ scal,
-                                     float* __restrict__ dx, long n, float ign) {
+template <bool VOID>
+__global__ void cbce_grad_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ scal,
+                                 float* __restrict__ dx, long n, float ign) {
   const float wp = scal[1], wn = scal[2];
   GRID_STRIDE(i, n) {
     const float xv = x[i], tv = t[i];
@@ -1759,31 +1650,35 @@ __global__ void cbce_ign_grad_kernel(const float* __restrict__ x, const float* _
     const float e = expf(-fabsf(xv));
     const float p = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
     const float g = pos ? wp * (p - 1.f) : wn * p;
-    dx[i] = tv != ign ? g : 0.f;
+    dx[i] = (!VOID || tv != ign) ? g : 0.f;
   }
 }
-void launch_loss_ignore(const float* logits, const float* gt, float* dlogits, float* loss, float* partial, int64_t n, int kind,
-                        float ignore, hipStream_t s) {
-  float* scal = partial + LOSS_IGN_SCAL;
-  int* cnt = (int*)(partial + LOSS_IGN_CNT);
-  const dim3 one(1), block(256), all(grid_for(n, 256));
+template <bool VOID>
+static void loss_launches(int kind, const float* logits, const float* gt, float* dlogits, float* loss, float* partial, long n,
+                          float ign, hipStream_t s) {
+  float* scal = partial + LOSS_SCAL;
+  int* cnt = (int*)(partial + LOSS_CNT);
+  const int nb = grid_for(n, 256, LOSS_BLOCKS);
+  const dim3 one(1), block(256), part(nb), all(grid_for(n, 256));
   if (kind == 0) {
-    const int nb = grid_for(n, 256, BCE_BLOCKS);
-    hipLaunchKernelGGL(bce_ign_partial_kernel, dim3(nb), block, 0, s, logits, gt, partial, cnt, (long)n, ignore);
-    hipLaunchKernelGGL(bce_ign_final_kernel, one, block, 0, s, partial, cnt, loss, scal, nb);
-    hipLaunchKernelGGL(bce_ign_grad_kernel, all, block, 0, s, logits, gt, scal, dlogits, (long)n, ignore);
-    return;
+    const float inv_n = 1.0f / (float)n;
+    hipLaunchKernelGGL((bce_partial_kernel<VOID>), part, block, 0, s, logits, gt, dlogits, partial, cnt, n, inv_n, ign);
+    hipLaunchKernelGGL((bce_final_kernel<VOID>), one, block, 0, s, partial, cnt, loss, scal, nb, inv_n);
+    if (VOID) hipLaunchKernelGGL(bce_grad_kernel, all, block, 0, s, logits, gt, scal, dlogits, n, ign);
+  } else if (kind == 3) {
+    hipLaunchKernelGGL((cbce_partial_kernel<VOID>), part, block, 0, s, logits, gt, (float4*)partial, cnt, n, ign);
+    hipLaunchKernelGGL((cbce_final_kernel<VOID>), one, block, 0, s, (const float4*)partial, cnt, nb, n, loss, scal);
+    hipLaunchKernelGGL((cbce_grad_kernel<VOID>), all, block, 0, s, logits, gt, scal, dlogits, n, ign);
+  } else {
+    hipLaunchKernelGGL((dice_partial_kernel<VOID>), part, block, 0, s, logits, gt, (float4*)partial, cnt, n, ign);
+    hipLaunchKernelGGL((dice_final_kernel<VOID>), one, block, 0, s, (const float4*)partial, cnt, nb, n, kind, loss, scal);
+    hipLaunchKernelGGL((dice_grad_kernel<VOID>), all, block, 0, s, logits, gt, scal, dlogits, n, ign);
   }
-  const int nb = grid_for(n, 256, 1024);
-  if (kind == 3) {
-    hipLaunchKernelGGL(cbce_ign_partial_kernel, dim3(nb), block, 0, s, logits, gt, (float4*)partial, cnt, (long)n, ignore);
-    hipLaunchKernelGGL(cbce_ign_final_kernel, one, block, 0, s, (const float4*)partial, cnt, nb, (long)n, loss, scal);
-    hipLaunchKernelGGL(cbce_ign_grad_kernel, all, block, 0, s, logits, gt, scal, dlogits, (long)n, ignore);
-    return;
-  }
-  hipLaunchKernelGGL(dice_ign_partial_kernel, dim3(nb), block, 0, s, logits, gt, (float4*)partial, cnt, (long)n, ignore);
-  hipLaunchKernelGGL(dice_ign_final_kernel, one, block, 0, s, (const float4*)partial, cnt, nb, kind, loss, scal);
-  hipLaunchKernelGGL(dice_ign_grad_kernel, all, block, 0, s, logits, gt, scal, dlogits, (long)n, ignore);
+}
+void launch_loss(int kind, const float* logits, const float* gt, float* dlogits, float* loss, float* partial, int64_t n,
+                 const float* ignore, hipStream_t s) {
+  if (ignore) loss_launches<true>(kind, logits, gt, dlogits, loss, partial, (long)n, *ignore, s);
+  else loss_launches<false>(kind, logits, gt, dlogits, loss, partial, (long)n, 0.f, s);
 }
 
 // ---- pseudo-label targets of online adaptation with an uncertainty band -----------------------------------------------

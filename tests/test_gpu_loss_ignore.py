@@ -148,6 +148,41 @@ def test_without_a_void_pixel_the_bits_are_those_of_the_plain_call(eng, kind):
     assert np.array_equal(a, b) and np.array_equal(ga, gb), kind
 
 
+BIG = (296, 296)                                        # batch 3: the engine's scratch holds BIG_N elements
+BIG_N = 1024 * 256 + 257
+
+
+@pytest.fixture(scope='module')
+def big_eng(weights):
+    from eosvos_amd.engine import Engine
+    e = Engine('resnet50', *BIG, max_batch=3, device=DEV)
+    e.load_model_state(*weights)
+    x, _ = synthetic.synthetic_frames(3, *BIG, seed=3)
+    e.forward(x.to(DEV), want_logits=False)
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize('pattern', ['none', 'random30'])
+@pytest.mark.parametrize('kind', [k for k in R.KINDS if k not in LOVASZ])
+def test_second_trip_of_the_partial_grid(big_eng, kind, pattern):
+    """The partial grids cap at 1024 blocks of 256 threads: 1024 * 256 + 257 elements is the smallest size at which the
+    grid-stride loop runs a second time, with a ragged tail.  (The Lovasz grids are per tile and run at 3 x 480 x 854 in
+    test_gpu_lovasz.py.)  Without a void pixel: the bits of the plain call; with 30 % void: the fp64 restatement."""
+    n = BIG_N
+    x, t, void = make_case(n, pattern, seed=53)
+    xd, td = dev(x), dev(t)
+    loss = big_eng.loss_of(kind, xd, td, ignore=IGN).cpu().numpy()
+    grad = dlogits_of(big_eng, n).copy()
+    if pattern == 'none':
+        plain = big_eng.loss_of(kind, xd, td).cpu().numpy()
+        assert np.array_equal(loss.view(np.uint32), plain.view(np.uint32)), (kind, loss, plain)
+        assert np.array_equal(grad.view(np.uint32), dlogits_of(big_eng, n).view(np.uint32)), kind
+    else:
+        ref_loss, ref_grad = R.one_set(kind, x, t, IGN)
+        check(f'{kind} n={n} {pattern}', kind, float(loss[0]), grad, ref_loss, ref_grad, void)
+
+
 @pytest.mark.parametrize('kind', R.KINDS)
 def test_non_finite_logits_at_void_pixels_never_reach_the_loss(eng, kind):
     n = 4097
