@@ -136,6 +136,16 @@ FILL = {
 }
 
 
+# Superpixel snapping of the evaluation's label maps, handled like EXTENSIONS, POSTPROCESS, CLEANUP and FILL (not part of BASE,
+# added by `parse_cli` only when the command line sets one of its keys: `eval_snap.step=16 eval_snap.min_share=0.6` -- example
+# values, untuned; read with `cfg.get(...)`).
+#   eval_snap         between the CRF and the component filter, every SLIC superpixel of the frame takes its majority label
+#                     (`snap.py`); the value below is the neutral one (`snap.DEFAULTS`: step 0, nothing new is called)
+SNAP = {
+    'eval_snap': {'step': 0, 'iterations': 5, 'compactness': 10, 'min_share': 0.5},
+}
+
+
 def _merge(dst, src):
     for k, v in src.items():
         if isinstance(v, dict) and isinstance(dst.get(k), dict):
@@ -182,7 +192,7 @@ def parse_cli(argv):
             raise KeyError(f'unknown named config: {a}')
     for k, v in updates:
         group = k.split('.')[0]
-        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL):
+        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL, SNAP):
             if group in groups and group not in cfg:
                 cfg[group] = copy.deepcopy(groups[group])
         _set_dotted(cfg, k, v)
@@ -198,6 +208,9 @@ def parse_cli(argv):
     if 'eval_holes' in cfg:
         from .holes import check as check_holes
         check_holes(cfg['eval_holes'])                      # ValueError: max_area -1, prev_overlap 1.5, ...
+    if 'eval_snap' in cfg:
+        from .snap import check as check_snap
+        check_snap(cfg['eval_snap'])                        # ValueError: step 3, compactness 65, ...
     unsupported(cfg)
     return cfg
 

@@ -208,7 +208,7 @@ struct eosvos_engine {
   size_t davis_cap = 0;
   void* crf_buf = nullptr;              // eosvos_crf_labels: unary + the two Q planes of the mean field (grow-only, freed by destroy)
   size_t crf_cap = 0;
-  void* ccl_buf = nullptr;              // eosvos_label_components / eosvos_filter_components / eosvos_fill_holes: union-find, ids, areas, flags (grow-only, freed by destroy)
+  void* ccl_buf = nullptr;              // eosvos_label_components / eosvos_filter_components / eosvos_fill_holes: union-find, ids, areas, flags; eosvos_superpixels / eosvos_snap_labels: ids, centres, sums, votes (grow-only, freed by destroy)
   size_t ccl_cap = 0;
   int lr_level = EOSVOS_LR_NEURON, lr_log = 0;
   float *lr_elem = nullptr, *glr_tmp = nullptr, *ptmp = nullptr;
@@ -2888,6 +2888,80 @@ int eosvos_fill_holes(eosvos_engine* e, const uint8_t* labels, int n_frames, int
   }
   if (filled_out) {
     HIPOK(hipMemcpyAsync(filled_out, filled, (size_t)n_frames * sizeof(int64_t), hipMemcpyDeviceToHost, e->s));
+    HIPOK(hipStreamSynchronize(e->s));
+  }
+  return 0;
+}
+
+// ---- SLIC superpixels and the superpixel vote on the merged label maps (between the CRF and the component filter) ----------
+// argument checks shared by the two entry points; `who` names the entry point in the message
+static int slic_check(const char* who, int n_frames, int height, int width, int step, int iterations, int compactness) {
+  const std::string w(who);
+  if (n_frames < 0 || height < 1 || width < 1) return fail(w + ": bad frame geometry");
+  if (height > 4096 || width > 4096) return fail(w + ": frames larger than 4096 pixels a side are not supported");
+  if (step < 4 || step > 64) return fail(w + ": step must be in [4, 64]");
+  if (iterations < 1 || iterations > 20) return fail(w + ": iterations must be in [1, 20]");
+  if (compactness < 1 || compactness > 64) return fail(w + ": compactness must be in [1, 64]");
+  if (n_frames > 65535) return fail(w + ": at most 65535 frames per call");
+  return 0;
+}
+
+// rules 1-4: init, (iterations - 1) x (assign + update), the last assign (with `labels` it also counts the votes)
+static void slic_run(const uint8_t* rgb, const uint8_t* labels, int n_frames, int height, int width, int step, int iterations,
+                     int compactness, int n_obj, int* centres, unsigned* sums, int* ids, unsigned* votes, hipStream_t s) {
+  launch_slic_init(rgb, n_frames, height, width, step, centres, s);
+  for (int t = 1; t < iterations; ++t) launch_slic_iterate(rgb, n_frames, height, width, step, compactness, centres, sums, s);
+  launch_slic_last(rgb, labels, n_frames, height, width, step, compactness, n_obj, centres, ids, votes, s);
+}
+
+int eosvos_superpixels(eosvos_engine* e, const uint8_t* rgb, int n_frames, int height, int width, int step, int iterations,
+                       int compactness, int32_t* ids_out) {
+  if (!e || !rgb || !ids_out) return fail("superpixels: null argument");
+  if (slic_check("superpixels", n_frames, height, width, step, iterations, compactness)) return 1;
+  if (n_frames == 0) return 0;
+  const size_t K = (size_t)((height + step - 1) / step) * ((width + step - 1) / step), nk = (size_t)n_frames * K;
+  if (ccl_scratch(e, "superpixels", 11 * nk * sizeof(int), n_frames)) return 1;      // [centres: 5 | sums: 6] words per cluster
+  int* centres = (int*)e->ccl_buf;
+  unsigned* sums = (unsigned*)(centres + 5 * nk);
+  HIPOK(hipMemsetAsync(sums, 0, 6 * nk * sizeof(unsigned), e->s));
+  slic_run(rgb, nullptr, n_frames, height, width, step, iterations, compactness, 0, centres, sums, ids_out, nullptr, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+
+int eosvos_snap_labels(eosvos_engine* e, const uint8_t* rgb, const uint8_t* labels, int n_frames, int height, int width, int n_obj,
+                       int step, int iterations, int compactness, int min_share_q16, const uint8_t* keep, uint8_t* out,
+                       int64_t* changed_out) {
+  if (!e || !rgb || !labels || !out) return fail("snap_labels: null argument");
+  if (slic_check("snap_labels", n_frames, height, width, step, iterations, compactness)) return 1;
+  if (n_obj < 1 || n_obj > 255) return fail("snap_labels: n_obj must be in [1, 255]");
+  if (min_share_q16 < 0 || min_share_q16 > 65536) return fail("snap_labels: min_share_q16 must be in [0, 65536]");
+  if (n_frames == 0) return 0;
+  const size_t P = (size_t)height * width, np = (size_t)n_frames * P;
+  const size_t K = (size_t)((height + step - 1) / step) * ((width + step - 1) / step), nk = (size_t)n_frames * K;
+  const size_t nl = (size_t)n_obj + 1;
+  // [ids: 1 per pixel | centres: 5 | sums: 6 | votes: n_obj + 1 per cluster] 32-bit words, pad to 8 bytes, [changed: 1 per
+  // frame] 64-bit words; everything from `sums` on starts out as 0
+  const size_t words = np + (11 + nl) * nk;
+  const size_t changed_at = (words * 4 + 7) / 8 * 8;
+  const size_t need = changed_at + (size_t)n_frames * 8;
+  if (ccl_scratch(e, "snap_labels", need, n_frames)) return 1;
+  int* ids = (int*)e->ccl_buf;
+  int* centres = ids + np;
+  unsigned *sums = (unsigned*)(centres + 5 * nk), *votes = sums + 6 * nk;
+  unsigned long long* changed = (unsigned long long*)((char*)e->ccl_buf + changed_at);
+  HIPOK(hipMemsetAsync(sums, 0, need - (np + 5 * nk) * sizeof(int), e->s));
+  slic_run(rgb, labels, n_frames, height, width, step, iterations, compactness, n_obj, centres, sums, ids, votes, e->s);
+  HIPOK(hipGetLastError());
+  auto kept = [&](int f) { return keep && keep[f] ? 1 : 0; };
+  for (int f = 0, g; f < n_frames; f = g) {                        // one apply launch per run of frames with the same `keep` flag
+    for (g = f + 1; g < n_frames && kept(g) == kept(f); ++g) {}
+    launch_slic_apply(labels + f * P, ids + f * P, votes + f * K * nl, kept(f), g - f, height, width, step, n_obj,
+                      (unsigned)min_share_q16, out + f * P, changed + f, e->s);
+    HIPOK(hipGetLastError());
+  }
+  if (changed_out) {
+    HIPOK(hipMemcpyAsync(changed_out, changed, (size_t)n_frames * sizeof(int64_t), hipMemcpyDeviceToHost, e->s));
     HIPOK(hipStreamSynchronize(e->s));
   }
   return 0;

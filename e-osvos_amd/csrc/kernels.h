@@ -459,6 +459,20 @@ void launch_hole_apply(const uint8_t* labels, const int* ids, const int* area, c
                        unsigned rel_q16, unsigned overlap_q16, uint8_t* out, uint8_t* pres_out, unsigned long long* filled,
                        hipStream_t s);
 
+// SLIC superpixels of uint8 frames and the superpixel vote on uint8 label maps (slic_kernels.hip; the rules: include/eosvos.h,
+// eosvos_superpixels / eosvos_snap_labels).  rgb [frame][3][H][W]; K = ceil(H / S) * ceil(W / S) clusters per frame; centres
+// [frame][K][5] (y, x, R, G, B), sums [frame][K][6] (n and the sums of y, x, R, G, B; zeroed by the caller once, kept zero by
+// launch_slic_iterate), ids [frame][H * W], votes [frame][K][n_obj + 1] and changed [frame] (both zeroed by the caller).
+// launch_slic_init: the centres of rule 1.  launch_slic_iterate: one assign + update (two launches).  launch_slic_last: the
+// last assign -> ids; with labels (not null) also the votes.  launch_slic_apply: winner and share rule per cluster -> out and
+// the pixels changed per frame; keep_all: the frames are copied unchanged.
+void launch_slic_init(const uint8_t* rgb, int n_frames, int H, int W, int S, int* centres, hipStream_t s);
+void launch_slic_iterate(const uint8_t* rgb, int n_frames, int H, int W, int S, int m, int* centres, unsigned* sums, hipStream_t s);
+void launch_slic_last(const uint8_t* rgb, const uint8_t* labels, int n_frames, int H, int W, int S, int m, int n_obj,
+                      const int* centres, int* ids, unsigned* votes, hipStream_t s);
+void launch_slic_apply(const uint8_t* labels, const int* ids, const unsigned* votes, int keep_all, int n_frames, int H, int W,
+                       int S, int n_obj, unsigned q16, uint8_t* out, unsigned long long* changed, hipStream_t s);
+
 // theta' = theta - lr[cout]*g, g = rowscale[cout] * sum_z ws[z][...]; optional gsum += g; g_out = g
 void launch_sgd_update(float* w, const float* ws, int splits, int64_t slab, const float* rowscale,
                        const float* lr, float* gsum, float* gout, int64_t rowlen, int64_t n,

@@ -692,6 +692,65 @@ class Engine:
             prev = out[g - 1]
         return (out, filled) if return_filled else out
 
+    def _check_rgb(self, who, rgb, labels=None):
+        from . import snap
+        for t in (rgb, labels):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.uint8):
+                raise ValueError(f'{who}: rgb and labels must be uint8 tensors on {self.device}')
+        snap._check_rgb(who, rgb, labels)
+
+    def superpixels(self, rgb, step=16, iterations=5, compactness=10):
+        """Integer SLIC superpixels (`eosvos_superpixels`; the rules: `snap.py`).  rgb (N, 3, H, W) uint8 on the engine's device
+        (`snap.quantise` makes it from fp32 frames), any H and W within the limits -> ids (N, H, W) int32, the cluster
+        cy * gx + cx of every pixel.  Nothing waits for the GPU; the frames go through in chunks under `snap.SCRATCH_CAP`."""
+        from . import snap
+        p = snap.check(dict(step=step, iterations=iterations, compactness=compactness))
+        if p['step'] == 0:
+            raise ValueError('superpixels: step=0 means "off" for the snapping stage; pass a step in [4, 64]')
+        self._check_rgb('superpixels', rgb)
+        self._check_stream()
+        rgb = rgb.contiguous()
+        n, _, h, w = rgb.shape
+        ids = torch.empty(n, h, w, dtype=torch.int32, device=self.device)
+        chunk = snap.frames_per_call(0, h, w, p['step'])
+        for f in range(0, n, chunk):
+            g = min(f + chunk, n)
+            _ffi.check(self.lib.eosvos_superpixels(self.h, _ptr(rgb[f:g]), g - f, h, w, p['step'], p['iterations'], p['compactness'],
+                                                   _ptr(ids[f:g])))
+        return ids
+
+    def snap_labels(self, rgb, labels, n_obj=255, step=16, iterations=5, compactness=10, min_share=0.5, keep=(),
+                    return_changed=False):
+        """The superpixel snapping of `snap.py` (`eosvos_snap_labels`).  rgb (N, 3, H, W) and labels (N, H, W) uint8 on the
+        engine's device, n_obj: labels above it neither vote nor change, keep: frame indices copied unchanged -> snapped maps
+        (N, H, W) uint8; with `return_changed` also the pixels changed per frame as an (N,) int64 numpy array (this waits for the
+        GPU).  step 0 copies.  The frames go through in chunks under `snap.SCRATCH_CAP`."""
+        import numpy as np
+        from . import snap
+        p = snap.check(dict(step=step, iterations=iterations, compactness=compactness, min_share=min_share))
+        n_obj = snap._check_n_obj(n_obj)
+        self._check_rgb('snap_labels', rgb, labels)
+        self._check_stream()
+        rgb, labels = rgb.contiguous(), labels.contiguous()
+        n, h, w = labels.shape
+        changed = np.zeros(n, dtype=np.int64)
+        if p['step'] == 0:
+            return (labels.clone(), changed) if return_changed else labels.clone()
+        flags = bytearray(n)
+        for f in keep:
+            if 0 <= int(f) < n:
+                flags[int(f)] = 1
+        out = torch.empty_like(labels)
+        changed_p = ctypes.POINTER(ctypes.c_int64)
+        chunk = snap.frames_per_call(n_obj, h, w, p['step'])
+        for f in range(0, n, chunk):
+            g = min(f + chunk, n)
+            _ffi.check(self.lib.eosvos_snap_labels(
+                self.h, _ptr(rgb[f:g]), _ptr(labels[f:g]), g - f, h, w, n_obj, p['step'], p['iterations'], p['compactness'],
+                snap.share_q16(p['min_share']), bytes(flags[f:g]), _ptr(out[f:g]),
+                changed[f:g].ctypes.data_as(changed_p) if return_changed else None))
+        return (out, changed) if return_changed else out
+
     # ---- meta-training ----------------------------------------------------------------
     def meta_task_begin(self):
         _ffi.check(self.lib.eosvos_meta_task_begin(self.h))

@@ -23,6 +23,7 @@ import torch
 from . import components as component_filter
 from . import crf as crf_refine
 from . import holes as hole_filler
+from . import snap as snapper
 from . import tta as tta_views
 from .helper_func import compute_loss, early_stopping, set_random_seeds
 
@@ -272,7 +273,7 @@ def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augm
     return out
 
 
-def merge_objects(engine, probs_all, frames=None, crf=None, keep=(), components=None, holes=None):
+def merge_objects(engine, probs_all, frames=None, crf=None, keep=(), components=None, holes=None, snap=None, frame_offset=None):
     """Per-object probabilities [(N,H,W)] -> label maps (N,H,W) uint8 (`evaluate.py:322-326`).
     `crf` (`crf.py`; None or iterations 0: off, the code below as it always was): the local dense CRF refines the merge against
     `frames` (N,3,H,W), one `crf_labels` call per chunk of frames.  The frames listed in `keep` -- the train frame of EVERY
@@ -281,14 +282,23 @@ def merge_objects(engine, probs_all, frames=None, crf=None, keep=(), components=
     connected-component filter zeroes small / non-dominant / ungated components frame by frame; the `keep` frames pass
     unchanged and anchor the gate of the frame after them.
     `holes` (`holes.py`; None or max_area 0: off, nothing new is called): last, enclosed background islands that are small
-    and were object in the previous frame's filled map are filled; the `keep` frames pass unchanged and anchor that chain."""
+    and were object in the previous frame's filled map are filled; the `keep` frames pass unchanged and anchor that chain.
+    `snap` (`snap.py`; None or step 0: off, nothing new is called): between the CRF and the component filter, every SLIC
+    superpixel of `frames` takes the label that holds its majority; the `keep` frames pass unchanged.  `frame_offset`: what the
+    data set subtracted from the RGB frame (`mean_val` under `data_cfg.normalize`), for `snap.quantise`.
+    The chain: merge -> CRF -> snap -> components -> holes."""
     stack = torch.stack(list(probs_all), dim=1)                       # (N, n_obj, H, W)
     clean = component_filter.active(components)
     fill = hole_filler.active(holes)
+    snapping = snapper.active(snap)
+    if snapping and (frames is None or frames.shape[0] != stack.shape[0] or frames.shape[2:] != stack.shape[2:]):
+        raise ValueError('merge_objects: snap needs the frames (N, 3, H, W) of the probabilities it snaps')
     if crf_refine.active(crf):
         labels = _merge_refined(engine, stack, frames, crf, keep)
     else:
         labels = torch.stack([engine.merge_labels(stack[f].contiguous()) for f in range(stack.shape[0])])
+    if snapping:
+        labels = snapper.snap(engine, snapper.quantise(frames, frame_offset), labels, snap, keep=keep, n_obj=stack.shape[1])
     if clean:
         labels = component_filter.filter(engine, labels, components, keep=keep)
     return hole_filler.fill(engine, labels, holes, keep=keep) if fill else labels
@@ -327,8 +337,20 @@ def _holes_kw(holes):
     return {'holes': holes} if hole_filler.active(holes) else {}
 
 
+def _snap_kw(snap, cfg, dataset=None):
+    """As `_holes_kw`: `snap` travels as a keyword, and only when it is set to something that snaps (`snap.active`, which also
+    validates it) -- then with the offset `snap.quantise` needs: the data set's `mean_val` where `data_cfg.normalize` had it
+    subtracted from the frames."""
+    if not snapper.active(snap):
+        return {}
+    if not cfg.get('data_cfg', {}).get('normalize'):
+        return {'snap': snap}
+    from .data import DAVIS
+    return {'snap': snap, 'frame_offset': tuple(getattr(dataset, 'mean_val', DAVIS.mean_val))}
+
+
 def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_gts, cfg, augment=None,
-                      train_frame_id=0, tta=None, crf=None, components=None, holes=None):
+                      train_frame_id=0, tta=None, crf=None, components=None, holes=None, snap=None):
     """frames (N,3,H,W) on the GPU, object_gts: list of (1,H,W) binary masks of the train frame.
     cfg keys (names of cfgs/meta.yaml): num_epochs.eval, eval_online_adapt.{step,reset_model_mode,
     num_epochs,min_prop (a threshold, or [lo, hi]: `min_prop_band`)}, data_cfg.batch_sizes.train, seed, loss_func, train_early_stopping_cfg.
@@ -337,6 +359,7 @@ def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_g
     `components` (`components.py`): the connected-component filter cleans the merged (and refined) maps; the train frame passes
     unchanged and anchors the gate.
     `holes` (`holes.py`): the hole filler runs after the component filter, with the same train frame kept.
+    `snap` (`snap.py`): the superpixel snapping runs between the CRF and the component filter, with the same train frame kept.
     Returns (labels (N,H,W) uint8, per-object probs list, train loss history per object)."""
     probs_all, hist_all = [], []
     for gt in object_gts:
@@ -344,10 +367,10 @@ def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_g
                                       **_tta_kw(tta))
         probs_all.append(probs)
         hist_all.append(hist)
-    if crf is None and components is None and not _holes_kw(holes):
+    if crf is None and components is None and not _holes_kw(holes) and not _snap_kw(snap, cfg):
         return merge_objects(model.engine, probs_all), probs_all, hist_all
     return merge_objects(model.engine, probs_all, frames, crf, keep=(train_frame_id,), **_components_kw(components),
-                         **_holes_kw(holes)), probs_all, hist_all
+                         **_holes_kw(holes), **_snap_kw(snap, cfg)), probs_all, hist_all
 
 
 def prediction_paths(save_dir, dataset_name, split):
@@ -364,7 +387,7 @@ def save_label_png(path, labels_hw):
 
 def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dataset_key, save_dir=None,
                      meta_iter=None, meta_epoch=None, best_mean_J=0.0, dist=None, device=None, vis_win_names=None,
-                     log=None, objects_in_flight=None, tta=None, crf=None, components=None, holes=None):
+                     log=None, objects_in_flight=None, tta=None, crf=None, components=None, holes=None, snap=None):
     """The evaluation worker of `src/util/evaluate.py:111-382` for the DeepLab path: every sequence of `dataset`
     (an `eosvos_amd.data` reader), every object, fine-tune / online adaptation / inference / merge; prediction PNGs
     under `{save_dir}/best_eval_preds/{name}/{split}/{seq}/{frame}.png`, J per sequence, and the
@@ -388,6 +411,8 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
     `components` (`components.py`): the connected-component filter cleans the merged (and refined) label maps before the PNGs,
     J_seq and the J / F counts see them; the same train frame passes unchanged.
     `holes` (`holes.py`): the hole filler runs after the component filter; the PNGs, J_seq and the J / F counts see the filled maps.
+    `snap` (`snap.py`): the superpixel snapping runs between the CRF and the component filter, on the frames quantised back to
+    uint8 RGB; the PNGs, J_seq and the J / F counts see the final maps.
     Returns dict(J_seq, mean_J, best_mean_J, time_per_frame, labels={seq: (N,H,W) uint8}) and the DAVIS J / F statistics
     of `eval_davis_seq` (`evaluate.py:345-359`), one entry per object in sequence order: J_obj (the per-object J means the
     reference calls J_seq), J_recall_seq, J_decay_seq, F_seq, F_recall_seq, F_decay_seq, with mean_F and
@@ -516,11 +541,11 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
         if model.engine is None:                                                # this rank had no item yet
             model._ensure_engine(frames.shape[2], frames.shape[3], 1)
         keep = {'keep': tuple(set(fids)) if len(set(fids)) == 1 else ()} \
-            if crf is not None or components is not None or holes is not None else {}
-        if crf is not None:
+            if crf is not None or components is not None or holes is not None or _snap_kw(snap, cfg) else {}
+        if crf is not None or _snap_kw(snap, cfg):
             keep = dict(frames=frames, **keep)
         labels = merge_objects(model.engine, [probs[o] for o in range(len(gts))], **keep, **_crf_kw(crf),
-                               **_components_kw(components), **_holes_kw(holes))
+                               **_components_kw(components), **_holes_kw(holes), **_snap_kw(snap, cfg, dataset))
         counts = None
         if not dataset.test_mode:                                               # J / F counts where the labels are
             gt_dev = torch.from_numpy(np.ascontiguousarray(gt_maps, dtype=np.uint8)).to(labels.device)

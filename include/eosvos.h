@@ -436,6 +436,56 @@ int eosvos_fill_holes(eosvos_engine* e, const uint8_t* labels, int n_frames, int
                       int max_area, int rel_q16, int overlap_q16, const uint8_t* prev, const uint8_t* keep, uint8_t* out,
                       int64_t* filled_out);
 
+/* ---- SLIC superpixels and the superpixel vote on the merged label maps (between the CRF and the component filter) ----- */
+/* The reference has no such step; the OSVOS family snaps its masks to superpixels of the frame ("contour snapping"): each
+ * superpixel takes the label that holds its majority, which moves a label boundary onto the image edge it belongs to.  The
+ * superpixels are SLIC in its GPU form (gSLIC) restricted to integers.  An opt-in extension; the parameter values shown anywhere
+ * are examples, untuned.
+ * rgb: device uint8 [n_frames][3][height][width], planar (the caller quantises its frames: eosvos_amd/snap.py `quantise`);
+ * labels: device uint8 maps [n_frames][height][width], 0 is background, 1..n_obj are objects.  Frames never interact.  Every
+ * quantity is an integer.  S = step, T = iterations, m = compactness.
+ *   1. grid  gy = ceil(height / S), gx = ceil(width / S), K = gy * gx clusters per frame; the id of cell (cy, cx) is
+ *        cy * gx + cx.  Its initial centre is the pixel (min(cy * S + S / 2, height - 1), min(cx * S + S / 2, width - 1))
+ *        (integer division) and that pixel's colour: a centre is five integers (y, x, R, G, B).
+ *   2. assign  pixel (y, x) has home cell (y / S, x / S); its candidates are the clusters of the up to nine cells within +-1 of
+ *        the home cell that exist in the grid.  D = (dR^2 + dG^2 + dB^2) * S^2 + m^2 * (dy^2 + dx^2) against the candidate's
+ *        current centre; the pixel takes the smallest D, ties go to the smaller id.  D < 2^32 under the limits (colour
+ *        <= 195075 * 4096; a centre is a mean of pixels of cells within +-1 of its own, so |d| < 3 S and the position gives
+ *        <= 2 * 192^2 * 4096): the kernel computes it in unsigned 32 bits.
+ *   3. update  per cluster n and the sums of y, x, R, G, B over its pixels (each fits 32 bits: <= (3 * 64)^2 pixels * 4095); a
+ *        new centre component is (2 * sum + n) / (2 * n), integer division (round half up); a cluster with n = 0 keeps its
+ *        centre.
+ *   4. schedule  for t = 1..T: assign; if t < T: update.  The ids are those of the last assign.  No connectivity enforcement:
+ *        a cluster may be disconnected, and the vote below is per id.
+ *   5. vote  for a cluster c, cnt_c[l] = its pixels with label l <= n_obj, n_c their sum; a pixel with a label > n_obj votes
+ *        nowhere and is copied unchanged.  The winner w is the label with the largest count, ties to the smaller label.  If
+ *        n_c > 0 and cnt_c[w] * 65536 >= min_share_q16 * n_c (64-bit products; min_share_q16 = round(min_share * 65536) with
+ *        min_share in [0, 1], computed once by the caller), every voting pixel of c becomes w; otherwise the pixels of c are
+ *        copied.
+ *   6. keep  (HOST memory, n_frames flags, may be NULL) frames flagged there -- the train frames -- are copied unchanged.
+ * eosvos_superpixels writes the ids of rules 1-4 to ids_out (device int32 [n_frames][height][width]); asynchronous on the
+ * engine's stream.  eosvos_snap_labels writes the snapped maps to `out` (device, not overlapping `labels`) and, if changed_out
+ * (HOST memory, n_frames values) is not NULL, the number of pixels changed per frame -- it then synchronises the engine's
+ * stream; otherwise nothing waits.  `e` lends its stream and scratch memory only; frames of any size within the limits.
+ * Launches (csrc/slic_kernels.hip): one init; per iteration but the last a fused assign + accumulate (64 x 16 pixel tiles, the
+ * centres of the at most 133 clusters a tile can meet and their accumulators in LDS, one global integer atomic per non-zero
+ * accumulator word) and a finish (new centres, sums zeroed); the last assign writes the ids and, for the vote, counts into the
+ * K x (n_obj + 1) table (privatised in LDS where the tile's slice fits in 2048 words, else one atomic per wave and distinct
+ * target); then one apply per run of frames with the same keep flag.  Integer atomics only: results are exact and independent
+ * of arrival order.  No launch is cooperative, no workgroup waits for another.
+ * Scratch (shared with the component filter and the hole filler), 32-bit words: eosvos_superpixels 5 + 6 per cluster;
+ * eosvos_snap_labels 1 per pixel (ids) + 5 + 6 + (n_obj + 1) per cluster, + 8 bytes per frame (pixels changed) + up to 8 of
+ * padding; allocated on first use, growing only, at most 512 MB per call -- a call that needs more is rejected, a single frame
+ * included, never truncated (pass fewer frames per call).
+ * Rejected without a launch: a null pointer (keep, changed_out excepted), height or width < 1 or > 4096, step outside [4, 64],
+ * iterations outside [1, 20], compactness outside [1, 64], n_obj outside [1, 255], min_share_q16 outside [0, 65536], more than
+ * 65535 frames. */
+int eosvos_superpixels(eosvos_engine* e, const uint8_t* rgb, int n_frames, int height, int width, int step, int iterations,
+                       int compactness, int32_t* ids_out);
+int eosvos_snap_labels(eosvos_engine* e, const uint8_t* rgb, const uint8_t* labels, int n_frames, int height, int width, int n_obj,
+                       int step, int iterations, int compactness, int min_share_q16, const uint8_t* keep, uint8_t* out,
+                       int64_t* changed_out);
+
 /* ---- learning-rate hierarchy (meta_optim.py:27-67) ------------------------------------ */
 /* `lr_hierarchy_level`: how the learned lr state is stored.  NEURON (cfgs/meta.yaml:36) one
  * value per output channel; TENSOR one per trainable tensor (`log_init_lr` of shape
