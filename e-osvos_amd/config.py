@@ -146,6 +146,16 @@ SNAP = {
 }
 
 
+# Motion compensation of the clean-up's temporal rules, handled like the groups above (`eval_motion.block=8
+# eval_motion.radius=24` -- example values, untuned; read with `cfg.get(...)`).
+#   eval_motion       the gate of the component filter and `prev_overlap` of the hole filler see the previous frame's cleaned
+#                     map warped by block motion (`motion.py`); the value below is the neutral one (`motion.DEFAULTS`: block
+#                     0, nothing new is called).  Active, it needs `eval_components.gate` or `eval_holes.prev_overlap`.
+MOTION = {
+    'eval_motion': {'block': 0, 'radius': 16, 'bias': 2},
+}
+
+
 def _merge(dst, src):
     for k, v in src.items():
         if isinstance(v, dict) and isinstance(dst.get(k), dict):
@@ -192,7 +202,7 @@ def parse_cli(argv):
             raise KeyError(f'unknown named config: {a}')
     for k, v in updates:
         group = k.split('.')[0]
-        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL, SNAP):
+        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL, SNAP, MOTION):
             if group in groups and group not in cfg:
                 cfg[group] = copy.deepcopy(groups[group])
         _set_dotted(cfg, k, v)
@@ -211,6 +221,17 @@ def parse_cli(argv):
     if 'eval_snap' in cfg:
         from .snap import check as check_snap
         check_snap(cfg['eval_snap'])                        # ValueError: step 3, compactness 65, ...
+    if 'eval_motion' in cfg:
+        from . import motion
+        if motion.active(cfg['eval_motion']):               # ValueError: block 12, radius 33, bias 256, ...
+            from .components import check as check_gate
+            from .holes import active as fills, check as check_overlap, overlap_q16
+            fill = cfg.get('eval_holes', {})
+            if not check_gate(cfg.get('eval_components', {}))['gate'] and \
+                    not (fills(fill) and overlap_q16(check_overlap(fill)['prev_overlap'])):
+                raise ValueError('eval_motion has no consumer: set eval_components.gate or eval_holes.prev_overlap')
+        else:
+            motion.check(cfg['eval_motion'])
     unsupported(cfg)
     return cfg
 

@@ -208,7 +208,7 @@ struct eosvos_engine {
   size_t davis_cap = 0;
   void* crf_buf = nullptr;              // eosvos_crf_labels: unary + the two Q planes of the mean field (grow-only, freed by destroy)
   size_t crf_cap = 0;
-  void* ccl_buf = nullptr;              // eosvos_label_components / eosvos_filter_components / eosvos_fill_holes: union-find, ids, areas, flags; eosvos_superpixels / eosvos_snap_labels: ids, centres, sums, votes (grow-only, freed by destroy)
+  void* ccl_buf = nullptr;              // eosvos_label_components / eosvos_filter_components / eosvos_fill_holes: union-find, ids, areas, flags; eosvos_superpixels / eosvos_snap_labels: ids, centres, sums, votes; eosvos_block_motion: luma planes (grow-only, freed by destroy)
   size_t ccl_cap = 0;
   int lr_level = EOSVOS_LR_NEURON, lr_log = 0;
   float *lr_elem = nullptr, *glr_tmp = nullptr, *ptmp = nullptr;
@@ -2964,6 +2964,44 @@ int eosvos_snap_labels(eosvos_engine* e, const uint8_t* rgb, const uint8_t* labe
     HIPOK(hipMemcpyAsync(changed_out, changed, (size_t)n_frames * sizeof(int64_t), hipMemcpyDeviceToHost, e->s));
     HIPOK(hipStreamSynchronize(e->s));
   }
+  return 0;
+}
+
+// ---- block motion on 8-bit luma and the warp of label maps by it (for the temporal rules of the filter and the hole filler) --
+int eosvos_block_motion(eosvos_engine* e, const uint8_t* rgb, const uint8_t* prev_rgb, int n_frames, int height, int width, int block,
+                        int radius, int bias, int8_t* mv) {
+  if (!e || !rgb || !mv) return fail("block_motion: null argument");
+  if (n_frames < 0 || height < 1 || width < 1) return fail("block_motion: bad frame geometry");
+  if (height > 4096 || width > 4096) return fail("block_motion: frames larger than 4096 pixels a side are not supported");
+  if (block != 8 && block != 16) return fail("block_motion: block must be 8 or 16");
+  if (radius < 1 || radius > 32) return fail("block_motion: radius must be in [1, 32]");
+  if (bias < 0 || bias > 255) return fail("block_motion: bias must be in [0, 255]");
+  if (n_frames > 65534) return fail("block_motion: at most 65534 frames per call");
+  if (n_frames == 0) return 0;
+  // n_frames + 1 luma planes of height rows, each row padded to a multiple of four bytes
+  const size_t plane = (size_t)height * ((width + 3) / 4 * 4);
+  if (ccl_scratch(e, "block_motion", ((size_t)n_frames + 1) * plane, n_frames)) return 1;
+  unsigned* luma = (unsigned*)e->ccl_buf;
+  const int first = prev_rgb ? 0 : 1;
+  const size_t per_frame = (size_t)((height + block - 1) / block) * ((width + block - 1) / block) * 2;
+  if (first) HIPOK(hipMemsetAsync(mv, 0, per_frame, e->s));          // no frame before the first: zeros
+  launch_motion_luma(rgb, prev_rgb, n_frames, height, width, luma, e->s);
+  HIPOK(hipGetLastError());
+  launch_motion_search(luma, first, n_frames, height, width, block, radius, bias, mv, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+
+int eosvos_warp_labels(eosvos_engine* e, const uint8_t* labels, const int8_t* mv, int n_frames, int height, int width, int block,
+                       uint8_t* out) {
+  if (!e || !labels || !mv || !out) return fail("warp_labels: null argument");
+  if (n_frames < 0 || height < 1 || width < 1) return fail("warp_labels: bad frame geometry");
+  if (height > 4096 || width > 4096) return fail("warp_labels: frames larger than 4096 pixels a side are not supported");
+  if (block != 8 && block != 16) return fail("warp_labels: block must be 8 or 16");
+  if (n_frames > 65535) return fail("warp_labels: at most 65535 frames per call");
+  if (n_frames == 0) return 0;
+  launch_motion_warp(labels, mv, n_frames, height, width, block, out, e->s);
+  HIPOK(hipGetLastError());
   return 0;
 }
 

@@ -473,6 +473,17 @@ void launch_slic_last(const uint8_t* rgb, const uint8_t* labels, int n_frames, i
 void launch_slic_apply(const uint8_t* labels, const int* ids, const unsigned* votes, int keep_all, int n_frames, int H, int W,
                        int S, int n_obj, unsigned q16, uint8_t* out, unsigned long long* changed, hipStream_t s);
 
+// Block motion on 8-bit luma and the warp of label maps by it (motion_kernels.hip; the rules: include/eosvos.h,
+// eosvos_block_motion / eosvos_warp_labels).  rgb [frame][3][H][W], prev_rgb [3][H][W] or null; luma: n_frames + 1 planes of
+// H * LW words, LW = ceil(W / 4) (plane 0: prev_rgb, plane 1 + f: frame f; padding bytes 0); mv [frame][by][bx][2] (dy, dx).
+// launch_motion_luma: the planes (plane 0 only with prev_rgb).  launch_motion_search: the vectors of frames first .. n_frames - 1
+// (first = 1 without prev_rgb: frame 0 is the caller's to zero).  launch_motion_warp: out(y, x) = labels(y + dy, x + dx),
+// clamped to the frame.
+void launch_motion_luma(const uint8_t* rgb, const uint8_t* prev_rgb, int n_frames, int H, int W, unsigned* luma, hipStream_t s);
+void launch_motion_search(const unsigned* luma, int first, int n_frames, int H, int W, int block, int radius, int bias, int8_t* mv,
+                          hipStream_t s);
+void launch_motion_warp(const uint8_t* labels, const int8_t* mv, int n_frames, int H, int W, int block, uint8_t* out, hipStream_t s);
+
 // theta' = theta - lr[cout]*g, g = rowscale[cout] * sum_z ws[z][...]; optional gsum += g; g_out = g
 void launch_sgd_update(float* w, const float* ws, int splits, int64_t slab, const float* rowscale,
                        const float* lr, float* gsum, float* gout, int64_t rowlen, int64_t n,

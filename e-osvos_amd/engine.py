@@ -751,6 +751,49 @@ class Engine:
                 changed[f:g].ctypes.data_as(changed_p) if return_changed else None))
         return (out, changed) if return_changed else out
 
+    def block_motion(self, rgb, block=8, radius=16, bias=2, prev_rgb=None):
+        """Block vectors between consecutive frames (`eosvos_block_motion`; the rules: `motion.py`).  rgb (N, 3, H, W) uint8 on the
+        engine's device in frame order (`snap.quantise` makes it from fp32 frames), prev_rgb (3, H, W) uint8 or None: the frame
+        before the first -> mv (N, by, bx, 2) int8, (dy, dx) per block; without `prev_rgb` the first frame gets zeros.  Nothing
+        waits for the GPU; the frames go through in chunks under `motion.SCRATCH_CAP`, a chunk's last frame is the `prev_rgb`
+        of the next."""
+        from . import motion
+        p = motion.check(dict(block=block, radius=radius, bias=bias))
+        if p['block'] == 0:
+            raise ValueError('block_motion: block=0 means "off" for the motion compensation; pass 8 or 16')
+        self._check_rgb('block_motion', rgb, None)
+        if prev_rgb is not None and (not isinstance(prev_rgb, torch.Tensor) or prev_rgb.device != self.device or prev_rgb.dtype != torch.uint8):
+            raise ValueError(f'block_motion: prev_rgb must be a uint8 tensor on {self.device}')
+        motion._check_rgb('block_motion', rgb, prev_rgb)
+        self._check_stream()
+        rgb = rgb.contiguous()
+        n, _, h, w = rgb.shape
+        mv = torch.empty((n,) + motion.grid(h, w, p['block']) + (2,), dtype=torch.int8, device=self.device)
+        chunk = motion.frames_per_call(h, w)
+        prev = prev_rgb.contiguous() if prev_rgb is not None else None
+        for f in range(0, n, chunk):
+            g = min(f + chunk, n)
+            _ffi.check(self.lib.eosvos_block_motion(self.h, _ptr(rgb[f:g]), _optr(prev), g - f, h, w, p['block'], p['radius'], p['bias'],
+                                                    _ptr(mv[f:g])))
+            prev = rgb[g - 1]
+        return mv
+
+    def warp_labels(self, labels, mv, block):
+        """Label maps warped by block vectors (`eosvos_warp_labels`; `motion.py`, rule 7).  labels (N, H, W) uint8 and mv
+        (N, by, bx, 2) int8 on the engine's device -> (N, H, W) uint8, out(y, x) = labels(y + dy, x + dx) with the vector of the
+        pixel's block; frame n is warped by mv[n].  Nothing waits for the GPU."""
+        from . import motion
+        self._check_label_maps('warp_labels', labels)
+        if not isinstance(mv, torch.Tensor) or mv.device != self.device or mv.dtype != torch.int8:
+            raise ValueError(f'warp_labels: mv must be an int8 tensor on {self.device}')
+        motion._check_mv('warp_labels', labels, mv, block)
+        self._check_stream()
+        labels, mv = labels.contiguous(), mv.contiguous()
+        n, h, w = labels.shape
+        out = torch.empty_like(labels)
+        _ffi.check(self.lib.eosvos_warp_labels(self.h, _ptr(labels), _ptr(mv), n, h, w, block, _ptr(out)))
+        return out
+
     # ---- meta-training ----------------------------------------------------------------
     def meta_task_begin(self):
         _ffi.check(self.lib.eosvos_meta_task_begin(self.h))

@@ -23,6 +23,7 @@ import torch
 from . import components as component_filter
 from . import crf as crf_refine
 from . import holes as hole_filler
+from . import motion as mover
 from . import snap as snapper
 from . import tta as tta_views
 from .helper_func import compute_loss, early_stopping, set_random_seeds
@@ -273,7 +274,8 @@ def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augm
     return out
 
 
-def merge_objects(engine, probs_all, frames=None, crf=None, keep=(), components=None, holes=None, snap=None, frame_offset=None):
+def merge_objects(engine, probs_all, frames=None, crf=None, keep=(), components=None, holes=None, snap=None, frame_offset=None,
+                  motion=None):
     """Per-object probabilities [(N,H,W)] -> label maps (N,H,W) uint8 (`evaluate.py:322-326`).
     `crf` (`crf.py`; None or iterations 0: off, the code below as it always was): the local dense CRF refines the merge against
     `frames` (N,3,H,W), one `crf_labels` call per chunk of frames.  The frames listed in `keep` -- the train frame of EVERY
@@ -286,6 +288,10 @@ def merge_objects(engine, probs_all, frames=None, crf=None, keep=(), components=
     `snap` (`snap.py`; None or step 0: off, nothing new is called): between the CRF and the component filter, every SLIC
     superpixel of `frames` takes the label that holds its majority; the `keep` frames pass unchanged.  `frame_offset`: what the
     data set subtracted from the RGB frame (`mean_val` under `data_cfg.normalize`), for `snap.quantise`.
+    `motion` (`motion.py`; None or block 0: off, nothing new is called): the gate of the component filter and `prev_overlap` of
+    the hole filler see the previous frame's cleaned map warped onto the current frame by block motion of `frames`.  The
+    vectors of all frames are computed once; a stage whose temporal rule is on then runs one frame per call, a stage whose
+    rule is off keeps its single batched call.  Needs `frames` and at least one of the two rules.
     The chain: merge -> CRF -> snap -> components -> holes."""
     stack = torch.stack(list(probs_all), dim=1)                       # (N, n_obj, H, W)
     clean = component_filter.active(components)
@@ -293,15 +299,47 @@ def merge_objects(engine, probs_all, frames=None, crf=None, keep=(), components=
     snapping = snapper.active(snap)
     if snapping and (frames is None or frames.shape[0] != stack.shape[0] or frames.shape[2:] != stack.shape[2:]):
         raise ValueError('merge_objects: snap needs the frames (N, 3, H, W) of the probabilities it snaps')
+    moving = mover.active(motion)
+    gated = clean and component_filter.check(components)['gate'] > 0
+    overlapped = fill and hole_filler.overlap_q16(hole_filler.check(holes)['prev_overlap']) > 0
+    if moving and (frames is None or frames.shape[0] != stack.shape[0] or frames.shape[2:] != stack.shape[2:]):
+        raise ValueError('merge_objects: motion needs the frames (N, 3, H, W) of the probabilities it follows')
+    if moving and not (gated or overlapped):
+        raise ValueError('merge_objects: motion has no consumer: neither components.gate nor holes.prev_overlap is on')
     if crf_refine.active(crf):
         labels = _merge_refined(engine, stack, frames, crf, keep)
     else:
         labels = torch.stack([engine.merge_labels(stack[f].contiguous()) for f in range(stack.shape[0])])
+    rgb = snapper.quantise(frames, frame_offset) if snapping or moving else None
     if snapping:
-        labels = snapper.snap(engine, snapper.quantise(frames, frame_offset), labels, snap, keep=keep, n_obj=stack.shape[1])
+        labels = snapper.snap(engine, rgb, labels, snap, keep=keep, n_obj=stack.shape[1])
+    if not moving:
+        if clean:
+            labels = component_filter.filter(engine, labels, components, keep=keep)
+        return hole_filler.fill(engine, labels, holes, keep=keep) if fill else labels
+    block = mover.check(motion)['block']
+    mv = mover.vectors(engine, rgb, motion)
     if clean:
-        labels = component_filter.filter(engine, labels, components, keep=keep)
-    return hole_filler.fill(engine, labels, holes, keep=keep) if fill else labels
+        labels = _follow(component_filter.filter, engine, labels, components, keep, mv, block) if gated else \
+            component_filter.filter(engine, labels, components, keep=keep)
+    if fill:
+        labels = _follow(hole_filler.fill, engine, labels, holes, keep, mv, block) if overlapped else \
+            hole_filler.fill(engine, labels, holes, keep=keep)
+    return labels
+
+
+def _follow(stage, engine, labels, params, keep, mv, block):
+    """A temporal stage (`components.filter`, `holes.fill`) one frame per call in ascending order, each frame against the
+    stage's output of the frame before it warped by the frame's vectors (`motion.py`, rule 8).  Frame 0 has no `prev`; a `keep`
+    frame passes unchanged and is still warped for its successor."""
+    keep = {int(f) for f in keep}
+    out = torch.empty_like(labels)
+    prev = None
+    for f in range(labels.shape[0]):
+        out[f:f + 1] = stage(engine, labels[f:f + 1], params, prev=prev, keep=(0,) if f in keep else ())
+        if f + 1 < labels.shape[0]:
+            prev = mover.warp(engine, out[f:f + 1], mv[f + 1:f + 2], block)[0]
+    return out
 
 
 def _merge_refined(engine, stack, frames, crf, keep):
@@ -349,8 +387,19 @@ def _snap_kw(snap, cfg, dataset=None):
     return {'snap': snap, 'frame_offset': tuple(getattr(dataset, 'mean_val', DAVIS.mean_val))}
 
 
+def _motion_kw(motion, cfg, dataset=None):
+    """As `_snap_kw`: `motion` travels as a keyword, and only when it is set to something that estimates (`motion.active`,
+    which also validates it) -- then with the offset `snap.quantise` needs."""
+    if not mover.active(motion):
+        return {}
+    if not cfg.get('data_cfg', {}).get('normalize'):
+        return {'motion': motion}
+    from .data import DAVIS
+    return {'motion': motion, 'frame_offset': tuple(getattr(dataset, 'mean_val', DAVIS.mean_val))}
+
+
 def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_gts, cfg, augment=None,
-                      train_frame_id=0, tta=None, crf=None, components=None, holes=None, snap=None):
+                      train_frame_id=0, tta=None, crf=None, components=None, holes=None, snap=None, motion=None):
     """frames (N,3,H,W) on the GPU, object_gts: list of (1,H,W) binary masks of the train frame.
     cfg keys (names of cfgs/meta.yaml): num_epochs.eval, eval_online_adapt.{step,reset_model_mode,
     num_epochs,min_prop (a threshold, or [lo, hi]: `min_prop_band`)}, data_cfg.batch_sizes.train, seed, loss_func, train_early_stopping_cfg.
@@ -360,6 +409,7 @@ def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_g
     unchanged and anchors the gate.
     `holes` (`holes.py`): the hole filler runs after the component filter, with the same train frame kept.
     `snap` (`snap.py`): the superpixel snapping runs between the CRF and the component filter, with the same train frame kept.
+    `motion` (`motion.py`): the temporal rules of the filter and the hole filler see the previous map warped by block motion.
     Returns (labels (N,H,W) uint8, per-object probs list, train loss history per object)."""
     probs_all, hist_all = [], []
     for gt in object_gts:
@@ -367,10 +417,10 @@ def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_g
                                       **_tta_kw(tta))
         probs_all.append(probs)
         hist_all.append(hist)
-    if crf is None and components is None and not _holes_kw(holes) and not _snap_kw(snap, cfg):
+    if crf is None and components is None and not _holes_kw(holes) and not _snap_kw(snap, cfg) and not _motion_kw(motion, cfg):
         return merge_objects(model.engine, probs_all), probs_all, hist_all
     return merge_objects(model.engine, probs_all, frames, crf, keep=(train_frame_id,), **_components_kw(components),
-                         **_holes_kw(holes), **_snap_kw(snap, cfg)), probs_all, hist_all
+                         **_holes_kw(holes), **{**_snap_kw(snap, cfg), **_motion_kw(motion, cfg)}), probs_all, hist_all
 
 
 def prediction_paths(save_dir, dataset_name, split):
@@ -387,7 +437,7 @@ def save_label_png(path, labels_hw):
 
 def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dataset_key, save_dir=None,
                      meta_iter=None, meta_epoch=None, best_mean_J=0.0, dist=None, device=None, vis_win_names=None,
-                     log=None, objects_in_flight=None, tta=None, crf=None, components=None, holes=None, snap=None):
+                     log=None, objects_in_flight=None, tta=None, crf=None, components=None, holes=None, snap=None, motion=None):
     """The evaluation worker of `src/util/evaluate.py:111-382` for the DeepLab path: every sequence of `dataset`
     (an `eosvos_amd.data` reader), every object, fine-tune / online adaptation / inference / merge; prediction PNGs
     under `{save_dir}/best_eval_preds/{name}/{split}/{seq}/{frame}.png`, J per sequence, and the
@@ -413,6 +463,8 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
     `holes` (`holes.py`): the hole filler runs after the component filter; the PNGs, J_seq and the J / F counts see the filled maps.
     `snap` (`snap.py`): the superpixel snapping runs between the CRF and the component filter, on the frames quantised back to
     uint8 RGB; the PNGs, J_seq and the J / F counts see the final maps.
+    `motion` (`motion.py`): the gate of the component filter and `prev_overlap` of the hole filler see the previous frame's
+    cleaned map warped by block motion of the same quantised frames.
     Returns dict(J_seq, mean_J, best_mean_J, time_per_frame, labels={seq: (N,H,W) uint8}) and the DAVIS J / F statistics
     of `eval_davis_seq` (`evaluate.py:345-359`), one entry per object in sequence order: J_obj (the per-object J means the
     reference calls J_seq), J_recall_seq, J_decay_seq, F_seq, F_recall_seq, F_decay_seq, with mean_F and
@@ -541,11 +593,12 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
         if model.engine is None:                                                # this rank had no item yet
             model._ensure_engine(frames.shape[2], frames.shape[3], 1)
         keep = {'keep': tuple(set(fids)) if len(set(fids)) == 1 else ()} \
-            if crf is not None or components is not None or holes is not None or _snap_kw(snap, cfg) else {}
-        if crf is not None or _snap_kw(snap, cfg):
+            if crf is not None or components is not None or holes is not None or _snap_kw(snap, cfg) or _motion_kw(motion, cfg) else {}
+        if crf is not None or _snap_kw(snap, cfg) or _motion_kw(motion, cfg):
             keep = dict(frames=frames, **keep)
         labels = merge_objects(model.engine, [probs[o] for o in range(len(gts))], **keep, **_crf_kw(crf),
-                               **_components_kw(components), **_holes_kw(holes), **_snap_kw(snap, cfg, dataset))
+                               **_components_kw(components), **_holes_kw(holes),
+                               **{**_snap_kw(snap, cfg, dataset), **_motion_kw(motion, cfg, dataset)})
         counts = None
         if not dataset.test_mode:                                               # J / F counts where the labels are
             gt_dev = torch.from_numpy(np.ascontiguousarray(gt_maps, dtype=np.uint8)).to(labels.device)

@@ -486,6 +486,52 @@ int eosvos_snap_labels(eosvos_engine* e, const uint8_t* rgb, const uint8_t* labe
                        int step, int iterations, int compactness, int min_share_q16, const uint8_t* keep, uint8_t* out,
                        int64_t* changed_out);
 
+/* ---- block motion on 8-bit luma and the warp of label maps by it (for the filter's gate and the hole filler's overlap) - */
+/* The reference has no such step.  The gate of eosvos_filter_components and the previous-frame rule of eosvos_fill_holes read
+ * the previous frame's cleaned map at the same pixel coordinates, which is right only while an object moves less than the gate
+ * between two frames; the OSVOS / PReMVOS family propagates the previous mask by motion before it compares.  These two entry
+ * points are that step: exhaustive block matching on 8-bit luma and a gather.  The caller passes the warped map as `prev` of
+ * the two stages, one frame per call (eosvos_amd/evaluate.py `merge_objects(..., motion=)`).  An opt-in extension; the
+ * parameter values shown anywhere are examples, untuned.
+ * rgb: device uint8 [n_frames][3][height][width], planar, the frames of one sequence in order (the caller quantises its
+ * frames: eosvos_amd/snap.py `quantise`); prev_rgb: device uint8 [3][height][width], the frame before the first, or NULL.
+ * Every quantity is an integer.  B = block, R = radius.
+ *   1. luma  Y = (77 R + 150 G + 29 B + 128) >> 8, a uint8.
+ *   2. blocks  by = ceil(height / B), bx = ceil(width / B); block (j, i) covers rows [jB, min(jB + B, height)) and columns
+ *        [iB, min(iB + B, width)), n = its pixel count: blocks at the lower and right border are smaller, and a frame smaller
+ *        than one block is one partial block.
+ *   3. candidates  for frame f against frame f - 1, a displacement (dy, dx) with |dy|, |dx| <= R is valid for a block when the
+ *        whole block, shifted by it, lies inside the frame.  (0, 0) is always valid.
+ *   4. cost  cost(d) = sum over the block of |Y_f(y, x) - Y_{f-1}(y + dy, x + dx)|, plus bias * n for d != (0, 0): the bias keeps
+ *        flat regions at rest.
+ *   5. choice  the valid candidate that is smallest under the lexicographic order (cost, dy^2 + dx^2, dy, dx).  It packs into
+ *        one 64-bit key, cost << 26 | (dy^2 + dx^2) << 14 | (dy + 32) << 7 | (dx + 32) (cost <= 2 * 65280 < 2^17, then 12 + 7
+ *        + 7 bits): a single integer min decides, in whatever order the lanes reduce.
+ *   6. output  mv: device int8 [n_frames][by][bx][2], (dy, dx) per block.  Frame 0 of the call is matched against prev_rgb --
+ *        that is how a sequence is chunked: pass the last frame of a call as prev_rgb of the next; with NULL it gets zeros.
+ *   7. warp  out(y, x) = labels(y + dy, x + dx) with the vector of the pixel's block: the map of frame f - 1 as frame f sees
+ *        it.  Rule 3 keeps every read inside the frame; a vector from elsewhere that leaves it is clamped to the border.
+ * eosvos_warp_labels: labels, out: device uint8 [n_frames][height][width] (not overlapping); frame n is warped by mv[n].
+ * Both are asynchronous on the engine's stream; `e` lends its stream and scratch memory only; frames of any size within the
+ * limits.
+ * Launches (csrc/motion_kernels.hip): one luma launch (planes with rows padded to four bytes, so a word never straddles rows);
+ * one search launch: a workgroup owns 32 x 64 pixels of blocks and stages that tile of Y_f and the window of Y_{f-1} its
+ * candidates reach (at most 96 rows x 132 bytes, 0 outside the frame) in LDS, each wave takes blocks in turn, a lane takes a
+ * row offset dy and four adjacent dx -- the eight bytes a packed quad-SAD (v_qsad_pk_u16_u8) needs are two aligned words of a
+ * window row, one instruction per four bytes of a block row, sums in four 16-bit lanes (16 * 16 * 255 = 65280); blocks cut by
+ * the right border take v_alignbyte_b32 and a masked v_sad_u8 per candidate; the wave reduces the key by an integer min;
+ * one warp launch.  No atomics; the result does not depend on any order.  No launch is cooperative, no workgroup waits for
+ * another.
+ * Scratch of eosvos_block_motion (shared with the component filter, the hole filler and the snapping): n_frames + 1 luma
+ * planes of height * (width rounded up to 4) bytes; allocated on first use, growing only, at most 512 MB per call -- a call
+ * that needs more is rejected, never truncated (pass fewer frames per call).  eosvos_warp_labels takes none.
+ * Rejected without a launch: a null pointer (prev_rgb excepted), height or width < 1 or > 4096, block other than 8 or 16,
+ * radius outside [1, 32], bias outside [0, 255], more than 65534 (warp: 65535) frames. */
+int eosvos_block_motion(eosvos_engine* e, const uint8_t* rgb, const uint8_t* prev_rgb, int n_frames, int height, int width, int block,
+                        int radius, int bias, int8_t* mv);
+int eosvos_warp_labels(eosvos_engine* e, const uint8_t* labels, const int8_t* mv, int n_frames, int height, int width, int block,
+                       uint8_t* out);
+
 /* ---- learning-rate hierarchy (meta_optim.py:27-67) ------------------------------------ */
 /* `lr_hierarchy_level`: how the learned lr state is stored.  NEURON (cfgs/meta.yaml:36) one
  * value per output channel; TENSOR one per trainable tensor (`log_init_lr` of shape
