@@ -87,6 +87,13 @@ _SIGNATURES = {
                            [ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]),
     'eosvos_block_motion': (ctypes.c_int, [_E, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p]),
     'eosvos_warp_labels': (ctypes.c_int, [_E, ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+    'eosvos_zoom_boxes': (ctypes.c_int, [_E, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float] +
+                          [ctypes.c_int] * 5 + [ctypes.c_void_p]),
+    'eosvos_zoom_crop': (ctypes.c_int, [_E, c_float_p, ctypes.c_void_p] + [ctypes.c_int] * 4 + [c_float_p]),
+    'eosvos_zoom_accumulate': (ctypes.c_int, [_E, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                              c_float_p]),
+    'eosvos_zoom_blend': (ctypes.c_int, [_E, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                         c_float_p, c_float_p]),
     'eosvos_set_norm': (ctypes.c_int, [_E, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_float]),
     'eosvos_reset': (ctypes.c_int, [_E]),
     'eosvos_get_params': (ctypes.c_int, [_E, c_float_p]),

@@ -156,6 +156,18 @@ MOTION = {
 }
 
 
+# Object-centred zoom pass of the evaluation's inference calls, handled like the groups above (not part of BASE, added by
+# `parse_cli` only when the command line sets one of its keys: `eval_zoom.max_zoom=3 eval_zoom.margin=0.5` -- example values,
+# untuned; read with `cfg.get(...)`).
+#   eval_zoom         every frame gets a second look at a crop around the object its first pass found, magnified to the frame's
+#                     own size on the live engine and blended in inside the crop (`zoom.py`); the value below is the neutral
+#                     one (`zoom.DEFAULTS`: max_zoom 0, nothing new is called)
+ZOOM = {
+    'eval_zoom': {'max_zoom': 0, 'min_zoom': 1.5, 'threshold': 0.5, 'min_pixels': 16, 'margin': 0.5, 'margin_px': 8, 'weight': 0.5,
+                  'feather': 8},
+}
+
+
 def _merge(dst, src):
     for k, v in src.items():
         if isinstance(v, dict) and isinstance(dst.get(k), dict):
@@ -202,7 +214,7 @@ def parse_cli(argv):
             raise KeyError(f'unknown named config: {a}')
     for k, v in updates:
         group = k.split('.')[0]
-        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL, SNAP, MOTION):
+        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL, SNAP, MOTION, ZOOM):
             if group in groups and group not in cfg:
                 cfg[group] = copy.deepcopy(groups[group])
         _set_dotted(cfg, k, v)
@@ -232,6 +244,9 @@ def parse_cli(argv):
                 raise ValueError('eval_motion has no consumer: set eval_components.gate or eval_holes.prev_overlap')
         else:
             motion.check(cfg['eval_motion'])
+    if 'eval_zoom' in cfg:
+        from .zoom import check as check_zoom
+        check_zoom(cfg['eval_zoom'])                        # ValueError: max_zoom 5, min_zoom above max_zoom, weight 0, ...
     unsupported(cfg)
     return cfg
 

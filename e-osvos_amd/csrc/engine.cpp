@@ -208,7 +208,7 @@ struct eosvos_engine {
   size_t davis_cap = 0;
   void* crf_buf = nullptr;              // eosvos_crf_labels: unary + the two Q planes of the mean field (grow-only, freed by destroy)
   size_t crf_cap = 0;
-  void* ccl_buf = nullptr;              // eosvos_label_components / eosvos_filter_components / eosvos_fill_holes: union-find, ids, areas, flags; eosvos_superpixels / eosvos_snap_labels: ids, centres, sums, votes; eosvos_block_motion: luma planes (grow-only, freed by destroy)
+  void* ccl_buf = nullptr;              // eosvos_label_components / eosvos_filter_components / eosvos_fill_holes: union-find, ids, areas, flags; eosvos_superpixels / eosvos_snap_labels: ids, centres, sums, votes; eosvos_block_motion: luma planes; eosvos_zoom_boxes: the frames' bound records (grow-only, freed by destroy)
   size_t ccl_cap = 0;
   int lr_level = EOSVOS_LR_NEURON, lr_log = 0;
   float *lr_elem = nullptr, *glr_tmp = nullptr, *ptmp = nullptr;
@@ -3001,6 +3001,64 @@ int eosvos_warp_labels(eosvos_engine* e, const uint8_t* labels, const int8_t* mv
   if (n_frames > 65535) return fail("warp_labels: at most 65535 frames per call");
   if (n_frames == 0) return 0;
   launch_motion_warp(labels, mv, n_frames, height, width, block, out, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+
+// ---- object-centred zoom pass of the inference path: box, cut, put back, blend (eosvos_amd/zoom.py) -----------------------
+static bool finite_f(float v) { return v == v && v - v == 0.f; }
+int eosvos_zoom_boxes(eosvos_engine* e, const float* probs, int n_frames, int height, int width, float threshold, int min_pixels,
+                      int margin_q16, int margin_px, int min_zoom_q16, int max_zoom_q16, int32_t* boxes) {
+  if (!e || !probs || !boxes) return fail("zoom_boxes: null argument");
+  if (n_frames < 1 || height < 1 || width < 1) return fail("zoom_boxes: bad frame geometry");
+  if (height > 4096 || width > 4096) return fail("zoom_boxes: frames larger than 4096 pixels a side are not supported");
+  if (n_frames > 65535) return fail("zoom_boxes: at most 65535 frames per call");
+  if (!finite_f(threshold) || !(threshold > 0.f && threshold < 1.f)) return fail("zoom_boxes: threshold must be in (0, 1)");
+  if (min_pixels < 1) return fail("zoom_boxes: min_pixels must be >= 1");
+  if (margin_q16 < 0 || margin_q16 > 4 * 65536) return fail("zoom_boxes: margin must be in [0, 4] (Q16)");
+  if (margin_px < 0 || margin_px > 256) return fail("zoom_boxes: margin_px must be in [0, 256]");
+  if (max_zoom_q16 < 65536 || max_zoom_q16 > 4 * 65536) return fail("zoom_boxes: max_zoom must be in [1, 4] (Q16)");
+  if (min_zoom_q16 < 65536 || min_zoom_q16 > max_zoom_q16) return fail("zoom_boxes: min_zoom must be in [1, max_zoom] (Q16)");
+  // one record of 8 words per frame; zeroed here, on the stream, whatever the buffer held
+  const size_t need = (size_t)n_frames * 8 * sizeof(int);
+  if (ccl_scratch(e, "zoom_boxes", need, n_frames)) return 1;
+  int* rec = (int*)e->ccl_buf;
+  HIPOK(hipMemsetAsync(rec, 0, need, e->s));
+  launch_zoom_boxes(probs, n_frames, height, width, threshold, min_pixels, margin_q16, margin_px, min_zoom_q16, max_zoom_q16, rec,
+                    boxes, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+
+int eosvos_zoom_crop(eosvos_engine* e, const float* frames, const int32_t* boxes, int B, int C, int height, int width, float* out) {
+  if (!e || !frames || !boxes || !out) return fail("zoom_crop: null argument");
+  if (B < 1 || C < 1) return fail("zoom_crop: batch out of range");
+  if (height < 1 || width < 1) return fail("zoom_crop: bad frame geometry");
+  if (height > 4096 || width > 4096) return fail("zoom_crop: frames larger than 4096 pixels a side are not supported");
+  if ((int64_t)B * C > 0x7fffffff) return fail("zoom_crop: too many planes");
+  launch_zoom_crop(frames, boxes, B, C, height, width, out, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+
+int eosvos_zoom_accumulate(eosvos_engine* e, const int32_t* boxes, int batch, int mirror, float view_weight, int first, float* pz) {
+  if (!e || !boxes || !pz) return fail("zoom_accumulate: null argument");
+  if (batch < 1 || batch > e->maxB) return fail("zoom_accumulate: batch out of range");
+  if (!finite_f(view_weight)) return fail("zoom_accumulate: the weight must be finite");
+  launch_zoom_accumulate(e->logits, boxes, batch, e->H, e->W, mirror != 0, view_weight, first != 0, pz, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+
+int eosvos_zoom_blend(eosvos_engine* e, const int32_t* boxes, int B, int height, int width, float weight, int feather, const float* pz,
+                      float* probs_inout) {
+  if (!e || !boxes || !pz || !probs_inout) return fail("zoom_blend: null argument");
+  if (B < 1) return fail("zoom_blend: batch out of range");
+  if (height < 1 || width < 1) return fail("zoom_blend: bad frame geometry");
+  if (height > 4096 || width > 4096) return fail("zoom_blend: frames larger than 4096 pixels a side are not supported");
+  if (!finite_f(weight) || !(weight > 0.f && weight <= 1.f)) return fail("zoom_blend: weight must be in (0, 1]");
+  if (feather < 0 || feather > 64) return fail("zoom_blend: feather must be in [0, 64]");
+  launch_zoom_blend(boxes, B, height, width, weight, feather, pz, probs_inout, e->s);
   HIPOK(hipGetLastError());
   return 0;
 }

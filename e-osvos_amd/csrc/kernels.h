@@ -74,6 +74,17 @@ __device__ __forceinline__ int block_sum_i(int v, int* sh /*4*/) {
   __syncthreads();
   return sh[0] + sh[1] + sh[2] + sh[3];
 }
+// Source of output index o under torch's bilinear align_corners=False rule, scale = (float)in / (float)out: the coordinate
+// max(0, scale * (o + 0.5) - 0.5) in fp32, its lower neighbour i0, the upper one i1 clamped at the edge, and the weight of i1
+// (the arithmetic of resize_fwd_kernel's tables; tta_accumulate_kernel and the zoom kernels compute it in place).
+__device__ __forceinline__ void tta_src(int o, float scale, int in, int& i0, int& i1, float& lam) {
+  float src = scale * ((float)o + 0.5f) - 0.5f;
+  if (src < 0.f) src = 0.f;
+  i0 = (int)src;
+  if (i0 > in - 1) i0 = in - 1;
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  lam = src - (float)i0;
+}
 #endif
 
 // ---------------------------------------------------------------------------------
@@ -483,6 +494,20 @@ void launch_motion_luma(const uint8_t* rgb, const uint8_t* prev_rgb, int n_frame
 void launch_motion_search(const unsigned* luma, int first, int n_frames, int H, int W, int block, int radius, int bias, int8_t* mv,
                           hipStream_t s);
 void launch_motion_warp(const uint8_t* labels, const int8_t* mv, int n_frames, int H, int W, int block, uint8_t* out, hipStream_t s);
+
+// Object-centred zoom pass of the inference path (zoom_kernels.hip; the rules: include/eosvos.h, eosvos_zoom_boxes ..
+// eosvos_zoom_blend).  probs / pz [frame][H][W] fp32, boxes [frame][5] int32 (valid, y0, x0, bh, bw), read from device memory
+// and clamped into the frame by every consumer.  launch_zoom_boxes: two launches; rec [frame][8] int32 scratch, ZEROED BY THE
+// CALLER on the same stream (the bounds are kept as maxima of H - 1 - y, y, W - 1 - x, x, and the count).  H, W <= 4096,
+// frames <= 65535.  launch_zoom_crop: out = the frames cut to their boxes at H x W (invalid: copied).  launch_zoom_accumulate:
+// pz inside valid boxes (+)= weight * sigmoid(bilinear(unmirror(logits)) -> bh x bw).  launch_zoom_blend: probs = probs +
+// (weight * ramp) * (pz - probs) inside valid boxes, in place.
+void launch_zoom_boxes(const float* probs, int n_frames, int H, int W, float threshold, int min_pixels, int margin_q16, int margin_px,
+                       int min_zoom_q16, int max_zoom_q16, int* rec, int* boxes, hipStream_t s);
+void launch_zoom_crop(const float* frames, const int* boxes, int B, int C, int H, int W, float* out, hipStream_t s);
+void launch_zoom_accumulate(const float* logits, const int* boxes, int B, int H, int W, int mirror, float weight, int first, float* pz,
+                            hipStream_t s);
+void launch_zoom_blend(const int* boxes, int B, int H, int W, float weight, int feather, const float* pz, float* probs, hipStream_t s);
 
 // theta' = theta - lr[cout]*g, g = rowscale[cout] * sum_z ws[z][...]; optional gsum += g; g_out = g
 void launch_sgd_update(float* w, const float* ws, int splits, int64_t slab, const float* rowscale,

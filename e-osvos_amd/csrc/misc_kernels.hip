@@ -751,15 +751,8 @@ void launch_sigmoid(const float* x, float* y, int64_t n, hipStream_t s) {
 // with logits (B, h, w).  The resize is torch's bilinear align_corners=False rule (source coordinate
 // max(0, (in / out) * (o + 0.5) - 0.5), upper neighbour clamped at the edge; the arithmetic of resize_fwd_kernel) with the
 // coordinates computed in place: a view is resampled once, so a table would cost more than it saves.  h == H and w == W
-// reads the logit itself.  One thread per output pixel, one writer per pixel: no LDS, no atomics, order-free.
-__device__ __forceinline__ void tta_src(int o, float scale, int in, int& i0, int& i1, float& lam) {
-  float src = scale * ((float)o + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  i0 = (int)src;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  lam = src - (float)i0;
-}
+// reads the logit itself.  One thread per output pixel, one writer per pixel: no LDS, no atomics, order-free.  (tta_src: kernels.h,
+// shared with zoom_kernels.hip.)
 __global__ __launch_bounds__(256) void tta_accumulate_kernel(const float* __restrict__ logits, float* __restrict__ acc, int B,
                                                              int h, int w, int H, int W, float sy, float sx, int mirror,
                                                              float weight, int first) {

@@ -552,6 +552,74 @@ class Engine:
         _ffi.check(self.lib.eosvos_resize_frames(self.h, _ptr(frames), b, c, h, w, int(height), int(width), _ptr(out)))
         return out
 
+    # ---- object-centred zoom pass (a second look at a crop around the object, see zoom.py) -----
+    def _check_zoom(self, who, t, name, dtype=torch.float32, shape=None):
+        if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f'{who}: {name} must be a contiguous {dtype} tensor on {self.device}')
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f'{who}: {name} must be {tuple(shape)}, got {tuple(t.shape)}')
+
+    def zoom_boxes(self, probs, params):
+        """`eosvos_zoom_boxes` (`zoom.py`, rules 1-5): first-pass probabilities (N, 1, H, W) or (N, H, W) fp32 on the engine's
+        device, any H, W <= 4096 -> boxes (N, 5) int32 on the device: valid, y0, x0, bh, bw.  Nothing waits for the GPU."""
+        from . import zoom
+        p = zoom.check(params)
+        if p['max_zoom'] == 0:
+            raise ValueError('zoom_boxes: max_zoom=0 means "off" for the zoom pass; pass a number in [1, 4]')
+        self._check_zoom('zoom_boxes', probs, 'probs')
+        if probs.dim() == 4 and probs.shape[1] == 1:
+            probs = probs[:, 0]
+        if probs.dim() != 3 or probs.shape[0] < 1 or min(probs.shape[1:]) < 1 or max(probs.shape[1:]) > zoom.MAX_SIDE:
+            raise ValueError(f'zoom_boxes: probs must be (N, 1, H, W) or (N, H, W) with 1 <= H, W <= {zoom.MAX_SIDE}, got '
+                             f'{tuple(probs.shape)}')
+        self._check_stream()
+        n, h, w = probs.shape
+        boxes = torch.empty(n, 5, dtype=torch.int32, device=self.device)
+        _ffi.check(self.lib.eosvos_zoom_boxes(self.h, _ptr(probs), n, h, w, p['threshold'], p['min_pixels'], zoom.q16(p['margin']),
+                                              p['margin_px'], zoom.q16(p['min_zoom']), zoom.q16(p['max_zoom']), _ptr(boxes)))
+        return boxes
+
+    def zoom_crop(self, frames, boxes, out=None):
+        """`eosvos_zoom_crop` (`zoom.py`, rule 6): frames (B, C, H, W) fp32 cut to their boxes (B, 5) int32 and magnified to
+        H x W; an invalid frame is copied.  Returns `out` (a new tensor without it)."""
+        self._check_zoom('zoom_crop', frames, 'frames')
+        if frames.dim() != 4:
+            raise ValueError(f'zoom_crop: frames must be (B, C, H, W), got {tuple(frames.shape)}')
+        self._check_zoom('zoom_crop', boxes, 'boxes', torch.int32, (frames.shape[0], 5))
+        out = torch.empty_like(frames) if out is None else out
+        self._check_zoom('zoom_crop', out, 'out', shape=frames.shape)
+        self._check_stream()
+        b, c, h, w = frames.shape
+        _ffi.check(self.lib.eosvos_zoom_crop(self.h, _ptr(frames), _ptr(boxes), b, c, h, w, _ptr(out)))
+        return out
+
+    def zoom_accumulate(self, boxes, pz, view_weight, mirror=False, first=False):
+        """`eosvos_zoom_accumulate` (`zoom.py`, rule 8): pz (B, 1, H, W) inside each valid box (+)= view_weight *
+        sigmoid(bilinear(un-mirrored logits of this engine's last forward -> bh x bw)); `first` stores instead of adding.
+        Everything outside the boxes keeps its bits.  Returns pz."""
+        self._check_zoom('zoom_accumulate', pz, 'pz')
+        if pz.dim() != 4 or tuple(pz.shape[1:]) != (1, self.height, self.width) or not 1 <= pz.shape[0] <= self.max_batch:
+            raise ValueError(f'zoom_accumulate: pz must be (B <= {self.max_batch}, 1, {self.height}, {self.width}), got '
+                             f'{tuple(pz.shape)}')
+        self._check_zoom('zoom_accumulate', boxes, 'boxes', torch.int32, (pz.shape[0], 5))
+        self._check_stream()
+        _ffi.check(self.lib.eosvos_zoom_accumulate(self.h, _ptr(boxes), pz.shape[0], int(bool(mirror)), float(view_weight),
+                                                   int(bool(first)), _ptr(pz)))
+        return pz
+
+    def zoom_blend(self, boxes, pz, probs, weight, feather):
+        """`eosvos_zoom_blend` (`zoom.py`, rule 9): probs (B, 1, H, W) = probs + (weight * ramp) * (pz - probs) inside valid
+        boxes, IN PLACE; invalid frames and pixels outside the boxes are not written.  Returns probs."""
+        self._check_zoom('zoom_blend', probs, 'probs')
+        if probs.dim() != 4 or probs.shape[1] != 1:
+            raise ValueError(f'zoom_blend: probs must be (B, 1, H, W), got {tuple(probs.shape)}')
+        self._check_zoom('zoom_blend', pz, 'pz', shape=probs.shape)
+        self._check_zoom('zoom_blend', boxes, 'boxes', torch.int32, (probs.shape[0], 5))
+        self._check_stream()
+        b, _, h, w = probs.shape
+        _ffi.check(self.lib.eosvos_zoom_blend(self.h, _ptr(boxes), b, h, w, float(weight), int(feather), _ptr(pz), _ptr(probs)))
+        return probs
+
     def merge_labels(self, probs):
         """probs: (n_obj, H, W) device fp32 -> (H, W) uint8.  `evaluate.py:322-326`."""
         probs = probs.contiguous()

@@ -26,6 +26,7 @@ from . import holes as hole_filler
 from . import motion as mover
 from . import snap as snapper
 from . import tta as tta_views
+from . import zoom as zoom_pass
 from .helper_func import compute_loss, early_stopping, set_random_seeds
 
 
@@ -86,17 +87,24 @@ def min_prop_band(min_prop):
     return float(min_prop[0]), float(min_prop[1])
 
 
-def finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None):
+def finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None,
+                    zoom=None):
     """One (sequence, object) work item of `evaluate.py:132-317`: fine-tune on the train frame, predict the following
     frames, with online adaptation re-fine-tune every `step` frames.  Returns (probs (N,H,W) with the train frame seeded
-    as 2*GT (`:167-168`), train-loss history per round).  `tta`: test-time augmentation of every inference call (`tta.py`)."""
+    as 2*GT (`:167-168`), train-loss history per round).  `tta`: test-time augmentation of every inference call (`tta.py`).
+    `zoom`: the object-centred second look after every inference call (`zoom.py`)."""
     return _drain(finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id,
-                                        **_tta_kw(tta)))
+                                        **_tta_kw(tta), **_zoom_kw(zoom)))
 
 
 def _tta_kw(tta):
     """`tta` travels as a keyword, and only when it is set: without it every call below is the one made before it existed."""
     return {} if tta is None else {'tta': tta}
+
+
+def _zoom_kw(zoom):
+    """As `_tta_kw`: `zoom` travels as a keyword, and only when it is set."""
+    return {} if zoom is None else {'zoom': zoom}
 
 
 def _drain(gen):
@@ -107,7 +115,8 @@ def _drain(gen):
         return stop.value
 
 
-def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None):
+def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None,
+                          zoom=None):
     """`finetune_object` as a generator: it yields each time a fine-tune iteration (or a few inference frames) has been
     ENQUEUED on the model's engine and before the host waits for its loss, so that a caller holding several objects
     (one model / engine / stream each, `run_objects_in_flight`) can queue the others' work in between.  Everything
@@ -119,6 +128,10 @@ def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, 
     # test-time augmentation: the frames' probabilities (the propagated targets of the adaptation rounds included: they are the
     # frames' prediction) are the mean over the views; off = the plain inference call below
     view_set = tta_views.ViewSet(model, frames.shape[2], frames.shape[3], tta) if tta_views.active(tta) else None
+    # the zoom pass follows the first pass of each inference batch (the propagated targets see the refined probabilities, as they
+    # see the mean over the views); off = nothing new is called
+    refiner = zoom_pass.Refiner(model, frames.shape[2], frames.shape[3], zoom, tta if view_set is not None else None) \
+        if zoom_pass.active(zoom) else None
     n = frames.shape[0]
     ona = cfg['eval_online_adapt']
     band = min_prop_band(ona['min_prop'])
@@ -193,7 +206,10 @@ def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, 
             view_set.sync()                     # the view engines of other sizes take this round's weights
         for f in range(rd['eval_min'], rd['eval_max'], nb):
             g = min(f + nb, rd['eval_max'])
-            if view_set is not None:
+            if refiner is not None:
+                x = frames[f:g].contiguous()
+                masks[f:g] = refiner.refine(x, view_set.infer(x) if view_set is not None else model.engine.infer(x))
+            elif view_set is not None:
                 masks[f:g] = view_set.infer(frames[f:g].contiguous())
             else:
                 masks[f:g] = model.engine.infer(frames[f:g].contiguous())
@@ -239,7 +255,7 @@ def object_workers(model, meta_optim, meta_optim_cfg, n, wg_budget=256):
     return ws
 
 
-def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augment=None, train_frame_id=0, tta=None):
+def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augment=None, train_frame_id=0, tta=None, zoom=None):
     """[(probs, hist)] for the objects `gts` of one sequence, up to len(workers) of them in flight together; results are
     those of `finetune_object` one after the other (same engine arithmetic at the same workgroup budget).
     `train_frame_id`: one frame for all objects, or one per object (YouTube-VOS objects that appear later)."""
@@ -259,7 +275,7 @@ def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augm
             if wi not in active and pending:
                 oi = pending.pop(0)
                 active[wi] = (oi, finetune_object_steps(w.model, w.meta_optim, meta_optim_state_dict, frames, gts[oi], cfg,
-                                                        augment, tfid[oi], **_tta_kw(tta)))
+                                                        augment, tfid[oi], **_tta_kw(tta), **_zoom_kw(zoom)))
         for wi in sorted(active):
             oi, gen = active[wi]
             w = workers[wi]
@@ -399,7 +415,7 @@ def _motion_kw(motion, cfg, dataset=None):
 
 
 def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_gts, cfg, augment=None,
-                      train_frame_id=0, tta=None, crf=None, components=None, holes=None, snap=None, motion=None):
+                      train_frame_id=0, tta=None, crf=None, components=None, holes=None, snap=None, motion=None, zoom=None):
     """frames (N,3,H,W) on the GPU, object_gts: list of (1,H,W) binary masks of the train frame.
     cfg keys (names of cfgs/meta.yaml): num_epochs.eval, eval_online_adapt.{step,reset_model_mode,
     num_epochs,min_prop (a threshold, or [lo, hi]: `min_prop_band`)}, data_cfg.batch_sizes.train, seed, loss_func, train_early_stopping_cfg.
@@ -410,11 +426,12 @@ def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_g
     `holes` (`holes.py`): the hole filler runs after the component filter, with the same train frame kept.
     `snap` (`snap.py`): the superpixel snapping runs between the CRF and the component filter, with the same train frame kept.
     `motion` (`motion.py`): the temporal rules of the filter and the hole filler see the previous map warped by block motion.
+    `zoom` (`zoom.py`): every inference call is followed by the object-centred second look at a crop around the object.
     Returns (labels (N,H,W) uint8, per-object probs list, train loss history per object)."""
     probs_all, hist_all = [], []
     for gt in object_gts:
         probs, hist = finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id,
-                                      **_tta_kw(tta))
+                                      **_tta_kw(tta), **_zoom_kw(zoom))
         probs_all.append(probs)
         hist_all.append(hist)
     if crf is None and components is None and not _holes_kw(holes) and not _snap_kw(snap, cfg) and not _motion_kw(motion, cfg):
@@ -437,7 +454,8 @@ def save_label_png(path, labels_hw):
 
 def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dataset_key, save_dir=None,
                      meta_iter=None, meta_epoch=None, best_mean_J=0.0, dist=None, device=None, vis_win_names=None,
-                     log=None, objects_in_flight=None, tta=None, crf=None, components=None, holes=None, snap=None, motion=None):
+                     log=None, objects_in_flight=None, tta=None, crf=None, components=None, holes=None, snap=None, motion=None,
+                     zoom=None):
     """The evaluation worker of `src/util/evaluate.py:111-382` for the DeepLab path: every sequence of `dataset`
     (an `eosvos_amd.data` reader), every object, fine-tune / online adaptation / inference / merge; prediction PNGs
     under `{save_dir}/best_eval_preds/{name}/{split}/{seq}/{frame}.png`, J per sequence, and the
@@ -465,6 +483,8 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
     uint8 RGB; the PNGs, J_seq and the J / F counts see the final maps.
     `motion` (`motion.py`): the gate of the component filter and `prev_overlap` of the hole filler see the previous frame's
     cleaned map warped by block motion of the same quantised frames.
+    `zoom` (`zoom.py`): every inference call is followed by the object-centred second look: the frame cut to a box around the
+    first pass's foreground, scored again on the live engine at the frame's size and blended in inside the box.
     Returns dict(J_seq, mean_J, best_mean_J, time_per_frame, labels={seq: (N,H,W) uint8}) and the DAVIS J / F statistics
     of `eval_davis_seq` (`evaluate.py:345-359`), one entry per object in sequence order: J_obj (the per-object J means the
     reference calls J_seq), J_recall_seq, J_decay_seq, F_seq, F_recall_seq, F_decay_seq, with mean_F and
@@ -576,7 +596,7 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
             item += 1
         if workers is not None and len(mine) > 1:
             res = run_objects_in_flight(workers, meta_optim_state_dict, frames, [gts[o] for o in mine], cfg,
-                                        train_frame_id=[fids[o] for o in mine], **_tta_kw(tta))
+                                        train_frame_id=[fids[o] for o in mine], **_tta_kw(tta), **_zoom_kw(zoom))
             for o, (p, _) in zip(mine, res):
                 probs[o] = p
         else:
@@ -584,7 +604,7 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
                 model.set_wg_budget(0)                                          # alone on the GPU
             for o in mine:
                 probs[o], _ = finetune_object(model, meta_optim, meta_optim_state_dict, frames, gts[o], cfg,
-                                              train_frame_id=fids[o], **_tta_kw(tta))
+                                              train_frame_id=fids[o], **_tta_kw(tta), **_zoom_kw(zoom))
         if world > 1:
             dist.all_reduce(probs)
         eval_time += time.perf_counter() - t0

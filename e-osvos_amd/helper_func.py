@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import tta as tta_views
+from . import zoom as zoom_pass
 from .networks import DeepLabV3, DeepLabV3Plus
 
 
@@ -69,16 +70,20 @@ def init_parent_model(architecture, encoder, train_encoder, decoder_norm_layer=N
     return model, parent_states
 
 
-def run_frames(model, frames, gts=None, loss_func='cross_entropy', tta=None):
+def run_frames(model, frames, gts=None, loss_func='cross_entropy', tta=None, zoom=None):
     """Inference over frames (N,3,H,W) one at a time (batch 1, `test` batch size of the configs):
     returns (`loss_func` per frame or None, acc per frame or None, probs (N,1,H,W)) -- `run_loader`,
     helper_func.py:131-142, evaluates the configured loss with `batch_average: False`.
     `tta` ({'flip': bool, 'scales': [floats]}, `tta.py`): probs are the mean over the mirrored / rescaled views, and the
-    loss is that of the averaged prediction (of its logit, log(p / (1 - p))); None or the neutral dictionary: one plain view."""
+    loss is that of the averaged prediction (of its logit, log(p / (1 - p))); None or the neutral dictionary: one plain view.
+    `zoom` (`zoom.py`): every frame gets a second look at a crop around the object its first pass (the plain view or the mean
+    over the views) found, blended into probs inside the crop; the loss is that of the refined prediction's logit.  None or
+    `max_zoom: 0`: off."""
     model.eval()
     probs, losses, accs = [], [], []
     use_tta = tta_views.active(tta)
-    view_set = None
+    use_zoom = zoom_pass.active(zoom)
+    view_set = refiner = None
     for i in range(frames.shape[0]):
         x = frames[i:i + 1].contiguous()
         eng = model._ensure_engine(x.shape[2], x.shape[3], 1)
@@ -89,9 +94,13 @@ def run_frames(model, frames, gts=None, loss_func='cross_entropy', tta=None):
             p = view_set.infer(x)
         else:
             p = eng.infer(x)
+        if use_zoom:
+            if refiner is None or (refiner.height, refiner.width) != tuple(x.shape[2:]):
+                refiner = zoom_pass.Refiner(model, x.shape[2], x.shape[3], zoom, tta if use_tta else None)
+            p = refiner.refine(x, p)
         probs.append(p)
         if gts is not None:
-            logits = torch.logit(p, eps=1e-7) if use_tta else eng.debug_tensor('logits')[:1]
+            logits = torch.logit(p, eps=1e-7) if use_tta or use_zoom else eng.debug_tensor('logits')[:1]
             losses.append(eng.loss_of(loss_func, logits, gts[i:i + 1].contiguous()))
             pred = p.ge(0.5)
             accs.append(pred.eq(gts[i:i + 1].bool()).float().mean().view(1))

@@ -532,6 +532,62 @@ int eosvos_block_motion(eosvos_engine* e, const uint8_t* rgb, const uint8_t* pre
 int eosvos_warp_labels(eosvos_engine* e, const uint8_t* labels, const int8_t* mv, int n_frames, int height, int width, int block,
                        uint8_t* out);
 
+/* ---- object-centred zoom pass of the inference path: a second look at a crop around the object ------------------------ */
+/* The reference scores each frame once (helper_func.py:131-142).  At output stride 16 a 30-pixel object is two cells of the
+ * ASPP input; the OSVOS / PReMVOS family answers small objects with a second look at a crop around them.  These four entry
+ * points are that step.  The zoomed view has the frame's own size, so it runs on the live engine (eosvos_infer_view) with the
+ * fine-tuned weights in it: what is new is finding the box, cutting the view and putting the result back.  An opt-in extension
+ * (eosvos_amd/zoom.py, `eval_zoom`); the parameter values shown anywhere are examples, untuned.
+ * Per frame, from its first-pass probabilities p0 (height x width = H x W).  Box arithmetic is in integers only; the two zooms
+ * and the margin enter as Q16, zq = round(z * 65536).
+ *   1. mask box  my0, my1, mx0, mx1 = the inclusive bounds of {p0 >= threshold} (an fp32 compare), cnt = its size.
+ *        cnt < min_pixels: the frame is INVALID.
+ *   2. wanted extent  mh = my1 - my0 + 1, mw likewise; pad = ((max(mh, mw) * margin_q16) >> 16) + margin_px;
+ *        gh = mh + 2 pad, gw = mw + 2 pad.
+ *   3. box size, the frame's aspect  bh = min(H, max(gh, ceil(gw * H / W), ceil(H * 65536 / max_zoom_q16)));
+ *        bw = min(W, ceil(bh * W / H)).  bh * min_zoom_q16 > H * 65536: the frame is INVALID (the object is already large, or
+ *        a distant false positive has blown the box up).
+ *   4. position  y0 = clamp((2 my0 + mh - bh) >> 1, 0, H - bh) with an arithmetic shift; x0 likewise: centred on the mask
+ *        box, pushed inside the frame.
+ *   5. record  five int32 per frame: valid, y0, x0, bh, bw.  Invalid frames carry 0, 0, 0, H, W.
+ * eosvos_zoom_boxes: probs device fp32 [n_frames][H][W] -> boxes device int32 [n_frames][5]; any H, W <= 4096, not tied to e's
+ * frame size.  Two launches (csrc/zoom_kernels.hip): a wave per 64-pixel row segment takes the segment's x-range from the
+ * lowest and highest set bit of the ballot word and the count from its popcount, the workgroup combines in LDS and issues
+ * integer atomicMax / atomicAdd on the frame's record (8 words of the engine's scratch, zeroed by the call itself on the
+ * stream); then one thread per frame does steps 2-5.  No float atomics: the result does not depend on any order.  No launch
+ * is cooperative, no workgroup waits for another.
+ *   6. cut  view = bilinear(frame[:, y0 : y0 + bh, x0 : x0 + bw] -> H x W) with torch's align_corners=False rule applied to
+ *        the slice (it clamps at the box edge), scales (float)bh / (float)H and (float)bw / (float)W as in
+ *        eosvos_tta_accumulate.  An invalid frame is copied through bit for bit.
+ * eosvos_zoom_crop: frames, out device fp32 [B][C][H][W] (not overlapping), one thread per output element; the box is read
+ * from device memory, so nothing waits for eosvos_zoom_boxes on the host.
+ *   7. score  eosvos_infer_view(e, view, B, mirror) on the live engine.
+ *   8. put back  pz = sum over the views of view_weight * sigmoid(bilinear(U(logits), H x W -> bh x bw)), the sigmoid
+ *        expression and the resize rule of eosvos_tta_accumulate, U un-mirroring the logits when mirror != 0; defined inside
+ *        the box only.  Plain bilinear down-sampling: the logits are a x4 bilinear up-sampling of the decoder's output, so up
+ *        to max_zoom 4 point sampling between them loses nothing the network produced.
+ * eosvos_zoom_accumulate: reads the logits of e's last forward (H, W are e's frame size) and writes pz (device fp32
+ * [batch][H][W]) inside each valid frame's box only: pz = (first ? 0 : pz) + view_weight * ...; everything else keeps its
+ * bits.
+ *   9. blend  inside the box out = p0 + (weight * f) * (pz - p0), fp32, in this order; outside out = p0.  The ramp is
+ *        f = min(1, (d + 1) / (feather + 1)), d the smallest distance in whole pixels to a box side that is NOT on the frame
+ *        border (y - y0 counts only when y0 > 0, y0 + bh - 1 - y only when y0 + bh < H, the same for x); no such side, or
+ *        feather 0: f = 1.
+ * eosvos_zoom_blend: in place on probs_inout (device fp32 [B][H][W]), inside valid boxes only: invalid frames and pixels
+ * outside the boxes are not written, their bits stay p0's.
+ * All four are asynchronous on the engine's stream and read the boxes from device memory (every consumer clamps a box into the
+ * frame before it addresses anything).  The cost of never reading a box on the host: an invalid frame still pays its forward.
+ * Rejected without a launch: a null pointer; n_frames, B, C, height or width < 1; height or width > 4096; more than 65535
+ * frames; a batch beyond e's (accumulate); threshold outside (0, 1); min_pixels < 1; margin_q16 outside [0, 4 * 65536];
+ * margin_px outside [0, 256]; max_zoom_q16 outside [65536, 4 * 65536]; min_zoom_q16 outside [65536, max_zoom_q16]; a
+ * non-finite view_weight; weight outside (0, 1]; feather outside [0, 64]. */
+int eosvos_zoom_boxes(eosvos_engine* e, const float* probs, int n_frames, int height, int width, float threshold, int min_pixels,
+                      int margin_q16, int margin_px, int min_zoom_q16, int max_zoom_q16, int32_t* boxes);
+int eosvos_zoom_crop(eosvos_engine* e, const float* frames, const int32_t* boxes, int B, int C, int height, int width, float* out);
+int eosvos_zoom_accumulate(eosvos_engine* e, const int32_t* boxes, int batch, int mirror, float view_weight, int first, float* pz);
+int eosvos_zoom_blend(eosvos_engine* e, const int32_t* boxes, int B, int height, int width, float weight, int feather,
+                      const float* pz, float* probs_inout);
+
 /* ---- learning-rate hierarchy (meta_optim.py:27-67) ------------------------------------ */
 /* `lr_hierarchy_level`: how the learned lr state is stored.  NEURON (cfgs/meta.yaml:36) one
  * value per output channel; TENSOR one per trainable tensor (`log_init_lr` of shape
