@@ -94,6 +94,10 @@ _SIGNATURES = {
                                               c_float_p]),
     'eosvos_zoom_blend': (ctypes.c_int, [_E, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                          c_float_p, c_float_p]),
+    'eosvos_lucid_plate': (ctypes.c_int, [_E, c_float_p, c_float_p] + [ctypes.c_int] * 4 + [c_float_p]),
+    'eosvos_lucid_compose': (ctypes.c_int, [_E, c_float_p, c_float_p, c_float_p] + [ctypes.c_int] * 4 +
+                             [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), c_float_p, c_float_p,
+                              ctypes.POINTER(ctypes.c_int32)]),
     'eosvos_set_norm': (ctypes.c_int, [_E, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_float]),
     'eosvos_reset': (ctypes.c_int, [_E]),
     'eosvos_get_params': (ctypes.c_int, [_E, c_float_p]),

@@ -168,6 +168,18 @@ ZOOM = {
 }
 
 
+# Lucid first-frame synthesis for the evaluation's one-shot fine-tune, handled like the groups above (not part of BASE, added
+# by `parse_cli` only when the command line sets one of its keys: `eval_lucid.samples=2 eval_lucid.shift=0.1` -- example values,
+# untuned; read with `cfg.get(...)`).
+#   eval_lucid        some samples of every round-0 batch are composed from the annotated frame with the object and its
+#                     background moved independently (`lucid.py`); the value below is the neutral one (`lucid.DEFAULTS`:
+#                     samples 0, nothing new is called, nothing is drawn)
+LUCID = {
+    'eval_lucid': {'samples': 0, 'dilate': 4, 'rot': 15.0, 'scale': 0.15, 'shift': 0.1, 'bg_rot': 5.0, 'bg_scale': 0.05,
+                   'bg_shift': 0.05, 'min_keep': 0.5},
+}
+
+
 def _merge(dst, src):
     for k, v in src.items():
         if isinstance(v, dict) and isinstance(dst.get(k), dict):
@@ -214,7 +226,7 @@ def parse_cli(argv):
             raise KeyError(f'unknown named config: {a}')
     for k, v in updates:
         group = k.split('.')[0]
-        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL, SNAP, MOTION, ZOOM):
+        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL, SNAP, MOTION, ZOOM, LUCID):
             if group in groups and group not in cfg:
                 cfg[group] = copy.deepcopy(groups[group])
         _set_dotted(cfg, k, v)
@@ -247,6 +259,9 @@ def parse_cli(argv):
     if 'eval_zoom' in cfg:
         from .zoom import check as check_zoom
         check_zoom(cfg['eval_zoom'])                        # ValueError: max_zoom 5, min_zoom above max_zoom, weight 0, ...
+    if 'eval_lucid' in cfg:
+        from .lucid import check as check_lucid
+        check_lucid(cfg['eval_lucid'])                      # ValueError: samples -1, dilate 17, min_keep 0, ...
     unsupported(cfg)
     return cfg
 

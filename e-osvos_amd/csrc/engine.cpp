@@ -208,7 +208,7 @@ struct eosvos_engine {
   size_t davis_cap = 0;
   void* crf_buf = nullptr;              // eosvos_crf_labels: unary + the two Q planes of the mean field (grow-only, freed by destroy)
   size_t crf_cap = 0;
-  void* ccl_buf = nullptr;              // eosvos_label_components / eosvos_filter_components / eosvos_fill_holes: union-find, ids, areas, flags; eosvos_superpixels / eosvos_snap_labels: ids, centres, sums, votes; eosvos_block_motion: luma planes; eosvos_zoom_boxes: the frames' bound records (grow-only, freed by destroy)
+  void* ccl_buf = nullptr;              // eosvos_label_components / eosvos_filter_components / eosvos_fill_holes: union-find, ids, areas, flags; eosvos_superpixels / eosvos_snap_labels: ids, centres, sums, votes; eosvos_block_motion: luma planes; eosvos_zoom_boxes: the frames' bound records; eosvos_lucid_plate: the pyramid above level 0; eosvos_lucid_compose: the samples' counts (grow-only, freed by destroy)
   size_t ccl_cap = 0;
   int lr_level = EOSVOS_LR_NEURON, lr_log = 0;
   float *lr_elem = nullptr, *glr_tmp = nullptr, *ptmp = nullptr;
@@ -2588,12 +2588,8 @@ int eosvos_warp_affine(eosvos_engine* e, const float* src, int channels, int fli
   if (!e) return fail("bad argument");
   return eosvos_warp_affine_hw(e, src, channels, e->H, e->W, flip, rot_deg, scale, interp, dst, nonzero_host);
 }
-int eosvos_warp_affine_hw(eosvos_engine* e, const float* src, int channels, int height, int width, int flip, double rot_deg,
-                          double scale, int interp, float* dst, int* nonzero_host) {
-  ModeScope mode_scope(e);
-  if (!e || !src || !dst || channels < 1 || height < 1 || width < 1) return fail("bad argument");
-  if (interp != EOSVOS_INTER_NEAREST && interp != EOSVOS_INTER_CUBIC) return fail("unknown interpolation");
-  const int H = height, W = width;
+// the warp's counter and the cubic coefficient table, allocated on first use (eosvos_warp_affine_hw, eosvos_lucid_compose)
+static int aug_tables(eosvos_engine* e) {
   if (!e->aug_tab) {
     e->aug_tab = (int*)e->falloc(4);            // the non-zero counter of label warps
     e->aug_ctab = e->falloc(128);
@@ -2609,6 +2605,15 @@ int eosvos_warp_affine_hw(eosvos_engine* e, const float* src, int channels, int 
     }
     HIPOK(hipMemcpy(e->aug_ctab, ct, sizeof(ct), hipMemcpyHostToDevice));
   }
+  return 0;
+}
+int eosvos_warp_affine_hw(eosvos_engine* e, const float* src, int channels, int height, int width, int flip, double rot_deg,
+                          double scale, int interp, float* dst, int* nonzero_host) {
+  ModeScope mode_scope(e);
+  if (!e || !src || !dst || channels < 1 || height < 1 || width < 1) return fail("bad argument");
+  if (interp != EOSVOS_INTER_NEAREST && interp != EOSVOS_INTER_CUBIC) return fail("unknown interpolation");
+  const int H = height, W = width;
+  if (aug_tables(e)) return 1;
   // cv2.getRotationMatrix2D((w/2, h/2), rot, sc): center is a Point2f
   const double ang = rot_deg * (3.1415926535897932384626433832795 / 180.0);
   const double alpha = cos(ang) * scale, beta = sin(ang) * scale;
@@ -3060,6 +3065,50 @@ int eosvos_zoom_blend(eosvos_engine* e, const int32_t* boxes, int B, int height,
   if (feather < 0 || feather > 64) return fail("zoom_blend: feather must be in [0, 64]");
   launch_zoom_blend(boxes, B, height, width, weight, feather, pz, probs_inout, e->s);
   HIPOK(hipGetLastError());
+  return 0;
+}
+
+// ---- lucid first-frame synthesis for the fine-tune: the background plate and the composed samples (eosvos_amd/lucid.py) ----
+static int lucid_check(const char* who, int channels, int height, int width) {
+  const std::string w(who);
+  if (channels < 1 || channels > 64) return fail(w + ": channels must be in [1, 64]");
+  if (height < 1 || width < 1) return fail(w + ": bad frame geometry");
+  if (height > 4096 || width > 4096) return fail(w + ": frames larger than 4096 pixels a side are not supported");
+  return 0;
+}
+int eosvos_lucid_plate(eosvos_engine* e, const float* frame, const float* mask, int channels, int height, int width, int dilate,
+                       float* plate) {
+  if (!e || !frame || !mask || !plate) return fail("lucid_plate: null argument");
+  if (lucid_check("lucid_plate", channels, height, width)) return 1;
+  if (dilate < 0 || dilate > 16) return fail("lucid_plate: dilate must be in [0, 16]");
+  size_t floats, bytes;
+  lucid_scratch(channels, height, width, &floats, &bytes);
+  if (ccl_scratch(e, "lucid_plate", (floats * sizeof(float) + bytes + 3) / 4 * 4, 1)) return 1;
+  float* vbuf = (float*)e->ccl_buf;
+  launch_lucid_plate(frame, mask, channels, height, width, dilate, plate, vbuf, (uint8_t*)(vbuf + floats), e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+int eosvos_lucid_compose(eosvos_engine* e, const float* frame, const float* mask, const float* plate, int channels, int height,
+                         int width, int n_samples, const int32_t* flips, const double* matrices, float* images, float* labels,
+                         int32_t* counts_host) {
+  if (!e || !frame || !mask || !plate || !flips || !matrices || !images || !labels) return fail("lucid_compose: null argument");
+  if (lucid_check("lucid_compose", channels, height, width)) return 1;
+  if (n_samples < 1 || n_samples > LUCID_MAX_SAMPLES)
+    return fail("lucid_compose: between 1 and " + std::to_string(LUCID_MAX_SAMPLES) + " samples per call");
+  for (int i = 0; i < n_samples * 12; ++i)
+    if (!std::isfinite(matrices[i])) return fail("lucid_compose: the matrices must be finite");
+  if (aug_tables(e)) return 1;
+  if (ccl_scratch(e, "lucid_compose", LUCID_MAX_SAMPLES * sizeof(int), n_samples)) return 1;
+  int* counts = (int*)e->ccl_buf;
+  HIPOK(hipMemsetAsync(counts, 0, (size_t)n_samples * sizeof(int), e->s));
+  launch_lucid_compose(frame, mask, plate, channels, height, width, n_samples, flips, matrices, e->aug_ctab, images, labels, counts,
+                       e->s);
+  HIPOK(hipGetLastError());
+  if (counts_host) {                                                // the batch attempt's one host read
+    HIPOK(hipMemcpyAsync(counts_host, counts, (size_t)n_samples * sizeof(int), hipMemcpyDeviceToHost, e->s));
+    HIPOK(hipStreamSynchronize(e->s));
+  }
   return 0;
 }
 

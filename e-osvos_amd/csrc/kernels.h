@@ -85,6 +85,13 @@ __device__ __forceinline__ void tta_src(int o, float scale, int in, int& i0, int
   i1 = i0 + (i0 < in - 1 ? 1 : 0);
   lam = src - (float)i0;
 }
+// An entry of cv::warpAffine's fixed-point tables (10 fractional bits), computed where it is used: (a * i) * 1024 per column
+// and (a * i + b) * 1024 + round_delta per row, in double with each operation rounded on its own (no fused multiply-add),
+// then round-half-even to int like lrint (warp_affine_kernel, lucid_compose_kernel).
+__device__ __forceinline__ int warp_fix(double a, int i) { return __double2int_rn(__dmul_rn(__dmul_rn(a, (double)i), 1024.0)); }
+__device__ __forceinline__ int warp_fix(double a, int i, double b, int rd) {
+  return __double2int_rn(__dmul_rn(__dadd_rn(__dmul_rn(a, (double)i), b), 1024.0)) + rd;
+}
 #endif
 
 // ---------------------------------------------------------------------------------
@@ -508,6 +515,20 @@ void launch_zoom_crop(const float* frames, const int* boxes, int B, int C, int H
 void launch_zoom_accumulate(const float* logits, const int* boxes, int B, int H, int W, int mirror, float weight, int first, float* pz,
                             hipStream_t s);
 void launch_zoom_blend(const int* boxes, int B, int H, int W, float weight, int feather, const float* pz, float* probs, hipStream_t s);
+
+// Lucid first-frame synthesis (lucid_kernels.hip; the rules: include/eosvos.h, eosvos_lucid_plate / eosvos_lucid_compose).
+// frame / plate [C][H][W] fp32, mask [H][W] fp32 (object = != 0), H, W <= 4096.  launch_lucid_plate: 2 + 2 (levels - 1) small
+// launches; vbuf / kbuf hold `floats` floats and `bytes` bytes of lucid_scratch, every element a call reads is written by it
+// first.  launch_lucid_compose: ONE launch for n_samples <= LUCID_MAX_SAMPLES; flips [n] and matrices [n][12] (the inverse
+// background matrix, then the inverse object matrix) are HOST arrays copied into the launch's arguments; images
+// [n][C][H][W], labels [n][H][W]; counts [n] int32 on the device, ZEROED BY THE CALLER on the same stream.
+#define LUCID_MAX_SAMPLES 16
+void lucid_scratch(int C, int H, int W, size_t* floats, size_t* bytes);
+void launch_lucid_plate(const float* frame, const float* mask, int C, int H, int W, int dilate, float* plate, float* vbuf,
+                        uint8_t* kbuf, hipStream_t s);
+void launch_lucid_compose(const float* frame, const float* mask, const float* plate, int C, int H, int W, int n_samples,
+                          const int* flips, const double* matrices, const float* ctab, float* images, float* labels, int* counts,
+                          hipStream_t s);
 
 // theta' = theta - lr[cout]*g, g = rowscale[cout] * sum_z ws[z][...]; optional gsum += g; g_out = g
 void launch_sgd_update(float* w, const float* ws, int splits, int64_t slab, const float* rowscale,

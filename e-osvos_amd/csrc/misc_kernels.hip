@@ -1711,11 +1711,8 @@ namespace eosvos {
 // launch carries everything it reads: no table buffer a later call could overwrite while this one is still queued).
 // Same double expressions as the host form, (M0 * x) * 1024 and (M1 * y + M2) * 1024, each operation rounded on its own
 // (no fused multiply-add), then round-half-even to int like lrint.
+// (`warp_fix` is in kernels.h: lucid_compose_kernel evaluates the same entries.)
 struct WarpMat { double m[6]; int round_delta; };
-__device__ __forceinline__ int warp_fix(double a, int i) { return __double2int_rn(__dmul_rn(__dmul_rn(a, (double)i), 1024.0)); }
-__device__ __forceinline__ int warp_fix(double a, int i, double b, int rd) {
-  return __double2int_rn(__dmul_rn(__dadd_rn(__dmul_rn(a, (double)i), b), 1024.0)) + rd;
-}
 __global__ __launch_bounds__(256) void warp_affine_kernel(const float* __restrict__ src, float* __restrict__ dst,
                                                            int C, int H, int W, const WarpMat wm, const float* __restrict__ ctab,
                                                            int cubic, int flip, int* __restrict__ nonzero) {

@@ -620,6 +620,53 @@ class Engine:
         _ffi.check(self.lib.eosvos_zoom_blend(self.h, _ptr(boxes), b, h, w, float(weight), int(feather), _ptr(pz), _ptr(probs)))
         return probs
 
+    # ---- lucid first-frame synthesis (object and background moved independently, see lucid.py) -----
+    def lucid_plate(self, frame, mask, dilate):
+        """`eosvos_lucid_plate` (`lucid.py`, rules 1-5): frame (C, H, W) and mask (1, H, W) or (H, W), fp32 on the engine's
+        device, any H, W <= 4096 -> the plate (C, H, W): the frame with the mask (grown by `dilate`) filled from the push-pull
+        pyramid.  Nothing waits for the GPU."""
+        from . import lucid
+        if isinstance(dilate, bool) or not isinstance(dilate, int) or not 0 <= dilate <= lucid.MAX_DILATE:
+            raise ValueError(f'lucid_plate: dilate={dilate!r}: an integer in [0, {lucid.MAX_DILATE}]')
+        c, h, w = self._check_lucid('lucid_plate', frame, mask)
+        self._check_stream()
+        plate = torch.empty_like(frame)
+        _ffi.check(self.lib.eosvos_lucid_plate(self.h, _ptr(frame), _ptr(mask), c, h, w, dilate, _ptr(plate)))
+        return plate
+
+    def _check_lucid(self, who, frame, mask, plate=None):
+        from . import lucid
+        self._check_zoom(who, frame, 'frame')
+        if frame.dim() != 3 or frame.shape[0] < 1 or min(frame.shape[1:]) < 1 or max(frame.shape[1:]) > lucid.MAX_SIDE:
+            raise ValueError(f'{who}: frame must be (C, H, W) with 1 <= H, W <= {lucid.MAX_SIDE}, got {tuple(frame.shape)}')
+        self._check_zoom(who, mask, 'mask')
+        if tuple(mask.shape) not in ((1, *frame.shape[1:]), tuple(frame.shape[1:])):
+            raise ValueError(f'{who}: mask must be (1, H, W) or (H, W) of the frame\'s size, got {tuple(mask.shape)}')
+        if plate is not None:
+            self._check_zoom(who, plate, 'plate', shape=frame.shape)
+        return tuple(int(v) for v in frame.shape)
+
+    def lucid_compose(self, frame, mask, plate, params, read_counts=True):
+        """`eosvos_lucid_compose` (`lucid.py`, rules 6-9): ONE launch for the samples params = [{'flip', 'Bi', 'Oi'}] (at most
+        16; the matrices are the inverse ones, 6 doubles each) -> (images (S, C, H, W), labels (S, 1, H, W) of 0 / 1, counts:
+        a list of S ints after one host read, or None without `read_counts`, when nothing waits for the GPU)."""
+        from . import lucid
+        c, h, w = self._check_lucid('lucid_compose', frame, mask, plate)
+        n = len(params)
+        if not 1 <= n <= lucid.MAX_SAMPLES_PER_LAUNCH:
+            raise ValueError(f'lucid_compose: between 1 and {lucid.MAX_SAMPLES_PER_LAUNCH} samples per call, got {n}')
+        flips = (ctypes.c_int32 * n)(*[int(bool(p['flip'])) for p in params])
+        mats = (ctypes.c_double * (12 * n))(*[float(v) for p in params for v in tuple(p['Bi']) + tuple(p['Oi'])])
+        if len(mats) != 12 * n:
+            raise ValueError('lucid_compose: every sample needs two matrices of 6 numbers')
+        self._check_stream()
+        images = torch.empty(n, c, h, w, device=self.device)
+        labels = torch.empty(n, 1, h, w, device=self.device)
+        counts = (ctypes.c_int32 * n)() if read_counts else None
+        _ffi.check(self.lib.eosvos_lucid_compose(self.h, _ptr(frame), _ptr(mask), _ptr(plate), c, h, w, n, flips, mats, _ptr(images),
+                                                 _ptr(labels), counts))
+        return images, labels, (list(counts) if read_counts else None)
+
     def merge_labels(self, probs):
         """probs: (n_obj, H, W) device fp32 -> (H, W) uint8.  `evaluate.py:322-326`."""
         probs = probs.contiguous()

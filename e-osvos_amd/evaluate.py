@@ -26,6 +26,7 @@ from . import holes as hole_filler
 from . import motion as mover
 from . import snap as snapper
 from . import tta as tta_views
+from . import lucid as lucid_pass
 from . import zoom as zoom_pass
 from .helper_func import compute_loss, early_stopping, set_random_seeds
 
@@ -88,13 +89,14 @@ def min_prop_band(min_prop):
 
 
 def finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None,
-                    zoom=None):
+                    zoom=None, lucid=None):
     """One (sequence, object) work item of `evaluate.py:132-317`: fine-tune on the train frame, predict the following
     frames, with online adaptation re-fine-tune every `step` frames.  Returns (probs (N,H,W) with the train frame seeded
     as 2*GT (`:167-168`), train-loss history per round).  `tta`: test-time augmentation of every inference call (`tta.py`).
-    `zoom`: the object-centred second look after every inference call (`zoom.py`)."""
+    `zoom`: the object-centred second look after every inference call (`zoom.py`).  `lucid`: some samples of every round-0
+    batch are composed with the object and its background moved independently (`lucid.py`)."""
     return _drain(finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id,
-                                        **_tta_kw(tta), **_zoom_kw(zoom)))
+                                        **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid)))
 
 
 def _tta_kw(tta):
@@ -107,6 +109,34 @@ def _zoom_kw(zoom):
     return {} if zoom is None else {'zoom': zoom}
 
 
+def _lucid_kw(lucid):
+    """As `_tta_kw`: `lucid` travels as a keyword, and only when it is set."""
+    return {} if lucid is None else {'lucid': lucid}
+
+
+def lucid_batches(model, augment, frame, gt, batch, lucid):
+    """The round-0 batch source of rule 12 of `lucid.py`: `fn(seed) -> (inputs, gts)` whose first batch - k samples come from
+    `augment` (today's path, called for batch - k samples and not at all for 0) and whose last k = min(samples, batch) are
+    synthesised.  The plate is built at the first batch, once.  A mask that is empty or fills the frame: every batch is today's."""
+    k = min(lucid_pass.check(lucid)['samples'], batch)
+    held = []                                                       # the augmenter, built at the first batch
+
+    def fn(seed):
+        eng = model._ensure_engine(frame.shape[2], frame.shape[3], batch)
+        if not held:
+            held.append(lucid_pass.LucidAugmenter(eng, frame[0].contiguous(), gt[0].contiguous(), lucid))
+        aug = held[0]
+        aug.engine = eng                                            # the model's live engine (its stream, its scratch)
+        if not aug.has_object:
+            return augment(frame, gt, batch, seed)
+        plain = augment(frame, gt, batch - k, seed) if batch - k else None
+        images, labels, _ = aug.batch(k)
+        if plain is None:
+            return images, labels
+        return torch.cat([plain[0], images]), torch.cat([plain[1], labels])
+    return fn
+
+
 def _drain(gen):
     try:
         while True:
@@ -116,7 +146,7 @@ def _drain(gen):
 
 
 def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None,
-                          zoom=None):
+                          zoom=None, lucid=None):
     """`finetune_object` as a generator: it yields each time a fine-tune iteration (or a few inference frames) has been
     ENQUEUED on the model's engine and before the host waits for its loss, so that a caller holding several objects
     (one model / engine / stream each, `run_objects_in_flight`) can queue the others' work in between.  Everything
@@ -142,6 +172,10 @@ def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, 
     gt = gt.to(frames.device).float().view(1, 1, *gt.shape[-2:])
     masks = torch.zeros(n, 1, *frames.shape[-2:], device=frames.device)
     masks[train_frame_id] = 2 * gt[0]                               # evaluate.py:167-168
+    # lucid synthesis: the last samples of every round-0 batch are composed from the train frame (the plate is built once per
+    # object, at the first batch); off = nothing new is called, nothing is drawn
+    lucid_batch = lucid_batches(model, augment, frames[train_frame_id:train_frame_id + 1], gt, bsz, lucid) \
+        if lucid_pass.active(lucid) else None
     hist = []
     for r, rd in enumerate(online_adapt_schedule(n, train_frame_id, step, bsz)):
         if r == 0 or ona['reset_model_mode'] == 'FULL':
@@ -181,7 +215,9 @@ def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, 
             round_inputs, round_gts = round_inputs.contiguous(), round_gts.contiguous()
         for epoch in range(1, num_epochs + 1):
             set_random_seeds(cfg.get('seed', 1) + epoch + r)
-            if r == 0:
+            if r == 0 and lucid_batch is not None:
+                inputs, gts = lucid_batch(cfg.get('seed', 1) + epoch)
+            elif r == 0:
                 inputs, gts = augment(frames[train_frame_id:train_frame_id + 1], gt, bsz, cfg.get('seed', 1) + epoch)
             else:
                 inputs, gts = round_inputs, round_gts
@@ -255,7 +291,8 @@ def object_workers(model, meta_optim, meta_optim_cfg, n, wg_budget=256):
     return ws
 
 
-def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augment=None, train_frame_id=0, tta=None, zoom=None):
+def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augment=None, train_frame_id=0, tta=None, zoom=None,
+                          lucid=None):
     """[(probs, hist)] for the objects `gts` of one sequence, up to len(workers) of them in flight together; results are
     those of `finetune_object` one after the other (same engine arithmetic at the same workgroup budget).
     `train_frame_id`: one frame for all objects, or one per object (YouTube-VOS objects that appear later)."""
@@ -275,7 +312,8 @@ def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augm
             if wi not in active and pending:
                 oi = pending.pop(0)
                 active[wi] = (oi, finetune_object_steps(w.model, w.meta_optim, meta_optim_state_dict, frames, gts[oi], cfg,
-                                                        augment, tfid[oi], **_tta_kw(tta), **_zoom_kw(zoom)))
+                                                        augment, tfid[oi], **_tta_kw(tta), **_zoom_kw(zoom),
+                                                        **_lucid_kw(lucid)))
         for wi in sorted(active):
             oi, gen = active[wi]
             w = workers[wi]
@@ -415,7 +453,8 @@ def _motion_kw(motion, cfg, dataset=None):
 
 
 def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_gts, cfg, augment=None,
-                      train_frame_id=0, tta=None, crf=None, components=None, holes=None, snap=None, motion=None, zoom=None):
+                      train_frame_id=0, tta=None, crf=None, components=None, holes=None, snap=None, motion=None, zoom=None,
+                      lucid=None):
     """frames (N,3,H,W) on the GPU, object_gts: list of (1,H,W) binary masks of the train frame.
     cfg keys (names of cfgs/meta.yaml): num_epochs.eval, eval_online_adapt.{step,reset_model_mode,
     num_epochs,min_prop (a threshold, or [lo, hi]: `min_prop_band`)}, data_cfg.batch_sizes.train, seed, loss_func, train_early_stopping_cfg.
@@ -427,11 +466,13 @@ def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_g
     `snap` (`snap.py`): the superpixel snapping runs between the CRF and the component filter, with the same train frame kept.
     `motion` (`motion.py`): the temporal rules of the filter and the hole filler see the previous map warped by block motion.
     `zoom` (`zoom.py`): every inference call is followed by the object-centred second look at a crop around the object.
+    `lucid` (`lucid.py`): the last `samples` samples of every round-0 batch are composed from the train frame with the object
+    and its background moved independently.
     Returns (labels (N,H,W) uint8, per-object probs list, train loss history per object)."""
     probs_all, hist_all = [], []
     for gt in object_gts:
         probs, hist = finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id,
-                                      **_tta_kw(tta), **_zoom_kw(zoom))
+                                      **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid))
         probs_all.append(probs)
         hist_all.append(hist)
     if crf is None and components is None and not _holes_kw(holes) and not _snap_kw(snap, cfg) and not _motion_kw(motion, cfg):
@@ -455,7 +496,7 @@ def save_label_png(path, labels_hw):
 def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dataset_key, save_dir=None,
                      meta_iter=None, meta_epoch=None, best_mean_J=0.0, dist=None, device=None, vis_win_names=None,
                      log=None, objects_in_flight=None, tta=None, crf=None, components=None, holes=None, snap=None, motion=None,
-                     zoom=None):
+                     zoom=None, lucid=None):
     """The evaluation worker of `src/util/evaluate.py:111-382` for the DeepLab path: every sequence of `dataset`
     (an `eosvos_amd.data` reader), every object, fine-tune / online adaptation / inference / merge; prediction PNGs
     under `{save_dir}/best_eval_preds/{name}/{split}/{seq}/{frame}.png`, J per sequence, and the
@@ -485,6 +526,8 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
     cleaned map warped by block motion of the same quantised frames.
     `zoom` (`zoom.py`): every inference call is followed by the object-centred second look: the frame cut to a box around the
     first pass's foreground, scored again on the live engine at the frame's size and blended in inside the box.
+    `lucid` (`lucid.py`): the one-shot fine-tune of every object sees `samples` synthesised samples per round-0 batch: the
+    object cut out of the train frame, the hole filled, object and background moved independently and composed again.
     Returns dict(J_seq, mean_J, best_mean_J, time_per_frame, labels={seq: (N,H,W) uint8}) and the DAVIS J / F statistics
     of `eval_davis_seq` (`evaluate.py:345-359`), one entry per object in sequence order: J_obj (the per-object J means the
     reference calls J_seq), J_recall_seq, J_decay_seq, F_seq, F_recall_seq, F_decay_seq, with mean_F and
@@ -596,7 +639,8 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
             item += 1
         if workers is not None and len(mine) > 1:
             res = run_objects_in_flight(workers, meta_optim_state_dict, frames, [gts[o] for o in mine], cfg,
-                                        train_frame_id=[fids[o] for o in mine], **_tta_kw(tta), **_zoom_kw(zoom))
+                                        train_frame_id=[fids[o] for o in mine], **_tta_kw(tta), **_zoom_kw(zoom),
+                                        **_lucid_kw(lucid))
             for o, (p, _) in zip(mine, res):
                 probs[o] = p
         else:
@@ -604,7 +648,7 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
                 model.set_wg_budget(0)                                          # alone on the GPU
             for o in mine:
                 probs[o], _ = finetune_object(model, meta_optim, meta_optim_state_dict, frames, gts[o], cfg,
-                                              train_frame_id=fids[o], **_tta_kw(tta), **_zoom_kw(zoom))
+                                              train_frame_id=fids[o], **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid))
         if world > 1:
             dist.all_reduce(probs)
         eval_time += time.perf_counter() - t0

@@ -588,6 +588,53 @@ int eosvos_zoom_accumulate(eosvos_engine* e, const int32_t* boxes, int batch, in
 int eosvos_zoom_blend(eosvos_engine* e, const int32_t* boxes, int B, int height, int width, float weight, int feather,
                       const float* pz, float* probs_inout);
 
+/* ---- lucid first-frame synthesis for the one-shot fine-tune: the object and its background moved independently --------- */
+/* The reference's only first-frame augmentation warps the whole frame about its centre (custom_transforms.py), so in every
+ * training sample the object sits in the same place relative to its background.  "Lucid data dreaming" (Khoreva et al.) cuts
+ * the object out, fills the hole, moves object and background independently and composes them again.  These two entry points
+ * are that step; an opt-in extension (eosvos_amd/lucid.py, `eval_lucid`), off by default.  The parameter values shown anywhere
+ * are examples, UNTUNED.  frame [C][H][W] fp32, mask [H][W] fp32 (object = mask != 0), height x width = H x W.
+ * Plate, the frame with the object removed (once per sequence and object):
+ *   1. hole(y, x) = 1 iff a pixel with mask != 0 lies within Chebyshev distance `dilate` inside the frame; known = !hole.
+ *   2. level 0 is H x W: v0 = frame where known, else 0; k0 = known.
+ *   3. level l + 1 is ceil(H_l / 2) x ceil(W_l / 2): k = the OR of the up to four children (2y + i, 2x + j) inside level l;
+ *        v = the sum of the known children's v in the order (0,0), (0,1), (1,0), (1,1), divided by their number, 0 if none is
+ *        known.  Levels are built down to 1 x 1 whatever the data: their number depends on (H, W) only, nothing is read back.
+ *   4. pull, l = top - 1 .. 0: a pixel with k_l = 0 takes the bilinear sample of the COMPLETED level l + 1 at
+ *        ((y + 0.5) / 2 - 0.5, (x + 0.5) / 2 - 0.5): taps floor and floor + 1, both clamped to the level, weights 1/4 and 3/4;
+ *        (1 - ly) * ((1 - lx) * v00 + lx * v01) + ly * ((1 - lx) * v10 + lx * v11), every operation rounded on its own.
+ *        Known pixels keep their value.
+ *   5. plate = v0.  Known pixels carry the frame's bits; a frame with no known pixel gives an all-zero plate.  fp32, no
+ *        atomics, deterministic; every scratch element a call reads is written by it first (EOSVOS_DEBUG_FILL changes no bit).
+ * eosvos_lucid_plate: asynchronous on the engine's stream, 2 + 2 (levels - 1) small launches (csrc/lucid_kernels.hip); the
+ * levels above 0 live in the engine's grow-only scratch.  Any H, W <= 4096, not tied to e's frame size.
+ * Compose, per sample s with `flip`, the inverse background matrix Bi and the inverse object matrix Oi (2 x 3 doubles each, built
+ * and inverted on the host; X = m0 x + m1 y + m2, Y = m3 x + m4 y + m5):
+ *   6. output pixel (y, x): xm = flip ? W - 1 - x : x.  Source coordinates in the 10-bit fixed point of eosvos_warp_affine, entry
+ *        by entry: Xf = lrint((m1 * y + m2) * 1024) + 16 + lrint((m0 * xm) * 1024), Yf likewise from m4, m5, m3 (16 = the
+ *        interpolating round_delta); X = Xf >> 5, Y = Yf >> 5 carry 5 fractional bits.  Evaluated once for Bi, once for Oi.
+ *   7. coverage  A = sum over the 2 x 2 bilinear taps at the object coordinates of wy_i * wx_j * [mask(sy + i, sx + j) != 0],
+ *        sy = Y >> 5, sx = X >> 5, integer weights (32 - f, f), taps outside the frame 0: an integer in [0, 1024].
+ *        label = (A >= 512), alpha = A / 1024, both exact.
+ *   8. Bg = the bicubic sample of the plate at the background coordinates, Ob = that of the frame at the object coordinates:
+ *        the a = -0.75 table at 1/32 pixel of eosvos_warp_affine, taps (Y >> 5) - 1 .. + 2, taps outside the frame 0, the 16
+ *        products value * (cy[i] * cx[j]) added tap by tap, rows first.  Ob is only sampled where A > 0.  image = Ob where
+ *        A == 1024, Bg where A == 0, Bg + alpha * (Ob - Bg) otherwise, fp32, every operation rounded on its own.
+ *   9. count[s] = the number of labelled pixels of sample s: an integer sum (wave reduction, one integer atomic per wave) on a
+ *        record the call zeroes itself on the stream.
+ * eosvos_lucid_compose: ONE launch for all n_samples <= 16 samples (one thread per output pixel, the sample in the grid's third
+ * dimension).  flips [n] int32 and matrices [n][12] doubles (Bi, then Oi) are HOST arrays copied into the launch's arguments:
+ * a queued launch owns everything it reads.  images [n][C][H][W], labels [n][H][W] (0.f / 1.f) on the device, not overlapping
+ * the inputs.  counts_host non-null: the counts [n] are copied there and the call waits for the stream (the one host read of a
+ * batch attempt); null: nothing waits.  Acceptance, redraws and the batch layout (rules 10-13) are the caller's: lucid.py.
+ * Rejected without a launch: a null pointer (counts_host excepted); channels outside [1, 64]; height or width < 1 or > 4096;
+ * dilate outside [0, 16]; n_samples outside [1, 16]; a non-finite matrix entry. */
+int eosvos_lucid_plate(eosvos_engine* e, const float* frame, const float* mask, int channels, int height, int width, int dilate,
+                       float* plate);
+int eosvos_lucid_compose(eosvos_engine* e, const float* frame, const float* mask, const float* plate, int channels, int height,
+                         int width, int n_samples, const int32_t* flips, const double* matrices, float* images, float* labels,
+                         int32_t* counts_host);
+
 /* ---- learning-rate hierarchy (meta_optim.py:27-67) ------------------------------------ */
 /* `lr_hierarchy_level`: how the learned lr state is stored.  NEURON (cfgs/meta.yaml:36) one
  * value per output channel; TENSOR one per trainable tensor (`log_init_lr` of shape
