@@ -98,6 +98,10 @@ _SIGNATURES = {
     'eosvos_lucid_compose': (ctypes.c_int, [_E, c_float_p, c_float_p, c_float_p] + [ctypes.c_int] * 4 +
                              [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), c_float_p, c_float_p,
                               ctypes.POINTER(ctypes.c_int32)]),
+    'eosvos_distance_sq': (ctypes.c_int, [_E, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_void_p]),
+    'eosvos_adapt_targets': (ctypes.c_int, [_E, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int] +
+                             [ctypes.c_float] * 3 + [ctypes.c_int] * 2 + [ctypes.c_float, c_float_p, ctypes.POINTER(ctypes.c_int64)]),
     'eosvos_set_norm': (ctypes.c_int, [_E, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_float]),
     'eosvos_reset': (ctypes.c_int, [_E]),
     'eosvos_get_params': (ctypes.c_int, [_E, c_float_p]),

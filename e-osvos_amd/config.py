@@ -180,6 +180,17 @@ LUCID = {
 }
 
 
+# Distance-gated negatives for online adaptation, handled like the groups above (not part of BASE, whose `eval_online_adapt`
+# keeps the reference's four keys; added by `parse_cli` only when the command line sets one of its keys: `eval_adapt.neg_dist=220
+# eval_adapt.erode=15` -- OnAVOS's published 480p values, an example, untuned; read with `cfg.get(...)`).
+#   eval_adapt        the propagated targets of the adaptation rounds are 0 wherever a pixel is farther than `neg_dist` from the
+#                     mask of the frame before it, eroded by `erode` (`adapt.py`); the value below is the neutral one
+#                     (`adapt.DEFAULTS`: neg_dist 0, nothing new is called).  Active, it needs `eval_online_adapt.step` > 0.
+ADAPT = {
+    'eval_adapt': {'neg_dist': 0, 'erode': 0},
+}
+
+
 def _merge(dst, src):
     for k, v in src.items():
         if isinstance(v, dict) and isinstance(dst.get(k), dict):
@@ -226,7 +237,7 @@ def parse_cli(argv):
             raise KeyError(f'unknown named config: {a}')
     for k, v in updates:
         group = k.split('.')[0]
-        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL, SNAP, MOTION, ZOOM, LUCID):
+        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL, SNAP, MOTION, ZOOM, LUCID, ADAPT):
             if group in groups and group not in cfg:
                 cfg[group] = copy.deepcopy(groups[group])
         _set_dotted(cfg, k, v)
@@ -262,6 +273,10 @@ def parse_cli(argv):
     if 'eval_lucid' in cfg:
         from .lucid import check as check_lucid
         check_lucid(cfg['eval_lucid'])                      # ValueError: samples -1, dilate 17, min_keep 0, ...
+    if 'eval_adapt' in cfg:
+        from .adapt import active as adapts
+        if adapts(cfg['eval_adapt']) and not cfg['eval_online_adapt']['step']:      # ValueError: neg_dist 4096, erode -1, a float, ...
+            raise ValueError('eval_adapt has no consumer: set eval_online_adapt.step')
     unsupported(cfg)
     return cfg
 

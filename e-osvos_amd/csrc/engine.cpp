@@ -3112,6 +3112,55 @@ int eosvos_lucid_compose(eosvos_engine* e, const float* frame, const float* mask
   return 0;
 }
 
+// ---- online adaptation: the capped distance transform and the distance-gated targets (OnAVOS; evaluate.py:231-240) ------
+static int edt_check(const char* who, int n_frames, int height, int width) {
+  const std::string w(who);
+  if (n_frames < 1 || n_frames > 65535) return fail(w + ": between 1 and 65535 frames per call");
+  if (height < 1 || width < 1 || height > 4096 || width > 4096) return fail(w + ": frames of 1 .. 4096 pixels a side");
+  return 0;
+}
+int eosvos_distance_sq(eosvos_engine* e, const float* probs, int n_frames, int height, int width, float threshold, int invert,
+                       int limit, int32_t* out) {
+  if (!e || !probs || !out) return fail("distance_sq: null argument");
+  if (edt_check("distance_sq", n_frames, height, width)) return 1;
+  if (limit < 1 || limit > 4095) return fail("distance_sq: limit must be in [1, 4095]");
+  if (std::isnan(threshold)) return fail("distance_sq: the threshold is NaN");
+  const size_t np = (size_t)n_frames * height * width;
+  if (ccl_scratch(e, "distance_sq", (np * sizeof(uint16_t) + 3) / 4 * 4, n_frames)) return 1;
+  launch_edt_distance(probs, n_frames, height, width, threshold, invert != 0, limit, (uint16_t*)e->ccl_buf, out, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+int eosvos_adapt_targets(eosvos_engine* e, const float* probs, const float* anchors, int n_frames, int height, int width, float lo,
+                         float hi, float anchor_thr, int erode, int neg_dist, float ignore, float* targets, int64_t* n_pos) {
+  if (!e || !probs || !anchors || !targets) return fail("adapt_targets: null argument");
+  if (edt_check("adapt_targets", n_frames, height, width)) return 1;
+  if (neg_dist < 1 || neg_dist > 4095) return fail("adapt_targets: neg_dist must be in [1, 4095]");
+  if (erode < 0 || erode > 255) return fail("adapt_targets: erode must be in [0, 255]");
+  if (!(lo >= 0.f && lo < hi && hi <= 1.f)) return fail("adapt_targets: needs 0 <= lo < hi <= 1");
+  if (std::isnan(anchor_thr)) return fail("adapt_targets: the anchor threshold is NaN");
+  if (!ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  // [count_e | n_pos: 1 word per frame each] [g: 1 16-bit word per pixel] [eroded: 1 byte per pixel, erode > 0 only]
+  const size_t np = (size_t)n_frames * height * width, words = 2 * (size_t)n_frames;
+  const size_t need = (words * sizeof(int) + np * sizeof(uint16_t) + (erode > 0 ? np : 0) + 3) / 4 * 4;
+  if (ccl_scratch(e, "adapt_targets", need, n_frames)) return 1;
+  int* count_e = (int*)e->ccl_buf;
+  int* pos = count_e + n_frames;
+  uint16_t* g = (uint16_t*)(pos + n_frames);
+  uint8_t* eroded = (uint8_t*)(g + np);
+  HIPOK(hipMemsetAsync(count_e, 0, words * sizeof(int), e->s));
+  launch_edt_targets(probs, anchors, n_frames, height, width, lo, hi, anchor_thr, erode, neg_dist, ignore, g, eroded, count_e, pos,
+                     targets, e->s);
+  HIPOK(hipGetLastError());
+  if (n_pos) {                                                      // the round's one host read
+    std::vector<int> host(n_frames);
+    HIPOK(hipMemcpyAsync(host.data(), pos, sizeof(int) * n_frames, hipMemcpyDeviceToHost, e->s));
+    HIPOK(hipStreamSynchronize(e->s));
+    for (int f = 0; f < n_frames; ++f) n_pos[f] = host[f];
+  }
+  return 0;
+}
+
 int eosvos_meta_task_begin(eosvos_engine* e) {
   ModeScope mode_scope(e);
   if (!e) return fail("null engine");
@@ -3567,6 +3616,8 @@ int eosvos_debug_tensor(eosvos_engine* e, const char* name, float** ptr, int64_t
   auto set = [&](float* p, int h, int w, int c) { *ptr = p; dims4[0] = B; dims4[1] = h; dims4[2] = w; dims4[3] = c; return 0; };
   // folded frozen-norm scale / shift (a = gamma / sqrt(var + eps), b = beta - mean * a), all norm layers concatenated
   if (n == "norm_a" || n == "norm_b") { *ptr = n == "norm_a" ? e->na : e->nb; dims4[0] = dims4[1] = dims4[2] = 1; dims4[3] = e->t.nnorm; return 0; }
+  // the grow-only scratch of the label-map and adaptation stages, as 32-bit words (null and 0 words before its first use)
+  if (n == "ccl_scratch") { *ptr = (float*)e->ccl_buf; dims4[0] = dims4[1] = dims4[2] = 1; dims4[3] = (int64_t)(e->ccl_cap / 4); return 0; }
   if (n == "c1") return set(e->c1, e->h2, e->w2, 64);
   if (n == "p1") return set(e->p1, e->h4, e->w4, 64);
   if (n == "g_c1") return set(e->g_c1, e->h2, e->w2, 64);

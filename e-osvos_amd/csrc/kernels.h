@@ -530,6 +530,18 @@ void launch_lucid_compose(const float* frame, const float* mask, const float* pl
                           const int* flips, const double* matrices, const float* ctab, float* images, float* labels, int* counts,
                           hipStream_t s);
 
+// Capped squared distance transform and the distance-gated targets of online adaptation (edt_kernels.hip; the rules:
+// include/eosvos.h, eosvos_distance_sq / eosvos_adapt_targets).  probs / anchors / targets [frame][H][W] fp32, H, W <= 4096,
+// frames <= 65535, limits in [1, 4095].  g: [frame][H][W] 16-bit scratch, eroded: [frame][H][W] byte scratch (erode > 0 only);
+// every word of both that a launch reads is written by the launch before it.  launch_edt_distance: 2 launches, out [frame][H][W]
+// int32 = min(D^2, limit^2 + 1).  launch_edt_targets: 2 launches (4 with erode > 0); count_e / n_pos [frame] int32 on the
+// device, ZEROED BY THE CALLER on the same stream.
+void launch_edt_distance(const float* probs, int n_frames, int H, int W, float threshold, int invert, int limit, uint16_t* g,
+                         int32_t* out, hipStream_t s);
+void launch_edt_targets(const float* probs, const float* anchors, int n_frames, int H, int W, float lo, float hi, float anchor_thr,
+                        int erode, int neg_dist, float ignore, uint16_t* g, uint8_t* eroded, int* count_e, int* n_pos, float* targets,
+                        hipStream_t s);
+
 // theta' = theta - lr[cout]*g, g = rowscale[cout] * sum_z ws[z][...]; optional gsum += g; g_out = g
 void launch_sgd_update(float* w, const float* ws, int splits, int64_t slab, const float* rowscale,
                        const float* lr, float* gsum, float* gout, int64_t rowlen, int64_t n,

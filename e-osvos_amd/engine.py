@@ -463,6 +463,64 @@ class Engine:
                                                        _ptr(out), n_pos))
         return out, ([int(v) for v in n_pos] if counts else None)
 
+    def _check_maps(self, who, t, name):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == self.device and t.dtype == torch.float32):
+            raise ValueError(f'{who}: {name} must be an fp32 tensor on {self.device}')
+        if t.dim() == 4 and t.shape[1] == 1:
+            t = t[:, 0]
+        if t.dim() != 3 or t.shape[0] < 1 or min(t.shape[1:]) < 1 or max(t.shape[1:]) > 4096:
+            raise ValueError(f'{who}: {name} must be (N, 1, H, W) or (N, H, W) with 1 <= H, W <= 4096, got {tuple(t.shape)}')
+        return t.contiguous()
+
+    def distance_sq(self, probs, threshold, invert=False, limit=4095):
+        """Capped squared Euclidean distance to the nearest seed (`eosvos_distance_sq`, rule 1 of `adapt.py`): probs (N, 1, H, W)
+        or (N, H, W) fp32 on the engine's device, any H, W <= 4096; seeds = {probs >= threshold}, or its complement with
+        `invert`.  Returns min(D^2, limit^2 + 1) as int32 of the shape of `probs`.  Nothing waits for the GPU."""
+        from . import adapt
+        limit = adapt._check_limit('distance_sq', limit)
+        if threshold != threshold:
+            raise ValueError('distance_sq: the threshold is NaN')
+        maps = self._check_maps('distance_sq', probs, 'probs')
+        self._check_stream()
+        n, h, w = maps.shape
+        out = torch.empty(n, h, w, dtype=torch.int32, device=self.device)
+        step = adapt.frames_per_call(h, w)
+        for f in range(0, n, step):
+            g = min(f + step, n)
+            _ffi.check(self.lib.eosvos_distance_sq(self.h, _ptr(maps[f:g]), g - f, h, w, threshold, int(bool(invert)), limit,
+                                                   _ptr(out[f:g])))
+        return out.view(probs.shape)
+
+    def adapt_targets(self, probs, anchors, lo, hi, params, ignore, counts=True):
+        """Distance-gated pseudo-label targets of online adaptation (`eosvos_adapt_targets`, rules 2-6 of `adapt.py`): probs and
+        anchors (F, 1, H, W) or (F, H, W) fp32 -- frame i's own probabilities and those of the frame before it -- -> (targets
+        of the shape of `probs`: the band's rule with 0 wherever the pixel is farther than `neg_dist` from the eroded anchor
+        {anchors >= hi}; the number of 1s per frame as a list of ints after ONE host read per chunk of frames under
+        `adapt.SCRATCH_CAP`, or None with counts=False)."""
+        from . import adapt
+        p = adapt.check(params)
+        if not p['neg_dist']:
+            raise ValueError('adapt_targets: neg_dist=0 means "off" for the distance gate; pass a value in [1, 4095]')
+        if not 0.0 <= lo < hi <= 1.0:
+            raise ValueError(f'adapt_targets: needs 0 <= lo < hi <= 1, got {lo!r}, {hi!r}')
+        x, a = self._check_maps('adapt_targets', probs, 'probs'), self._check_maps('adapt_targets', anchors, 'anchors')
+        if x.shape != a.shape:
+            raise ValueError(f'adapt_targets: probs {tuple(x.shape)} and anchors {tuple(a.shape)} must share one shape')
+        ignore = check_ignore(ignore)
+        self._check_stream()
+        n, h, w = x.shape
+        out = torch.empty_like(x)
+        n_pos = []
+        step = adapt.frames_per_call(h, w, p['erode'])
+        for f in range(0, n, step):
+            g = min(f + step, n)
+            host = (ctypes.c_int64 * (g - f))() if counts else None
+            _ffi.check(self.lib.eosvos_adapt_targets(self.h, _ptr(x[f:g]), _ptr(a[f:g]), g - f, h, w, lo, hi, hi, p['erode'],
+                                                     p['neg_dist'], ignore, _ptr(out[f:g]), host))
+            if counts:
+                n_pos.extend(int(v) for v in host)
+        return out.view(probs.shape), (n_pos if counts else None)
+
     def bce(self, logits, masks):
         """Mean BCE-with-logits of arbitrary device tensors (no gradient kept)."""
         logits, masks = logits.contiguous(), masks.contiguous()

@@ -22,6 +22,7 @@ import torch
 
 from . import components as component_filter
 from . import crf as crf_refine
+from . import adapt as adapt_gate
 from . import holes as hole_filler
 from . import motion as mover
 from . import snap as snapper
@@ -89,14 +90,15 @@ def min_prop_band(min_prop):
 
 
 def finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None,
-                    zoom=None, lucid=None):
+                    zoom=None, lucid=None, adapt=None):
     """One (sequence, object) work item of `evaluate.py:132-317`: fine-tune on the train frame, predict the following
     frames, with online adaptation re-fine-tune every `step` frames.  Returns (probs (N,H,W) with the train frame seeded
     as 2*GT (`:167-168`), train-loss history per round).  `tta`: test-time augmentation of every inference call (`tta.py`).
     `zoom`: the object-centred second look after every inference call (`zoom.py`).  `lucid`: some samples of every round-0
-    batch are composed with the object and its background moved independently (`lucid.py`)."""
+    batch are composed with the object and its background moved independently (`lucid.py`).  `adapt`: the propagated targets of
+    the adaptation rounds are 0 wherever a pixel is far from the previous frame's mask (`adapt.py`)."""
     return _drain(finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id,
-                                        **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid)))
+                                        **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid), **_adapt_kw(adapt)))
 
 
 def _tta_kw(tta):
@@ -112,6 +114,11 @@ def _zoom_kw(zoom):
 def _lucid_kw(lucid):
     """As `_tta_kw`: `lucid` travels as a keyword, and only when it is set."""
     return {} if lucid is None else {'lucid': lucid}
+
+
+def _adapt_kw(adapt):
+    """As `_tta_kw`: `adapt` travels as a keyword, and only when it is set."""
+    return {} if adapt is None else {'adapt': adapt}
 
 
 def lucid_batches(model, augment, frame, gt, batch, lucid):
@@ -146,7 +153,7 @@ def _drain(gen):
 
 
 def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None,
-                          zoom=None, lucid=None):
+                          zoom=None, lucid=None, adapt=None):
     """`finetune_object` as a generator: it yields each time a fine-tune iteration (or a few inference frames) has been
     ENQUEUED on the model's engine and before the host waits for its loss, so that a caller holding several objects
     (one model / engine / stream each, `run_objects_in_flight`) can queue the others' work in between.  Everything
@@ -165,6 +172,9 @@ def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, 
     n = frames.shape[0]
     ona = cfg['eval_online_adapt']
     band = min_prop_band(ona['min_prop'])
+    # the distance gate of the adaptation rounds (`adapt.py`): a scalar min_prop t becomes the band (0, t); off = nothing new is
+    # called, the two branches below as they were
+    gate = adapt_gate.band_of(ona['min_prop'], band) if adapt_gate.active(adapt) else None
     step = ona['step']
     bsz = cfg['data_cfg']['batch_sizes']['train']
     es = cfg.get('train_early_stopping_cfg', {'patience': None, 'min_loss_improv': 0.001})
@@ -196,7 +206,19 @@ def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, 
             # the adaptation batch of this round: train frame + the propagated frames whose thresholded prediction is
             # not empty (evaluate.py:231-240).  The reference rebuilds it every epoch from the same masks; once is enough.
             round_inputs, round_gts = frames[train_frame_id:train_frame_id + 1], gt
-            if band is None:
+            if gate is not None:
+                # distance gate: one call builds every propagated frame's targets -- the band's, and 0 wherever the pixel is far
+                # from the (eroded) mask of the frame before it -- and counts its positives; one host read for the round
+                if rd['propagate_frames']:
+                    fs = list(rd['propagate_frames'])
+                    pg, n_pos = adapt_gate.targets(model.engine, masks[fs], masks[[f - 1 for f in fs]], gate[0], gate[1], adapt,
+                                                   PROPAGATION_IGNORE)
+                    keep = [i for i, c in enumerate(n_pos) if c != 0]
+                    if keep:
+                        loss_kwargs = {'ignore': PROPAGATION_IGNORE}
+                        round_inputs = torch.cat([round_inputs, frames[[fs[i] for i in keep]]])
+                        round_gts = torch.cat([round_gts, pg[keep]])
+            elif band is None:
                 for f in rd['propagate_frames']:
                     pg = masks[f:f + 1].ge(ona['min_prop']).float()
                     if pg.sum().item() != 0:                            # evaluate.py:239
@@ -292,7 +314,7 @@ def object_workers(model, meta_optim, meta_optim_cfg, n, wg_budget=256):
 
 
 def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augment=None, train_frame_id=0, tta=None, zoom=None,
-                          lucid=None):
+                          lucid=None, adapt=None):
     """[(probs, hist)] for the objects `gts` of one sequence, up to len(workers) of them in flight together; results are
     those of `finetune_object` one after the other (same engine arithmetic at the same workgroup budget).
     `train_frame_id`: one frame for all objects, or one per object (YouTube-VOS objects that appear later)."""
@@ -313,7 +335,7 @@ def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augm
                 oi = pending.pop(0)
                 active[wi] = (oi, finetune_object_steps(w.model, w.meta_optim, meta_optim_state_dict, frames, gts[oi], cfg,
                                                         augment, tfid[oi], **_tta_kw(tta), **_zoom_kw(zoom),
-                                                        **_lucid_kw(lucid)))
+                                                        **_lucid_kw(lucid), **_adapt_kw(adapt)))
         for wi in sorted(active):
             oi, gen = active[wi]
             w = workers[wi]
@@ -454,7 +476,7 @@ def _motion_kw(motion, cfg, dataset=None):
 
 def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_gts, cfg, augment=None,
                       train_frame_id=0, tta=None, crf=None, components=None, holes=None, snap=None, motion=None, zoom=None,
-                      lucid=None):
+                      lucid=None, adapt=None):
     """frames (N,3,H,W) on the GPU, object_gts: list of (1,H,W) binary masks of the train frame.
     cfg keys (names of cfgs/meta.yaml): num_epochs.eval, eval_online_adapt.{step,reset_model_mode,
     num_epochs,min_prop (a threshold, or [lo, hi]: `min_prop_band`)}, data_cfg.batch_sizes.train, seed, loss_func, train_early_stopping_cfg.
@@ -468,11 +490,12 @@ def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_g
     `zoom` (`zoom.py`): every inference call is followed by the object-centred second look at a crop around the object.
     `lucid` (`lucid.py`): the last `samples` samples of every round-0 batch are composed from the train frame with the object
     and its background moved independently.
+    `adapt` (`adapt.py`): the propagated targets of the adaptation rounds are gated by the distance to the previous frame's mask.
     Returns (labels (N,H,W) uint8, per-object probs list, train loss history per object)."""
     probs_all, hist_all = [], []
     for gt in object_gts:
         probs, hist = finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id,
-                                      **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid))
+                                      **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid), **_adapt_kw(adapt))
         probs_all.append(probs)
         hist_all.append(hist)
     if crf is None and components is None and not _holes_kw(holes) and not _snap_kw(snap, cfg) and not _motion_kw(motion, cfg):
@@ -496,7 +519,7 @@ def save_label_png(path, labels_hw):
 def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dataset_key, save_dir=None,
                      meta_iter=None, meta_epoch=None, best_mean_J=0.0, dist=None, device=None, vis_win_names=None,
                      log=None, objects_in_flight=None, tta=None, crf=None, components=None, holes=None, snap=None, motion=None,
-                     zoom=None, lucid=None):
+                     zoom=None, lucid=None, adapt=None):
     """The evaluation worker of `src/util/evaluate.py:111-382` for the DeepLab path: every sequence of `dataset`
     (an `eosvos_amd.data` reader), every object, fine-tune / online adaptation / inference / merge; prediction PNGs
     under `{save_dir}/best_eval_preds/{name}/{split}/{seq}/{frame}.png`, J per sequence, and the
@@ -528,6 +551,8 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
     first pass's foreground, scored again on the live engine at the frame's size and blended in inside the box.
     `lucid` (`lucid.py`): the one-shot fine-tune of every object sees `samples` synthesised samples per round-0 batch: the
     object cut out of the train frame, the hole filled, object and background moved independently and composed again.
+    `adapt` (`adapt.py`): with online adaptation, the propagated targets of every adaptation round are 0 wherever a pixel is
+    farther than `neg_dist` from the (eroded) mask of the frame before it, whatever the network says there.
     Returns dict(J_seq, mean_J, best_mean_J, time_per_frame, labels={seq: (N,H,W) uint8}) and the DAVIS J / F statistics
     of `eval_davis_seq` (`evaluate.py:345-359`), one entry per object in sequence order: J_obj (the per-object J means the
     reference calls J_seq), J_recall_seq, J_decay_seq, F_seq, F_recall_seq, F_decay_seq, with mean_F and
@@ -640,7 +665,7 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
         if workers is not None and len(mine) > 1:
             res = run_objects_in_flight(workers, meta_optim_state_dict, frames, [gts[o] for o in mine], cfg,
                                         train_frame_id=[fids[o] for o in mine], **_tta_kw(tta), **_zoom_kw(zoom),
-                                        **_lucid_kw(lucid))
+                                        **_lucid_kw(lucid), **_adapt_kw(adapt))
             for o, (p, _) in zip(mine, res):
                 probs[o] = p
         else:
@@ -648,7 +673,8 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
                 model.set_wg_budget(0)                                          # alone on the GPU
             for o in mine:
                 probs[o], _ = finetune_object(model, meta_optim, meta_optim_state_dict, frames, gts[o], cfg,
-                                              train_frame_id=fids[o], **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid))
+                                              train_frame_id=fids[o], **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid),
+                                              **_adapt_kw(adapt))
         if world > 1:
             dist.all_reduce(probs)
         eval_time += time.perf_counter() - t0

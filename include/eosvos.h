@@ -635,6 +635,45 @@ int eosvos_lucid_compose(eosvos_engine* e, const float* frame, const float* mask
                          int width, int n_samples, const int32_t* flips, const double* matrices, float* images, float* labels,
                          int32_t* counts_host);
 
+/* ---- online adaptation: distance-gated negatives from a capped distance transform --------------------------------------- */
+/* The pseudo-labels of the adaptation rounds (evaluate.py:231-240) come from the frame's own probabilities; nothing looks at
+ * where the object was, so a confident blob on a look-alike becomes a positive target of every later round.  OnAVOS
+ * (Voigtlaender & Leibe, 2017) gates them by distance: pixels farther than `neg_dist` from the eroded mask of the previous frame
+ * are negatives whatever the network says, sure and near pixels are positives, the rest is void.  An opt-in extension
+ * (eosvos_amd/adapt.py, `eval_adapt`), off by default; neg_dist 220 / erode 15 (OnAVOS's 480p values) are examples, UNTUNED.
+ * Everything below is integer arithmetic; frames are [H][W] fp32 maps, H, W <= 4096.
+ *   1. capped squared distance  S a set of seed pixels of a frame, L >= 1 an integer limit: D2(p) = min over q in S of
+ *        dy^2 + dx^2 (pixel centres, inside the frame only), out(p) = min(D2(p), L^2 + 1); an empty S gives L^2 + 1 everywhere.
+ *        int32; L <= 4095.  The definition does not depend on the algorithm.  A NaN probability is never a seed under p >= t and
+ *        always one under the inverted predicate !(p >= t).
+ *   2. anchor  for a propagated frame f: A = {p(f - 1) >= t_pos}, p(f - 1) the previous frame's probabilities (the train frame
+ *        holds 2 * ground truth, evaluate.py:167-168); t_pos = the scalar `min_prop`, or `hi` of the band.
+ *   3. erosion  erode = e > 0: E = {q in A : D2_in(q) > e^2}, D2_in = rule 1 with the frame's pixels NOT in A as seeds and
+ *        L = e.  Pixels outside the frame are not background: an object cut by the border is not eroded from the border.
+ *        e = 0: E = A.
+ *   4. far  far(p) <=> rule 1 with seeds E and L = neg_dist gives out(p) > neg_dist^2.
+ *   5. targets of f (p = the frame's own probability): the band's rule, 1 where p >= hi, 0 where p < lo, `ignore` otherwise (a
+ *        NaN is void); a scalar min_prop = t is the band (0, t): nothing near is negative.  Then target = 0 where far.
+ *   6. counts  n_pos[f] = the 1s after the override.  An empty E (object lost or eroded away): n_pos[f] = 0 and the frame's
+ *        targets are the band rule's; the caller drops frames with n_pos = 0.
+ * eosvos_distance_sq (rule 1, the public primitive): seeds = {probs >= threshold}, or its complement with invert != 0;
+ * out [n_frames][H][W] int32.  2 launches (csrc/edt_kernels.hip): a column pass, one thread per column, leaves the vertical
+ * distance capped at L + 1 as 16-bit words in the engine's grow-only scratch; a row pass, one workgroup per row staged in LDS,
+ * takes min over k of k^2 + g^2[x +- k] and stops at k^2 >= best, which is exact.
+ * eosvos_adapt_targets (rules 2-6): anchors [n_frames][H][W] holds frame i's previous-frame probabilities; 2 launches with
+ * erode 0, 4 with it; the distances never reach memory (the row pass writes the eroded mask bytes, or the targets, itself).
+ * Scratch: 2 bytes per pixel, 1 more with erode, 8 per frame; at most 512 MB per call (pass fewer frames).  The two counts per
+ * frame are integer sums (wave reduction, one integer atomic per wave) on words the call zeroes itself on the stream; nothing
+ * depends on what scratch or outputs held before.  n_pos (may be NULL: nothing waits) receives the counts after one
+ * synchronisation.  Asynchronous on the engine's stream otherwise; not tied to e's frame size.
+ * Rejected without a launch, the outputs untouched: a null pointer (n_pos excepted); n_frames outside [1, 65535]; height or
+ * width outside [1, 4096]; limit outside [1, 4095]; neg_dist outside [1, 4095]; erode outside [0, 255]; not 0 <= lo < hi <= 1;
+ * a NaN threshold; an ignore label that is not finite or lies in [0, 1]. */
+int eosvos_distance_sq(eosvos_engine* e, const float* probs, int n_frames, int height, int width, float threshold, int invert,
+                       int limit, int32_t* out);
+int eosvos_adapt_targets(eosvos_engine* e, const float* probs, const float* anchors, int n_frames, int height, int width, float lo,
+                         float hi, float anchor_thr, int erode, int neg_dist, float ignore, float* targets, int64_t* n_pos);
+
 /* ---- learning-rate hierarchy (meta_optim.py:27-67) ------------------------------------ */
 /* `lr_hierarchy_level`: how the learned lr state is stored.  NEURON (cfgs/meta.yaml:36) one
  * value per output channel; TENSOR one per trainable tensor (`log_init_lr` of shape
@@ -766,7 +805,8 @@ int eosvos_bench_conv(eosvos_engine* e, int conv_idx, int kind, int batch, int r
 int eosvos_mfma_probe(eosvos_engine* e, int iters, float* ms_host, double* flops_host);
 /* Device pointer + {B,H,W,C} of a named internal NHWC activation / gradient buffer of the
  * last forward/backward ("c1","p1","blk<i>.out","cat","proj","dcat","d1","d2","lowlog",
- * "logits", "g_*" ...), for the per-stage parity tests. */
+ * "logits", "g_*" ...), for the per-stage parity tests; "ccl_scratch": the grow-only scratch of the label-map and adaptation
+ * stages as dims4[3] 32-bit words (null before its first use). */
 /* Measurement aid: HIP events around every launch of the matrix-core kernels, on the stream each one runs on.
  * profile_read returns, per kernel symbol (names: max_kernels x 64 chars), launches, summed duration (ms) and summed
  * executed fp32-equivalent FLOPs since profile_launches(e, 1).  bench.py's roofline (dominant kernel by time). */
