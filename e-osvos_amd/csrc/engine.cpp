@@ -35,6 +35,7 @@
 
 #include "../../include/eosvos.h"
 #include "kernels.h"
+#include "scratch_layout.h"
 
 using namespace eosvos;
 
@@ -204,12 +205,11 @@ struct eosvos_engine {
   float* lovasz_scratch = nullptr;      // sort buffers of the Lovasz hinge kinds, allocated when one is first selected or used
   int* aug_tab = nullptr;               // eosvos_warp_affine: adelta[W] bdelta[W] X0[H] Y0[H], then the nonzero counter
   float* aug_ctab = nullptr;            // bicubic coefficients at 1/32 pixel: [32][4]
-  void* davis_buf = nullptr;            // eosvos_davis_counts: counts + bit-packed boundary maps (grow-only, freed by destroy)
-  size_t davis_cap = 0;
-  void* crf_buf = nullptr;              // eosvos_crf_labels: unary + the two Q planes of the mean field (grow-only, freed by destroy)
-  size_t crf_cap = 0;
-  void* ccl_buf = nullptr;              // eosvos_label_components / eosvos_filter_components / eosvos_fill_holes: union-find, ids, areas, flags; eosvos_superpixels / eosvos_snap_labels: ids, centres, sums, votes; eosvos_block_motion: luma planes; eosvos_zoom_boxes: the frames' bound records; eosvos_lucid_plate: the pyramid above level 0; eosvos_lucid_compose: the samples' counts (grow-only, freed by destroy)
-  size_t ccl_cap = 0;
+  // the call scratch of every evaluation-stage entry point (scratch_for, scratch_layout.h; grow-only, freed by destroy).  One
+  // buffer serves them all: a call uses it only for launches it enqueues itself on `s`, and either ends with a synchronised
+  // read-back or leaves nothing behind, so the stream orders one call's use before the next one's
+  void* scratch = nullptr;
+  size_t scratch_cap = 0;
   int lr_level = EOSVOS_LR_NEURON, lr_log = 0;
   float *lr_elem = nullptr, *glr_tmp = nullptr, *ptmp = nullptr;
   int *row_tensor = nullptr, *tensor_row0 = nullptr, *all_row0 = nullptr;
@@ -1821,9 +1821,7 @@ int eosvos_destroy(eosvos_engine* e) {
   for (auto& evt : e->ev) (void)hipEventDestroy(evt);
   if (e->ev_wino_w) (void)hipEventDestroy(e->ev_wino_w);
   for (void* p : e->allocs) (void)hipFree(p);
-  if (e->davis_buf) (void)hipFree(e->davis_buf);
-  if (e->crf_buf) (void)hipFree(e->crf_buf);
-  if (e->ccl_buf) (void)hipFree(e->ccl_buf);
+  if (e->scratch) (void)hipFree(e->scratch);
   delete e;
   return 0;
 }
@@ -2642,44 +2640,87 @@ int eosvos_warp_affine_hw(eosvos_engine* e, const float* src, int channels, int 
   return 0;
 }
 
+// ---- what the evaluation-stage entry points below share: the scratch arena, the geometry check, keep runs, the count read ----
+// Makes e->scratch hold `need` bytes; with `capped`, a call may ask for 512 MB at most.  Grow-only.
+static int scratch_grow(eosvos_engine* e, const char* who, size_t need, int n_frames, bool capped = true) {
+  const std::string w(who);
+  if (capped && need > ((size_t)512 << 20))
+    return fail(w + ": " + std::to_string(need >> 20) + " MB of scratch for " + std::to_string(n_frames) +
+                " frames exceeds the 512 MB cap of one call: pass fewer frames per call");
+  if (need > e->scratch_cap) {
+    HIPOK(hipStreamSynchronize(e->s));                              // earlier calls' launches may still read the old buffer
+    if (e->scratch) HIPOK(hipFree(e->scratch));
+    e->scratch = nullptr;
+    e->scratch_cap = 0;
+    if (hipMalloc(&e->scratch, need) != hipSuccess) {
+      (void)hipGetLastError();                                      // the failed allocation is reported here, not by a later call
+      e->scratch = nullptr;
+      return fail(w + ": hipMalloc of " + std::to_string(need >> 20) + " MB of scratch failed");
+    }
+    e->scratch_cap = need;
+    static const char* fill = getenv("EOSVOS_DEBUG_FILL");          // as falloc: the buffer starts out as that word
+    if (fill) { (void)hipMemsetD32((hipDeviceptr_t)e->scratch, (int)strtoul(fill, nullptr, 16), need / 4); (void)hipDeviceSynchronize(); }
+  }
+  return 0;
+}
+// ... for a stage's layout, with the range that stage needs cleared set to 0 on the stream
+static int scratch_for(eosvos_engine* e, const char* who, const ScratchLayout& L, int n_frames, bool capped = true) {
+  if (scratch_grow(e, who, L.need(), n_frames, capped)) return 1;
+  if (L.clear_bytes) HIPOK(hipMemsetAsync((char*)e->scratch + L.clear_at, 0, L.clear_bytes, e->s));
+  return 0;
+}
+// frames in [min_frames, max_frames] and sides in [1, max_side]; a limit of 0 is not checked
+static int frames_check(const char* who, int n_frames, int height, int width, int max_frames = 65535, int max_side = 4096, int min_frames = 0) {
+  const std::string w(who);
+  if (n_frames < min_frames || height < 1 || width < 1) return fail(w + ": bad frame geometry");
+  if (max_side && (height > max_side || width > max_side))
+    return fail(w + ": frames larger than " + std::to_string(max_side) + " pixels a side are not supported");
+  if (max_frames && n_frames > max_frames) return fail(w + ": at most " + std::to_string(max_frames) + " frames per call");
+  return 0;
+}
+extern "C++" {
+template <class T> static T* scratch_at(eosvos_engine* e, ScratchAt<T> r) { return (T*)((char*)e->scratch + r.at); }
+// launch(f, frames, flag) for every run of frames with the same `keep` flag: one frame per run where a frame reads the result
+// of the frame before it (`chained`), one run of kept frames with `all`
+template <class F> static int keep_runs(const uint8_t* keep, int n_frames, bool all, bool chained, F launch) {
+  for (int f = 0, g; f < n_frames; f = g) {
+    const int flag = all || (keep && keep[f]);
+    for (g = f + 1; !chained && g < n_frames && (all || (keep && keep[g]) == flag); ++g) {}
+    launch(f, g - f, flag);
+    HIPOK(hipGetLastError());
+  }
+  return 0;
+}
+// a call's one host read: its n counters at `at`, widened where the device keeps narrower ones; without `host`, no wait
+template <class D, class H> static int read_counts(eosvos_engine* e, ScratchAt<D> at, size_t n, H* host) {
+  if (!host) return 0;
+  std::vector<D> dev(n);
+  HIPOK(hipMemcpyAsync(dev.data(), scratch_at(e, at), n * sizeof(D), hipMemcpyDeviceToHost, e->s));
+  HIPOK(hipStreamSynchronize(e->s));
+  std::copy(dev.begin(), dev.end(), host);
+  return 0;
+}
+}
+
 // ---- DAVIS-2017 evaluation counts (evaluate.py:345-359, helper_func.py:444-458) -------------------------------------
 int eosvos_davis_counts(eosvos_engine* e, const uint8_t* pred, const uint8_t* gt, int n_frames, int height, int width, int n_obj,
                         int bound_pix, int64_t* counts_out) {
   if (!e || !pred || !gt || !counts_out) return fail("davis_counts: null argument");
-  if (n_frames < 0 || height < 1 || width < 1) return fail("davis_counts: bad frame geometry");
+  if (frames_check("davis_counts", n_frames, height, width, 0, 0)) return 1;
   if (width > 64 * 64) return fail("davis_counts: frames wider than 4096 pixels are not supported");
   if (n_obj < 1 || n_obj > 255) return fail("davis_counts: n_obj must be in [1, 255]");
   if (bound_pix < 0 || bound_pix > 63) return fail("davis_counts: the dilation radius must be in [0, 63] pixels");
   if (n_frames == 0) return 0;
-  // frames go through in chunks whose boundary maps take at most 64 MB (at least one frame per chunk)
-  const size_t nw = (size_t)(width + 63) / 64;
-  const size_t map_words = (size_t)n_obj * height * nw;          // one frame, one of the two maps
-  const size_t count_bytes = (size_t)n_frames * n_obj * 6 * sizeof(int64_t);
-  size_t chunk = (size_t)(64 << 20) / (2 * map_words * 8);
-  chunk = std::max<size_t>(1, std::min<size_t>({chunk, (size_t)n_frames, 65535}));
-  const size_t need = count_bytes + 2 * chunk * map_words * 8;
-  if (need > e->davis_cap) {
-    HIPOK(hipStreamSynchronize(e->s));                            // earlier calls' launches may still read the old buffer
-    if (e->davis_buf) HIPOK(hipFree(e->davis_buf));
-    e->davis_buf = nullptr;
-    e->davis_cap = 0;
-    HIPOK(hipMalloc(&e->davis_buf, need));
-    e->davis_cap = need;
-  }
-  int64_t* counts = (int64_t*)e->davis_buf;
-  unsigned long long* bmp = (unsigned long long*)((char*)e->davis_buf + count_bytes);     // count_bytes is a multiple of 8
-  unsigned long long* bmg = bmp + chunk * map_words;
-  HIPOK(hipMemsetAsync(counts, 0, count_bytes, e->s));
+  const DavisCountsLayout L(n_frames, n_obj, height, width);
+  if (scratch_for(e, "davis_counts", L, n_frames, false)) return 1;   // no cap: the maps are chunked here, the counts are small
   const size_t plane = (size_t)height * width;
-  for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += chunk) {
-    const int nf = (int)std::min<size_t>(chunk, (size_t)n_frames - f0);
-    launch_davis_counts(pred + f0 * plane, gt + f0 * plane, nf, height, width, n_obj, bound_pix, bmp, bmg,
-                        counts + f0 * n_obj * 6, e->s);
+  for (size_t f0 = 0; f0 < (size_t)n_frames; f0 += L.chunk) {
+    const int nf = (int)std::min<size_t>(L.chunk, (size_t)n_frames - f0);
+    launch_davis_counts(pred + f0 * plane, gt + f0 * plane, nf, height, width, n_obj, bound_pix, scratch_at(e, L.pred_map),
+                        scratch_at(e, L.gt_map), scratch_at(e, L.counts) + f0 * n_obj * 6, e->s);
     HIPOK(hipGetLastError());
   }
-  HIPOK(hipMemcpyAsync(counts_out, counts, count_bytes, hipMemcpyDeviceToHost, e->s));
-  HIPOK(hipStreamSynchronize(e->s));
-  return 0;
+  return read_counts(e, L.counts, (size_t)n_frames * n_obj * 6, counts_out);
 }
 
 // ---- local dense-CRF refinement of the merged label maps (beside evaluate.py:322-326) -------------------------------
@@ -2687,7 +2728,7 @@ int eosvos_crf_labels(eosvos_engine* e, const float* images, const float* probs,
                       int iterations, int radius, int dilation, float w_appearance, float w_smooth, float theta_alpha,
                       float theta_beta, float theta_gamma, uint8_t* labels_out, float* q_out) {
   if (!e || !images || !probs || !labels_out) return fail("crf_labels: null argument");
-  if (n_frames < 0 || height < 1 || width < 1) return fail("crf_labels: bad frame geometry");
+  if (frames_check("crf_labels", n_frames, height, width, 65535, 0)) return 1;
   if (n_obj < 1 || n_obj > 255) return fail("crf_labels: n_obj must be in [1, 255]");
   if (iterations < 0 || iterations > 20) return fail("crf_labels: iterations must be in [0, 20]");
   if (radius < 1 || radius > 7) return fail("crf_labels: radius must be in [1, 7]");
@@ -2698,7 +2739,6 @@ int eosvos_crf_labels(eosvos_engine* e, const float* images, const float* probs,
   if (!std::isfinite(theta_alpha) || !std::isfinite(theta_beta) || !std::isfinite(theta_gamma) || theta_alpha <= 0.f ||
       theta_beta <= 0.f || theta_gamma <= 0.f)
     return fail("crf_labels: every theta must be finite and > 0");
-  if (n_frames > 65535) return fail("crf_labels: at most 65535 frames per call");
   if (n_frames == 0) return 0;
   const int n_lab = n_obj + 1;
   const int64_t n_pix = (int64_t)height * width;
@@ -2707,27 +2747,10 @@ int eosvos_crf_labels(eosvos_engine* e, const float* images, const float* probs,
     HIPOK(hipGetLastError());
     return 0;
   }
-  const size_t plane = (size_t)n_frames * n_lab * n_pix;           // floats of one of the three buffers
-  const size_t need = 3 * plane * sizeof(float);
-  if (need > ((size_t)512 << 20))
-    return fail("crf_labels: " + std::to_string(need >> 20) + " MB of scratch for " + std::to_string(n_frames) +
-                " frames exceeds the 512 MB cap of one call: pass fewer frames per call");
-  if (need > e->crf_cap) {
-    HIPOK(hipStreamSynchronize(e->s));                              // earlier calls' launches may still read the old buffer
-    if (e->crf_buf) HIPOK(hipFree(e->crf_buf));
-    e->crf_buf = nullptr;
-    e->crf_cap = 0;
-    if (hipMalloc(&e->crf_buf, need) != hipSuccess) {
-      (void)hipGetLastError();                                      // the failed allocation is reported here, not by a later call
-      e->crf_buf = nullptr;
-      return fail("crf_labels: hipMalloc of " + std::to_string(need >> 20) + " MB of scratch failed");
-    }
-    e->crf_cap = need;
-    static const char* fill = getenv("EOSVOS_DEBUG_FILL");          // as falloc: the buffer starts out as that word
-    if (fill) { (void)hipMemsetD32((hipDeviceptr_t)e->crf_buf, (int)strtoul(fill, nullptr, 16), need / 4); (void)hipDeviceSynchronize(); }
-  }
-  float* unary = (float*)e->crf_buf;
-  float* q[2] = {unary + plane, unary + 2 * plane};
+  const CrfLabelsLayout L((size_t)n_frames * n_lab * n_pix);
+  if (scratch_for(e, "crf_labels", L, n_frames)) return 1;
+  float* unary = scratch_at(e, L.unary);
+  float* q[2] = {scratch_at(e, L.q[0]), scratch_at(e, L.q[1])};
   CrfTables tab;
   crf_fill_tables(tab, radius, dilation, theta_alpha, theta_gamma);
   launch_crf_prepare(probs, n_frames, n_obj, n_pix, q[0], unary, nullptr, e->s);
@@ -2745,32 +2768,9 @@ int eosvos_crf_labels(eosvos_engine* e, const float* images, const float* probs,
 // argument checks shared by the two entry points; `who` names the entry point in the message
 static int ccl_check(const char* who, int n_frames, int height, int width, int connectivity) {
   const std::string w(who);
-  if (n_frames < 0 || height < 1 || width < 1) return fail(w + ": bad frame geometry");
-  if (height > 4096 || width > 4096) return fail(w + ": frames larger than 4096 pixels a side are not supported");
+  if (frames_check(who, n_frames, height, width)) return 1;
   if ((int64_t)height * width >= ((int64_t)1 << 24)) return fail(w + ": frames of 2^24 pixels or more are not supported");
   if (connectivity != 4 && connectivity != 8) return fail(w + ": connectivity must be 4 or 8");
-  if (n_frames > 65535) return fail(w + ": at most 65535 frames per call");
-  return 0;
-}
-static int ccl_scratch(eosvos_engine* e, const char* who, size_t need, int n_frames) {
-  const std::string w(who);
-  if (need > ((size_t)512 << 20))
-    return fail(w + ": " + std::to_string(need >> 20) + " MB of scratch for " + std::to_string(n_frames) +
-                " frames exceeds the 512 MB cap of one call: pass fewer frames per call");
-  if (need > e->ccl_cap) {
-    HIPOK(hipStreamSynchronize(e->s));                              // earlier calls' launches may still read the old buffer
-    if (e->ccl_buf) HIPOK(hipFree(e->ccl_buf));
-    e->ccl_buf = nullptr;
-    e->ccl_cap = 0;
-    if (hipMalloc(&e->ccl_buf, need) != hipSuccess) {
-      (void)hipGetLastError();
-      e->ccl_buf = nullptr;
-      return fail(w + ": hipMalloc of " + std::to_string(need >> 20) + " MB of scratch failed");
-    }
-    e->ccl_cap = need;
-    static const char* fill = getenv("EOSVOS_DEBUG_FILL");          // as falloc: the buffer starts out as that word
-    if (fill) { (void)hipMemsetD32((hipDeviceptr_t)e->ccl_buf, (int)strtoul(fill, nullptr, 16), need / 4); (void)hipDeviceSynchronize(); }
-  }
   return 0;
 }
 
@@ -2779,10 +2779,10 @@ int eosvos_label_components(eosvos_engine* e, const uint8_t* labels, int n_frame
   if (!e || !labels || !ids_out) return fail("label_components: null argument");
   if (ccl_check("label_components", n_frames, height, width, connectivity)) return 1;
   if (n_frames == 0) return 0;
-  const size_t np = (size_t)n_frames * height * width;
-  if (ccl_scratch(e, "label_components", ((2 * np * sizeof(int)) + 3) / 4 * 4, n_frames)) return 1;
-  int* parent = (int*)e->ccl_buf;
-  launch_ccl_label(labels, n_frames, height, width, connectivity, parent, parent + np, ids_out, nullptr, e->s);
+  const LabelComponentsLayout L((size_t)n_frames * height * width);
+  if (scratch_for(e, "label_components", L, n_frames)) return 1;
+  launch_ccl_label(labels, n_frames, height, width, connectivity, scratch_at(e, L.parent), scratch_at(e, L.tarea), ids_out,
+                   nullptr, e->s);
   HIPOK(hipGetLastError());
   return 0;
 }
@@ -2797,46 +2797,26 @@ int eosvos_filter_components(eosvos_engine* e, const uint8_t* labels, int n_fram
   if (rel_q16 < 0 || rel_q16 > 65536) return fail("filter_components: rel_q16 must be in [0, 65536]");
   if (n_frames == 0) return 0;
   const size_t P = (size_t)height * width, np = (size_t)n_frames * P;
-  // [parent | tarea | ids | area] ints, [best: 256 per frame | removed: 1 per frame] 64-bit words, [cand: 1 per pixel |
-  // pres: 256 per frame and 256 for `prev`] bytes; everything from `area` on starts out as 0
-  const size_t words = (size_t)n_frames * 257, bytes = np + ((size_t)n_frames + 1) * 256;
-  const size_t need = (4 * np * sizeof(int) + words * 8 + bytes + 3) / 4 * 4;
-  if (ccl_scratch(e, "filter_components", need, n_frames)) return 1;
-  int* parent = (int*)e->ccl_buf;
-  int *tarea = parent + np, *ids = tarea + np, *area = ids + np;
-  unsigned long long* best = (unsigned long long*)(area + np);     // 16 * np bytes in: 8-byte aligned
-  unsigned long long* removed = best + (size_t)n_frames * 256;
-  uint8_t* cand = (uint8_t*)(removed + n_frames);
-  uint8_t* pres = cand + np;
-  HIPOK(hipMemsetAsync(area, 0, np * sizeof(int) + words * 8 + bytes, e->s));
-  launch_ccl_label(labels, n_frames, height, width, connectivity, parent, tarea, ids, area, e->s);
+  const FilterComponentsLayout L(n_frames, np);
+  if (scratch_for(e, "filter_components", L, n_frames)) return 1;
+  int *ids = scratch_at(e, L.ids), *area = scratch_at(e, L.area);
+  unsigned long long *best = scratch_at(e, L.best), *removed = scratch_at(e, L.removed);
+  uint8_t *cand = scratch_at(e, L.cand), *pres = scratch_at(e, L.pres);
+  launch_ccl_label(labels, n_frames, height, width, connectivity, scratch_at(e, L.parent), scratch_at(e, L.tarea), ids, area,
+                   e->s);
   HIPOK(hipGetLastError());
-  auto kept = [&](int f) { return keep && keep[f] ? 1 : 0; };
-  if (gate > 0) {                        // frame by frame: the gate of a frame reads the filtered frame before it
-    if (prev) launch_ccl_presence(prev, (int)P, pres, e->s);
-    for (int f = 0; f < n_frames; ++f) {
-      const uint8_t* R = f == 0 ? prev : out + (size_t)(f - 1) * P;
-      const uint8_t* pres_f = R ? pres + (size_t)f * 256 : nullptr;
-      if (R && !kept(f)) launch_ccl_gate(labels + f * P, R, pres_f, ids + f * P, height, width, gate, cand + f * P, e->s);
-      launch_ccl_filter(labels + f * P, ids + f * P, area + f * P, pres_f, cand + f * P, kept(f), 1, (int)P, min_area,
-                        (unsigned)rel_q16, largest_only != 0, best + (size_t)f * 256, out + f * P, pres + (size_t)(f + 1) * 256,
-                        removed + f, e->s);
-      HIPOK(hipGetLastError());
-    }
-  } else {                               // no frame depends on another: one launch per run of frames with the same `keep` flag
-    for (int f = 0, g; f < n_frames; f = g) {
-      for (g = f + 1; g < n_frames && kept(g) == kept(f); ++g) {}
-      launch_ccl_filter(labels + f * P, ids + f * P, area + f * P, nullptr, cand + f * P, kept(f), g - f, (int)P, min_area,
-                        (unsigned)rel_q16, largest_only != 0, best + (size_t)f * 256, out + f * P, pres + (size_t)(f + 1) * 256,
-                        removed + f, e->s);
-      HIPOK(hipGetLastError());
-    }
-  }
-  if (removed_out) {
-    HIPOK(hipMemcpyAsync(removed_out, removed, (size_t)n_frames * sizeof(int64_t), hipMemcpyDeviceToHost, e->s));
-    HIPOK(hipStreamSynchronize(e->s));
-  }
-  return 0;
+  const bool chained = gate > 0;          // frame by frame: the gate of a frame reads the filtered frame before it
+  if (chained && prev) launch_ccl_presence(prev, (int)P, pres, e->s);
+  if (keep_runs(keep, n_frames, false, chained, [&](int f, int frames, int flag) {
+        const uint8_t* R = !chained ? nullptr : f == 0 ? prev : out + (size_t)(f - 1) * P;
+        const uint8_t* pres_f = R ? pres + (size_t)f * 256 : nullptr;
+        if (R && !flag) launch_ccl_gate(labels + f * P, R, pres_f, ids + f * P, height, width, gate, cand + f * P, e->s);
+        launch_ccl_filter(labels + f * P, ids + f * P, area + f * P, pres_f, cand + f * P, flag, frames, (int)P, min_area,
+                          (unsigned)rel_q16, largest_only != 0, best + (size_t)f * 256, out + f * P, pres + (size_t)(f + 1) * 256,
+                          removed + f, e->s);
+      }))
+    return 1;
+  return read_counts(e, L.removed, n_frames, removed_out);
 }
 
 // ---- hole filling of the merged label maps (after the component filter) ------------------------------------------------
@@ -2850,64 +2830,43 @@ int eosvos_fill_holes(eosvos_engine* e, const uint8_t* labels, int n_frames, int
   if (overlap_q16 < 0 || overlap_q16 > 65536) return fail("fill_holes: overlap_q16 must be in [0, 65536]");
   if (n_frames == 0) return 0;
   const size_t P = (size_t)height * width, np = (size_t)n_frames * P;
-  // [parent | tarea | ids | area | rec | cnt] 32-bit words per pixel, [hist: 256 per frame] 32-bit words, pad to 8 bytes,
-  // [filled: 1 per frame] 64-bit words, [pres: 256 per frame and 256 for `prev`] bytes; everything from `area` on starts out as 0
-  const size_t words = 6 * np + (size_t)n_frames * 256;
-  const size_t filled_at = (words * 4 + 7) / 8 * 8;
-  const size_t need = filled_at + (size_t)n_frames * 8 + ((size_t)n_frames + 1) * 256;
-  if (ccl_scratch(e, "fill_holes", need, n_frames)) return 1;
-  int* parent = (int*)e->ccl_buf;
-  int *tarea = parent + np, *ids = tarea + np, *area = ids + np;
-  unsigned *rec = (unsigned*)(area + np), *cnt = rec + np, *hist = cnt + np;
-  unsigned long long* filled = (unsigned long long*)((char*)e->ccl_buf + filled_at);
-  uint8_t* pres = (uint8_t*)(filled + n_frames);
-  HIPOK(hipMemsetAsync(area, 0, need - 3 * np * sizeof(int), e->s));
-  auto kept = [&](int f) { return keep && keep[f] ? 1 : 0; };
+  const FillHolesLayout L(n_frames, np);
+  if (scratch_for(e, "fill_holes", L, n_frames)) return 1;
+  int *ids = scratch_at(e, L.ids), *area = scratch_at(e, L.area);
+  unsigned *rec = scratch_at(e, L.rec), *cnt = scratch_at(e, L.cnt), *hist = scratch_at(e, L.hist);
+  unsigned long long* filled = scratch_at(e, L.filled);
+  uint8_t* pres = scratch_at(e, L.pres);
   const bool off = max_area == 0 || rel_q16 == 0;                  // no hole can pass the size rule: every frame is copied
   if (!off) {
-    launch_ccl_label_zero(labels, n_frames, height, width, connectivity == 8 ? 4 : 8, parent, tarea, ids, area, e->s);
+    launch_ccl_label_zero(labels, n_frames, height, width, connectivity == 8 ? 4 : 8, scratch_at(e, L.parent),
+                          scratch_at(e, L.tarea), ids, area, e->s);
     launch_hole_scan(labels, ids, n_frames, height, width, connectivity, rec, hist, e->s);
     HIPOK(hipGetLastError());
   }
-  if (!off && overlap_q16 > 0) {         // frame by frame: the rule of a frame reads the filled frame before it
-    if (prev) launch_ccl_presence(prev, (int)P, pres, e->s);
-    for (int f = 0; f < n_frames; ++f) {
-      const uint8_t* R = f == 0 ? prev : out + (size_t)(f - 1) * P;
-      const uint8_t* pres_f = R ? pres + (size_t)f * 256 : nullptr;
-      if (R && !kept(f))
-        launch_hole_overlap(labels + f * P, R, pres_f, ids + f * P, area + f * P, rec + f * P, hist + (size_t)f * 256, (int)P, max_area,
-                            (unsigned)rel_q16, cnt + f * P, e->s);
-      launch_hole_apply(labels + f * P, ids + f * P, area + f * P, rec + f * P, hist + (size_t)f * 256, cnt + f * P, pres_f, kept(f), 1,
-                        (int)P, max_area, (unsigned)rel_q16, (unsigned)overlap_q16, out + f * P, pres + (size_t)(f + 1) * 256,
-                        filled + f, e->s);
-      HIPOK(hipGetLastError());
-    }
-  } else {                               // no frame depends on another: one launch per run of frames with the same `keep` flag
-    for (int f = 0, g; f < n_frames; f = g) {
-      for (g = f + 1; g < n_frames && (off || kept(g) == kept(f)); ++g) {}
-      launch_hole_apply(labels + f * P, ids + f * P, area + f * P, rec + f * P, hist + (size_t)f * 256, cnt + f * P, nullptr,
-                        off || kept(f), g - f, (int)P, max_area, (unsigned)rel_q16, 0u, out + f * P, pres + (size_t)(f + 1) * 256,
-                        filled + f, e->s);
-      HIPOK(hipGetLastError());
-    }
-  }
-  if (filled_out) {
-    HIPOK(hipMemcpyAsync(filled_out, filled, (size_t)n_frames * sizeof(int64_t), hipMemcpyDeviceToHost, e->s));
-    HIPOK(hipStreamSynchronize(e->s));
-  }
-  return 0;
+  const bool chained = !off && overlap_q16 > 0;   // frame by frame: the rule of a frame reads the filled frame before it
+  if (chained && prev) launch_ccl_presence(prev, (int)P, pres, e->s);
+  if (keep_runs(keep, n_frames, off, chained, [&](int f, int frames, int flag) {
+        const uint8_t* R = !chained ? nullptr : f == 0 ? prev : out + (size_t)(f - 1) * P;
+        const uint8_t* pres_f = R ? pres + (size_t)f * 256 : nullptr;
+        if (R && !flag)
+          launch_hole_overlap(labels + f * P, R, pres_f, ids + f * P, area + f * P, rec + f * P, hist + (size_t)f * 256, (int)P,
+                              max_area, (unsigned)rel_q16, cnt + f * P, e->s);
+        launch_hole_apply(labels + f * P, ids + f * P, area + f * P, rec + f * P, hist + (size_t)f * 256, cnt + f * P, pres_f, flag,
+                          frames, (int)P, max_area, (unsigned)rel_q16, chained ? (unsigned)overlap_q16 : 0u, out + f * P,
+                          pres + (size_t)(f + 1) * 256, filled + f, e->s);
+      }))
+    return 1;
+  return read_counts(e, L.filled, n_frames, filled_out);
 }
 
 // ---- SLIC superpixels and the superpixel vote on the merged label maps (between the CRF and the component filter) ----------
 // argument checks shared by the two entry points; `who` names the entry point in the message
 static int slic_check(const char* who, int n_frames, int height, int width, int step, int iterations, int compactness) {
   const std::string w(who);
-  if (n_frames < 0 || height < 1 || width < 1) return fail(w + ": bad frame geometry");
-  if (height > 4096 || width > 4096) return fail(w + ": frames larger than 4096 pixels a side are not supported");
+  if (frames_check(who, n_frames, height, width)) return 1;
   if (step < 4 || step > 64) return fail(w + ": step must be in [4, 64]");
   if (iterations < 1 || iterations > 20) return fail(w + ": iterations must be in [1, 20]");
   if (compactness < 1 || compactness > 64) return fail(w + ": compactness must be in [1, 64]");
-  if (n_frames > 65535) return fail(w + ": at most 65535 frames per call");
   return 0;
 }
 
@@ -2924,12 +2883,10 @@ int eosvos_superpixels(eosvos_engine* e, const uint8_t* rgb, int n_frames, int h
   if (!e || !rgb || !ids_out) return fail("superpixels: null argument");
   if (slic_check("superpixels", n_frames, height, width, step, iterations, compactness)) return 1;
   if (n_frames == 0) return 0;
-  const size_t K = (size_t)((height + step - 1) / step) * ((width + step - 1) / step), nk = (size_t)n_frames * K;
-  if (ccl_scratch(e, "superpixels", 11 * nk * sizeof(int), n_frames)) return 1;      // [centres: 5 | sums: 6] words per cluster
-  int* centres = (int*)e->ccl_buf;
-  unsigned* sums = (unsigned*)(centres + 5 * nk);
-  HIPOK(hipMemsetAsync(sums, 0, 6 * nk * sizeof(unsigned), e->s));
-  slic_run(rgb, nullptr, n_frames, height, width, step, iterations, compactness, 0, centres, sums, ids_out, nullptr, e->s);
+  const SuperpixelsLayout L(n_frames * slic_clusters(height, width, step));
+  if (scratch_for(e, "superpixels", L, n_frames)) return 1;
+  slic_run(rgb, nullptr, n_frames, height, width, step, iterations, compactness, 0, scratch_at(e, L.centres),
+           scratch_at(e, L.sums), ids_out, nullptr, e->s);
   HIPOK(hipGetLastError());
   return 0;
 }
@@ -2942,51 +2899,35 @@ int eosvos_snap_labels(eosvos_engine* e, const uint8_t* rgb, const uint8_t* labe
   if (n_obj < 1 || n_obj > 255) return fail("snap_labels: n_obj must be in [1, 255]");
   if (min_share_q16 < 0 || min_share_q16 > 65536) return fail("snap_labels: min_share_q16 must be in [0, 65536]");
   if (n_frames == 0) return 0;
-  const size_t P = (size_t)height * width, np = (size_t)n_frames * P;
-  const size_t K = (size_t)((height + step - 1) / step) * ((width + step - 1) / step), nk = (size_t)n_frames * K;
-  const size_t nl = (size_t)n_obj + 1;
-  // [ids: 1 per pixel | centres: 5 | sums: 6 | votes: n_obj + 1 per cluster] 32-bit words, pad to 8 bytes, [changed: 1 per
-  // frame] 64-bit words; everything from `sums` on starts out as 0
-  const size_t words = np + (11 + nl) * nk;
-  const size_t changed_at = (words * 4 + 7) / 8 * 8;
-  const size_t need = changed_at + (size_t)n_frames * 8;
-  if (ccl_scratch(e, "snap_labels", need, n_frames)) return 1;
-  int* ids = (int*)e->ccl_buf;
-  int* centres = ids + np;
-  unsigned *sums = (unsigned*)(centres + 5 * nk), *votes = sums + 6 * nk;
-  unsigned long long* changed = (unsigned long long*)((char*)e->ccl_buf + changed_at);
-  HIPOK(hipMemsetAsync(sums, 0, need - (np + 5 * nk) * sizeof(int), e->s));
-  slic_run(rgb, labels, n_frames, height, width, step, iterations, compactness, n_obj, centres, sums, ids, votes, e->s);
+  const size_t P = (size_t)height * width, K = slic_clusters(height, width, step), nl = (size_t)n_obj + 1;
+  const SnapLabelsLayout L(n_frames, n_frames * P, n_frames * K, nl);
+  if (scratch_for(e, "snap_labels", L, n_frames)) return 1;
+  int* ids = scratch_at(e, L.ids);
+  unsigned* votes = scratch_at(e, L.votes);
+  unsigned long long* changed = scratch_at(e, L.changed);
+  slic_run(rgb, labels, n_frames, height, width, step, iterations, compactness, n_obj, scratch_at(e, L.centres),
+           scratch_at(e, L.sums), ids, votes, e->s);
   HIPOK(hipGetLastError());
-  auto kept = [&](int f) { return keep && keep[f] ? 1 : 0; };
-  for (int f = 0, g; f < n_frames; f = g) {                        // one apply launch per run of frames with the same `keep` flag
-    for (g = f + 1; g < n_frames && kept(g) == kept(f); ++g) {}
-    launch_slic_apply(labels + f * P, ids + f * P, votes + f * K * nl, kept(f), g - f, height, width, step, n_obj,
-                      (unsigned)min_share_q16, out + f * P, changed + f, e->s);
-    HIPOK(hipGetLastError());
-  }
-  if (changed_out) {
-    HIPOK(hipMemcpyAsync(changed_out, changed, (size_t)n_frames * sizeof(int64_t), hipMemcpyDeviceToHost, e->s));
-    HIPOK(hipStreamSynchronize(e->s));
-  }
-  return 0;
+  if (keep_runs(keep, n_frames, false, false, [&](int f, int frames, int flag) {
+        launch_slic_apply(labels + f * P, ids + f * P, votes + f * K * nl, flag, frames, height, width, step, n_obj,
+                          (unsigned)min_share_q16, out + f * P, changed + f, e->s);
+      }))
+    return 1;
+  return read_counts(e, L.changed, n_frames, changed_out);
 }
 
 // ---- block motion on 8-bit luma and the warp of label maps by it (for the temporal rules of the filter and the hole filler) --
 int eosvos_block_motion(eosvos_engine* e, const uint8_t* rgb, const uint8_t* prev_rgb, int n_frames, int height, int width, int block,
                         int radius, int bias, int8_t* mv) {
   if (!e || !rgb || !mv) return fail("block_motion: null argument");
-  if (n_frames < 0 || height < 1 || width < 1) return fail("block_motion: bad frame geometry");
-  if (height > 4096 || width > 4096) return fail("block_motion: frames larger than 4096 pixels a side are not supported");
+  if (frames_check("block_motion", n_frames, height, width, 65534)) return 1;   // one plane more than frames: `prev_rgb`'s
   if (block != 8 && block != 16) return fail("block_motion: block must be 8 or 16");
   if (radius < 1 || radius > 32) return fail("block_motion: radius must be in [1, 32]");
   if (bias < 0 || bias > 255) return fail("block_motion: bias must be in [0, 255]");
-  if (n_frames > 65534) return fail("block_motion: at most 65534 frames per call");
   if (n_frames == 0) return 0;
-  // n_frames + 1 luma planes of height rows, each row padded to a multiple of four bytes
-  const size_t plane = (size_t)height * ((width + 3) / 4 * 4);
-  if (ccl_scratch(e, "block_motion", ((size_t)n_frames + 1) * plane, n_frames)) return 1;
-  unsigned* luma = (unsigned*)e->ccl_buf;
+  const BlockMotionLayout L(n_frames, height, width);
+  if (scratch_for(e, "block_motion", L, n_frames)) return 1;
+  unsigned* luma = scratch_at(e, L.luma);
   const int first = prev_rgb ? 0 : 1;
   const size_t per_frame = (size_t)((height + block - 1) / block) * ((width + block - 1) / block) * 2;
   if (first) HIPOK(hipMemsetAsync(mv, 0, per_frame, e->s));          // no frame before the first: zeros
@@ -3000,10 +2941,8 @@ int eosvos_block_motion(eosvos_engine* e, const uint8_t* rgb, const uint8_t* pre
 int eosvos_warp_labels(eosvos_engine* e, const uint8_t* labels, const int8_t* mv, int n_frames, int height, int width, int block,
                        uint8_t* out) {
   if (!e || !labels || !mv || !out) return fail("warp_labels: null argument");
-  if (n_frames < 0 || height < 1 || width < 1) return fail("warp_labels: bad frame geometry");
-  if (height > 4096 || width > 4096) return fail("warp_labels: frames larger than 4096 pixels a side are not supported");
+  if (frames_check("warp_labels", n_frames, height, width)) return 1;
   if (block != 8 && block != 16) return fail("warp_labels: block must be 8 or 16");
-  if (n_frames > 65535) return fail("warp_labels: at most 65535 frames per call");
   if (n_frames == 0) return 0;
   launch_motion_warp(labels, mv, n_frames, height, width, block, out, e->s);
   HIPOK(hipGetLastError());
@@ -3015,9 +2954,7 @@ static bool finite_f(float v) { return v == v && v - v == 0.f; }
 int eosvos_zoom_boxes(eosvos_engine* e, const float* probs, int n_frames, int height, int width, float threshold, int min_pixels,
                       int margin_q16, int margin_px, int min_zoom_q16, int max_zoom_q16, int32_t* boxes) {
   if (!e || !probs || !boxes) return fail("zoom_boxes: null argument");
-  if (n_frames < 1 || height < 1 || width < 1) return fail("zoom_boxes: bad frame geometry");
-  if (height > 4096 || width > 4096) return fail("zoom_boxes: frames larger than 4096 pixels a side are not supported");
-  if (n_frames > 65535) return fail("zoom_boxes: at most 65535 frames per call");
+  if (frames_check("zoom_boxes", n_frames, height, width, 65535, 4096, 1)) return 1;
   if (!finite_f(threshold) || !(threshold > 0.f && threshold < 1.f)) return fail("zoom_boxes: threshold must be in (0, 1)");
   if (min_pixels < 1) return fail("zoom_boxes: min_pixels must be >= 1");
   if (margin_q16 < 0 || margin_q16 > 4 * 65536) return fail("zoom_boxes: margin must be in [0, 4] (Q16)");
@@ -3026,8 +2963,8 @@ int eosvos_zoom_boxes(eosvos_engine* e, const float* probs, int n_frames, int he
   if (min_zoom_q16 < 65536 || min_zoom_q16 > max_zoom_q16) return fail("zoom_boxes: min_zoom must be in [1, max_zoom] (Q16)");
   // one record of 8 words per frame; zeroed here, on the stream, whatever the buffer held
   const size_t need = (size_t)n_frames * 8 * sizeof(int);
-  if (ccl_scratch(e, "zoom_boxes", need, n_frames)) return 1;
-  int* rec = (int*)e->ccl_buf;
+  if (scratch_grow(e, "zoom_boxes", need, n_frames)) return 1;
+  int* rec = (int*)e->scratch;
   HIPOK(hipMemsetAsync(rec, 0, need, e->s));
   launch_zoom_boxes(probs, n_frames, height, width, threshold, min_pixels, margin_q16, margin_px, min_zoom_q16, max_zoom_q16, rec,
                     boxes, e->s);
@@ -3038,8 +2975,7 @@ int eosvos_zoom_boxes(eosvos_engine* e, const float* probs, int n_frames, int he
 int eosvos_zoom_crop(eosvos_engine* e, const float* frames, const int32_t* boxes, int B, int C, int height, int width, float* out) {
   if (!e || !frames || !boxes || !out) return fail("zoom_crop: null argument");
   if (B < 1 || C < 1) return fail("zoom_crop: batch out of range");
-  if (height < 1 || width < 1) return fail("zoom_crop: bad frame geometry");
-  if (height > 4096 || width > 4096) return fail("zoom_crop: frames larger than 4096 pixels a side are not supported");
+  if (frames_check("zoom_crop", B, height, width, 0)) return 1;
   if ((int64_t)B * C > 0x7fffffff) return fail("zoom_crop: too many planes");
   launch_zoom_crop(frames, boxes, B, C, height, width, out, e->s);
   HIPOK(hipGetLastError());
@@ -3059,8 +2995,7 @@ int eosvos_zoom_blend(eosvos_engine* e, const int32_t* boxes, int B, int height,
                       float* probs_inout) {
   if (!e || !boxes || !pz || !probs_inout) return fail("zoom_blend: null argument");
   if (B < 1) return fail("zoom_blend: batch out of range");
-  if (height < 1 || width < 1) return fail("zoom_blend: bad frame geometry");
-  if (height > 4096 || width > 4096) return fail("zoom_blend: frames larger than 4096 pixels a side are not supported");
+  if (frames_check("zoom_blend", B, height, width, 0)) return 1;
   if (!finite_f(weight) || !(weight > 0.f && weight <= 1.f)) return fail("zoom_blend: weight must be in (0, 1]");
   if (feather < 0 || feather > 64) return fail("zoom_blend: feather must be in [0, 64]");
   launch_zoom_blend(boxes, B, height, width, weight, feather, pz, probs_inout, e->s);
@@ -3072,9 +3007,7 @@ int eosvos_zoom_blend(eosvos_engine* e, const int32_t* boxes, int B, int height,
 static int lucid_check(const char* who, int channels, int height, int width) {
   const std::string w(who);
   if (channels < 1 || channels > 64) return fail(w + ": channels must be in [1, 64]");
-  if (height < 1 || width < 1) return fail(w + ": bad frame geometry");
-  if (height > 4096 || width > 4096) return fail(w + ": frames larger than 4096 pixels a side are not supported");
-  return 0;
+  return frames_check(who, 1, height, width, 0);
 }
 int eosvos_lucid_plate(eosvos_engine* e, const float* frame, const float* mask, int channels, int height, int width, int dilate,
                        float* plate) {
@@ -3083,8 +3016,8 @@ int eosvos_lucid_plate(eosvos_engine* e, const float* frame, const float* mask, 
   if (dilate < 0 || dilate > 16) return fail("lucid_plate: dilate must be in [0, 16]");
   size_t floats, bytes;
   lucid_scratch(channels, height, width, &floats, &bytes);
-  if (ccl_scratch(e, "lucid_plate", (floats * sizeof(float) + bytes + 3) / 4 * 4, 1)) return 1;
-  float* vbuf = (float*)e->ccl_buf;
+  if (scratch_grow(e, "lucid_plate", (floats * sizeof(float) + bytes + 3) / 4 * 4, 1)) return 1;
+  float* vbuf = (float*)e->scratch;
   launch_lucid_plate(frame, mask, channels, height, width, dilate, plate, vbuf, (uint8_t*)(vbuf + floats), e->s);
   HIPOK(hipGetLastError());
   return 0;
@@ -3099,24 +3032,20 @@ int eosvos_lucid_compose(eosvos_engine* e, const float* frame, const float* mask
   for (int i = 0; i < n_samples * 12; ++i)
     if (!std::isfinite(matrices[i])) return fail("lucid_compose: the matrices must be finite");
   if (aug_tables(e)) return 1;
-  if (ccl_scratch(e, "lucid_compose", LUCID_MAX_SAMPLES * sizeof(int), n_samples)) return 1;
-  int* counts = (int*)e->ccl_buf;
+  if (scratch_grow(e, "lucid_compose", LUCID_MAX_SAMPLES * sizeof(int), n_samples)) return 1;
+  int* counts = (int*)e->scratch;
   HIPOK(hipMemsetAsync(counts, 0, (size_t)n_samples * sizeof(int), e->s));
   launch_lucid_compose(frame, mask, plate, channels, height, width, n_samples, flips, matrices, e->aug_ctab, images, labels, counts,
                        e->s);
   HIPOK(hipGetLastError());
-  if (counts_host) {                                                // the batch attempt's one host read
-    HIPOK(hipMemcpyAsync(counts_host, counts, (size_t)n_samples * sizeof(int), hipMemcpyDeviceToHost, e->s));
-    HIPOK(hipStreamSynchronize(e->s));
-  }
-  return 0;
+  return read_counts(e, ScratchAt<int>{0}, n_samples, counts_host);            // the batch attempt's one host read
 }
 
 // ---- online adaptation: the capped distance transform and the distance-gated targets (OnAVOS; evaluate.py:231-240) ------
 static int edt_check(const char* who, int n_frames, int height, int width) {
   const std::string w(who);
   if (n_frames < 1 || n_frames > 65535) return fail(w + ": between 1 and 65535 frames per call");
-  if (height < 1 || width < 1 || height > 4096 || width > 4096) return fail(w + ": frames of 1 .. 4096 pixels a side");
+  if (frames_check(who, n_frames, height, width)) return fail(w + ": frames of 1 .. 4096 pixels a side");   // this stage's wording
   return 0;
 }
 int eosvos_distance_sq(eosvos_engine* e, const float* probs, int n_frames, int height, int width, float threshold, int invert,
@@ -3125,9 +3054,9 @@ int eosvos_distance_sq(eosvos_engine* e, const float* probs, int n_frames, int h
   if (edt_check("distance_sq", n_frames, height, width)) return 1;
   if (limit < 1 || limit > 4095) return fail("distance_sq: limit must be in [1, 4095]");
   if (std::isnan(threshold)) return fail("distance_sq: the threshold is NaN");
-  const size_t np = (size_t)n_frames * height * width;
-  if (ccl_scratch(e, "distance_sq", (np * sizeof(uint16_t) + 3) / 4 * 4, n_frames)) return 1;
-  launch_edt_distance(probs, n_frames, height, width, threshold, invert != 0, limit, (uint16_t*)e->ccl_buf, out, e->s);
+  const DistanceSqLayout L((size_t)n_frames * height * width);
+  if (scratch_for(e, "distance_sq", L, n_frames)) return 1;
+  launch_edt_distance(probs, n_frames, height, width, threshold, invert != 0, limit, scratch_at(e, L.g), out, e->s);
   HIPOK(hipGetLastError());
   return 0;
 }
@@ -3140,25 +3069,12 @@ int eosvos_adapt_targets(eosvos_engine* e, const float* probs, const float* anch
   if (!(lo >= 0.f && lo < hi && hi <= 1.f)) return fail("adapt_targets: needs 0 <= lo < hi <= 1");
   if (std::isnan(anchor_thr)) return fail("adapt_targets: the anchor threshold is NaN");
   if (!ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
-  // [count_e | n_pos: 1 word per frame each] [g: 1 16-bit word per pixel] [eroded: 1 byte per pixel, erode > 0 only]
-  const size_t np = (size_t)n_frames * height * width, words = 2 * (size_t)n_frames;
-  const size_t need = (words * sizeof(int) + np * sizeof(uint16_t) + (erode > 0 ? np : 0) + 3) / 4 * 4;
-  if (ccl_scratch(e, "adapt_targets", need, n_frames)) return 1;
-  int* count_e = (int*)e->ccl_buf;
-  int* pos = count_e + n_frames;
-  uint16_t* g = (uint16_t*)(pos + n_frames);
-  uint8_t* eroded = (uint8_t*)(g + np);
-  HIPOK(hipMemsetAsync(count_e, 0, words * sizeof(int), e->s));
-  launch_edt_targets(probs, anchors, n_frames, height, width, lo, hi, anchor_thr, erode, neg_dist, ignore, g, eroded, count_e, pos,
-                     targets, e->s);
+  const AdaptTargetsLayout L(n_frames, (size_t)n_frames * height * width, erode > 0);
+  if (scratch_for(e, "adapt_targets", L, n_frames)) return 1;
+  launch_edt_targets(probs, anchors, n_frames, height, width, lo, hi, anchor_thr, erode, neg_dist, ignore, scratch_at(e, L.g),
+                     scratch_at(e, L.eroded), scratch_at(e, L.count_e), scratch_at(e, L.n_pos), targets, e->s);
   HIPOK(hipGetLastError());
-  if (n_pos) {                                                      // the round's one host read
-    std::vector<int> host(n_frames);
-    HIPOK(hipMemcpyAsync(host.data(), pos, sizeof(int) * n_frames, hipMemcpyDeviceToHost, e->s));
-    HIPOK(hipStreamSynchronize(e->s));
-    for (int f = 0; f < n_frames; ++f) n_pos[f] = host[f];
-  }
-  return 0;
+  return read_counts(e, L.n_pos, n_frames, n_pos);             // the round's one host read (32-bit counters on the device)
 }
 
 int eosvos_meta_task_begin(eosvos_engine* e) {
@@ -3617,7 +3533,7 @@ int eosvos_debug_tensor(eosvos_engine* e, const char* name, float** ptr, int64_t
   // folded frozen-norm scale / shift (a = gamma / sqrt(var + eps), b = beta - mean * a), all norm layers concatenated
   if (n == "norm_a" || n == "norm_b") { *ptr = n == "norm_a" ? e->na : e->nb; dims4[0] = dims4[1] = dims4[2] = 1; dims4[3] = e->t.nnorm; return 0; }
   // the grow-only scratch of the label-map and adaptation stages, as 32-bit words (null and 0 words before its first use)
-  if (n == "ccl_scratch") { *ptr = (float*)e->ccl_buf; dims4[0] = dims4[1] = dims4[2] = 1; dims4[3] = (int64_t)(e->ccl_cap / 4); return 0; }
+  if (n == "ccl_scratch") { *ptr = (float*)e->scratch; dims4[0] = dims4[1] = dims4[2] = 1; dims4[3] = (int64_t)(e->scratch_cap / 4); return 0; }
   if (n == "c1") return set(e->c1, e->h2, e->w2, 64);
   if (n == "p1") return set(e->p1, e->h4, e->w4, 64);
   if (n == "g_c1") return set(e->g_c1, e->h2, e->w2, 64);

@@ -20,6 +20,20 @@ def _optr(t):
     return _ptr(t) if t is not None else None
 
 
+def _chunks(n, step):
+    """(f, g) of every run of at most `step` frames of n, in order."""
+    return ((f, min(f + step, n)) for f in range(0, n, step))
+
+
+def _keep_flags(keep, n):
+    """One byte per frame, 1 for the frame indices of `keep` (indices outside [0, n) are ignored)."""
+    flags = bytearray(n)
+    for f in keep:
+        if 0 <= int(f) < n:
+            flags[int(f)] = 1
+    return flags
+
+
 def _relu_bits(t):
     """ReLU mask bytes of t (..., C), the form the engine's data gradients read: bit j of byte q = (channel 4q + j > 0)."""
     if t is None:
@@ -484,9 +498,7 @@ class Engine:
         self._check_stream()
         n, h, w = maps.shape
         out = torch.empty(n, h, w, dtype=torch.int32, device=self.device)
-        step = adapt.frames_per_call(h, w)
-        for f in range(0, n, step):
-            g = min(f + step, n)
+        for f, g in _chunks(n, adapt.frames_per_call(h, w)):
             _ffi.check(self.lib.eosvos_distance_sq(self.h, _ptr(maps[f:g]), g - f, h, w, threshold, int(bool(invert)), limit,
                                                    _ptr(out[f:g])))
         return out.view(probs.shape)
@@ -511,9 +523,7 @@ class Engine:
         n, h, w = x.shape
         out = torch.empty_like(x)
         n_pos = []
-        step = adapt.frames_per_call(h, w, p['erode'])
-        for f in range(0, n, step):
-            g = min(f + step, n)
+        for f, g in _chunks(n, adapt.frames_per_call(h, w, p['erode'])):
             host = (ctypes.c_int64 * (g - f))() if counts else None
             _ffi.check(self.lib.eosvos_adapt_targets(self.h, _ptr(x[f:g]), _ptr(a[f:g]), g - f, h, w, lo, hi, hi, p['erode'],
                                                      p['neg_dist'], ignore, _ptr(out[f:g]), host))
@@ -769,9 +779,7 @@ class Engine:
         n, n_obj, h, w = probs.shape
         out = torch.empty(n, h, w, dtype=torch.uint8, device=self.device)
         q = torch.empty(n, n_obj + 1, h, w, device=self.device) if return_q else None
-        step = crf.frames_per_call(n_obj, h, w)
-        for f in range(0, n, step):
-            g = min(f + step, n)
+        for f, g in _chunks(n, crf.frames_per_call(n_obj, h, w)):
             _ffi.check(self.lib.eosvos_crf_labels(self.h, _ptr(images[f:g]), _ptr(probs[f:g]), g - f, n_obj, h, w, p['iterations'],
                                                   p['radius'], p['dilation'], p['w_appearance'], p['w_smooth'], p['theta_alpha'],
                                                   p['theta_beta'], p['theta_gamma'], _ptr(out[f:g]), _optr(q[f:g] if return_q else None)))
@@ -796,9 +804,7 @@ class Engine:
         labels = labels.contiguous()
         n, h, w = labels.shape
         ids = torch.empty(n, h, w, dtype=torch.int32, device=self.device)
-        step = components.frames_per_call(h, w)
-        for f in range(0, n, step):
-            g = min(f + step, n)
+        for f, g in _chunks(n, components.frames_per_call(h, w)):
             _ffi.check(self.lib.eosvos_label_components(self.h, _ptr(labels[f:g]), g - f, h, w, connectivity, _ptr(ids[f:g])))
         return ids
 
@@ -816,17 +822,12 @@ class Engine:
         self._check_stream()
         labels = labels.contiguous()
         n, h, w = labels.shape
-        flags = bytearray(n)
-        for f in keep:
-            if 0 <= int(f) < n:
-                flags[int(f)] = 1
+        flags = _keep_flags(keep, n)
         out = torch.empty_like(labels)
         removed = np.zeros(n, dtype=np.int64)
         rem_p = ctypes.POINTER(ctypes.c_int64)
-        step = components.frames_per_call(h, w)
         prev = prev.contiguous() if prev is not None else None
-        for f in range(0, n, step):
-            g = min(f + step, n)
+        for f, g in _chunks(n, components.frames_per_call(h, w)):
             _ffi.check(self.lib.eosvos_filter_components(
                 self.h, _ptr(labels[f:g]), g - f, h, w, p['connectivity'], p['min_area'], components.rel_q16(p['min_rel_area']),
                 int(p['largest_only']), p['gate'], _optr(prev), bytes(flags[f:g]), _ptr(out[f:g]),
@@ -847,17 +848,12 @@ class Engine:
         self._check_stream()
         labels = labels.contiguous()
         n, h, w = labels.shape
-        flags = bytearray(n)
-        for f in keep:
-            if 0 <= int(f) < n:
-                flags[int(f)] = 1
+        flags = _keep_flags(keep, n)
         out = torch.empty_like(labels)
         filled = np.zeros(n, dtype=np.int64)
         fill_p = ctypes.POINTER(ctypes.c_int64)
-        step = holes.frames_per_call(h, w)
         prev = prev.contiguous() if prev is not None else None
-        for f in range(0, n, step):
-            g = min(f + step, n)
+        for f, g in _chunks(n, holes.frames_per_call(h, w)):
             _ffi.check(self.lib.eosvos_fill_holes(
                 self.h, _ptr(labels[f:g]), g - f, h, w, p['connectivity'], p['max_area'], holes.rel_q16(p['max_rel_area']),
                 holes.overlap_q16(p['prev_overlap']), _optr(prev), bytes(flags[f:g]), _ptr(out[f:g]),
@@ -885,9 +881,7 @@ class Engine:
         rgb = rgb.contiguous()
         n, _, h, w = rgb.shape
         ids = torch.empty(n, h, w, dtype=torch.int32, device=self.device)
-        chunk = snap.frames_per_call(0, h, w, p['step'])
-        for f in range(0, n, chunk):
-            g = min(f + chunk, n)
+        for f, g in _chunks(n, snap.frames_per_call(0, h, w, p['step'])):
             _ffi.check(self.lib.eosvos_superpixels(self.h, _ptr(rgb[f:g]), g - f, h, w, p['step'], p['iterations'], p['compactness'],
                                                    _ptr(ids[f:g])))
         return ids
@@ -909,15 +903,10 @@ class Engine:
         changed = np.zeros(n, dtype=np.int64)
         if p['step'] == 0:
             return (labels.clone(), changed) if return_changed else labels.clone()
-        flags = bytearray(n)
-        for f in keep:
-            if 0 <= int(f) < n:
-                flags[int(f)] = 1
+        flags = _keep_flags(keep, n)
         out = torch.empty_like(labels)
         changed_p = ctypes.POINTER(ctypes.c_int64)
-        chunk = snap.frames_per_call(n_obj, h, w, p['step'])
-        for f in range(0, n, chunk):
-            g = min(f + chunk, n)
+        for f, g in _chunks(n, snap.frames_per_call(n_obj, h, w, p['step'])):
             _ffi.check(self.lib.eosvos_snap_labels(
                 self.h, _ptr(rgb[f:g]), _ptr(labels[f:g]), g - f, h, w, n_obj, p['step'], p['iterations'], p['compactness'],
                 snap.share_q16(p['min_share']), bytes(flags[f:g]), _ptr(out[f:g]),
@@ -942,10 +931,8 @@ class Engine:
         rgb = rgb.contiguous()
         n, _, h, w = rgb.shape
         mv = torch.empty((n,) + motion.grid(h, w, p['block']) + (2,), dtype=torch.int8, device=self.device)
-        chunk = motion.frames_per_call(h, w)
         prev = prev_rgb.contiguous() if prev_rgb is not None else None
-        for f in range(0, n, chunk):
-            g = min(f + chunk, n)
+        for f, g in _chunks(n, motion.frames_per_call(h, w)):
             _ffi.check(self.lib.eosvos_block_motion(self.h, _ptr(rgb[f:g]), _optr(prev), g - f, h, w, p['block'], p['radius'], p['bias'],
                                                     _ptr(mv[f:g])))
             prev = rgb[g - 1]

@@ -805,8 +805,8 @@ int eosvos_bench_conv(eosvos_engine* e, int conv_idx, int kind, int batch, int r
 int eosvos_mfma_probe(eosvos_engine* e, int iters, float* ms_host, double* flops_host);
 /* Device pointer + {B,H,W,C} of a named internal NHWC activation / gradient buffer of the
  * last forward/backward ("c1","p1","blk<i>.out","cat","proj","dcat","d1","d2","lowlog",
- * "logits", "g_*" ...), for the per-stage parity tests; "ccl_scratch": the grow-only scratch of the label-map and adaptation
- * stages as dims4[3] 32-bit words (null before its first use). */
+ * "logits", "g_*" ...), for the per-stage parity tests; "ccl_scratch": the one grow-only scratch arena that every
+ * evaluation-stage entry point shares, as dims4[3] 32-bit words (null before its first use). */
 /* Measurement aid: HIP events around every launch of the matrix-core kernels, on the stream each one runs on.
  * profile_read returns, per kernel symbol (names: max_kernels x 64 chars), launches, summed duration (ms) and summed
  * executed fp32-equivalent FLOPs since profile_launches(e, 1).  bench.py's roofline (dominant kernel by time). */
