@@ -3542,6 +3542,11 @@ int eosvos_debug_tensor(eosvos_engine* e, const char* name, float** ptr, int64_t
   if (n == "g_cat") return set(e->g_cat, e->h16, e->w16, 1280);
   if (n == "proj") return set(e->proj, e->h16, e->w16, 256);
   if (n == "g_proj") return set(e->g_proj, e->h16, e->w16, 256);
+  // image-pooling branch of the ASPP: one vector per image
+  if (n == "vec") return set(e->vec, 1, 1, 2048);
+  if (n == "gvec") return set(e->gvec, 1, 1, 2048);
+  if (n == "poolout") return set(e->poolout, 1, 1, 256);
+  if (n == "gp") return set(e->gp, 1, 1, 256);
   if (n == "dcat") return set(e->dcat, e->h4, e->w4, 304);
   if (n == "g_dcat") return set(e->g_dcat, e->h4, e->w4, 304);
   if (n == "d1") return set(e->d1, e->h4, e->w4, 256);

@@ -108,8 +108,13 @@ int eosvos_set_wg_budget(eosvos_engine* e, int workgroups);
  * a sequence (evaluate.py:132) -- are better off with ONE queue each (on = 0): the other engines fill the chip, and the
  * fork / join events between the two streams of every engine only add bubbles.  Measured on one MI355X at 480x854
  * (tools/inflight_sweep.py, profiles/r03_inflight_sweep.txt): 4 engines at batch 1, 192 -> 264 fine-tune iterations/s;
- * 3 engines at batch 3, 95.6 -> 105.5.  Call it while the engine is idle.  Results do not change (same kernels, same
- * order per engine).  Returns 0 / 1 = the state now in effect, -1 on error. */
+ * 3 engines at batch 3, 95.6 -> 105.5.  Call it while the engine is idle.  The loss, every data gradient and
+ * most weight gradients do not change (same kernels, same order per engine).  Two groups of weight gradients keep their
+ * accuracy but take another fp32 summation order, i.e. are not bit-identical across the switch: at batch > 1 layer1's ten
+ * (an engine without the stream groups them into one stage launch, which plans their K splits together; with the stream
+ * they overlap the data-gradient chain one by one), and in the f16x3 mode those of the pre-split operand path (stride-16
+ * maps of >= 4000 pixels), which only an engine with the stream takes.  Returns 0 / 1 = the state now in effect, -1 on
+ * error. */
 int eosvos_set_side_stream(eosvos_engine* e, int on);
 
 /* Number of convolutions of DeepLabV3+ on `arch` (63 for ResNet-50); -1 on bad arch.
@@ -805,7 +810,10 @@ int eosvos_bench_conv(eosvos_engine* e, int conv_idx, int kind, int batch, int r
 int eosvos_mfma_probe(eosvos_engine* e, int iters, float* ms_host, double* flops_host);
 /* Device pointer + {B,H,W,C} of a named internal NHWC activation / gradient buffer of the
  * last forward/backward ("c1","p1","blk<i>.out","cat","proj","dcat","d1","d2","lowlog",
- * "logits", "g_*" ...), for the per-stage parity tests; "ccl_scratch": the one grow-only scratch arena that every
+ * "logits", "g_*" ...), for the per-stage parity tests; the ASPP image-pooling branch, read-only, as {B,1,1,C}: "vec"
+ * (the mean of layer4's output over the pixels, C = 2048), "poolout" (the branch's conv + norm + ReLU of it, C = 256), "gp"
+ * (the gradient of the loss w.r.t. the pre-ReLU "poolout": the pixel sum of "g_cat"[:, 1024:1280]) and "gvec" (w.r.t. "vec");
+ * "ccl_scratch": the one grow-only scratch arena that every
  * evaluation-stage entry point shares, as dims4[3] 32-bit words (null before its first use). */
 /* Measurement aid: HIP events around every launch of the matrix-core kernels, on the stream each one runs on.
  * profile_read returns, per kernel symbol (names: max_kernels x 64 chars), launches, summed duration (ms) and summed
