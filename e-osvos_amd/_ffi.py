@@ -117,6 +117,7 @@ _SIGNATURES = {
                                             ctypes.POINTER(ctypes.c_float)]),
     'eosvos_keep_grads': (ctypes.c_int, [_E, ctypes.c_int]),
     'eosvos_get_grads': (ctypes.c_int, [_E, c_float_p]),
+    'eosvos_debug_gsum': (ctypes.c_int, [_E, c_float_p]),
     'eosvos_infer': (ctypes.c_int, [_E, c_float_p, ctypes.c_int, c_float_p]),
     'eosvos_infer_view': (ctypes.c_int, [_E, c_float_p, ctypes.c_int, ctypes.c_int]),
     'eosvos_tta_accumulate': (ctypes.c_int, [_E, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,

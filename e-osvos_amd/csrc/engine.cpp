@@ -2512,6 +2512,15 @@ int eosvos_get_grads(eosvos_engine* e, float* out) {
   HIPOK(hipGetLastError());
   return 0;
 }
+int eosvos_debug_gsum(eosvos_engine* e, float* out) {
+  ModeScope mode_scope(e);
+  if (!e || !out) return fail("null argument");
+  if (!e->gsum) return fail("eosvos_debug_gsum without eosvos_meta_task_begin");
+  if (e->train_from > 0) HIPOK(hipMemsetAsync(out, 0, (size_t)e->tf_poff * 4, e->s));     // frozen tensors: nothing is summed
+  export_params(e, e->gsum, out, 1.f, 0, true);
+  HIPOK(hipGetLastError());
+  return 0;
+}
 int eosvos_keep_grads(eosvos_engine* e, int on) {
   if (!e) return fail("null engine");
   e->keep_grads = on != 0;

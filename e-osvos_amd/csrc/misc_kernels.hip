@@ -897,12 +897,16 @@ __global__ void radam_kernel(float* __restrict__ p, const float* __restrict__ g,
   GRID_STRIDE(i, n) {
     float gr = g[i] * grad_scale;
     if (grad_clip > 0.f) gr = fminf(fmaxf(gr, -grad_clip), grad_clip);
-    const float vv = v[i] * beta2 + (1.f - beta2) * gr * gr;
-    const float mm = m[i] * beta1 + (1.f - beta1) * gr;
+    float vv, mm, pv = p[i];
+    {   // every product rounded on its own, as the separate tensor ops of radam.py:58-59,83-84 round them: only the final
+        // multiply-add below may be contracted
+#pragma clang fp contract(off)
+      vv = v[i] * beta2 + (1.f - beta2) * gr * gr;
+      mm = m[i] * beta1 + (1.f - beta1) * gr;
+      if (wd != 0.f) pv += (-wd * lr) * pv;
+    }
     v[i] = vv;
     m[i] = mm;
-    float pv = p[i];
-    if (wd != 0.f) pv += (-wd * lr) * pv;
     if (use_denom) pv += (-step_size * lr) * (mm / (sqrtf(vv) + eps));
     else pv += (-step_size * lr) * mm;
     p[i] = pv;
@@ -918,9 +922,12 @@ void launch_radam(float* p, const float* g, float* m, float* v, int64_t n, float
 __device__ __forceinline__ float outer_radam(float pv, float graw, float& mm, float& vv, float lr, float wd, const OuterHyper& h) {
   float gr = graw * h.grad_scale;
   if (h.grad_clip > 0.f) gr = fminf(fmaxf(gr, -h.grad_clip), h.grad_clip);
-  vv = vv * h.beta2 + (1.f - h.beta2) * gr * gr;
-  mm = mm * h.beta1 + (1.f - h.beta1) * gr;
-  if (wd != 0.f) pv += (-wd * lr) * pv;
+  {   // (no contraction here either: see radam_kernel)
+#pragma clang fp contract(off)
+    vv = vv * h.beta2 + (1.f - h.beta2) * gr * gr;
+    mm = mm * h.beta1 + (1.f - h.beta1) * gr;
+    if (wd != 0.f) pv += (-wd * lr) * pv;
+  }
   if (h.use_denom) pv += (-h.step_size * lr) * (mm / (sqrtf(vv) + h.eps));
   else pv += (-h.step_size * lr) * mm;
   return pv;

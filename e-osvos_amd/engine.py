@@ -586,6 +586,15 @@ class Engine:
             self.synchronize()
         return out
 
+    def debug_gsum(self):
+        """`eosvos_debug_gsum`: copy of the gradient sum of the accumulating steps since `meta_task_begin`, flat OIHW as
+        `get_grads` (per-link tests)."""
+        out = torch.empty(self.n_param, device=self.device)
+        _ffi.check(self.lib.eosvos_debug_gsum(self.h, _ptr(out)))
+        if torch.cuda.current_stream(self.device) != self.stream:
+            self.synchronize()
+        return out
+
     def infer(self, images):
         b = self._check_images(images)
         self._guard(images)

@@ -251,6 +251,10 @@ int eosvos_finetune_step(eosvos_engine* e, const float* images, const float* mas
  * engine only materialises it after eosvos_keep_grads(e, 1) (one extra 161 MB write/step). */
 int eosvos_keep_grads(eosvos_engine* e, int on);
 int eosvos_get_grads(eosvos_engine* e, float* flat_grads_out);
+/* Read-only copy of the gradient sum of the accumulating steps since eosvos_meta_task_begin (the `gsum` eosvos_meta_grad
+ * multiplies with the meta frame's gradient), flat OIHW as eosvos_get_grads, zeros for the frozen tensors (for the per-link
+ * tests).  Fails without eosvos_meta_task_begin; changes nothing in the engine. */
+int eosvos_debug_gsum(eosvos_engine* e, float* flat_gsum_out);
 
 /* ---- inference (helper_func.py:131-142, evaluate.py:322-326) ----------------------- */
 /* probs = sigmoid(model(images)[-1]); probs_out B x 1 x H x W.  An inference forward keeps no ReLU masks: a loss +

@@ -14,7 +14,8 @@ CPU and makes no engine call.  tests/test_backward_links_host.py proves every fu
 network; tests/test_gpu_backward_links.py feeds them the engine's buffers.
 
 Scope: DeepLabV3+ on ResNet-50 with frozen BatchNorm.  Not covered: GroupNorm mode (it overwrites the stored raw outputs
-with dz and exposes neither), resnet101, plain DeepLabV3, the accumulating (`gsum`) meta path and the trainable boundary.
+with dz and exposes neither), resnet101, plain DeepLabV3.  The accumulating (`gsum`) meta path and the trainable boundary:
+tests/meta_links_ref.py.
 """
 from collections import namedtuple
 

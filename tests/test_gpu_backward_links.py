@@ -16,8 +16,8 @@ bounds apply unchanged.  ReLU masks are exact.  The update is checked per elemen
 
 One MARGIN line per link group (profiles/backward_links_margins.txt holds a run's lines).
 
-Not covered: GroupNorm mode (it overwrites the stored raw outputs with dz and exposes neither), resnet101, plain DeepLabV3,
-the accumulating (`gsum`) meta path and the trainable boundary.
+Not covered: GroupNorm mode (it overwrites the stored raw outputs with dz and exposes neither), resnet101, plain DeepLabV3.
+The accumulating (`gsum`) meta path and the trainable boundary: tests/test_gpu_meta_links.py.
 """
 import numpy as np
 import pytest
