@@ -29,13 +29,13 @@
 #include <cmath>
 #include <functional>
 #include <map>
-#include <set>
 #include <string>
 #include <vector>
 
 #include "../../include/eosvos.h"
 #include "kernels.h"
 #include "scratch_layout.h"
+#include "tensor_views.h"
 
 using namespace eosvos;
 
@@ -197,7 +197,6 @@ struct eosvos_engine {
   float *Wp = nullptr, *Winit = nullptr, *Wsnap = nullptr, *lr = nullptr, *na = nullptr, *nb = nullptr;
   float *gsum = nullptr, *gout = nullptr, *stage = nullptr;
   bool keep_grads = false;
-  // learned-lr storage level (meta_optim.py:27-67): the update consumes `lr` (per neuron) or `lr_elem`
   int loss_kind = EOSVOS_LOSS_BCE;      // loss of the fused entry points (eosvos_set_loss)
   bool loss_ignore_on = false;          // eosvos_set_loss_ignore: the fused entry points evaluate their loss with a void label
   float loss_ignore = 0.f;
@@ -210,32 +209,38 @@ struct eosvos_engine {
   // read-back or leaves nothing behind, so the stream orders one call's use before the next one's
   void* scratch = nullptr;
   size_t scratch_cap = 0;
+  // learned-lr storage level (meta_optim.py:27-67): the update consumes `lr` (per neuron) or `lr_elem`
   int lr_level = EOSVOS_LR_NEURON, lr_log = 0;
   float *lr_elem = nullptr, *glr_tmp = nullptr, *ptmp = nullptr;
   int *row_tensor = nullptr, *tensor_row0 = nullptr, *all_row0 = nullptr;
   int ntensors = 0;
-  // activations
-  float *xpad, *c1, *p1;
+  // activations (phase 0) and their gradients (phase 1, g_*): records of `ts` (tensor_views.h), each made once by
+  // eosvos_create_ex with its geometry; its mask bytes, absmax slot and fp16-pair sibling hang off the record
+  TensorSet ts;
+  float* xpad;
+  Tensor *c1, *p1, *g_c1, *g_p1, *cat, *g_cat, *proj, *g_proj, *dcat, *g_dcat, *d1, *g_d1, *d2, *g_d2;
   uint8_t* p1idx;
-  struct BlkBuf { float *t1, *t2, *out, *dsb, *g_t1, *g_t2, *g_out; int Hi, Wi, Ho, Wo, Hm, Wm; const float* xin; float* g_xin; int Cin; };
+  struct BlkBuf { Tensor *xin, *t1, *t2, *out, *dsb, *g_xin, *g_t1, *g_t2, *g_out; };   // dsb: null without a projection shortcut
   std::vector<BlkBuf> bb;
-  float *g_c1, *g_p1;
-  float *cat, *g_cat, *vec, *gvec, *poolout, *gp, *colscratch, *proj, *g_proj;
-  float *dcat, *g_dcat, *d1, *g_d1, *d2, *g_d2, *lowlog, *g_low, *logits, *dlogits, *loss_dev, *bce_partial;
+  float *vec, *gvec, *poolout, *gp, *colscratch, *lowlog, *g_low, *logits, *dlogits, *loss_dev, *bce_partial;
   float *ws_conv, *ws_wg, *ws_conv2 = nullptr;
-  // Winograd F(2x2,3x3) path of the decoder's 3x3 convs: per conv the transformed input planes V (made by the
-  // forward pass, reused by the weight gradient) and transformed weights U; one shared buffer for the
-  // output-domain planes (forward: M, backward: dM)
-  std::map<int, float*> wino_V, wino_U, wino_Us, wino_dM;   // Us = a[cout] * U (data gradient), made with U  // dM = A dY A^T: made once per backward, read by wgrad and dgrad
-  std::map<int, int> wino_v_batch;                // batch size V was computed for (0 = stale)
-  std::map<int, int> wino_dm_batch;               // batch size dM is valid for (0 = stale)
-  std::map<int, int> wino_us_valid;               // U / Us match the current weights (set when they are made, cleared by every weight change)
+  // Winograd F(2x2,3x3) / F(4x4,3x3) path: per conv the transformed input planes V (made by the forward pass, reused by the
+  // weight gradient) and transformed weights U; one shared buffer for the output-domain planes (forward: M, backward: dV)
+  struct WinoRec {
+    float *V = nullptr, *U = nullptr;   // V null: no buffers were reserved for the conv
+    float* Us = nullptr;                // a[cout] * U (data gradient), made with U
+    float* dM = nullptr;                // A dY A^T: made once per backward, read by wgrad and dgrad
+    int v_batch = 0;                    // batch size V was computed for (0 = stale)
+    int dm_batch = 0;                   // batch size dM is valid for (0 = stale)
+    bool us_valid = false;              // U / Us match the current weights (set when they are made, cleared by every weight change)
+  };
+  std::vector<WinoRec> wino;            // per conv
   hipEvent_t ev_wino_w = nullptr;                 // the side stream has made the transformed weights of this forward
   bool wino_w_wait = false;
   float *wino_m = nullptr, *wino_dv = nullptr;    // forward M planes; data-gradient dV planes (transient)
   int64_t wino_m_n = 0;
   int norm_mode = 0;                  // EOSVOS_NORM_BN_FROZEN / EOSVOS_NORM_GN16
-  std::vector<float*> zbuf;           // GN: raw conv outputs (then, in backward, their gradients), dense [B*Ho*Wo][cout]
+  std::vector<Tensor*> zbuf;          // GN: raw conv outputs (then, in backward, their gradients: phase 1), dense [B*Ho*Wo][cout]
   std::vector<float*> gn_stats;       // GN: per conv {mean, rstd} per (image, group)
   float *gn_sums = nullptr, *gn_partial = nullptr;
   struct TapTab { int* prefix; int* mask; long total; int* order; };
@@ -284,26 +289,8 @@ struct eosvos_engine {
   int64_t tf_poff = 0, tf_lroff = 0;  // arena / per-neuron lr offset of the first trainable conv
   int tf_tensor = 0;                  // trainable tensors before it
   long* tf_toff = nullptr;            // export table of the trainable tensors, offsets relative to tf_poff (export_params)
-  std::set<const float*> m8_frozen;   // activations whose ReLU mask only a frozen conv's data gradient would read
-  // pre-split operand path (presplit_kernels.hip, round 6): "pair8" siblings of fp32 tensors -- the two fp16 pieces of the
-  // f16x3 product laid out for LDS-DMA.  One sibling per TENSOR (keyed like the absmax slots: first element of the
-  // allocation; a view's sibling is the same offset into it).  Once a consumer has asked for a tensor's sibling (`want`), the
-  // conv epilogues / fix-up passes that write the tensor also write the sibling, under the scale the consumer side left for
-  // them at the end of the previous iteration (sc[1 + parity]); the consumer side validates that scale against this iteration's
-  // absmax and re-splits the view from the fp32 tensor if it does not fit (pair_split_multi_kernel) -- always correct, and free
-  // of split passes whenever the tensor's magnitude moves by less than the margin between two iterations.
-  struct PairBuf {
-    unsigned char* p = nullptr;
-    float* sc = nullptr;             // [0] the scale the sibling holds now (consumers), [1], [2]: for the producers of even / odd iterations
-    int64_t floats = 0;
-    bool want = false;
-    bool fresh = true;               // no producer scale yet (new sibling / pair_reset): this iteration's consumers run the
-                                     // register-staged kernels, which leave the scale for the next iteration's producers
-    bool covered = false;            // every writer of the tensor in iteration cover_iter wrote the sibling too
-    long cover_iter = -1;
-  };
-  std::map<const float*, PairBuf> pairs[2];
-  long pair_iter = 0;                             // training forwards so far (parity selects the producers' scale word)
+  // pre-split operand path (presplit_kernels.hip, round 6): the fp16-pair siblings of the tensors (Tensor::pair)
+  long pair_iter = 0;                            // training forwards so far (parity selects the producers' scale word)
   unsigned char* pair_zero = nullptr;             // 4 KB of zeros: K rows past the last contributing pixel
   float* pair_sc_pool = nullptr;
   int pair_sc_used = 0;
@@ -326,25 +313,10 @@ struct eosvos_engine {
   long* amax_w_off = nullptr;        // device tables of launch_absmax_segments over the parameter arena
   int* amax_w_n = nullptr;
   std::vector<char> ks_amax_valid;   // KS slots match the current norm scales
-  // tensor slots: absmax accumulated by the kernels that WRITE a tensor (conv epilogue, fix-up, Winograd output
-  // transforms); phase 0 = activations of this forward, phase 1 = gradients of this backward.  `valid`: the last
-  // writer that covered the whole tensor, and every writer since, had the fused absmax -- only then a consumer trusts it
-  struct TRec { int idx; bool valid; };
-  std::map<const float*, TRec> treg[2];
-  static constexpr int TSLOTS = 384;   // per phase
-
-  // ReLU masks as bytes (ConvArgs::mask8): one buffer per activation tensor a data gradient masks with, written by the
-  // forward pass that applies the ReLU (conv epilogue, fix-up, Winograd output transform, GroupNorm apply pass, pooling
-  // broadcast).  They are the only form of the mask the backward pass reads.
-  std::map<const float*, uint8_t*> mask8;
+  // tensor slots (Tensor::slot): absmax accumulated by the kernels that WRITE a tensor (conv epilogue, fix-up, Winograd
+  // output transforms); phase 0 = activations of this forward, phase 1 = gradients of this backward
   bool fwd_masks = true;             // false during eosvos_infer: no backward pass will read the masks of this forward
   bool masks_valid = false;          // the mask bytes belong to the activations of the last forward
-  uint8_t* m8(const float* key) const {
-    auto it = mask8.find(key);
-    return it == mask8.end() ? nullptr : it->second;
-  }
-  // for the forward's writers: no bytes for a mask that no backward pass of this engine reads (frozen region)
-  uint8_t* m8w(const float* key) const { return fwd_masks && !m8_frozen.count(key) ? m8(key) : nullptr; }
   int64_t max_alloc_floats = 0;      // largest single allocation (every conv operand is one of them)
   // EOSVOS_DEBUG_GUARD=1: every buffer sits between two 256 KB guard bands filled with a pattern;
   // eosvos_debug_check_guards reports bands a kernel wrote into (out-of-bounds writes)
@@ -384,7 +356,7 @@ namespace {
 
 // the weights changed: the scaled Winograd weights a[cout] * U of the last forward are stale
 void wino_weights_changed(eosvos_engine* e) {
-  for (auto& kv : e->wino_us_valid) kv.second = 0;
+  for (auto& w : e->wino) w.us_valid = false;
   e->w_amax_valid = false;
 }
 
@@ -401,13 +373,13 @@ enum { AM_X = 0, AM_V = 1, AM_G = 2, AM_DM = 3, AM_W = 4, AM_U = 5, AM_US = 6, A
 // Columns: [X | V | forward tensors][G | DM | backward tensors][W | U | US | KS] -- each phase's slots are one column
 // range, zeroed by one 2-D memset when the phase begins.
 inline size_t amax_col(const eosvos_engine* e, int kind, int ci) {
-  const size_t nc = e->t.convs.size(), T = eosvos_engine::TSLOTS;
+  const size_t nc = e->t.convs.size(), T = TSLOTS;
   if (kind <= AM_V) return (size_t)kind * nc + ci;
   if (kind <= AM_DM) return 2 * nc + T + (size_t)(kind - AM_G) * nc + ci;
   return 4 * nc + 2 * T + (size_t)(kind - AM_W) * nc + ci;
 }
 inline size_t amax_tcol(const eosvos_engine* e, int phase, int idx) {
-  return (phase == 0 ? 2 : 4) * e->t.convs.size() + (size_t)phase * eosvos_engine::TSLOTS + idx;
+  return (phase == 0 ? 2 : 4) * e->t.convs.size() + (size_t)phase * TSLOTS + idx;
 }
 // zero the slots [first, first + count) (all their words)
 inline void amax_zero(unsigned* first, size_t count, hipStream_t st) { launch_amax_zero(first, (int)count, st); }
@@ -424,7 +396,7 @@ struct ModeScope {
 };
 int amax_init(eosvos_engine* e) {
   if (e->amax) return 0;
-  const size_t n = (size_t)AM_KINDS * e->t.convs.size() + 2 * eosvos_engine::TSLOTS;
+  const size_t n = (size_t)AM_KINDS * e->t.convs.size() + 2 * TSLOTS;
   if (n > AMAX_ROW) return 1;
   e->amax = (unsigned*)e->falloc((int64_t)AMAX_SUB * AMAX_ROW);
   if (!e->amax) return 1;
@@ -436,45 +408,38 @@ int amax_init(eosvos_engine* e) {
 inline unsigned* amax_slot(eosvos_engine* e, int kind, int ci) { return e->amax + amax_col(e, kind, ci); }
 // host-side record of slot (kind, ci)
 inline eosvos_engine::AmaxRec& amax_rec_of(eosvos_engine* e, int kind, int ci) { return e->amax_rec[(size_t)kind * e->t.convs.size() + ci]; }
-// slot of the tensor that starts at `key` (phase 0: activation, 1: gradient); nullptr when the table is full
-unsigned* tslot(eosvos_engine* e, int phase, const float* key) {
-  auto& reg = e->treg[phase];
-  auto it = reg.find(key);
-  if (it == reg.end()) {
-    if ((int)reg.size() >= eosvos_engine::TSLOTS) return nullptr;
-    it = reg.emplace(key, eosvos_engine::TRec{(int)reg.size(), false}).first;
-  }
-  return e->amax + amax_tcol(e, phase, it->second.idx);
+// the tensor's slot; nullptr when the phase's table is full
+unsigned* tslot(eosvos_engine* e, Tensor& t) {
+  const int idx = e->ts.slot_of(t);
+  return idx < 0 ? nullptr : e->amax + amax_tcol(e, t.phase, idx);
 }
-void pair_uncover(eosvos_engine* e, int phase, const float* key);
-void pair_attach(eosvos_engine* e, int phase, const float* key, const float* y, bool full, ConvArgs& a);
-void pair_covered(eosvos_engine* e, int phase, const float* key, const ConvArgs& a);
-void pair_reset(eosvos_engine* e);
-// a kernel with the fused absmax is about to write the tensor at `key` (full = every element): returns the slot to pass
-unsigned* twrite_fused(eosvos_engine* e, int phase, const float* key, bool full) {
-  pair_uncover(e, phase, key);
-  if (!h3_mode() || amax_init(e)) return nullptr;
-  unsigned* sl = tslot(e, phase, key);
-  if (sl && full) e->treg[phase][key].valid = true;
-  return sl;
+// a kernel is about to write (part of) the tensor: until a writer that covers it whole reports the fused sibling write
+// (pair_covered), the sibling is stale
+inline void pair_uncover(Tensor& t) { t.pair.covered = false; }
+// A kernel with the fused absmax is about to write the view.  What it must be handed: the tensor's absmax slot (f16x3 mode)
+// and, for a writer that applies the ReLU, where the mask bytes go (none for a mask that no backward pass of this engine
+// reads: inference, frozen region).
+struct Written { unsigned* slot; uint8_t* mask; int ldmask; };
+Written twrite_fused(eosvos_engine* e, const View& v) {
+  pair_uncover(*v.t);
+  Written w{nullptr, e->fwd_masks ? v.mask_to_write() : nullptr, v.ldmask()};
+  if (!h3_mode() || amax_init(e)) return w;
+  w.slot = tslot(e, *v.t);
+  if (w.slot && v.whole()) v.t->valid = true;
+  return w;
 }
-// a kernel WITHOUT the fused absmax writes into the tensor at `key`
-void twrite_plain(eosvos_engine* e, int phase, const float* key) {
-  pair_uncover(e, phase, key);
-  if (!h3_mode()) return;
-  auto it = e->treg[phase].find(key);
-  if (it != e->treg[phase].end()) it->second.valid = false;
+// a kernel WITHOUT the fused absmax writes into the tensor
+void twrite_plain(Tensor& t) {
+  pair_uncover(t);
+  if (h3_mode()) t.valid = false;
 }
 // every writer of the tensor since the phase began went into its slot (the caller has checked that)
-void tmark_valid(eosvos_engine* e, int phase, const float* key) {
-  auto it = e->treg[phase].find(key);
-  if (it != e->treg[phase].end()) it->second.valid = true;
+void tmark_valid(Tensor& t) {
+  if (t.slot >= 0) t.valid = true;
 }
 // consumer: the tensor's slot if it can be trusted
-const unsigned* tlookup(eosvos_engine* e, int phase, const float* key) {
-  auto it = e->treg[phase].find(key);
-  if (it == e->treg[phase].end() || !it->second.valid) return nullptr;
-  return e->amax + amax_tcol(e, phase, it->second.idx);
+const unsigned* tlookup(eosvos_engine* e, const Tensor& t) {
+  return t.slot >= 0 && t.valid ? e->amax + amax_tcol(e, t.phase, t.slot) : nullptr;
 }
 // a new forward (phase 0) / backward (phase 1) epoch: its slots are zeroed in one memset
 void amax_new_phase(eosvos_engine* e, int phase) {
@@ -483,9 +448,9 @@ void amax_new_phase(eosvos_engine* e, int phase) {
   long& ep = phase == 0 ? e->fwd_epoch : e->bwd_epoch;
   ++ep;
   const int k0 = phase == 0 ? AM_X : AM_G;
-  amax_zero(amax_slot(e, k0, 0), 2 * nc + eosvos_engine::TSLOTS, e->s);     // the two kinds + the phase's tensor slots
+  amax_zero(amax_slot(e, k0, 0), 2 * nc + TSLOTS, e->s);     // the two kinds + the phase's tensor slots
   for (size_t i = k0 * nc; i < (k0 + 2) * nc; ++i) e->amax_rec[i].zero_epoch = ep;
-  for (auto& kv : e->treg[phase]) kv.second.valid = false;
+  e->ts.new_phase(phase);
 }
 // absmax of the [rows x C] view at `ptr` into slot (kind, ci) -- computed once per epoch and view
 const unsigned* amax_get(eosvos_engine* e, int kind, int ci, const float* ptr, long rows, int C, int ld, hipStream_t st) {
@@ -647,6 +612,82 @@ void trace(const char* kind, int ci, long M, long N, long K, int splits, double 
   plan_mix((uint64_t)ci); plan_mix((uint64_t)M); plan_mix((uint64_t)N); plan_mix((uint64_t)K); plan_mix((uint64_t)splits);
   trace_line(kind, ci, M, N, K, splits, 2.0 * M * N * K * frac);
 }
+// ---- pre-split operand path ---------------------------------------------------------------------------------------------
+// Weight gradients whose channel counts are multiples of 256 (layer3, layer4, ASPP) run on wgrad_p_kernel (presplit_kernels.hip)
+// in the f16x3 mode: 1.3-1.7x the register-staged kernel per launch (profiles/r06_wgrad_p_probe.txt).  EOSVOS_PRESPLIT=0: off.
+int g_presplit = -1;               // process-wide switch (eosvos_set_presplit); -1: not read from the environment yet
+bool presplit_switch() {
+  if (g_presplit < 0) g_presplit = (getenv("EOSVOS_PRESPLIT") && atoi(getenv("EOSVOS_PRESPLIT")) == 0) ? 0 : 1;
+  return g_presplit != 0;
+}
+// Only engines WITH a side stream take the path (or every engine under EOSVOS_TUNE_PRESPLIT_INFLIGHT=1, read when the engine is
+// built: single-stream profiling).  An engine without one runs beside other engines (the objects of a sequence, the tasks of a
+// meta-batch in flight: eosvos_set_side_stream): a 256 x 256 workgroup owns its CU, and several engines' one-per-CU launches
+// block each other -- measured end to end on a two-object 70-frame sequence with the objects in flight
+// (profiles/r06_eval_sequence_time.txt): e-OSVOS-50 0.505 -> 0.617 s per object with the path, e-OSVOS-100-OnA 1.85 -> 1.95.
+bool presplit_enabled(const eosvos_engine* e) {
+  return presplit_switch() && h3_mode() && e->force_algo == 0 && (e->s2 || e->presplit_inflight);
+}
+bool presplit_wgrad_shape(const ConvL& c, int P, int ldg, int ldx) {
+  // (minimum pixel count: at batch 1 -- 1620 pixels on the stride-16 map, 50 K steps for 256 x 256 tiles -- the path is 4 % slower
+  // than the register-staged kernels, profiles/r06_ab_log.txt; batch 3 = 4860 pixels)
+  const int minp = g_presplit == 2 ? 1 : 4000;          // eosvos_set_presplit(2): every eligible shape (tests on small maps)
+  // (stride 1 only: the inputs of the strided convs are the large maps of the previous stage, whose producers -- the streaming
+  // kernels -- write no siblings: a split pass over 40-80 MB per step costs more than the kernel gains)
+  return c.cout % 256 == 0 && c.cin % 256 == 0 && c.stride == 1 && ldg % 8 == 0 && ldx % 8 == 0 && P >= minp;
+}
+constexpr int PAIR_SC_POOL = 3072;
+// the tensor's sibling ([rows][C] floats), allocated on first use; nullptr: out of memory
+PairBuf* pair_buf(eosvos_engine* e, Tensor& t, long rows) {
+  PairBuf& pb = t.pair;
+  const int64_t need = (int64_t)rows * t.C;
+  if (!e->pair_zero) {
+    e->pair_zero = (unsigned char*)e->falloc(1024);
+    e->pair_sc_pool = e->falloc(PAIR_SC_POOL);
+    if (!e->pair_zero || !e->pair_sc_pool) return nullptr;
+    (void)hipMemsetAsync(e->pair_zero, 0, 4096, e->s);
+    (void)hipMemsetAsync(e->pair_sc_pool, 0, PAIR_SC_POOL * 4, e->s);
+  }
+  if (pb.floats < need) {
+    // (the scale words first: a sibling is committed, and with that handed out by later calls, only together with them)
+    if (!pb.sc && e->pair_sc_used + 3 > PAIR_SC_POOL) return nullptr;
+    pb.p = (unsigned char*)e->falloc(need);
+    if (!pb.p) { pb.floats = 0; return nullptr; }
+    if (!pb.sc) {
+      pb.sc = e->pair_sc_pool + e->pair_sc_used;
+      e->pair_sc_used += 3;
+    }
+    pb.floats = need; pb.covered = false; pb.fresh = true;
+  }
+  return &pb;
+}
+// conv epilogue / fix-up about to write the whole tensor through the view y (the launch's arguments are filled): hand it the
+// sibling if one is wanted
+void pair_attach(eosvos_engine* e, const View& y, ConvArgs& a) {
+  a.y2 = nullptr; a.y2_sc = nullptr; a.y2_done = 0;
+  if (!presplit_enabled(e) || e->gn() || !y.whole() || a.dst_up || a.par || a.plane_rows) return;
+  if (y.t->phase == 0 && !e->fwd_masks) return;                  // inference forward: no backward pass will read it
+  const PairBuf& pb = y.t->pair;
+  if (!pb.want || pb.fresh || !pb.p || (a.ldy & 7) || (a.N & 7)) return;
+  if ((int64_t)a.M * a.ldy > pb.floats) return;
+  a.y2 = y.sibling();
+  a.y2_sc = pb.sc + 1 + (e->pair_iter & 1);
+  if (trace_on()) fprintf(stderr, "EOSVOS_PAIR attach phase=%d M=%d N=%d ldy=%d\n", y.t->phase, a.M, a.N, a.ldy);
+}
+// after the launch: it wrote the sibling too
+void pair_covered(eosvos_engine* e, Tensor& t, const ConvArgs& a) {
+  if (!a.y2 || !a.y2_done) return;
+  t.pair.covered = true;
+  t.pair.cover_iter = e->pair_iter;
+}
+// a new trajectory (reset / new state / another batch size): the producers' scales of the previous one are forgotten; the
+// first iteration runs on the register-staged kernels (which leave fresh scales), the pre-split path resumes with the second
+// -- results do not depend on what the engine ran before
+void pair_reset(eosvos_engine* e) {
+  if (!e->pair_sc_pool) return;
+  (void)hipMemsetAsync(e->pair_sc_pool, 0, PAIR_SC_POOL * 4, e->s);
+  for (Tensor& t : e->ts.all) { t.pair.covered = false; t.pair.fresh = true; }
+}
 // Winograd F(2x2,3x3) / F(4x4,3x3) path (forward, data gradient, weight gradient) of 3x3 / stride 1 convs: 2.25x / 4x fewer MACs,
 // paid for with HBM-bound transform passes.  Always on for the decoder's two convs on the stride-4 map (27 % of a
 // batch-3 iteration's FLOPs); for the dilated / undilated conv2 of layer3 / layer4 only when the launch is large
@@ -681,9 +722,9 @@ bool wino_on(const eosvos_engine* e, int ci, int B, int Ho, int Wo) {
   const ConvL& c = e->t.convs[ci];
   if (e->force_algo == EOSVOS_ALGO_DIRECT) return false;
   if (!wino_shape(c)) return false;
-  if (e->force_algo == EOSVOS_ALGO_WINO_F2 || e->force_algo == EOSVOS_ALGO_WINO_F4) return e->wino_V.find(ci) != e->wino_V.end();
+  if (e->force_algo == EOSVOS_ALGO_WINO_F2 || e->force_algo == EOSVOS_ALGO_WINO_F4) return e->wino[ci].V != nullptr;
   if (ci == e->t.dec_a || ci == e->t.dec_b) return true;
-  if (e->wino_V.find(ci) == e->wino_V.end()) return false;            // no buffers were reserved for it
+  if (!e->wino[ci].V) return false;            // no buffers were reserved for it
   // f16x3 mode: the matrix kernels are 1.3-1.5x faster, the HBM-bound transforms are not -- layer4's conv2 and the d = 6 ASPP
   // conv no longer gain (same box, batch 1: 5.62 -> 5.45 ms without them, batch 3: 9.97 -> 9.93); the decoder keeps its F(4,3)
   if (conv_mfma_mode() == 2) return false;
@@ -706,24 +747,41 @@ ConvArgs wino_plane_gemm(const eosvos_engine* e, const ConvL& c, const WinoGeom&
 // U = G w G^T and Us = a[cout] * U (the data gradient's copy) of conv ci: remade on stream st when the weights changed
 // since they were last made
 void wino_ensure_weights(eosvos_engine* e, int ci, int tm, hipStream_t st) {
-  if (e->wino_us_valid[ci]) return;
+  auto& w = e->wino[ci];
+  if (w.us_valid) return;
   const ConvL& c = e->t.convs[ci];
   unsigned* us = amax_wino_weights(e, ci, st);
-  launch_wino_weight(tm, e->W_(ci), c.cout, c.cin, e->A_(ci), e->wino_U[ci], e->wino_Us[ci], st, us, us ? us + e->t.convs.size() : nullptr);
-  e->wino_us_valid[ci] = 1;
+  launch_wino_weight(tm, e->W_(ci), c.cout, c.cin, e->A_(ci), w.U, w.Us, st, us, us ? us + e->t.convs.size() : nullptr);
+  w.us_valid = true;
 }
-// `side`: launch on the side stream with its own stream-K workspace (forward branches that do not depend on
-// each other: downsample convs, decoder.conv1)
-void conv_fwd(eosvos_engine* e, int ci, const float* x, int ldx, int Hi, int Wi, float* y, int ldy, int B,
-              const float* res, int ldres, bool relu, bool side = false, const float* xkey = nullptr, const float* ykey = nullptr) {
-  // xkey / ykey: first element of the tensors that x / y are views of (f16x3 absmax slots are kept per tensor)
-  if (!xkey) xkey = x;
-  if (!ykey) ykey = y;
+// The optional operands and the flags of conv_fwd / conv_dgrad (as ConvArgs holds them: one set for both passes), named at
+// the call: conv_fwd(e, ci, x, y, B, Opt().relu().add(res)), conv_dgrad(e, ci, g, gx, B, Opt().accum().mask(x, 256)).
+struct Opt {
+  View add_;                       // forward: the residual; data gradient: a gradient added in front of the mask
+  bool relu_ = false, side_ = false, accum_ = false;
+  const Tensor* mask_ = nullptr;
+  int mask_c0_ = 0;
+  Opt& add(const View& v) { add_ = v; return *this; }
+  Opt& relu(bool on = true) { relu_ = on; return *this; }
+  // launch on the side stream with its own stream-K workspace (forward branches that do not depend on each other:
+  // downsample convs, decoder.conv1)
+  Opt& side(bool on = true) { side_ = on; return *this; }
+  Opt& accum(bool on = true) { accum_ = on; return *this; }
+  // zero where the ReLU mask of `x` (the forward activation gx is the gradient of: same layout) is clear, in channels >= c0
+  Opt& mask(const Tensor* x, int c0 = 0) { mask_ = x; mask_c0_ = c0; return *this; }
+};
+// y = conv ci of x (the map size is x's tensor's)
+void conv_fwd(eosvos_engine* e, int ci, const View& xv, const View& yv, int B, const Opt& o = Opt()) {
+  const float *x = xv.ptr(), *res = o.add_.ptr();
+  float* y = yv.ptr();
+  const int ldx = xv.ld(), ldy = yv.ld(), ldres = o.add_.ld(), Hi = xv.t->H, Wi = xv.t->W;
+  const bool relu = o.relu_, side = o.side_;
   const ConvL& c = e->t.convs[ci];
   ConvArgs a;
   memset(&a, 0, sizeof(a));
   a.wg_budget = e->wg_budget;
   hipStream_t st = side ? e->s2 : e->s;
+  const Written yw = twrite_fused(e, yv);
   a.x = x; a.w = e->W_(ci); a.y = y; a.ws = side ? e->ws_conv2 : e->ws_conv;
   a.B = B; a.Hi = Hi; a.Wi = Wi; a.ldx = ldx; a.Kc = c.cin;
   a.Ho = conv_out(Hi, c.k, c.stride, c.dil, c.pad); a.Wo = conv_out(Wi, c.k, c.stride, c.dil, c.pad);
@@ -741,51 +799,46 @@ void conv_fwd(eosvos_engine* e, int ci, const float* x, int ldx, int Hi, int Wi,
     // forward with a side stream has already queued all of them there (forward_impl), beside layer1..3
     if (e->wino_w_wait) { (void)hipStreamWaitEvent(st, e->ev_wino_w, 0); e->wino_w_wait = false; }
     wino_ensure_weights(e, ci, wg.tm, st);
-    unsigned* vslot = amax_fused_slot(e, AM_V, ci, e->wino_V[ci], st);   // the input transform accumulates max|V| itself
-    launch_wino_input(wg.tm, x, ldx, c.cin, B, Hi, Wi, th, tw, wg.d, prow, e->wino_V[ci], st, vslot);
-    e->wino_v_batch[ci] = B;
-    ConvArgs m = wino_plane_gemm(e, c, wg, e->wino_V[ci], e->wino_U[ci], e->wino_m, a.ws, 0);
+    auto& w = e->wino[ci];
+    unsigned* vslot = amax_fused_slot(e, AM_V, ci, w.V, st);   // the input transform accumulates max|V| itself
+    launch_wino_input(wg.tm, x, ldx, c.cin, B, Hi, Wi, th, tw, wg.d, prow, w.V, st, vslot);
+    w.v_batch = B;
+    ConvArgs m = wino_plane_gemm(e, c, wg, w.V, w.U, e->wino_m, a.ws, 0);
     if (vslot) { m.amax_x = vslot; m.amax_w = amax_slot(e, AM_U, ci); }
     // the output transform writes y (directly, or the raw conv output of the GroupNorm mode)
     // (GroupNorm mode: the output transform writes the raw conv output; y and its absmax come from the GroupNorm apply pass)
-    unsigned* const yslot_any = twrite_fused(e, 0, ykey, ldy == c.cout);
-    unsigned* yslot = gn ? nullptr : yslot_any;
-    uint8_t* ym8 = (gn || !e->m8w(ykey)) ? nullptr : e->m8w(ykey) + (y - ykey) / 4;
     trace("fwd", ci, m.M, m.N, c.cin, conv_plan(m));
     launch_conv(m, st);
     launch_wino_output(wg.tm, e->wino_m, prow, c.cout, B, a.Ho, a.Wo, th, tw, wg.d, gn ? nullptr : e->A_(ci), gn ? nullptr : e->B_(ci),
-                       (!gn && relu) ? 1 : 0, gn ? e->zbuf[ci] : y, gn ? c.cout : ldy, st, yslot, ym8, ldy / 4);
+                       (!gn && relu) ? 1 : 0, gn ? e->zbuf[ci]->p : y, gn ? c.cout : ldy, st, gn ? nullptr : yw.slot,
+                       gn ? nullptr : yw.mask, yw.ldmask);
     if (gn)
-      launch_gn_forward(e->zbuf[ci], c.cout, e->G_(ci), e->nb + c.noff, res, ldres, y, ldy, e->gn_stats[ci], e->gn_partial, B,
-                        a.Ho * a.Wo, c.cout, 1e-5f, relu ? 1 : 0, st, yslot_any, (relu && e->m8w(ykey)) ? e->m8w(ykey) + (y - ykey) / 4 : nullptr, ldy / 4);
+      launch_gn_forward(e->zbuf[ci]->p, c.cout, e->G_(ci), e->nb + c.noff, res, ldres, y, ldy, e->gn_stats[ci], e->gn_partial, B,
+                        a.Ho * a.Wo, c.cout, 1e-5f, relu ? 1 : 0, st, yw.slot, relu ? yw.mask : nullptr, yw.ldmask);
     return;
   }
   if (gn) {                       // raw conv output -> GroupNorm kernels (statistics are data dependent)
-    a.y = e->zbuf[ci]; a.ldy = c.cout;
+    a.y = e->zbuf[ci]->p; a.ldy = c.cout;
   } else {
     a.scale = e->A_(ci); a.bias = e->B_(ci);
     a.res = res; a.ldres = ldres; a.relu = relu ? 1 : 0;
-    if (relu)
-      if (uint8_t* m = e->m8w(ykey)) { a.mask8_out = m + (y - ykey) / 4; a.ldm8_out = ldy / 4; }
+    if (relu && yw.mask) { a.mask8_out = yw.mask; a.ldm8_out = yw.ldmask; }
   }
   attach_tap_table(e, ci, 0, B, a);
-  unsigned* gn_yslot = nullptr;
   if (h3_mode() && !amax_init(e)) {
     amax_weights(e, st);
-    a.amax_x = tlookup(e, 0, xkey);
+    a.amax_x = tlookup(e, *xv.t);
     if (!a.amax_x) a.amax_x = amax_get(e, AM_X, ci, x, (long)B * Hi * Wi, c.cin, ldx, st);
     a.amax_w = amax_slot(e, AM_W, ci);
-    gn_yslot = twrite_fused(e, 0, ykey, ldy == c.cout);      // GroupNorm mode: y (and its absmax) is written by the apply pass
-    if (!gn) a.amax_y = gn_yslot;
+    if (!gn) a.amax_y = yw.slot;      // GroupNorm mode: y (and its absmax) is written by the apply pass
   }
-  if (!gn && !side) pair_attach(e, 0, ykey, y, ldy == c.cout, a);
+  if (!gn && !side) pair_attach(e, yv, a);
   trace("fwd", ci, a.M, a.N, (long)c.T() * c.cin, conv_plan(a), conv_exec_frac(a));
   launch_conv(a, st);
-  pair_covered(e, 0, ykey, a);
+  pair_covered(e, *yv.t, a);
   if (gn)
-    launch_gn_forward(e->zbuf[ci], c.cout, e->G_(ci), e->nb + c.noff, res, ldres, y, ldy, e->gn_stats[ci], e->gn_partial, B,
-                      a.Ho * a.Wo, c.cout, 1e-5f, relu ? 1 : 0, st, gn ? gn_yslot : nullptr,
-                      (relu && e->m8w(ykey)) ? e->m8w(ykey) + (y - ykey) / 4 : nullptr, ldy / 4);
+    launch_gn_forward(e->zbuf[ci]->p, c.cout, e->G_(ci), e->nb + c.noff, res, ldres, y, ldy, e->gn_stats[ci], e->gn_partial, B,
+                      a.Ho * a.Wo, c.cout, 1e-5f, relu ? 1 : 0, st, yw.slot, relu ? yw.mask : nullptr, yw.ldmask);
 }
 // A data-gradient GEMM whose N leaves a tail of <= 64 columns over whole 128-wide column tiles, e.g. the decoder's 304
 // input channels: 2 column tiles of 128 + a 64-wide launch instead of 3 x 128 (the 128-wide kernel would spend a third of
@@ -803,21 +856,20 @@ void launch_dgrad_tail_split(eosvos_engine* e, int ci, ConvArgs a, long K) {
   trace("dgrad", ci, b.M, b.N, K, conv_plan(b));
   launch_conv(b, e->s);
 }
-// gx[B,Hin,Win,cin] (ld ldgx) (+)= dgrad of conv ci applied to g[B,Ho,Wo,cout] (ld ldg), zero in channels >= mask_c0
-// where the ReLU mask of `relu_x` (the forward activation gx is the gradient of: same layout) is clear.  relu_x must
-// have mask bytes (eosvos_engine::mask8); a masked gradient without them is an error, never an unmasked result.
-int conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int Win, float* gx, int ldgx, int B,
-               bool accum, const float* relu_x, int mask_c0, const float* add = nullptr, int ldadd = 0,
-               const float* gkey = nullptr, const float* gxkey = nullptr) {
-  const uint8_t* mask8 = relu_x ? e->m8(relu_x) : nullptr;
-  if (relu_x && !mask8) return fail("internal: a masked data gradient of conv " + std::to_string(ci) + " has no ReLU mask bytes");
+// gx[B,Hin,Win,cin] (+)= dgrad of conv ci applied to g[B,Ho,Wo,cout] (+ add) (the map size is gx's tensor's).  The mask
+// tensor must have mask bytes (Tensor::mask); a masked gradient without them is an error, never an unmasked result.
+int conv_dgrad(eosvos_engine* e, int ci, View gv, const View& gxv, int B, const Opt& o = Opt()) {
+  const uint8_t* mask8 = o.mask_ ? o.mask_->mask : nullptr;
+  if (o.mask_ && !mask8) return fail("internal: a masked data gradient of conv " + std::to_string(ci) + " has no ReLU mask bytes");
   const ConvL& c = e->t.convs[ci];
   ConvArgs a;
   memset(&a, 0, sizeof(a));
   a.wg_budget = e->wg_budget;
-  if (!gkey) gkey = g;
-  if (!gxkey) gxkey = gx;
-  if (e->gn() && c.norm) { g = e->zbuf[ci]; ldg = c.cout; gkey = g; }   // gradient w.r.t. the raw conv output (conv_wgrad made it)
+  if (e->gn() && c.norm) gv = View(e->zbuf[ci]);   // gradient w.r.t. the raw conv output (conv_wgrad made it)
+  const float *g = gv.ptr(), *add = o.add_.ptr();
+  float* gx = gxv.ptr();
+  const int ldg = gv.ld(), ldgx = gxv.ld(), ldadd = o.add_.ld(), Hin = gxv.t->H, Win = gxv.t->W;
+  unsigned* const gxs = twrite_fused(e, gxv).slot;
   a.x = g; a.w = e->W_(ci); a.y = gx; a.ws = e->ws_conv;
   a.B = B; a.Hi = conv_out(Hin, c.k, c.stride, c.dil, c.pad); a.Wi = conv_out(Win, c.k, c.stride, c.dil, c.pad);
   a.ldx = ldg; a.Kc = c.cout;
@@ -825,16 +877,16 @@ int conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int W
   a.mul = 1; a.off0 = c.pad; a.kstep = -c.dil; a.upshift = c.stride == 2 ? 1 : 0;
   a.M = B * Hin * Win; a.wN = c.cout; a.wK = c.cin; a.kmajor = 1;
   a.kscale = e->A_(ci);
-  a.mask8 = mask8; a.ldm8 = ldgx / 4; a.mask_c0 = mask_c0; a.accum = accum ? 1 : 0;
+  a.mask8 = mask8; a.ldm8 = gxv.ldmask(); a.mask_c0 = o.mask_c0_; a.accum = o.accum_ ? 1 : 0;
   a.res = add; a.ldres = ldadd;
   const bool wino_dg = !add && wino_on(e, ci, B, Hin, Win);
   if (h3_mode() && !wino_dg && !amax_init(e)) {
     amax_weights(e, e->s);
-    a.amax_x = tlookup(e, 1, gkey);
+    a.amax_x = tlookup(e, *gv.t);
     if (!a.amax_x) a.amax_x = amax_get(e, AM_G, ci, g, (long)B * a.Hi * a.Wi, c.cout, ldg, e->s);
     a.amax_w = amax_slot(e, AM_W, ci);
     a.amax_ks = amax_ks(e, ci, e->s);
-    a.amax_y = twrite_fused(e, 1, gxkey, ldgx == c.cin);
+    a.amax_y = gxs;
   }
   if (wino_dg) {
     // Winograd data gradient: dV[p] = dM[p] (a[cout] U[p]), 16 / 36 GEMMs [tiles x cout] x [cout x cin] in one batched
@@ -842,31 +894,31 @@ int conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int W
     const WinoGeom wg = wino_geom(e, c, B, Hin, Win);
     const int th = wg.th, tw = wg.tw;
     const long prow = wg.prow;
-    if (e->wino_dm_batch[ci] != B) {
-      unsigned* dms = amax_fused_slot(e, AM_DM, ci, e->wino_dM[ci], e->s);
-      launch_wino_grad(wg.tm, g, ldg, c.cout, B, Hin, Win, th, tw, wg.d, prow, e->wino_dM[ci], e->s, dms);
+    auto& w = e->wino[ci];
+    if (w.dm_batch != B) {
+      unsigned* dms = amax_fused_slot(e, AM_DM, ci, w.dM, e->s);
+      launch_wino_grad(wg.tm, g, ldg, c.cout, B, Hin, Win, th, tw, wg.d, prow, w.dM, e->s, dms);
     }
-    e->wino_dm_batch[ci] = 0;
+    w.dm_batch = 0;
     wino_ensure_weights(e, ci, wg.tm, e->s);         // no forward since the weights changed: rebuild a[cout] * U
-    ConvArgs m = wino_plane_gemm(e, c, wg, e->wino_dM[ci], e->wino_Us[ci], e->wino_dv, e->ws_conv, 1);
+    ConvArgs m = wino_plane_gemm(e, c, wg, w.dM, w.Us, e->wino_dv, e->ws_conv, 1);
     if (h3_mode() && !amax_init(e)) {
-      m.amax_x = amax_get(e, AM_DM, ci, e->wino_dM[ci], (long)wg.np * prow, c.cout, c.cout, e->s);   // made by the transform
+      m.amax_x = amax_get(e, AM_DM, ci, w.dM, (long)wg.np * prow, c.cout, c.cout, e->s);   // made by the transform
       m.amax_w = amax_slot(e, AM_US, ci);
     }
-    unsigned* gxs = twrite_fused(e, 1, gxkey, ldgx == c.cin);
     if (dgrad_has_tail(m)) {
       launch_dgrad_tail_split(e, ci, m, c.cout);
     } else {
       trace("dgrad", ci, m.M, m.N, c.cout, conv_plan(m));
       launch_conv(m, e->s);
     }
-    launch_wino_dgrad_output(wg.tm, e->wino_dv, prow, c.cin, B, Hin, Win, th, tw, wg.d, mask8, a.ldm8, mask_c0, accum ? 1 : 0, gx, ldgx, e->s, gxs);
+    launch_wino_dgrad_output(wg.tm, e->wino_dv, prow, c.cin, B, Hin, Win, th, tw, wg.d, mask8, a.ldm8, a.mask_c0, a.accum, gx, ldgx, e->s, gxs);
     return 0;
   }
   if (c.k == 1 && c.stride == 2 && !add) {
     // only the even pixels of the finer grid receive a contribution: run the GEMM on the
     // coarse grid (4x less MFMA work) and scatter; untouched pixels are zero (or keep their sum)
-    if (!accum) (void)hipMemsetAsync(gx, 0, (size_t)B * Hin * Win * ldgx * sizeof(float), e->s);
+    if (!a.accum) (void)hipMemsetAsync(gx, 0, (size_t)B * Hin * Win * ldgx * sizeof(float), e->s);
     a.Ho = a.Hi; a.Wo = a.Wi; a.mul = 1; a.off0 = 0; a.kstep = 0; a.upshift = 0;
     a.M = B * a.Ho * a.Wo; a.dst_up = 1; a.Hf = Hin; a.Wf = Win;
   }
@@ -875,10 +927,10 @@ int conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int W
     return 0;
   }
   attach_tap_table(e, ci, 1, B, a);
-  pair_attach(e, 1, gxkey, gx, ldgx == c.cin, a);
+  pair_attach(e, gxv, a);
   trace("dgrad", ci, a.M, a.N, (long)c.T() * c.cout, conv_plan(a), conv_exec_frac(a));
   launch_conv(a, e->s);
-  pair_covered(e, 1, gxkey, a);
+  pair_covered(e, *gxv.t, a);
   return 0;
 }
 // Weight-gradient launches are queued and forked onto the side stream a few layers at a time: every
@@ -888,89 +940,6 @@ int conv_dgrad(eosvos_engine* e, int ci, const float* g, int ldg, int Hin, int W
 // Measured: at batch 1 (launch-bound layers) forking every 4 layers gains 1.8 %; at batch 3 the later start of the
 // weight gradients costs more than the bubbles (+1.7 %), so there every layer forks at once.
 #define EOSVOS_SIDE_BATCH 4
-// ---- pre-split operand path ---------------------------------------------------------------------------------------------
-// Weight gradients whose channel counts are multiples of 256 (layer3, layer4, ASPP) run on wgrad_p_kernel (presplit_kernels.hip)
-// in the f16x3 mode: 1.3-1.7x the register-staged kernel per launch (profiles/r06_wgrad_p_probe.txt).  EOSVOS_PRESPLIT=0: off.
-int g_presplit = -1;               // process-wide switch (eosvos_set_presplit); -1: not read from the environment yet
-bool presplit_switch() {
-  if (g_presplit < 0) g_presplit = (getenv("EOSVOS_PRESPLIT") && atoi(getenv("EOSVOS_PRESPLIT")) == 0) ? 0 : 1;
-  return g_presplit != 0;
-}
-// Only engines WITH a side stream take the path (or every engine under EOSVOS_TUNE_PRESPLIT_INFLIGHT=1, read when the engine is
-// built: single-stream profiling).  An engine without one runs beside other engines (the objects of a sequence, the tasks of a
-// meta-batch in flight: eosvos_set_side_stream): a 256 x 256 workgroup owns its CU, and several engines' one-per-CU launches
-// block each other -- measured end to end on a two-object 70-frame sequence with the objects in flight
-// (profiles/r06_eval_sequence_time.txt): e-OSVOS-50 0.505 -> 0.617 s per object with the path, e-OSVOS-100-OnA 1.85 -> 1.95.
-bool presplit_enabled(const eosvos_engine* e) {
-  return presplit_switch() && h3_mode() && e->force_algo == 0 && (e->s2 || e->presplit_inflight);
-}
-bool presplit_wgrad_shape(const ConvL& c, int P, int ldg, int ldx) {
-  // (minimum pixel count: at batch 1 -- 1620 pixels on the stride-16 map, 50 K steps for 256 x 256 tiles -- the path is 4 % slower
-  // than the register-staged kernels, profiles/r06_ab_log.txt; batch 3 = 4860 pixels)
-  const int minp = g_presplit == 2 ? 1 : 4000;          // eosvos_set_presplit(2): every eligible shape (tests on small maps)
-  // (stride 1 only: the inputs of the strided convs are the large maps of the previous stage, whose producers -- the streaming
-  // kernels -- write no siblings: a split pass over 40-80 MB per step costs more than the kernel gains)
-  return c.cout % 256 == 0 && c.cin % 256 == 0 && c.stride == 1 && ldg % 8 == 0 && ldx % 8 == 0 && P >= minp;
-}
-constexpr int PAIR_SC_POOL = 3072;
-// the sibling of the tensor at `key` ([rows][ld] floats), allocated on first use; nullptr: out of memory
-eosvos_engine::PairBuf* pair_buf(eosvos_engine* e, int phase, const float* key, long rows, int ld) {
-  auto& pb = e->pairs[phase][key];
-  const int64_t need = (int64_t)rows * ld;
-  if (!e->pair_zero) {
-    e->pair_zero = (unsigned char*)e->falloc(1024);
-    e->pair_sc_pool = e->falloc(PAIR_SC_POOL);
-    if (!e->pair_zero || !e->pair_sc_pool) return nullptr;
-    (void)hipMemsetAsync(e->pair_zero, 0, 4096, e->s);
-    (void)hipMemsetAsync(e->pair_sc_pool, 0, PAIR_SC_POOL * 4, e->s);
-  }
-  if (pb.floats < need) {
-    // (the scale words first: a sibling is committed, and with that handed out by later calls, only together with them)
-    if (!pb.sc && e->pair_sc_used + 3 > PAIR_SC_POOL) return nullptr;
-    pb.p = (unsigned char*)e->falloc(need);
-    if (!pb.p) { pb.floats = 0; return nullptr; }
-    if (!pb.sc) {
-      pb.sc = e->pair_sc_pool + e->pair_sc_used;
-      e->pair_sc_used += 3;
-    }
-    pb.floats = need; pb.covered = false; pb.fresh = true;
-  }
-  return &pb;
-}
-// a kernel is about to write (part of) the tensor at `key`: until a writer that covers it whole reports the fused sibling
-// write (pair_covered), the sibling is stale
-void pair_uncover(eosvos_engine* e, int phase, const float* key) {
-  auto it = e->pairs[phase].find(key);
-  if (it != e->pairs[phase].end()) it->second.covered = false;
-}
-// conv epilogue / fix-up about to write the whole tensor at `key` through the view y: hand it the sibling if one is wanted
-void pair_attach(eosvos_engine* e, int phase, const float* key, const float* y, bool full, ConvArgs& a) {
-  a.y2 = nullptr; a.y2_sc = nullptr; a.y2_done = 0;
-  if (!presplit_enabled(e) || e->gn() || !full || a.dst_up || a.par || a.plane_rows) return;
-  if (phase == 0 && !e->fwd_masks) return;                  // inference forward: no backward pass will read it
-  auto it = e->pairs[phase].find(key);
-  if (it == e->pairs[phase].end() || !it->second.want || it->second.fresh || !it->second.p || (a.ldy & 7) || (a.N & 7)) return;
-  if ((int64_t)a.M * a.ldy > it->second.floats) return;
-  a.y2 = it->second.p + (y - key) * 4;
-  a.y2_sc = it->second.sc + 1 + (e->pair_iter & 1);
-  if (trace_on()) fprintf(stderr, "EOSVOS_PAIR attach phase=%d M=%d N=%d ldy=%d\n", phase, a.M, a.N, a.ldy);
-}
-void pair_covered(eosvos_engine* e, int phase, const float* key, const ConvArgs& a) {
-  if (!a.y2 || !a.y2_done) return;
-  auto it = e->pairs[phase].find(key);
-  if (it == e->pairs[phase].end()) return;
-  it->second.covered = true;
-  it->second.cover_iter = e->pair_iter;
-}
-// a new trajectory (reset / new state / another batch size): the producers' scales of the previous one are forgotten; the
-// first iteration runs on the register-staged kernels (which leave fresh scales), the pre-split path resumes with the second
-// -- results do not depend on what the engine ran before
-void pair_reset(eosvos_engine* e) {
-  if (!e->pair_sc_pool) return;
-  (void)hipMemsetAsync(e->pair_sc_pool, 0, PAIR_SC_POOL * 4, e->s);
-  for (int ph = 0; ph < 2; ++ph)
-    for (auto& kv : e->pairs[ph]) { kv.second.covered = false; kv.second.fresh = true; }
-}
 // Workgroup budget of the pre-split weight gradients.  Beside the data-gradient chain (engines with a side stream) they plan for
 // THREE QUARTERS of the chip: a 256 x 256 workgroup owns its CU (128 KB of LDS: no conv workgroup fits beside it), so a launch that
 // covers every CU makes the main stream's next data gradient wait for whole weight-gradient workgroups to finish, and one that
@@ -987,15 +956,16 @@ int pair_margin(int phase) {
   static const int margin_g = getenv("EOSVOS_TUNE_PAIR_MARGIN_G") ? atoi(getenv("EOSVOS_TUNE_PAIR_MARGIN_G")) : 3;
   return phase == 0 ? margin_x : margin_g;
 }
-// consumer side: the sibling of the tensor at `key` is wanted from now on; true when this iteration's producers wrote it
-bool pair_operand(eosvos_engine* e, int phase, const float* key, const float* view, long rows, int C, int ld, eosvos_engine::PairBuf*& pb) {
+// consumer side: the sibling of the view's tensor is wanted from now on; true when this iteration's producers wrote it
+bool pair_operand(eosvos_engine* e, const View& v, long rows, PairBuf*& pb) {
   // sized for the engine's largest batch: the sibling never moves (the grouped launches' device tables hold its address)
   const long rows_alloc = e->lastB > 0 ? rows / e->lastB * e->maxB : rows;
-  pb = pair_buf(e, phase, key, std::max(rows, rows_alloc), ld);
-  if (!pb || (view - key) < 0 || (view - key) + (rows - 1) * (int64_t)ld + C > pb->floats || ((view - key) & 7)) { pb = nullptr; return false; }
+  pb = pair_buf(e, *v.t, std::max(rows, rows_alloc));
+  if (!pb || v.c0 < 0 || v.c0 + (rows - 1) * (int64_t)v.ld() + v.C > pb->floats || (v.c0 & 7)) { pb = nullptr; return false; }
   pb->want = true;
   const bool cov = pb->covered && pb->cover_iter == e->pair_iter && !pb->fresh;
-  if (trace_on()) fprintf(stderr, "EOSVOS_PAIR operand phase=%d rows=%ld C=%d ld=%d covered=%d fresh=%d\n", phase, rows, C, ld, (int)cov, (int)pb->fresh);
+  if (trace_on())
+    fprintf(stderr, "EOSVOS_PAIR operand phase=%d rows=%ld C=%d ld=%d covered=%d fresh=%d\n", v.t->phase, rows, v.C, v.ld(), (int)cov, (int)pb->fresh);
   return cov;
 }
 void side_flush(eosvos_engine* e) {
@@ -1194,19 +1164,23 @@ int flush_wgrad_group(eosvos_engine* e, int stage, int B) {
 // arguments, record the slab count in upd_splits and return the launch for conv_wgrad to place.
 using WgLaunch = std::function<void(hipStream_t)>;
 // Winograd domain: dM = A dY A^T feeds this weight gradient (side stream) and the data gradient (main stream)
-WgLaunch wgrad_wino(eosvos_engine* e, int ci, const float* g, int ldg, const float* x, int ldx, int Hin, int Win, int B, int Ho, int Wo) {
+WgLaunch wgrad_wino(eosvos_engine* e, int ci, const View& gv, const View& xv, int B, int Ho, int Wo) {
   const ConvL& c = e->t.convs[ci];
   const WinoGeom wg = wino_geom(e, c, B, Ho, Wo);
-  unsigned* dms = amax_fused_slot(e, AM_DM, ci, e->wino_dM[ci], e->s);
-  launch_wino_grad(wg.tm, g, ldg, c.cout, B, Ho, Wo, wg.th, wg.tw, wg.d, wg.prow, e->wino_dM[ci], e->s, dms);
-  e->wino_dm_batch[ci] = B;
+  auto& w = e->wino[ci];
+  float* const dM = w.dM;
+  unsigned* dms = amax_fused_slot(e, AM_DM, ci, dM, e->s);
+  launch_wino_grad(wg.tm, gv.ptr(), gv.ld(), c.cout, B, Ho, Wo, wg.th, wg.tw, wg.d, wg.prow, dM, e->s, dms);
+  w.dm_batch = B;
   const long ntile = wg.ntile, prow = wg.prow;
-  float* V = e->wino_V[ci];
-  const bool need_v = e->wino_v_batch[ci] != B;       // else: V comes from the forward pass
+  float* V = w.V;
+  const bool need_v = w.v_batch != B;       // else: V comes from the forward pass
+  const float* x = xv.ptr();
+  const int ldx = xv.ld(), Hin = xv.t->H, Win = xv.t->W;
   float* final_slab = e->ws_wg + e->ws_off[ci];
   WgradArgs a;
   memset(&a, 0, sizeof(a));
-  a.g = e->wino_dM[ci]; a.x = V; a.ws = final_slab + c.wsize();
+  a.g = dM; a.x = V; a.ws = final_slab + c.wsize();
   a.B = 1; a.Ho = 1; a.Wo = (int)ntile; a.ldg = c.cout; a.Cout = c.cout; a.Hi = 1; a.Wi = (int)ntile; a.ldx = c.cin; a.Cin = c.cin;
   a.KH = a.KW = wg.tm + 2; a.stride = 1; a.pad = 0; a.dil = 0;  // the "taps" are the Winograd positions, no pixel shift
   a.g_tap_stride = prow * c.cout; a.x_tap_stride = prow * c.cin;
@@ -1219,7 +1193,7 @@ WgLaunch wgrad_wino(eosvos_engine* e, int ci, const float* g, int ldg, const flo
   const int cin = c.cin, cout = c.cout;
   const bool h3 = h3_mode() && !amax_init(e);
   if (h3) {
-    a.amax_g = amax_get(e, AM_DM, ci, e->wino_dM[ci], (long)wg.np * prow, c.cout, c.cout, e->s);
+    a.amax_g = amax_get(e, AM_DM, ci, dM, (long)wg.np * prow, c.cout, c.cout, e->s);
     a.amax_x = amax_slot(e, AM_V, ci);
     if (!need_v && amax_rec_of(e, AM_V, ci).epoch != e->fwd_epoch)      // V of a forward in another mode
       a.amax_x = amax_get(e, AM_V, ci, V, (long)wg.np * prow, c.cin, c.cin, e->s);
@@ -1238,16 +1212,16 @@ WgLaunch wgrad_wino(eosvos_engine* e, int ci, const float* g, int ldg, const flo
 // Pre-split operand path: 256 x 256 tiles on the pair8 siblings of g and x when this iteration's producers wrote both
 // (`covered`); otherwise the register-staged kernel with the same K splits, which leaves the scales for the next iteration's
 // producers (a.scn_*).  false: the conv does not take the path.
-bool wgrad_presplit_args(eosvos_engine* e, const ConvL& c, const float* gkey, const float* xkey, WgradArgs& a, WgradPArgs& pa, bool& covered) {
+bool wgrad_presplit_args(eosvos_engine* e, const ConvL& c, const View& gv, const View& xv, WgradArgs& a, WgradPArgs& pa, bool& covered) {
   if (!presplit_enabled(e) || e->gn() || !a.amax_g || !a.amax_x || !presplit_wgrad_shape(c, a.B * a.Ho * a.Wo, a.ldg, a.ldx)) return false;
   const long rows_g = (long)a.B * a.Ho * a.Wo, rows_x = (long)a.B * a.Hi * a.Wi;
-  eosvos_engine::PairBuf *xb = nullptr, *gb = nullptr;
-  const bool covx = pair_operand(e, 0, xkey, a.x, rows_x, c.cin, a.ldx, xb);
-  const bool covg = pair_operand(e, 1, gkey, a.g, rows_g, c.cout, a.ldg, gb);
+  PairBuf *xb = nullptr, *gb = nullptr;
+  const bool covx = pair_operand(e, xv, rows_x, xb);
+  const bool covg = pair_operand(e, gv, rows_g, gb);
   if (!xb || !gb) return false;
   const int par = (int)(e->pair_iter & 1);
   memset(&pa, 0, sizeof(pa));
-  pa.g2 = gb->p + (a.g - gkey) * 4; pa.x2 = xb->p + (a.x - xkey) * 4; pa.ws = a.ws;
+  pa.g2 = gv.sibling(); pa.x2 = xv.sibling(); pa.ws = a.ws;
   pa.B = a.B; pa.Ho = a.Ho; pa.Wo = a.Wo; pa.ldg = a.ldg; pa.Cout = c.cout; pa.Hi = a.Hi; pa.Wi = a.Wi; pa.ldx = a.ldx; pa.Cin = c.cin;
   pa.KH = pa.KW = c.k; pa.stride = c.stride; pa.pad = c.pad; pa.dil = c.dil;
   pa.zero = e->pair_zero;
@@ -1262,9 +1236,10 @@ bool wgrad_presplit_args(eosvos_engine* e, const ConvL& c, const float* gkey, co
   return true;
 }
 // direct form; an empty launch: queued for the stage's grouped launch (flush_wgrad_group records the slab count)
-WgLaunch wgrad_direct(eosvos_engine* e, int ci, const float* g, int ldg, const float* x, int ldx, int Hin, int Win, int B, int Ho, int Wo,
-                      const float* gkey, const float* xkey) {
+WgLaunch wgrad_direct(eosvos_engine* e, int ci, const View& gv, const View& xv, int B, int Ho, int Wo) {
   const ConvL& c = e->t.convs[ci];
+  const float *g = gv.ptr(), *x = xv.ptr();
+  const int ldg = gv.ld(), ldx = xv.ld(), Hin = xv.t->H, Win = xv.t->W;
   WgradArgs a;
   memset(&a, 0, sizeof(a));
   a.g = g; a.x = x; a.ws = e->ws_wg + e->ws_off[ci];
@@ -1272,10 +1247,10 @@ WgLaunch wgrad_direct(eosvos_engine* e, int ci, const float* g, int ldg, const f
   a.ldg = ldg; a.Cout = c.cout; a.Hi = Hin; a.Wi = Win; a.ldx = ldx; a.Cin = c.cin;
   a.KH = a.KW = c.k; a.stride = c.stride; a.pad = c.pad; a.dil = c.dil;
   if (h3_mode() && !amax_init(e)) {
-    a.amax_g = tlookup(e, 1, gkey);
+    a.amax_g = tlookup(e, *gv.t);
     if (!a.amax_g) a.amax_g = amax_get(e, AM_G, ci, g, (long)B * Ho * Wo, c.cout, ldg, e->s);
     // the input activation: the slot of its tensor or of this conv's view from the forward pass, else it is made now
-    a.amax_x = tlookup(e, 0, xkey);
+    a.amax_x = tlookup(e, *xv.t);
     if (!a.amax_x) {
       unsigned* xs = amax_slot(e, AM_X, ci);
       auto& r = amax_rec_of(e, AM_X, ci);
@@ -1284,7 +1259,7 @@ WgLaunch wgrad_direct(eosvos_engine* e, int ci, const float* g, int ldg, const f
   }
   WgradPArgs pa{};
   bool covered = false;
-  const bool presplit = wgrad_presplit_args(e, c, gkey, xkey, a, pa, covered);
+  const bool presplit = wgrad_presplit_args(e, c, gv, xv, a, pa, covered);
   if (wgrad_groupable(e, ci, B)) {
     e->wg_pending.push_back({ci, a, presplit, pa, covered});
     return nullptr;
@@ -1301,20 +1276,17 @@ WgLaunch wgrad_direct(eosvos_engine* e, int ci, const float* g, int ldg, const f
   return [a](hipStream_t ws) { launch_wgrad(a, ws); };
 }
 // slabs of dW into ws_wg (their number: upd_splits[ci]; of a conv queued for its stage's grouped launch: set by flush_wgrad_group)
-void conv_wgrad(eosvos_engine* e, int ci, const float* g, int ldg, const float* x, int ldx, int Hin, int Win, int B,
-                const float* gkey = nullptr, const float* xkey = nullptr) {
+// (g: gradient w.r.t. the conv's output; x: its input activation, whose tensor gives the map size)
+void conv_wgrad(eosvos_engine* e, int ci, View gv, const View& xv, int B) {
   const ConvL& c = e->t.convs[ci];
-  if (!gkey) gkey = g;
-  if (!xkey) xkey = x;
-  const int Ho = conv_out(Hin, c.k, c.stride, c.dil, c.pad), Wo = conv_out(Win, c.k, c.stride, c.dil, c.pad);
+  const int Ho = conv_out(xv.t->H, c.k, c.stride, c.dil, c.pad), Wo = conv_out(xv.t->W, c.k, c.stride, c.dil, c.pad);
   if (e->gn() && c.norm) {        // dz = GroupNorm backward of G_u, written over the stored raw output
     // (round 5: the apply pass reduces max|dz| itself -- the consumers below, weight and data gradient, read the slot)
-    launch_gn_backward(e->zbuf[ci], c.cout, g, ldg, e->G_(ci), e->gn_stats[ci], e->gn_partial, B, Ho * Wo, c.cout,
-                       e->s, twrite_fused(e, 1, e->zbuf[ci], true));
-    g = e->zbuf[ci]; ldg = c.cout; gkey = g;
+    launch_gn_backward(e->zbuf[ci]->p, c.cout, gv.ptr(), gv.ld(), e->G_(ci), e->gn_stats[ci], e->gn_partial, B, Ho * Wo, c.cout,
+                       e->s, twrite_fused(e, e->zbuf[ci]).slot);
+    gv = View(e->zbuf[ci]);
   }
-  WgLaunch go = wino_on(e, ci, B, Ho, Wo) ? wgrad_wino(e, ci, g, ldg, x, ldx, Hin, Win, B, Ho, Wo)
-                                         : wgrad_direct(e, ci, g, ldg, x, ldx, Hin, Win, B, Ho, Wo, gkey, xkey);
+  WgLaunch go = wino_on(e, ci, B, Ho, Wo) ? wgrad_wino(e, ci, gv, xv, B, Ho, Wo) : wgrad_direct(e, ci, gv, xv, B, Ho, Wo);
   if (!go) return;
   side_enqueue(e, std::move(go));
   if (e->s2 && (int)e->side_q.size() >= (B == 1 ? EOSVOS_SIDE_BATCH : 1)) side_flush(e);
@@ -1357,8 +1329,8 @@ int flush_updates(eosvos_engine* e, int B, bool update, bool accumulate, int par
   // the backward pass (main stream) reads only those.
   unsigned* amax_w = nullptr;
   if (update) {
-    for (auto& kv : e->wino_us_valid)
-      if (e->train_from == 0 || kv.first >= lo) kv.second = 0;     // a frozen conv keeps its transformed weights
+    for (int ci = 0; ci < (int)e->wino.size(); ++ci)
+      if (e->train_from == 0 || ci >= lo) e->wino[ci].us_valid = false;     // a frozen conv keeps its transformed weights
     if (h3_mode() && !amax_init(e) && e->w_amax_valid) {
       amax_w = amax_slot(e, AM_W, 0);
       amax_zero(amax_w + lo, (size_t)(hi - lo), stream);
@@ -1376,7 +1348,7 @@ int flush_updates(eosvos_engine* e, int B, bool update, bool accumulate, int par
 // + 3 x 9 taps x 256 (dilated 3x3, taps that fall into the padding for a whole tile skipped), no accumulate
 // read-modify-write between the branches, one fix-up pass.  Returns false when this engine / mode has to run them one by
 // one (GroupNorm mode: the gradients w.r.t. the raw conv outputs live in separate buffers; fp32-MFMA mode: no such kernel).
-bool aspp_dgrad_merged(eosvos_engine* e, int B, float* g_l4, const float* l4) {
+bool aspp_dgrad_merged(eosvos_engine* e, int B, Tensor* g_l4, const Tensor* l4) {
   const Topo& t = e->t;
   if (e->gn() || !conv_multi_supported() || e->force_algo != 0) return false;
   for (int i = 0; i < 4; ++i) {
@@ -1388,13 +1360,13 @@ bool aspp_dgrad_merged(eosvos_engine* e, int B, float* g_l4, const float* l4) {
   ConvArgs a;
   memset(&a, 0, sizeof(a));
   a.wg_budget = e->wg_budget;
-  a.x = e->g_cat; a.w = e->W_(t.aspp[0]); a.y = g_l4; a.ws = e->ws_conv;
-  a.B = B; a.Hi = e->h16; a.Wi = e->w16; a.ldx = 1280; a.Kc = 256;
+  a.x = e->g_cat->p; a.w = e->W_(t.aspp[0]); a.y = g_l4->p; a.ws = e->ws_conv;
+  a.B = B; a.Hi = e->h16; a.Wi = e->w16; a.ldx = e->g_cat->C; a.Kc = 256;
   a.Ho = e->h16; a.Wo = e->w16; a.N = c0.cin; a.ldy = c0.cin; a.KH = a.KW = 1;
   a.mul = 1; a.off0 = 0; a.kstep = 0; a.upshift = 0;
   a.M = B * e->h16 * e->w16; a.wN = 256; a.wK = c0.cin; a.kmajor = 1;
   a.kscale = e->A_(t.aspp[0]);
-  a.mask8 = e->m8(l4); a.ldm8 = c0.cin / 4; a.mask_c0 = 0; a.accum = 1;
+  a.mask8 = l4->mask; a.ldm8 = View(g_l4).ldmask(); a.mask_c0 = 0; a.accum = 1;
   if (!a.mask8) return false;                      // (conv_dgrad reports the missing mask bytes)
   a.nseg = 4;
   a.w_floats = 0;
@@ -1424,38 +1396,33 @@ bool aspp_dgrad_merged(eosvos_engine* e, int B, float* g_l4, const float* l4) {
   if (h3_mode()) {
     if (amax_init(e)) return false;
     amax_weights(e, e->s);
-    a.amax_x = tlookup(e, 1, e->g_cat);
-    if (!a.amax_x) a.amax_x = amax_get(e, AM_G, t.aspp[0], e->g_cat, (long)B * e->h16 * e->w16, 1280, 1280, e->s);
+    a.amax_x = tlookup(e, *e->g_cat);
+    if (!a.amax_x) a.amax_x = amax_get(e, AM_G, t.aspp[0], e->g_cat->p, (long)B * e->h16 * e->w16, e->g_cat->C, e->g_cat->C, e->s);
     for (int i = 0; i < 4; ++i) {
       a.seg_amax_w[i] = amax_slot(e, AM_W, t.aspp[i]);
       a.seg_amax_ks[i] = amax_ks(e, t.aspp[i], e->s);
     }
-    a.amax_y = twrite_fused(e, 1, g_l4, true);         // every element of g_l4 is rewritten (accumulating the pooling branch's broadcast)
+    a.amax_y = twrite_fused(e, g_l4).slot;         // every element of g_l4 is rewritten (accumulating the pooling branch's broadcast)
   }
-  double fl = 0;
-  for (int i = 0; i < 4; ++i) fl += 2.0 * a.M * a.N * t.convs[t.aspp[i]].T() * 256.0;
   if (trace_on())
     trace_line("dgrad", t.aspp[0], a.M, a.N, (long)(a.total_units * 32 / (((a.M + 127) / 128) * ((a.N + 127) / 128))), conv_plan(a),
                2.0 * 128 * 128 * 32 * (double)a.total_units);
-  (void)fl;
-  pair_attach(e, 1, g_l4, g_l4, true, a);
+  pair_attach(e, g_l4, a);
   launch_conv(a, e->s);
-  pair_covered(e, 1, g_l4, a);
+  pair_covered(e, *g_l4, a);
   return true;
 }
 
 // g_l4 (holding the pooling branch's broadcast) += the four ASPP branches' data gradients, masked with the ReLU mask of l4: the
 // K-concatenated launch, or -- where it declines, or `force_fallback` (parity tests) -- one accumulating conv_dgrad per branch,
 // the mask applied by the last.  *merged (may be null): which of the two ran.
-int aspp_dgrad(eosvos_engine* e, int B, float* g_l4, const float* l4, bool force_fallback, bool* merged) {
+int aspp_dgrad(eosvos_engine* e, int B, Tensor* g_l4, const Tensor* l4, bool force_fallback, bool* merged) {
   const Topo& t = e->t;
   const bool m = !force_fallback && aspp_dgrad_merged(e, B, g_l4, l4);
   if (merged) *merged = m;
   if (m) return 0;
   for (int i = 0; i < 4; ++i)
-    if (conv_dgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, e->h16, e->w16, g_l4, 2048, B, true, i == 3 ? l4 : nullptr, 0, nullptr, 0,
-                   e->g_cat))
-      return 1;
+    if (conv_dgrad(e, t.aspp[i], View(e->g_cat, 256 * i, 256), g_l4, B, Opt().accum().mask(i == 3 ? l4 : nullptr))) return 1;
   return 0;
 }
 
@@ -1467,8 +1434,7 @@ void plans_match_mode(eosvos_engine* e) {
   e->plan_mode = mode;
   e->wg_plans.clear();                             // (the device tables stay allocated until the engine goes: a few KB per switch)
   for (auto& tab : e->upd_tab) tab = nullptr;
-  e->wino_v_batch.clear();                         // Winograd selection differs per mode: V / dM of the other mode are stale
-  for (auto& kv : e->wino_dm_batch) kv.second = 0;
+  for (auto& w : e->wino) w.v_batch = w.dm_batch = 0;      // Winograd selection differs per mode: V / dM of the other mode are stale
 }
 
 int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }
@@ -1622,11 +1588,24 @@ int eosvos_create_ex(eosvos_engine** out, int arch, int norm_mode, int height, i
   HIPOK(hipMemset(e->Wp, 0, (size_t)t.nparam * 4));
   HIPOK(hipMemset(e->Winit, 0, (size_t)t.nparam * 4));
   HIPOK(hipMemset(e->lr, 0, (size_t)t.nlr * 4));
-  const int64_t n2 = (int64_t)B * e->h2 * e->w2, n4 = (int64_t)B * e->h4 * e->w4;
-  const int64_t n16 = (int64_t)B * e->h16 * e->w16;
-  ALLOC(e->c1, n2 * 64); ALLOC(e->g_c1, n2 * 64);
-  ALLOC(e->p1, n4 * 64); ALLOC(e->g_p1, n4 * 64);
-  { float* t8; ALLOC(t8, (n4 * 64 + 3) / 4); e->p1idx = (uint8_t*)t8; }
+  // a tensor of the engine, [B][h][w][c]; `masked`: with ReLU mask bytes (an activation that a data gradient masks with; in
+  // the GroupNorm mode the apply pass that writes y = relu(gn(z) (+ res)) writes them), one byte per 4 floats
+  auto new_tensor = [&](int h, int w, int c, int phase, bool masked) {
+    Tensor* x = e->ts.add(nullptr, h, w, c, phase);
+    x->p = e->falloc(x->floats(B));
+    if (x->p && masked) x->mask = (uint8_t*)e->falloc((x->floats(B) / 4 + 3) / 4);
+    return x;
+  };
+#define TENSOR(ptr, h, w, c, phase, masked)                                                 \
+  do {                                                                                      \
+    ptr = new_tensor(h, w, c, phase, masked);                                               \
+    if (!ptr->p) { eosvos_destroy(e); return fail("hipMalloc " #ptr); }                     \
+    if (masked && !ptr->mask) { eosvos_destroy(e); return fail("hipMalloc ReLU mask bytes"); } \
+  } while (0)
+  const int64_t n4 = (int64_t)B * e->h4 * e->w4;
+  TENSOR(e->c1, e->h2, e->w2, 64, 0, false); TENSOR(e->g_c1, e->h2, e->w2, 64, 1, false);
+  TENSOR(e->p1, e->h4, e->w4, 64, 0, false); TENSOR(e->g_p1, e->h4, e->w4, 64, 1, false);
+  { float* t8; ALLOC(t8, (e->p1->floats(B) + 3) / 4); e->p1idx = (uint8_t*)t8; }
 
   int64_t wsc = conv_ws_floats(), wsw = 0;
   e->zbuf.assign(t.convs.size(), nullptr);
@@ -1634,9 +1613,9 @@ int eosvos_create_ex(eosvos_engine** out, int arch, int norm_mode, int height, i
   if (e->gn()) {
     e->gn_sums = e->falloc((int64_t)B * 32);
     e->gn_partial = e->falloc((int64_t)gn_partial_floats(B));
-    e->zbuf[0] = e->falloc((int64_t)B * e->h2 * e->w2 * 64);
+    e->zbuf[0] = new_tensor(e->h2, e->w2, 64, 1, false);
     e->gn_stats[0] = e->falloc((int64_t)B * 32);
-    e->zbuf[t.pool] = e->falloc((int64_t)B * 256);
+    e->zbuf[t.pool] = new_tensor(1, 1, 256, 1, false);
     e->gn_stats[t.pool] = e->falloc((int64_t)B * 32);
   }
   e->ws_off.assign(t.convs.size(), 0);
@@ -1646,12 +1625,11 @@ int eosvos_create_ex(eosvos_engine** out, int arch, int norm_mode, int height, i
   std::vector<int64_t> slabs(t.convs.size(), 0);   // floats of slab space per conv (max over batch sizes)
   e->conv_hin.assign(t.convs.size(), 0);
   e->conv_win.assign(t.convs.size(), 0);
+  e->wino.assign(t.convs.size(), eosvos_engine::WinoRec());
   auto track = [&](int ci, int Hin, int Win) {
     const ConvL& c = t.convs[ci];
     e->conv_hin[ci] = Hin; e->conv_win[ci] = Win;
     const int Ho = conv_out(Hin, c.k, c.stride, c.dil, c.pad), Wo = conv_out(Win, c.k, c.stride, c.dil, c.pad);
-    const int Mf = B * Ho * Wo, Md = B * Hin * Win;
-    (void)Md;
     for (int b = 1; b <= B; ++b)
       for (int wb = 0; wb <= 512; wb += 64)          // every budget eosvos_set_wg_budget accepts
         slabs[ci] = max64(slabs[ci], (int64_t)wgrad_max_splits(b * Ho * Wo, c.cout, c.cin, c.T(), wb) * c.wsize());
@@ -1665,71 +1643,49 @@ int eosvos_create_ex(eosvos_engine** out, int arch, int norm_mode, int height, i
       }
       const WinoGeom gm = wino_geom(e, c, B, Ho, Wo);
       const int64_t prow = gm.prow, np = gm.np;
-      e->wino_V[ci] = e->falloc(np * prow * c.cin);
-      e->wino_U[ci] = e->falloc(np * c.cout * c.cin);
-      e->wino_Us[ci] = e->falloc(np * c.cout * c.cin);
-      e->wino_us_valid[ci] = 0;
-      e->wino_dM[ci] = e->falloc(np * prow * c.cout);
-      e->wino_v_batch[ci] = 0; e->wino_dm_batch[ci] = 0;
+      auto& w = e->wino[ci];
+      w.V = e->falloc(np * prow * c.cin);
+      w.U = e->falloc(np * c.cout * c.cin);
+      w.Us = e->falloc(np * c.cout * c.cin);
+      w.dM = e->falloc(np * prow * c.cout);
       e->wino_m_n = max64(e->wino_m_n, np * prow * max64(c.cout, c.cin));
     }
-    (void)Mf;
     if (e->gn() && c.norm) {
-      e->zbuf[ci] = e->falloc((int64_t)B * Ho * Wo * c.cout);
+      e->zbuf[ci] = new_tensor(Ho, Wo, c.cout, 1, false);
       e->gn_stats[ci] = e->falloc((int64_t)B * 32);
     }
   };
   // bottleneck buffers
-  int Hc = e->h4, Wc = e->w4, Cc = 64;
-  const float* xin = e->p1;
-  float* gxin = e->g_p1;
+  eosvos_engine::BlkBuf bf;
+  bf.out = e->p1; bf.g_out = e->g_p1;
   for (size_t i = 0; i < t.blocks.size(); ++i) {
     const Block& b = t.blocks[i];
     const ConvL &c1 = t.convs[b.c1], &c2 = t.convs[b.c2], &c3 = t.convs[b.c3];
-    eosvos_engine::BlkBuf bf;
-    bf.Hi = Hc; bf.Wi = Wc; bf.Cin = Cc; bf.xin = xin; bf.g_xin = gxin;
-    bf.Hm = conv_out(Hc, 1, c1.stride, 1, 0); bf.Wm = conv_out(Wc, 1, c1.stride, 1, 0);
-    bf.Ho = conv_out(bf.Hm, 3, c2.stride, c2.dil, c2.pad); bf.Wo = conv_out(bf.Wm, 3, c2.stride, c2.dil, c2.pad);
-    const int64_t nm = (int64_t)B * bf.Hm * bf.Wm, no = (int64_t)B * bf.Ho * bf.Wo;
-    ALLOC(bf.t1, nm * c1.cout); ALLOC(bf.g_t1, nm * c1.cout);
-    ALLOC(bf.t2, no * c2.cout); ALLOC(bf.g_t2, no * c2.cout);
-    ALLOC(bf.out, no * c3.cout); ALLOC(bf.g_out, no * c3.cout);
+    bf.xin = bf.out; bf.g_xin = bf.g_out;
+    const int Hm = conv_out(bf.xin->H, 1, c1.stride, 1, 0), Wm = conv_out(bf.xin->W, 1, c1.stride, 1, 0);
+    const int Ho = conv_out(Hm, 3, c2.stride, c2.dil, c2.pad), Wo = conv_out(Wm, 3, c2.stride, c2.dil, c2.pad);
+    TENSOR(bf.t1, Hm, Wm, c1.cout, 0, true); TENSOR(bf.g_t1, Hm, Wm, c1.cout, 1, false);
+    TENSOR(bf.t2, Ho, Wo, c2.cout, 0, true); TENSOR(bf.g_t2, Ho, Wo, c2.cout, 1, false);
+    TENSOR(bf.out, Ho, Wo, c3.cout, 0, true); TENSOR(bf.g_out, Ho, Wo, c3.cout, 1, false);
     bf.dsb = nullptr;
-    if (b.ds >= 0) ALLOC(bf.dsb, no * c3.cout);
-    track(b.c1, Hc, Wc); track(b.c2, bf.Hm, bf.Wm); track(b.c3, bf.Ho, bf.Wo);
-    if (b.ds >= 0) track(b.ds, Hc, Wc);
+    if (b.ds >= 0) TENSOR(bf.dsb, Ho, Wo, c3.cout, 0, false);
+    track(b.c1, bf.xin->H, bf.xin->W); track(b.c2, Hm, Wm); track(b.c3, Ho, Wo);
+    if (b.ds >= 0) track(b.ds, bf.xin->H, bf.xin->W);
     e->bb.push_back(bf);
-    Hc = bf.Ho; Wc = bf.Wo; Cc = c3.cout; xin = bf.out; gxin = bf.g_out;
   }
-  if (Hc != e->h16 || Wc != e->w16) { eosvos_destroy(e); return fail("internal: stride-16 geometry mismatch"); }
-  ALLOC(e->cat, n16 * 1280); ALLOC(e->g_cat, n16 * 1280);
+  if (bf.out->H != e->h16 || bf.out->W != e->w16) { eosvos_destroy(e); return fail("internal: stride-16 geometry mismatch"); }
+  TENSOR(e->cat, e->h16, e->w16, 1280, 0, true); TENSOR(e->g_cat, e->h16, e->w16, 1280, 1, false);   // 4 ASPP branches + the pooling branch
   ALLOC(e->vec, (int64_t)B * 2048); ALLOC(e->gvec, (int64_t)B * 2048);
   ALLOC(e->poolout, (int64_t)B * 256); ALLOC(e->gp, (int64_t)B * 256);
   ALLOC(e->colscratch, (int64_t)B * 64 * 2048);      // COLSUM_CHUNKS partial sums
-  ALLOC(e->proj, n16 * 256); ALLOC(e->g_proj, n16 * 256);
-  ALLOC(e->dcat, n4 * 304); ALLOC(e->g_dcat, n4 * 304);
-  ALLOC(e->d1, n4 * 256); ALLOC(e->g_d1, n4 * 256);
-  ALLOC(e->d2, n4 * 256); ALLOC(e->g_d2, n4 * 256);
+  TENSOR(e->proj, e->h16, e->w16, 256, 0, true); TENSOR(e->g_proj, e->h16, e->w16, 256, 1, false);
+  TENSOR(e->dcat, e->h4, e->w4, 304, 0, true); TENSOR(e->g_dcat, e->h4, e->w4, 304, 1, false);       // upsampled projection (256) + decoder.conv1 (48)
+  TENSOR(e->d1, e->h4, e->w4, 256, 0, true); TENSOR(e->g_d1, e->h4, e->w4, 256, 1, false);
+  TENSOR(e->d2, e->h4, e->w4, 256, 0, false); TENSOR(e->g_d2, e->h4, e->w4, 256, 1, false);
   ALLOC(e->lowlog, n4); ALLOC(e->g_low, n4);
   ALLOC(e->logits, (int64_t)B * H * W); ALLOC(e->dlogits, (int64_t)B * H * W);
   ALLOC(e->loss_dev, 4); ALLOC(e->bce_partial, LOSS_PARTIAL_FLOATS);
-  {                                               // ReLU mask bytes of the tensors the data gradients read as masks
-    // (GroupNorm mode, round 5: the apply pass that writes y = relu(gn(z) (+ res)) writes the bytes)
-    auto m8alloc = [&](const float* key, int64_t floats) {     // one byte per 4 floats
-      float* p = e->falloc((floats / 4 + 3) / 4);
-      if (p) e->mask8[key] = (uint8_t*)p;
-      return p != nullptr;
-    };
-    bool ok = true;
-    for (size_t i = 0; i < t.blocks.size(); ++i) {
-      const Block& b = t.blocks[i];
-      const auto& f = e->bb[i];
-      const int64_t nm = (int64_t)B * f.Hm * f.Wm, no = (int64_t)B * f.Ho * f.Wo;
-      ok = ok && m8alloc(f.t1, nm * t.convs[b.c1].cout) && m8alloc(f.t2, no * t.convs[b.c2].cout) && m8alloc(f.out, no * t.convs[b.c3].cout);
-    }
-    ok = ok && m8alloc(e->cat, n16 * 1280) && m8alloc(e->proj, n16 * 256) && m8alloc(e->dcat, n4 * 304) && m8alloc(e->d1, n4 * 256);
-    if (!ok) { eosvos_destroy(e); return fail("hipMalloc ReLU mask bytes"); }
-  }
+#undef TENSOR
   for (int i = 0; i < 4; ++i) track(t.aspp[i], e->h16, e->w16);
   track(t.project, e->h16, e->w16);
   if (t.v3) {
@@ -2060,7 +2016,8 @@ static int forward_impl(eosvos_engine* e, const float* images, int B, bool mirro
   if (h3_mode()) {
     amax_weights(e, s);
     bool stale = false, fresh = false;
-    for (auto& kv : e->wino_us_valid) { stale |= !kv.second; fresh |= kv.second != 0; }
+    for (const auto& w : e->wino)
+      if (w.V) { stale |= !w.us_valid; fresh |= w.us_valid; }
     if (stale && !fresh) {                          // every Winograd-domain weight is remade by this forward
       amax_zero(amax_slot(e, AM_U, 0), 2 * t.convs.size(), s);
       e->us_zero_epoch = e->fwd_epoch;
@@ -2074,13 +2031,13 @@ static int forward_impl(eosvos_engine* e, const float* images, int B, bool mirro
     else launch_stem_fwd(e->xpad, e->W_(0), a, b, y, B, e->H, e->W, e->h2, e->w2, s);
   };
   if (e->gn()) {
-    stem_fwd(nullptr, nullptr, e->zbuf[0]);
-    launch_gn_forward(e->zbuf[0], 64, e->G_(0), e->nb, nullptr, 0, e->c1, 64, e->gn_stats[0], e->gn_partial, B, e->h2 * e->w2, 64,
+    stem_fwd(nullptr, nullptr, e->zbuf[0]->p);
+    launch_gn_forward(e->zbuf[0]->p, 64, e->G_(0), e->nb, nullptr, 0, e->c1->p, 64, e->gn_stats[0], e->gn_partial, B, e->h2 * e->w2, 64,
                       1e-5f, 1, s);
   } else {
-    stem_fwd(e->A_(0), e->B_(0), e->c1);
+    stem_fwd(e->A_(0), e->B_(0), e->c1->p);
   }
-  launch_maxpool_fwd(e->c1, e->p1, e->p1idx, B, e->h2, e->w2, 64, e->h4, e->w4, s, twrite_fused(e, 0, e->p1, true));
+  launch_maxpool_fwd(e->c1->p, e->p1->p, e->p1idx, B, e->h2, e->w2, 64, e->h4, e->w4, s, twrite_fused(e, e->p1).slot);
   // independent forward branches go to the side stream (frozen-BN mode; the GroupNorm kernels share scratch)
   const bool fside = e->s2 != nullptr && !e->gn();
   auto fork = [&](int ci) {      // the side stream continues from this point of the main stream
@@ -2091,9 +2048,8 @@ static int forward_impl(eosvos_engine* e, const float* images, int B, bool mirro
     // Winograd-domain weights depend on the weights only: all of them are made on the side stream now, beside the stem
     // and layer1..3, instead of in front of each Winograd conv on the critical path
     bool any = false;
-    for (auto& kv : e->wino_us_valid) {
-      const int ci = kv.first;
-      if (kv.second || ci >= (int)e->conv_hin.size() || !e->conv_hin[ci]) continue;
+    for (int ci = 0; ci < (int)e->wino.size(); ++ci) {      // (ascending: the order fixes the side stream's launch sequence)
+      if (!e->wino[ci].V || e->wino[ci].us_valid || ci >= (int)e->conv_hin.size() || !e->conv_hin[ci]) continue;
       const ConvL& c = t.convs[ci];
       const int Ho = conv_out(e->conv_hin[ci], c.k, c.stride, c.dil, c.pad), Wo = conv_out(e->conv_win[ci], c.k, c.stride, c.dil, c.pad);
       if (!wino_on(e, ci, B, Ho, Wo)) continue;
@@ -2102,69 +2058,67 @@ static int forward_impl(eosvos_engine* e, const float* images, int B, bool mirro
     }
     if (any) { (void)hipEventRecord(e->ev_wino_w, e->s2); e->wino_w_wait = true; }
   }
+  const View dcat_low(e->dcat, 256, 48);      // decoder.conv1's slice of the decoder concat, behind the upsampled projection
   for (size_t i = 0; i < t.blocks.size(); ++i) {
     const Block& b = t.blocks[i];
     auto& f = e->bb[i];
-    const int cmid = t.convs[b.c1].cout, cout = t.convs[b.c3].cout;
-    const float* res = f.xin;
-    int ldres = f.Cin;
     if (b.ds >= 0) {               // the projection shortcut only needs the block input: beside conv1 / conv2
       if (fside) fork(b.ds);
-      conv_fwd(e, b.ds, f.xin, f.Cin, f.Hi, f.Wi, f.dsb, cout, B, nullptr, 0, false, fside);
+      conv_fwd(e, b.ds, f.xin, f.dsb, B, Opt().side(fside));
       if (fside) (void)hipEventRecord(e->ev[b.c3], e->s2);
-      res = f.dsb; ldres = cout;
     }
-    conv_fwd(e, b.c1, f.xin, f.Cin, f.Hi, f.Wi, f.t1, cmid, B, nullptr, 0, true);
-    conv_fwd(e, b.c2, f.t1, cmid, f.Hm, f.Wm, f.t2, cmid, B, nullptr, 0, true);
+    conv_fwd(e, b.c1, f.xin, f.t1, B, Opt().relu());
+    conv_fwd(e, b.c2, f.t1, f.t2, B, Opt().relu());
     if (b.ds >= 0 && fside) (void)hipStreamWaitEvent(s, e->ev[b.c3], 0);
-    conv_fwd(e, b.c3, f.t2, cmid, f.Ho, f.Wo, f.out, cout, B, res, ldres, true);
+    conv_fwd(e, b.c3, f.t2, f.out, B, Opt().relu().add(b.ds >= 0 ? f.dsb : f.xin));
     if ((int)i == t.layer1_last_block && fside && !t.v3) {
       // decoder.conv1 reads the layer1 feature only: it runs beside layer2..4 + ASPP
       fork(t.dec1);
-      conv_fwd(e, t.dec1, f.out, 256, e->h4, e->w4, e->dcat + 256, 304, B, nullptr, 0, true, true, nullptr, e->dcat);
+      conv_fwd(e, t.dec1, f.out, dcat_low, B, Opt().relu().side());
       (void)hipEventRecord(e->ev[t.dec_a], e->s2);
     }
   }
-  const float* l4 = e->bb.back().out;
+  Tensor* const l4 = e->bb.back().out;
   const int P16 = e->h16 * e->w16;
   // The image-pooling branch (column sums, GEMV, broadcast, absmax: five small latency-bound launches) reads layer4's output
   // only: with a side stream it runs there, beside the four ASPP convs, and joins in front of the projection.
   hipStream_t ps = fside ? e->s2 : s;
   if (fside) fork(t.pool);
   auto pool_branch = [&]() {
-    launch_colsum(l4, 2048, e->vec, B, P16, 2048, 1.0f / (float)P16, e->colscratch, ps);
+    launch_colsum(l4->p, l4->C, e->vec, B, P16, 2048, 1.0f / (float)P16, e->colscratch, ps);
     if (e->gn()) {
-      launch_gemv_fwd(e->W_(t.pool), e->vec, nullptr, nullptr, e->zbuf[t.pool], B, 256, 2048, ps);
-      launch_gn_forward(e->zbuf[t.pool], 256, e->G_(t.pool), e->nb + t.convs[t.pool].noff, nullptr, 0, e->poolout, 256,
+      launch_gemv_fwd(e->W_(t.pool), e->vec, nullptr, nullptr, e->zbuf[t.pool]->p, B, 256, 2048, ps);
+      launch_gn_forward(e->zbuf[t.pool]->p, 256, e->G_(t.pool), e->nb + t.convs[t.pool].noff, nullptr, 0, e->poolout, 256,
                         e->gn_stats[t.pool], e->gn_partial, B, 1, 256, 1e-5f, 1, ps);
     } else {
       launch_gemv_fwd(e->W_(t.pool), e->vec, e->A_(t.pool), e->B_(t.pool), e->poolout, B, 256, 2048, ps);
     }
-    launch_bcast_pixels(e->poolout, e->cat + 1024, 1280, B, P16, 256, 1.f, ps, e->m8w(e->cat) ? e->m8w(e->cat) + 1024 / 4 : nullptr, 1280 / 4);
+    const View cat_pool(e->cat, 1024, 256);      // the pooling branch's slice of the ASPP concat, behind the four conv branches
+    launch_bcast_pixels(e->poolout, cat_pool.ptr(), cat_pool.ld(), B, P16, 256, 1.f, ps, e->fwd_masks ? cat_pool.mask_to_write() : nullptr,
+                        cat_pool.ldmask());
   };
   if (fside) pool_branch();
   for (int i = 0; i < 4; ++i)
-    conv_fwd(e, t.aspp[i], l4, 2048, e->h16, e->w16, e->cat + 256 * i, 1280, B, nullptr, 0, true, false, nullptr, e->cat);
+    conv_fwd(e, t.aspp[i], l4, View(e->cat, 256 * i, 256), B, Opt().relu());
   if (!fside) pool_branch();
   if (h3_mode() && !amax_init(e)) {
     // cat = 4 conv outputs (their epilogues fed the tensor's slot) + the broadcast pooling branch (its B x 256 values here)
-    if (unsigned* cs = tslot(e, 0, e->cat)) { launch_absmax(e->poolout, 1, B * 256, B * 256, cs, ps); tmark_valid(e, 0, e->cat); }
+    if (unsigned* cs = tslot(e, *e->cat)) { launch_absmax(e->poolout, 1, B * 256, B * 256, cs, ps); tmark_valid(*e->cat); }
   }
   if (fside) { (void)hipEventRecord(e->ev[t.pool], e->s2); (void)hipStreamWaitEvent(s, e->ev[t.pool], 0); }
-  conv_fwd(e, t.project, e->cat, 1280, e->h16, e->w16, e->proj, 256, B, nullptr, 0, true);
+  conv_fwd(e, t.project, e->cat, e->proj, B, Opt().relu());
   const ConvL& lc = t.convs[t.last];
   if (t.v3) {
     // DeepLabHead after ASPP: 3x3 conv + norm + ReLU, 1x1 classifier, logits resized from the ASPP map (deeplabv3.py:13)
-    conv_fwd(e, t.head3, e->proj, 256, e->h16, e->w16, e->d1, 256, B, nullptr, 0, true);
-    launch_last_fwd(e->d1, e->W_(t.last), e->W_(t.last) + lc.wsize(), e->lowlog, (int64_t)B * e->h16 * e->w16, 256, s);
+    conv_fwd(e, t.head3, e->proj, e->d1, B, Opt().relu());
+    launch_last_fwd(e->d1->p, e->W_(t.last), e->W_(t.last) + lc.wsize(), e->lowlog, (int64_t)B * e->h16 * e->w16, 256, s);
   } else {
-    const float* low = e->bb[t.layer1_last_block].out;
     if (fside) (void)hipStreamWaitEvent(s, e->ev[t.dec_a], 0);
-    else conv_fwd(e, t.dec1, low, 256, e->h4, e->w4, e->dcat + 256, 304, B, nullptr, 0, true, false, nullptr, e->dcat);
-    launch_resize_fwd(e->proj, 256, e->dcat, 304, B, 256, e->up_h, e->up_w, s);
-    conv_fwd(e, t.dec_a, e->dcat, 304, e->h4, e->w4, e->d1, 256, B, nullptr, 0, true);
-    conv_fwd(e, t.dec_b, e->d1, 256, e->h4, e->w4, e->d2, 256, B, nullptr, 0, true);
-    launch_last_fwd(e->d2, e->W_(t.last), e->W_(t.last) + lc.wsize(), e->lowlog, (int64_t)B * e->h4 * e->w4, 256, s);
+    else conv_fwd(e, t.dec1, e->bb[t.layer1_last_block].out, dcat_low, B, Opt().relu());
+    launch_resize_fwd(e->proj->p, e->proj->C, e->dcat->p, e->dcat->C, B, 256, e->up_h, e->up_w, s);
+    conv_fwd(e, t.dec_a, e->dcat, e->d1, B, Opt().relu());
+    conv_fwd(e, t.dec_b, e->d1, e->d2, B, Opt().relu());
+    launch_last_fwd(e->d2->p, e->W_(t.last), e->W_(t.last) + lc.wsize(), e->lowlog, (int64_t)B * e->h4 * e->w4, 256, s);
   }
   launch_resize_fwd(e->lowlog, 1, e->logits, 1, B, 1, e->fin_h, e->fin_w, s);
   e->lastB = B;
@@ -2201,65 +2155,67 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     // classifier conv (Cout = 1) and the head's 3x3 conv, both on the ASPP map; the projection output is ReLU-masked
     const int64_t PA = (int64_t)B * e->h16 * e->w16;
     const int chunks = last_bwd_chunks(PA);
-    launch_last_bwd(e->d1, e->W_(t.last), e->g_low, e->g_d1, e->ws_wg + e->ws_off[t.last], PA, 256, chunks, s);
-    twrite_plain(e, 1, e->g_d1);
+    launch_last_bwd(e->d1->p, e->W_(t.last), e->g_low, e->g_d1->p, e->ws_wg + e->ws_off[t.last], PA, 256, chunks, s);
+    twrite_plain(*e->g_d1);
     e->upd_splits[t.last] = chunks;
-    conv_wgrad(e, t.head3, e->g_d1, 256, e->proj, 256, e->h16, e->w16, B);
-    if (conv_dgrad(e, t.head3, e->g_d1, 256, e->h16, e->w16, e->g_proj, 256, B, false, e->proj, 0)) return 1;
+    conv_wgrad(e, t.head3, e->g_d1, e->proj, B);
+    if (conv_dgrad(e, t.head3, e->g_d1, e->g_proj, B, Opt().mask(e->proj))) return 1;
   } else {
   // classifier conv (Cout = 1)
   {
     const int chunks = last_bwd_chunks(P4);
-    launch_last_bwd(e->d2, e->W_(t.last), e->g_low, e->g_d2, e->ws_wg + e->ws_off[t.last], P4, 256, chunks, s);
-    twrite_plain(e, 1, e->g_d2);
+    launch_last_bwd(e->d2->p, e->W_(t.last), e->g_low, e->g_d2->p, e->ws_wg + e->ws_off[t.last], P4, 256, chunks, s);
+    twrite_plain(*e->g_d2);
     e->upd_splits[t.last] = chunks;
   }
   // decoder 3x3 convs
   {
-    conv_wgrad(e, t.dec_b, e->g_d2, 256, e->d1, 256, e->h4, e->w4, B);
-    if (conv_dgrad(e, t.dec_b, e->g_d2, 256, e->h4, e->w4, e->g_d1, 256, B, false, e->d1, 0)) return 1;
-    conv_wgrad(e, t.dec_a, e->g_d1, 256, e->dcat, 304, e->h4, e->w4, B);
+    conv_wgrad(e, t.dec_b, e->g_d2, e->d1, B);
+    if (conv_dgrad(e, t.dec_b, e->g_d2, e->g_d1, B, Opt().mask(e->d1))) return 1;
+    conv_wgrad(e, t.dec_a, e->g_d1, e->dcat, B);
     // channels [0,256) of dcat are the (unclamped) upsampled ASPP output: no ReLU mask there
-    if (conv_dgrad(e, t.dec_a, e->g_d1, 256, e->h4, e->w4, e->g_dcat, 304, B, false, e->dcat, 256)) return 1;
+    if (conv_dgrad(e, t.dec_a, e->g_d1, e->g_dcat, B, Opt().mask(e->dcat, 256))) return 1;
   }
   // decoder.conv1 on the low-level feature: raw gradient into g_out of layer1's last block
   {
-    float* g_low_feat = e->bb[t.layer1_last_block].g_out;
-    const float* low = e->bb[t.layer1_last_block].out;
-    conv_wgrad(e, t.dec1, e->g_dcat + 256, 304, low, 256, e->h4, e->w4, B, e->g_dcat);
-    if (!frozen && conv_dgrad(e, t.dec1, e->g_dcat + 256, 304, e->h4, e->w4, g_low_feat, 256, B, false, nullptr, 0, nullptr, 0, e->g_dcat))
-      return 1;
+    const auto& low = e->bb[t.layer1_last_block];
+    const View g_dcat_low(e->g_dcat, 256, 48);
+    conv_wgrad(e, t.dec1, g_dcat_low, low.out, B);
+    if (!frozen && conv_dgrad(e, t.dec1, g_dcat_low, low.g_out, B)) return 1;
   }
   // decoder upsample backward (+ ReLU mask of the projection output)
-  if (!e->m8(e->proj)) return fail("internal: the projection output has no ReLU mask bytes");
-  launch_resize_bwd(e->g_dcat, 304, e->g_proj, 256, e->m8(e->proj), 256 / 4, B, 256, e->up_h, e->up_w, s, twrite_fused(e, 1, e->g_proj, true));
+  const View proj(e->proj);
+  if (!proj.mask()) return fail("internal: the projection output has no ReLU mask bytes");
+  launch_resize_bwd(e->g_dcat->p, e->g_dcat->C, e->g_proj->p, e->g_proj->C, proj.mask(), proj.ldmask(), B, 256, e->up_h, e->up_w, s,
+                    twrite_fused(e, e->g_proj).slot);
   }
   // ASPP projection
   {
-    conv_wgrad(e, t.project, e->g_proj, 256, e->cat, 1280, e->h16, e->w16, B);
-    if (conv_dgrad(e, t.project, e->g_proj, 256, e->h16, e->w16, e->g_cat, 1280, B, false, e->cat, 0)) return 1;
+    conv_wgrad(e, t.project, e->g_proj, e->cat, B);
+    if (conv_dgrad(e, t.project, e->g_proj, e->g_cat, B, Opt().mask(e->cat))) return 1;
   }
-  float* g_l4 = e->bb.back().g_out;
-  const float* l4 = e->bb.back().out;
+  Tensor* const g_l4 = e->bb.back().g_out;
+  Tensor* const l4 = e->bb.back().out;
   // image-pooling branch: gp = sum_p g_cat[:,1024:1280]; g_l4 starts as the broadcast of its input gradient
   {
-    launch_colsum(e->g_cat + 1024, 1280, e->gp, B, P16, 256, 1.f, e->colscratch, s);
+    const View g_cat_pool(e->g_cat, 1024, 256);
+    launch_colsum(g_cat_pool.ptr(), g_cat_pool.ld(), e->gp, B, P16, 256, 1.f, e->colscratch, s);
     const float* gpz = e->gp;
     if (e->gn()) {
-      launch_gn_backward(e->zbuf[t.pool], 256, e->gp, 256, e->G_(t.pool), e->gn_stats[t.pool], e->gn_partial, B, 1, 256, s);
-      gpz = e->zbuf[t.pool];
+      launch_gn_backward(e->zbuf[t.pool]->p, 256, e->gp, 256, e->G_(t.pool), e->gn_stats[t.pool], e->gn_partial, B, 1, 256, s);
+      gpz = e->zbuf[t.pool]->p;
     }
     // (frozen backbone: the weight gradient only, no input gradient)
     launch_gemv_bwd(e->W_(t.pool), e->vec, gpz, e->A_(t.pool), l4_frozen ? nullptr : e->gvec, e->ws_wg + e->ws_off[t.pool], B, 256,
                     2048, s);
     if (!l4_frozen) {
-      launch_bcast_pixels(e->gvec, g_l4, 2048, B, P16, 2048, 1.0f / (float)P16, s);
-      twrite_plain(e, 1, g_l4);
+      launch_bcast_pixels(e->gvec, g_l4->p, g_l4->C, B, P16, 2048, 1.0f / (float)P16, s);
+      twrite_plain(*g_l4);
     }
     e->upd_splits[t.pool] = 1;
   }
   {
-    for (int i = 0; i < 4; ++i) conv_wgrad(e, t.aspp[i], e->g_cat + 256 * i, 1280, l4, 2048, e->h16, e->w16, B, e->g_cat);
+    for (int i = 0; i < 4; ++i) conv_wgrad(e, t.aspp[i], View(e->g_cat, 256 * i, 256), l4, B);
     if (!l4_frozen && aspp_dgrad(e, B, g_l4, l4, false, nullptr)) return 1;
   }
   // layer4, ASPP and decoder are done: update them now (on the side stream if there is one)
@@ -2283,28 +2239,27 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
     }
     const Block& b = t.blocks[i];
     auto& f = e->bb[i];
-    const int cmid = t.convs[b.c1].cout, cout = t.convs[b.c3].cout;
-    conv_wgrad(e, b.c3, f.g_out, cout, f.t2, cmid, f.Ho, f.Wo, B);
-    if (conv_dgrad(e, b.c3, f.g_out, cout, f.Ho, f.Wo, f.g_t2, cmid, B, false, f.t2, 0)) return 1;
-    conv_wgrad(e, b.c2, f.g_t2, cmid, f.t1, cmid, f.Hm, f.Wm, B);
-    if (conv_dgrad(e, b.c2, f.g_t2, cmid, f.Hm, f.Wm, f.g_t1, cmid, B, false, f.t1, 0)) return 1;
+    conv_wgrad(e, b.c3, f.g_out, f.t2, B);
+    if (conv_dgrad(e, b.c3, f.g_out, f.g_t2, B, Opt().mask(f.t2))) return 1;
+    conv_wgrad(e, b.c2, f.g_t2, f.t1, B);
+    if (conv_dgrad(e, b.c2, f.g_t2, f.g_t1, B, Opt().mask(f.t1))) return 1;
     // gradient w.r.t. the block input: conv1 path + identity / downsample path
     const bool is_first_block = i == 0;
     // the low-level feature already holds decoder.conv1's contribution
     bool have = !t.v3 && (i == t.layer1_last_block + 1);
-    const float* inmask = is_first_block ? nullptr : f.xin;   // p1 is a max-pool output: masked in maxpool_bwd
+    const Tensor* inmask = is_first_block ? nullptr : f.xin;   // p1 is a max-pool output: masked in maxpool_bwd
     // (the block's input is a frozen conv's output: weight gradients only)
     const bool in_frozen = frozen && b.c1 == e->train_from;
     if (b.ds >= 0) {
-      conv_wgrad(e, b.ds, f.g_out, cout, f.xin, f.Cin, f.Hi, f.Wi, B);
-      if (!in_frozen && conv_dgrad(e, b.ds, f.g_out, cout, f.Hi, f.Wi, f.g_xin, f.Cin, B, have, nullptr, 0)) return 1;
-      conv_wgrad(e, b.c1, f.g_t1, cmid, f.xin, f.Cin, f.Hi, f.Wi, B);
-      if (!in_frozen && conv_dgrad(e, b.c1, f.g_t1, cmid, f.Hi, f.Wi, f.g_xin, f.Cin, B, true, inmask, 0)) return 1;
+      conv_wgrad(e, b.ds, f.g_out, f.xin, B);
+      if (!in_frozen && conv_dgrad(e, b.ds, f.g_out, f.g_xin, B, Opt().accum(have))) return 1;
+      conv_wgrad(e, b.c1, f.g_t1, f.xin, B);
+      if (!in_frozen && conv_dgrad(e, b.c1, f.g_t1, f.g_xin, B, Opt().accum().mask(inmask))) return 1;
     } else {
       // identity path: g_xin = mask * (dgrad_conv1(g_t1) + g_out)
       if (have) return fail("internal: identity block after the low-level tap is unsupported");
-      conv_wgrad(e, b.c1, f.g_t1, cmid, f.xin, f.Cin, f.Hi, f.Wi, B);
-      if (conv_dgrad(e, b.c1, f.g_t1, cmid, f.Hi, f.Wi, f.g_xin, f.Cin, B, false, inmask, 0, f.g_out, cout)) return 1;
+      conv_wgrad(e, b.c1, f.g_t1, f.xin, B);
+      if (conv_dgrad(e, b.c1, f.g_t1, f.g_xin, B, Opt().mask(inmask).add(f.g_out))) return 1;
     }
     // first block of a ResNet layer: its data-gradient chain is queued, every operand of the stage's weight gradients
     // is final -> one grouped launch per tile shape
@@ -2317,14 +2272,14 @@ static int backward_impl(eosvos_engine* e, bool update, bool accumulate) {
   const auto& xrec = amax_rec_of(e, AM_X, 0);
   const bool stem_h3 = h3_mode() && e->amax && xrec.epoch == e->fwd_epoch && xrec.ptr == e->xpad;
   // (GroupNorm mode, round 5: the gradient operand is dz of the stem's GroupNorm, whose apply pass reduces its absmax)
-  unsigned* ag = stem_h3 ? amax_fused_slot(e, AM_G, 0, e->gn() ? e->zbuf[0] : e->g_c1, s) : nullptr;
-  launch_maxpool_bwd(e->g_p1, e->p1idx, e->g_c1, B, e->h2, e->w2, 64, e->h4, e->w4, s, e->gn() ? nullptr : ag);
+  unsigned* ag = stem_h3 ? amax_fused_slot(e, AM_G, 0, e->gn() ? e->zbuf[0]->p : e->g_c1->p, s) : nullptr;
+  launch_maxpool_bwd(e->g_p1->p, e->p1idx, e->g_c1->p, B, e->h2, e->w2, 64, e->h4, e->w4, s, e->gn() ? nullptr : ag);
   {
     const int chunks = stem_wgrad_chunks(B, e->h2, e->w2);
-    const float* gc1 = e->g_c1;
+    const float* gc1 = e->g_c1->p;
     if (e->gn()) {
-      launch_gn_backward(e->zbuf[0], 64, e->g_c1, 64, e->G_(0), e->gn_stats[0], e->gn_partial, B, e->h2 * e->w2, 64, s, ag);
-      gc1 = e->zbuf[0];
+      launch_gn_backward(e->zbuf[0]->p, 64, e->g_c1->p, 64, e->G_(0), e->gn_stats[0], e->gn_partial, B, e->h2 * e->w2, 64, s, ag);
+      gc1 = e->zbuf[0]->p;
     }
     if (ag) launch_stem_wgrad_h3(e->xpad, gc1, e->ws_wg + e->ws_off[0], B, e->H, e->W, e->h2, e->w2, chunks, ag, amax_slot(e, AM_X, 0), s);
     else launch_stem_wgrad(e->xpad, gc1, e->ws_wg + e->ws_off[0], B, e->H, e->W, e->h2, e->w2, chunks, s);
@@ -3310,12 +3265,10 @@ int eosvos_set_trainable_from(eosvos_engine* e, int conv_idx) {
   for (auto& tab : e->upd_tab) tab = nullptr;       // the update's part 0 covers another conv range
   if (e->gsum) HIPOK(hipMemsetAsync(e->gsum, 0, (size_t)t.nparam * 4, e->s));
   // ReLU masks that only a frozen conv's data gradient reads: the activations of the frozen blocks
-  e->m8_frozen.clear();
-  if (conv_idx > 0)
-    for (size_t i = 0; i < t.blocks.size(); ++i) {
-      if (t.blocks[i].c1 >= conv_idx) break;
-      e->m8_frozen.insert({e->bb[i].t1, e->bb[i].t2, e->bb[i].out});
-    }
+  for (size_t i = 0; i < t.blocks.size(); ++i) {
+    const bool frozen = t.blocks[i].c1 < conv_idx;
+    e->bb[i].t1->mask_frozen = e->bb[i].t2->mask_frozen = e->bb[i].out->mask_frozen = frozen;
+  }
   e->masks_valid = false;                   // a backward pass needs a forward made under this boundary
   return 0;
 }
@@ -3425,23 +3378,23 @@ int eosvos_time_hot_kernel(eosvos_engine* e, int batch, int reps, float* ms_host
   hipEvent_t a, b;
   HIPOK(hipEventCreate(&a));
   HIPOK(hipEventCreate(&b));
-  conv_fwd(e, t.dec_a, e->dcat, 304, e->h4, e->w4, e->d1, 256, batch, nullptr, 0, true);   // warm (and fills V / U)
+  conv_fwd(e, t.dec_a, e->dcat, e->d1, batch, Opt().relu());   // warm (and fills V / U)
   const ConvL& c = t.convs[t.dec_a];
   if (wino_on(e, t.dec_a, batch, e->h4, e->w4)) {
     // the step runs this layer in the Winograd domain: time its batched GEMM launch (+ fix-up), the largest
     // conv_igemm launch of an iteration, against the GEMM's own FLOPs
     const WinoGeom wg = wino_geom(e, c, batch, e->h4, e->w4);
     const long ntile = wg.ntile;
-    ConvArgs m = wino_plane_gemm(e, c, wg, e->wino_V[t.dec_a], e->wino_U[t.dec_a], e->wino_m, e->ws_conv, 0);
+    ConvArgs m = wino_plane_gemm(e, c, wg, e->wino[t.dec_a].V, e->wino[t.dec_a].U, e->wino_m, e->ws_conv, 0);
     HIPOK(hipEventRecord(a, e->s));
     for (int i = 0; i < reps; ++i) { ConvArgs k = m; launch_conv(k, e->s); }
     HIPOK(hipEventRecord(b, e->s));
     *flops_host = 2.0 * wg.np * (double)ntile * c.cout * c.cin;
   } else {
     HIPOK(hipEventRecord(a, e->s));
-    for (int i = 0; i < reps; ++i) conv_fwd(e, t.dec_a, e->dcat, 304, e->h4, e->w4, e->d1, 256, batch, nullptr, 0, true);
+    for (int i = 0; i < reps; ++i) conv_fwd(e, t.dec_a, e->dcat, e->d1, batch, Opt().relu());
     HIPOK(hipEventRecord(b, e->s));
-    *flops_host = 2.0 * (double)batch * e->h4 * e->w4 * 256.0 * 304.0 * 9.0;
+    *flops_host = 2.0 * (double)batch * e->h4 * e->w4 * (double)c.cout * c.cin * 9.0;
   }
   HIPOK(hipEventSynchronize(b));
   float ms = 0.f;
@@ -3460,35 +3413,31 @@ int eosvos_bench_conv(eosvos_engine* e, int ci, int kind, int batch, int reps, f
   const Topo& t = e->t;
   if (ci < 1 || ci >= (int)t.convs.size()) return fail("conv index out of range");
   const ConvL& c = t.convs[ci];
-  const float *x = nullptr, *g = nullptr;
-  float *y = nullptr, *gx = nullptr;
-  int ldx = c.cin, ldy = c.cout, Hi = 0, Wi = 0;
+  Tensor *x = nullptr, *gx = nullptr;      // the conv's input and its gradient
+  View y, g;                               // its output and the gradient w.r.t. it
   for (size_t i = 0; i < t.blocks.size() && !x; ++i) {
     const Block& b = t.blocks[i];
     auto& f = e->bb[i];
-    if (ci == b.c1) { x = f.xin; gx = f.g_xin; y = f.t1; g = f.g_t1; Hi = f.Hi; Wi = f.Wi; }
-    else if (ci == b.c2) { x = f.t1; gx = f.g_t1; y = f.t2; g = f.g_t2; Hi = f.Hm; Wi = f.Wm; }
-    else if (ci == b.c3) { x = f.t2; gx = f.g_t2; y = f.out; g = f.g_out; Hi = f.Ho; Wi = f.Wo; }
-    else if (ci == b.ds) { x = f.xin; gx = f.g_xin; y = f.dsb; g = f.g_out; Hi = f.Hi; Wi = f.Wi; }
+    if (ci == b.c1) { x = f.xin; gx = f.g_xin; y = f.t1; g = f.g_t1; }
+    else if (ci == b.c2) { x = f.t1; gx = f.g_t1; y = f.t2; g = f.g_t2; }
+    else if (ci == b.c3) { x = f.t2; gx = f.g_t2; y = f.out; g = f.g_out; }
+    else if (ci == b.ds) { x = f.xin; gx = f.g_xin; y = f.dsb; g = f.g_out; }
   }
   if (!x) {
-    if (ci == t.dec_a) { x = e->dcat; gx = e->g_dcat; y = e->d1; g = e->g_d1; Hi = e->h4; Wi = e->w4; }
-    else if (ci == t.dec_b) { x = e->d1; gx = e->g_d1; y = e->d2; g = e->g_d2; Hi = e->h4; Wi = e->w4; }
-    else if (ci == t.project) { x = e->cat; gx = e->g_cat; y = e->proj; g = e->g_proj; Hi = e->h16; Wi = e->w16; }
+    if (ci == t.dec_a) { x = e->dcat; gx = e->g_dcat; y = e->d1; g = e->g_d1; }
+    else if (ci == t.dec_b) { x = e->d1; gx = e->g_d1; y = e->d2; g = e->g_d2; }
+    else if (ci == t.project) { x = e->cat; gx = e->g_cat; y = e->proj; g = e->g_proj; }
     else {
       for (int i = 0; i < 4; ++i)
-        if (ci == t.aspp[i]) {
-          x = e->bb.back().out; gx = e->bb.back().g_out; y = e->cat + 256 * i; g = e->g_cat + 256 * i;
-          ldy = 1280; Hi = e->h16; Wi = e->w16;
-        }
+        if (ci == t.aspp[i]) { x = e->bb.back().out; gx = e->bb.back().g_out; y = View(e->cat, 256 * i, 256); g = View(e->g_cat, 256 * i, 256); }
     }
   }
   if (!x) return fail("conv not benchable");
-  const int Ho = conv_out(Hi, c.k, c.stride, c.dil, c.pad), Wo = conv_out(Wi, c.k, c.stride, c.dil, c.pad);
+  const int Ho = conv_out(x->H, c.k, c.stride, c.dil, c.pad), Wo = conv_out(x->W, c.k, c.stride, c.dil, c.pad);
   auto run = [&]() {
-    if (kind == 0) conv_fwd(e, ci, x, ldx, Hi, Wi, y, ldy, batch, nullptr, 0, true);
-    else if (kind == 1) (void)conv_dgrad(e, ci, g, ldy, Hi, Wi, gx, ldx, batch, false, e->m8(x) ? x : nullptr, 0);   // (p1 has no bytes)
-    else conv_wgrad(e, ci, g, ldy, x, ldx, Hi, Wi, batch);
+    if (kind == 0) conv_fwd(e, ci, x, y, batch, Opt().relu());
+    else if (kind == 1) (void)conv_dgrad(e, ci, g, gx, batch, Opt().mask(x->mask ? x : nullptr));   // (p1 has no bytes)
+    else conv_wgrad(e, ci, g, x, batch);
   };
   hipEvent_t a, b;
   HIPOK(hipEventCreate(&a));
@@ -3539,29 +3488,21 @@ int eosvos_debug_tensor(eosvos_engine* e, const char* name, float** ptr, int64_t
   const int B = e->lastB > 0 ? e->lastB : 1;
   const std::string n(name);
   auto set = [&](float* p, int h, int w, int c) { *ptr = p; dims4[0] = B; dims4[1] = h; dims4[2] = w; dims4[3] = c; return 0; };
+  auto tensor = [&](const Tensor* x) { return set(x->p, x->H, x->W, x->C); };
   // folded frozen-norm scale / shift (a = gamma / sqrt(var + eps), b = beta - mean * a), all norm layers concatenated
   if (n == "norm_a" || n == "norm_b") { *ptr = n == "norm_a" ? e->na : e->nb; dims4[0] = dims4[1] = dims4[2] = 1; dims4[3] = e->t.nnorm; return 0; }
   // the grow-only scratch of the label-map and adaptation stages, as 32-bit words (null and 0 words before its first use)
   if (n == "ccl_scratch") { *ptr = (float*)e->scratch; dims4[0] = dims4[1] = dims4[2] = 1; dims4[3] = (int64_t)(e->scratch_cap / 4); return 0; }
-  if (n == "c1") return set(e->c1, e->h2, e->w2, 64);
-  if (n == "p1") return set(e->p1, e->h4, e->w4, 64);
-  if (n == "g_c1") return set(e->g_c1, e->h2, e->w2, 64);
-  if (n == "g_p1") return set(e->g_p1, e->h4, e->w4, 64);
-  if (n == "cat") return set(e->cat, e->h16, e->w16, 1280);
-  if (n == "g_cat") return set(e->g_cat, e->h16, e->w16, 1280);
-  if (n == "proj") return set(e->proj, e->h16, e->w16, 256);
-  if (n == "g_proj") return set(e->g_proj, e->h16, e->w16, 256);
+  const std::pair<const char*, Tensor*> named[] = {{"c1", e->c1}, {"p1", e->p1}, {"g_c1", e->g_c1}, {"g_p1", e->g_p1}, {"cat", e->cat},
+      {"g_cat", e->g_cat}, {"proj", e->proj}, {"g_proj", e->g_proj}, {"dcat", e->dcat}, {"g_dcat", e->g_dcat}, {"d1", e->d1}, {"d2", e->d2},
+      {"g_d1", e->g_d1}, {"g_d2", e->g_d2}};
+  for (const auto& kv : named)
+    if (n == kv.first) return tensor(kv.second);
   // image-pooling branch of the ASPP: one vector per image
   if (n == "vec") return set(e->vec, 1, 1, 2048);
   if (n == "gvec") return set(e->gvec, 1, 1, 2048);
   if (n == "poolout") return set(e->poolout, 1, 1, 256);
   if (n == "gp") return set(e->gp, 1, 1, 256);
-  if (n == "dcat") return set(e->dcat, e->h4, e->w4, 304);
-  if (n == "g_dcat") return set(e->g_dcat, e->h4, e->w4, 304);
-  if (n == "d1") return set(e->d1, e->h4, e->w4, 256);
-  if (n == "d2") return set(e->d2, e->h4, e->w4, 256);
-  if (n == "g_d1") return set(e->g_d1, e->h4, e->w4, 256);
-  if (n == "g_d2") return set(e->g_d2, e->h4, e->w4, 256);
   if (n == "lowlog") return set(e->lowlog, e->h4, e->w4, 1);
   if (n == "g_low") return set(e->g_low, e->h4, e->w4, 1);
   if (n == "logits") return set(e->logits, e->H, e->W, 1);
@@ -3572,16 +3513,11 @@ int eosvos_debug_tensor(eosvos_engine* e, const char* name, float** ptr, int64_t
     const int i = atoi(n.substr(3, dot - 3).c_str());
     if (i < 0 || i >= (int)e->bb.size()) return fail("block index out of range");
     const auto& f = e->bb[i];
-    const Block& b = e->t.blocks[i];
-    const int cmid = e->t.convs[b.c1].cout, cout = e->t.convs[b.c3].cout;
     const std::string k = n.substr(dot + 1);
-    if (k == "t1") return set(f.t1, f.Hm, f.Wm, cmid);
-    if (k == "t2") return set(f.t2, f.Ho, f.Wo, cmid);
-    if (k == "out") return set(f.out, f.Ho, f.Wo, cout);
-    if (k == "g_t1") return set(f.g_t1, f.Hm, f.Wm, cmid);
-    if (k == "g_t2") return set(f.g_t2, f.Ho, f.Wo, cmid);
-    if (k == "g_out") return set(f.g_out, f.Ho, f.Wo, cout);
-    if (k == "dsb" && f.dsb) return set(f.dsb, f.Ho, f.Wo, cout);
+    const std::pair<const char*, Tensor*> named[] = {{"t1", f.t1}, {"t2", f.t2}, {"out", f.out}, {"g_t1", f.g_t1}, {"g_t2", f.g_t2},
+                                                     {"g_out", f.g_out}, {"dsb", f.dsb}};
+    for (const auto& kv : named)
+      if (k == kv.first && kv.second) return tensor(kv.second);
   }
   return fail("unknown debug tensor " + n);
 }
@@ -3605,6 +3541,7 @@ struct ScratchEngine {
     t.force_algo = algo;
     t.zbuf.assign(1, nullptr); t.gn_stats.assign(1, nullptr);
     t.ws_off.assign(1, 0); t.upd_splits.assign(1, 1);
+    t.wino.assign(1, eosvos_engine::WinoRec());
     const int Ho = conv_out(H, k, stride, dil, pad), Wo = conv_out(W, k, stride, dil, pad);
     t.Wp = t.falloc(c.wsize()); t.na = t.falloc(Cout); t.nb = t.falloc(Cout);
     t.ws_conv = t.falloc(conv_ws_floats());
@@ -3615,17 +3552,24 @@ struct ScratchEngine {
       if (!wino_shape(c)) return;
       const WinoGeom g = wino_geom(&t, c, B, Ho, Wo);
       slab = max64(slab, c.wsize() + (int64_t)wgrad_max_splits((int)g.ntile, Cout, Cin, g.np, 0) * Cout * g.np * Cin);
-      t.wino_V[0] = t.falloc(g.np * g.prow * Cin);
-      t.wino_U[0] = t.falloc((int64_t)g.np * Cout * Cin);
-      t.wino_Us[0] = t.falloc((int64_t)g.np * Cout * Cin);
-      t.wino_dM[0] = t.falloc(g.np * g.prow * Cout);
-      t.wino_us_valid[0] = 0; t.wino_v_batch[0] = 0; t.wino_dm_batch[0] = 0;
+      auto& w = t.wino[0];
+      w.V = t.falloc(g.np * g.prow * Cin);
+      w.U = t.falloc((int64_t)g.np * Cout * Cin);
+      w.Us = t.falloc((int64_t)g.np * Cout * Cin);
+      w.dM = t.falloc(g.np * g.prow * Cout);
       t.wino_m_n = g.np * g.prow * max64(Cout, Cin);
       t.wino_m = t.falloc(t.wino_m_n); t.wino_dv = t.falloc(t.wino_m_n);
-      if (!t.wino_V[0] || !t.wino_U[0] || !t.wino_Us[0] || !t.wino_dM[0] || !t.wino_m || !t.wino_dv) return;
+      if (!w.V || !w.U || !w.Us || !w.dM || !t.wino_m || !t.wino_dv) return;
     }
     t.ws_wg = t.falloc(slab);
     ok = t.Wp && t.na && t.nb && t.ws_conv && t.ws_wg;
+  }
+  // the caller's buffer at `key` as a tensor of this engine
+  Tensor* tensor(const float* key, int H, int W, int C, int phase) { return t.ts.add(const_cast<float*>(key), H, W, C, phase); }
+  // an eosvos_view of C channels: the slice [p - key, p - key + C) of the tensor at its key, or the tensor at p itself
+  View view(const eosvos_view& v, int H, int W, int C, int phase) {
+    if (!v.p) return View();
+    return View(tensor(v.key ? v.key : v.p, H, W, v.ld, phase), v.key ? (int)(v.p - v.key) : 0, C);
   }
   ~ScratchEngine() {
     (void)hipStreamSynchronize(t.s);
@@ -3651,9 +3595,10 @@ int eosvos_test_conv_algo(eosvos_engine* e, int algo, const float* x, const floa
     HIPOK(hipMemcpyAsync(t->na, scale, (size_t)Cout * 4, hipMemcpyDeviceToDevice, t->s));
     HIPOK(hipMemcpyAsync(t->nb, bias, (size_t)Cout * 4, hipMemcpyDeviceToDevice, t->s));
   }
-  if (res && wino_on(t, 0, B, conv_out(H, k, stride, dil, pad), conv_out(W, k, stride, dil, pad)))
-    return fail("the Winograd output transform has no residual input (the network never needs one)");
-  conv_fwd(t, 0, x, Cin, H, W, y, Cout, B, res, Cout, relu != 0);
+  const int Ho = conv_out(H, k, stride, dil, pad), Wo = conv_out(W, k, stride, dil, pad);
+  if (res && wino_on(t, 0, B, Ho, Wo)) return fail("the Winograd output transform has no residual input (the network never needs one)");
+  conv_fwd(t, 0, se.tensor(x, H, W, Cin, 0), se.tensor(y, Ho, Wo, Cout, 0), B,
+           Opt().relu(relu != 0).add(res ? View(se.tensor(res, Ho, Wo, Cout, 0)) : View()));
   HIPOK(hipStreamSynchronize(t->s));
   HIPOK(hipGetLastError());
   return 0;
@@ -3674,9 +3619,11 @@ int eosvos_test_conv_bwd_algo(eosvos_engine* e, int algo, const float* x, const 
   launch_oihw_to_ohwi(w_oihw, t->Wp, Cout, Cin, T, t->s);
   if (scale) HIPOK(hipMemcpyAsync(t->na, scale, (size_t)Cout * 4, hipMemcpyDeviceToDevice, t->s));
   // the order of the backward pass: weight gradient first (it makes the shared Winograd-domain dM), then data gradient
-  conv_wgrad(t, 0, g, Cout, x, Cin, H, W, B);
-  if (m8) t->mask8[x] = const_cast<uint8_t*>(m8);        // the mask bytes of x, as the forward pass would have left them
-  if (conv_dgrad(t, 0, g, Cout, H, W, dx, Cin, B, false, m8 ? x : nullptr, 0)) return 1;
+  Tensor* const xt = se.tensor(x, H, W, Cin, 0);
+  Tensor* const gt = se.tensor(g, conv_out(H, k, stride, dil, pad), conv_out(W, k, stride, dil, pad), Cout, 1);
+  conv_wgrad(t, 0, gt, xt, B);
+  xt->mask = const_cast<uint8_t*>(m8);        // the mask bytes of x, as the forward pass would have left them
+  if (conv_dgrad(t, 0, gt, se.tensor(dx, H, W, Cin, 1), B, Opt().mask(m8 ? xt : nullptr))) return 1;
   float* dw = t->falloc((int64_t)Cout * Cin * T);
   if (!dw) return fail("hipMalloc dw");
   const int64_t n = (int64_t)Cout * Cin * T;
@@ -3702,27 +3649,25 @@ int eosvos_test_conv_bwd(eosvos_engine* e, const float* x, const float* w_oihw, 
 // ---- the same convolution in the forms the network's passes use: channel slices of wider tensors (absmax slot, mask bytes
 // and pitch of the TENSOR), accumulating / adding / partially masked data gradients ------------------------------------
 namespace {
-// the absmax slot of the tensor at `key` as a consumer would read it: maximum of its words; valid = tlookup would return it
-int read_tslot(eosvos_engine* t, int phase, const float* key, unsigned* bits, int* valid) {
+// the tensor's absmax slot as a consumer would read it: maximum of its words; valid = tlookup would return it
+int read_tslot(eosvos_engine* t, const Tensor& x, unsigned* bits, int* valid) {
   *bits = 0; *valid = 0;
-  if (!h3_mode() || !t->amax) return 0;
-  auto it = t->treg[phase].find(key);
-  if (it == t->treg[phase].end()) return 0;
+  if (!h3_mode() || !t->amax || x.slot < 0) return 0;
   unsigned w[AMAX_SUB];
-  HIPOK(hipMemcpy2D(w, sizeof(unsigned), t->amax + amax_tcol(t, phase, it->second.idx), (size_t)AMAX_ROW * sizeof(unsigned),
+  HIPOK(hipMemcpy2D(w, sizeof(unsigned), t->amax + amax_tcol(t, x.phase, x.slot), (size_t)AMAX_ROW * sizeof(unsigned),
                     sizeof(unsigned), AMAX_SUB, hipMemcpyDeviceToHost));
   for (int i = 0; i < AMAX_SUB; ++i) *bits = w[i] > *bits ? w[i] : *bits;
-  *valid = it->second.valid ? 1 : 0;
+  *valid = x.valid ? 1 : 0;
   return 0;
 }
 // a producer's part for a source tensor that the caller filled: max|tensor| over ALL its channels into its slot, trusted
-int seed_tslot(eosvos_engine* t, int phase, const float* key, long rows, int C) {
+int seed_tslot(eosvos_engine* t, Tensor& x, long rows) {
   if (!h3_mode()) return 0;
   if (amax_init(t)) return fail("absmax arena");
-  unsigned* sl = tslot(t, phase, key);
+  unsigned* sl = tslot(t, x);
   if (!sl) return fail("no absmax slot left for the source tensor");
-  launch_absmax(key, rows, C, C, sl, t->s);
-  tmark_valid(t, phase, key);
+  launch_absmax(x.p, rows, x.C, x.C, sl, t->s);
+  tmark_valid(x);
   return 0;
 }
 bool view_ok(const eosvos_view& v, int C) {
@@ -3760,38 +3705,38 @@ int eosvos_test_conv_views(eosvos_engine* e, eosvos_conv_views* v) {
   launch_oihw_to_ohwi(v->w_oihw, t->Wp, Cout, Cin, T, t->s);
   if (v->scale) HIPOK(hipMemcpyAsync(t->na, v->scale, (size_t)Cout * 4, hipMemcpyDeviceToDevice, t->s));
   if (v->bias) HIPOK(hipMemcpyAsync(t->nb, v->bias, (size_t)Cout * 4, hipMemcpyDeviceToDevice, t->s));
-  const float* xkey = v->x.key ? v->x.key : v->x.p;
+  const View x = se.view(v->x, H, W, Cin, 0);
   v->slot_bits[0] = v->slot_bits[1] = v->src_slot_bits[0] = v->src_slot_bits[1] = 0;
   v->slot_valid[0] = v->slot_valid[1] = v->src_slot_valid[0] = v->src_slot_valid[1] = 0;
   amax_new_phase(t, 0);
-  if ((fwd || wg) && v->x.key && seed_tslot(t, 0, v->x.key, Pin, v->x.ldkey)) return 1;
+  if ((fwd || wg) && v->x.key && seed_tslot(t, *x.t, Pin)) return 1;
   if (fwd) {
     if (v->res.p && wino_on(t, 0, B, Ho, Wo)) return fail("the Winograd output transform has no residual input (the network never needs one)");
-    const float* ykey = v->y.key ? v->y.key : v->y.p;
-    if (v->y_m8) t->mask8[ykey] = v->y_m8;
+    const View y = se.view(v->y, Ho, Wo, Cout, 0);
+    y.t->mask = v->y_m8;
     for (int i = 0; i < nsl; ++i)
-      conv_fwd(t, 0, v->x.p + (long)i * Cin, v->x.ld, H, W, v->y.p + (long)i * Cout, v->y.ld, B, v->res.p, v->res.ld, v->relu != 0, false, xkey, ykey);
+      conv_fwd(t, 0, View(x.t, x.c0 + i * Cin, Cin), View(y.t, y.c0 + i * Cout, Cout), B,
+               Opt().relu(v->relu != 0).add(se.view(v->res, Ho, Wo, Cout, 0)));
     HIPOK(hipStreamSynchronize(t->s));
     HIPOK(hipGetLastError());
-    t->mask8.erase(ykey);
-    if (read_tslot(t, 0, ykey, &v->slot_bits[0], &v->slot_valid[0])) return 1;
+    if (read_tslot(t, *y.t, &v->slot_bits[0], &v->slot_valid[0])) return 1;
   }
-  if ((fwd || wg) && v->x.key && read_tslot(t, 0, v->x.key, &v->src_slot_bits[0], &v->src_slot_valid[0])) return 1;
+  if ((fwd || wg) && v->x.key && read_tslot(t, *x.t, &v->src_slot_bits[0], &v->src_slot_valid[0])) return 1;
+  const View g = se.view(v->g, Ho, Wo, Cout, 1);
   if (dg || wg) {
     amax_new_phase(t, 1);
-    const float* gkey = v->g.key ? v->g.key : v->g.p;
-    if (v->g.key && seed_tslot(t, 1, v->g.key, Pout, v->g.ldkey)) return 1;
+    if (v->g.key && seed_tslot(t, *g.t, Pout)) return 1;
     // the order of the backward pass: weight gradient first (it makes the shared Winograd-domain dM), then data gradient
-    if (wg) conv_wgrad(t, 0, v->g.p, v->g.ld, v->x.p, v->x.ld, H, W, B, gkey, xkey);
+    if (wg) conv_wgrad(t, 0, g, x, B);
     if (dg) {
-      const float* gxkey = v->gx.key ? v->gx.key : v->gx.p;
-      if (v->gx_m8) t->mask8[v->gx.p] = const_cast<uint8_t*>(v->gx_m8);      // the mask bytes of the activation gx is the gradient of
-      if (conv_dgrad(t, 0, v->g.p, v->g.ld, H, W, v->gx.p, v->gx.ld, B, v->accum != 0, v->gx_m8 ? v->gx.p : nullptr, v->mask_c0,
-                     v->add.p, v->add.ld, gkey, gxkey))
-        return 1;
+      const View gx = se.view(v->gx, H, W, Cin, 1);
+      // the mask bytes of the activation gx is the gradient of: a tensor laid out like the view gx
+      Tensor* const relu_x = v->gx_m8 ? se.tensor(v->gx.p, H, W, v->gx.ld, 0) : nullptr;
+      if (relu_x) relu_x->mask = const_cast<uint8_t*>(v->gx_m8);
+      if (conv_dgrad(t, 0, g, gx, B, Opt().accum(v->accum != 0).mask(relu_x, v->mask_c0).add(se.view(v->add, H, W, Cin, 1)))) return 1;
       HIPOK(hipStreamSynchronize(t->s));
       HIPOK(hipGetLastError());
-      if (read_tslot(t, 1, gxkey, &v->slot_bits[1], &v->slot_valid[1])) return 1;
+      if (read_tslot(t, *gx.t, &v->slot_bits[1], &v->slot_valid[1])) return 1;
     }
     if (wg) {
       const int64_t n = (int64_t)Cout * Cin * T;
@@ -3803,7 +3748,7 @@ int eosvos_test_conv_views(eosvos_engine* e, eosvos_conv_views* v) {
   }
   HIPOK(hipStreamSynchronize(t->s));
   HIPOK(hipGetLastError());
-  if ((dg || wg) && v->g.key && read_tslot(t, 1, v->g.key, &v->src_slot_bits[1], &v->src_slot_valid[1])) return 1;
+  if ((dg || wg) && v->g.key && read_tslot(t, *g.t, &v->src_slot_bits[1], &v->src_slot_valid[1])) return 1;
   return 0;
 }
 
@@ -3813,28 +3758,28 @@ int eosvos_test_aspp_dgrad(eosvos_engine* e, int batch, const float* g_cat, cons
   if (!e || !g_cat || !l4_m8 || !g_l4_inout || !merged_ran || !slot_bits || !slot_valid) return fail("null argument");
   if (batch < 1 || batch > e->maxB) return fail("batch out of range");
   const Topo& t = e->t;
-  float* g_l4 = e->bb.back().g_out;
-  const float* l4 = e->bb.back().out;
+  Tensor* const g_l4 = e->bb.back().g_out;
+  Tensor* const l4 = e->bb.back().out;
   const int cin = t.convs[t.aspp[0]].cin;
-  uint8_t* m8 = e->m8(l4);
+  uint8_t* m8 = l4->mask;
   if (cin != 2048 || e->gn() || !m8) return fail("eosvos_test_aspp_dgrad needs the frozen-norm ResNet-50/101 ASPP with mask bytes");
   const size_t P = (size_t)batch * e->h16 * e->w16;
   plans_match_mode(e);
   e->masks_valid = false;                         // the mask bytes of l4 and the gradient buffers no longer belong to a forward
   e->have_loss_grad = false;
-  HIPOK(hipMemcpyAsync(e->g_cat, g_cat, P * 1280 * sizeof(float), hipMemcpyDeviceToDevice, e->s));
+  HIPOK(hipMemcpyAsync(e->g_cat->p, g_cat, P * e->g_cat->C * sizeof(float), hipMemcpyDeviceToDevice, e->s));
   HIPOK(hipMemcpyAsync(m8, l4_m8, P * (cin / 4), hipMemcpyDeviceToDevice, e->s));
-  HIPOK(hipMemcpyAsync(g_l4, g_l4_inout, P * cin * sizeof(float), hipMemcpyDeviceToDevice, e->s));
+  HIPOK(hipMemcpyAsync(g_l4->p, g_l4_inout, P * cin * sizeof(float), hipMemcpyDeviceToDevice, e->s));
   amax_new_phase(e, 1);
-  if (seed_tslot(e, 1, e->g_cat, (long)P, 1280)) return 1;      // as the projection's data gradient, the writer of g_cat, leaves it
-  twrite_plain(e, 1, g_l4);                       // the pooling branch's broadcast has no fused absmax
+  if (seed_tslot(e, *e->g_cat, (long)P)) return 1;      // as the projection's data gradient, the writer of g_cat, leaves it
+  twrite_plain(*g_l4);                       // the pooling branch's broadcast has no fused absmax
   bool merged = false;
   if (aspp_dgrad(e, batch, g_l4, l4, force_fallback != 0, &merged)) return 1;
   *merged_ran = merged ? 1 : 0;
-  HIPOK(hipMemcpyAsync(g_l4_inout, g_l4, P * cin * sizeof(float), hipMemcpyDeviceToDevice, e->s));
+  HIPOK(hipMemcpyAsync(g_l4_inout, g_l4->p, P * cin * sizeof(float), hipMemcpyDeviceToDevice, e->s));
   HIPOK(hipStreamSynchronize(e->s));
   HIPOK(hipGetLastError());
-  return read_tslot(e, 1, g_l4, slot_bits, slot_valid);
+  return read_tslot(e, *g_l4, slot_bits, slot_valid);
 }
 
 // ---- op-level entry points of the other kernels (misc_kernels.hip) --------------------------------------------------
