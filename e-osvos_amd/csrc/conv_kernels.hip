@@ -18,10 +18,12 @@
 // Winograd-domain convolutions (ConvArgs::plane_rows, WgradArgs::*_tap_stride; transforms
 // in misc_kernels.hip, selection in engine.cpp wino_on()).
 #include "kernels.h"
+#include "conv_tile.h"
 
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
 #include <vector>
 
 namespace eosvos {
@@ -33,50 +35,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define EOSVOS_EB128 EOSVOS_EB      // rows per batch in the 128-wide kernels (their accumulators are dead here: registers to spare)
 #define EOSVOS_OCC 2
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
-// Blocks are dealt round-robin over the 8 XCDs; give each XCD a contiguous range of tiles
-// so neighbouring tiles (which share the gathered operand) meet in one L2.  Bijective for
-// every grid size.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
-__device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-// 16-byte buffer load; offsets past the descriptor's size return 0 (hardware range check)
-__device__ __forceinline__ float4 bufld4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-  auto v = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
-  return *reinterpret_cast<float4*>(&v);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* p, long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, (int)(bytes > 0x7fffffffL ? 0x7fffffffL : bytes), 0x00020000);
-}
-
-// destination pixel of GEMM row m: dense, or (1x1 stride-2 data gradient) the even pixels of
-// the finer destination grid -- the odd ones receive no contribution and are never touched
-__device__ __forceinline__ size_t dst_pixel(const ConvArgs& p, int m) {
-  if (p.par) return (size_t)conv_par_pixel(p.B, p.Ho, p.Wo, m);
-  if (!p.dst_up) return (size_t)m;
-  const int hw = p.Ho * p.Wo;
-  const int b = m / hw, rem = m - b * hw;
-  const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
-  return ((size_t)b * p.Hf + (oy << 1)) * p.Wf + (ox << 1);
-}
-
-// pre-split operand path: 4 consecutive channels n .. n + 3 of pixel `pix` into the destination's pair8 sibling
-// (presplit_kernels.hip: per 8 channels [8 x fp16 hi | 8 x fp16 lo]; same two pieces as h3_split_pair)
-__device__ __forceinline__ void pair_store4(unsigned char* y2, size_t pix, int ldy, int n, const float4& v, float s) {
-  typedef _Float16 ph2 __attribute__((ext_vector_type(2)));
-  typedef float pf2 __attribute__((ext_vector_type(2)));
-  const pf2 a = {v.x * s, v.y * s}, b = {v.z * s, v.w * s};
-  const ph2 ha = __builtin_convertvector(a, ph2), hb = __builtin_convertvector(b, ph2);
-  const pf2 ua = __builtin_convertvector(ha, pf2), ub = __builtin_convertvector(hb, pf2);
-  const pf2 ra = {a.x - ua.x, a.y - ua.y}, rb = {b.x - ub.x, b.y - ub.y};
-  const ph2 la = __builtin_convertvector(ra, ph2), lb = __builtin_convertvector(rb, ph2);
-  unsigned char* q = y2 + (pix * (size_t)ldy + (size_t)(n & ~7)) * 4 + (n & 4) * 2;
-  *reinterpret_cast<uint2*>(q) = make_uint2(__builtin_bit_cast(unsigned, ha), __builtin_bit_cast(unsigned, hb));
-  *reinterpret_cast<uint2*>(q + 16) = make_uint2(__builtin_bit_cast(unsigned, la), __builtin_bit_cast(unsigned, lb));
-}
 
 // Work decomposition ("stream-K"): the launch has nwg workgroups (<= 2 per CU, all resident);
 // the tiles x K-steps work units are dealt out in equal contiguous runs of `per` units, so a
@@ -1218,22 +1176,6 @@ __global__ __launch_bounds__(256, 2) void conv_x6_multi_kernel(const ConvArgs p)
 // strip's activations in flight behind the current strip's MFMAs.  Measured: layer1 conv3 (64 -> 256, + residual) 60 -> 41 us,
 // layer2 conv3 (128 -> 512) 43 -> 31 us, layer1 conv1 (256 -> 64) 35 -> 26 us.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void amax_block_commit8(unsigned m, unsigned* slot) {      // 8 waves per workgroup
-  __shared__ unsigned wmax8[8];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned t = (unsigned)__shfl_xor((int)m, o);
-    m = m > t ? m : t;
-  }
-  if ((threadIdx.x & 63) == 0) wmax8[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned q = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) q = q > wmax8[i] ? q : wmax8[i];
-    if (q) atomicMax(slot + (size_t)((blockIdx.x + blockIdx.y) & (AMAX_SUB - 1)) * AMAX_ROW, q);
-  }
-}
 __device__ __forceinline__ void s1_split8(const float4& lo, const float4& hi, float s, uint4& h0, uint4& h1) {
   unsigned a[4], b[4];
   h3_split_pair(lo.x, lo.y, s, a[0], b[0]);
@@ -1515,7 +1457,7 @@ __global__ __launch_bounds__(512, (K <= 128 ? EOSVOS_STREAM_OCC : 1)) void conv1
       }
     }
   }
-  if (p.amax_y) amax_block_commit8(ymax, p.amax_y);
+  if (p.amax_y) amax_block_commit<8>(ymax, p.amax_y);
 }
 // ---------------------------------------------------------------------------------------
 // The same structure for layer1's 3x3 convs (64 -> 64 channels, stride 1, 77 040 pixels at batch 3), forward and data gradient:
@@ -1715,7 +1657,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_stream_kernel(const ConvArgs p
     }
     cur = nx;
   }
-  if (p.amax_y) amax_block_commit8(ymax, p.amax_y);
+  if (p.amax_y) amax_block_commit<8>(ymax, p.amax_y);
 }
 static bool stream3x3_ok(const ConvArgs& a) {
   constexpr int min_m = 16384;
@@ -2270,8 +2212,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_h3_group_kernel(const WgradArgs*
 
 // max over the finite |x| of a [rows x C] view (row pitch ld floats) -> atomicMax of the bit pattern (|x| compares like
 // an unsigned integer).  HBM-bound: one read of the view.
-__device__ __forceinline__ unsigned absmax4(const float4& v, unsigned m) { return amax_f4(m, v); }
-__device__ __forceinline__ void absmax_finish(unsigned m, unsigned* slot) { amax_block_commit(m, slot); }
 // dense view: n4 float4 in a row
 __global__ __launch_bounds__(256) void absmax_flat_kernel(const float4* __restrict__ x, long n4, unsigned* __restrict__ slot) {
   unsigned m = 0;
@@ -2279,10 +2219,10 @@ __global__ __launch_bounds__(256) void absmax_flat_kernel(const float4* __restri
   long i = (long)blockIdx.x * 256 + threadIdx.x;
   for (; i + 3 * stride < n4; i += 4 * stride) {
     const float4 v0 = x[i], v1 = x[i + stride], v2 = x[i + 2 * stride], v3 = x[i + 3 * stride];
-    m = absmax4(v0, m); m = absmax4(v1, m); m = absmax4(v2, m); m = absmax4(v3, m);
+    m = amax_f4(m, v0); m = amax_f4(m, v1); m = amax_f4(m, v2); m = amax_f4(m, v3);
   }
-  for (; i < n4; i += stride) m = absmax4(x[i], m);
-  absmax_finish(m, slot);
+  for (; i < n4; i += stride) m = amax_f4(m, x[i]);
+  amax_block_commit(m, slot);
 }
 // strided view: 2^txs threads walk the C4 float4 of a row, 256 >> txs rows per workgroup pass
 __global__ __launch_bounds__(256) void absmax_rows_kernel(const float* __restrict__ x, int rows, int C4, int ld, int txs,
@@ -2291,9 +2231,9 @@ __global__ __launch_bounds__(256) void absmax_rows_kernel(const float* __restric
   unsigned m = 0;
   for (int r = blockIdx.x * rp + rl; r < rows; r += gridDim.x * rp) {
     const float* row = x + (size_t)r * ld;
-    for (int c = col; c < C4; c += tx) m = absmax4(ldg4(row + c * 4), m);
+    for (int c = col; c < C4; c += tx) m = amax_f4(m, ldg4(row + c * 4));
   }
-  absmax_finish(m, slot);
+  amax_block_commit(m, slot);
 }
 void launch_absmax(const float* x, long rows, int C, int ld, unsigned* slot, hipStream_t s) {
   const int C4 = C / 4;
@@ -2328,8 +2268,8 @@ __global__ __launch_bounds__(256) void absmax_segments_kernel(const float* __res
   if (n4 <= 0) return;
   const float4* x = reinterpret_cast<const float4*>(base + off[y]);
   unsigned m = 0;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) m = absmax4(x[i], m);
-  absmax_finish(m, slots + y);   // (blockIdx.x + blockIdx.y) spreads the words
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) m = amax_f4(m, x[i]);
+  amax_block_commit(m, slots + y);   // (blockIdx.x + blockIdx.y) spreads the words
 }
 void launch_absmax_segments(const float* base, const long* dev_off, const int* dev_n, int nseg, unsigned* slots, hipStream_t s) {
   hipLaunchKernelGGL(absmax_segments_kernel, dim3(64, (unsigned)nseg), dim3(256), 0, s, base, dev_off, dev_n, slots);
@@ -2356,25 +2296,34 @@ void conv_set_mfma_mode(int mode) { g_mfma_mode = mode == 2 ? 2 : (mode ? 1 : 0)
 // by time, its algorithmic FLOPs / its measured duration).  Off by default; no effect on results.
 // ---------------------------------------------------------------------------------------
 namespace {
+// Run-time tile widths (128, else 64) and flags -> the std::integral_constant a launcher instantiates its kernel with
+template <class F> void with_tile(int w, F&& f) {
+  if (w == 128) f(std::integral_constant<int, 128>{}); else f(std::integral_constant<int, 64>{});
+}
+template <class F> void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{}); else f(std::false_type{});
+}
 struct ProfRec { hipEvent_t a, b; int kernel; double flops; };
 bool g_prof_on = false;
 std::vector<ProfRec> g_prof;
 std::vector<hipEvent_t> g_prof_pool;
 const char* const kProfNames[] = {
-    "conv_x6_kernel<128, false>", "conv_x6_kernel<128, true>", "conv_x6_kernel<64, false>", "conv_x6_kernel<64, true>",
-    "wgrad_x6_kernel<128, 128>", "wgrad_x6_kernel<128, 64>", "wgrad_x6_kernel<64, 128>", "wgrad_x6_kernel<64, 64>",
-    "conv_igemm_kernel<128, false, *>", "conv_igemm_kernel<128, true, *>", "conv_igemm_kernel<64, false, 0>", "conv_igemm_kernel<64, true, 0>",
-    "wgrad_kernel<128, 128>", "wgrad_kernel<128, 64>", "wgrad_kernel<64, 128>", "wgrad_kernel<64, 64>",
-    "conv_fixup_kernel",
-    "wgrad_x6_group_kernel<128, 128>", "wgrad_x6_group_kernel<128, 64>", "wgrad_x6_group_kernel<64, 128>", "wgrad_x6_group_kernel<64, 64>",
-    "conv_h3_kernel<128, false>", "conv_h3_kernel<128, true>", "conv_h3_kernel<64, false>", "conv_h3_kernel<64, true>",
-    "wgrad_h3_kernel<128, 128>", "wgrad_h3_kernel<128, 64>", "wgrad_h3_kernel<64, 128>", "wgrad_h3_kernel<64, 64>",
-    "wgrad_h3_group_kernel<128, 128>", "wgrad_h3_group_kernel<128, 64>", "wgrad_h3_group_kernel<64, 128>", "wgrad_h3_group_kernel<64, 64>",
-    "conv_h3_multi_kernel", "conv_x6_multi_kernel", "conv1x1_stream_kernel<*, 128>", "conv1x1_stream_kernel<*, 64>",
-    "conv3x3_stream_kernel",
-    // pre-split operand path (presplit_kernels.hip), indices kProfPresplit0 ...
-    "wgrad_p_kernel<256, 256>", "wgrad_p_group_kernel<256, 256>"};
-constexpr int kProfKernels = sizeof(kProfNames) / sizeof(kProfNames[0]);
+#define EOSVOS_PROF_NAME(id, name) name,
+    EOSVOS_PROF_KERNELS(EOSVOS_PROF_NAME)
+#undef EOSVOS_PROF_NAME
+};
+static_assert(sizeof(kProfNames) / sizeof(kProfNames[0]) == kProfKernels, "one name per id");
+// Families of four records: <128, .>, <128, .>, <64, .>, <64, .> for the convs (tile width, then K-major), <bm, bn> for the
+// weight gradients (128 before 64 in both)
+int prof_conv(int mode, int bn, bool kmajor) {
+  return (mode == 2 ? kProfConvH3 : mode == 1 ? kProfConvX6 : kProfConvIgemm) + (bn == 128 ? 0 : 2) + (kmajor ? 1 : 0);
+}
+int prof_wgrad(int first, int bm, int bn) { return first + (bm == 128 ? 0 : 2) + (bn == 128 ? 0 : 1); }
+#define EOSVOS_PROF_FAMILY(first) static_assert(first##_1 == first + 1 && first##_2 == first + 2 && first##_3 == first + 3, "family of four")
+EOSVOS_PROF_FAMILY(kProfConvX6); EOSVOS_PROF_FAMILY(kProfConvIgemm); EOSVOS_PROF_FAMILY(kProfConvH3);
+EOSVOS_PROF_FAMILY(kProfWgradX6); EOSVOS_PROF_FAMILY(kProfWgrad); EOSVOS_PROF_FAMILY(kProfWgradH3);
+EOSVOS_PROF_FAMILY(kProfWgradX6Group); EOSVOS_PROF_FAMILY(kProfWgradH3Group);
+#undef EOSVOS_PROF_FAMILY
 hipEvent_t prof_event() {
   if (!g_prof_pool.empty()) { hipEvent_t e = g_prof_pool.back(); g_prof_pool.pop_back(); return e; }
   hipEvent_t e;
@@ -2551,13 +2500,13 @@ int conv_plan(ConvArgs& a) {
 void launch_conv(ConvArgs& a, hipStream_t s) {
   if (stream3x3_ok(a)) {                              // layer1's 64 -> 64 3x3 convs: all nine taps' weights resident in LDS
     a.dp_q = 0; a.per = 0; a.nwg = 0; a.splitk = 0;
-    ProfScope ps(37, 2.0 * a.M * a.N * a.Kc * 9, s);
+    ProfScope ps(kProfStream3x3, 2.0 * a.M * a.N * a.Kc * 9, s);
     launch_stream3x3(a, s);
     return;
   }
   if (const int nc = stream1x1_nc(a)) {               // short-K 1x1 convs on the large maps: the streaming kernel
     a.dp_q = 0; a.per = 0; a.nwg = 0; a.splitk = 0;
-    ProfScope ps(nc >= 128 ? 35 : 36, 2.0 * a.M * a.N * a.Kc, s);
+    ProfScope ps(nc >= 128 ? kProfStream1x1_128 : kProfStream1x1_64, 2.0 * a.M * a.N * a.Kc, s);      // (48 columns: filed under 64)
     if (nc == 128) {
       if (a.Kc == 64) launch_stream1x1<64, 128>(a, s);
       else if (a.Kc == 128) launch_stream1x1<128, 128>(a, s);
@@ -2580,40 +2529,23 @@ void launch_conv(ConvArgs& a, hipStream_t s) {
   const dim3 grid(nwg), block(256);
   const int mode = conv_mfma_mode();
   a.y2_done = (a.y2 && mode == 2) ? 1 : 0;       // conv_xs_body<NP = 2> and conv_fixup_kernel write the pair8 sibling
-  const int pk = a.nseg > 0 ? (mode == 2 ? 33 : 34) : (mode == 2 ? 21 : mode == 1 ? 0 : 8) + (bn == 128 ? 0 : 2) + (a.kmajor ? 1 : 0);
+  const int pk = a.nseg > 0 ? (mode == 2 ? kProfConvH3Multi : kProfConvX6Multi) : prof_conv(mode, bn, a.kmajor != 0);
   {
   ProfScope ps(pk, 2.0 * a.M * a.N * a.KH * a.KW * a.Kc * conv_exec_frac(a), s);
   if (a.nseg > 0) {
     if (mode == 2) hipLaunchKernelGGL(conv_h3_multi_kernel, grid, block, 0, s, a);
     else hipLaunchKernelGGL(conv_x6_multi_kernel, grid, block, 0, s, a);
-  } else if (mode == 2) {
-    if (a.kmajor) {
-      if (bn == 128) hipLaunchKernelGGL((conv_h3_kernel<128, true>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((conv_h3_kernel<64, true>), grid, block, 0, s, a);
-    } else {
-      if (bn == 128) hipLaunchKernelGGL((conv_h3_kernel<128, false>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((conv_h3_kernel<64, false>), grid, block, 0, s, a);
-    }
-  } else if (mode == 1) {
-    if (a.kmajor) {
-      if (bn == 128) hipLaunchKernelGGL((conv_x6_kernel<128, true>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((conv_x6_kernel<64, true>), grid, block, 0, s, a);
-    } else {
-      if (bn == 128) hipLaunchKernelGGL((conv_x6_kernel<128, false>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((conv_x6_kernel<64, false>), grid, block, 0, s, a);
-    }
-  } else if (a.deep == 1) {
-    if (a.kmajor) hipLaunchKernelGGL((conv_igemm_kernel<128, true, 1>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_igemm_kernel<128, false, 1>), grid, block, 0, s, a);
-  } else if (a.deep == 2) {
-    if (a.kmajor) hipLaunchKernelGGL((conv_igemm_kernel<128, true, 2>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_igemm_kernel<128, false, 2>), grid, block, 0, s, a);
-  } else if (a.kmajor) {
-    if (bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<128, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_igemm_kernel<64, true>), grid, block, 0, s, a);
+  } else if (mode == 0 && (a.deep == 1 || a.deep == 2)) {
+    with_bool(a.kmajor != 0, [&](auto km) {
+      if (a.deep == 1) hipLaunchKernelGGL((conv_igemm_kernel<128, km(), 1>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((conv_igemm_kernel<128, km(), 2>), grid, block, 0, s, a);
+    });
   } else {
-    if (bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<128, false>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((conv_igemm_kernel<64, false>), grid, block, 0, s, a);
+    with_tile(bn, [&](auto BN) { with_bool(a.kmajor != 0, [&](auto km) {
+      if (mode == 2) hipLaunchKernelGGL((conv_h3_kernel<BN(), km()>), grid, block, 0, s, a);
+      else if (mode == 1) hipLaunchKernelGGL((conv_x6_kernel<BN(), km()>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((conv_igemm_kernel<BN(), km()>), grid, block, 0, s, a);
+    }); });
   }
   }
   const int T = a.KH * a.KW;
@@ -2621,9 +2553,8 @@ void launch_conv(ConvArgs& a, hipStream_t s) {
   const long ksteps = (long)T * ((a.Kc + bk - 1) / bk);
   const long sk_tiles = tiles - (long)a.dp_q * nwg;
   if (a.splitk > 1 || (a.per > 0 && sk_tiles > 0 && (a.per % ksteps != 0 || a.tprefix))) {   // some tile is shared between workgroups
-    ProfScope ps(16, 0.0, s);
-    if (bn == 128) hipLaunchKernelGGL((conv_fixup_kernel<128>), dim3((unsigned)sk_tiles, 8), block, 0, s, a);
-    else hipLaunchKernelGGL((conv_fixup_kernel<64>), dim3((unsigned)sk_tiles, 8), block, 0, s, a);
+    ProfScope ps(kProfFixup, 0.0, s);
+    with_tile(bn, [&](auto BN) { hipLaunchKernelGGL((conv_fixup_kernel<BN()>), dim3((unsigned)sk_tiles, 8), block, 0, s, a); });
   }
 }
 
@@ -2837,18 +2768,11 @@ void launch_wgrad_group(const WgradArgs* dev_tab, const int* dev_map, int nwg, i
   const dim3 grid(nwg), block(256);
   const int2* map = reinterpret_cast<const int2*>(dev_map);
   const bool h3 = conv_mfma_mode() == 2;
-  ProfScope ps((h3 ? 29 : 17) + (bm == 128 ? 0 : 2) + (bn == 128 ? 0 : 1), flops, s);
-  if (h3) {
-    if (bm == 128 && bn == 128) hipLaunchKernelGGL((wgrad_h3_group_kernel<128, 128>), grid, block, 0, s, dev_tab, map);
-    else if (bm == 128) hipLaunchKernelGGL((wgrad_h3_group_kernel<128, 64>), grid, block, 0, s, dev_tab, map);
-    else if (bn == 128) hipLaunchKernelGGL((wgrad_h3_group_kernel<64, 128>), grid, block, 0, s, dev_tab, map);
-    else hipLaunchKernelGGL((wgrad_h3_group_kernel<64, 64>), grid, block, 0, s, dev_tab, map);
-    return;
-  }
-  if (bm == 128 && bn == 128) hipLaunchKernelGGL((wgrad_x6_group_kernel<128, 128>), grid, block, 0, s, dev_tab, map);
-  else if (bm == 128) hipLaunchKernelGGL((wgrad_x6_group_kernel<128, 64>), grid, block, 0, s, dev_tab, map);
-  else if (bn == 128) hipLaunchKernelGGL((wgrad_x6_group_kernel<64, 128>), grid, block, 0, s, dev_tab, map);
-  else hipLaunchKernelGGL((wgrad_x6_group_kernel<64, 64>), grid, block, 0, s, dev_tab, map);
+  ProfScope ps(prof_wgrad(h3 ? kProfWgradH3Group : kProfWgradX6Group, bm, bn), flops, s);
+  with_tile(bm, [&](auto BM) { with_tile(bn, [&](auto BN) {
+    if (h3) hipLaunchKernelGGL((wgrad_h3_group_kernel<BM(), BN()>), grid, block, 0, s, dev_tab, map);
+    else hipLaunchKernelGGL((wgrad_x6_group_kernel<BM(), BN()>), grid, block, 0, s, dev_tab, map);
+  }); });
 }
 
 void launch_wgrad(const WgradArgs& a, hipStream_t s) {
@@ -2859,26 +2783,13 @@ void launch_wgrad(const WgradArgs& a, hipStream_t s) {
   const int tiles = ((a.Cout + bm - 1) / bm) * ((a.Cin + bn - 1) / bn) * T;
   const dim3 grid(tiles * a.splits), block(256);
   const int mode = conv_mfma_mode();
-  ProfScope ps((mode == 2 ? 25 : mode == 1 ? 4 : 12) + (bm == 128 ? 0 : 2) + (bn == 128 ? 0 : 1),
+  ProfScope ps(prof_wgrad(mode == 2 ? kProfWgradH3 : mode == 1 ? kProfWgradX6 : kProfWgrad, bm, bn),
                2.0 * a.Cout * a.Cin * T * (double)P * wgrad_exec_frac(a), s);
-  if (mode == 2) {
-    if (bm == 128 && bn == 128) hipLaunchKernelGGL((wgrad_h3_kernel<128, 128>), grid, block, 0, s, a);
-    else if (bm == 128) hipLaunchKernelGGL((wgrad_h3_kernel<128, 64>), grid, block, 0, s, a);
-    else if (bn == 128) hipLaunchKernelGGL((wgrad_h3_kernel<64, 128>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((wgrad_h3_kernel<64, 64>), grid, block, 0, s, a);
-    return;
-  }
-  if (mode == 1) {
-    if (bm == 128 && bn == 128) hipLaunchKernelGGL((wgrad_x6_kernel<128, 128>), grid, block, 0, s, a);
-    else if (bm == 128) hipLaunchKernelGGL((wgrad_x6_kernel<128, 64>), grid, block, 0, s, a);
-    else if (bn == 128) hipLaunchKernelGGL((wgrad_x6_kernel<64, 128>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((wgrad_x6_kernel<64, 64>), grid, block, 0, s, a);
-    return;
-  }
-  if (bm == 128 && bn == 128) hipLaunchKernelGGL((wgrad_kernel<128, 128>), grid, block, 0, s, a);
-  else if (bm == 128) hipLaunchKernelGGL((wgrad_kernel<128, 64>), grid, block, 0, s, a);
-  else if (bn == 128) hipLaunchKernelGGL((wgrad_kernel<64, 128>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((wgrad_kernel<64, 64>), grid, block, 0, s, a);
+  with_tile(bm, [&](auto BM) { with_tile(bn, [&](auto BN) {
+    if (mode == 2) hipLaunchKernelGGL((wgrad_h3_kernel<BM(), BN()>), grid, block, 0, s, a);
+    else if (mode == 1) hipLaunchKernelGGL((wgrad_x6_kernel<BM(), BN()>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((wgrad_kernel<BM(), BN()>), grid, block, 0, s, a);
+  }); });
 }
 
 }  // namespace eosvos

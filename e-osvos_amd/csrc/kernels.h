@@ -35,8 +35,9 @@ __device__ __forceinline__ void relu_mask8(float4& v, unsigned bits) {
 // serialise in L2), on 32 words of one 128-byte line 13 us, on 32 words >= 256 bytes apart 0 us over the kernel
 // without atomics; reading the word first and skipping the atomic unless it raises it costs nothing there either, but a
 // fix-up workgroup that lives 5 us paid 2.5-9 us per launch for that dependent load.
+template <int WAVES = 4>          // waves of the workgroup
 __device__ __forceinline__ void amax_block_commit(unsigned m, unsigned* slot) {
-  __shared__ unsigned wmax[4];
+  __shared__ unsigned wmax[WAVES];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const unsigned t = (unsigned)__shfl_xor((int)m, o);
@@ -45,8 +46,9 @@ __device__ __forceinline__ void amax_block_commit(unsigned m, unsigned* slot) {
   if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
-    const unsigned a = wmax[0] > wmax[1] ? wmax[0] : wmax[1], b = wmax[2] > wmax[3] ? wmax[2] : wmax[3];
-    const unsigned q = a > b ? a : b;
+    unsigned q = 0;
+#pragma unroll
+    for (int i = 0; i < WAVES; ++i) q = q > wmax[i] ? q : wmax[i];
     if (q) atomicMax(slot + (size_t)((blockIdx.x + blockIdx.y) & (AMAX_SUB - 1)) * AMAX_ROW, q);
   }
 }
@@ -203,22 +205,53 @@ inline int conv_par_pixel(int B, int Ho, int Wo, int m) {
   const int cy = rr / Wc, cx = rr - cy * Wc;
   return (b * Ho + 2 * cy + py) * Wo + 2 * cx + px;
 }
-// fills a.per, launches the stream-K kernel (+ the fix-up kernel when tiles are shared)
+// plans the launch (conv_plan, unless a streaming kernel takes it), launches the kernel (+ the fix-up kernel when tiles are
+// shared); sets a.y2_done
 void launch_conv(ConvArgs& a, hipStream_t s);
 int conv_bn(const ConvArgs& a);      // tile width in N (64 or 128)
-int conv_plan(ConvArgs& a);          // number of workgroups, sets a.per
+int conv_plan(ConvArgs& a);          // number of workgroups; sets a.deep, a.dp_q, a.per, a.nwg, a.splitk
 void conv_set_mfma_mode(int mode);
 void conv_set_thread_mfma_mode(int mode);   // >= 0: overrides the process-wide mode on this host thread (an engine's own mode, per call); -1: none
 int conv_thread_mfma_mode();
 // per-launch HIP-event timing of the MFMA kernels (conv_kernels.hip)
 void conv_prof_enable(int on);
 int conv_prof_read(int max, const char** names, long* counts, double* ms, double* flops);
-void conv_prof_mark_begin(int kernel, double flops, hipStream_t s);   // launchers outside conv_kernels.hip; kernel = index into the name table
+void conv_prof_mark_begin(int kernel, double flops, hipStream_t s);   // launchers outside conv_kernels.hip; kernel = a ProfKernel id
 void conv_prof_mark_end(hipStream_t s);
-enum { kProfPresplit0 = 38 };    // first pre-split kernel in the name table: wgrad_p, wgrad_p_group
+// The profiled kernels: id and reported name of every record, in the order conv_prof_read reports them.  Families of four
+// are <128, false>, <128, true>, <64, false>, <64, true> (convs: tile width, K-major) or <128, 128>, <128, 64>, <64, 128>,
+// <64, 64> (weight gradients); a launcher adds the member's offset to the family's first id.
+#define EOSVOS_PROF_KERNELS(X) \
+  X(kProfConvX6, "conv_x6_kernel<128, false>") X(kProfConvX6_1, "conv_x6_kernel<128, true>") \
+  X(kProfConvX6_2, "conv_x6_kernel<64, false>") X(kProfConvX6_3, "conv_x6_kernel<64, true>") \
+  X(kProfWgradX6, "wgrad_x6_kernel<128, 128>") X(kProfWgradX6_1, "wgrad_x6_kernel<128, 64>") \
+  X(kProfWgradX6_2, "wgrad_x6_kernel<64, 128>") X(kProfWgradX6_3, "wgrad_x6_kernel<64, 64>") \
+  X(kProfConvIgemm, "conv_igemm_kernel<128, false, *>") X(kProfConvIgemm_1, "conv_igemm_kernel<128, true, *>") \
+  X(kProfConvIgemm_2, "conv_igemm_kernel<64, false, 0>") X(kProfConvIgemm_3, "conv_igemm_kernel<64, true, 0>") \
+  X(kProfWgrad, "wgrad_kernel<128, 128>") X(kProfWgrad_1, "wgrad_kernel<128, 64>") \
+  X(kProfWgrad_2, "wgrad_kernel<64, 128>") X(kProfWgrad_3, "wgrad_kernel<64, 64>") \
+  X(kProfFixup, "conv_fixup_kernel") \
+  X(kProfWgradX6Group, "wgrad_x6_group_kernel<128, 128>") X(kProfWgradX6Group_1, "wgrad_x6_group_kernel<128, 64>") \
+  X(kProfWgradX6Group_2, "wgrad_x6_group_kernel<64, 128>") X(kProfWgradX6Group_3, "wgrad_x6_group_kernel<64, 64>") \
+  X(kProfConvH3, "conv_h3_kernel<128, false>") X(kProfConvH3_1, "conv_h3_kernel<128, true>") \
+  X(kProfConvH3_2, "conv_h3_kernel<64, false>") X(kProfConvH3_3, "conv_h3_kernel<64, true>") \
+  X(kProfWgradH3, "wgrad_h3_kernel<128, 128>") X(kProfWgradH3_1, "wgrad_h3_kernel<128, 64>") \
+  X(kProfWgradH3_2, "wgrad_h3_kernel<64, 128>") X(kProfWgradH3_3, "wgrad_h3_kernel<64, 64>") \
+  X(kProfWgradH3Group, "wgrad_h3_group_kernel<128, 128>") X(kProfWgradH3Group_1, "wgrad_h3_group_kernel<128, 64>") \
+  X(kProfWgradH3Group_2, "wgrad_h3_group_kernel<64, 128>") X(kProfWgradH3Group_3, "wgrad_h3_group_kernel<64, 64>") \
+  X(kProfConvH3Multi, "conv_h3_multi_kernel") X(kProfConvX6Multi, "conv_x6_multi_kernel") \
+  X(kProfStream1x1_128, "conv1x1_stream_kernel<*, 128>") X(kProfStream1x1_64, "conv1x1_stream_kernel<*, 64>") \
+  X(kProfStream3x3, "conv3x3_stream_kernel") \
+  X(kProfWgradP, "wgrad_p_kernel<256, 256>") X(kProfWgradPGroup, "wgrad_p_group_kernel<256, 256>")      /* presplit_kernels.hip */
+enum ProfKernel {
+#define EOSVOS_PROF_ID(id, name) id,
+  EOSVOS_PROF_KERNELS(EOSVOS_PROF_ID)
+#undef EOSVOS_PROF_ID
+  kProfKernels
+};
 double conv_exec_frac(const struct ConvArgs& a);
 double wgrad_exec_frac(const struct WgradArgs& a);
-int conv_mfma_mode();                // 1: bf16x6 split kernels (default), 0: fp32 MFMA kernels (EOSVOS_MFMA=f32), 2: f16x3 (EOSVOS_MFMA=f16x3)
+int conv_mfma_mode();                // 2: f16x3 split kernels (default), 1: bf16x6 (EOSVOS_MFMA=bf16x6), 0: fp32 MFMA kernels (EOSVOS_MFMA=f32)
 // max|x| over rows x C floats (row pitch ld): atomicMax of the bit patterns into *slot (the caller zeroes the slot first)
 void launch_absmax(const float* x, long rows, int C, int ld, unsigned* slot, hipStream_t s);
 // zero `count` consecutive absmax slots (every word of each)
@@ -231,7 +264,8 @@ int64_t conv_ws_floats();
 }  // namespace eosvos
 #include <vector>
 namespace eosvos {
-long conv_build_tap_table(const ConvArgs& a, std::vector<int>& prefix, std::vector<int>& mask);            // size of ConvArgs::ws the launch may use
+// per-tile compacted K-step prefix (tiles + 1 entries) and valid-tap masks; returns the total number of valid K steps
+long conv_build_tap_table(const ConvArgs& a, std::vector<int>& prefix, std::vector<int>& mask);
 // K-concatenated data gradient: per segment (kernel size k, dilation, padding, channel offset, weight offset, norm-scale
 // offset); fills the global tap descriptors, the per-tile tap lists (32 bytes per tile) and the K-step prefix; returns the
 // total number of K steps

@@ -18,6 +18,7 @@
 //   * Bank swizzle on the SOURCE address: chunk c of pixel row k lies at slot c ^ f(k), f(k) = k0 | k1 << 2 | k3 << 3; the 8
 //     pixel rows x 2 chunks a 32-lane half of one transposed read touches then cover the 16 slots of a 256-byte bank row.
 #include "kernels.h"
+#include "conv_tile.h"
 #include <stdlib.h>
 
 namespace eosvos {
@@ -30,10 +31,6 @@ typedef float pf32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((__vector_size__(4 * sizeof(__fp16)))) __fp16 ph4;
 #define P_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
 
-__device__ __forceinline__ int p_xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, x = bid & 7, i = bid >> 3;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-}
 __device__ __forceinline__ unsigned p_pack(float e0, float e1) {
   pf32x2 v = {e0, e1};
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, pf16x2));
@@ -311,13 +308,13 @@ __device__ __forceinline__ void wgrad_p_body(const WgradPArgs& p, const int bid,
 template <int BM, int BN>
 __global__ __launch_bounds__(512, 1) void wgrad_p_kernel(const WgradPArgs p) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[131072];
-  wgrad_p_body<BM, BN>(p, p_xcd_remap(blockIdx.x, gridDim.x), smem);
+  wgrad_p_body<BM, BN>(p, xcd_remap(blockIdx.x, gridDim.x), smem);
 }
 // several weight gradients in one launch (wgrad_h3_group_kernel's scheme): workgroup w works on entry map[w].x as its workgroup map[w].y
 template <int BM, int BN>
 __global__ __launch_bounds__(512, 1) void wgrad_p_group_kernel(const WgradPArgs* __restrict__ tab, const int2* __restrict__ map) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[131072];
-  const int2 m = map[p_xcd_remap(blockIdx.x, gridDim.x)];
+  const int2 m = map[xcd_remap(blockIdx.x, gridDim.x)];
   const int ent = __builtin_amdgcn_readfirstlane(m.x), bid = __builtin_amdgcn_readfirstlane(m.y);
   const WgradPArgs p = tab[ent];
   wgrad_p_body<BM, BN>(p, bid, smem);
@@ -350,12 +347,12 @@ static double wgrad_p_flops(const WgradPArgs& a) {
 }
 void launch_wgrad_p(const WgradPArgs& a, hipStream_t s) {
   const int nwg = wgrad_p_tiles(a) * (a.groups > 0 ? a.groups : a.splits);
-  conv_prof_mark_begin(kProfPresplit0, wgrad_p_flops(a), s);
+  conv_prof_mark_begin(kProfWgradP, wgrad_p_flops(a), s);
   hipLaunchKernelGGL((wgrad_p_kernel<256, 256>), dim3(nwg), dim3(512), 0, s, a);
   conv_prof_mark_end(s);
 }
 void launch_wgrad_p_group(const WgradPArgs* dev_tab, const int* dev_map, int nwg, double flops, hipStream_t s) {
-  conv_prof_mark_begin(kProfPresplit0 + 1, flops, s);
+  conv_prof_mark_begin(kProfWgradPGroup, flops, s);
   hipLaunchKernelGGL((wgrad_p_group_kernel<256, 256>), dim3(nwg), dim3(512), 0, s, dev_tab, reinterpret_cast<const int2*>(dev_map));
   conv_prof_mark_end(s);
 }

@@ -328,6 +328,44 @@ def test_data_gradient_with_a_fused_add(eng, shape, add_ld):
     _run_dgrad(eng, 'f16x3', f'c1add {shape} {add_ld}', 'auto', shape + C1, want, add_ld=add_ld)
 
 
+@pytest.mark.parametrize('mode', MODES)
+@pytest.mark.parametrize('plan', ['b1_1025px', 'b2_546px', 'fixup'])
+def test_added_tensor_goes_in_before_the_old_contents(eng, mode, plan):
+    """A data gradient with BOTH a fused add and accumulate: g_xin = M * ((dgrad + g_out) + g_xin), in that order.  The two sums
+    commute up to one rounding, which no tolerance sees, so the operands are small integers and powers of two: the contraction
+    is exact in every matrix mode and the result must equal the two fp32 additions bit for bit.  `b1_1025px`: the streaming
+    kernel in f16x3, the tiled kernel of the mode otherwise (as `b2_546px` in every mode); `fixup`: K = 512 under a
+    64-workgroup budget is streamed, the order is then the fix-up pass's."""
+    B, H, W = (1, 25, 41) if plan == 'b1_1025px' else (2, 13, 21)
+    Ci, Co = 256, 512 if plan == 'fixup' else 64
+    gen = torch.Generator().manual_seed(Co + B)
+    g = torch.randint(-2, 3, (B, H, W, Co), generator=gen).float()
+    w = torch.randint(-1, 2, (Co, Ci, 1, 1), generator=gen).float()
+    a = 2.0 ** torch.randint(-1, 2, (Co,), generator=gen).float()
+    core = R.dgrad_ref(g, w, a, (H, W), 1, 1, 0).float()
+    assert bool((core * 2 == (core * 2).round()).all()) and float(core.abs().max()) < 2 ** 14      # multiples of 1/2: exact in every mode
+    sd = float(core.std())
+    addt, gx0 = torch.randn(B, H, W, Ci, generator=gen) * sd, torch.randn(B, H, W, Ci, generator=gen) * sd
+    m8 = torch.randint(0, 16, (B, H, W, Ci // 4), generator=gen, dtype=torch.uint8)
+    M = R.unpack_bits(m8)
+    want = torch.where(M, (core + addt) + gx0, torch.zeros(()))
+    swapped = torch.where(M, (core + gx0) + addt, torch.zeros(()))
+    assert not _same_bits(want, swapped), 'the data cannot tell the two orders apart'
+    stream = plan == 'b1_1025px' and mode == 'f16x3'
+    syms = [('conv1x1_stream_kernel<*, 128>',) if stream else tiled(mode, True, 128)] + ([FIXUP] if plan == 'fixup' else [])
+    gx = gx0.to(DEV).clone()
+    if plan == 'fixup':
+        eng.set_wg_budget(64)
+    try:
+        with matrix_mode(mode), symbols(eng, syms, f'both {plan} {mode}'):
+            eng.test_conv_views('auto', w.to(DEV), 1, 1, 0, (B, H, W), scale=a.to(DEV), g=g.to(DEV), gx=gx, add=addt.to(DEV),
+                                accum=True, gx_m8=m8.to(DEV))
+    finally:
+        if plan == 'fixup':
+            eng.set_wg_budget(0)          # the module's engine runs under the default budget
+    assert _same_bits(gx.cpu(), want), f'{plan} {mode}: {int((_bits(gx.cpu()) != _bits(want)).sum())} elements differ'
+
+
 @pytest.mark.parametrize('accum', [False, True], ids=['zero', 'accum'])
 def test_stride2_coarse_grid_scatter(eng, accum):
     """The stride-2 1x1 downsample gradient runs on the coarse grid and scatters to the even pixels: the others are zero, or
