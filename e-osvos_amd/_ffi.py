@@ -98,6 +98,10 @@ _SIGNATURES = {
     'eosvos_lucid_compose': (ctypes.c_int, [_E, c_float_p, c_float_p, c_float_p] + [ctypes.c_int] * 4 +
                              [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double), c_float_p, c_float_p,
                               ctypes.POINTER(ctypes.c_int32)]),
+    'eosvos_lucid_compose_layers': (ctypes.c_int, [_E, c_float_p, ctypes.c_void_p, c_float_p] + [ctypes.c_int] * 4 +
+                                    [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                     ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_double), ctypes.c_int, c_float_p,
+                                     c_float_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     'eosvos_distance_sq': (ctypes.c_int, [_E, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_void_p]),
     'eosvos_adapt_targets': (ctypes.c_int, [_E, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int] +

@@ -191,6 +191,18 @@ ADAPT = {
 }
 
 
+# The sequence's other objects as moving layers of the lucid synthesis, handled like the groups above (not part of BASE, added by
+# `parse_cli` only when the command line sets one of its keys: `eval_lucid_layers.others=3` -- an example value, untuned; read
+# with `cfg.get(...)`).  `eval_lucid` keeps its own nine keys.
+#   eval_lucid_layers up to `others` of the other objects annotated on the target's train frame are cut out with it and moved on
+#                     their own over the filled plate, each in front of the target with probability `front`
+#                     (`lucid_layers.py`); the value below is the neutral one (`lucid_layers.DEFAULTS`: others 0, nothing new
+#                     is called, nothing is drawn).  Active, it needs `eval_lucid.samples` > 0.
+LAYERS = {
+    'eval_lucid_layers': {'others': 0, 'front': 0.5},
+}
+
+
 def _merge(dst, src):
     for k, v in src.items():
         if isinstance(v, dict) and isinstance(dst.get(k), dict):
@@ -237,7 +249,7 @@ def parse_cli(argv):
             raise KeyError(f'unknown named config: {a}')
     for k, v in updates:
         group = k.split('.')[0]
-        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL, SNAP, MOTION, ZOOM, LUCID, ADAPT):
+        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL, SNAP, MOTION, ZOOM, LUCID, ADAPT, LAYERS):
             if group in groups and group not in cfg:
                 cfg[group] = copy.deepcopy(groups[group])
         _set_dotted(cfg, k, v)
@@ -277,6 +289,11 @@ def parse_cli(argv):
         from .adapt import active as adapts
         if adapts(cfg['eval_adapt']) and not cfg['eval_online_adapt']['step']:      # ValueError: neg_dist 4096, erode -1, a float, ...
             raise ValueError('eval_adapt has no consumer: set eval_online_adapt.step')
+    if 'eval_lucid_layers' in cfg:
+        from .lucid import active as lucid_on
+        from .lucid_layers import active as layered
+        if layered(cfg['eval_lucid_layers']) and not lucid_on(cfg.get('eval_lucid')):   # ValueError: others 8, front 1.5, a float, ...
+            raise ValueError('eval_lucid_layers has no consumer: set eval_lucid.samples')
     unsupported(cfg)
     return cfg
 

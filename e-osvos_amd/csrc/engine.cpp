@@ -3004,6 +3004,38 @@ int eosvos_lucid_compose(eosvos_engine* e, const float* frame, const float* mask
   HIPOK(hipGetLastError());
   return read_counts(e, ScratchAt<int>{0}, n_samples, counts_host);            // the batch attempt's one host read
 }
+int eosvos_lucid_compose_layers(eosvos_engine* e, const float* frame, const uint8_t* ids, const float* plate, int channels,
+                                int height, int width, int n_samples, const int32_t* flips, const int32_t* n_layers,
+                                const uint8_t* layer_ids, const double* matrices, int target_id, float* images, float* labels,
+                                uint8_t* ids_out, int32_t* counts_host) {
+  if (!e || !frame || !ids || !plate || !flips || !n_layers || !layer_ids || !matrices || !images || !labels)
+    return fail("lucid_compose_layers: null argument");
+  if (lucid_check("lucid_compose_layers", channels, height, width)) return 1;
+  if (n_samples < 1 || n_samples > LUCID_LAYERS_MAX_SAMPLES)
+    return fail("lucid_compose_layers: between 1 and " + std::to_string(LUCID_LAYERS_MAX_SAMPLES) + " samples per call");
+  if (target_id < 1 || target_id > 255) return fail("lucid_compose_layers: target_id must be in [1, 255]");
+  for (int i = 0; i < n_samples; ++i) {
+    const int nl = n_layers[i];
+    if (nl < 1 || nl > LUCID_MAX_LAYERS)
+      return fail("lucid_compose_layers: between 1 and " + std::to_string(LUCID_MAX_LAYERS) + " layers per sample");
+    const uint8_t* id = layer_ids + (size_t)i * LUCID_MAX_LAYERS;
+    for (int k = 0; k < nl; ++k) {
+      if (id[k] == 0) return fail("lucid_compose_layers: a layer id must be in [1, 255]");
+      for (int j = 0; j < k; ++j)
+        if (id[j] == id[k]) return fail("lucid_compose_layers: the layer ids of a sample must be distinct");
+    }
+    const double* m = matrices + (size_t)i * (1 + LUCID_MAX_LAYERS) * 6;       // Bi and the nl layer matrices are read
+    for (int j = 0; j < (1 + nl) * 6; ++j)
+      if (!std::isfinite(m[j])) return fail("lucid_compose_layers: the matrices must be finite");
+  }
+  if (aug_tables(e)) return 1;
+  const LucidLayersLayout L(n_samples);
+  if (scratch_for(e, "lucid_compose_layers", L, n_samples)) return 1;
+  launch_lucid_layers(frame, ids, plate, channels, height, width, n_samples, flips, n_layers, layer_ids, matrices, target_id,
+                      e->aug_ctab, images, labels, ids_out, scratch_at(e, L.counts), e->s);
+  HIPOK(hipGetLastError());
+  return read_counts(e, L.counts, (size_t)n_samples * LUCID_MAX_LAYERS, counts_host);   // the batch attempt's one host read
+}
 
 // ---- online adaptation: the capped distance transform and the distance-gated targets (OnAVOS; evaluate.py:231-240) ------
 static int edt_check(const char* who, int n_frames, int height, int width) {

@@ -563,6 +563,16 @@ void launch_lucid_plate(const float* frame, const float* mask, int C, int H, int
 void launch_lucid_compose(const float* frame, const float* mask, const float* plate, int C, int H, int W, int n_samples,
                           const int* flips, const double* matrices, const float* ctab, float* images, float* labels, int* counts,
                           hipStream_t s);
+// launch_lucid_layers (rules L2-L5 of eosvos_lucid_compose_layers): ONE launch for n_samples <= LUCID_LAYERS_MAX_SAMPLES, each
+// with n_layers[i] in [1, LUCID_MAX_LAYERS] layers, back to front.  ids [H][W] uint8 (0 = background); flips [n], n_layers [n],
+// layer_ids [n][8] and matrices [n][9][6] (Bi, then Oi_0 .. Oi_7) are HOST arrays copied into the launch's arguments (8 samples
+// of 9 matrices are 3.5 KB of HIP's 4 KB); labels = 1.f where the visible layer carries target_id; ids_out [n][H][W] may be
+// null; counts [n][8] int32 on the device, ZEROED BY THE CALLER on the same stream.
+#define LUCID_MAX_LAYERS 8
+#define LUCID_LAYERS_MAX_SAMPLES 8
+void launch_lucid_layers(const float* frame, const uint8_t* ids, const float* plate, int C, int H, int W, int n_samples,
+                         const int* flips, const int* n_layers, const uint8_t* layer_ids, const double* matrices, int target_id,
+                         const float* ctab, float* images, float* labels, uint8_t* ids_out, int* counts, hipStream_t s);
 
 // Capped squared distance transform and the distance-gated targets of online adaptation (edt_kernels.hip; the rules:
 // include/eosvos.h, eosvos_distance_sq / eosvos_adapt_targets).  probs / anchors / targets [frame][H][W] fp32, H, W <= 4096,

@@ -13,6 +13,9 @@
 //                         reads what it writes.
 //   lucid_compose_kernel  one thread per output pixel, rows of 256, the sample in the grid's third dimension.  The samples'
 //                         matrices travel by value (LucidParams), so a queued launch owns everything it reads.
+//   lucid_layers_kernel   the same launch shape for the layered samples (eosvos_lucid_compose_layers): up to 8 layers per sample,
+//                         each a label of the id map moved by its own matrix, composed back to front; the coordinate, coverage
+//                         and bicubic code is the compose kernel's (lucid_coords, lucid_coverage, lucid_cubic).
 // Every level is written in full by every call (level 0 and the pushes write each element, the pulls only overwrite), so the
 // result does not depend on what the scratch held.  fp32 with every operation rounded on its own (no contraction), in the
 // order of the numpy twin; no float atomics; the count is an integer sum.  One writer per element, no cooperative launch, no
@@ -124,6 +127,30 @@ __device__ __forceinline__ float lucid_cubic(const float* __restrict__ S, int H,
   return sum;
 }
 
+// rule 6: the source coordinates of output pixel (y, xm) under the inverse matrix m, 5 fractional bits
+__device__ __forceinline__ void lucid_coords(const double* m, int y, int xm, int& X, int& Y) {
+  const int rd = 16;                                      // the interpolating round_delta of warp_affine_kernel
+  X = (warp_fix(m[1], y, m[2], rd) + warp_fix(m[0], xm)) >> 5;
+  Y = (warp_fix(m[4], y, m[5], rd) + warp_fix(m[3], xm)) >> 5;
+}
+
+// rule 7: the coverage in 1/1024 of the 2 x 2 bilinear taps at (oy + i, ox + j) with the fractions (fy, fx) in 1/32; on(index)
+// is the tap predicate, asked only inside the frame
+template <class On>
+__device__ __forceinline__ int lucid_coverage(int H, int W, int oy, int ox, int fy, int fx, On on) {
+  int A = 0;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int yy = oy + i, xx = ox + j;
+      const bool hit = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W && on((long)yy * W + xx);
+      A += hit ? (i ? fy : 32 - fy) * (j ? fx : 32 - fx) : 0;
+    }
+  }
+  return A;
+}
+
 // grid (ceil(W / 256), H, samples), block 256.  No thread leaves before the wave sum.
 __global__ __launch_bounds__(256) void lucid_compose_kernel(const float* __restrict__ frame, const float* __restrict__ mask,
                                                              const float* __restrict__ plate, int C, int H, int W,
@@ -136,22 +163,11 @@ __global__ __launch_bounds__(256) void lucid_compose_kernel(const float* __restr
     const LucidSample& p = prm.s[s];
     const long hw = (long)H * W, o = (long)y * W + x;
     const int xm = p.flip ? W - 1 - x : x;
-    const int rd = 16;                                    // the interpolating round_delta of warp_affine_kernel
-    const int Xo = (warp_fix(p.oi[1], y, p.oi[2], rd) + warp_fix(p.oi[0], xm)) >> 5;
-    const int Yo = (warp_fix(p.oi[4], y, p.oi[5], rd) + warp_fix(p.oi[3], xm)) >> 5;
-    const int Xb = (warp_fix(p.bi[1], y, p.bi[2], rd) + warp_fix(p.bi[0], xm)) >> 5;
-    const int Yb = (warp_fix(p.bi[4], y, p.bi[5], rd) + warp_fix(p.bi[3], xm)) >> 5;
+    int Xo, Yo, Xb, Yb;
+    lucid_coords(p.oi, y, xm, Xo, Yo);
+    lucid_coords(p.bi, y, xm, Xb, Yb);
     const int ox = Xo >> 5, oy = Yo >> 5, fx = Xo & 31, fy = Yo & 31;
-    int A = 0;                                            // coverage in 1/1024
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int yy = oy + i, xx = ox + j;
-        const bool on = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W && mask[(long)yy * W + xx] != 0.f;
-        A += on ? (i ? fy : 32 - fy) * (j ? fx : 32 - fx) : 0;
-      }
-    }
+    const int A = lucid_coverage(H, W, oy, ox, fy, fx, [&](long at) { return mask[at] != 0.f; });   // coverage in 1/1024
     lab = A >= 512;
     labels[(long)s * hw + o] = lab ? 1.f : 0.f;
     const float alpha = (float)A * (1.f / 1024.f);        // exact
@@ -170,6 +186,85 @@ __global__ __launch_bounds__(256) void lucid_compose_kernel(const float* __restr
   }
   lab = wave_sum_i(lab);
   if ((threadIdx.x & 63) == 0 && lab) atomicAdd(counts + s, lab);
+}
+
+// The layered samples (rules L2-L5 of include/eosvos.h): per sample the inverse background matrix and up to LUCID_MAX_LAYERS
+// inverse layer matrices, back to front, each with the id its layer carries in `ids`.
+struct LucidLayerSample { double bi[6], oi[LUCID_MAX_LAYERS][6]; int flip, n_layers; uint8_t id[LUCID_MAX_LAYERS]; };
+struct LucidLayerParams { LucidLayerSample s[LUCID_LAYERS_MAX_SAMPLES]; };
+// HIP passes at most 4 KB of kernel arguments; the pointers and sizes beside the samples take 88 bytes
+static_assert(sizeof(LucidLayerParams) + 128 <= 4096, "LucidLayerParams must fit the kernel-argument segment: lower LUCID_LAYERS_MAX_SAMPLES");
+
+// layer k's coverage at output pixel (y, xm), with its coordinates
+__device__ __forceinline__ int lucid_layer_coverage(const LucidLayerSample& p, int k, const uint8_t* __restrict__ ids, int H, int W,
+                                                    int y, int xm, int& Xo, int& Yo) {
+  lucid_coords(p.oi[k], y, xm, Xo, Yo);
+  const int id = p.id[k];
+  return lucid_coverage(H, W, Yo >> 5, Xo >> 5, Yo & 31, Xo & 31, [&](long at) { return ids[at] == id; });
+}
+
+// grid (ceil(W / 256), H, samples), block 256.  No thread leaves before the wave sums.  Two walks over the sample's layers, both
+// uniform in k (the matrices are scalar loads): the first takes the coverages alone -- the visible layer, the front-most opaque
+// one and which layers touch the pixel at all --, the second samples the frame for the touching layers from the opaque one
+// upwards, four channels at a time.  What lies under an opaque layer is overwritten by rule L4 and never computed.
+__global__ __launch_bounds__(256) void lucid_layers_kernel(const float* __restrict__ frame, const uint8_t* __restrict__ ids,
+                                                            const float* __restrict__ plate, int C, int H, int W,
+                                                            const LucidLayerParams prm, int target_id,
+                                                            const float* __restrict__ ctab, float* __restrict__ images,
+                                                            float* __restrict__ labels, uint8_t* __restrict__ ids_out,
+                                                            int* __restrict__ counts) {
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, s = blockIdx.z;
+  const LucidLayerSample& p = prm.s[s];
+  const int L = p.n_layers;
+  int top = -1;                                           // the visible layer: the largest k with A_k >= 512
+  if (x < W) {
+    const long hw = (long)H * W, o = (long)y * W + x;
+    const int xm = p.flip ? W - 1 - x : x;
+    int opaque = -1;                                      // the largest k with A_k == 1024
+    unsigned touch = 0;                                   // bit k: A_k > 0
+    for (int k = 0; k < L; ++k) {
+      int Xo, Yo;
+      const int A = lucid_layer_coverage(p, k, ids, H, W, y, xm, Xo, Yo);
+      top = A >= 512 ? k : top;
+      opaque = A == 1024 ? k : opaque;
+      touch |= (A > 0 ? 1u : 0u) << k;
+    }
+    const int id_top = top >= 0 ? p.id[top] : 0;
+    labels[(long)s * hw + o] = id_top == target_id ? 1.f : 0.f;
+    if (ids_out) ids_out[(long)s * hw + o] = (uint8_t)id_top;
+    int Xb, Yb;
+    lucid_coords(p.bi, y, xm, Xb, Yb);
+    const float* bcx = ctab + (Xb & 31) * 4;
+    const float* bcy = ctab + (Yb & 31) * 4;
+    for (int c0 = 0; c0 < C; c0 += 4) {
+      float v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        v[j] = opaque < 0 && c0 + j < C ? lucid_cubic(plate + (c0 + j) * hw, H, W, (Yb >> 5) - 1, (Xb >> 5) - 1, bcy, bcx) : 0.f;
+      for (int k = max(opaque, 0); k < L; ++k) {
+        if (!((touch >> k) & 1)) continue;
+        int Xo, Yo;
+        const int A = lucid_layer_coverage(p, k, ids, H, W, y, xm, Xo, Yo);
+        const float alpha = (float)A * (1.f / 1024.f);    // exact
+        const float* ocx = ctab + (Xo & 31) * 4;
+        const float* ocy = ctab + (Yo & 31) * 4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (c0 + j < C) {
+            const float ob = lucid_cubic(frame + (c0 + j) * hw, H, W, (Yo >> 5) - 1, (Xo >> 5) - 1, ocy, ocx);
+            v[j] = A == 1024 ? ob : v[j] + alpha * (ob - v[j]);
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (c0 + j < C) images[((long)s * C + c0 + j) * hw + o] = v[j];
+    }
+  }
+  for (int k = 0; k < L; ++k) {                           // one wave sum and at most one integer atomic per layer
+    const int n = wave_sum_i(top == k);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(counts + s * LUCID_MAX_LAYERS + k, n);
+  }
 }
 }  // namespace
 
@@ -226,5 +321,23 @@ void launch_lucid_compose(const float* frame, const float* mask, const float* pl
   }
   hipLaunchKernelGGL(lucid_compose_kernel, dim3((W + 255) / 256, H, n_samples), dim3(256), 0, s, frame, mask, plate, C, H, W, prm, ctab,
                      images, labels, counts);
+}
+void launch_lucid_layers(const float* frame, const uint8_t* ids, const float* plate, int C, int H, int W, int n_samples,
+                         const int* flips, const int* n_layers, const uint8_t* layer_ids, const double* matrices, int target_id,
+                         const float* ctab, float* images, float* labels, uint8_t* ids_out, int* counts, hipStream_t s) {
+  LucidLayerParams prm = {};
+  for (int i = 0; i < n_samples; ++i) {
+    LucidLayerSample& p = prm.s[i];
+    const double* m = matrices + (size_t)i * (1 + LUCID_MAX_LAYERS) * 6;
+    for (int j = 0; j < 6; ++j) p.bi[j] = m[j];
+    for (int k = 0; k < n_layers[i]; ++k) {
+      for (int j = 0; j < 6; ++j) p.oi[k][j] = m[(1 + k) * 6 + j];
+      p.id[k] = layer_ids[i * LUCID_MAX_LAYERS + k];
+    }
+    p.flip = flips[i] != 0;
+    p.n_layers = n_layers[i];
+  }
+  hipLaunchKernelGGL(lucid_layers_kernel, dim3((W + 255) / 256, H, n_samples), dim3(256), 0, s, frame, ids, plate, C, H, W, prm,
+                     target_id, ctab, images, labels, ids_out, counts);
 }
 }  // namespace eosvos

@@ -81,6 +81,10 @@ struct AdaptTargetsLayout : ScratchLayout {                    // only the count
   ScratchAt<uint8_t> eroded;
   AdaptTargetsLayout(size_t n, size_t np, bool erode) : n(n), np(np), eroded(take<uint8_t>("eroded", erode ? np : 0)) { clear(0, g.at); }
 };
+struct LucidLayersLayout : ScratchLayout {                     // the visible-pixel counts [n][8 layers] start out as 0
+  ScratchAt<int> counts;
+  explicit LucidLayersLayout(size_t n) : counts(take<int>("counts", n * 8)) { clear(0, end); }
+};
 // the counts of all frames (they start out as 0), then the two bit-packed boundary maps (map_words per frame each) of one chunk
 // of frames: as many frames as 64 MB hold, at least one
 struct DavisCountsLayout : ScratchLayout {

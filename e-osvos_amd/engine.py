@@ -744,6 +744,53 @@ class Engine:
                                                  _ptr(labels), counts))
         return images, labels, (list(counts) if read_counts else None)
 
+    def lucid_compose_layers(self, frame, ids, plate, samples, target_id=1, read_counts=True, want_ids=False):
+        """`eosvos_lucid_compose_layers` (`lucid_layers.py`, rules L2-L5): ONE launch for the samples = [{'flip', 'Bi', 'layers':
+        [(id, Oi), ...] back to front}] (at most 8 samples of at most 8 layers; the matrices are the inverse ones, 6 doubles
+        each) over the id map `ids` (H, W) uint8 -> (images (S, C, H, W), labels (S, 1, H, W): 1 where the visible layer carries
+        `target_id`, counts: per sample the list of its layers' visible pixel counts after one host read, or None without
+        `read_counts`, when nothing waits for the GPU; ids_out (S, H, W) uint8 with `want_ids`, else None)."""
+        from . import lucid_layers as ll
+        self._check_zoom('lucid_compose_layers', frame, 'frame')
+        if frame.dim() != 3 or frame.shape[0] < 1 or min(frame.shape[1:]) < 1 or max(frame.shape[1:]) > ll.MAX_SIDE:
+            raise ValueError(f'lucid_compose_layers: frame must be (C, H, W) with 1 <= H, W <= {ll.MAX_SIDE}, got {tuple(frame.shape)}')
+        self._check_zoom('lucid_compose_layers', ids, 'ids', torch.uint8, frame.shape[1:])
+        self._check_zoom('lucid_compose_layers', plate, 'plate', shape=frame.shape)
+        c, h, w = (int(v) for v in frame.shape)
+        n = len(samples)
+        if not 1 <= n <= ll.MAX_SAMPLES_PER_LAUNCH:
+            raise ValueError(f'lucid_compose_layers: between 1 and {ll.MAX_SAMPLES_PER_LAUNCH} samples per call, got {n}')
+        if isinstance(target_id, bool) or not isinstance(target_id, int) or not 1 <= target_id <= 255:
+            raise ValueError(f'lucid_compose_layers: target_id={target_id!r}: an integer in [1, 255]')
+        flips = (ctypes.c_int32 * n)(*[int(bool(p['flip'])) for p in samples])
+        n_layers = (ctypes.c_int32 * n)(*[len(p['layers']) for p in samples])
+        layer_ids = (ctypes.c_uint8 * (ll.MAX_LAYERS * n))()
+        mats = (ctypes.c_double * (6 * (1 + ll.MAX_LAYERS) * n))()
+        for s, p in enumerate(samples):
+            layers = list(p['layers'])
+            if not 1 <= len(layers) <= ll.MAX_LAYERS:
+                raise ValueError(f'lucid_compose_layers: between 1 and {ll.MAX_LAYERS} layers per sample, got {len(layers)}')
+            rows = [tuple(p['Bi'])] + [tuple(oi) for _, oi in layers]
+            if any(len(r) != 6 for r in rows):
+                raise ValueError('lucid_compose_layers: every matrix has 6 numbers')
+            for k, (i, _) in enumerate(layers):
+                if isinstance(i, bool) or not isinstance(i, int) or not 1 <= i <= 255:
+                    raise ValueError(f'lucid_compose_layers: layer id {i!r}: an integer in [1, 255]')
+                layer_ids[s * ll.MAX_LAYERS + k] = i
+            for k, r in enumerate(rows):
+                for j, v in enumerate(r):
+                    mats[(s * (1 + ll.MAX_LAYERS) + k) * 6 + j] = float(v)
+        self._check_stream()
+        images = torch.empty(n, c, h, w, device=self.device)
+        labels = torch.empty(n, 1, h, w, device=self.device)
+        ids_out = torch.empty(n, h, w, dtype=torch.uint8, device=self.device) if want_ids else None
+        counts = (ctypes.c_int32 * (ll.MAX_LAYERS * n))() if read_counts else None
+        _ffi.check(self.lib.eosvos_lucid_compose_layers(self.h, _ptr(frame), _ptr(ids), _ptr(plate), c, h, w, n, flips, n_layers,
+                                                        layer_ids, mats, target_id, _ptr(images), _ptr(labels), _optr(ids_out),
+                                                        counts))
+        per_sample = [list(counts[s * ll.MAX_LAYERS:s * ll.MAX_LAYERS + n_layers[s]]) for s in range(n)] if read_counts else None
+        return images, labels, per_sample, ids_out
+
     def merge_labels(self, probs):
         """probs: (n_obj, H, W) device fp32 -> (H, W) uint8.  `evaluate.py:322-326`."""
         probs = probs.contiguous()

@@ -80,7 +80,8 @@ def run(cfg, run_dir, device, data_root='data', height=480, width=854, num_frame
                                        **({'motion': cfg['eval_motion']} if cfg.get('eval_motion') is not None else {}),
                                        **({'zoom': cfg['eval_zoom']} if cfg.get('eval_zoom') is not None else {}),
                                        **({'lucid': cfg['eval_lucid']} if cfg.get('eval_lucid') is not None else {}),
-                                       **({'adapt': cfg['eval_adapt']} if cfg.get('eval_adapt') is not None else {}))
+                                       **({'adapt': cfg['eval_adapt']} if cfg.get('eval_adapt') is not None else {}),
+                                       **({'layers': cfg['eval_lucid_layers']} if cfg.get('eval_lucid_layers') is not None else {}))
                 best[key] = res['best_mean_J']
                 line = {'dataset': key, 'meta_iter': info['meta_iter'], 'mean_J': res['mean_J'], 'best_mean_J': best[key],
                         'J_seq': res['J_seq'], 'time_per_frame': res['time_per_frame'], 'mean_F': res['mean_F'],

@@ -28,6 +28,7 @@ from . import motion as mover
 from . import snap as snapper
 from . import tta as tta_views
 from . import lucid as lucid_pass
+from . import lucid_layers as layer_pass
 from . import zoom as zoom_pass
 from .helper_func import compute_loss, early_stopping, set_random_seeds
 
@@ -90,15 +91,18 @@ def min_prop_band(min_prop):
 
 
 def finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None,
-                    zoom=None, lucid=None, adapt=None):
+                    zoom=None, lucid=None, adapt=None, layers=None, lucid_others=None):
     """One (sequence, object) work item of `evaluate.py:132-317`: fine-tune on the train frame, predict the following
     frames, with online adaptation re-fine-tune every `step` frames.  Returns (probs (N,H,W) with the train frame seeded
     as 2*GT (`:167-168`), train-loss history per round).  `tta`: test-time augmentation of every inference call (`tta.py`).
     `zoom`: the object-centred second look after every inference call (`zoom.py`).  `lucid`: some samples of every round-0
     batch are composed with the object and its background moved independently (`lucid.py`).  `adapt`: the propagated targets of
-    the adaptation rounds are 0 wherever a pixel is far from the previous frame's mask (`adapt.py`)."""
+    the adaptation rounds are 0 wherever a pixel is far from the previous frame's mask (`adapt.py`).  `layers` with
+    `lucid_others` (M, 1, H, W), the other objects' masks at this object's train frame: the lucid samples move those objects
+    too, each on its own, behind or in front of this one (`lucid_layers.py`)."""
     return _drain(finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id,
-                                        **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid), **_adapt_kw(adapt)))
+                                        **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid), **_adapt_kw(adapt),
+                                        **_layers_kw(layers, lucid_others)))
 
 
 def _tta_kw(tta):
@@ -121,17 +125,44 @@ def _adapt_kw(adapt):
     return {} if adapt is None else {'adapt': adapt}
 
 
-def lucid_batches(model, augment, frame, gt, batch, lucid):
+def _layers_kw(layers, lucid_others=None):
+    """As `_tta_kw`: `layers` travels as a keyword, with the other objects' masks, and only when it is set."""
+    return {} if layers is None else {'layers': layers, 'lucid_others': lucid_others}
+
+
+def others_at_train_frame(gts, train_frame_ids, o):
+    """The masks (M, 1, H, W) of the objects that share object o's train frame, in object order; None when there is none."""
+    sel = [gts[j].float().reshape(1, *gts[j].shape[-2:]) for j in range(len(gts)) if j != o and train_frame_ids[j] == train_frame_ids[o]]
+    return torch.stack(sel) if sel else None
+
+
+def _others_for(layers, gts, train_frame_ids, o):
+    """`others_at_train_frame` when `layers` is active, else None: an inactive `layers` computes nothing."""
+    return others_at_train_frame(gts, train_frame_ids, o) if layer_pass.active(layers) else None
+
+
+def lucid_batches(model, augment, frame, gt, batch, lucid, layers=None, lucid_others=None):
     """The round-0 batch source of rule 12 of `lucid.py`: `fn(seed) -> (inputs, gts)` whose first batch - k samples come from
     `augment` (today's path, called for batch - k samples and not at all for 0) and whose last k = min(samples, batch) are
-    synthesised.  The plate is built at the first batch, once.  A mask that is empty or fills the frame: every batch is today's."""
+    synthesised.  The plate is built at the first batch, once.  A mask that is empty or fills the frame: every batch is today's.
+    With `layers` active and an other object in `lucid_others` (rule L9 of `lucid_layers.py`) the samples are the layered
+    ones; otherwise they are today's."""
     k = min(lucid_pass.check(lucid)['samples'], batch)
     held = []                                                       # the augmenter, built at the first batch
+    layered = layer_pass.active(layers) and lucid_others is not None and len(lucid_others) > 0
+
+    def build(eng):
+        if layered:
+            aug = layer_pass.LayeredAugmenter(eng, frame[0].contiguous(), gt[0].contiguous(),
+                                              lucid_others.to(frame.device).float().contiguous(), lucid, layers)
+            if aug.has_layers:
+                return aug
+        return lucid_pass.LucidAugmenter(eng, frame[0].contiguous(), gt[0].contiguous(), lucid)
 
     def fn(seed):
         eng = model._ensure_engine(frame.shape[2], frame.shape[3], batch)
         if not held:
-            held.append(lucid_pass.LucidAugmenter(eng, frame[0].contiguous(), gt[0].contiguous(), lucid))
+            held.append(build(eng))
         aug = held[0]
         aug.engine = eng                                            # the model's live engine (its stream, its scratch)
         if not aug.has_object:
@@ -153,7 +184,7 @@ def _drain(gen):
 
 
 def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None,
-                          zoom=None, lucid=None, adapt=None):
+                          zoom=None, lucid=None, adapt=None, layers=None, lucid_others=None):
     """`finetune_object` as a generator: it yields each time a fine-tune iteration (or a few inference frames) has been
     ENQUEUED on the model's engine and before the host waits for its loss, so that a caller holding several objects
     (one model / engine / stream each, `run_objects_in_flight`) can queue the others' work in between.  Everything
@@ -184,8 +215,10 @@ def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, 
     masks[train_frame_id] = 2 * gt[0]                               # evaluate.py:167-168
     # lucid synthesis: the last samples of every round-0 batch are composed from the train frame (the plate is built once per
     # object, at the first batch); off = nothing new is called, nothing is drawn
-    lucid_batch = lucid_batches(model, augment, frames[train_frame_id:train_frame_id + 1], gt, bsz, lucid) \
-        if lucid_pass.active(lucid) else None
+    if layers is not None:
+        layer_pass.check(layers)
+    lucid_batch = lucid_batches(model, augment, frames[train_frame_id:train_frame_id + 1], gt, bsz, lucid,
+                                **_layers_kw(layers, lucid_others)) if lucid_pass.active(lucid) else None
     hist = []
     for r, rd in enumerate(online_adapt_schedule(n, train_frame_id, step, bsz)):
         if r == 0 or ona['reset_model_mode'] == 'FULL':
@@ -314,10 +347,12 @@ def object_workers(model, meta_optim, meta_optim_cfg, n, wg_budget=256):
 
 
 def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augment=None, train_frame_id=0, tta=None, zoom=None,
-                          lucid=None, adapt=None):
+                          lucid=None, adapt=None, layers=None, lucid_others=None):
     """[(probs, hist)] for the objects `gts` of one sequence, up to len(workers) of them in flight together; results are
     those of `finetune_object` one after the other (same engine arithmetic at the same workgroup budget).
-    `train_frame_id`: one frame for all objects, or one per object (YouTube-VOS objects that appear later)."""
+    `train_frame_id`: one frame for all objects, or one per object (YouTube-VOS objects that appear later).
+    `layers` (`lucid_layers.py`): every object's lucid samples move the objects of `gts` that share its train frame too;
+    `lucid_others`, one entry per object, replaces them (a caller that holds only some of the sequence's objects)."""
     out = [None] * len(gts)
     tfid = list(train_frame_id) if isinstance(train_frame_id, (list, tuple)) else [train_frame_id] * len(gts)
     if frames.is_cuda:
@@ -335,7 +370,9 @@ def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augm
                 oi = pending.pop(0)
                 active[wi] = (oi, finetune_object_steps(w.model, w.meta_optim, meta_optim_state_dict, frames, gts[oi], cfg,
                                                         augment, tfid[oi], **_tta_kw(tta), **_zoom_kw(zoom),
-                                                        **_lucid_kw(lucid), **_adapt_kw(adapt)))
+                                                        **_lucid_kw(lucid), **_adapt_kw(adapt),
+                                                        **_layers_kw(layers, lucid_others[oi] if lucid_others is not None
+                                                                     else _others_for(layers, gts, tfid, oi))))
         for wi in sorted(active):
             oi, gen = active[wi]
             w = workers[wi]
@@ -476,7 +513,7 @@ def _motion_kw(motion, cfg, dataset=None):
 
 def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_gts, cfg, augment=None,
                       train_frame_id=0, tta=None, crf=None, components=None, holes=None, snap=None, motion=None, zoom=None,
-                      lucid=None, adapt=None):
+                      lucid=None, adapt=None, layers=None):
     """frames (N,3,H,W) on the GPU, object_gts: list of (1,H,W) binary masks of the train frame.
     cfg keys (names of cfgs/meta.yaml): num_epochs.eval, eval_online_adapt.{step,reset_model_mode,
     num_epochs,min_prop (a threshold, or [lo, hi]: `min_prop_band`)}, data_cfg.batch_sizes.train, seed, loss_func, train_early_stopping_cfg.
@@ -491,11 +528,14 @@ def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_g
     `lucid` (`lucid.py`): the last `samples` samples of every round-0 batch are composed from the train frame with the object
     and its background moved independently.
     `adapt` (`adapt.py`): the propagated targets of the adaptation rounds are gated by the distance to the previous frame's mask.
+    `layers` (`lucid_layers.py`): the lucid samples of every object move the sequence's other objects too, as layers of their own.
     Returns (labels (N,H,W) uint8, per-object probs list, train loss history per object)."""
     probs_all, hist_all = [], []
-    for gt in object_gts:
+    for o, gt in enumerate(object_gts):
+        others = _others_for(layers, object_gts, [train_frame_id] * len(object_gts), o)
         probs, hist = finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id,
-                                      **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid), **_adapt_kw(adapt))
+                                      **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid), **_adapt_kw(adapt),
+                                      **_layers_kw(layers, others))
         probs_all.append(probs)
         hist_all.append(hist)
     if crf is None and components is None and not _holes_kw(holes) and not _snap_kw(snap, cfg) and not _motion_kw(motion, cfg):
@@ -519,7 +559,7 @@ def save_label_png(path, labels_hw):
 def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dataset_key, save_dir=None,
                      meta_iter=None, meta_epoch=None, best_mean_J=0.0, dist=None, device=None, vis_win_names=None,
                      log=None, objects_in_flight=None, tta=None, crf=None, components=None, holes=None, snap=None, motion=None,
-                     zoom=None, lucid=None, adapt=None):
+                     zoom=None, lucid=None, adapt=None, layers=None):
     """The evaluation worker of `src/util/evaluate.py:111-382` for the DeepLab path: every sequence of `dataset`
     (an `eosvos_amd.data` reader), every object, fine-tune / online adaptation / inference / merge; prediction PNGs
     under `{save_dir}/best_eval_preds/{name}/{split}/{seq}/{frame}.png`, J per sequence, and the
@@ -553,6 +593,8 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
     object cut out of the train frame, the hole filled, object and background moved independently and composed again.
     `adapt` (`adapt.py`): with online adaptation, the propagated targets of every adaptation round are 0 wherever a pixel is
     farther than `neg_dist` from the (eroded) mask of the frame before it, whatever the network says there.
+    `layers` (`lucid_layers.py`): the lucid samples move up to `others` of the other objects annotated on the object's train
+    frame as layers of their own, behind or in front of it.
     Returns dict(J_seq, mean_J, best_mean_J, time_per_frame, labels={seq: (N,H,W) uint8}) and the DAVIS J / F statistics
     of `eval_davis_seq` (`evaluate.py:345-359`), one entry per object in sequence order: J_obj (the per-object J means the
     reference calls J_seq), J_recall_seq, J_decay_seq, F_seq, F_recall_seq, F_decay_seq, with mean_F and
@@ -665,7 +707,8 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
         if workers is not None and len(mine) > 1:
             res = run_objects_in_flight(workers, meta_optim_state_dict, frames, [gts[o] for o in mine], cfg,
                                         train_frame_id=[fids[o] for o in mine], **_tta_kw(tta), **_zoom_kw(zoom),
-                                        **_lucid_kw(lucid), **_adapt_kw(adapt))
+                                        **_lucid_kw(lucid), **_adapt_kw(adapt),
+                                        **_layers_kw(layers, [_others_for(layers, gts, fids, o) for o in mine]))
             for o, (p, _) in zip(mine, res):
                 probs[o] = p
         else:
@@ -674,7 +717,8 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
             for o in mine:
                 probs[o], _ = finetune_object(model, meta_optim, meta_optim_state_dict, frames, gts[o], cfg,
                                               train_frame_id=fids[o], **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid),
-                                              **_adapt_kw(adapt))
+                                              **_adapt_kw(adapt),
+                                              **_layers_kw(layers, _others_for(layers, gts, fids, o)))
         if world > 1:
             dist.all_reduce(probs)
         eval_time += time.perf_counter() - t0

@@ -211,7 +211,8 @@ def _run(cfg, run, run_dir, meta_mode, eval_proc, height, width, num_frames, num
                                             **({'motion': cfg['eval_motion']} if cfg.get('eval_motion') is not None else {}),
                                             **({'zoom': cfg['eval_zoom']} if cfg.get('eval_zoom') is not None else {}),
                                             **({'lucid': cfg['eval_lucid']} if cfg.get('eval_lucid') is not None else {}),
-                                            **({'adapt': cfg['eval_adapt']} if cfg.get('eval_adapt') is not None else {}))
+                                            **({'adapt': cfg['eval_adapt']} if cfg.get('eval_adapt') is not None else {}),
+                                            **({'layers': cfg['eval_lucid_layers']} if cfg.get('eval_lucid_layers') is not None else {}))
         if dev.startswith('cuda'):
             torch.cuda.synchronize()
         if rank == 0:

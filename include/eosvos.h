@@ -644,6 +644,46 @@ int eosvos_lucid_compose(eosvos_engine* e, const float* frame, const float* mask
                          int width, int n_samples, const int32_t* flips, const double* matrices, float* images, float* labels,
                          int32_t* counts_host);
 
+/* ---- lucid synthesis with the sequence's other objects as moving layers ------------------------------------------------ */
+/* eosvos_lucid_compose moves one object; the train frame's other annotated objects stay in the plate, move rigidly with the
+ * background and never cover the target.  Lucid data dreaming proper moves every object on its own over the filled plate, with
+ * a depth order: each object's net sees its neighbours as negatives in new places, sometimes in front of it.  An opt-in
+ * extension (eosvos_amd/lucid_layers.py, `eval_lucid_layers`), off by default; every value shown anywhere is UNTUNED.
+ * frame [C][H][W] fp32; ids [H][W] uint8: 0 = background, 1 = the target, 2 .. M + 1 = the other objects in the order given (a
+ * pixel lying in several masks takes the target if it is in the target's mask, else the largest id).
+ *  L1. plate     rules 1-5 above on the mask ids != 0: eosvos_lucid_plate, called unchanged.  The hole is the union of all
+ *        layered objects grown by `dilate`.
+ *  L2. sample    `flip` and Bi as above; a layer count L in [1, 8]; per layer k = 0 .. L - 1, BACK TO FRONT, an id id_k in
+ *        [1, 255], distinct within the sample, and an inverse matrix Oi_k.  Coordinates: rule 6 entry by entry, once for Bi and
+ *        once per Oi_k.
+ *  L3. coverage  A_k = rule 7 with the tap predicate ids(tap) == id_k: an integer in [0, 1024].
+ *  L4. image     v = Bg, the rule-8 bicubic sample of the plate at the background coordinates; then for k = 0 .. L - 1:
+ *        A_k == 1024: v = Ob_k; else A_k > 0: v = v + (A_k / 1024) * (Ob_k - v); else v unchanged.  Ob_k = the rule-8 bicubic
+ *        sample of the frame at layer k's coordinates.  fp32, every operation rounded on its own.  The kernel starts at the
+ *        front-most layer with A == 1024 (what lies under it is overwritten) and samples Ob_k only where A_k > 0: the bits are
+ *        the rule's either way.
+ *  L5. visible   top = the largest k with A_k >= 512, or none.  ids_out = id_top, 0 when there is none; label = 1.f iff
+ *        id_top == target_id; counts[s][k] = the number of pixels of sample s whose top is k: an integer sum (one wave
+ *        reduction per layer, one integer atomic per wave and non-zero layer) on a record the call zeroes itself on the stream.
+ *  L6. one layer is eosvos_lucid_compose: L = 1, id_0 = 1 and ids = (mask != 0) give its images, labels and count bit for bit
+ *        (the two kernels share the coordinate, coverage and bicubic code).
+ * The draws, the depth order, acceptance on the target's visible count and which objects take part (rules L7-L10) are the
+ * caller's: lucid_layers.py.
+ * eosvos_lucid_compose_layers: ONE launch for all n_samples <= 8 samples (one thread per output pixel, the sample in the grid's
+ * third dimension).  flips [n] int32, n_layers [n] int32, layer_ids [n][8] uint8 and matrices [n][9][6] doubles (Bi, then Oi_0 ..
+ * Oi_7; of both only the first n_layers[s] layer entries of a sample are read) are HOST arrays copied into the launch's
+ * arguments (8 samples are 3.5 KB of HIP's 4 KB): a queued launch owns everything it reads.  images [n][C][H][W], labels
+ * [n][H][W] (0.f / 1.f) and ids_out [n][H][W] (may be null) on the device, not overlapping the inputs.  counts_host non-null: the
+ * counts [n][8] (0 for layers a sample does not have) are copied there and the call waits for the stream; null: nothing waits.
+ * The result does not depend on what the outputs or the engine's scratch held.
+ * Rejected without a launch, the outputs untouched: a null pointer (ids_out and counts_host excepted); channels outside [1, 64];
+ * height or width < 1 or > 4096; n_samples outside [1, 8]; a layer count outside [1, 8]; a layer id of 0 or one repeated within
+ * a sample; target_id outside [1, 255]; a non-finite entry of a matrix that is read. */
+int eosvos_lucid_compose_layers(eosvos_engine* e, const float* frame, const uint8_t* ids, const float* plate, int channels,
+                                int height, int width, int n_samples, const int32_t* flips, const int32_t* n_layers,
+                                const uint8_t* layer_ids, const double* matrices, int target_id, float* images, float* labels,
+                                uint8_t* ids_out, int32_t* counts_host);
+
 /* ---- online adaptation: distance-gated negatives from a capped distance transform --------------------------------------- */
 /* The pseudo-labels of the adaptation rounds (evaluate.py:231-240) come from the frame's own probabilities; nothing looks at
  * where the object was, so a confident blob on a look-alike becomes a positive target of every later round.  OnAVOS
