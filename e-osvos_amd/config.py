@@ -15,6 +15,8 @@ import copy
 
 import yaml
 
+from . import eval_options
+
 BASE = {
     'seed': 1,
     'meta_batch_size': 4,
@@ -96,111 +98,20 @@ NAMED = {
 }
 
 
-# Options beyond the reference's cfgs/meta.yaml.  They are NOT part of BASE (the reference's key set): `parse_cli` adds a group
-# only when the command line sets one of its keys (`eval_tta.flip=True eval_tta.scales=[0.75,1.0,1.25]`), consumers read them
-# with `cfg.get(...)`.
-#   eval_tta   test-time augmentation of the evaluation's inference passes (`tta.py`): mirrored and rescaled views averaged in
-#              probability space with equal weights; the value below is the neutral one (one plain view = off)
-EXTENSIONS = {
-    'eval_tta': {'flip': False, 'scales': [1.0]},
-}
-
-
-# Post-processing of the evaluation's label maps, handled like EXTENSIONS (not part of BASE, added by `parse_cli` only when the
-# command line sets one of its keys: `eval_crf.iterations=5 eval_crf.w_appearance=10`, read with `cfg.get(...)`).
-#   eval_crf   local dense-CRF refinement of the final merge (`crf.py`); the value below is the neutral one (0 iterations = the plain
-#              merge), the other keys hold `crf.DEFAULTS` -- customary values, not tuned on data
-POSTPROCESS = {
-    'eval_crf': {'iterations': 0, 'radius': 5, 'dilation': 2, 'w_appearance': 10.0, 'w_smooth': 3.0,
-                 'theta_alpha': 8.0, 'theta_beta': 0.05, 'theta_gamma': 3.0},
-}
-
-
-# Region-level clean-up of the evaluation's label maps, handled like EXTENSIONS and POSTPROCESS (not part of BASE, added by
-# `parse_cli` only when the command line sets one of its keys: `eval_components.gate=24 eval_components.min_rel_area=0.05
-# eval_components.largest_only=True` -- example values, untuned; read with `cfg.get(...)`).
-#   eval_components   connected-component filter after the merge and the CRF (`components.py`); the value below is the neutral
-#                     one (`components.DEFAULTS`: nothing is filtered, nothing new is called)
-CLEANUP = {
-    'eval_components': {'connectivity': 8, 'min_area': 0, 'min_rel_area': 0.0, 'largest_only': False, 'gate': 0},
-}
-
-
-# Hole filling of the evaluation's label maps, handled like EXTENSIONS, POSTPROCESS and CLEANUP (not part of BASE, added by
-# `parse_cli` only when the command line sets one of its keys: `eval_holes.max_area=64 eval_holes.prev_overlap=0.5` -- example
-# values, untuned; read with `cfg.get(...)`).
-#   eval_holes        enclosed background islands are filled after the component filter (`holes.py`); the value below is the
-#                     neutral one (`holes.DEFAULTS`: max_area 0, nothing is filled, nothing new is called)
-FILL = {
-    'eval_holes': {'connectivity': 8, 'max_area': 0, 'max_rel_area': 1.0, 'prev_overlap': 0.0},
-}
-
-
-# Superpixel snapping of the evaluation's label maps, handled like EXTENSIONS, POSTPROCESS, CLEANUP and FILL (not part of BASE,
-# added by `parse_cli` only when the command line sets one of its keys: `eval_snap.step=16 eval_snap.min_share=0.6` -- example
-# values, untuned; read with `cfg.get(...)`).
-#   eval_snap         between the CRF and the component filter, every SLIC superpixel of the frame takes its majority label
-#                     (`snap.py`); the value below is the neutral one (`snap.DEFAULTS`: step 0, nothing new is called)
-SNAP = {
-    'eval_snap': {'step': 0, 'iterations': 5, 'compactness': 10, 'min_share': 0.5},
-}
-
-
-# Motion compensation of the clean-up's temporal rules, handled like the groups above (`eval_motion.block=8
-# eval_motion.radius=24` -- example values, untuned; read with `cfg.get(...)`).
-#   eval_motion       the gate of the component filter and `prev_overlap` of the hole filler see the previous frame's cleaned
-#                     map warped by block motion (`motion.py`); the value below is the neutral one (`motion.DEFAULTS`: block
-#                     0, nothing new is called).  Active, it needs `eval_components.gate` or `eval_holes.prev_overlap`.
-MOTION = {
-    'eval_motion': {'block': 0, 'radius': 16, 'bias': 2},
-}
-
-
-# Object-centred zoom pass of the evaluation's inference calls, handled like the groups above (not part of BASE, added by
-# `parse_cli` only when the command line sets one of its keys: `eval_zoom.max_zoom=3 eval_zoom.margin=0.5` -- example values,
-# untuned; read with `cfg.get(...)`).
-#   eval_zoom         every frame gets a second look at a crop around the object its first pass found, magnified to the frame's
-#                     own size on the live engine and blended in inside the crop (`zoom.py`); the value below is the neutral
-#                     one (`zoom.DEFAULTS`: max_zoom 0, nothing new is called)
-ZOOM = {
-    'eval_zoom': {'max_zoom': 0, 'min_zoom': 1.5, 'threshold': 0.5, 'min_pixels': 16, 'margin': 0.5, 'margin_px': 8, 'weight': 0.5,
-                  'feather': 8},
-}
-
-
-# Lucid first-frame synthesis for the evaluation's one-shot fine-tune, handled like the groups above (not part of BASE, added
-# by `parse_cli` only when the command line sets one of its keys: `eval_lucid.samples=2 eval_lucid.shift=0.1` -- example values,
-# untuned; read with `cfg.get(...)`).
-#   eval_lucid        some samples of every round-0 batch are composed from the annotated frame with the object and its
-#                     background moved independently (`lucid.py`); the value below is the neutral one (`lucid.DEFAULTS`:
-#                     samples 0, nothing new is called, nothing is drawn)
-LUCID = {
-    'eval_lucid': {'samples': 0, 'dilate': 4, 'rot': 15.0, 'scale': 0.15, 'shift': 0.1, 'bg_rot': 5.0, 'bg_scale': 0.05,
-                   'bg_shift': 0.05, 'min_keep': 0.5},
-}
-
-
-# Distance-gated negatives for online adaptation, handled like the groups above (not part of BASE, whose `eval_online_adapt`
-# keeps the reference's four keys; added by `parse_cli` only when the command line sets one of its keys: `eval_adapt.neg_dist=220
-# eval_adapt.erode=15` -- OnAVOS's published 480p values, an example, untuned; read with `cfg.get(...)`).
-#   eval_adapt        the propagated targets of the adaptation rounds are 0 wherever a pixel is farther than `neg_dist` from the
-#                     mask of the frame before it, eroded by `erode` (`adapt.py`); the value below is the neutral one
-#                     (`adapt.DEFAULTS`: neg_dist 0, nothing new is called).  Active, it needs `eval_online_adapt.step` > 0.
-ADAPT = {
-    'eval_adapt': {'neg_dist': 0, 'erode': 0},
-}
-
-
-# The sequence's other objects as moving layers of the lucid synthesis, handled like the groups above (not part of BASE, added by
-# `parse_cli` only when the command line sets one of its keys: `eval_lucid_layers.others=3` -- an example value, untuned; read
-# with `cfg.get(...)`).  `eval_lucid` keeps its own nine keys.
-#   eval_lucid_layers up to `others` of the other objects annotated on the target's train frame are cut out with it and moved on
-#                     their own over the filled plate, each in front of the target with probability `front`
-#                     (`lucid_layers.py`); the value below is the neutral one (`lucid_layers.DEFAULTS`: others 0, nothing new
-#                     is called, nothing is drawn).  Active, it needs `eval_lucid.samples` > 0.
-LAYERS = {
-    'eval_lucid_layers': {'others': 0, 'front': 0.5},
-}
+# Options beyond the reference's cfgs/meta.yaml: the evaluation's opt-in groups.  They are NOT part of BASE (the reference's key set):
+# `parse_cli` adds a group, with its neutral values, only when the command line sets one of its keys, and consumers read them with
+# `eval_options.from_cfg`.  What each group does, its example values and its neutral values stand in its row of `eval_options.TABLE`;
+# the names below are views of that table, one per group.
+EXTENSIONS = {'eval_tta': eval_options.DEFAULTS['eval_tta']}
+POSTPROCESS = {'eval_crf': eval_options.DEFAULTS['eval_crf']}
+CLEANUP = {'eval_components': eval_options.DEFAULTS['eval_components']}
+FILL = {'eval_holes': eval_options.DEFAULTS['eval_holes']}
+SNAP = {'eval_snap': eval_options.DEFAULTS['eval_snap']}
+MOTION = {'eval_motion': eval_options.DEFAULTS['eval_motion']}
+ZOOM = {'eval_zoom': eval_options.DEFAULTS['eval_zoom']}
+LUCID = {'eval_lucid': eval_options.DEFAULTS['eval_lucid']}
+ADAPT = {'eval_adapt': eval_options.DEFAULTS['eval_adapt']}
+LAYERS = {'eval_lucid_layers': eval_options.DEFAULTS['eval_lucid_layers']}
 
 
 def _merge(dst, src):
@@ -249,51 +160,10 @@ def parse_cli(argv):
             raise KeyError(f'unknown named config: {a}')
     for k, v in updates:
         group = k.split('.')[0]
-        for groups in (EXTENSIONS, POSTPROCESS, CLEANUP, FILL, SNAP, MOTION, ZOOM, LUCID, ADAPT, LAYERS):
-            if group in groups and group not in cfg:
-                cfg[group] = copy.deepcopy(groups[group])
+        if group in eval_options.DEFAULTS and group not in cfg:
+            cfg[group] = copy.deepcopy(eval_options.DEFAULTS[group])
         _set_dotted(cfg, k, v)
-    if 'eval_tta' in cfg:
-        from .tta import check
-        check(cfg['eval_tta'])                              # ValueError: empty list, scale <= 0, ...
-    if 'eval_crf' in cfg:
-        from .crf import check as check_crf
-        check_crf(cfg['eval_crf'])                          # ValueError: radius 0, a negative weight, ...
-    if 'eval_components' in cfg:
-        from .components import check as check_components
-        check_components(cfg['eval_components'])            # ValueError: gate 64, connectivity 6, ...
-    if 'eval_holes' in cfg:
-        from .holes import check as check_holes
-        check_holes(cfg['eval_holes'])                      # ValueError: max_area -1, prev_overlap 1.5, ...
-    if 'eval_snap' in cfg:
-        from .snap import check as check_snap
-        check_snap(cfg['eval_snap'])                        # ValueError: step 3, compactness 65, ...
-    if 'eval_motion' in cfg:
-        from . import motion
-        if motion.active(cfg['eval_motion']):               # ValueError: block 12, radius 33, bias 256, ...
-            from .components import check as check_gate
-            from .holes import active as fills, check as check_overlap, overlap_q16
-            fill = cfg.get('eval_holes', {})
-            if not check_gate(cfg.get('eval_components', {}))['gate'] and \
-                    not (fills(fill) and overlap_q16(check_overlap(fill)['prev_overlap'])):
-                raise ValueError('eval_motion has no consumer: set eval_components.gate or eval_holes.prev_overlap')
-        else:
-            motion.check(cfg['eval_motion'])
-    if 'eval_zoom' in cfg:
-        from .zoom import check as check_zoom
-        check_zoom(cfg['eval_zoom'])                        # ValueError: max_zoom 5, min_zoom above max_zoom, weight 0, ...
-    if 'eval_lucid' in cfg:
-        from .lucid import check as check_lucid
-        check_lucid(cfg['eval_lucid'])                      # ValueError: samples -1, dilate 17, min_keep 0, ...
-    if 'eval_adapt' in cfg:
-        from .adapt import active as adapts
-        if adapts(cfg['eval_adapt']) and not cfg['eval_online_adapt']['step']:      # ValueError: neg_dist 4096, erode -1, a float, ...
-            raise ValueError('eval_adapt has no consumer: set eval_online_adapt.step')
-    if 'eval_lucid_layers' in cfg:
-        from .lucid import active as lucid_on
-        from .lucid_layers import active as layered
-        if layered(cfg['eval_lucid_layers']) and not lucid_on(cfg.get('eval_lucid')):   # ValueError: others 8, front 1.5, a float, ...
-            raise ValueError('eval_lucid_layers has no consumer: set eval_lucid.samples')
+    eval_options.check_cfg(cfg)                             # ValueError: a bad value, an active group without its consumer
     unsupported(cfg)
     return cfg
 

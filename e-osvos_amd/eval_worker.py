@@ -21,6 +21,8 @@ import time
 
 import torch
 
+from . import eval_options
+
 
 def _datasets(cfg, data_root, height, width, num_frames):
     """{key: reader} for every dataset with `eval: True` whose root exists; else one synthetic set."""
@@ -72,16 +74,7 @@ def run(cfg, run_dir, device, data_root='data', height=480, width=854, num_frame
                 res = evaluate_dataset(model, meta_optim, sd, ds, cfg, key, save_dir=run_dir, meta_iter=info['meta_iter'],
                                        meta_epoch=info['meta_epoch'], best_mean_J=best[key], device=device,
                                        vis_win_names=info.get('vis_win_names'),
-                                       **({'tta': cfg['eval_tta']} if cfg.get('eval_tta') is not None else {}),
-                                       **({'crf': cfg['eval_crf']} if cfg.get('eval_crf') is not None else {}),
-                                       **({'components': cfg['eval_components']} if cfg.get('eval_components') is not None else {}),
-                                       **({'holes': cfg['eval_holes']} if cfg.get('eval_holes') is not None else {}),
-                                       **({'snap': cfg['eval_snap']} if cfg.get('eval_snap') is not None else {}),
-                                       **({'motion': cfg['eval_motion']} if cfg.get('eval_motion') is not None else {}),
-                                       **({'zoom': cfg['eval_zoom']} if cfg.get('eval_zoom') is not None else {}),
-                                       **({'lucid': cfg['eval_lucid']} if cfg.get('eval_lucid') is not None else {}),
-                                       **({'adapt': cfg['eval_adapt']} if cfg.get('eval_adapt') is not None else {}),
-                                       **({'layers': cfg['eval_lucid_layers']} if cfg.get('eval_lucid_layers') is not None else {}))
+                                       **eval_options.from_cfg(cfg))
                 best[key] = res['best_mean_J']
                 line = {'dataset': key, 'meta_iter': info['meta_iter'], 'mean_J': res['mean_J'], 'best_mean_J': best[key],
                         'J_seq': res['J_seq'], 'time_per_frame': res['time_per_frame'], 'mean_F': res['mean_F'],

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import components as component_filter
+from . import eval_options
 from . import crf as crf_refine
 from . import adapt as adapt_gate
 from . import holes as hole_filler
@@ -90,44 +91,15 @@ def min_prop_band(min_prop):
     return float(min_prop[0]), float(min_prop[1])
 
 
-def finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None,
-                    zoom=None, lucid=None, adapt=None, layers=None, lucid_others=None):
+def finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, lucid_others=None,
+                    **groups):
     """One (sequence, object) work item of `evaluate.py:132-317`: fine-tune on the train frame, predict the following
     frames, with online adaptation re-fine-tune every `step` frames.  Returns (probs (N,H,W) with the train frame seeded
-    as 2*GT (`:167-168`), train-loss history per round).  `tta`: test-time augmentation of every inference call (`tta.py`).
-    `zoom`: the object-centred second look after every inference call (`zoom.py`).  `lucid`: some samples of every round-0
-    batch are composed with the object and its background moved independently (`lucid.py`).  `adapt`: the propagated targets of
-    the adaptation rounds are 0 wherever a pixel is far from the previous frame's mask (`adapt.py`).  `layers` with
-    `lucid_others` (M, 1, H, W), the other objects' masks at this object's train frame: the lucid samples move those objects
-    too, each on its own, behind or in front of this one (`lucid_layers.py`)."""
+    as 2*GT (`:167-168`), train-loss history per round).  `groups`: the object-stage option groups of `eval_options.TABLE`, by
+    keyword; `lucid_others` (M, 1, H, W), the other objects' masks at this object's train frame, goes with `layers`."""
+    share, _ = eval_options.split('finetune_object', groups, merge=False)
     return _drain(finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id,
-                                        **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid), **_adapt_kw(adapt),
-                                        **_layers_kw(layers, lucid_others)))
-
-
-def _tta_kw(tta):
-    """`tta` travels as a keyword, and only when it is set: without it every call below is the one made before it existed."""
-    return {} if tta is None else {'tta': tta}
-
-
-def _zoom_kw(zoom):
-    """As `_tta_kw`: `zoom` travels as a keyword, and only when it is set."""
-    return {} if zoom is None else {'zoom': zoom}
-
-
-def _lucid_kw(lucid):
-    """As `_tta_kw`: `lucid` travels as a keyword, and only when it is set."""
-    return {} if lucid is None else {'lucid': lucid}
-
-
-def _adapt_kw(adapt):
-    """As `_tta_kw`: `adapt` travels as a keyword, and only when it is set."""
-    return {} if adapt is None else {'adapt': adapt}
-
-
-def _layers_kw(layers, lucid_others=None):
-    """As `_tta_kw`: `layers` travels as a keyword, with the other objects' masks, and only when it is set."""
-    return {} if layers is None else {'layers': layers, 'lucid_others': lucid_others}
+                                        **eval_options.travelling(share, lucid_others=lucid_others)))
 
 
 def others_at_train_frame(gts, train_frame_ids, o):
@@ -139,6 +111,11 @@ def others_at_train_frame(gts, train_frame_ids, o):
 def _others_for(layers, gts, train_frame_ids, o):
     """`others_at_train_frame` when `layers` is active, else None: an inactive `layers` computes nothing."""
     return others_at_train_frame(gts, train_frame_ids, o) if layer_pass.active(layers) else None
+
+
+def _object_share(share, gts, train_frame_ids, o):
+    """The object-stage share as it travels to object o's fine-tune: `layers` with the masks of the objects on o's train frame."""
+    return eval_options.travelling(share, lucid_others=_others_for(share.get('layers'), gts, train_frame_ids, o))
 
 
 def lucid_batches(model, augment, frame, gt, batch, lucid, layers=None, lucid_others=None):
@@ -183,13 +160,20 @@ def _drain(gen):
         return stop.value
 
 
-def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0, tta=None,
-                          zoom=None, lucid=None, adapt=None, layers=None, lucid_others=None):
+def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment=None, train_frame_id=0,
+                          lucid_others=None, **groups):
     """`finetune_object` as a generator: it yields each time a fine-tune iteration (or a few inference frames) has been
     ENQUEUED on the model's engine and before the host waits for its loss, so that a caller holding several objects
     (one model / engine / stream each, `run_objects_in_flight`) can queue the others' work in between.  Everything
     random (`set_random_seeds` + the augmentation draws of an iteration) happens inside one resume, so the draws of an
-    object do not depend on what runs beside it.  The generator's return value is `finetune_object`'s."""
+    object do not depend on what runs beside it.  The generator's return value is `finetune_object`'s.
+    The consumer of the object-stage groups of `eval_options.TABLE`; a name that is none of them raises here, at the call."""
+    share, _ = eval_options.split('finetune_object_steps', groups, merge=False)
+    return _object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id, lucid_others, **share)
+
+
+def _object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id, lucid_others, tta=None,
+                  zoom=None, lucid=None, adapt=None, layers=None):
     if augment is None and cfg['data_cfg'].get('random_train_transform'):
         augment = device_augment(model)
     augment = augment or _repeat_batch
@@ -217,8 +201,8 @@ def finetune_object_steps(model, meta_optim, meta_optim_state_dict, frames, gt, 
     # object, at the first batch); off = nothing new is called, nothing is drawn
     if layers is not None:
         layer_pass.check(layers)
-    lucid_batch = lucid_batches(model, augment, frames[train_frame_id:train_frame_id + 1], gt, bsz, lucid,
-                                **_layers_kw(layers, lucid_others)) if lucid_pass.active(lucid) else None
+    lucid_batch = lucid_batches(model, augment, frames[train_frame_id:train_frame_id + 1], gt, bsz, lucid, layers, lucid_others) \
+        if lucid_pass.active(lucid) else None
     hist = []
     for r, rd in enumerate(online_adapt_schedule(n, train_frame_id, step, bsz)):
         if r == 0 or ona['reset_model_mode'] == 'FULL':
@@ -346,13 +330,15 @@ def object_workers(model, meta_optim, meta_optim_cfg, n, wg_budget=256):
     return ws
 
 
-def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augment=None, train_frame_id=0, tta=None, zoom=None,
-                          lucid=None, adapt=None, layers=None, lucid_others=None):
+def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augment=None, train_frame_id=0, lucid_others=None,
+                          **groups):
     """[(probs, hist)] for the objects `gts` of one sequence, up to len(workers) of them in flight together; results are
     those of `finetune_object` one after the other (same engine arithmetic at the same workgroup budget).
     `train_frame_id`: one frame for all objects, or one per object (YouTube-VOS objects that appear later).
-    `layers` (`lucid_layers.py`): every object's lucid samples move the objects of `gts` that share its train frame too;
-    `lucid_others`, one entry per object, replaces them (a caller that holds only some of the sequence's objects)."""
+    `groups`: the object-stage option groups of `eval_options.TABLE`, by keyword.  With `layers`, every object's lucid samples move
+    the objects of `gts` that share its train frame too; `lucid_others`, one entry per object, replaces them (a caller that holds
+    only some of the sequence's objects)."""
+    share, _ = eval_options.split('run_objects_in_flight', groups, merge=False)
     out = [None] * len(gts)
     tfid = list(train_frame_id) if isinstance(train_frame_id, (list, tuple)) else [train_frame_id] * len(gts)
     if frames.is_cuda:
@@ -368,11 +354,9 @@ def run_objects_in_flight(workers, meta_optim_state_dict, frames, gts, cfg, augm
         for wi, w in enumerate(workers):
             if wi not in active and pending:
                 oi = pending.pop(0)
+                others = lucid_others[oi] if lucid_others is not None else _others_for(share.get('layers'), gts, tfid, oi)
                 active[wi] = (oi, finetune_object_steps(w.model, w.meta_optim, meta_optim_state_dict, frames, gts[oi], cfg,
-                                                        augment, tfid[oi], **_tta_kw(tta), **_zoom_kw(zoom),
-                                                        **_lucid_kw(lucid), **_adapt_kw(adapt),
-                                                        **_layers_kw(layers, lucid_others[oi] if lucid_others is not None
-                                                                     else _others_for(layers, gts, tfid, oi))))
+                                                        augment, tfid[oi], **eval_options.travelling(share, lucid_others=others)))
         for wi in sorted(active):
             oi, gen = active[wi]
             w = workers[wi]
@@ -472,76 +456,26 @@ def _merge_refined(engine, stack, frames, crf, keep):
     return out
 
 
-def _crf_kw(crf):
-    """As `_tta_kw`: `crf` travels as a keyword, and only when it is set."""
-    return {} if crf is None else {'crf': crf}
-
-
-def _components_kw(components):
-    """As `_tta_kw`: `components` travels as a keyword, and only when it is set."""
-    return {} if components is None else {'components': components}
-
-
-def _holes_kw(holes):
-    """As `_tta_kw`: `holes` travels as a keyword, and only when it is set to something that fills (`holes.active`, which
-    also validates it)."""
-    return {'holes': holes} if hole_filler.active(holes) else {}
-
-
-def _snap_kw(snap, cfg, dataset=None):
-    """As `_holes_kw`: `snap` travels as a keyword, and only when it is set to something that snaps (`snap.active`, which also
-    validates it) -- then with the offset `snap.quantise` needs: the data set's `mean_val` where `data_cfg.normalize` had it
-    subtracted from the frames."""
-    if not snapper.active(snap):
-        return {}
-    if not cfg.get('data_cfg', {}).get('normalize'):
-        return {'snap': snap}
-    from .data import DAVIS
-    return {'snap': snap, 'frame_offset': tuple(getattr(dataset, 'mean_val', DAVIS.mean_val))}
-
-
-def _motion_kw(motion, cfg, dataset=None):
-    """As `_snap_kw`: `motion` travels as a keyword, and only when it is set to something that estimates (`motion.active`,
-    which also validates it) -- then with the offset `snap.quantise` needs."""
-    if not mover.active(motion):
-        return {}
-    if not cfg.get('data_cfg', {}).get('normalize'):
-        return {'motion': motion}
-    from .data import DAVIS
-    return {'motion': motion, 'frame_offset': tuple(getattr(dataset, 'mean_val', DAVIS.mean_val))}
-
-
-def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_gts, cfg, augment=None,
-                      train_frame_id=0, tta=None, crf=None, components=None, holes=None, snap=None, motion=None, zoom=None,
-                      lucid=None, adapt=None, layers=None):
+def evaluate_sequence(model, meta_optim, meta_optim_state_dict, frames, object_gts, cfg, augment=None, train_frame_id=0, **groups):
     """frames (N,3,H,W) on the GPU, object_gts: list of (1,H,W) binary masks of the train frame.
     cfg keys (names of cfgs/meta.yaml): num_epochs.eval, eval_online_adapt.{step,reset_model_mode,
     num_epochs,min_prop (a threshold, or [lo, hi]: `min_prop_band`)}, data_cfg.batch_sizes.train, seed, loss_func, train_early_stopping_cfg.
-    `tta` ({'flip': bool, 'scales': [floats]}, `tta.py`): every inference call averages the mirrored / rescaled views.
-    `crf` (`crf.py`): the final merge is refined by the local dense CRF; the train frame keeps the plain merge.
-    `components` (`components.py`): the connected-component filter cleans the merged (and refined) maps; the train frame passes
-    unchanged and anchors the gate.
-    `holes` (`holes.py`): the hole filler runs after the component filter, with the same train frame kept.
-    `snap` (`snap.py`): the superpixel snapping runs between the CRF and the component filter, with the same train frame kept.
-    `motion` (`motion.py`): the temporal rules of the filter and the hole filler see the previous map warped by block motion.
-    `zoom` (`zoom.py`): every inference call is followed by the object-centred second look at a crop around the object.
-    `lucid` (`lucid.py`): the last `samples` samples of every round-0 batch are composed from the train frame with the object
-    and its background moved independently.
-    `adapt` (`adapt.py`): the propagated targets of the adaptation rounds are gated by the distance to the previous frame's mask.
-    `layers` (`lucid_layers.py`): the lucid samples of every object move the sequence's other objects too, as layers of their own.
+    `groups`: the option groups of `eval_options.TABLE`, by keyword; the object-stage ones go to every `finetune_object`, the
+    merge-stage ones to `merge_objects`, where the train frame is the `keep` frame.
     Returns (labels (N,H,W) uint8, per-object probs list, train loss history per object)."""
+    share, merge_share = eval_options.split('evaluate_sequence', groups)
     probs_all, hist_all = [], []
     for o, gt in enumerate(object_gts):
-        others = _others_for(layers, object_gts, [train_frame_id] * len(object_gts), o)
         probs, hist = finetune_object(model, meta_optim, meta_optim_state_dict, frames, gt, cfg, augment, train_frame_id,
-                                      **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid), **_adapt_kw(adapt),
-                                      **_layers_kw(layers, others))
+                                      **_object_share(share, object_gts, [train_frame_id] * len(object_gts), o))
         probs_all.append(probs)
         hist_all.append(hist)
-    if crf is None and components is None and not _holes_kw(holes) and not _snap_kw(snap, cfg) and not _motion_kw(motion, cfg):
+    merge_kw = eval_options.travelling(merge_share, cfg)
+    if not merge_kw:
         return merge_objects(model.engine, probs_all), probs_all, hist_all
-    return merge_objects(model.engine, probs_all, frames, crf, keep=(train_frame_id,), **_components_kw(components),
-                         **_holes_kw(holes), **{**_snap_kw(snap, cfg), **_motion_kw(motion, cfg)}), probs_all, hist_all
+    # this call site hands `frames` and `crf` over by position, the CRF set or not
+    return merge_objects(model.engine, probs_all, frames, merge_kw.pop('crf', None), keep=(train_frame_id,), **merge_kw), \
+        probs_all, hist_all
 
 
 def prediction_paths(save_dir, dataset_name, split):
@@ -558,8 +492,7 @@ def save_label_png(path, labels_hw):
 
 def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dataset_key, save_dir=None,
                      meta_iter=None, meta_epoch=None, best_mean_J=0.0, dist=None, device=None, vis_win_names=None,
-                     log=None, objects_in_flight=None, tta=None, crf=None, components=None, holes=None, snap=None, motion=None,
-                     zoom=None, lucid=None, adapt=None, layers=None):
+                     log=None, objects_in_flight=None, **groups):
     """The evaluation worker of `src/util/evaluate.py:111-382` for the DeepLab path: every sequence of `dataset`
     (an `eosvos_amd.data` reader), every object, fine-tune / online adaptation / inference / merge; prediction PNGs
     under `{save_dir}/best_eval_preds/{name}/{split}/{seq}/{frame}.png`, J per sequence, and the
@@ -576,25 +509,10 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
     grouped): budget and grouping change the split-K partition, i.e. the order of fp32 partial sums, so the last
     bits of a result (not its parity margins, `profiles/*parity_margins*`) depend on how many objects of the sequence
     landed on this rank.  EOSVOS_OBJECTS_IN_FLIGHT=1 gives one schedule-independent order.
-    `tta` ({'flip': bool, 'scales': [floats]}, `tta.py`): test-time augmentation of every inference call; the view engines
-    it builds are released with the parked ones at the end.
-    `crf` (`crf.py`): the merged label maps -- and with them the PNGs, J_seq and the J / F counts -- are refined by the local dense
-    CRF; a frame that is the train frame of every object of its sequence keeps the plain merge (its seeded ground truth).
-    `components` (`components.py`): the connected-component filter cleans the merged (and refined) label maps before the PNGs,
-    J_seq and the J / F counts see them; the same train frame passes unchanged.
-    `holes` (`holes.py`): the hole filler runs after the component filter; the PNGs, J_seq and the J / F counts see the filled maps.
-    `snap` (`snap.py`): the superpixel snapping runs between the CRF and the component filter, on the frames quantised back to
-    uint8 RGB; the PNGs, J_seq and the J / F counts see the final maps.
-    `motion` (`motion.py`): the gate of the component filter and `prev_overlap` of the hole filler see the previous frame's
-    cleaned map warped by block motion of the same quantised frames.
-    `zoom` (`zoom.py`): every inference call is followed by the object-centred second look: the frame cut to a box around the
-    first pass's foreground, scored again on the live engine at the frame's size and blended in inside the box.
-    `lucid` (`lucid.py`): the one-shot fine-tune of every object sees `samples` synthesised samples per round-0 batch: the
-    object cut out of the train frame, the hole filled, object and background moved independently and composed again.
-    `adapt` (`adapt.py`): with online adaptation, the propagated targets of every adaptation round are 0 wherever a pixel is
-    farther than `neg_dist` from the (eroded) mask of the frame before it, whatever the network says there.
-    `layers` (`lucid_layers.py`): the lucid samples move up to `others` of the other objects annotated on the object's train
-    frame as layers of their own, behind or in front of it.
+    `groups`: the option groups of `eval_options.TABLE`, by keyword (`eval_options.from_cfg(cfg)` for a parsed config).  The
+    object-stage ones go to every object's fine-tune (the view engines `tta` builds are released with the parked ones at the
+    end); the merge-stage ones to `merge_objects`, so that the PNGs, J_seq and the J / F counts see the final label maps.  A frame
+    that is the train frame of every object of its sequence is the `keep` frame of the merge.
     Returns dict(J_seq, mean_J, best_mean_J, time_per_frame, labels={seq: (N,H,W) uint8}) and the DAVIS J / F statistics
     of `eval_davis_seq` (`evaluate.py:345-359`), one entry per object in sequence order: J_obj (the per-object J means the
     reference calls J_seq), J_recall_seq, J_decay_seq, F_seq, F_recall_seq, F_decay_seq, with mean_F and
@@ -602,6 +520,7 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
     (`data.davis_counts`); J_seq, mean_J and the best-checkpoint choice stay per sequence, from `sequence_J`."""
     from .checkpoint import save_meta_checkpoint
     from .data import davis_counts, measures_from_counts, sequence_J
+    share, merge_share = eval_options.split('evaluate_dataset', groups)
     rank = dist.get_rank() if dist is not None else 0
     world = dist.get_world_size() if dist is not None else 1
     ds_cfg = cfg['datasets'][dataset_key]
@@ -706,9 +625,8 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
             item += 1
         if workers is not None and len(mine) > 1:
             res = run_objects_in_flight(workers, meta_optim_state_dict, frames, [gts[o] for o in mine], cfg,
-                                        train_frame_id=[fids[o] for o in mine], **_tta_kw(tta), **_zoom_kw(zoom),
-                                        **_lucid_kw(lucid), **_adapt_kw(adapt),
-                                        **_layers_kw(layers, [_others_for(layers, gts, fids, o) for o in mine]))
+                                        train_frame_id=[fids[o] for o in mine],
+                                        lucid_others=[_others_for(share.get('layers'), gts, fids, o) for o in mine], **share)
             for o, (p, _) in zip(mine, res):
                 probs[o] = p
         else:
@@ -716,9 +634,7 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
                 model.set_wg_budget(0)                                          # alone on the GPU
             for o in mine:
                 probs[o], _ = finetune_object(model, meta_optim, meta_optim_state_dict, frames, gts[o], cfg,
-                                              train_frame_id=fids[o], **_tta_kw(tta), **_zoom_kw(zoom), **_lucid_kw(lucid),
-                                              **_adapt_kw(adapt),
-                                              **_layers_kw(layers, _others_for(layers, gts, fids, o)))
+                                              train_frame_id=fids[o], **_object_share(share, gts, fids, o))
         if world > 1:
             dist.all_reduce(probs)
         eval_time += time.perf_counter() - t0
@@ -726,13 +642,14 @@ def evaluate_dataset(model, meta_optim, meta_optim_state_dict, dataset, cfg, dat
         num_frames += n * len(gts)                                              # per (object, frame), evaluate.py:320
         if model.engine is None:                                                # this rank had no item yet
             model._ensure_engine(frames.shape[2], frames.shape[3], 1)
-        keep = {'keep': tuple(set(fids)) if len(set(fids)) == 1 else ()} \
-            if crf is not None or components is not None or holes is not None or _snap_kw(snap, cfg) or _motion_kw(motion, cfg) else {}
-        if crf is not None or _snap_kw(snap, cfg) or _motion_kw(motion, cfg):
-            keep = dict(frames=frames, **keep)
-        labels = merge_objects(model.engine, [probs[o] for o in range(len(gts))], **keep, **_crf_kw(crf),
-                               **_components_kw(components), **_holes_kw(holes),
-                               **{**_snap_kw(snap, cfg, dataset), **_motion_kw(motion, cfg, dataset)})
+        merge_kw = eval_options.travelling(merge_share, cfg, dataset)
+        # this call site hands everything over by keyword: `keep` also beside a `holes` that is set and fills nothing, `frames`
+        # only to the stages that read them
+        if merge_kw or 'holes' in merge_share:
+            merge_kw['keep'] = tuple(set(fids)) if len(set(fids)) == 1 else ()
+        if any(k in merge_kw for k in ('crf', 'snap', 'motion')):
+            merge_kw['frames'] = frames
+        labels = merge_objects(model.engine, [probs[o] for o in range(len(gts))], **merge_kw)
         counts = None
         if not dataset.test_mode:                                               # J / F counts where the labels are
             gt_dev = torch.from_numpy(np.ascontiguousarray(gt_maps, dtype=np.uint8)).to(labels.device)

@@ -30,6 +30,7 @@ import torch
 
 from . import config as config_mod
 from . import data as data_mod
+from . import eval_options
 from . import synthetic
 from .checkpoint import checkpoint_names, load_meta_checkpoint, save_meta_checkpoint
 from .evaluate import evaluate_dataset
@@ -203,16 +204,7 @@ def _run(cfg, run, run_dir, meta_mode, eval_proc, height, width, num_frames, num
             load_parent_state(model, parent_states, key, pm['encoder'], log)   # evaluate.py:46-50
             results[key] = evaluate_dataset(model, meta_optim, meta_optim.state_dict(), reader, cfg, key, save_dir=run_dir,
                                             meta_iter=meta_iter, meta_epoch=0, dist=dist if world > 1 else None, device=dev,
-                                            **({'tta': cfg['eval_tta']} if cfg.get('eval_tta') is not None else {}),
-                                            **({'crf': cfg['eval_crf']} if cfg.get('eval_crf') is not None else {}),
-                                            **({'components': cfg['eval_components']} if cfg.get('eval_components') is not None else {}),
-                                            **({'holes': cfg['eval_holes']} if cfg.get('eval_holes') is not None else {}),
-                                            **({'snap': cfg['eval_snap']} if cfg.get('eval_snap') is not None else {}),
-                                            **({'motion': cfg['eval_motion']} if cfg.get('eval_motion') is not None else {}),
-                                            **({'zoom': cfg['eval_zoom']} if cfg.get('eval_zoom') is not None else {}),
-                                            **({'lucid': cfg['eval_lucid']} if cfg.get('eval_lucid') is not None else {}),
-                                            **({'adapt': cfg['eval_adapt']} if cfg.get('eval_adapt') is not None else {}),
-                                            **({'layers': cfg['eval_lucid_layers']} if cfg.get('eval_lucid_layers') is not None else {}))
+                                            **eval_options.from_cfg(cfg))
         if dev.startswith('cuda'):
             torch.cuda.synchronize()
         if rank == 0:

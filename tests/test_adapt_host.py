@@ -307,13 +307,18 @@ def test_a_scalar_the_gate_cannot_use_raises_before_any_engine_work(bad):
 
 
 def test_the_keyword_travels_only_when_set():
-    assert evaluate._adapt_kw(None) == {} and evaluate._adapt_kw({'neg_dist': 3}) == {'adapt': {'neg_dist': 3}}
+    from eosvos_amd import eval_options
+    assert eval_options.travelling({'adapt': None}) == {} and eval_options.travelling({'adapt': {'neg_dist': 3}}) == {'adapt': {'neg_dist': 3}}
     import inspect
     for fn in (evaluate.finetune_object, evaluate.finetune_object_steps, evaluate.run_objects_in_flight, evaluate.evaluate_sequence,
                evaluate.evaluate_dataset):
-        assert inspect.signature(fn).parameters['adapt'].default is None, fn.__name__
+        # the functions take the groups through one `**groups` checked against the table: `adapt` is accepted, and optional
+        assert inspect.signature(fn).parameters['groups'].kind is inspect.Parameter.VAR_KEYWORD, fn.__name__
+        assert eval_options.split(fn.__name__, {}) == ({}, {}) and eval_options.split(fn.__name__, {'adapt': None}, merge=False) == ({}, {})
+        assert eval_options.split(fn.__name__, {'adapt': {'neg_dist': 3}}, merge=False) == ({'adapt': {'neg_dist': 3}}, {})
+    assert eval_options.from_cfg({'eval_adapt': None}) == {} and eval_options.from_cfg({'eval_adapt': {'neg_dist': 3}}) == {'adapt': {'neg_dist': 3}}
     for name in ('eval_worker.py', 'train_meta.py'):
-        assert "cfg.get('eval_adapt')" in open(os.path.join(ROOT, 'e-osvos_amd', name)).read(), name
+        assert '**eval_options.from_cfg(cfg)' in open(os.path.join(ROOT, 'e-osvos_amd', name)).read(), name
 
 
 def test_entries_are_declared_at_every_layer():
