@@ -2373,6 +2373,25 @@ int conv_prof_read(int max, const char** names, long* counts, double* ms, double
     if (c[k]) { names[n] = kProfNames[k]; counts[n] = c[k]; ms[n] = t[k]; flops[n] = f[k]; ++n; }
   return n;
 }
+// plan log (kernels.h ConvPlanRec): what launch_conv decided, for the tests to assert the plan they claim to cover
+static bool g_plan_log_on = false;
+static int g_plan_log_n = 0;
+static ConvPlanRec g_plan_log[kConvPlanLogCap];
+void conv_plan_log_enable(int on) {
+  g_plan_log_on = on != 0;
+  if (g_plan_log_on) g_plan_log_n = 0;
+}
+int conv_plan_log_read(ConvPlanRec* out, const char** names, int max) {
+  for (int i = 0; i < g_plan_log_n && i < max && i < kConvPlanLogCap; ++i) {
+    out[i] = g_plan_log[i];
+    names[i] = kProfNames[g_plan_log[i].kernel];
+  }
+  return g_plan_log_n;
+}
+static void plan_log_add(const ConvPlanRec& r) {
+  if (g_plan_log_n < kConvPlanLogCap) g_plan_log[g_plan_log_n] = r;
+  ++g_plan_log_n;
+}
 // share of the nominal multiply-accumulates a launch executes (taps skipped by tap tables / pixel rectangles)
 double conv_exec_frac(const ConvArgs& a) {
   if (!a.tprefix || a.total_units <= 0) return 1.0;
@@ -2417,10 +2436,19 @@ int conv_wg_budget_of(int requested) { return conv_wg_budget(requested); }
 static_assert(CONV_MAX_WG <= CONV_MAX_WG_DEEP, "conv_ws_floats");
 int64_t conv_ws_floats() { return (int64_t)CONV_MAX_WG_DEEP * 2 * 128 * 128; }
 
-// returns the number of workgroups; fills a.dp_q / a.per / a.nwg.
-//   tiles >= 512: each workgroup takes dp_q = tiles/512 whole tiles (no workspace traffic) and
-//                 the tiles%512 leftover tiles are streamed over all workgroups in equal K runs;
-//   tiles <  512: everything is streamed (K split across workgroups).
+// returns the number of workgroups; fills a.deep / a.dp_q / a.per / a.nwg / a.splitk.  With nwg0 = the workgroup budget (768 for the
+// deep variants):
+//   tap table with its tile order, tiles >= nwg0, K <= 1536 (f16x3 / bf16x6 modes): whole tiles dealt out longest first,
+//                 dp_q = ceil(tiles / nwg0) per workgroup;
+//   tiles >= nwg0, no tap table: dp_q = tiles / nwg0 whole tiles per workgroup (no workspace traffic).  A leftover of at least
+//                 1 % of nwg0 tiles: one more whole tile each on fewer workgroups (the last may run past `tiles` and skips);
+//                 a smaller one is streamed over all workgroups in equal K runs of `per` steps (fix-up pass), or, when that
+//                 gives runs of less than 2 steps, taken as whole tiles too;
+//   otherwise:    short K, or many tiles with a short K: one whole tile per workgroup (per = ksteps, nwg = tiles); else
+//                 stream-K: the tiles' K steps (the tap table's compacted steps) in equal runs of `per` >= EOSVOS_MINK steps
+//                 (fix-up pass wherever a run ends inside a tile);
+//   f16x3 mode, few tiles with a long, even K: uniform split-K (splitk chunks per tile, nwg = tiles x splitk, fix-up pass)
+//                 instead of stream-K.
 int conv_plan(ConvArgs& a) {
   const int bn = conv_bn(a);
   const int T = a.KH * a.KW;
@@ -2500,12 +2528,14 @@ int conv_plan(ConvArgs& a) {
 void launch_conv(ConvArgs& a, hipStream_t s) {
   if (stream3x3_ok(a)) {                              // layer1's 64 -> 64 3x3 convs: all nine taps' weights resident in LDS
     a.dp_q = 0; a.per = 0; a.nwg = 0; a.splitk = 0;
+    if (g_plan_log_on) { ConvPlanRec r{}; r.kernel = kProfStream3x3; r.kmajor = a.kmajor; r.budget = conv_wg_budget(a.wg_budget); plan_log_add(r); }
     ProfScope ps(kProfStream3x3, 2.0 * a.M * a.N * a.Kc * 9, s);
     launch_stream3x3(a, s);
     return;
   }
   if (const int nc = stream1x1_nc(a)) {               // short-K 1x1 convs on the large maps: the streaming kernel
     a.dp_q = 0; a.per = 0; a.nwg = 0; a.splitk = 0;
+    if (g_plan_log_on) { ConvPlanRec r{}; r.kernel = nc >= 128 ? kProfStream1x1_128 : kProfStream1x1_64; r.kmajor = a.kmajor; r.budget = conv_wg_budget(a.wg_budget); plan_log_add(r); }
     ProfScope ps(nc >= 128 ? kProfStream1x1_128 : kProfStream1x1_64, 2.0 * a.M * a.N * a.Kc, s);      // (48 columns: filed under 64)
     if (nc == 128) {
       if (a.Kc == 64) launch_stream1x1<64, 128>(a, s);
@@ -2552,7 +2582,11 @@ void launch_conv(ConvArgs& a, hipStream_t s) {
   const int bk = a.deep == 2 ? EOSVOS_BK_DEEP : EOSVOS_BK;
   const long ksteps = (long)T * ((a.Kc + bk - 1) / bk);
   const long sk_tiles = tiles - (long)a.dp_q * nwg;
-  if (a.splitk > 1 || (a.per > 0 && sk_tiles > 0 && (a.per % ksteps != 0 || a.tprefix))) {   // some tile is shared between workgroups
+  const bool fixup = a.splitk > 1 || (a.per > 0 && sk_tiles > 0 && (a.per % ksteps != 0 || a.tprefix));   // some tile is shared between workgroups
+  if (g_plan_log_on)
+    plan_log_add(ConvPlanRec{pk, a.kmajor != 0, bn, (int)tiles, (int)ksteps, a.deep, a.dp_q, a.per, nwg, a.splitk, a.tprefix != nullptr,
+                             a.torder != nullptr, fixup, conv_wg_budget(a.wg_budget)});
+  if (fixup) {
     ProfScope ps(kProfFixup, 0.0, s);
     with_tile(bn, [&](auto BN) { hipLaunchKernelGGL((conv_fixup_kernel<BN()>), dim3((unsigned)sk_tiles, 8), block, 0, s, a); });
   }

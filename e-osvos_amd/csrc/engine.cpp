@@ -3402,6 +3402,27 @@ int eosvos_profile_read(eosvos_engine* e, int max_kernels, char* names, int64_t*
   return 0;
 }
 
+int eosvos_test_conv_plan_log(eosvos_engine* e, int on) {
+  if (!e) return fail("null engine");
+  conv_plan_log_enable(on);
+  return 0;
+}
+int eosvos_test_conv_plan_log_read(eosvos_engine* e, int max_records, char* names, int* fields, int* n_out) {
+  if (!e || !names || !fields || !n_out || max_records < 1) return fail("bad argument");
+  static_assert(kConvPlanLogFields == EOSVOS_PLAN_LOG_FIELDS, "include/eosvos.h lists the fields of ConvPlanRec");
+  std::vector<ConvPlanRec> recs(max_records);
+  std::vector<const char*> nm(max_records);
+  const int seen = conv_plan_log_read(recs.data(), nm.data(), max_records);
+  const int n = std::min(seen, std::min(max_records, kConvPlanLogCap));
+  for (int i = 0; i < n; ++i) {
+    strncpy(names + 64 * i, nm[i], 63);
+    names[64 * i + 63] = 0;
+    memcpy(fields + (size_t)i * kConvPlanLogFields, &recs[i], sizeof(ConvPlanRec));
+  }
+  *n_out = seen;
+  return 0;
+}
+
 int eosvos_time_hot_kernel(eosvos_engine* e, int batch, int reps, float* ms_host, double* flops_host) {
   ModeScope mode_scope(e);
   if (!e || !ms_host || !flops_host || batch < 1 || batch > e->maxB || reps < 1) return fail("bad argument");
@@ -3571,19 +3592,25 @@ struct ScratchEngine {
     t.arch = e->arch; t.H = H; t.W = W; t.maxB = B; t.dev = e->dev; t.s = e->s; t.s2 = nullptr;
     t.norm_mode = EOSVOS_NORM_BN_FROZEN;
     t.force_algo = algo;
+    t.wg_budget = e->wg_budget;          // the launches plan under the caller's eosvos_set_wg_budget
     t.zbuf.assign(1, nullptr); t.gn_stats.assign(1, nullptr);
     t.ws_off.assign(1, 0); t.upd_splits.assign(1, 1);
     t.wino.assign(1, eosvos_engine::WinoRec());
     const int Ho = conv_out(H, k, stride, dil, pad), Wo = conv_out(W, k, stride, dil, pad);
     t.Wp = t.falloc(c.wsize()); t.na = t.falloc(Cout); t.nb = t.falloc(Cout);
     t.ws_conv = t.falloc(conv_ws_floats());
+    // slabs for every budget eosvos_set_wg_budget accepts, as eosvos_create sizes them: the split count is not monotone in the
+    // budget (the Winograd-domain gradient plans for half of it, which rounds up to another accepted budget)
     int64_t slab = 0;
-    for (int b = 1; b <= B; ++b) slab = max64(slab, (int64_t)wgrad_max_splits(b * Ho * Wo, Cout, Cin, k * k, 0) * c.wsize());
+    for (int b = 1; b <= B; ++b)
+      for (int wb = 0; wb <= 512; wb += 64)
+        slab = max64(slab, (int64_t)wgrad_max_splits(b * Ho * Wo, Cout, Cin, k * k, wb) * c.wsize());
     const bool wino = algo == EOSVOS_ALGO_WINO_F2 || algo == EOSVOS_ALGO_WINO_F4;
     if (wino) {
       if (!wino_shape(c)) return;
       const WinoGeom g = wino_geom(&t, c, B, Ho, Wo);
-      slab = max64(slab, c.wsize() + (int64_t)wgrad_max_splits((int)g.ntile, Cout, Cin, g.np, 0) * Cout * g.np * Cin);
+      for (int wb = 0; wb <= 512; wb += 64)
+        slab = max64(slab, c.wsize() + (int64_t)wgrad_max_splits((int)g.ntile, Cout, Cin, g.np, wb) * Cout * g.np * Cin);
       auto& w = t.wino[0];
       w.V = t.falloc(g.np * g.prow * Cin);
       w.U = t.falloc((int64_t)g.np * Cout * Cin);

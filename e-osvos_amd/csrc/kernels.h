@@ -218,6 +218,22 @@ void conv_prof_enable(int on);
 int conv_prof_read(int max, const char** names, long* counts, double* ms, double* flops);
 void conv_prof_mark_begin(int kernel, double flops, hipStream_t s);   // launchers outside conv_kernels.hip; kernel = a ProfKernel id
 void conv_prof_mark_end(hipStream_t s);
+// Plan log for the tests (host bookkeeping only, off by default): one record per launch_conv call since conv_plan_log_enable(1),
+// the first kConvPlanLogCap of them.  A launch a streaming kernel took has its kernel id and zeros in the plan fields.
+struct ConvPlanRec {
+  int kernel;                       // ProfKernel id of the main kernel
+  int kmajor, bn;                   // gather side, column-tile width
+  int tiles, ksteps;                // output tiles, nominal K steps of one tile (of 16 channels for deep == 2)
+  int deep, dp_q, per, nwg, splitk; // what conv_plan set
+  int tprefix, torder;              // 1: the launch had a tap table / its longest-first tile order
+  int fixup;                        // 1: the fix-up pass was launched
+  int budget;                       // conv_wg_budget_of(a.wg_budget): the workgroups the launch planned for
+};
+constexpr int kConvPlanLogCap = 16;
+constexpr int kConvPlanLogFields = sizeof(ConvPlanRec) / sizeof(int);
+void conv_plan_log_enable(int on);  // 1: clear and record; 0: stop (the records stay readable)
+// copies min(launches, max, kConvPlanLogCap) records and their kernel names; returns the launches seen since the enable
+int conv_plan_log_read(ConvPlanRec* out, const char** names, int max);
 // The profiled kernels: id and reported name of every record, in the order conv_prof_read reports them.  Families of four
 // are <128, false>, <128, true>, <64, false>, <64, true> (convs: tile width, K-major) or <128, 128>, <128, 64>, <64, 128>,
 // <64, 64> (weight gradients); a launcher adds the member's offset to the family's first id.

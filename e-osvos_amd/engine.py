@@ -1132,6 +1132,29 @@ class Engine:
         return {names.raw[64 * i:64 * i + 64].split(b'\0')[0].decode(): (int(counts[i]), float(ms[i]), float(fl[i]))
                 for i in range(n.value)}
 
+    PLAN_LOG_FIELDS = ('kernel_id', 'kmajor', 'bn', 'tiles', 'ksteps', 'deep', 'dp_q', 'per', 'nwg', 'splitk', 'tprefix', 'torder',
+                       'fixup', 'budget')          # include/eosvos.h EOSVOS_PLAN_LOG_FIELDS
+
+    def plan_log(self, on=True):
+        """Record how every tiled-conv launch is planned from now on (host bookkeeping for the tests; clears the log)."""
+        _ffi.check(self.lib.eosvos_test_conv_plan_log(self.h, int(on)))
+
+    def plan_log_read(self):
+        """The launches since plan_log(True), in order: one dict per launch with 'kernel' (symbol) and PLAN_LOG_FIELDS
+        (include/eosvos.h eosvos_test_conv_plan_log_read).  Raises when more launches ran than the log keeps."""
+        mx, nf = 16, len(self.PLAN_LOG_FIELDS)
+        names = ctypes.create_string_buffer(64 * mx)
+        fields, n = (ctypes.c_int * (mx * nf))(), ctypes.c_int()
+        _ffi.check(self.lib.eosvos_test_conv_plan_log_read(self.h, mx, names, fields, ctypes.byref(n)))
+        if n.value > mx:
+            raise _ffi.EosvosError(f'plan log: {n.value} launches, {mx} kept')
+        out = []
+        for i in range(n.value):
+            rec = {'kernel': names.raw[64 * i:64 * i + 64].split(b'\0')[0].decode()}
+            rec.update(zip(self.PLAN_LOG_FIELDS, (int(v) for v in fields[i * nf:(i + 1) * nf])))
+            out.append(rec)
+        return out
+
     def mfma_probe(self, iters=20000):
         """Sustained fp32 MFMA TFLOP/s of this device (register-only calibration kernel)."""
         ms, fl = ctypes.c_float(), ctypes.c_double()
@@ -1174,7 +1197,7 @@ class Engine:
         Cout, _, k, _ = w_oihw.shape
         Ho = (H + 2 * pad - dil * (k - 1) - 1) // stride + 1
         Wo = (W + 2 * pad - dil * (k - 1) - 1) // stride + 1
-        y = torch.empty(B, Ho, Wo, Cout, device=self.device)
+        y = torch.full((B, Ho, Wo, Cout), float('nan'), device=self.device)          # an element no workgroup wrote stays NaN
         p = lambda t: _ptr(t) if t is not None else None
         _ffi.check(self.lib.eosvos_test_conv_algo(self.h, self.ALGOS[algo], _ptr(x_nhwc), _ptr(w_oihw), p(scale), p(bias),
                                                   p(res), int(relu), B, H, W, Cin, Cout, k, stride, dil, pad, _ptr(y)))
@@ -1185,8 +1208,8 @@ class Engine:
         like x) is <= 0, passed to the engine as mask bytes."""
         B, H, W, Cin = x_nhwc.shape
         Cout, _, k, _ = w_oihw.shape
-        dx = torch.empty_like(x_nhwc)
-        dw = torch.empty_like(w_oihw)
+        dx = torch.full_like(x_nhwc, float('nan'))          # an element no workgroup wrote stays NaN
+        dw = torch.full_like(w_oihw, float('nan'))
         m8 = _relu_bits(mask)
         _ffi.check(self.lib.eosvos_test_conv_bwd_algo(self.h, self.ALGOS[algo], _ptr(x_nhwc), _ptr(w_oihw), _ptr(g_nhwc),
                                                       _optr(scale), _optr(m8), B, H, W, Cin, Cout, k, stride, dil, pad, _ptr(dx),
@@ -1262,7 +1285,7 @@ class Engine:
         if gx_m8 is not None:
             assert gx_m8.dtype == torch.uint8 and gx_m8.is_contiguous() and tuple(gx_m8.shape) == (B, H, W, a.gx.ld // 4), tuple(gx_m8.shape)
             a.gx_m8 = gx_m8.data_ptr()
-        dw = torch.empty_like(w_oihw) if want_dw else None
+        dw = torch.full_like(w_oihw, float('nan')) if want_dw else None
         if dw is not None:
             a.dw_oihw = dw.data_ptr()
         torch.cuda.synchronize(self.device)

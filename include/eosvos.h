@@ -865,6 +865,17 @@ int eosvos_mfma_probe(eosvos_engine* e, int iters, float* ms_host, double* flops
 int eosvos_profile_launches(eosvos_engine* e, int on);
 int eosvos_profile_read(eosvos_engine* e, int max_kernels, char* names, int64_t* counts, double* ms_host,
                         double* flops_host, int* n_out_host);
+/* Test aid: a host-side log of how every tiled-conv launch was planned (off by default; no device work, no synchronisation, no
+ * effect on any launch).  plan_log(e, 1) clears the log and starts recording, plan_log(e, 0) stops; the first 16 launches are
+ * kept.  plan_log_read copies min(launches, max_records, 16) records: the main kernel's symbol (names: max_records x 64 chars)
+ * and EOSVOS_PLAN_LOG_FIELDS ints per record, in this order: kernel id, K-major gather, column-tile width, tiles, K steps of
+ * one tile, deep variant (0 / 1 / 2), whole tiles per workgroup (dp_q), streamed K steps per workgroup (per), workgroups,
+ * split-K chunks, tap table attached, longest-first tile order attached, fix-up pass launched, workgroups the launch
+ * planned for (eosvos_set_wg_budget).  A launch taken by a streaming kernel has zeros in the plan fields.  *n_out_host: the
+ * launches seen since the log was enabled (more than 16: the later ones were dropped). */
+#define EOSVOS_PLAN_LOG_FIELDS 14
+int eosvos_test_conv_plan_log(eosvos_engine* e, int on);
+int eosvos_test_conv_plan_log_read(eosvos_engine* e, int max_records, char* names, int* fields_host, int* n_out_host);
 int eosvos_debug_tensor(eosvos_engine* e, const char* name, float** ptr_out, int64_t* dims4_out);
 /* Low-level op entry used by the kernel parity tests: a single NHWC convolution
  * y = relu?(a*conv(x,w)+b (+res)); w is OIHW; all dense tensors; stride/dil/pad as torch. */
@@ -878,7 +889,9 @@ int eosvos_test_conv(eosvos_engine* e, const float* x_nhwc, const float* w_oihw,
 #define EOSVOS_ALGO_WINO_F2 2  /* Winograd F(2x2,3x3); dilated convs as d*d interleaved sub-grids */
 #define EOSVOS_ALGO_WINO_F4 3  /* Winograd F(4x4,3x3) */
 /* The same convolution through the production forward path with the algorithm forced (3x3 / stride 1 /
- * pad == dilation <= 8 for the Winograd forms).  torchvision Bottleneck / ASPP / decoder convs, SURVEY 2.2 K3/K4. */
+ * pad == dilation <= 8 for the Winograd forms).  torchvision Bottleneck / ASPP / decoder convs, SURVEY 2.2 K3/K4.
+ * This entry, eosvos_test_conv_bwd_algo and eosvos_test_conv_views plan their launches under the workgroup budget of `e`
+ * (eosvos_set_wg_budget), as the network's passes do; their weight-gradient slabs are sized for every budget. */
 int eosvos_test_conv_algo(eosvos_engine* e, int algo, const float* x_nhwc, const float* w_oihw,
                           const float* scale, const float* bias, const float* res_nhwc, int relu,
                           int B, int H, int W, int Cin, int Cout, int k, int stride, int dil, int pad,

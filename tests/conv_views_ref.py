@@ -69,6 +69,43 @@ def wgrad_ref(g, x, wshape, a, stride, dil, pad):
     return torch.nn.grad.conv2d_weight(nchw(x.double()), tuple(wshape), ga, stride, pad, dil)
 
 
+def _rows(t, dtype):
+    return t.to(dtype).reshape(-1, t.shape[-1])
+
+
+def fwd_ref_mm(x, w, a, b, res=None, relu=False, dtype=torch.float64):
+    """fwd_ref of a 1x1 stride-1 unpadded conv as ONE matrix product [pixels x Cin] [Cin x Cout], computed in `dtype` on the
+    device the operands live on (long reductions over many pixels, where torch's CPU fp64 convolution is slow; with
+    dtype = float32: the plain single-precision evaluation of the same op that an error bound can be taken from)."""
+    Co, Ci = w.shape[:2]
+    y = _rows(x, dtype) @ w.to(dtype).reshape(Co, Ci).t()
+    if a is not None:
+        y = y * a.to(dtype)
+    if b is not None:
+        y = y + b.to(dtype)
+    if res is not None:
+        y = y + _rows(res, dtype)
+    return (F.relu(y) if relu else y).reshape(*x.shape[:-1], Co)
+
+
+def dgrad_ref_mm(g, w, a, m8=None, mask_c0=0, dtype=torch.float64):
+    """dgrad_ref (no initial contents, no added tensor) of a 1x1 stride-1 unpadded conv: M * ((a * g) [pixels x Cout] w [Cout x Cin])."""
+    Co, Ci = w.shape[:2]
+    ga = _rows(g, dtype) if a is None else _rows(g, dtype) * a.to(dtype)
+    gx = (ga @ w.to(dtype).reshape(Co, Ci)).reshape(*g.shape[:-1], Ci)
+    if m8 is not None:
+        M = unpack_bits(m8)
+        M[..., :mask_c0] = True
+        gx = gx * M
+    return gx
+
+
+def wgrad_ref_mm(g, x, a, dtype=torch.float64):
+    """wgrad_ref of a 1x1 stride-1 unpadded conv: dw [Cout][Cin][1][1] = (a * g)^T [Cout x pixels] x [pixels x Cin]."""
+    ga = _rows(g, dtype) if a is None else _rows(g, dtype) * a.to(dtype)
+    return (ga.t() @ _rows(x, dtype)).reshape(g.shape[-1], x.shape[-1], 1, 1)
+
+
 def dgrad_taps_ref(g, w, a, d):
     """dgrad(a * g) of a stride-1 conv with padding = d * (k // 2), tap by tap: pixel (y, x) of g reaches input pixel
     (y + dy, x + dx), (dy, dx) = ((ky, kx) - k // 2) * d, through w[:, :, ky, kx] -- one fp64 matrix product per tap, on the

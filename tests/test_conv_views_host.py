@@ -51,6 +51,25 @@ def test_mask_bytes_round_trip_and_ignore_the_high_bits():
     assert R.relu_bytes(one).flatten().tolist() == [0, 0, 2, 0]
 
 
+def test_matrix_product_forms_of_the_1x1_references_are_the_conv_forms():
+    """fwd_ref_mm / dgrad_ref_mm / wgrad_ref_mm (tests/test_gpu_conv_plans.py: long reductions) against the convolution forms."""
+    g = torch.Generator().manual_seed(5)
+    B, H, W, Ci, Co = 2, 5, 7, 24, 16
+    x = torch.relu(torch.randn(B, H, W, Ci, generator=g))
+    w = torch.randn(Co, Ci, 1, 1, generator=g)
+    a, b = torch.rand(Co, generator=g) + 0.5, torch.randn(Co, generator=g)
+    res, gy = torch.randn(B, H, W, Co, generator=g), torch.randn(B, H, W, Co, generator=g)
+    m8 = R.relu_bytes(x)
+    for relu in (False, True):
+        assert _rel(R.fwd_ref_mm(x, w, a, b, res=res, relu=relu), R.fwd_ref(x, w, a, b, 1, 1, 0, res=res, relu=relu)) < 1e-14
+    ref = R.dgrad_ref(gy, w, a, (H, W), 1, 1, 0, m8=m8, mask_c0=8)
+    got = R.dgrad_ref_mm(gy, w, a, m8=m8, mask_c0=8)
+    assert _rel(got, ref) < 1e-14 and torch.equal(got == 0, ref == 0)
+    assert _rel(R.wgrad_ref_mm(gy, x, a), R.wgrad_ref(gy, x, w.shape, a, 1, 1, 0)) < 1e-14
+    f32 = R.fwd_ref_mm(x, w, a, b, res=res, relu=True, dtype=torch.float32)
+    assert f32.dtype == torch.float32 and 0 < _rel(f32.double(), R.fwd_ref_mm(x, w, a, b, res=res, relu=True)) < 1e-5
+
+
 @pytest.mark.parametrize('downsample', [False, True], ids=['identity', 'downsample'])
 def test_bottleneck_input_gradient_is_the_engines_composition(downsample):
     """torchvision Bottleneck (stride on conv2).  Identity block: g_xin = M * (g_out + dgrad_conv1(a1 * g_t1)) -- the fused-add

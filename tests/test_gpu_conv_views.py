@@ -356,13 +356,19 @@ def test_added_tensor_goes_in_before_the_old_contents(eng, mode, plan):
     gx = gx0.to(DEV).clone()
     if plan == 'fixup':
         eng.set_wg_budget(64)
+    eng.plan_log(True)
     try:
         with matrix_mode(mode), symbols(eng, syms, f'both {plan} {mode}'):
             eng.test_conv_views('auto', w.to(DEV), 1, 1, 0, (B, H, W), scale=a.to(DEV), g=g.to(DEV), gx=gx, add=addt.to(DEV),
                                 accum=True, gx_m8=m8.to(DEV))
+        logged = eng.plan_log_read()
     finally:
+        eng.plan_log(False)
         if plan == 'fixup':
             eng.set_wg_budget(0)          # the module's engine runs under the default budget
+    if plan == 'fixup':      # the op-level entry plans under the engine's budget: 10 tiles x 16 K steps in runs of 4 (40 workgroups under 512 too)
+        assert len(logged) == 1, logged
+        assert {k: logged[0][k] for k in ('budget', 'fixup', 'per', 'nwg')} == dict(budget=64, fixup=1, per=4, nwg=40), logged
     assert _same_bits(gx.cpu(), want), f'{plan} {mode}: {int((_bits(gx.cpu()) != _bits(want)).sum())} elements differ'
 
 
