@@ -202,6 +202,8 @@ struct eosvos_engine {
   float loss_ignore = 0.f;
   int* prop_count = nullptr;            // eosvos_propagation_targets: per-frame positive counts
   float* lovasz_scratch = nullptr;      // sort buffers of the Lovasz hinge kinds, allocated when one is first selected or used
+  float* bootstrap_scratch = nullptr;   // histograms, state and partials of the bootstrapped BCE, allocated like lovasz_scratch
+  int bootstrap_q = 16384;              // eosvos_set_loss_bootstrap: round(fraction * 65536), default 0.25
   int* aug_tab = nullptr;               // eosvos_warp_affine: adelta[W] bdelta[W] X0[H] Y0[H], then the nonzero counter
   float* aug_ctab = nullptr;            // bicubic coefficients at 1/32 pixel: [32][4]
   // the call scratch of every evaluation-stage entry point (scratch_for, scratch_layout.h; grow-only, freed by destroy).  One
@@ -2310,7 +2312,7 @@ int eosvos_forward(eosvos_engine* e, const float* images, int batch, float* logi
 }
 namespace {
 inline bool lovasz_kind(int kind) { return kind == EOSVOS_LOSS_LOVASZ_HINGE || kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT; }
-inline bool loss_kind_ok(int kind) { return kind >= EOSVOS_LOSS_BCE && kind <= EOSVOS_LOSS_LOVASZ_HINGE_FLAT; }
+inline bool loss_kind_ok(int kind) { return kind >= EOSVOS_LOSS_BCE && kind <= EOSVOS_LOSS_BOOTSTRAPPED_BCE; }
 // a void label is a finite value no target can take
 inline bool ignore_ok(float v) { return std::isfinite(v) && (v < 0.f || v > 1.f); }
 constexpr int PROP_MAX_FRAMES = 1024;
@@ -2326,6 +2328,17 @@ int lovasz_ensure(eosvos_engine* e) {
   }
   return 0;
 }
+// the bootstrapped BCE's scratch, for maxB sets (its size does not depend on the number of pixels); 0 on success
+int bootstrap_ensure(eosvos_engine* e) {
+  if (e->bootstrap_scratch) return 0;
+  if ((int64_t)e->maxB * e->H * e->W >= ((int64_t)1 << 31)) return fail("bootstrapped cross-entropy: a set must have fewer than 2^31 pixels");
+  e->bootstrap_scratch = e->falloc(bootstrap_scratch_floats(e->maxB));
+  if (!e->bootstrap_scratch) {
+    (void)hipGetLastError();              // as lovasz_ensure
+    return fail("bootstrapped cross-entropy: out of device memory for the selection scratch");
+  }
+  return 0;
+}
 // Loss `kind` (checked by the caller) of `images` maps of n_per_image pixels -- the Lovasz kinds: per map, or with `flat` over
 // all of them as one set -- with its gradient, into the device pointers loss / dlogits.  `ignore`: the void label, or null.
 int loss_eval(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n_per_image, int images, int flat,
@@ -2333,6 +2346,11 @@ int loss_eval(eosvos_engine* e, int kind, const float* logits, const float* mask
   if (lovasz_kind(kind)) {
     if (lovasz_ensure(e)) return 1;
     launch_lovasz(logits, masks, dlogits, loss, e->lovasz_scratch, n_per_image, images, flat, ignore, e->s);
+  } else if (kind == EOSVOS_LOSS_BOOTSTRAPPED_BCE) {          // per image, or (`flat`: caller tensors) all elements one set
+    if (bootstrap_ensure(e)) return 1;
+    if (n_per_image * (flat ? images : 1) >= ((int64_t)1 << 31)) return fail("bootstrapped cross-entropy: a set must have fewer than 2^31 pixels");
+    launch_bootstrap_bce(logits, masks, dlogits, loss, e->bootstrap_scratch, flat ? n_per_image * images : n_per_image,
+                         flat ? 1 : images, e->bootstrap_q, ignore, e->s);
   } else {
     launch_loss(kind, logits, masks, dlogits, loss, e->bce_partial, n_per_image * images, ignore, e->s);
   }
@@ -2399,7 +2417,15 @@ int eosvos_set_loss(eosvos_engine* e, int kind) {
   if (!e) return fail("null engine");
   if (!loss_kind_ok(kind)) return fail("unknown loss kind");
   if (lovasz_kind(kind) && lovasz_ensure(e)) return 1;
+  if (kind == EOSVOS_LOSS_BOOTSTRAPPED_BCE && bootstrap_ensure(e)) return 1;
   e->loss_kind = kind;
+  return 0;
+}
+int eosvos_set_loss_bootstrap(eosvos_engine* e, float fraction) {
+  if (!e) return fail("null engine");
+  if (!(fraction > 0.f && fraction <= 1.f)) return fail("the bootstrap fraction must be in (0, 1]");      // (NaN fails both)
+  const long q = lround((double)fraction * 65536.0);
+  e->bootstrap_q = (int)(q < 1 ? 1 : q > 65536 ? 65536 : q);
   return 0;
 }
 int eosvos_bce(eosvos_engine* e, const float* logits, const float* masks, int64_t n, float* loss_out,

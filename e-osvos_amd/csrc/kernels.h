@@ -456,6 +456,16 @@ void launch_loss(int kind, const float* logits, const float* gt, float* dlogits,
 int64_t lovasz_scratch_floats(int64_t n_total, int max_images);
 void launch_lovasz(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_image,
                    int images, int flat, const float* ignore, hipStream_t s);
+// Bootstrapped BCE (bootstrap_kernels.hip): `sets` sets of n_per_set pixels; per set the k = max(1, (|V| * q + 32768) >> 16)
+// valid pixels with the largest keys -x * (2 * (t >= .5) - 1) are kept (ties at the threshold share the remaining slots
+// with weight r / T), their BCE terms summed and divided by k; the loss is the mean over the sets, each gradient scaled by
+// 1 / (k * sets) and exactly +0 at a dropped or void pixel.  An exact three-pass radix select (11 + 11 + 10 bits) on integer
+// histograms, fixed-order float sums: bit-reproducible.  q in [1, 65536]; n_per_set < 2^31; scratch:
+// bootstrap_scratch_floats(sets) floats, zeroed by the call itself.
+constexpr int BOOTSTRAP_BLOCKS = 256;             // cap of the grid per set (256 threads each)
+int64_t bootstrap_scratch_floats(int max_sets);
+void launch_bootstrap_bce(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_set,
+                          int sets, int q, const float* ignore, hipStream_t s);
 // targets = 1 where probs >= hi, 0 where probs < lo, `ignore` between, for n_frames maps of n_pix; n_pos[frame] (zeroed by the
 // caller) += the frame's number of 1s
 void launch_propagation_targets(const float* probs, float* targets, int* n_pos, int n_frames, int64_t n_pix, float lo, float hi,

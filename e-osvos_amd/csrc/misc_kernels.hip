@@ -9,6 +9,7 @@
 #include <cassert>
 
 #include "kernels.h"
+#include "loss_expr.h"
 
 namespace eosvos {
 
@@ -1458,10 +1459,7 @@ __device__ __forceinline__ long valid_total(const int* __restrict__ cnt, int nb,
   const int lo = block_sum_i((int)(c & 0xffff), shi), hi = block_sum_i((int)(c >> 16), shi);
   return ((long)hi << 16) + lo;
 }
-__device__ __forceinline__ float bce_grad(float xv, float tv, float e /*exp(-|xv|)*/, float inv_n) {
-  const float sig = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-  return (sig - tv) * inv_n;
-}
+// (bce_value / bce_grad: loss_expr.h, shared with bootstrap_kernels.hip)
 // VOID = false: dx = dL/dx with the host's inv_n = 1 / n
 template <bool VOID>
 __global__ __launch_bounds__(256) void bce_partial_kernel(const float* __restrict__ x, const float* __restrict__ t,
@@ -1475,7 +1473,7 @@ __global__ __launch_bounds__(256) void bce_partial_kernel(const float* __restric
     const float xv = x[i], tv = t[i];
     const bool ok = !VOID || tv != ign;
     const float e = expf(-fabsf(xv));
-    const float v = fmaxf(xv, 0.f) - xv * tv + log1pf(e);
+    const float v = bce_value(xv, tv, e);
     s = ok ? s + v : s;
     c += ok ? 1 : 0;
     if constexpr (!VOID) dx[i] = bce_grad(xv, tv, e, inv_n);

@@ -8,7 +8,7 @@ import ctypes
 
 import torch
 
-from . import _ffi
+from . import _ffi, bootstrap
 from .topology import ARCH_ID, norm_layers, trainable
 
 
@@ -64,7 +64,23 @@ def _touched(*tensors):
 
 LR_LEVELS = {'NEURON': 0, 'TENSOR': 1, 'SINGLE': 2, 'PARAM': 3}      # include/eosvos.h EOSVOS_LR_*
 LOSS_KINDS = {'cross_entropy': 0, 'dice': 1, 'cross_entropy_and_dice': 2, 'class_balanced_cross_entropy': 3,
-              'lovasz_hinge': 4, 'lovasz_hinge_flat': 5}      # the last two: networks/loss_lovasz.py:78-111, per_image True / False
+              'lovasz_hinge': 4, 'lovasz_hinge_flat': 5,      # these two: networks/loss_lovasz.py:78-111, per_image True / False
+              'bootstrapped_cross_entropy': 6}                # the hardest fraction of the pixels per image (bootstrap.py)
+
+
+def resolve_loss(name, fraction=None):
+    """A spelled loss name -> (kind id, fraction or None).  `bootstrapped_cross_entropy_<P>` carries P percent; `fraction`
+    is the keyword form, for that kind only; the two may not disagree.  None: the engine's current fraction stays.  A bad
+    spelling under the bootstrap prefix raises NotImplementedError, any other unknown name KeyError."""
+    base, f = bootstrap.parse(name)
+    kind = LOSS_KINDS[base]
+    if fraction is not None:
+        if base != bootstrap.NAME:
+            raise ValueError(f"fraction= belongs to '{bootstrap.NAME}', not to '{name}'")
+        if f is not None and bootstrap.q_of(f) != bootstrap.q_of(fraction):
+            raise ValueError(f"loss_func='{name}' and fraction={fraction!r} disagree")
+        f = fraction
+    return kind, (None if f is None else bootstrap.check_fraction(f))
 
 
 def check_ignore(ignore):
@@ -203,13 +219,27 @@ class Engine:
         self.lr_level, self.lr_log, self.n_lr_store = level, bool(use_log), n
         self.synchronize()
 
-    def set_loss(self, name, ignore=None):
-        """Loss of finetune_step / meta_grad (`loss_func`, helper_func.py:28-56) and its void label (None: every pixel counts)."""
-        if name not in LOSS_KINDS:
+    def set_loss(self, name, ignore=None, fraction=None):
+        """Loss of finetune_step / meta_grad (`loss_func`, helper_func.py:28-56) and its void label (None: every pixel counts).
+        `bootstrapped_cross_entropy_<P>` or `fraction=` also set the engine's bootstrap fraction (see `_loss_kind`)."""
+        if bootstrap.parse(name)[0] not in LOSS_KINDS:
             raise NotImplementedError(name)             # helper_func.py:55-56
         v = None if ignore is None else check_ignore(ignore)
-        _ffi.check(self.lib.eosvos_set_loss(self.h, LOSS_KINDS[name]))
+        _ffi.check(self.lib.eosvos_set_loss(self.h, self._loss_kind(name, fraction)))
         _ffi.check(self.lib.eosvos_set_loss_ignore(self.h, int(v is not None), v or 0.0))
+
+    def set_loss_bootstrap(self, fraction):
+        """The fraction of `bootstrapped_cross_entropy` for every later evaluation on this engine (`eosvos_set_loss_bootstrap`;
+        0.25 on a new engine)."""
+        _ffi.check(self.lib.eosvos_set_loss_bootstrap(self.h, bootstrap.check_fraction(fraction)))
+
+    def _loss_kind(self, name, fraction=None):
+        """The kind id of a spelled loss name (`resolve_loss`); a fraction carried by the name or the keyword becomes the
+        engine's before the call that follows."""
+        kind, f = resolve_loss(name, fraction)
+        if f is not None:
+            self.set_loss_bootstrap(f)
+        return kind
 
     def set_norm(self, gamma, beta, mean, var, eps=1e-5):
         ts = [_dev_f32(t, self.device) for t in (gamma, beta, mean, var)]
@@ -351,10 +381,11 @@ class Engine:
 
     def _loss_call(self, kind, masks, ignore, out):
         """eosvos_loss, or eosvos_loss_ignore with a void label, on the last forward."""
+        kid = self._loss_kind(kind)
         if ignore is None:
-            _ffi.check(self.lib.eosvos_loss(self.h, LOSS_KINDS[kind], _ptr(masks), masks.shape[0], _optr(out)))
+            _ffi.check(self.lib.eosvos_loss(self.h, kid, _ptr(masks), masks.shape[0], _optr(out)))
         else:
-            _ffi.check(self.lib.eosvos_loss_ignore(self.h, LOSS_KINDS[kind], _ptr(masks), masks.shape[0], ignore, _optr(out)))
+            _ffi.check(self.lib.eosvos_loss_ignore(self.h, kid, _ptr(masks), masks.shape[0], ignore, _optr(out)))
 
     def _verify_step(self, images, masks, loss_kind=None, ignore=None):
         """The fine-tune-step half of the guard (see verify_matrix_mode): one step in each split mode from the same weights.
@@ -436,10 +467,11 @@ class Engine:
             self._chk_masks, self._chk_kind, self._chk_ignore = masks, 'cross_entropy', None
         return loss
 
-    def loss(self, kind, masks, ignore=None):
+    def loss(self, kind, masks, ignore=None, fraction=None):
         """kind: a compute_loss name (helper_func.py:28-56, see LOSS_KINDS); leaves dL/dlogits.  `ignore`: the void label --
-        pixels whose mask equals it are in no sum, count or ranking and get gradient 0 (`eosvos_loss_ignore`)."""
-        LOSS_KINDS[kind]
+        pixels whose mask equals it are in no sum, count or ranking and get gradient 0 (`eosvos_loss_ignore`).  `fraction`:
+        of `bootstrapped_cross_entropy`, as in `set_loss`."""
+        self._loss_kind(kind, fraction)
         ignore = None if ignore is None else check_ignore(ignore)
         assert masks.is_cuda and masks.dtype == torch.float32 and masks.is_contiguous()
         out = torch.empty(1, device=self.device)
@@ -448,16 +480,18 @@ class Engine:
             self._chk_masks, self._chk_kind, self._chk_ignore = masks, kind, ignore
         return out
 
-    def loss_of(self, kind, logits, masks, ignore=None):
+    def loss_of(self, kind, logits, masks, ignore=None, fraction=None):
         """Value of a compute_loss loss on arbitrary device tensors (one sample of a batch for
-        `batch_average: False`); no gradient is kept.  `ignore`: as in `loss` (`eosvos_loss_tensors_ignore`)."""
+        `batch_average: False`); no gradient is kept.  `ignore`: as in `loss` (`eosvos_loss_tensors_ignore`); `fraction`: of
+        `bootstrapped_cross_entropy`, as in `set_loss`."""
         logits, masks = logits.contiguous(), masks.contiguous()
         assert logits.is_cuda and masks.is_cuda and logits.numel() == masks.numel()
         out = torch.empty(1, device=self.device)
+        kid = self._loss_kind(kind, fraction)
         if ignore is None:
-            _ffi.check(self.lib.eosvos_loss_tensors(self.h, LOSS_KINDS[kind], _ptr(logits), _ptr(masks), logits.numel(), _ptr(out)))
+            _ffi.check(self.lib.eosvos_loss_tensors(self.h, kid, _ptr(logits), _ptr(masks), logits.numel(), _ptr(out)))
         else:
-            _ffi.check(self.lib.eosvos_loss_tensors_ignore(self.h, LOSS_KINDS[kind], _ptr(logits), _ptr(masks), logits.numel(),
+            _ffi.check(self.lib.eosvos_loss_tensors_ignore(self.h, kid, _ptr(logits), _ptr(masks), logits.numel(),
                                                            check_ignore(ignore), _ptr(out)))
         return out
 

@@ -13,14 +13,18 @@ Lovasz hinge of `networks/loss_lovasz.py:78-111` as `lovasz_hinge` (`per_image=T
 `lovasz_hinge_flat` (`per_image=False`); unknown names raise NotImplementedError as in the reference (`:55-56`).
 `loss_kwargs={'ignore': v}` marks the pixels whose target equals `v` as void for every kind: the reference's keyword for the
 Lovasz hinge (`networks/loss_lovasz.py:78-126`), the same rule for the others (in no sum and no count, gradient 0).
+`bootstrapped_cross_entropy` (`bootstrap.py`; not in the reference) averages the BCE of the hardest fraction of each image's
+pixels: the engine's fraction (0.25 by default), `bootstrapped_cross_entropy_<P>` for P percent, or `loss_kwargs={'fraction': f}`.
 """
 import random
 
 import numpy as np
 import torch
 
+from . import bootstrap
 from . import tta as tta_views
 from . import zoom as zoom_pass
+from .engine import resolve_loss
 from .networks import DeepLabV3, DeepLabV3Plus
 
 
@@ -28,9 +32,14 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
     """`compute_loss(loss_func, outputs, gts, loss_kwargs=None)`, helper_func.py:28-56.  The returned
     0-dim loss carries the engine handle so `MetaOptimizer.step(loss)` can run the backward."""
     loss_kwargs = loss_kwargs or {}
-    if loss_func not in ('cross_entropy', 'dice', 'cross_entropy_and_dice', 'class_balanced_cross_entropy',
-                         'lovasz_hinge', 'lovasz_hinge_flat'):
+    base, _ = bootstrap.parse(loss_func)                   # (a bad spelling under the bootstrap prefix: NotImplementedError)
+    if base not in ('cross_entropy', 'dice', 'cross_entropy_and_dice', 'class_balanced_cross_entropy',
+                    'lovasz_hinge', 'lovasz_hinge_flat', bootstrap.NAME):
         raise NotImplementedError(f"loss_func='{loss_func}'")
+    frac = {}
+    if loss_kwargs.get('fraction') is not None:            # the keyword form of bootstrapped_cross_entropy_<P>
+        resolve_loss(loss_func, loss_kwargs['fraction'])   # ValueError: another kind, out of (0, 1], or a suffix that disagrees
+        frac = {'fraction': loss_kwargs['fraction']}
     if loss_func == 'lovasz_hinge' and not loss_kwargs.get('per_image', True):
         loss_func = 'lovasz_hinge_flat'                    # loss_lovasz.py:89-90: the whole batch as one set
     if loss_func == 'class_balanced_cross_entropy' and not loss_kwargs.get('size_average', True):
@@ -42,11 +51,11 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
     gts = gts.contiguous().float()
     ign = {'ignore': loss_kwargs['ignore']} if loss_kwargs.get('ignore') is not None else {}      # void label, every kind
     if loss_kwargs.get('batch_average', True):
-        loss = eng.loss(loss_func, gts, **ign).view(())      # also leaves dL/dlogits in the engine
+        loss = eng.loss(loss_func, gts, **ign, **frac).view(())      # also leaves dL/dlogits in the engine
         loss._eosvos_engine = eng
         return loss
     # per-sample values (run_loader metrics, helper_func.py:131-137): every loss evaluated sample by sample
-    return torch.cat([eng.loss_of(loss_func, outputs[b], gts[b], **ign) for b in range(outputs.shape[0])])
+    return torch.cat([eng.loss_of(loss_func, outputs[b], gts[b], **ign, **frac) for b in range(outputs.shape[0])])
 
 
 def init_parent_model(architecture, encoder, train_encoder, decoder_norm_layer=None,

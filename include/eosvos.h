@@ -192,6 +192,34 @@ int eosvos_loss_bce(eosvos_engine* e, const float* masks, int batch, float* loss
  * engine usable with the other kinds. */
 #define EOSVOS_LOSS_LOVASZ_HINGE 4
 #define EOSVOS_LOSS_LOVASZ_HINGE_FLAT 5
+/* Bootstrapped (hard-pixel) cross-entropy of OnAVOS / PReMVOS, `bootstrapped_cross_entropy`: per set, the BCE mean over the
+ * hardest fraction of the pixels only.  A set is one image of the batch for eosvos_loss* and the fused entry points; through
+ * eosvos_loss_tensors* the n elements are one set.  Within a set, V = the non-void pixels, n = |V|:
+ *   key    key_p = -z_p * (2 * (y_p >= .5) - 1), an exact fp32 sign flip (the Lovasz sign rule).  For hard targets BCE-with-
+ *          logits is strictly increasing in the key, so the top-k keys are the top-k losses; for soft targets this is the
+ *          documented ranking and the summed term is still the true BCE.  Keys are compared as order-preserving 32-bit
+ *          unsigned words (negative float: all bits flipped; otherwise the top bit set); -0 counts as +0; a NaN key maps to
+ *          0xFFFFFFFF, so a NaN logit at a valid pixel is selected and makes the loss NaN.
+ *   k      q = round(fraction * 65536), 1 <= q <= 65536;  k = max(1, (n * q + 32768) >> 16) in 64 bits.
+ *   tau    the k-th largest key;  G = #{key > tau}, T = #{key = tau}, r = k - G (1 <= r <= T).
+ *          w_p = 1 where key > tau, (float)r / (float)T where key = tau (one fp32 division, exactly 1 when r = T), else 0:
+ *          the tied pixels share the remaining slots, nothing depends on an index order.
+ *   loss   set loss = (sum_V w_p * bce_p) / k, bce_p = max(z, 0) - z * y + log1p(exp(-|z|));  loss = the mean of the set
+ *          losses over the images;  dL/dz_p = w_p * (sigmoid(z_p) - y_p) / (k * images).  A pixel with w_p = 0 and every void
+ *          pixel gets exactly +0, and the logit of a void pixel never reaches the result (it may be NaN / inf).  An empty V
+ *          gives set loss 0: an all-void image adds 0 to the mean.
+ * Fraction 1 keeps every valid pixel: EOSVOS_LOSS_BCE up to summation order.  Limits: fraction in (0, 1]; sets of fewer than
+ * 2^31 pixels; one kind, per image on the forward path (no whole-batch sibling).  The selection is an exact radix select on
+ * integer histograms and the sums run in a fixed order: loss and gradient are bit-identical from run to run.  The first use
+ * allocates a small scratch (about 27 KB per image of the largest batch) once; a failed allocation is reported and leaves
+ * the engine usable with the other kinds.  The default fraction 0.25 is OnAVOS's and is untuned here: no J&F figure exists
+ * for it, no dataset being at hand. */
+#define EOSVOS_LOSS_BOOTSTRAPPED_BCE 6
+/* The fraction of EOSVOS_LOSS_BOOTSTRAPPED_BCE for every evaluation on this engine (eosvos_loss, eosvos_loss_ignore,
+ * eosvos_loss_tensors[_ignore], eosvos_finetune_step, eosvos_meta_grad[_ex]): in (0, 1], anything else (NaN included) is an
+ * error and changes nothing.  Per engine, 0.25 on every new engine; an engine that shares another's state does not take it
+ * over. */
+int eosvos_set_loss_bootstrap(eosvos_engine* e, float fraction);
 int eosvos_loss(eosvos_engine* e, int kind, const float* masks, int batch, float* loss_out);
 /* The value of the last loss evaluated by eosvos_loss* / eosvos_finetune_step / eosvos_meta_grad*, copied to a DEVICE
  * float on the engine's stream without synchronising (several engines in flight on one GPU: concurrent meta tasks). */
