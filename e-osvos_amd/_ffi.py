@@ -68,6 +68,9 @@ _SIGNATURES = {
                                                   c_float_p]),
     'eosvos_set_loss_ignore': (ctypes.c_int, [_E, ctypes.c_int, ctypes.c_float]),
     'eosvos_set_loss_bootstrap': (ctypes.c_int, [_E, ctypes.c_float]),
+    'eosvos_set_loss_boundary': (ctypes.c_int, [_E, ctypes.c_int]),
+    'eosvos_boundary_f': (ctypes.c_int, [_E, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_float, c_float_p, c_float_p]),
     'eosvos_propagation_targets': (ctypes.c_int, [_E, c_float_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float,
                                                   ctypes.c_float, c_float_p, ctypes.POINTER(ctypes.c_int64)]),
     'eosvos_warp_affine': (ctypes.c_int, [_E, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,

@@ -204,6 +204,8 @@ struct eosvos_engine {
   float* lovasz_scratch = nullptr;      // sort buffers of the Lovasz hinge kinds, allocated when one is first selected or used
   float* bootstrap_scratch = nullptr;   // histograms, state and partials of the bootstrapped BCE, allocated like lovasz_scratch
   int bootstrap_q = 16384;              // eosvos_set_loss_bootstrap: round(fraction * 65536), default 0.25
+  float* boundary_scratch = nullptr;    // per-pixel maps and partials of the boundary-F kinds, allocated like lovasz_scratch
+  int boundary_radius = 0;              // eosvos_set_loss_boundary: 1 .. 16, 0 = the frame-size default
   int* aug_tab = nullptr;               // eosvos_warp_affine: adelta[W] bdelta[W] X0[H] Y0[H], then the nonzero counter
   float* aug_ctab = nullptr;            // bicubic coefficients at 1/32 pixel: [32][4]
   // the call scratch of every evaluation-stage entry point (scratch_for, scratch_layout.h; grow-only, freed by destroy).  One
@@ -2312,7 +2314,9 @@ int eosvos_forward(eosvos_engine* e, const float* images, int batch, float* logi
 }
 namespace {
 inline bool lovasz_kind(int kind) { return kind == EOSVOS_LOSS_LOVASZ_HINGE || kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT; }
-inline bool loss_kind_ok(int kind) { return kind >= EOSVOS_LOSS_BCE && kind <= EOSVOS_LOSS_BOOTSTRAPPED_BCE; }
+inline bool boundary_kind(int kind) { return kind == EOSVOS_LOSS_BOUNDARY_F || kind == EOSVOS_LOSS_BCE_AND_BOUNDARY_F; }
+// (7 is unassigned on purpose, see include/eosvos.h)
+inline bool loss_kind_ok(int kind) { return (kind >= EOSVOS_LOSS_BCE && kind <= EOSVOS_LOSS_BOOTSTRAPPED_BCE) || boundary_kind(kind); }
 // a void label is a finite value no target can take
 inline bool ignore_ok(float v) { return std::isfinite(v) && (v < 0.f || v > 1.f); }
 constexpr int PROP_MAX_FRAMES = 1024;
@@ -2339,6 +2343,31 @@ int bootstrap_ensure(eosvos_engine* e) {
   }
   return 0;
 }
+// the boundary-F kinds' scratch, sized for the engine's largest batch; 0 on success
+int boundary_ensure(eosvos_engine* e) {
+  if (e->boundary_scratch) return 0;
+  if ((int64_t)e->H * e->W >= ((int64_t)1 << 31)) return fail("boundary_f: an image must have fewer than 2^31 pixels");
+  e->boundary_scratch = e->falloc(boundary_scratch_floats((int64_t)e->maxB * e->H * e->W, e->maxB));
+  if (!e->boundary_scratch) {
+    (void)hipGetLastError();              // as lovasz_ensure
+    return fail("boundary_f: out of device memory for the boundary maps");
+  }
+  return 0;
+}
+// min(16, ceil(0.008 * the frame diagonal)): the DAVIS boundary tolerance (data.davis_bound_pix) as the window radius
+inline int boundary_default_radius(int H, int W) {
+  const int r = (int)std::ceil(0.008 * std::sqrt((double)H * H + (double)W * W));
+  return r < 1 ? 1 : r > 16 ? 16 : r;
+}
+// `images` maps of H x W; the combined kind evaluates the cross-entropy first and the boundary launches add to it
+int boundary_eval(eosvos_engine* e, bool combined, const float* logits, const float* masks, int H, int W, int images, int radius,
+                  const float* ignore, float* dlogits, float* loss) {
+  if (boundary_ensure(e)) return 1;
+  if (combined) launch_loss(EOSVOS_LOSS_BCE, logits, masks, dlogits, loss, e->bce_partial, (int64_t)H * W * images, ignore, e->s);
+  launch_boundary_f(logits, masks, dlogits, loss, e->boundary_scratch, H, W, images, radius ? radius : boundary_default_radius(H, W),
+                    combined ? 1 : 0, ignore, e->s);
+  return 0;
+}
 // Loss `kind` (checked by the caller) of `images` maps of n_per_image pixels -- the Lovasz kinds: per map, or with `flat` over
 // all of them as one set -- with its gradient, into the device pointers loss / dlogits.  `ignore`: the void label, or null.
 int loss_eval(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n_per_image, int images, int flat,
@@ -2351,6 +2380,12 @@ int loss_eval(eosvos_engine* e, int kind, const float* logits, const float* mask
     if (n_per_image * (flat ? images : 1) >= ((int64_t)1 << 31)) return fail("bootstrapped cross-entropy: a set must have fewer than 2^31 pixels");
     launch_bootstrap_bce(logits, masks, dlogits, loss, e->bootstrap_scratch, flat ? n_per_image * images : n_per_image,
                          flat ? 1 : images, e->bootstrap_q, ignore, e->s);
+  } else if (boundary_kind(kind)) {                           // needs the frame's shape: an image is the engine's H x W
+    if (n_per_image != (int64_t)e->H * e->W)
+      return fail("boundary_f: the loss needs the frame's shape, so n must be the engine's H * W (one image); use eosvos_boundary_f for another shape");
+    if (boundary_eval(e, kind == EOSVOS_LOSS_BCE_AND_BOUNDARY_F, logits, masks, e->H, e->W, images, e->boundary_radius, ignore,
+                      dlogits, loss))
+      return 1;
   } else {
     launch_loss(kind, logits, masks, dlogits, loss, e->bce_partial, n_per_image * images, ignore, e->s);
   }
@@ -2418,6 +2453,7 @@ int eosvos_set_loss(eosvos_engine* e, int kind) {
   if (!loss_kind_ok(kind)) return fail("unknown loss kind");
   if (lovasz_kind(kind) && lovasz_ensure(e)) return 1;
   if (kind == EOSVOS_LOSS_BOOTSTRAPPED_BCE && bootstrap_ensure(e)) return 1;
+  if (boundary_kind(kind) && boundary_ensure(e)) return 1;
   e->loss_kind = kind;
   return 0;
 }
@@ -2426,6 +2462,27 @@ int eosvos_set_loss_bootstrap(eosvos_engine* e, float fraction) {
   if (!(fraction > 0.f && fraction <= 1.f)) return fail("the bootstrap fraction must be in (0, 1]");      // (NaN fails both)
   const long q = lround((double)fraction * 65536.0);
   e->bootstrap_q = (int)(q < 1 ? 1 : q > 65536 ? 65536 : q);
+  return 0;
+}
+int eosvos_set_loss_boundary(eosvos_engine* e, int radius) {
+  if (!e) return fail("null engine");
+  if (radius < 0 || radius > 16) return fail("the boundary radius must be 1 .. 16, or 0 for the frame-size default");
+  e->boundary_radius = radius;
+  return 0;
+}
+int eosvos_boundary_f(eosvos_engine* e, const float* logits, const float* masks, int batch, int height, int width, int radius,
+                      int combined, int ignore_on, float ignore, float* loss_out, float* dlogits_out) {
+  ModeScope mode_scope(e);
+  if (!e || !logits || !masks || !loss_out) return fail("null argument");
+  if (batch < 1 || batch > e->maxB || height < 1 || width < 1) return fail("eosvos_boundary_f: bad geometry");
+  if ((int64_t)batch * height * width > (int64_t)e->maxB * e->H * e->W) return fail("eosvos_boundary_f: more pixels than the engine's scratch holds");
+  if (radius < 0 || radius > 16) return fail("the boundary radius must be 1 .. 16, or 0 for the frame-size default");
+  if (ignore_on && !ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  if (!dlogits_out) e->have_loss_grad = false;
+  if (boundary_eval(e, combined != 0, logits, masks, height, width, batch, radius, ignore_on ? &ignore : nullptr,
+                    dlogits_out ? dlogits_out : e->dlogits, loss_out))
+    return 1;
+  HIPOK(hipGetLastError());
   return 0;
 }
 int eosvos_bce(eosvos_engine* e, const float* logits, const float* masks, int64_t n, float* loss_out,

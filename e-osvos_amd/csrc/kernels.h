@@ -466,6 +466,14 @@ constexpr int BOOTSTRAP_BLOCKS = 256;             // cap of the grid per set (25
 int64_t bootstrap_scratch_floats(int max_sets);
 void launch_bootstrap_bce(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int64_t n_per_set,
                           int sets, int q, const float* ignore, hipStream_t s);
+// Soft boundary-F loss (boundary_kernels.hip; the definition: include/eosvos.h at EOSVOS_LOSS_BOUNDARY_F): `images` maps of
+// H x W pixels, radius in [1, 16]; the loss is the mean over the images of 1 - BF, the gradient goes to dlogits.  `add`: loss and
+// dlogits already hold the cross-entropy term of the combined kind and are added to.  No atomics, fixed-order sums: bit-
+// reproducible.  scratch: boundary_scratch_floats(images * H * W, images) floats, every word written before it is read.
+constexpr int BOUNDARY_BLOCKS = 1024;            // cap of the grid per image (256 threads each)
+int64_t boundary_scratch_floats(int64_t n_total, int max_images);
+void launch_boundary_f(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int H, int W, int images,
+                       int radius, int add, const float* ignore, hipStream_t s);
 // targets = 1 where probs >= hi, 0 where probs < lo, `ignore` between, for n_frames maps of n_pix; n_pos[frame] (zeroed by the
 // caller) += the frame's number of 1s
 void launch_propagation_targets(const float* probs, float* targets, int* n_pos, int n_frames, int64_t n_pix, float lo, float hi,

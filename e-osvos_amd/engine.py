@@ -8,7 +8,7 @@ import ctypes
 
 import torch
 
-from . import _ffi, bootstrap
+from . import _ffi, bootstrap, boundary
 from .topology import ARCH_ID, norm_layers, trainable
 
 
@@ -68,11 +68,18 @@ LOSS_KINDS = {'cross_entropy': 0, 'dice': 1, 'cross_entropy_and_dice': 2, 'class
               'bootstrapped_cross_entropy': 6}                # the hardest fraction of the pixels per image (bootstrap.py)
 
 
-def resolve_loss(name, fraction=None):
+def resolve_loss(name, fraction=None, radius=None):
     """A spelled loss name -> (kind id, fraction or None).  `bootstrapped_cross_entropy_<P>` carries P percent; `fraction`
     is the keyword form, for that kind only; the two may not disagree.  None: the engine's current fraction stays.  A bad
-    spelling under the bootstrap prefix raises NotImplementedError, any other unknown name KeyError."""
+    spelling under the bootstrap prefix raises NotImplementedError, any other unknown name KeyError.  The kinds that need the
+    frame's shape (`boundary.KINDS`) are consulted after LOSS_KINDS and give (kind id, None); their radius, from the name
+    or `radius=`, is `resolve_radius`'s, which this call checks too."""
+    radius = resolve_radius(name, radius)
     base, f = bootstrap.parse(name)
+    if base not in LOSS_KINDS and boundary.parse(name)[0] in boundary.KINDS:
+        if fraction is not None:
+            raise ValueError(f"fraction= belongs to '{bootstrap.NAME}', not to '{name}'")
+        return boundary.KINDS[boundary.parse(name)[0]], None
     kind = LOSS_KINDS[base]
     if fraction is not None:
         if base != bootstrap.NAME:
@@ -81,6 +88,20 @@ def resolve_loss(name, fraction=None):
             raise ValueError(f"loss_func='{name}' and fraction={fraction!r} disagree")
         f = fraction
     return kind, (None if f is None else bootstrap.check_fraction(f))
+
+
+def resolve_radius(name, radius=None):
+    """The window radius a spelled loss name asks for: `boundary_f_<r>` / `cross_entropy_and_boundary_f_<r>` carry r,
+    `radius` is the keyword form, for those kinds only; the two may not disagree.  None: the engine's current radius stays."""
+    base, r = boundary.parse(name)
+    if radius is not None:
+        if base not in boundary.KINDS:
+            raise ValueError(f"radius= belongs to {' / '.join(repr(k) for k in boundary.KINDS)}, not to '{name}'")
+        radius = boundary.check_radius(radius)
+        if r is not None and r != radius:
+            raise ValueError(f"loss_func='{name}' and radius={radius!r} disagree")
+        r = radius
+    return r
 
 
 def check_ignore(ignore):
@@ -219,13 +240,14 @@ class Engine:
         self.lr_level, self.lr_log, self.n_lr_store = level, bool(use_log), n
         self.synchronize()
 
-    def set_loss(self, name, ignore=None, fraction=None):
+    def set_loss(self, name, ignore=None, fraction=None, radius=None):
         """Loss of finetune_step / meta_grad (`loss_func`, helper_func.py:28-56) and its void label (None: every pixel counts).
-        `bootstrapped_cross_entropy_<P>` or `fraction=` also set the engine's bootstrap fraction (see `_loss_kind`)."""
-        if bootstrap.parse(name)[0] not in LOSS_KINDS:
+        `bootstrapped_cross_entropy_<P>` or `fraction=` also set the engine's bootstrap fraction, `boundary_f_<r>` /
+        `cross_entropy_and_boundary_f_<r>` or `radius=` its boundary radius (see `_loss_kind`)."""
+        if bootstrap.parse(name)[0] not in LOSS_KINDS and boundary.parse(name)[0] not in boundary.KINDS:
             raise NotImplementedError(name)             # helper_func.py:55-56
         v = None if ignore is None else check_ignore(ignore)
-        _ffi.check(self.lib.eosvos_set_loss(self.h, self._loss_kind(name, fraction)))
+        _ffi.check(self.lib.eosvos_set_loss(self.h, self._loss_kind(name, fraction, radius)))
         _ffi.check(self.lib.eosvos_set_loss_ignore(self.h, int(v is not None), v or 0.0))
 
     def set_loss_bootstrap(self, fraction):
@@ -233,12 +255,22 @@ class Engine:
         0.25 on a new engine)."""
         _ffi.check(self.lib.eosvos_set_loss_bootstrap(self.h, bootstrap.check_fraction(fraction)))
 
-    def _loss_kind(self, name, fraction=None):
-        """The kind id of a spelled loss name (`resolve_loss`); a fraction carried by the name or the keyword becomes the
-        engine's before the call that follows."""
-        kind, f = resolve_loss(name, fraction)
+    def set_loss_boundary(self, radius):
+        """The window radius of `boundary_f` / `cross_entropy_and_boundary_f` for every later evaluation on this engine
+        (`eosvos_set_loss_boundary`): 1 .. 16, or 0 for the frame-size default `boundary.default_radius(H, W)`, which a new
+        engine has."""
+        _ffi.check(self.lib.eosvos_set_loss_boundary(self.h, 0 if radius == 0 and not isinstance(radius, bool)
+                                                     else boundary.check_radius(radius)))
+
+    def _loss_kind(self, name, fraction=None, radius=None):
+        """The kind id of a spelled loss name (`resolve_loss`); a fraction or radius carried by the name or the keyword becomes
+        the engine's before the call that follows."""
+        kind, f = resolve_loss(name, fraction, radius)
+        r = resolve_radius(name, radius)
         if f is not None:
             self.set_loss_bootstrap(f)
+        if r is not None:
+            self.set_loss_boundary(r)
         return kind
 
     def set_norm(self, gamma, beta, mean, var, eps=1e-5):
@@ -467,11 +499,11 @@ class Engine:
             self._chk_masks, self._chk_kind, self._chk_ignore = masks, 'cross_entropy', None
         return loss
 
-    def loss(self, kind, masks, ignore=None, fraction=None):
+    def loss(self, kind, masks, ignore=None, fraction=None, radius=None):
         """kind: a compute_loss name (helper_func.py:28-56, see LOSS_KINDS); leaves dL/dlogits.  `ignore`: the void label --
         pixels whose mask equals it are in no sum, count or ranking and get gradient 0 (`eosvos_loss_ignore`).  `fraction`:
-        of `bootstrapped_cross_entropy`, as in `set_loss`."""
-        self._loss_kind(kind, fraction)
+        of `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, as in `set_loss`."""
+        self._loss_kind(kind, fraction, radius)
         ignore = None if ignore is None else check_ignore(ignore)
         assert masks.is_cuda and masks.dtype == torch.float32 and masks.is_contiguous()
         out = torch.empty(1, device=self.device)
@@ -480,20 +512,37 @@ class Engine:
             self._chk_masks, self._chk_kind, self._chk_ignore = masks, kind, ignore
         return out
 
-    def loss_of(self, kind, logits, masks, ignore=None, fraction=None):
+    def loss_of(self, kind, logits, masks, ignore=None, fraction=None, radius=None):
         """Value of a compute_loss loss on arbitrary device tensors (one sample of a batch for
         `batch_average: False`); no gradient is kept.  `ignore`: as in `loss` (`eosvos_loss_tensors_ignore`); `fraction`: of
-        `bootstrapped_cross_entropy`, as in `set_loss`."""
+        `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, as in `set_loss`.  The boundary kinds need the frame's
+        shape: they take one image of the engine's H * W elements only (`boundary_f` below takes any shape)."""
         logits, masks = logits.contiguous(), masks.contiguous()
         assert logits.is_cuda and masks.is_cuda and logits.numel() == masks.numel()
         out = torch.empty(1, device=self.device)
-        kid = self._loss_kind(kind, fraction)
+        kid = self._loss_kind(kind, fraction, radius)
         if ignore is None:
             _ffi.check(self.lib.eosvos_loss_tensors(self.h, kid, _ptr(logits), _ptr(masks), logits.numel(), _ptr(out)))
         else:
             _ffi.check(self.lib.eosvos_loss_tensors_ignore(self.h, kid, _ptr(logits), _ptr(masks), logits.numel(),
                                                            check_ignore(ignore), _ptr(out)))
         return out
+
+    def boundary_f(self, logits, masks, radius=None, ignore=None, combined=False):
+        """`boundary_f` (or with `combined` `cross_entropy_and_boundary_f`) of device tensors (B, H, W) or (H, W) of any frame
+        size that fits the engine's scratch (`eosvos_boundary_f`); `radius` None: that shape's default.  Returns (loss,
+        dL/dlogits of the logits' shape); the engine's own gradient is untouched."""
+        logits, masks = logits.contiguous(), masks.contiguous()
+        assert logits.is_cuda and masks.is_cuda and logits.dtype == masks.dtype == torch.float32 and logits.shape == masks.shape
+        assert logits.dim() in (2, 3)
+        b = logits.shape[0] if logits.dim() == 3 else 1
+        h, w = logits.shape[-2:]
+        v = None if ignore is None else check_ignore(ignore)
+        out, grad = torch.empty(1, device=self.device), torch.empty_like(logits)
+        _ffi.check(self.lib.eosvos_boundary_f(self.h, _ptr(logits), _ptr(masks), b, h, w,
+                                              0 if radius is None else boundary.check_radius(radius), int(bool(combined)),
+                                              int(v is not None), v or 0.0, _ptr(out), _ptr(grad)))
+        return out, grad
 
     def propagation_targets(self, probs, lo, hi, ignore, counts=True):
         """Pseudo-label targets of online adaptation with an uncertainty band (`eosvos_propagation_targets`): probs (F, ...)

@@ -15,13 +15,16 @@ Lovasz hinge of `networks/loss_lovasz.py:78-111` as `lovasz_hinge` (`per_image=T
 Lovasz hinge (`networks/loss_lovasz.py:78-126`), the same rule for the others (in no sum and no count, gradient 0).
 `bootstrapped_cross_entropy` (`bootstrap.py`; not in the reference) averages the BCE of the hardest fraction of each image's
 pixels: the engine's fraction (0.25 by default), `bootstrapped_cross_entropy_<P>` for P percent, or `loss_kwargs={'fraction': f}`.
+`boundary_f` / `cross_entropy_and_boundary_f` (`boundary.py`; not in the reference) are the soft boundary-F loss and its sum
+with `cross_entropy`: the engine's window radius (by default the DAVIS tolerance of the frame size), `boundary_f_<r>` for
+r pixels, or `loss_kwargs={'radius': r}`.
 """
 import random
 
 import numpy as np
 import torch
 
-from . import bootstrap
+from . import bootstrap, boundary
 from . import tta as tta_views
 from . import zoom as zoom_pass
 from .engine import resolve_loss
@@ -34,12 +37,15 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
     loss_kwargs = loss_kwargs or {}
     base, _ = bootstrap.parse(loss_func)                   # (a bad spelling under the bootstrap prefix: NotImplementedError)
     if base not in ('cross_entropy', 'dice', 'cross_entropy_and_dice', 'class_balanced_cross_entropy',
-                    'lovasz_hinge', 'lovasz_hinge_flat', bootstrap.NAME):
-        raise NotImplementedError(f"loss_func='{loss_func}'")
+                    'lovasz_hinge', 'lovasz_hinge_flat', bootstrap.NAME) and boundary.parse(loss_func)[0] not in boundary.KINDS:
+        raise NotImplementedError(f"loss_func='{loss_func}'")              # (a bad spelling under a boundary prefix too)
     frac = {}
     if loss_kwargs.get('fraction') is not None:            # the keyword form of bootstrapped_cross_entropy_<P>
         resolve_loss(loss_func, loss_kwargs['fraction'])   # ValueError: another kind, out of (0, 1], or a suffix that disagrees
         frac = {'fraction': loss_kwargs['fraction']}
+    if loss_kwargs.get('radius') is not None:              # the keyword form of boundary_f_<r>
+        resolve_loss(loss_func, radius=loss_kwargs['radius'])      # ValueError: another kind, out of 1 .. 16, or a suffix that disagrees
+        frac = dict(frac, radius=loss_kwargs['radius'])
     if loss_func == 'lovasz_hinge' and not loss_kwargs.get('per_image', True):
         loss_func = 'lovasz_hinge_flat'                    # loss_lovasz.py:89-90: the whole batch as one set
     if loss_func == 'class_balanced_cross_entropy' and not loss_kwargs.get('size_average', True):

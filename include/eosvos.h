@@ -220,6 +220,38 @@ int eosvos_loss_bce(eosvos_engine* e, const float* masks, int batch, float* loss
  * error and changes nothing.  Per engine, 0.25 on every new engine; an engine that shares another's state does not take it
  * over. */
 int eosvos_set_loss_bootstrap(eosvos_engine* e, float fraction);
+/* Soft boundary-F loss, `boundary_f`: the soft form of the DAVIS F measure (Bokhovkin & Burnaev, "Boundary Loss for Remote
+ * Sensing Imagery Semantic Segmentation", 2019).  Not in the reference.  Per image of H x W pixels, z the logits, y the targets,
+ * V the valid (non-void) pixels; every window is square, centred, clipped to the frame and ranges over valid pixels only:
+ *   q = sigmoid(-z), formed with the branch on the sign of z, never as 1 - sigmoid(z);  h = 1 - y
+ *   pb(i) = max_{N1(i)} q - q(i),  gb(i) = max_{N1(i)} h - h(i)     N1 the 3 x 3 window; both 0 at void pixels
+ *   pe(i) = max_{Nr(i)} pb,        ge(i) = max_{Nr(i)} gb           Nr the (2r+1)^2 window; both 0 at void pixels
+ *   Sp = sum_V pb + eps,  Sg = sum_V gb + eps,  P = sum_V pb ge / Sp,  R = sum_V pe gb / Sg,  BF = 2PR / (P + R + eps),
+ *   eps = 1e-7;  image loss = 1 - BF, 0 (with gradient 0) for an image without a valid pixel;  loss = the mean over the images.
+ * Among equal maxima the first in row-major order is the arg-max (torch's max_pool2d rule on the CPU); the gradient routes
+ * through both arg-max maps and is exactly 0 at void pixels, whose logits never reach the result.  An empty target, a full
+ * target or constant logits give loss exactly 1 and gradient 0; a NaN logit at a valid pixel makes the loss NaN.
+ * EOSVOS_LOSS_BCE_AND_BOUNDARY_F, `cross_entropy_and_boundary_f`: EOSVOS_LOSS_BCE over the same valid pixels plus the above,
+ * a plain 1:1 sum (this project's own combination).
+ * The radius r is per engine (eosvos_set_loss_boundary), in [1, 16]; by default min(16, ceil(0.008 * the frame diagonal)), the
+ * DAVIS boundary tolerance: 8 at 480 x 854.  It is untuned: no J&F figure exists for it.  Both kinds need the frame's shape:
+ * through eosvos_loss* and the fused entry points an image is the engine's H x W; eosvos_loss_tensors* accept n == H * W only,
+ * as one image.  No atomics and fixed-order sums: loss and gradient are bit-identical from run to run.  The first use allocates
+ * a scratch of 34 bytes per pixel of the engine's largest batch once; a failed allocation is reported and leaves the engine
+ * usable with the other kinds.
+ * Kind 7 is deliberately left unassigned: the tests of the earlier kinds use it as their unknown loss kind, so it stays an
+ * error. */
+#define EOSVOS_LOSS_BOUNDARY_F 8
+#define EOSVOS_LOSS_BCE_AND_BOUNDARY_F 9
+/* The radius of the two boundary kinds for every evaluation on this engine: 1 .. 16, or 0 for the frame-size default; anything
+ * else is an error and changes nothing.  Per engine, like the bootstrap fraction. */
+int eosvos_set_loss_boundary(eosvos_engine* e, int radius);
+/* The boundary kinds on caller tensors with an explicit shape: `batch` images of height x width (batch <= the engine's largest
+ * batch, batch * height * width <= its pixels), DEVICE pointers.  radius 1 .. 16, or 0 for this shape's default; `combined`
+ * selects EOSVOS_LOSS_BCE_AND_BOUNDARY_F; `ignore_on` the void label `ignore`.  The loss goes to loss_out, the gradient to
+ * dlogits_out or, when that is null, to the engine's own gradient scratch (a pending eosvos_loss* gradient is then lost). */
+int eosvos_boundary_f(eosvos_engine* e, const float* logits, const float* masks, int batch, int height, int width, int radius,
+                      int combined, int ignore_on, float ignore, float* loss_out, float* dlogits_out);
 int eosvos_loss(eosvos_engine* e, int kind, const float* masks, int batch, float* loss_out);
 /* The value of the last loss evaluated by eosvos_loss* / eosvos_finetune_step / eosvos_meta_grad*, copied to a DEVICE
  * float on the engine's stream without synchronising (several engines in flight on one GPU: concurrent meta tasks). */
