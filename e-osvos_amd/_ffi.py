@@ -67,6 +67,13 @@ _SIGNATURES = {
     'eosvos_loss_tensors_ignore': (ctypes.c_int, [_E, ctypes.c_int, c_float_p, c_float_p, ctypes.c_int64, ctypes.c_float,
                                                   c_float_p]),
     'eosvos_set_loss_ignore': (ctypes.c_int, [_E, ctypes.c_int, ctypes.c_float]),
+    'eosvos_set_loss_sum': (ctypes.c_int, [_E, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float)]),
+    'eosvos_loss_sum': (ctypes.c_int, [_E, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float), c_float_p,
+                                       ctypes.c_int, ctypes.c_int, ctypes.c_float, c_float_p]),
+    'eosvos_loss_sum_tensors': (ctypes.c_int, [_E, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float),
+                                               c_float_p, c_float_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, c_float_p,
+                                               c_float_p]),
+    'eosvos_last_loss_terms': (ctypes.c_int, [_E, c_float_p, ctypes.POINTER(ctypes.c_int)]),
     'eosvos_set_loss_bootstrap': (ctypes.c_int, [_E, ctypes.c_float]),
     'eosvos_set_loss_boundary': (ctypes.c_int, [_E, ctypes.c_int]),
     'eosvos_boundary_f': (ctypes.c_int, [_E, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,

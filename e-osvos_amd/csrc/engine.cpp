@@ -206,6 +206,14 @@ struct eosvos_engine {
   int bootstrap_q = 16384;              // eosvos_set_loss_bootstrap: round(fraction * 65536), default 0.25
   float* boundary_scratch = nullptr;    // per-pixel maps and partials of the boundary-F kinds, allocated like lovasz_scratch
   int boundary_radius = 0;              // eosvos_set_loss_boundary: 1 .. 16, 0 = the frame-size default
+  // weighted sums of kinds (eosvos_set_loss_sum / eosvos_loss_sum*): a gradient slice of maxB * H * W floats per term, allocated
+  // when a sum first needs that many terms; sum_vals: the terms' values as evaluated [0, 4) and of the last whole sum [4, 8)
+  float* sum_slice[EOSVOS_LOSS_MAX_TERMS] = {nullptr, nullptr, nullptr, nullptr};
+  float* sum_vals = nullptr;
+  int sum_last_terms = 0;               // number of terms of the last evaluated sum, 0 = none yet
+  int sum_n = 0;                        // eosvos_set_loss_sum: the fused entry points evaluate this sum; 0 = the single loss_kind
+  int sum_kinds[EOSVOS_LOSS_MAX_TERMS] = {0, 0, 0, 0};
+  float sum_weights[EOSVOS_LOSS_MAX_TERMS] = {0.f, 0.f, 0.f, 0.f};
   int* aug_tab = nullptr;               // eosvos_warp_affine: adelta[W] bdelta[W] X0[H] Y0[H], then the nonzero counter
   float* aug_ctab = nullptr;            // bicubic coefficients at 1/32 pixel: [32][4]
   // the call scratch of every evaluation-stage entry point (scratch_for, scratch_layout.h; grow-only, freed by destroy).  One
@@ -2418,9 +2426,79 @@ int loss_on_tensors(eosvos_engine* e, int kind, const float* logits, const float
   }
   return loss_eval(e, kind, logits, masks, n, 1, 1, ignore, dlogits_out ? dlogits_out : e->dlogits, loss_out);
 }
+// ---- weighted sums of kinds (include/eosvos.h at eosvos_set_loss_sum) ----
+// the checks every sum entry point shares; 0 when the term list is a sum
+int sum_terms_ok(int n_terms, const int* kinds, const float* weights) {
+  if (n_terms < 1 || n_terms > EOSVOS_LOSS_MAX_TERMS) return fail("a loss sum has 1 .. 4 terms");
+  if (!kinds || !weights) return fail("null argument");
+  int boundary = 0;
+  for (int i = 0; i < n_terms; ++i) {
+    if (!loss_kind_ok(kinds[i])) return fail("unknown loss kind");
+    if (!(std::isfinite(weights[i]) && weights[i] > 0.f)) return fail("the weights of a loss sum must be finite and > 0");
+    for (int j = 0; j < i; ++j)
+      if (kinds[j] == kinds[i]) return fail("a loss sum names a kind twice");
+    boundary += boundary_kind(kinds[i]) ? 1 : 0;
+  }
+  if (boundary > 1) return fail("a loss sum takes one boundary kind: the two share the engine's radius");
+  return 0;
+}
+// every term's own scratch, the value slots and one gradient slice per term; 0 on success
+int sum_ensure(eosvos_engine* e, int n_terms, const int* kinds) {
+  for (int i = 0; i < n_terms; ++i) {
+    if (lovasz_kind(kinds[i]) && lovasz_ensure(e)) return 1;
+    if (kinds[i] == EOSVOS_LOSS_BOOTSTRAPPED_BCE && bootstrap_ensure(e)) return 1;
+    if (boundary_kind(kinds[i]) && boundary_ensure(e)) return 1;
+  }
+  if (!e->sum_vals) {
+    e->sum_vals = e->falloc(2 * EOSVOS_LOSS_MAX_TERMS);
+    if (e->sum_vals && hipMemsetAsync(e->sum_vals, 0, sizeof(float) * 2 * EOSVOS_LOSS_MAX_TERMS, e->s) != hipSuccess) e->sum_vals = nullptr;
+  }
+  for (int i = 0; e->sum_vals && i < n_terms; ++i) {
+    if (!e->sum_slice[i]) e->sum_slice[i] = e->falloc((int64_t)e->maxB * e->H * e->W);
+    if (!e->sum_slice[i]) break;
+  }
+  if (!e->sum_vals || !e->sum_slice[n_terms - 1]) {
+    (void)hipGetLastError();              // as lovasz_ensure
+    return fail("loss sum: out of device memory for the terms' gradients");
+  }
+  return 0;
+}
+// The sum (checked by sum_terms_ok) of `images` maps of n_per_image pixels: each term by loss_eval's own launches into its
+// slice and value slot, then one launch that combines them into dlogits / loss.  `one_set`: caller tensors, every kind takes
+// the elements as one set (loss_on_tensors' rule); otherwise only the flat Lovasz kind does.
+int loss_sum_eval(eosvos_engine* e, int n_terms, const int* kinds, const float* weights, const float* logits, const float* masks,
+                  int64_t n_per_image, int images, bool one_set, const float* ignore, float* dlogits, float* loss) {
+  const int64_t n = n_per_image * images;
+  if (n > (int64_t)e->maxB * e->H * e->W) return fail("n exceeds the engine's scratch");
+  if (sum_ensure(e, n_terms, kinds)) return 1;
+  for (int i = 0; i < n_terms; ++i)
+    if (loss_eval(e, kinds[i], logits, masks, n_per_image, images, one_set || kinds[i] == EOSVOS_LOSS_LOVASZ_HINGE_FLAT, ignore,
+                  e->sum_slice[i], e->sum_vals + i))
+      return 1;
+  launch_loss_sum(n_terms, e->sum_slice, weights, e->sum_vals, dlogits, loss, e->sum_vals + EOSVOS_LOSS_MAX_TERMS, n, e->s);
+  HIPOK(hipGetLastError());
+  e->sum_last_terms = n_terms;
+  return 0;
+}
+// the sum on the logits of the last forward: leaves dL/dlogits for eosvos_backward_step
+int loss_sum_on_forward(eosvos_engine* e, int n_terms, const int* kinds, const float* weights, const float* masks, int batch,
+                        const float* ignore, float* loss_out) {
+  if (!e || !masks) return fail("null argument");
+  if (sum_terms_ok(n_terms, kinds, weights)) return 1;
+  if (ignore && !ignore_ok(*ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  if (batch != e->lastB) return fail("loss batch differs from the last forward");
+  e->have_loss_grad = false;
+  if (loss_sum_eval(e, n_terms, kinds, weights, e->logits, masks, (int64_t)e->H * e->W, batch, false, ignore, e->dlogits, e->loss_dev))
+    return 1;
+  e->have_loss_grad = true;
+  if (loss_out) HIPOK(hipMemcpyAsync(loss_out, e->loss_dev, 4, hipMemcpyDeviceToDevice, e->s));
+  return 0;
+}
 // the loss of the fused entry points
 inline int fused_loss(eosvos_engine* e, const float* masks, int batch) {
-  return loss_on_forward(e, e->loss_kind, masks, batch, e->loss_ignore_on ? &e->loss_ignore : nullptr, nullptr);
+  const float* ignore = e->loss_ignore_on ? &e->loss_ignore : nullptr;
+  if (e->sum_n) return loss_sum_on_forward(e, e->sum_n, e->sum_kinds, e->sum_weights, masks, batch, ignore, nullptr);
+  return loss_on_forward(e, e->loss_kind, masks, batch, ignore, nullptr);
 }
 }  // namespace
 
@@ -2455,6 +2533,37 @@ int eosvos_set_loss(eosvos_engine* e, int kind) {
   if (kind == EOSVOS_LOSS_BOOTSTRAPPED_BCE && bootstrap_ensure(e)) return 1;
   if (boundary_kind(kind) && boundary_ensure(e)) return 1;
   e->loss_kind = kind;
+  e->sum_n = 0;
+  return 0;
+}
+int eosvos_set_loss_sum(eosvos_engine* e, int n_terms, const int* kinds, const float* weights) {
+  if (!e) return fail("null engine");
+  if (sum_terms_ok(n_terms, kinds, weights)) return 1;
+  if (sum_ensure(e, n_terms, kinds)) return 1;
+  for (int i = 0; i < n_terms; ++i) { e->sum_kinds[i] = kinds[i]; e->sum_weights[i] = weights[i]; }
+  e->sum_n = n_terms;
+  return 0;
+}
+int eosvos_loss_sum(eosvos_engine* e, int n_terms, const int* kinds, const float* weights, const float* masks, int batch,
+                    int ignore_on, float ignore, float* loss_out) {
+  ModeScope mode_scope(e);
+  return loss_sum_on_forward(e, n_terms, kinds, weights, masks, batch, ignore_on ? &ignore : nullptr, loss_out);
+}
+int eosvos_loss_sum_tensors(eosvos_engine* e, int n_terms, const int* kinds, const float* weights, const float* logits,
+                            const float* masks, int64_t n, int ignore_on, float ignore, float* loss_out, float* dlogits_out) {
+  ModeScope mode_scope(e);
+  if (!e || !logits || !masks || !loss_out || n < 1) return fail("bad argument");
+  if (sum_terms_ok(n_terms, kinds, weights)) return 1;
+  if (ignore_on && !ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  if (!dlogits_out) e->have_loss_grad = false;
+  return loss_sum_eval(e, n_terms, kinds, weights, logits, masks, n, 1, true, ignore_on ? &ignore : nullptr,
+                       dlogits_out ? dlogits_out : e->dlogits, loss_out);
+}
+int eosvos_last_loss_terms(eosvos_engine* e, float* out, int* n_terms_host) {
+  if (!e || !out) return fail("null argument");
+  if (!e->sum_last_terms) return fail("eosvos_last_loss_terms: no loss sum has been evaluated on this engine");
+  HIPOK(hipMemcpyAsync(out, e->sum_vals + EOSVOS_LOSS_MAX_TERMS, sizeof(float) * EOSVOS_LOSS_MAX_TERMS, hipMemcpyDeviceToDevice, e->s));
+  if (n_terms_host) *n_terms_host = e->sum_last_terms;
   return 0;
 }
 int eosvos_set_loss_bootstrap(eosvos_engine* e, float fraction) {

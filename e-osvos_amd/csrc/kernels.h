@@ -474,6 +474,12 @@ constexpr int BOUNDARY_BLOCKS = 1024;            // cap of the grid per image (2
 int64_t boundary_scratch_floats(int64_t n_total, int max_images);
 void launch_boundary_f(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int H, int W, int images,
                        int radius, int add, const float* ignore, hipStream_t s);
+// Weighted sum of n_terms (1 .. EOSVOS_LOSS_MAX_TERMS) evaluated losses (misc_kernels.hip; the rule: include/eosvos.h at
+// eosvos_set_loss_sum): out[i] = w0 * g0[i] (+ w1 * g1[i] ...) over n elements, *loss the same expression of vals[0 .. n_terms),
+// which are copied unweighted to terms[0 .. n_terms).  grads / weights: host arrays; vals, out, loss, terms: device.  Every
+// product and sum is rounded on its own (no fused multiply-add); one launch, no atomics; `out` may be unaligned.
+void launch_loss_sum(int n_terms, const float* const* grads, const float* weights, const float* vals, float* out, float* loss,
+                     float* terms, int64_t n, hipStream_t s);
 // targets = 1 where probs >= hi, 0 where probs < lo, `ignore` between, for n_frames maps of n_pix; n_pos[frame] (zeroed by the
 // caller) += the frame's number of 1s
 void launch_propagation_targets(const float* probs, float* targets, int* n_pos, int n_frames, int64_t n_pix, float lo, float hi,

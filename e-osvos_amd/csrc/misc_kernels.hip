@@ -1679,6 +1679,78 @@ void launch_loss(int kind, const float* logits, const float* gt, float* dlogits,
   else loss_launches<false>(kind, logits, gt, dlogits, loss, partial, (long)n, 0.f, s);
 }
 
+// ---- weighted sums of the device losses (launch_loss_sum; the rule: include/eosvos.h at eosvos_set_loss_sum) ----------
+// acc = w0 * x0, then acc = acc + wi * xi in spelled order, every product and every sum rounded on its own.  hipcc contracts
+// a + w * b into one fused multiply-add by default, and the __fmul_rn / __fadd_rn family does not stop it (inline functions
+// of a header compiled under that default, fused after inlining: the assembly showed v_fmac / v_pk_fma), so the expressions
+// are plain operators under the pragma, as in lucid_kernels.hip.
+template <int NT>
+struct LossSumTerms { const float* d[NT]; float w[NT]; };
+template <int NT>
+__device__ __forceinline__ float loss_sum_of(const float (&x)[NT], const float (&w)[NT]) {
+#pragma clang fp contract(off)
+  float acc = w[0] * x[0];
+#pragma unroll
+  for (int t = 1; t < NT; ++t) {
+    const float p = w[t] * x[t];
+    acc = acc + p;
+  }
+  return acc;
+}
+// One streaming pass over the NT gradient slices: 16-byte loads and stores while `vec` (every pointer 16-byte aligned), the
+// n mod 4 tail -- or, with an unaligned caller pointer, everything -- by single elements.  The first workgroup forms the
+// loss value from the NT term values and copies those, unweighted, to `terms`.
+template <int NT>
+__global__ __launch_bounds__(256) void loss_sum_kernel(const LossSumTerms<NT> a, const float* __restrict__ vals,
+                                                        float* __restrict__ out, float* __restrict__ loss,
+                                                        float* __restrict__ terms, long n, int vec) {
+  const long n4 = vec ? n >> 2 : 0;
+  GRID_STRIDE(i, n4) {
+    float4 v[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) v[t] = reinterpret_cast<const float4*>(a.d[t])[i];
+    float x[NT], y[NT], z[NT], w[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) { x[t] = v[t].x; y[t] = v[t].y; z[t] = v[t].z; w[t] = v[t].w; }
+    reinterpret_cast<float4*>(out)[i] =
+        make_float4(loss_sum_of<NT>(x, a.w), loss_sum_of<NT>(y, a.w), loss_sum_of<NT>(z, a.w), loss_sum_of<NT>(w, a.w));
+  }
+  for (long i = 4 * n4 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    float x[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) x[t] = a.d[t][i];
+    out[i] = loss_sum_of<NT>(x, a.w);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    float x[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) terms[t] = x[t] = vals[t];
+    *loss = loss_sum_of<NT>(x, a.w);
+  }
+}
+template <int NT>
+static void loss_sum_launch(const float* const* grads, const float* weights, const float* vals, float* out, float* loss,
+                            float* terms, long n, hipStream_t s) {
+  LossSumTerms<NT> a;
+  bool vec = ((uintptr_t)out & 15) == 0;
+  for (int t = 0; t < NT; ++t) {
+    a.d[t] = grads[t];
+    a.w[t] = weights[t];
+    vec = vec && ((uintptr_t)grads[t] & 15) == 0;
+  }
+  hipLaunchKernelGGL((loss_sum_kernel<NT>), dim3(grid_for(vec ? (n + 3) / 4 : n, 256, 2048)), dim3(256), 0, s, a, vals, out,
+                     loss, terms, n, vec ? 1 : 0);
+}
+void launch_loss_sum(int n_terms, const float* const* grads, const float* weights, const float* vals, float* out, float* loss,
+                     float* terms, int64_t n, hipStream_t s) {
+  switch (n_terms) {
+    case 1: loss_sum_launch<1>(grads, weights, vals, out, loss, terms, (long)n, s); break;
+    case 2: loss_sum_launch<2>(grads, weights, vals, out, loss, terms, (long)n, s); break;
+    case 3: loss_sum_launch<3>(grads, weights, vals, out, loss, terms, (long)n, s); break;
+    default: loss_sum_launch<4>(grads, weights, vals, out, loss, terms, (long)n, s); break;
+  }
+}
+
 // ---- pseudo-label targets of online adaptation with an uncertainty band -----------------------------------------------
 // targets = 1 where p >= hi, 0 where p < lo, `ign` between (a NaN probability is void); n_pos[frame] += the frame's count
 // of 1s: summed over the wave, one integer atomic per wave (integer adds commute: the counts do not depend on arrival order)

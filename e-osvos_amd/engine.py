@@ -5,10 +5,11 @@ torch-ROCm is used for device memory and streams only; every arithmetic call goe
 the C-ABI of include/eosvos.h.
 """
 import ctypes
+import functools
 
 import torch
 
-from . import _ffi, bootstrap, boundary
+from . import _ffi, bootstrap, boundary, loss_sum
 from .topology import ARCH_ID, norm_layers, trainable
 
 
@@ -102,6 +103,16 @@ def resolve_radius(name, radius=None):
             raise ValueError(f"loss_func='{name}' and radius={radius!r} disagree")
         r = radius
     return r
+
+
+@functools.lru_cache(maxsize=64, typed=True)
+def _resolve_sum(name, fraction, radius):
+    """`loss_sum.resolve` as the ctypes arrays of the eosvos_*loss_sum* calls, kept per spelling: (kinds, weights, fraction
+    or None, radius or None).  Splitting and checking a spelling takes ~10 us on the host, which a loss whose launches take
+    30 us would otherwise pay on every evaluation (`profiles/loss_sum_time.txt`); a spelling that raises is not kept."""
+    kinds, weights, _, f, r = loss_sum.resolve(name, fraction, radius)
+    n = len(kinds)
+    return (ctypes.c_int * n)(*kinds), (ctypes.c_float * n)(*weights), f, r
 
 
 def check_ignore(ignore):
@@ -243,7 +254,13 @@ class Engine:
     def set_loss(self, name, ignore=None, fraction=None, radius=None):
         """Loss of finetune_step / meta_grad (`loss_func`, helper_func.py:28-56) and its void label (None: every pixel counts).
         `bootstrapped_cross_entropy_<P>` or `fraction=` also set the engine's bootstrap fraction, `boundary_f_<r>` /
-        `cross_entropy_and_boundary_f_<r>` or `radius=` its boundary radius (see `_loss_kind`)."""
+        `cross_entropy_and_boundary_f_<r>` or `radius=` its boundary radius (see `_loss_kind`).  A sum spelling
+        (`0.5*lovasz_hinge+boundary_f_4`, `loss_sum.py`) selects `eosvos_set_loss_sum`; a single name returns to one kind."""
+        if loss_sum.is_sum(name):
+            v = None if ignore is None else check_ignore(ignore)
+            _ffi.check(self.lib.eosvos_set_loss_sum(self.h, *self._loss_sum_args(name, fraction, radius)))
+            _ffi.check(self.lib.eosvos_set_loss_ignore(self.h, int(v is not None), v or 0.0))
+            return
         if bootstrap.parse(name)[0] not in LOSS_KINDS and boundary.parse(name)[0] not in boundary.KINDS:
             raise NotImplementedError(name)             # helper_func.py:55-56
         v = None if ignore is None else check_ignore(ignore)
@@ -272,6 +289,16 @@ class Engine:
         if r is not None:
             self.set_loss_boundary(r)
         return kind
+
+    def _loss_sum_args(self, name, fraction=None, radius=None):
+        """(n_terms, kinds, weights) of a sum spelling for the eosvos_*loss_sum* calls (`loss_sum.resolve`); a fraction or
+        radius carried by a term or a keyword becomes the engine's before the call that follows, as in `_loss_kind`."""
+        kinds, weights, f, r = _resolve_sum(name, fraction, radius)
+        if f is not None:
+            self.set_loss_bootstrap(f)
+        if r is not None:
+            self.set_loss_boundary(r)
+        return len(kinds), kinds, weights
 
     def set_norm(self, gamma, beta, mean, var, eps=1e-5):
         ts = [_dev_f32(t, self.device) for t in (gamma, beta, mean, var)]
@@ -412,7 +439,11 @@ class Engine:
         return self._verify_step(images, masks, loss_kind)
 
     def _loss_call(self, kind, masks, ignore, out):
-        """eosvos_loss, or eosvos_loss_ignore with a void label, on the last forward."""
+        """eosvos_loss, or eosvos_loss_ignore with a void label, on the last forward; eosvos_loss_sum for a sum spelling."""
+        if loss_sum.is_sum(kind):
+            _ffi.check(self.lib.eosvos_loss_sum(self.h, *self._loss_sum_args(kind), _ptr(masks), masks.shape[0],
+                                                int(ignore is not None), ignore or 0.0, _optr(out)))
+            return
         kid = self._loss_kind(kind)
         if ignore is None:
             _ffi.check(self.lib.eosvos_loss(self.h, kid, _ptr(masks), masks.shape[0], _optr(out)))
@@ -502,8 +533,12 @@ class Engine:
     def loss(self, kind, masks, ignore=None, fraction=None, radius=None):
         """kind: a compute_loss name (helper_func.py:28-56, see LOSS_KINDS); leaves dL/dlogits.  `ignore`: the void label --
         pixels whose mask equals it are in no sum, count or ranking and get gradient 0 (`eosvos_loss_ignore`).  `fraction`:
-        of `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, as in `set_loss`."""
-        self._loss_kind(kind, fraction, radius)
+        of `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, as in `set_loss`.  A sum spelling evaluates the
+        weighted sum of its terms (`eosvos_loss_sum`); `last_loss_terms` then gives the terms' own values."""
+        if loss_sum.is_sum(kind):
+            self._loss_sum_args(kind, fraction, radius)
+        else:
+            self._loss_kind(kind, fraction, radius)
         ignore = None if ignore is None else check_ignore(ignore)
         assert masks.is_cuda and masks.dtype == torch.float32 and masks.is_contiguous()
         out = torch.empty(1, device=self.device)
@@ -520,6 +555,11 @@ class Engine:
         logits, masks = logits.contiguous(), masks.contiguous()
         assert logits.is_cuda and masks.is_cuda and logits.numel() == masks.numel()
         out = torch.empty(1, device=self.device)
+        if loss_sum.is_sum(kind):                       # the n elements one set for every term; no gradient is kept
+            v = None if ignore is None else check_ignore(ignore)
+            _ffi.check(self.lib.eosvos_loss_sum_tensors(self.h, *self._loss_sum_args(kind, fraction, radius), _ptr(logits), _ptr(masks),
+                                                        logits.numel(), int(v is not None), v or 0.0, _ptr(out), None))
+            return out
         kid = self._loss_kind(kind, fraction, radius)
         if ignore is None:
             _ffi.check(self.lib.eosvos_loss_tensors(self.h, kid, _ptr(logits), _ptr(masks), logits.numel(), _ptr(out)))
@@ -527,6 +567,28 @@ class Engine:
             _ffi.check(self.lib.eosvos_loss_tensors_ignore(self.h, kid, _ptr(logits), _ptr(masks), logits.numel(),
                                                            check_ignore(ignore), _ptr(out)))
         return out
+
+    def loss_grad_of(self, name, logits, masks, ignore=None, fraction=None, radius=None):
+        """(loss, dL/dlogits of the logits' shape) of a single kind or a sum on arbitrary device tensors, the elements one set
+        as in `loss_of` (`eosvos_loss_sum_tensors`; a single kind is the sum of one term of weight 1, which has that kind's
+        bits).  At most the engine's largest batch of pixels; the engine's own gradient is untouched."""
+        logits, masks = logits.contiguous(), masks.contiguous()
+        assert logits.is_cuda and masks.is_cuda and logits.dtype == masks.dtype == torch.float32
+        assert logits.numel() == masks.numel()
+        v = None if ignore is None else check_ignore(ignore)
+        out, grad = torch.empty(1, device=self.device), torch.empty_like(logits)
+        _ffi.check(self.lib.eosvos_loss_sum_tensors(self.h, *self._loss_sum_args(name, fraction, radius), _ptr(logits), _ptr(masks),
+                                                    logits.numel(), int(v is not None), v or 0.0, _ptr(out), _ptr(grad)))
+        return out, grad
+
+    def last_loss_terms(self):
+        """The unweighted values of the terms of the last sum evaluated on this engine, in spelled order
+        (`eosvos_last_loss_terms`): by `loss` / `loss_of` / `loss_grad_of`, or by `finetune_step` / `meta_grad` under a sum."""
+        out, n = torch.empty(loss_sum.MAX_TERMS, device=self.device), ctypes.c_int(0)
+        _ffi.check(self.lib.eosvos_last_loss_terms(self.h, _ptr(out), ctypes.byref(n)))
+        if torch.cuda.current_stream(self.device) != self.stream:
+            self.synchronize()
+        return out[:n.value].tolist()
 
     def boundary_f(self, logits, masks, radius=None, ignore=None, combined=False):
         """`boundary_f` (or with `combined` `cross_entropy_and_boundary_f`) of device tensors (B, H, W) or (H, W) of any frame

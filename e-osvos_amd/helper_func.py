@@ -18,13 +18,14 @@ pixels: the engine's fraction (0.25 by default), `bootstrapped_cross_entropy_<P>
 `boundary_f` / `cross_entropy_and_boundary_f` (`boundary.py`; not in the reference) are the soft boundary-F loss and its sum
 with `cross_entropy`: the engine's window radius (by default the DAVIS tolerance of the frame size), `boundary_f_<r>` for
 r pixels, or `loss_kwargs={'radius': r}`.
+A `loss_func` with a '+' or a '*' is a weighted sum of up to four of these (`loss_sum.py`), e.g. `0.5*lovasz_hinge+boundary_f_4`.
 """
 import random
 
 import numpy as np
 import torch
 
-from . import bootstrap, boundary
+from . import bootstrap, boundary, loss_sum
 from . import tta as tta_views
 from . import zoom as zoom_pass
 from .engine import resolve_loss
@@ -35,6 +36,8 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
     """`compute_loss(loss_func, outputs, gts, loss_kwargs=None)`, helper_func.py:28-56.  The returned
     0-dim loss carries the engine handle so `MetaOptimizer.step(loss)` can run the backward."""
     loss_kwargs = loss_kwargs or {}
+    if loss_sum.is_sum(loss_func):
+        return _compute_loss_sum(loss_func, outputs, gts, loss_kwargs)
     base, _ = bootstrap.parse(loss_func)                   # (a bad spelling under the bootstrap prefix: NotImplementedError)
     if base not in ('cross_entropy', 'dice', 'cross_entropy_and_dice', 'class_balanced_cross_entropy',
                     'lovasz_hinge', 'lovasz_hinge_flat', bootstrap.NAME) and boundary.parse(loss_func)[0] not in boundary.KINDS:
@@ -62,6 +65,27 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
         return loss
     # per-sample values (run_loader metrics, helper_func.py:131-137): every loss evaluated sample by sample
     return torch.cat([eng.loss_of(loss_func, outputs[b], gts[b], **ign, **frac) for b in range(outputs.shape[0])])
+
+
+def _compute_loss_sum(loss_func, outputs, gts, loss_kwargs):
+    """`compute_loss` for a sum spelling (`loss_sum.py`): the keywords go to the one term of their family."""
+    per_image = loss_kwargs.get('per_image', True)
+    names = loss_sum.resolve(loss_func, loss_kwargs.get('fraction'), loss_kwargs.get('radius'), per_image)[2]
+    if 'class_balanced_cross_entropy' in names and not loss_kwargs.get('size_average', True):
+        raise NotImplementedError('class_balanced_cross_entropy with size_average=False')
+    if not per_image:
+        loss_func = loss_sum.flat_spelling(loss_func)      # loss_lovasz.py:89-90: the whole batch as one set
+    eng = getattr(outputs, '_eosvos_engine', None)
+    if eng is None:
+        raise RuntimeError('compute_loss needs logits produced by eosvos_amd.networks.DeepLabV3Plus '
+                           '(there is no CPU/eager path)')
+    gts = gts.contiguous().float()
+    kw = {k: loss_kwargs[k] for k in ('ignore', 'fraction', 'radius') if loss_kwargs.get(k) is not None}
+    if loss_kwargs.get('batch_average', True):
+        loss = eng.loss(loss_func, gts, **kw).view(())      # also leaves dL/dlogits in the engine
+        loss._eosvos_engine = eng
+        return loss
+    return torch.cat([eng.loss_of(loss_func, outputs[b], gts[b], **kw) for b in range(outputs.shape[0])])
 
 
 def init_parent_model(architecture, encoder, train_encoder, decoder_norm_layer=None,

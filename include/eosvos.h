@@ -293,6 +293,40 @@ int eosvos_loss_tensors_ignore(eosvos_engine* e, int kind, const float* logits, 
  * `ignore` (networks/loss_lovasz.py:78-126) while `on` != 0.  Per engine, off by default; an engine that shares another's state
  * (eosvos_alias_state) does not take its setting over. */
 int eosvos_set_loss_ignore(eosvos_engine* e, int on, float ignore);
+/* ---- weighted sums of the kinds above (`0.5*lovasz_hinge+boundary_f`) ---------------------------------------------------
+ * A sum is a list of 1 .. EOSVOS_LOSS_MAX_TERMS kinds with weights; it needs no kind id of its own.  With terms
+ * i = 0 .. n-1 in the order given, L_i / d_i the loss and the gradient kind i produces alone (its own rule for what a set is,
+ * its own void-pixel handling, its own limits) and w_i its weight:
+ *   acc = w_0 (x) x_0;   acc = acc (+) (w_i (x) x_i)   for i = 1 .. n-1        x = the loss value, and per element the gradient
+ * where every (x) and every (+) is an fp32 operation rounded on its own -- never a fused multiply-add -- so that float32
+ * arithmetic on the host reproduces loss and gradient bit for bit (`loss_sum.combine_host`).  A void pixel keeps gradient +0:
+ * (w (x) +0) (+) +0 = +0; a NaN loss in any term makes the sum NaN.
+ * Checks, before any launch: 1 <= n_terms <= 4, every kind valid, no kind twice, not both boundary kinds (they share the
+ * engine's radius), every weight finite and > 0.  The terms are evaluated by their own launches, unchanged, into a gradient
+ * slice of the largest batch's H * W floats each, then one streaming launch combines them (16-byte accesses, no atomics; bit-
+ * identical from run to run like its terms).  The slices and every term's own scratch are allocated when a sum is set or first
+ * used; a failed allocation is reported and leaves the engine usable with single kinds.  A term fails as it fails alone, and a
+ * failed term fails the sum.  The existing 1:1 kinds EOSVOS_LOSS_BCE_DICE and EOSVOS_LOSS_BCE_AND_BOUNDARY_F keep their own
+ * kernels and bits; they may be terms.  The weights are untuned: no J&F figure exists for any sum. */
+#define EOSVOS_LOSS_MAX_TERMS 4
+/* The sum becomes the loss of eosvos_finetune_step / eosvos_meta_grad[_ex]; eosvos_set_loss returns the engine to a single
+ * kind, eosvos_set_loss_ignore applies to both.  Per engine, like eosvos_set_loss. */
+int eosvos_set_loss_sum(eosvos_engine* e, int n_terms, const int* kinds, const float* weights);
+/* The sum on the logits of the last forward (eosvos_loss's rules: the Lovasz hinge and the bootstrapped BCE per image, the
+ * boundary kinds per frame); `ignore_on` selects the void label `ignore`.  Leaves dL/dlogits for eosvos_backward_step. */
+int eosvos_loss_sum(eosvos_engine* e, int n_terms, const int* kinds, const float* weights, const float* masks, int batch,
+                    int ignore_on, float ignore, float* loss_out);
+/* The sum on n elements of caller tensors (DEVICE pointers), the n elements one set for every term as in eosvos_loss_tensors;
+ * n may not exceed the largest batch's pixels, and a boundary term accepts n == H * W only.  The gradient goes to dlogits_out
+ * (any 4-byte alignment) or, when that is NULL, to the engine's own scratch (a pending loss gradient is then invalidated).
+ * With one term of weight 1 this is that kind's value and gradient, bit for bit. */
+int eosvos_loss_sum_tensors(eosvos_engine* e, int n_terms, const int* kinds, const float* weights, const float* logits,
+                            const float* masks, int64_t n, int ignore_on, float ignore, float* loss_out, float* dlogits_out);
+/* The unweighted term values L_i of the last sum evaluated on this engine (eosvos_loss_sum*, or a fused entry point under
+ * eosvos_set_loss_sum), copied to EOSVOS_LOSS_MAX_TERMS DEVICE floats on the engine's stream without synchronising; the
+ * entries past that sum's n_terms, which goes to the HOST int n_terms_host (may be NULL), are unspecified.  An error before the
+ * first sum. */
+int eosvos_last_loss_terms(eosvos_engine* e, float* out, int* n_terms_host);
 /* Pseudo-label targets of online adaptation with an uncertainty band (the thresholding of evaluate.py:231-240, whose void
  * label the losses above skip, networks/loss_lovasz.py:78-126): for n_frames probability maps of n_pix pixels,
  * targets_out = 1 where p >= hi, 0 where p < lo, `ignore` between (0 <= lo < hi <= 1, n_frames <= 1024).  n_pos_host (may be
