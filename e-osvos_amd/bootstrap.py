@@ -8,40 +8,11 @@ Per set (one image on the forward path, all n elements through `loss_of`), V the
   w_p = 1 above tau, fp32 r / T at tau, 0 below and at void pixels;
   set loss = sum_V w_p bce_p / k;  loss = mean over the sets;  dL/dz_p = w_p (sigmoid(z_p) - y_p) / (k * sets).
 The OnAVOS fraction 0.25 is the default; it is untuned here (no J&F figure exists for it)."""
-import math
-
 import numpy as np
 
-NAME = 'bootstrapped_cross_entropy'
+from .loss_names import BOOTSTRAP as NAME, check_fraction, parse_bootstrap as parse, q_of  # noqa: F401  (the spelling's home)
+
 DEFAULT_FRACTION = 0.25
-
-
-def parse(name):
-    """`bootstrapped_cross_entropy` -> (NAME, None): the engine's fraction; `bootstrapped_cross_entropy_<P>`, P an integer
-    percent 1 .. 100 without a leading zero -> (NAME, P / 100).  A name that does not start with NAME is returned as
-    (name, None); anything else under the prefix raises NotImplementedError like an unknown loss name."""
-    if not isinstance(name, str) or not name.startswith(NAME):
-        return name, None
-    rest = name[len(NAME):]
-    if rest == '':
-        return NAME, None
-    digits = rest[1:]
-    if rest[0] != '_' or not digits.isascii() or not digits.isdigit() or digits[0] == '0' or not 1 <= int(digits) <= 100:
-        raise NotImplementedError(f"loss_func='{name}'")
-    return NAME, int(digits) / 100.0
-
-
-def check_fraction(fraction):
-    """The fraction as the float the library receives: in (0, 1]."""
-    f = float(np.float32(fraction))
-    if not (0.0 < f <= 1.0) or not (0.0 < float(fraction) <= 1.0):
-        raise ValueError(f'fraction={fraction!r}: the bootstrap fraction must be in (0, 1]')
-    return f
-
-
-def q_of(fraction):
-    """round(fraction * 65536) of the fp32 fraction (halves away from zero), clamped to [1, 65536]."""
-    return min(65536, max(1, int(math.floor(check_fraction(fraction) * 65536.0 + 0.5))))
 
 
 def k_of(n, fraction):

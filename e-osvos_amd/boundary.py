@@ -17,38 +17,10 @@ import math
 import torch
 import torch.nn.functional as F
 
-NAME = 'boundary_f'
-COMBINED = 'cross_entropy_and_boundary_f'
-KINDS = {NAME: 8, COMBINED: 9}          # the kinds that need the frame's shape (include/eosvos.h; 7 stays unassigned)
-MAX_RADIUS = 16
+from .loss_names import (BOUNDARY_COMBINED as COMBINED, BOUNDARY_F as NAME, BOUNDARY_KINDS as KINDS,  # noqa: F401
+                         MAX_RADIUS, check_radius, parse_boundary as parse)                          # (the spelling's home)
+
 EPS = 1e-7
-
-
-def parse(name):
-    """`boundary_f` / `cross_entropy_and_boundary_f` -> (name, None): the engine's radius; with `_<r>`, r an integer 1 .. 16
-    without a leading zero -> (base name, r).  A name under neither prefix is returned as (name, None); anything else under a
-    prefix raises NotImplementedError like an unknown loss name."""
-    if not isinstance(name, str):
-        return name, None
-    for base in (COMBINED, NAME):
-        if name.startswith(base):
-            rest = name[len(base):]
-            if rest == '':
-                return base, None
-            digits = rest[1:]
-            if (rest[0] != '_' or not digits.isascii() or not digits.isdigit() or digits[0] == '0'
-                    or not 1 <= int(digits) <= MAX_RADIUS):
-                raise NotImplementedError(f"loss_func='{name}'")
-            return base, int(digits)
-    return name, None
-
-
-def check_radius(radius):
-    """The radius as the int the library receives: a whole number 1 .. 16."""
-    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or radius != radius or radius != int(radius) \
-            or not 1 <= int(radius) <= MAX_RADIUS:
-        raise ValueError(f'radius={radius!r}: the boundary radius must be a whole number in 1 .. {MAX_RADIUS}')
-    return int(radius)
 
 
 def default_radius(height, width):

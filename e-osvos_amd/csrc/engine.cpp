@@ -180,6 +180,30 @@ HostResize make_resize(int in, int out, bool align_corners) {
   return r;
 }
 
+// One loss, as every loss entry point hands it down.  Without `combine` it is kinds[0] alone, whose own launches write the
+// gradient and the value where they are wanted.  With it, each of the n terms goes to its gradient slice and value slot and
+// one launch combines them by the weights (include/eosvos.h at eosvos_set_loss_sum), for one term too.
+struct LossSpec {
+  int n = 1;                            // as the caller gave it; loss_spec_ok checks it before anything reads kinds / weights
+  int kinds[EOSVOS_LOSS_MAX_TERMS] = {EOSVOS_LOSS_BCE, 0, 0, 0};
+  float weights[EOSVOS_LOSS_MAX_TERMS] = {1.f, 0.f, 0.f, 0.f};
+  bool combine = false;
+  bool null_terms = false;              // a sum whose caller passed no kinds or no weights
+  static LossSpec single(int kind) {
+    LossSpec s;
+    s.kinds[0] = kind;
+    return s;
+  }
+  static LossSpec sum(int n_terms, const int* kinds, const float* weights) {
+    LossSpec s;
+    s.n = n_terms;
+    s.combine = true;
+    s.null_terms = !kinds || !weights;
+    for (int i = 0; !s.null_terms && i < n_terms && i < EOSVOS_LOSS_MAX_TERMS; ++i) { s.kinds[i] = kinds[i]; s.weights[i] = weights[i]; }
+    return s;
+  }
+};
+
 }  // namespace
 
 struct eosvos_engine {
@@ -197,7 +221,7 @@ struct eosvos_engine {
   float *Wp = nullptr, *Winit = nullptr, *Wsnap = nullptr, *lr = nullptr, *na = nullptr, *nb = nullptr;
   float *gsum = nullptr, *gout = nullptr, *stage = nullptr;
   bool keep_grads = false;
-  int loss_kind = EOSVOS_LOSS_BCE;      // loss of the fused entry points (eosvos_set_loss)
+  LossSpec fused;                       // loss of the fused entry points (eosvos_set_loss / eosvos_set_loss_sum)
   bool loss_ignore_on = false;          // eosvos_set_loss_ignore: the fused entry points evaluate their loss with a void label
   float loss_ignore = 0.f;
   int* prop_count = nullptr;            // eosvos_propagation_targets: per-frame positive counts
@@ -211,9 +235,6 @@ struct eosvos_engine {
   float* sum_slice[EOSVOS_LOSS_MAX_TERMS] = {nullptr, nullptr, nullptr, nullptr};
   float* sum_vals = nullptr;
   int sum_last_terms = 0;               // number of terms of the last evaluated sum, 0 = none yet
-  int sum_n = 0;                        // eosvos_set_loss_sum: the fused entry points evaluate this sum; 0 = the single loss_kind
-  int sum_kinds[EOSVOS_LOSS_MAX_TERMS] = {0, 0, 0, 0};
-  float sum_weights[EOSVOS_LOSS_MAX_TERMS] = {0.f, 0.f, 0.f, 0.f};
   int* aug_tab = nullptr;               // eosvos_warp_affine: adelta[W] bdelta[W] X0[H] Y0[H], then the nonzero counter
   float* aug_ctab = nullptr;            // bicubic coefficients at 1/32 pixel: [32][4]
   // the call scratch of every evaluation-stage entry point (scratch_for, scratch_layout.h; grow-only, freed by destroy).  One
@@ -2322,43 +2343,51 @@ int eosvos_forward(eosvos_engine* e, const float* images, int batch, float* logi
 }
 namespace {
 inline bool lovasz_kind(int kind) { return kind == EOSVOS_LOSS_LOVASZ_HINGE || kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT; }
+inline bool bootstrap_kind(int kind) { return kind == EOSVOS_LOSS_BOOTSTRAPPED_BCE; }
 inline bool boundary_kind(int kind) { return kind == EOSVOS_LOSS_BOUNDARY_F || kind == EOSVOS_LOSS_BCE_AND_BOUNDARY_F; }
 // (7 is unassigned on purpose, see include/eosvos.h)
 inline bool loss_kind_ok(int kind) { return (kind >= EOSVOS_LOSS_BCE && kind <= EOSVOS_LOSS_BOOTSTRAPPED_BCE) || boundary_kind(kind); }
-// a void label is a finite value no target can take
-inline bool ignore_ok(float v) { return std::isfinite(v) && (v < 0.f || v > 1.f); }
+// a void label (null: none) is a finite value no target can take; 0 when it is one
+int ignore_check(const float* v) {
+  if (v && !(std::isfinite(*v) && (*v < 0.f || *v > 1.f))) return fail("the ignore label must be finite and outside [0, 1]");
+  return 0;
+}
 constexpr int PROP_MAX_FRAMES = 1024;
-// the Lovasz kinds' sort scratch, sized for the engine's largest batch; 0 on success
-int lovasz_ensure(eosvos_engine* e) {
-  if (e->lovasz_scratch) return 0;
-  const int64_t n = (int64_t)e->maxB * e->H * e->W;
-  if (n >= ((int64_t)1 << 30)) return fail("lovasz hinge: too many pixels for 32-bit sort values");
-  e->lovasz_scratch = e->falloc(lovasz_scratch_floats(n, e->maxB));
-  if (!e->lovasz_scratch) {
-    (void)hipGetLastError();              // the failed hipMalloc must not surface in a later call's launch check
-    return fail("lovasz hinge: out of device memory for the sort scratch");
-  }
-  return 0;
-}
-// the bootstrapped BCE's scratch, for maxB sets (its size does not depend on the number of pixels); 0 on success
-int bootstrap_ensure(eosvos_engine* e) {
-  if (e->bootstrap_scratch) return 0;
-  if ((int64_t)e->maxB * e->H * e->W >= ((int64_t)1 << 31)) return fail("bootstrapped cross-entropy: a set must have fewer than 2^31 pixels");
-  e->bootstrap_scratch = e->falloc(bootstrap_scratch_floats(e->maxB));
-  if (!e->bootstrap_scratch) {
-    (void)hipGetLastError();              // as lovasz_ensure
-    return fail("bootstrapped cross-entropy: out of device memory for the selection scratch");
-  }
-  return 0;
-}
-// the boundary-F kinds' scratch, sized for the engine's largest batch; 0 on success
-int boundary_ensure(eosvos_engine* e) {
-  if (e->boundary_scratch) return 0;
-  if ((int64_t)e->H * e->W >= ((int64_t)1 << 31)) return fail("boundary_f: an image must have fewer than 2^31 pixels");
-  e->boundary_scratch = e->falloc(boundary_scratch_floats((int64_t)e->maxB * e->H * e->W, e->maxB));
-  if (!e->boundary_scratch) {
-    (void)hipGetLastError();              // as lovasz_ensure
-    return fail("boundary_f: out of device memory for the boundary maps");
+// The scratch some kinds need beside the gradient, sized for the engine's largest batch and allocated when such a kind is
+// first selected or used: the Lovasz kinds' sort buffers, the bootstrapped BCE's histograms, state and partials (for maxB
+// sets; their size does not depend on the number of pixels), the boundary-F kinds' per-pixel maps and partials.
+const struct {
+  bool (*uses)(int kind);
+  float* eosvos_engine::*buf;
+  int64_t (*floats)(const eosvos_engine*);
+  int64_t (*pixels)(const eosvos_engine*);      // what `limit` bounds
+  int64_t limit;
+  const char *too_many, *no_memory;
+} LOSS_SCRATCH[] = {
+    {lovasz_kind, &eosvos_engine::lovasz_scratch,
+     [](const eosvos_engine* e) { return (int64_t)lovasz_scratch_floats((int64_t)e->maxB * e->H * e->W, e->maxB); },
+     [](const eosvos_engine* e) { return (int64_t)e->maxB * e->H * e->W; }, (int64_t)1 << 30,
+     "lovasz hinge: too many pixels for 32-bit sort values", "lovasz hinge: out of device memory for the sort scratch"},
+    {bootstrap_kind, &eosvos_engine::bootstrap_scratch,
+     [](const eosvos_engine* e) { return (int64_t)bootstrap_scratch_floats(e->maxB); },
+     [](const eosvos_engine* e) { return (int64_t)e->maxB * e->H * e->W; }, (int64_t)1 << 31,
+     "bootstrapped cross-entropy: a set must have fewer than 2^31 pixels",
+     "bootstrapped cross-entropy: out of device memory for the selection scratch"},
+    {boundary_kind, &eosvos_engine::boundary_scratch,
+     [](const eosvos_engine* e) { return (int64_t)boundary_scratch_floats((int64_t)e->maxB * e->H * e->W, e->maxB); },
+     [](const eosvos_engine* e) { return (int64_t)e->H * e->W; }, (int64_t)1 << 31,
+     "boundary_f: an image must have fewer than 2^31 pixels", "boundary_f: out of device memory for the boundary maps"},
+};
+// the scratch of `kind`, if it needs one: called wherever a kind is about to be used or is selected; 0 on success
+int loss_scratch_ensure(eosvos_engine* e, int kind) {
+  for (const auto& s : LOSS_SCRATCH) {
+    if (!s.uses(kind) || e->*s.buf) continue;
+    if (s.pixels(e) >= s.limit) return fail(s.too_many);
+    e->*s.buf = e->falloc(s.floats(e));
+    if (!(e->*s.buf)) {
+      (void)hipGetLastError();              // the failed hipMalloc must not surface in a later call's launch check
+      return fail(s.no_memory);
+    }
   }
   return 0;
 }
@@ -2367,156 +2396,173 @@ inline int boundary_default_radius(int H, int W) {
   const int r = (int)std::ceil(0.008 * std::sqrt((double)H * H + (double)W * W));
   return r < 1 ? 1 : r > 16 ? 16 : r;
 }
-// `images` maps of H x W; the combined kind evaluates the cross-entropy first and the boundary launches add to it
-int boundary_eval(eosvos_engine* e, bool combined, const float* logits, const float* masks, int H, int W, int images, int radius,
-                  const float* ignore, float* dlogits, float* loss) {
-  if (boundary_ensure(e)) return 1;
+// `images` maps of H x W (the scratch ensured by the caller); the combined kind evaluates the cross-entropy first and the
+// boundary launches add to it
+void boundary_eval(eosvos_engine* e, bool combined, const float* logits, const float* masks, int H, int W, int images, int radius,
+                   const float* ignore, float* dlogits, float* loss) {
   if (combined) launch_loss(EOSVOS_LOSS_BCE, logits, masks, dlogits, loss, e->bce_partial, (int64_t)H * W * images, ignore, e->s);
   launch_boundary_f(logits, masks, dlogits, loss, e->boundary_scratch, H, W, images, radius ? radius : boundary_default_radius(H, W),
                     combined ? 1 : 0, ignore, e->s);
-  return 0;
 }
 // Loss `kind` (checked by the caller) of `images` maps of n_per_image pixels -- the Lovasz kinds: per map, or with `flat` over
 // all of them as one set -- with its gradient, into the device pointers loss / dlogits.  `ignore`: the void label, or null.
 int loss_eval(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n_per_image, int images, int flat,
               const float* ignore, float* dlogits, float* loss) {
+  if (boundary_kind(kind) && n_per_image != (int64_t)e->H * e->W)      // needs the frame's shape: an image is the engine's H x W
+    return fail("boundary_f: the loss needs the frame's shape, so n must be the engine's H * W (one image); use eosvos_boundary_f for another shape");
+  if (loss_scratch_ensure(e, kind)) return 1;
   if (lovasz_kind(kind)) {
-    if (lovasz_ensure(e)) return 1;
     launch_lovasz(logits, masks, dlogits, loss, e->lovasz_scratch, n_per_image, images, flat, ignore, e->s);
-  } else if (kind == EOSVOS_LOSS_BOOTSTRAPPED_BCE) {          // per image, or (`flat`: caller tensors) all elements one set
-    if (bootstrap_ensure(e)) return 1;
+  } else if (bootstrap_kind(kind)) {                          // per image, or (`flat`: caller tensors) all elements one set
     if (n_per_image * (flat ? images : 1) >= ((int64_t)1 << 31)) return fail("bootstrapped cross-entropy: a set must have fewer than 2^31 pixels");
     launch_bootstrap_bce(logits, masks, dlogits, loss, e->bootstrap_scratch, flat ? n_per_image * images : n_per_image,
                          flat ? 1 : images, e->bootstrap_q, ignore, e->s);
-  } else if (boundary_kind(kind)) {                           // needs the frame's shape: an image is the engine's H x W
-    if (n_per_image != (int64_t)e->H * e->W)
-      return fail("boundary_f: the loss needs the frame's shape, so n must be the engine's H * W (one image); use eosvos_boundary_f for another shape");
-    if (boundary_eval(e, kind == EOSVOS_LOSS_BCE_AND_BOUNDARY_F, logits, masks, e->H, e->W, images, e->boundary_radius, ignore,
-                      dlogits, loss))
-      return 1;
+  } else if (boundary_kind(kind)) {
+    boundary_eval(e, kind == EOSVOS_LOSS_BCE_AND_BOUNDARY_F, logits, masks, e->H, e->W, images, e->boundary_radius, ignore, dlogits, loss);
   } else {
     launch_loss(kind, logits, masks, dlogits, loss, e->bce_partial, n_per_image * images, ignore, e->s);
   }
   HIPOK(hipGetLastError());
   return 0;
 }
-// on the logits of the last forward: leaves dL/dlogits for eosvos_backward_step
-int loss_on_forward(eosvos_engine* e, int kind, const float* masks, int batch, const float* ignore, float* loss_out) {
-  if (!e || !masks) return fail("null argument");
-  if (!loss_kind_ok(kind)) return fail("unknown loss kind");
-  if (ignore && !ignore_ok(*ignore)) return fail("the ignore label must be finite and outside [0, 1]");
-  if (batch != e->lastB) return fail("loss batch differs from the last forward");
-  if (loss_eval(e, kind, e->logits, masks, (int64_t)e->H * e->W, batch, kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT, ignore,
-                e->dlogits, e->loss_dev))
-    return 1;
-  e->have_loss_grad = true;
-  if (loss_out) HIPOK(hipMemcpyAsync(loss_out, e->loss_dev, 4, hipMemcpyDeviceToDevice, e->s));
-  return 0;
-}
-// on caller tensors, the n elements one set.  Without a caller buffer the gradient goes to the engine's own dlogits scratch,
-// which bounds n and invalidates a pending eosvos_loss* gradient.
-int loss_on_tensors(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n, const float* ignore,
-                    float* loss_out, float* dlogits_out) {
-  if (!e || !logits || !masks || !loss_out || n < 1) return fail("bad argument");
-  if (!loss_kind_ok(kind)) return fail("unknown loss kind");
-  if (ignore && !ignore_ok(*ignore)) return fail("the ignore label must be finite and outside [0, 1]");
-  if (!dlogits_out) {
-    if (n > (int64_t)e->maxB * e->H * e->W) return fail("n exceeds the engine's scratch");
-    e->have_loss_grad = false;
-  }
-  return loss_eval(e, kind, logits, masks, n, 1, 1, ignore, dlogits_out ? dlogits_out : e->dlogits, loss_out);
-}
-// ---- weighted sums of kinds (include/eosvos.h at eosvos_set_loss_sum) ----
-// the checks every sum entry point shares; 0 when the term list is a sum
-int sum_terms_ok(int n_terms, const int* kinds, const float* weights) {
-  if (n_terms < 1 || n_terms > EOSVOS_LOSS_MAX_TERMS) return fail("a loss sum has 1 .. 4 terms");
-  if (!kinds || !weights) return fail("null argument");
+// 0 when the spec names a loss: one known kind, or the term list of a sum (include/eosvos.h at eosvos_set_loss_sum)
+int loss_spec_ok(const LossSpec& spec) {
+  if (!spec.combine) return loss_kind_ok(spec.kinds[0]) ? 0 : fail("unknown loss kind");
+  if (spec.n < 1 || spec.n > EOSVOS_LOSS_MAX_TERMS) return fail("a loss sum has 1 .. 4 terms");
+  if (spec.null_terms) return fail("null argument");
   int boundary = 0;
-  for (int i = 0; i < n_terms; ++i) {
-    if (!loss_kind_ok(kinds[i])) return fail("unknown loss kind");
-    if (!(std::isfinite(weights[i]) && weights[i] > 0.f)) return fail("the weights of a loss sum must be finite and > 0");
+  for (int i = 0; i < spec.n; ++i) {
+    if (!loss_kind_ok(spec.kinds[i])) return fail("unknown loss kind");
+    if (!(std::isfinite(spec.weights[i]) && spec.weights[i] > 0.f)) return fail("the weights of a loss sum must be finite and > 0");
     for (int j = 0; j < i; ++j)
-      if (kinds[j] == kinds[i]) return fail("a loss sum names a kind twice");
-    boundary += boundary_kind(kinds[i]) ? 1 : 0;
+      if (spec.kinds[j] == spec.kinds[i]) return fail("a loss sum names a kind twice");
+    boundary += boundary_kind(spec.kinds[i]) ? 1 : 0;
   }
   if (boundary > 1) return fail("a loss sum takes one boundary kind: the two share the engine's radius");
   return 0;
 }
-// every term's own scratch, the value slots and one gradient slice per term; 0 on success
-int sum_ensure(eosvos_engine* e, int n_terms, const int* kinds) {
-  for (int i = 0; i < n_terms; ++i) {
-    if (lovasz_kind(kinds[i]) && lovasz_ensure(e)) return 1;
-    if (kinds[i] == EOSVOS_LOSS_BOOTSTRAPPED_BCE && bootstrap_ensure(e)) return 1;
-    if (boundary_kind(kinds[i]) && boundary_ensure(e)) return 1;
-  }
+// all a (checked) spec needs beside the launches' arguments: every kind's own scratch and, where it combines, the value
+// slots and one gradient slice per term; 0 on success
+int loss_spec_ensure(eosvos_engine* e, const LossSpec& spec) {
+  for (int i = 0; i < spec.n; ++i)
+    if (loss_scratch_ensure(e, spec.kinds[i])) return 1;
+  if (!spec.combine) return 0;
   if (!e->sum_vals) {
     e->sum_vals = e->falloc(2 * EOSVOS_LOSS_MAX_TERMS);
     if (e->sum_vals && hipMemsetAsync(e->sum_vals, 0, sizeof(float) * 2 * EOSVOS_LOSS_MAX_TERMS, e->s) != hipSuccess) e->sum_vals = nullptr;
   }
-  for (int i = 0; e->sum_vals && i < n_terms; ++i) {
+  for (int i = 0; e->sum_vals && i < spec.n; ++i) {
     if (!e->sum_slice[i]) e->sum_slice[i] = e->falloc((int64_t)e->maxB * e->H * e->W);
     if (!e->sum_slice[i]) break;
   }
-  if (!e->sum_vals || !e->sum_slice[n_terms - 1]) {
-    (void)hipGetLastError();              // as lovasz_ensure
+  if (!e->sum_vals || !e->sum_slice[spec.n - 1]) {
+    (void)hipGetLastError();              // as loss_scratch_ensure
     return fail("loss sum: out of device memory for the terms' gradients");
   }
   return 0;
 }
-// The sum (checked by sum_terms_ok) of `images` maps of n_per_image pixels: each term by loss_eval's own launches into its
-// slice and value slot, then one launch that combines them into dlogits / loss.  `one_set`: caller tensors, every kind takes
-// the elements as one set (loss_on_tensors' rule); otherwise only the flat Lovasz kind does.
-int loss_sum_eval(eosvos_engine* e, int n_terms, const int* kinds, const float* weights, const float* logits, const float* masks,
-                  int64_t n_per_image, int images, bool one_set, const float* ignore, float* dlogits, float* loss) {
+// The (checked) spec on `images` maps of n_per_image pixels, into the device pointers loss / dlogits.  `one_set`: caller
+// tensors, every kind takes the elements as one set; otherwise only the flat Lovasz kind does.  One kind: its own launches and
+// nothing else.  A sum: each term by the same launches into its slice and value slot, then the one that combines them; the
+// slices bound n.
+int loss_spec_eval(eosvos_engine* e, const LossSpec& spec, const float* logits, const float* masks, int64_t n_per_image, int images,
+                   bool one_set, const float* ignore, float* dlogits, float* loss) {
+  const auto flat = [&](int kind) { return one_set || kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT; };
+  if (!spec.combine) return loss_eval(e, spec.kinds[0], logits, masks, n_per_image, images, flat(spec.kinds[0]), ignore, dlogits, loss);
   const int64_t n = n_per_image * images;
   if (n > (int64_t)e->maxB * e->H * e->W) return fail("n exceeds the engine's scratch");
-  if (sum_ensure(e, n_terms, kinds)) return 1;
-  for (int i = 0; i < n_terms; ++i)
-    if (loss_eval(e, kinds[i], logits, masks, n_per_image, images, one_set || kinds[i] == EOSVOS_LOSS_LOVASZ_HINGE_FLAT, ignore,
-                  e->sum_slice[i], e->sum_vals + i))
+  if (loss_spec_ensure(e, spec)) return 1;
+  for (int i = 0; i < spec.n; ++i)
+    if (loss_eval(e, spec.kinds[i], logits, masks, n_per_image, images, flat(spec.kinds[i]), ignore, e->sum_slice[i], e->sum_vals + i))
       return 1;
-  launch_loss_sum(n_terms, e->sum_slice, weights, e->sum_vals, dlogits, loss, e->sum_vals + EOSVOS_LOSS_MAX_TERMS, n, e->s);
+  launch_loss_sum(spec.n, e->sum_slice, spec.weights, e->sum_vals, dlogits, loss, e->sum_vals + EOSVOS_LOSS_MAX_TERMS, n, e->s);
   HIPOK(hipGetLastError());
-  e->sum_last_terms = n_terms;
+  e->sum_last_terms = spec.n;
   return 0;
 }
-// the sum on the logits of the last forward: leaves dL/dlogits for eosvos_backward_step
-int loss_sum_on_forward(eosvos_engine* e, int n_terms, const int* kinds, const float* weights, const float* masks, int batch,
-                        const float* ignore, float* loss_out) {
+// on the logits of the last forward: leaves dL/dlogits for eosvos_backward_step, and none after a failed evaluation
+int loss_on_forward(eosvos_engine* e, const LossSpec& spec, const float* masks, int batch, const float* ignore, float* loss_out) {
   if (!e || !masks) return fail("null argument");
-  if (sum_terms_ok(n_terms, kinds, weights)) return 1;
-  if (ignore && !ignore_ok(*ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  if (loss_spec_ok(spec) || ignore_check(ignore)) return 1;
   if (batch != e->lastB) return fail("loss batch differs from the last forward");
   e->have_loss_grad = false;
-  if (loss_sum_eval(e, n_terms, kinds, weights, e->logits, masks, (int64_t)e->H * e->W, batch, false, ignore, e->dlogits, e->loss_dev))
-    return 1;
+  if (loss_spec_eval(e, spec, e->logits, masks, (int64_t)e->H * e->W, batch, false, ignore, e->dlogits, e->loss_dev)) return 1;
   e->have_loss_grad = true;
   if (loss_out) HIPOK(hipMemcpyAsync(loss_out, e->loss_dev, 4, hipMemcpyDeviceToDevice, e->s));
   return 0;
 }
+// where an evaluation on caller tensors puts its gradient: the caller's buffer, or the engine's own dlogits scratch, which
+// invalidates a pending eosvos_loss* gradient
+float* grad_target(eosvos_engine* e, float* dlogits_out) {
+  if (!dlogits_out) e->have_loss_grad = false;
+  return dlogits_out ? dlogits_out : e->dlogits;
+}
+// on caller tensors, the n elements one set.  The engine's dlogits scratch bounds n; a single kind with a caller buffer has no
+// bound, a sum always that of its slices.
+int loss_on_tensors(eosvos_engine* e, const LossSpec& spec, const float* logits, const float* masks, int64_t n, const float* ignore,
+                    float* loss_out, float* dlogits_out) {
+  if (!e || !logits || !masks || !loss_out || n < 1) return fail("bad argument");
+  if (loss_spec_ok(spec) || ignore_check(ignore)) return 1;
+  if (!spec.combine && !dlogits_out && n > (int64_t)e->maxB * e->H * e->W) return fail("n exceeds the engine's scratch");
+  return loss_spec_eval(e, spec, logits, masks, n, 1, true, ignore, grad_target(e, dlogits_out), loss_out);
+}
 // the loss of the fused entry points
 inline int fused_loss(eosvos_engine* e, const float* masks, int batch) {
-  const float* ignore = e->loss_ignore_on ? &e->loss_ignore : nullptr;
-  if (e->sum_n) return loss_sum_on_forward(e, e->sum_n, e->sum_kinds, e->sum_weights, masks, batch, ignore, nullptr);
-  return loss_on_forward(e, e->loss_kind, masks, batch, ignore, nullptr);
+  return loss_on_forward(e, e->fused, masks, batch, e->loss_ignore_on ? &e->loss_ignore : nullptr, nullptr);
+}
+int set_fused_loss(eosvos_engine* e, const LossSpec& spec) {
+  if (!e) return fail("null engine");
+  if (loss_spec_ok(spec) || loss_spec_ensure(e, spec)) return 1;
+  e->fused = spec;
+  return 0;
 }
 }  // namespace
 
+// ---- the loss entry points: forms of loss_on_forward / loss_on_tensors, each building its LossSpec ----
 int eosvos_loss_bce(eosvos_engine* e, const float* masks, int batch, float* loss_out) {
   ModeScope mode_scope(e);
-  return loss_on_forward(e, EOSVOS_LOSS_BCE, masks, batch, nullptr, loss_out);
+  return loss_on_forward(e, LossSpec::single(EOSVOS_LOSS_BCE), masks, batch, nullptr, loss_out);
 }
 int eosvos_loss(eosvos_engine* e, int kind, const float* masks, int batch, float* loss_out) {
   ModeScope mode_scope(e);
-  return loss_on_forward(e, kind, masks, batch, nullptr, loss_out);
+  return loss_on_forward(e, LossSpec::single(kind), masks, batch, nullptr, loss_out);
 }
 int eosvos_loss_ignore(eosvos_engine* e, int kind, const float* masks, int batch, float ignore, float* loss_out) {
   ModeScope mode_scope(e);
-  return loss_on_forward(e, kind, masks, batch, &ignore, loss_out);
+  return loss_on_forward(e, LossSpec::single(kind), masks, batch, &ignore, loss_out);
+}
+int eosvos_loss_sum(eosvos_engine* e, int n_terms, const int* kinds, const float* weights, const float* masks, int batch,
+                    int ignore_on, float ignore, float* loss_out) {
+  ModeScope mode_scope(e);
+  return loss_on_forward(e, LossSpec::sum(n_terms, kinds, weights), masks, batch, ignore_on ? &ignore : nullptr, loss_out);
+}
+int eosvos_bce(eosvos_engine* e, const float* logits, const float* masks, int64_t n, float* loss_out,
+               float* dlogits_out) {
+  ModeScope mode_scope(e);
+  return loss_on_tensors(e, LossSpec::single(EOSVOS_LOSS_BCE), logits, masks, n, nullptr, loss_out, dlogits_out);
+}
+int eosvos_loss_tensors(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n, float* loss_out) {
+  ModeScope mode_scope(e);
+  return loss_on_tensors(e, LossSpec::single(kind), logits, masks, n, nullptr, loss_out, nullptr);
+}
+int eosvos_loss_tensors_ignore(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n, float ignore,
+                               float* loss_out) {
+  ModeScope mode_scope(e);
+  return loss_on_tensors(e, LossSpec::single(kind), logits, masks, n, &ignore, loss_out, nullptr);
+}
+int eosvos_loss_sum_tensors(eosvos_engine* e, int n_terms, const int* kinds, const float* weights, const float* logits,
+                            const float* masks, int64_t n, int ignore_on, float ignore, float* loss_out, float* dlogits_out) {
+  ModeScope mode_scope(e);
+  return loss_on_tensors(e, LossSpec::sum(n_terms, kinds, weights), logits, masks, n, ignore_on ? &ignore : nullptr, loss_out,
+                         dlogits_out);
+}
+int eosvos_set_loss(eosvos_engine* e, int kind) { return set_fused_loss(e, LossSpec::single(kind)); }
+int eosvos_set_loss_sum(eosvos_engine* e, int n_terms, const int* kinds, const float* weights) {
+  return set_fused_loss(e, LossSpec::sum(n_terms, kinds, weights));
 }
 int eosvos_set_loss_ignore(eosvos_engine* e, int on, float ignore) {
   if (!e) return fail("null engine");
-  if (on && !ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  if (on && ignore_check(&ignore)) return 1;
   e->loss_ignore_on = on != 0;
   e->loss_ignore = on ? ignore : 0.f;
   return 0;
@@ -2525,39 +2571,6 @@ int eosvos_last_loss(eosvos_engine* e, float* loss_out) {
   if (!e || !loss_out) return fail("null argument");
   HIPOK(hipMemcpyAsync(loss_out, e->loss_dev, 4, hipMemcpyDeviceToDevice, e->s));
   return 0;
-}
-int eosvos_set_loss(eosvos_engine* e, int kind) {
-  if (!e) return fail("null engine");
-  if (!loss_kind_ok(kind)) return fail("unknown loss kind");
-  if (lovasz_kind(kind) && lovasz_ensure(e)) return 1;
-  if (kind == EOSVOS_LOSS_BOOTSTRAPPED_BCE && bootstrap_ensure(e)) return 1;
-  if (boundary_kind(kind) && boundary_ensure(e)) return 1;
-  e->loss_kind = kind;
-  e->sum_n = 0;
-  return 0;
-}
-int eosvos_set_loss_sum(eosvos_engine* e, int n_terms, const int* kinds, const float* weights) {
-  if (!e) return fail("null engine");
-  if (sum_terms_ok(n_terms, kinds, weights)) return 1;
-  if (sum_ensure(e, n_terms, kinds)) return 1;
-  for (int i = 0; i < n_terms; ++i) { e->sum_kinds[i] = kinds[i]; e->sum_weights[i] = weights[i]; }
-  e->sum_n = n_terms;
-  return 0;
-}
-int eosvos_loss_sum(eosvos_engine* e, int n_terms, const int* kinds, const float* weights, const float* masks, int batch,
-                    int ignore_on, float ignore, float* loss_out) {
-  ModeScope mode_scope(e);
-  return loss_sum_on_forward(e, n_terms, kinds, weights, masks, batch, ignore_on ? &ignore : nullptr, loss_out);
-}
-int eosvos_loss_sum_tensors(eosvos_engine* e, int n_terms, const int* kinds, const float* weights, const float* logits,
-                            const float* masks, int64_t n, int ignore_on, float ignore, float* loss_out, float* dlogits_out) {
-  ModeScope mode_scope(e);
-  if (!e || !logits || !masks || !loss_out || n < 1) return fail("bad argument");
-  if (sum_terms_ok(n_terms, kinds, weights)) return 1;
-  if (ignore_on && !ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
-  if (!dlogits_out) e->have_loss_grad = false;
-  return loss_sum_eval(e, n_terms, kinds, weights, logits, masks, n, 1, true, ignore_on ? &ignore : nullptr,
-                       dlogits_out ? dlogits_out : e->dlogits, loss_out);
 }
 int eosvos_last_loss_terms(eosvos_engine* e, float* out, int* n_terms_host) {
   if (!e || !out) return fail("null argument");
@@ -2586,27 +2599,12 @@ int eosvos_boundary_f(eosvos_engine* e, const float* logits, const float* masks,
   if (batch < 1 || batch > e->maxB || height < 1 || width < 1) return fail("eosvos_boundary_f: bad geometry");
   if ((int64_t)batch * height * width > (int64_t)e->maxB * e->H * e->W) return fail("eosvos_boundary_f: more pixels than the engine's scratch holds");
   if (radius < 0 || radius > 16) return fail("the boundary radius must be 1 .. 16, or 0 for the frame-size default");
-  if (ignore_on && !ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
-  if (!dlogits_out) e->have_loss_grad = false;
-  if (boundary_eval(e, combined != 0, logits, masks, height, width, batch, radius, ignore_on ? &ignore : nullptr,
-                    dlogits_out ? dlogits_out : e->dlogits, loss_out))
-    return 1;
+  if (ignore_on && ignore_check(&ignore)) return 1;
+  float* const dlogits = grad_target(e, dlogits_out);
+  if (loss_scratch_ensure(e, EOSVOS_LOSS_BOUNDARY_F)) return 1;
+  boundary_eval(e, combined != 0, logits, masks, height, width, batch, radius, ignore_on ? &ignore : nullptr, dlogits, loss_out);
   HIPOK(hipGetLastError());
   return 0;
-}
-int eosvos_bce(eosvos_engine* e, const float* logits, const float* masks, int64_t n, float* loss_out,
-               float* dlogits_out) {
-  ModeScope mode_scope(e);
-  return loss_on_tensors(e, EOSVOS_LOSS_BCE, logits, masks, n, nullptr, loss_out, dlogits_out);
-}
-int eosvos_loss_tensors(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n, float* loss_out) {
-  ModeScope mode_scope(e);
-  return loss_on_tensors(e, kind, logits, masks, n, nullptr, loss_out, nullptr);
-}
-int eosvos_loss_tensors_ignore(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n, float ignore,
-                               float* loss_out) {
-  ModeScope mode_scope(e);
-  return loss_on_tensors(e, kind, logits, masks, n, &ignore, loss_out, nullptr);
 }
 int eosvos_propagation_targets(eosvos_engine* e, const float* probs, int n_frames, int64_t n_pix, float lo, float hi,
                                float ignore, float* targets_out, int64_t* n_pos_host) {
@@ -2614,7 +2612,7 @@ int eosvos_propagation_targets(eosvos_engine* e, const float* probs, int n_frame
   if (n_frames < 1 || n_frames > PROP_MAX_FRAMES || n_pix < 1 || n_pix >= ((int64_t)1 << 31))
     return fail("eosvos_propagation_targets: 1 .. 1024 frames of 1 .. 2^31 - 1 pixels");
   if (!(lo >= 0.f && lo < hi && hi <= 1.f)) return fail("eosvos_propagation_targets: needs 0 <= lo < hi <= 1");
-  if (!ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  if (ignore_check(&ignore)) return 1;
   if (!e->prop_count) {
     e->prop_count = (int*)e->falloc(PROP_MAX_FRAMES);
     if (!e->prop_count) {
@@ -3256,7 +3254,7 @@ int eosvos_adapt_targets(eosvos_engine* e, const float* probs, const float* anch
   if (erode < 0 || erode > 255) return fail("adapt_targets: erode must be in [0, 255]");
   if (!(lo >= 0.f && lo < hi && hi <= 1.f)) return fail("adapt_targets: needs 0 <= lo < hi <= 1");
   if (std::isnan(anchor_thr)) return fail("adapt_targets: the anchor threshold is NaN");
-  if (!ignore_ok(ignore)) return fail("the ignore label must be finite and outside [0, 1]");
+  if (ignore_check(&ignore)) return 1;
   const AdaptTargetsLayout L(n_frames, (size_t)n_frames * height * width, erode > 0);
   if (scratch_for(e, "adapt_targets", L, n_frames)) return 1;
   launch_edt_targets(probs, anchors, n_frames, height, width, lo, hi, anchor_thr, erode, neg_dist, ignore, scratch_at(e, L.g),

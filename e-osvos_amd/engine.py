@@ -4,12 +4,14 @@ model per process, `src/util/helper_func.py:499-512`).
 torch-ROCm is used for device memory and streams only; every arithmetic call goes through
 the C-ABI of include/eosvos.h.
 """
+import collections
 import ctypes
 import functools
 
 import torch
 
 from . import _ffi, bootstrap, boundary, loss_sum
+from .loss_names import LOSS_KINDS, resolve_loss, resolve_radius  # noqa: F401  (their home; callers import them from here)
 from .topology import ARCH_ID, norm_layers, trainable
 
 
@@ -64,55 +66,25 @@ def _touched(*tensors):
 
 
 LR_LEVELS = {'NEURON': 0, 'TENSOR': 1, 'SINGLE': 2, 'PARAM': 3}      # include/eosvos.h EOSVOS_LR_*
-LOSS_KINDS = {'cross_entropy': 0, 'dice': 1, 'cross_entropy_and_dice': 2, 'class_balanced_cross_entropy': 3,
-              'lovasz_hinge': 4, 'lovasz_hinge_flat': 5,      # these two: networks/loss_lovasz.py:78-111, per_image True / False
-              'bootstrapped_cross_entropy': 6}                # the hardest fraction of the pixels per image (bootstrap.py)
-
-
-def resolve_loss(name, fraction=None, radius=None):
-    """A spelled loss name -> (kind id, fraction or None).  `bootstrapped_cross_entropy_<P>` carries P percent; `fraction`
-    is the keyword form, for that kind only; the two may not disagree.  None: the engine's current fraction stays.  A bad
-    spelling under the bootstrap prefix raises NotImplementedError, any other unknown name KeyError.  The kinds that need the
-    frame's shape (`boundary.KINDS`) are consulted after LOSS_KINDS and give (kind id, None); their radius, from the name
-    or `radius=`, is `resolve_radius`'s, which this call checks too."""
-    radius = resolve_radius(name, radius)
-    base, f = bootstrap.parse(name)
-    if base not in LOSS_KINDS and boundary.parse(name)[0] in boundary.KINDS:
-        if fraction is not None:
-            raise ValueError(f"fraction= belongs to '{bootstrap.NAME}', not to '{name}'")
-        return boundary.KINDS[boundary.parse(name)[0]], None
-    kind = LOSS_KINDS[base]
-    if fraction is not None:
-        if base != bootstrap.NAME:
-            raise ValueError(f"fraction= belongs to '{bootstrap.NAME}', not to '{name}'")
-        if f is not None and bootstrap.q_of(f) != bootstrap.q_of(fraction):
-            raise ValueError(f"loss_func='{name}' and fraction={fraction!r} disagree")
-        f = fraction
-    return kind, (None if f is None else bootstrap.check_fraction(f))
-
-
-def resolve_radius(name, radius=None):
-    """The window radius a spelled loss name asks for: `boundary_f_<r>` / `cross_entropy_and_boundary_f_<r>` carry r,
-    `radius` is the keyword form, for those kinds only; the two may not disagree.  None: the engine's current radius stays."""
-    base, r = boundary.parse(name)
-    if radius is not None:
-        if base not in boundary.KINDS:
-            raise ValueError(f"radius= belongs to {' / '.join(repr(k) for k in boundary.KINDS)}, not to '{name}'")
-        radius = boundary.check_radius(radius)
-        if r is not None and r != radius:
-            raise ValueError(f"loss_func='{name}' and radius={radius!r} disagree")
-        r = radius
-    return r
+# One resolved `loss_func`: the ctypes arrays of its n kinds and weights, whether the engine combines them (a spelling with
+# '+' or '*') or runs kinds[0]'s own launches alone, and the fraction / radius the spelling or its keyword carries (None: the
+# engine's current value stays).
+LossSpec = collections.namedtuple('LossSpec', 'n kinds weights combine fraction radius')
 
 
 @functools.lru_cache(maxsize=64, typed=True)
-def _resolve_sum(name, fraction, radius):
-    """`loss_sum.resolve` as the ctypes arrays of the eosvos_*loss_sum* calls, kept per spelling: (kinds, weights, fraction
-    or None, radius or None).  Splitting and checking a spelling takes ~10 us on the host, which a loss whose launches take
-    30 us would otherwise pay on every evaluation (`profiles/loss_sum_time.txt`); a spelling that raises is not kept."""
-    kinds, weights, _, f, r = loss_sum.resolve(name, fraction, radius)
+def _resolve(name, fraction, radius):
+    """A sum spelling (`loss_sum.resolve`) or a plain name (`resolve_loss` / `resolve_radius`, one term of weight 1) as a
+    LossSpec, kept per spelling: splitting and checking one takes ~10 us on the host, which a loss whose launches take 30 us
+    would otherwise pay on every evaluation (`profiles/loss_sum_time.txt`); a spelling that raises is not kept."""
+    combine = loss_sum.is_sum(name)
+    if combine:
+        kinds, weights, _, f, r = loss_sum.resolve(name, fraction, radius)
+    else:
+        kind, f = resolve_loss(name, fraction, radius)
+        kinds, weights, r = [kind], [1.0], resolve_radius(name, radius)
     n = len(kinds)
-    return (ctypes.c_int * n)(*kinds), (ctypes.c_float * n)(*weights), f, r
+    return LossSpec(n, (ctypes.c_int * n)(*kinds), (ctypes.c_float * n)(*weights), combine, f, r)
 
 
 def check_ignore(ignore):
@@ -254,17 +226,17 @@ class Engine:
     def set_loss(self, name, ignore=None, fraction=None, radius=None):
         """Loss of finetune_step / meta_grad (`loss_func`, helper_func.py:28-56) and its void label (None: every pixel counts).
         `bootstrapped_cross_entropy_<P>` or `fraction=` also set the engine's bootstrap fraction, `boundary_f_<r>` /
-        `cross_entropy_and_boundary_f_<r>` or `radius=` its boundary radius (see `_loss_kind`).  A sum spelling
+        `cross_entropy_and_boundary_f_<r>` or `radius=` its boundary radius (see `_loss_spec`).  A sum spelling
         (`0.5*lovasz_hinge+boundary_f_4`, `loss_sum.py`) selects `eosvos_set_loss_sum`; a single name returns to one kind."""
-        if loss_sum.is_sum(name):
-            v = None if ignore is None else check_ignore(ignore)
-            _ffi.check(self.lib.eosvos_set_loss_sum(self.h, *self._loss_sum_args(name, fraction, radius)))
-            _ffi.check(self.lib.eosvos_set_loss_ignore(self.h, int(v is not None), v or 0.0))
-            return
-        if bootstrap.parse(name)[0] not in LOSS_KINDS and boundary.parse(name)[0] not in boundary.KINDS:
-            raise NotImplementedError(name)             # helper_func.py:55-56
+        try:
+            spec = self._loss_spec(name, fraction, radius)
+        except KeyError:
+            raise NotImplementedError(name) from None   # helper_func.py:55-56
         v = None if ignore is None else check_ignore(ignore)
-        _ffi.check(self.lib.eosvos_set_loss(self.h, self._loss_kind(name, fraction, radius)))
+        if spec.combine:
+            _ffi.check(self.lib.eosvos_set_loss_sum(self.h, spec.n, spec.kinds, spec.weights))
+        else:
+            _ffi.check(self.lib.eosvos_set_loss(self.h, spec.kinds[0]))
         _ffi.check(self.lib.eosvos_set_loss_ignore(self.h, int(v is not None), v or 0.0))
 
     def set_loss_bootstrap(self, fraction):
@@ -279,26 +251,39 @@ class Engine:
         _ffi.check(self.lib.eosvos_set_loss_boundary(self.h, 0 if radius == 0 and not isinstance(radius, bool)
                                                      else boundary.check_radius(radius)))
 
-    def _loss_kind(self, name, fraction=None, radius=None):
-        """The kind id of a spelled loss name (`resolve_loss`); a fraction or radius carried by the name or the keyword becomes
-        the engine's before the call that follows."""
-        kind, f = resolve_loss(name, fraction, radius)
-        r = resolve_radius(name, radius)
-        if f is not None:
-            self.set_loss_bootstrap(f)
-        if r is not None:
-            self.set_loss_boundary(r)
-        return kind
+    def _loss_spec(self, name, fraction=None, radius=None):
+        """The LossSpec of a spelled `loss_func` (`_resolve`); a fraction or radius carried by the spelling or the keyword
+        becomes the engine's before the call that follows."""
+        spec = _resolve(name, fraction, radius)
+        if spec.fraction is not None:
+            self.set_loss_bootstrap(spec.fraction)
+        if spec.radius is not None:
+            self.set_loss_boundary(spec.radius)
+        return spec
 
-    def _loss_sum_args(self, name, fraction=None, radius=None):
-        """(n_terms, kinds, weights) of a sum spelling for the eosvos_*loss_sum* calls (`loss_sum.resolve`); a fraction or
-        radius carried by a term or a keyword becomes the engine's before the call that follows, as in `_loss_kind`."""
-        kinds, weights, f, r = _resolve_sum(name, fraction, radius)
-        if f is not None:
-            self.set_loss_bootstrap(f)
-        if r is not None:
-            self.set_loss_boundary(r)
-        return len(kinds), kinds, weights
+    def _loss_on_forward(self, spec, masks, ignore, out):
+        """The spec on the last forward: eosvos_loss, eosvos_loss_ignore with a void label, or eosvos_loss_sum."""
+        b = masks.shape[0]
+        if spec.combine:
+            _ffi.check(self.lib.eosvos_loss_sum(self.h, spec.n, spec.kinds, spec.weights, _ptr(masks), b, int(ignore is not None),
+                                                ignore or 0.0, _optr(out)))
+        elif ignore is None:
+            _ffi.check(self.lib.eosvos_loss(self.h, spec.kinds[0], _ptr(masks), b, _optr(out)))
+        else:
+            _ffi.check(self.lib.eosvos_loss_ignore(self.h, spec.kinds[0], _ptr(masks), b, ignore, _optr(out)))
+
+    def _loss_on_tensors(self, spec, logits, masks, ignore, out, grad=None):
+        """The spec on caller tensors, the elements one set: eosvos_loss_tensors, eosvos_loss_tensors_ignore with a void label,
+        or eosvos_loss_sum_tensors -- the one that hands a gradient back, so with `grad` a single kind goes there too, as the
+        sum of one term of weight 1, which has that kind's bits."""
+        n = logits.numel()
+        if spec.combine or grad is not None:
+            _ffi.check(self.lib.eosvos_loss_sum_tensors(self.h, spec.n, spec.kinds, spec.weights, _ptr(logits), _ptr(masks), n,
+                                                        int(ignore is not None), ignore or 0.0, _ptr(out), _optr(grad)))
+        elif ignore is None:
+            _ffi.check(self.lib.eosvos_loss_tensors(self.h, spec.kinds[0], _ptr(logits), _ptr(masks), n, _ptr(out)))
+        else:
+            _ffi.check(self.lib.eosvos_loss_tensors_ignore(self.h, spec.kinds[0], _ptr(logits), _ptr(masks), n, ignore, _ptr(out)))
 
     def set_norm(self, gamma, beta, mean, var, eps=1e-5):
         ts = [_dev_f32(t, self.device) for t in (gamma, beta, mean, var)]
@@ -438,18 +423,6 @@ class Engine:
             return 'f16x3'
         return self._verify_step(images, masks, loss_kind)
 
-    def _loss_call(self, kind, masks, ignore, out):
-        """eosvos_loss, or eosvos_loss_ignore with a void label, on the last forward; eosvos_loss_sum for a sum spelling."""
-        if loss_sum.is_sum(kind):
-            _ffi.check(self.lib.eosvos_loss_sum(self.h, *self._loss_sum_args(kind), _ptr(masks), masks.shape[0],
-                                                int(ignore is not None), ignore or 0.0, _optr(out)))
-            return
-        kid = self._loss_kind(kind)
-        if ignore is None:
-            _ffi.check(self.lib.eosvos_loss(self.h, kid, _ptr(masks), masks.shape[0], _optr(out)))
-        else:
-            _ffi.check(self.lib.eosvos_loss_ignore(self.h, kid, _ptr(masks), masks.shape[0], ignore, _optr(out)))
-
     def _verify_step(self, images, masks, loss_kind=None, ignore=None):
         """The fine-tune-step half of the guard (see verify_matrix_mode): one step in each split mode from the same weights.
         `loss_kind` None: the fused step with the engine's own loss and void label; otherwise that loss with `ignore`."""
@@ -465,7 +438,7 @@ class Engine:
                     _ffi.check(self.lib.eosvos_finetune_step(self.h, _ptr(images), _ptr(masks), b, 0, None))
                 else:
                     _ffi.check(self.lib.eosvos_forward(self.h, _ptr(images), b, None))
-                    self._loss_call(loss_kind, masks, ignore, None)
+                    self._loss_on_forward(self._loss_spec(loss_kind), masks, ignore, None)
                     _ffi.check(self.lib.eosvos_backward_step(self.h, 0))
                 loss = torch.empty(1, device=self.device)
                 _ffi.check(self.lib.eosvos_last_loss(self.h, _ptr(loss)))
@@ -535,14 +508,11 @@ class Engine:
         pixels whose mask equals it are in no sum, count or ranking and get gradient 0 (`eosvos_loss_ignore`).  `fraction`:
         of `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, as in `set_loss`.  A sum spelling evaluates the
         weighted sum of its terms (`eosvos_loss_sum`); `last_loss_terms` then gives the terms' own values."""
-        if loss_sum.is_sum(kind):
-            self._loss_sum_args(kind, fraction, radius)
-        else:
-            self._loss_kind(kind, fraction, radius)
+        spec = self._loss_spec(kind, fraction, radius)
         ignore = None if ignore is None else check_ignore(ignore)
         assert masks.is_cuda and masks.dtype == torch.float32 and masks.is_contiguous()
         out = torch.empty(1, device=self.device)
-        self._loss_call(kind, masks, ignore, out)
+        self._loss_on_forward(spec, masks, ignore, out)
         if getattr(self, '_step_check_pending', False):
             self._chk_masks, self._chk_kind, self._chk_ignore = masks, kind, ignore
         return out
@@ -555,17 +525,8 @@ class Engine:
         logits, masks = logits.contiguous(), masks.contiguous()
         assert logits.is_cuda and masks.is_cuda and logits.numel() == masks.numel()
         out = torch.empty(1, device=self.device)
-        if loss_sum.is_sum(kind):                       # the n elements one set for every term; no gradient is kept
-            v = None if ignore is None else check_ignore(ignore)
-            _ffi.check(self.lib.eosvos_loss_sum_tensors(self.h, *self._loss_sum_args(kind, fraction, radius), _ptr(logits), _ptr(masks),
-                                                        logits.numel(), int(v is not None), v or 0.0, _ptr(out), None))
-            return out
-        kid = self._loss_kind(kind, fraction, radius)
-        if ignore is None:
-            _ffi.check(self.lib.eosvos_loss_tensors(self.h, kid, _ptr(logits), _ptr(masks), logits.numel(), _ptr(out)))
-        else:
-            _ffi.check(self.lib.eosvos_loss_tensors_ignore(self.h, kid, _ptr(logits), _ptr(masks), logits.numel(),
-                                                           check_ignore(ignore), _ptr(out)))
+        self._loss_on_tensors(self._loss_spec(kind, fraction, radius), logits, masks,
+                              None if ignore is None else check_ignore(ignore), out)
         return out
 
     def loss_grad_of(self, name, logits, masks, ignore=None, fraction=None, radius=None):
@@ -577,8 +538,11 @@ class Engine:
         assert logits.numel() == masks.numel()
         v = None if ignore is None else check_ignore(ignore)
         out, grad = torch.empty(1, device=self.device), torch.empty_like(logits)
-        _ffi.check(self.lib.eosvos_loss_sum_tensors(self.h, *self._loss_sum_args(name, fraction, radius), _ptr(logits), _ptr(masks),
-                                                    logits.numel(), int(v is not None), v or 0.0, _ptr(out), _ptr(grad)))
+        try:
+            spec = self._loss_spec(name, fraction, radius)
+        except KeyError:
+            raise NotImplementedError(f"loss_func='{name}'") from None
+        self._loss_on_tensors(spec, logits, masks, v, out, grad)
         return out, grad
 
     def last_loss_terms(self):
@@ -695,7 +659,7 @@ class Engine:
             if not accumulate and x is not None and m is not None and m.shape[0] == x.shape[0] and _guard_enabled():
                 self._verify_step(x, m, kind, ign)
                 _ffi.check(self.lib.eosvos_forward(self.h, _ptr(x), x.shape[0], None))
-                self._loss_call(kind, m, ign, None)
+                self._loss_on_forward(self._loss_spec(kind), m, ign, None)
         _ffi.check(self.lib.eosvos_backward_step(self.h, int(accumulate)))
         self.steps_since_reset += 1
 

@@ -25,10 +25,9 @@ import random
 import numpy as np
 import torch
 
-from . import bootstrap, boundary, loss_sum
+from . import loss_sum
 from . import tta as tta_views
 from . import zoom as zoom_pass
-from .engine import resolve_loss
 from .networks import DeepLabV3, DeepLabV3Plus
 
 
@@ -36,40 +35,9 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
     """`compute_loss(loss_func, outputs, gts, loss_kwargs=None)`, helper_func.py:28-56.  The returned
     0-dim loss carries the engine handle so `MetaOptimizer.step(loss)` can run the backward."""
     loss_kwargs = loss_kwargs or {}
-    if loss_sum.is_sum(loss_func):
-        return _compute_loss_sum(loss_func, outputs, gts, loss_kwargs)
-    base, _ = bootstrap.parse(loss_func)                   # (a bad spelling under the bootstrap prefix: NotImplementedError)
-    if base not in ('cross_entropy', 'dice', 'cross_entropy_and_dice', 'class_balanced_cross_entropy',
-                    'lovasz_hinge', 'lovasz_hinge_flat', bootstrap.NAME) and boundary.parse(loss_func)[0] not in boundary.KINDS:
-        raise NotImplementedError(f"loss_func='{loss_func}'")              # (a bad spelling under a boundary prefix too)
-    frac = {}
-    if loss_kwargs.get('fraction') is not None:            # the keyword form of bootstrapped_cross_entropy_<P>
-        resolve_loss(loss_func, loss_kwargs['fraction'])   # ValueError: another kind, out of (0, 1], or a suffix that disagrees
-        frac = {'fraction': loss_kwargs['fraction']}
-    if loss_kwargs.get('radius') is not None:              # the keyword form of boundary_f_<r>
-        resolve_loss(loss_func, radius=loss_kwargs['radius'])      # ValueError: another kind, out of 1 .. 16, or a suffix that disagrees
-        frac = dict(frac, radius=loss_kwargs['radius'])
-    if loss_func == 'lovasz_hinge' and not loss_kwargs.get('per_image', True):
-        loss_func = 'lovasz_hinge_flat'                    # loss_lovasz.py:89-90: the whole batch as one set
-    if loss_func == 'class_balanced_cross_entropy' and not loss_kwargs.get('size_average', True):
-        raise NotImplementedError('class_balanced_cross_entropy with size_average=False')
-    eng = getattr(outputs, '_eosvos_engine', None)
-    if eng is None:
-        raise RuntimeError('compute_loss needs logits produced by eosvos_amd.networks.DeepLabV3Plus '
-                           '(there is no CPU/eager path)')
-    gts = gts.contiguous().float()
-    ign = {'ignore': loss_kwargs['ignore']} if loss_kwargs.get('ignore') is not None else {}      # void label, every kind
-    if loss_kwargs.get('batch_average', True):
-        loss = eng.loss(loss_func, gts, **ign, **frac).view(())      # also leaves dL/dlogits in the engine
-        loss._eosvos_engine = eng
-        return loss
-    # per-sample values (run_loader metrics, helper_func.py:131-137): every loss evaluated sample by sample
-    return torch.cat([eng.loss_of(loss_func, outputs[b], gts[b], **ign, **frac) for b in range(outputs.shape[0])])
-
-
-def _compute_loss_sum(loss_func, outputs, gts, loss_kwargs):
-    """`compute_loss` for a sum spelling (`loss_sum.py`): the keywords go to the one term of their family."""
     per_image = loss_kwargs.get('per_image', True)
+    # a plain name is the sum of one term here (the engine still runs it as that one kind); unknown names and bad suffixes:
+    # NotImplementedError; a keyword without a term of its family, out of range or against a suffix: ValueError
     names = loss_sum.resolve(loss_func, loss_kwargs.get('fraction'), loss_kwargs.get('radius'), per_image)[2]
     if 'class_balanced_cross_entropy' in names and not loss_kwargs.get('size_average', True):
         raise NotImplementedError('class_balanced_cross_entropy with size_average=False')
@@ -85,6 +53,7 @@ def _compute_loss_sum(loss_func, outputs, gts, loss_kwargs):
         loss = eng.loss(loss_func, gts, **kw).view(())      # also leaves dL/dlogits in the engine
         loss._eosvos_engine = eng
         return loss
+    # per-sample values (run_loader metrics, helper_func.py:131-137): every loss evaluated sample by sample
     return torch.cat([eng.loss_of(loss_func, outputs[b], gts[b], **kw) for b in range(outputs.shape[0])])
 
 

@@ -1,0 +1,106 @@
+"""The spelling of one device loss: the name table, the `_<integer>` suffixes and what a name plus its keyword asks of the
+engine.  Host only and a leaf: importing this module needs neither torch nor the built library, and nothing else of the
+package.  `bootstrap.py`, `boundary.py` and `engine.py` re-export what callers know under their names; sums of names are
+`loss_sum.py`."""
+import math
+
+import numpy as np
+
+LOSS_KINDS = {'cross_entropy': 0, 'dice': 1, 'cross_entropy_and_dice': 2, 'class_balanced_cross_entropy': 3,
+              'lovasz_hinge': 4, 'lovasz_hinge_flat': 5,      # these two: networks/loss_lovasz.py:78-111, per_image True / False
+              'bootstrapped_cross_entropy': 6}                # the hardest fraction of the pixels per image (bootstrap.py)
+BOOTSTRAP = 'bootstrapped_cross_entropy'
+BOUNDARY_F = 'boundary_f'
+BOUNDARY_COMBINED = 'cross_entropy_and_boundary_f'
+# the kinds that need the frame's shape (include/eosvos.h; 7 stays unassigned)
+BOUNDARY_KINDS = {BOUNDARY_F: 8, BOUNDARY_COMBINED: 9}
+MAX_RADIUS = 16
+
+
+def parse_suffix(name, bases, hi):
+    """`<base>` -> (base, None); `<base>_<i>`, i an integer 1 .. hi without a leading zero -> (base, i), for the first of
+    `bases` the name starts with.  A name under no base is returned as (name, None); anything else under a base raises
+    NotImplementedError like an unknown loss name."""
+    if isinstance(name, str):
+        for base in bases:
+            if name.startswith(base):
+                rest = name[len(base):]
+                if rest == '':
+                    return base, None
+                digits = rest[1:]
+                if rest[0] != '_' or not digits.isascii() or not digits.isdigit() or digits[0] == '0' or not 1 <= int(digits) <= hi:
+                    raise NotImplementedError(f"loss_func='{name}'")
+                return base, int(digits)
+    return name, None
+
+
+def parse_bootstrap(name):
+    """`bootstrapped_cross_entropy` -> (NAME, None): the engine's fraction; `bootstrapped_cross_entropy_<P>`, P an integer
+    percent 1 .. 100 without a leading zero -> (NAME, P / 100).  A name that does not start with NAME is returned as
+    (name, None); anything else under the prefix raises NotImplementedError like an unknown loss name."""
+    base, percent = parse_suffix(name, (BOOTSTRAP,), 100)
+    return base, (None if percent is None else percent / 100.0)
+
+
+def parse_boundary(name):
+    """`boundary_f` / `cross_entropy_and_boundary_f` -> (name, None): the engine's radius; with `_<r>`, r an integer 1 .. 16
+    without a leading zero -> (base name, r).  A name under neither prefix is returned as (name, None); anything else under a
+    prefix raises NotImplementedError like an unknown loss name."""
+    return parse_suffix(name, (BOUNDARY_COMBINED, BOUNDARY_F), MAX_RADIUS)
+
+
+def check_fraction(fraction):
+    """The fraction as the float the library receives: in (0, 1]."""
+    f = float(np.float32(fraction))
+    if not (0.0 < f <= 1.0) or not (0.0 < float(fraction) <= 1.0):
+        raise ValueError(f'fraction={fraction!r}: the bootstrap fraction must be in (0, 1]')
+    return f
+
+
+def q_of(fraction):
+    """round(fraction * 65536) of the fp32 fraction (halves away from zero), clamped to [1, 65536]."""
+    return min(65536, max(1, int(math.floor(check_fraction(fraction) * 65536.0 + 0.5))))
+
+
+def check_radius(radius):
+    """The radius as the int the library receives: a whole number 1 .. 16."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or radius != radius or radius != int(radius) \
+            or not 1 <= int(radius) <= MAX_RADIUS:
+        raise ValueError(f'radius={radius!r}: the boundary radius must be a whole number in 1 .. {MAX_RADIUS}')
+    return int(radius)
+
+
+def resolve_loss(name, fraction=None, radius=None):
+    """A spelled loss name -> (kind id, fraction or None).  `bootstrapped_cross_entropy_<P>` carries P percent; `fraction`
+    is the keyword form, for that kind only; the two may not disagree.  None: the engine's current fraction stays.  A bad
+    spelling under the bootstrap prefix raises NotImplementedError, any other unknown name KeyError.  The kinds that need the
+    frame's shape (BOUNDARY_KINDS) are consulted after LOSS_KINDS and give (kind id, None); their radius, from the name
+    or `radius=`, is `resolve_radius`'s, which this call checks too."""
+    radius = resolve_radius(name, radius)
+    base, f = parse_bootstrap(name)
+    if base not in LOSS_KINDS and parse_boundary(name)[0] in BOUNDARY_KINDS:
+        if fraction is not None:
+            raise ValueError(f"fraction= belongs to '{BOOTSTRAP}', not to '{name}'")
+        return BOUNDARY_KINDS[parse_boundary(name)[0]], None
+    kind = LOSS_KINDS[base]
+    if fraction is not None:
+        if base != BOOTSTRAP:
+            raise ValueError(f"fraction= belongs to '{BOOTSTRAP}', not to '{name}'")
+        if f is not None and q_of(f) != q_of(fraction):
+            raise ValueError(f"loss_func='{name}' and fraction={fraction!r} disagree")
+        f = fraction
+    return kind, (None if f is None else check_fraction(f))
+
+
+def resolve_radius(name, radius=None):
+    """The window radius a spelled loss name asks for: `boundary_f_<r>` / `cross_entropy_and_boundary_f_<r>` carry r,
+    `radius` is the keyword form, for those kinds only; the two may not disagree.  None: the engine's current radius stays."""
+    base, r = parse_boundary(name)
+    if radius is not None:
+        if base not in BOUNDARY_KINDS:
+            raise ValueError(f"radius= belongs to {' / '.join(repr(k) for k in BOUNDARY_KINDS)}, not to '{name}'")
+        radius = check_radius(radius)
+        if r is not None and r != radius:
+            raise ValueError(f"loss_func='{name}' and radius={radius!r} disagree")
+        r = radius
+    return r

@@ -6,7 +6,8 @@ eosvos_set_loss_sum).  Host only; importing this module needs neither torch nor 
     term      := [weight '*'] name         name: any single spelling `compute_loss` accepts, suffixes included
     weight    := digits ['.' digits]       a plain decimal, no sign, no exponent, > 0; absent = 1
 
-A name with neither '+' nor '*' is not a sum and never comes here on its way to the engine.  With L_i / d_i the loss and the
+A name with neither '+' nor '*' is not a sum: `resolve` takes it as one term of weight 1, and the engine evaluates it by
+that kind's own launches, without the combine launch.  With L_i / d_i the loss and the
 gradient term i gives alone and w_i its weight as fp32, the sum is
     acc = w_0 * x_0;  acc = acc + w_i * x_i  (i = 1 .. n-1)         x = the loss value, and per element the gradient
 every product and every sum an fp32 operation rounded on its own, never a fused multiply-add, so `combine_host` reproduces
@@ -15,6 +16,8 @@ import re
 from fractions import Fraction
 
 import numpy as np
+
+from .loss_names import BOOTSTRAP, BOUNDARY_KINDS, parse_boundary, parse_bootstrap, resolve_loss, resolve_radius
 
 MAX_TERMS = 4                           # EOSVOS_LOSS_MAX_TERMS of include/eosvos.h
 _WEIGHT = re.compile(r'[0-9]+(\.[0-9]+)?\Z')
@@ -38,16 +41,10 @@ def _weight(literal):
     return float(best) if best > 0 else None
 
 
-def _term_kind(term):
-    """The kind id of one term's name; KeyError / NotImplementedError as `engine.resolve_loss` raises them."""
-    from .engine import resolve_loss
-    return resolve_loss(term)[0]
-
-
 def parse(name):
     """A spelled sum -> [(weight, term name), ...] in spelled order; a single name is the sum of one term of weight 1.  The
     weight is the fp32 value nearest to its literal, as a float.  The split happens before any term reaches `bootstrap.parse`
-    / `boundary.parse`; each term name is then checked by the existing resolvers.  Anything outside the grammar, an unknown
+    / `boundary.parse`; each term name is then checked by `loss_names.resolve_loss`.  Anything outside the grammar, an unknown
     term name and a bad suffix under a known prefix raise NotImplementedError like an unknown loss name."""
     bad = NotImplementedError(f"loss_func='{name}'")
     if not isinstance(name, str) or name == '' or any(c.isspace() for c in name):
@@ -64,7 +61,7 @@ def parse(name):
         if w is None or term == '' or '*' in weight:
             raise bad
         try:
-            _term_kind(term)
+            resolve_loss(term)
         except (KeyError, NotImplementedError):
             raise bad from None
         terms.append((w, term))
@@ -86,21 +83,19 @@ def resolve(name, fraction=None, radius=None, per_image=True):
     returned fraction / radius are what the name or the keyword carries (None: the engine's current value stays).  `per_image`
     False turns a `lovasz_hinge` term into `lovasz_hinge_flat`.  The same kind twice, or both boundary kinds (they share the
     engine's one radius), is a ValueError."""
-    from . import bootstrap, boundary
-    from .engine import resolve_loss, resolve_radius
     terms = [(w, 'lovasz_hinge_flat' if t == 'lovasz_hinge' and not per_image else t) for w, t in parse(name)]
     names = [t for _, t in terms]
     kinds = [resolve_loss(t)[0] for t in names]
     if len(set(kinds)) != len(kinds):
         raise ValueError(f"loss_func='{name}' names a loss twice")
-    boundary_terms = [t for t in names if boundary.parse(t)[0] in boundary.KINDS]
+    boundary_terms = [t for t in names if parse_boundary(t)[0] in BOUNDARY_KINDS]
     if len(boundary_terms) > 1:
         raise ValueError(f"loss_func='{name}' holds both boundary kinds; they share the engine's one radius")
-    bootstrap_terms = [t for t in names if bootstrap.parse(t)[0] == bootstrap.NAME]
+    bootstrap_terms = [t for t in names if parse_bootstrap(t)[0] == BOOTSTRAP]
     if fraction is not None and not bootstrap_terms:
-        raise ValueError(f"fraction= belongs to '{bootstrap.NAME}', which is no term of '{name}'")
+        raise ValueError(f"fraction= belongs to '{BOOTSTRAP}', which is no term of '{name}'")
     if radius is not None and not boundary_terms:
-        raise ValueError(f"radius= belongs to {' / '.join(repr(k) for k in boundary.KINDS)}, neither is a term of '{name}'")
+        raise ValueError(f"radius= belongs to {' / '.join(repr(k) for k in BOUNDARY_KINDS)}, neither is a term of '{name}'")
     f = resolve_loss(bootstrap_terms[0], fraction)[1] if bootstrap_terms else None
     r = resolve_radius(boundary_terms[0], radius) if boundary_terms else None
     return kinds, [w for w, _ in terms], names, f, r

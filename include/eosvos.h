@@ -173,7 +173,13 @@ int eosvos_restore_params(eosvos_engine* e);
 /* logits = model(images)[-1]  (deeplabv3plus.py:282-301); keeps activations for backward.
  * images: B x 3 x H x W, logits_out: B x 1 x H x W (may be NULL). */
 int eosvos_forward(eosvos_engine* e, const float* images, int batch, float* logits_out);
-/* Fused BCE-with-logits (mean over B*H*W, helper_func.py:32-37) of the last forward and
+/* The loss entry points below are forms of one evaluation.  On the last forward: eosvos_loss_bce, eosvos_loss,
+ * eosvos_loss_ignore and eosvos_loss_sum, which leave dL/dlogits for eosvos_backward_step -- and leave none when they return
+ * an error -- and which eosvos_finetune_step / eosvos_meta_grad* run with what eosvos_set_loss / eosvos_set_loss_sum /
+ * eosvos_set_loss_ignore stored.  On caller tensors: eosvos_bce, eosvos_loss_tensors, eosvos_loss_tensors_ignore and
+ * eosvos_loss_sum_tensors.  A form with a kind runs that kind's own launches and nothing else; a form with a term list
+ * runs each term into its slice and then the combine launch, for one term too.
+ * Fused BCE-with-logits (mean over B*H*W, helper_func.py:32-37) of the last forward and
  * its gradient.  loss_out: one device float (may be NULL). */
 int eosvos_loss_bce(eosvos_engine* e, const float* masks, int batch, float* loss_out);
 /* Same for the other losses of compute_loss (helper_func.py:28-56), batch_average=True:
@@ -252,6 +258,7 @@ int eosvos_set_loss_boundary(eosvos_engine* e, int radius);
  * dlogits_out or, when that is null, to the engine's own gradient scratch (a pending eosvos_loss* gradient is then lost). */
 int eosvos_boundary_f(eosvos_engine* e, const float* logits, const float* masks, int batch, int height, int width, int radius,
                       int combined, int ignore_on, float ignore, float* loss_out, float* dlogits_out);
+/* eosvos_loss_bce for any kind (the forms of one evaluation, see there). */
 int eosvos_loss(eosvos_engine* e, int kind, const float* masks, int batch, float* loss_out);
 /* The value of the last loss evaluated by eosvos_loss* / eosvos_finetune_step / eosvos_meta_grad*, copied to a DEVICE
  * float on the engine's stream without synchronising (several engines in flight on one GPU: concurrent meta tasks). */
@@ -312,11 +319,13 @@ int eosvos_set_loss_ignore(eosvos_engine* e, int on, float ignore);
 /* The sum becomes the loss of eosvos_finetune_step / eosvos_meta_grad[_ex]; eosvos_set_loss returns the engine to a single
  * kind, eosvos_set_loss_ignore applies to both.  Per engine, like eosvos_set_loss. */
 int eosvos_set_loss_sum(eosvos_engine* e, int n_terms, const int* kinds, const float* weights);
-/* The sum on the logits of the last forward (eosvos_loss's rules: the Lovasz hinge and the bootstrapped BCE per image, the
+/* The term-list form of eosvos_loss / eosvos_loss_ignore.
+ * The sum on the logits of the last forward (eosvos_loss's rules: the Lovasz hinge and the bootstrapped BCE per image, the
  * boundary kinds per frame); `ignore_on` selects the void label `ignore`.  Leaves dL/dlogits for eosvos_backward_step. */
 int eosvos_loss_sum(eosvos_engine* e, int n_terms, const int* kinds, const float* weights, const float* masks, int batch,
                     int ignore_on, float ignore, float* loss_out);
-/* The sum on n elements of caller tensors (DEVICE pointers), the n elements one set for every term as in eosvos_loss_tensors;
+/* The term-list form of eosvos_loss_tensors[_ignore].
+ * The sum on n elements of caller tensors (DEVICE pointers), the n elements one set for every term as in eosvos_loss_tensors;
  * n may not exceed the largest batch's pixels, and a boundary term accepts n == H * W only.  The gradient goes to dlogits_out
  * (any 4-byte alignment) or, when that is NULL, to the engine's own scratch (a pending loss gradient is then invalidated).
  * With one term of weight 1 this is that kind's value and gradient, bit for bit. */

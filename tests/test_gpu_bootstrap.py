@@ -21,6 +21,7 @@ import pytest
 import torch
 
 from eosvos_amd import bootstrap, synthetic
+from loss_common import dev, dlogits_of, dlogits_raw, masked_frames, poke_logits, void_mask
 
 pytestmark = pytest.mark.gpu
 
@@ -50,52 +51,6 @@ def eng(weights):
     e.forward(x.to(DEV), want_logits=False)
     yield e
     e.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def dlogits_of(e, n):
-    return e.debug_tensor('dlogits').reshape(-1)[:n].cpu().numpy()
-
-
-def dlogits_raw(e, n):
-    """The first n floats of the gradient buffer, also before any forward (debug_tensor reports one image then)."""
-    from eosvos_amd import _ffi
-    ptr, dims = ctypes.c_void_p(), (ctypes.c_int64 * 4)()
-    _ffi.check(e.lib.eosvos_debug_tensor(e.h, b'dlogits', ctypes.byref(ptr), dims))
-    out = torch.empty(n, device=DEV)
-    e.synchronize()
-    rc = ctypes.CDLL('libamdhip64.so').hipMemcpy(ctypes.c_void_p(out.data_ptr()), ptr, ctypes.c_size_t(n * 4), 3)
-    assert rc == 0
-    return out.cpu().numpy()
-
-
-def poke_logits(e, logits):
-    """Overwrite the engine's logits of the last forward with `logits` (a device tensor of lastB x H x W elements)."""
-    from eosvos_amd import _ffi
-    ptr, dims = ctypes.c_void_p(), (ctypes.c_int64 * 4)()
-    _ffi.check(e.lib.eosvos_debug_tensor(e.h, b'logits', ctypes.byref(ptr), dims))
-    assert logits.numel() == dims[0] * dims[1] * dims[2] * dims[3] and logits.is_contiguous()
-    e.synchronize()
-    torch.cuda.synchronize()
-    rc = ctypes.CDLL('libamdhip64.so').hipMemcpy(ptr, ctypes.c_void_p(logits.data_ptr()), ctypes.c_size_t(logits.numel() * 4), 3)
-    assert rc == 0
-
-
-def void_mask(n, pattern, rng):
-    v = np.zeros(n, dtype=bool)
-    if pattern == 'all':
-        v[:] = True
-    elif pattern == 'random30':
-        v = rng.rand(n) < 0.3
-    elif pattern == 'block':                    # one whole 256-element block and the first element of its neighbour
-        start = 256 if n > 513 else 0
-        v[start:start + 257] = True
-    elif pattern == 'last_valid':
-        v[:-1] = True
-    return v
 
 
 def make_case(n, pattern, seed):
@@ -342,18 +297,10 @@ def test_the_setter(eng, weights):
 
 
 # ---- integration ---------------------------------------------------------------------------------------------------------
-def masked_frames(seed):
-    x, y = synthetic.synthetic_frames(3, *SMALL, seed=seed)
-    void = torch.from_numpy(np.random.RandomState(seed).rand(*y.shape) < 0.3)
-    ym = y.clone()
-    ym[void] = IGN
-    return x.to(DEV), y.to(DEV), ym.to(DEV)
-
-
 @pytest.mark.parametrize('ign', [None, IGN])
 def test_fused_step_equals_the_separate_calls(eng, weights, ign):
     """set_loss('bootstrapped_cross_entropy_25', ignore=v) + finetune_step == forward -> loss -> backward_step, bit for bit."""
-    xd, yd, ym = masked_frames(4)
+    xd, yd, ym = masked_frames(4, SMALL, 0.3)
     masks = yd if ign is None else ym
     eng.load_model_state(*weights)
     eng.set_loss_bootstrap(0.5)                              # the suffix below must win over what the engine held
@@ -380,7 +327,7 @@ def test_fused_step_equals_the_separate_calls(eng, weights, ign):
 
 
 def test_meta_grad_and_the_matrix_mode_guard_run_under_the_kind(eng, weights):
-    xd, yd, ym = masked_frames(8)
+    xd, yd, ym = masked_frames(8, SMALL, 0.3)
     eng.load_model_state(*weights)
     eng.set_loss(NAME, ignore=IGN, fraction=0.25)
     try:
@@ -405,7 +352,7 @@ def test_meta_grad_and_the_matrix_mode_guard_run_under_the_kind(eng, weights):
 
 def test_compute_loss_keyword_equals_suffix(eng, weights):
     from eosvos_amd.helper_func import compute_loss
-    xd, yd, _ = masked_frames(12)
+    xd, yd, _ = masked_frames(12, SMALL, 0.3)
     eng.load_model_state(*weights)
     out = eng.forward(xd)
     out._eosvos_engine = eng

@@ -29,6 +29,7 @@ import torch
 import torch.nn.functional as F
 
 from eosvos_amd import boundary, synthetic
+from loss_common import dlogits_dev as dlogits_of, masked_frames, poke_logits
 
 pytestmark = pytest.mark.gpu
 
@@ -65,22 +66,6 @@ def eng(weights):
 
 def bits(t):
     return t.detach().cpu().contiguous().numpy().view(np.uint32)
-
-
-def dlogits_of(e, n):
-    return e.debug_tensor('dlogits').reshape(-1)[:n].clone()
-
-
-def poke_logits(e, logits):
-    """Overwrite the engine's logits of the last forward with `logits` (a device tensor of lastB x H x W elements)."""
-    from eosvos_amd import _ffi
-    ptr, dims = ctypes.c_void_p(), (ctypes.c_int64 * 4)()
-    _ffi.check(e.lib.eosvos_debug_tensor(e.h, b'logits', ctypes.byref(ptr), dims))
-    assert logits.numel() == dims[0] * dims[1] * dims[2] * dims[3] and logits.is_contiguous()
-    e.synchronize()
-    torch.cuda.synchronize()
-    rc = ctypes.CDLL('libamdhip64.so').hipMemcpy(ptr, ctypes.c_void_p(logits.data_ptr()), ctypes.c_size_t(logits.numel() * 4), 3)
-    assert rc == 0
 
 
 # ---- inputs --------------------------------------------------------------------------------------------------------------
@@ -393,18 +378,10 @@ def test_the_name_suffix_equals_the_keyword_and_the_tensor_entry_takes_one_frame
 
 
 # ---- integration ---------------------------------------------------------------------------------------------------------
-def masked_frames(seed):
-    x, y = synthetic.synthetic_frames(3, *FRAME, seed=seed)
-    void = torch.from_numpy(np.random.RandomState(seed).rand(*y.shape) < 0.1)
-    ym = y.clone()
-    ym[void] = IGN
-    return x.to(DEV), y.to(DEV), ym.to(DEV)
-
-
 @pytest.mark.parametrize('ign', [None, IGN])
 def test_fused_step_equals_the_separate_calls(eng, weights, ign):
     """set_loss('cross_entropy_and_boundary_f_2', ignore=v) + finetune_step == forward -> loss -> backward_step, bit for bit."""
-    xd, yd, ym = masked_frames(4)
+    xd, yd, ym = masked_frames(4, FRAME, 0.1)
     masks = yd if ign is None else ym
     eng.load_model_state(*weights)
     eng.set_loss_boundary(5)                                 # the suffix below must win over what the engine held
@@ -432,7 +409,7 @@ def test_fused_step_equals_the_separate_calls(eng, weights, ign):
 
 
 def test_meta_grad_and_the_matrix_mode_guard_run_under_the_kind(eng, weights):
-    xd, yd, ym = masked_frames(8)
+    xd, yd, ym = masked_frames(8, FRAME, 0.1)
     eng.load_model_state(*weights)
     eng.set_loss(N, ignore=IGN, radius=2)
     try:
@@ -458,7 +435,7 @@ def test_meta_grad_and_the_matrix_mode_guard_run_under_the_kind(eng, weights):
 
 def test_compute_loss_per_image_values(eng, weights):
     from eosvos_amd.helper_func import compute_loss
-    xd, yd, _ = masked_frames(12)
+    xd, yd, _ = masked_frames(12, FRAME, 0.1)
     eng.load_model_state(*weights)
     out = eng.forward(xd)
     out._eosvos_engine = eng

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import loss_ignore_ref as R
+from loss_common import dev, dlogits_of, masked_frames, poke_logits, void_mask
 from eosvos_amd import synthetic
 
 pytestmark = pytest.mark.gpu
@@ -47,40 +48,6 @@ def eng(weights):
     e.forward(x.to(DEV), want_logits=False)
     yield e
     e.close()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def dlogits_of(e, n):
-    return e.debug_tensor('dlogits').reshape(-1)[:n].cpu().numpy()
-
-
-def poke_logits(e, logits):
-    """Overwrite the engine's logits of the last forward with `logits` (a device tensor of lastB x H x W elements)."""
-    from eosvos_amd import _ffi
-    ptr, dims = ctypes.c_void_p(), (ctypes.c_int64 * 4)()
-    _ffi.check(e.lib.eosvos_debug_tensor(e.h, b'logits', ctypes.byref(ptr), dims))
-    assert logits.numel() == dims[0] * dims[1] * dims[2] * dims[3] and logits.is_contiguous()
-    e.synchronize()
-    torch.cuda.synchronize()
-    rc = ctypes.CDLL('libamdhip64.so').hipMemcpy(ptr, ctypes.c_void_p(logits.data_ptr()), ctypes.c_size_t(logits.numel() * 4), 3)
-    assert rc == 0
-
-
-def void_mask(n, pattern, rng):
-    v = np.zeros(n, dtype=bool)
-    if pattern == 'all':
-        v[:] = True
-    elif pattern == 'random30':
-        v = rng.rand(n) < 0.3
-    elif pattern == 'block':                    # one whole 256-element block and the first element of its neighbour
-        start = 256 if n > 513 else 0
-        v[start:start + 257] = True
-    elif pattern == 'last_valid':
-        v[:-1] = True
-    return v
 
 
 def make_case(n, pattern, seed):
@@ -260,18 +227,10 @@ def test_bad_ignore_is_rejected_by_the_library(eng, bad):
         eng.set_loss('dice', ignore=bad)
 
 
-def masked_frames(seed):
-    x, y = synthetic.synthetic_frames(3, *SMALL, seed=seed)
-    void = torch.from_numpy(np.random.RandomState(seed).rand(*y.shape) < 0.3)
-    ym = y.clone()
-    ym[void] = IGN
-    return x.to(DEV), y.to(DEV), ym.to(DEV)
-
-
 @pytest.mark.parametrize('kind', ['cross_entropy', 'dice', 'lovasz_hinge'])
 def test_fused_step_equals_the_separate_calls(eng, weights, kind):
     """set_loss(kind, ignore=v) + finetune_step == forward -> loss(kind, masks, ignore=v) -> backward_step, bit for bit."""
-    xd, _, ym = masked_frames(4)
+    xd, _, ym = masked_frames(4, SMALL, 0.3)
     eng.load_model_state(*weights)
     eng.set_loss(kind, ignore=IGN)
     try:
@@ -293,7 +252,7 @@ def test_fused_step_equals_the_separate_calls(eng, weights, kind):
 
 def test_the_fused_flag_is_live_and_off_by_default(eng, weights):
     """One BCE step with 30 % void differs from the same step without ignore; set_loss(name) alone turns it off again."""
-    xd, yd, ym = masked_frames(6)
+    xd, yd, ym = masked_frames(6, SMALL, 0.3)
     y0 = torch.where(ym == IGN, torch.zeros_like(ym), ym)               # the same targets with the void pixels as background
     got = {}
     for tag, ign, masks in (('ignore', IGN, ym), ('plain', None, y0), ('after', None, y0)):
@@ -318,7 +277,7 @@ def test_a_new_engine_and_an_aliasing_engine_do_not_take_the_void_label_over(eng
     """The flag is per engine and off by default: a second engine (what `spawn` builds) steps on void-labelled masks as the
     plain loss does, also while it aliases the state of an engine whose flag is on; that engine's own flag stays on."""
     from eosvos_amd.engine import Engine
-    xd, _, ym = masked_frames(10)
+    xd, _, ym = masked_frames(10, SMALL, 0.3)
     got = {}
     for tag, ign in (('on', IGN), ('off', None)):
         eng.load_model_state(*weights)
@@ -345,7 +304,7 @@ def test_a_new_engine_and_an_aliasing_engine_do_not_take_the_void_label_over(eng
 
 
 def test_meta_grad_runs_with_the_void_label(eng, weights):
-    xd, yd, ym = masked_frames(8)
+    xd, yd, ym = masked_frames(8, SMALL, 0.3)
     eng.load_model_state(*weights)
     eng.set_loss('dice', ignore=IGN)
     try:

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from eosvos_amd import loss_sum, synthetic
-from test_gpu_boundary import bits, dlogits_of, masked_frames, poke_logits  # noqa: E402
+from loss_common import dlogits_dev as dlogits_of, masked_frames, poke_logits
 
 pytestmark = pytest.mark.gpu
 
@@ -87,7 +87,7 @@ def check_sum_on_forward(e, spelled, masks, ign):
 @pytest.mark.parametrize('void', [False, True])
 @pytest.mark.parametrize('B', [1, 3])
 def test_the_sum_is_combine_host_of_its_terms(eng, B, void, spelled):
-    xd, yd, ym = masked_frames(5)
+    xd, yd, ym = masked_frames(5, FRAME, 0.1)
     masks = (ym if void else yd)[:B].contiguous()
     ign = IGN if void else None
     try:
@@ -103,7 +103,7 @@ def test_the_sum_is_combine_host_of_its_terms(eng, B, void, spelled):
 
 
 def test_a_nan_term_makes_the_sum_nan(eng):
-    xd, yd, _ = masked_frames(5)
+    xd, yd, _ = masked_frames(5, FRAME, 0.1)
     eng.forward(xd, want_logits=False)
     z = torch.randn(3, 1, *FRAME, generator=torch.Generator().manual_seed(3))
     z[1, 0, 7, 9] = float('nan')
@@ -153,7 +153,7 @@ def test_tails_and_an_unaligned_gradient_pointer(eng, n):
 
 # ---- 3. a single name goes where it went ------------------------------------------------------------------------------------
 def test_a_single_name_keeps_its_bits_and_twice_dice_is_twice_dice(eng):
-    xd, yd, ym = masked_frames(6)
+    xd, yd, ym = masked_frames(6, FRAME, 0.1)
     eng.forward(xd, want_logits=False)
     n = ym.numel()
     before = f32(eng.loss('dice', ym, ignore=IGN)), f32(dlogits_of(eng, n))
@@ -171,7 +171,7 @@ def test_a_single_name_keeps_its_bits_and_twice_dice_is_twice_dice(eng):
 def test_fused_step_equals_the_separate_calls(eng, weights, ign):
     """set_loss(sum, ignore=v) + finetune_step == forward -> loss(sum) -> backward_step, bit for bit; set_loss('dice') then
     leaves no trace of the sum."""
-    xd, yd, ym = masked_frames(4)
+    xd, yd, ym = masked_frames(4, FRAME, 0.1)
     masks = yd if ign is None else ym
     try:
         eng.load_model_state(*weights)
@@ -209,9 +209,42 @@ def test_fused_step_equals_the_separate_calls(eng, weights, ign):
     assert same_bits(fused[1], np.float32(w[0] * np.float32(fused_terms[0])) + np.float32(w[1] * np.float32(fused_terms[1])))
 
 
+def test_a_sum_that_was_set_leaves_no_trace_in_a_single_kind(eng, weights):
+    """set_loss('2*dice') then set_loss('dice'): the fused step has the bits of an engine that never saw a sum, and
+    last_loss_terms goes on reporting the last sum that was evaluated -- on an engine that evaluated none, it goes on raising."""
+    from eosvos_amd.engine import Engine
+    xd, yd, _ = masked_frames(10, FRAME, 0.1)
+    clean = Engine('resnet50', *FRAME, max_batch=3, device=DEV)
+    try:
+        got = []
+        for names in (('dice',), ('2*dice', 'dice')):
+            clean.load_model_state(*weights)
+            for name in names:
+                clean.set_loss(name)
+            got.append((clean.finetune_step(xd, yd), clean.get_params().clone()))
+            with pytest.raises(RuntimeError, match='no loss sum'):
+                clean.last_loss_terms()
+    finally:
+        clean.close()
+    try:
+        eng.load_model_state(*weights)
+        eng.forward(xd, want_logits=False)
+        eng.loss('2*dice', yd)
+        terms = eng.last_loss_terms()
+        eng.set_loss('2*dice')
+        eng.set_loss('dice')
+        got.append((eng.finetune_step(xd, yd), eng.get_params().clone()))
+        assert len(terms) == 1 and eng.last_loss_terms() == terms
+    finally:
+        eng.set_loss('cross_entropy')
+        eng.load_model_state(*weights)
+    for loss, params in got[1:]:
+        assert same_bits(loss, got[0][0]) and torch.equal(params, got[0][1])
+
+
 # ---- 5. meta_grad and the matrix-mode guard ---------------------------------------------------------------------------------
 def test_meta_grad_and_the_matrix_mode_guard_run_under_a_sum(eng, weights):
-    xd, yd, ym = masked_frames(8)
+    xd, yd, ym = masked_frames(8, FRAME, 0.1)
     try:
         eng.load_model_state(*weights)
         eng.set_loss(JF, ignore=IGN)
@@ -243,7 +276,7 @@ def test_meta_grad_and_the_matrix_mode_guard_run_under_a_sum(eng, weights):
 # ---- 6. compute_loss -------------------------------------------------------------------------------------------------------
 def test_compute_loss(eng, weights):
     from eosvos_amd.helper_func import compute_loss
-    xd, yd, ym = masked_frames(12)
+    xd, yd, ym = masked_frames(12, FRAME, 0.1)
     spelled = 'lovasz_hinge+0.3*boundary_f_3'
     try:
         eng.load_model_state(*weights)
@@ -278,7 +311,7 @@ def test_compute_loss(eng, weights):
 
 # ---- 7. failure is contained -----------------------------------------------------------------------------------------------
 def test_a_failed_term_fails_the_sum_and_nothing_else(eng):
-    xd, yd, _ = masked_frames(6)
+    xd, yd, _ = masked_frames(6, FRAME, 0.1)
     eng.forward(xd, want_logits=False)
     z, y = torch.randn(1000, device=DEV), (torch.rand(1000, device=DEV) < 0.5).float()
     with pytest.raises(RuntimeError, match='H \\* W'):
@@ -304,7 +337,7 @@ def test_a_failed_term_fails_the_sum_and_nothing_else(eng):
 
 # ---- 8. reproducible -------------------------------------------------------------------------------------------------------
 def test_two_evaluations_are_bit_identical_also_from_a_dirty_scratch(eng):
-    xd, _, ym = masked_frames(9)
+    xd, _, ym = masked_frames(9, FRAME, 0.1)
     eng.forward(xd, want_logits=False)
     n = ym.numel()
     try:

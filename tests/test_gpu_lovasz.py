@@ -8,7 +8,6 @@ non-negative terms is within log2(n) * 2^-24 = 1.2e-6; x8).  Against the referen
 stored distance to the restatement (it forms its weights by subtracting fp32 numbers near 1): loss within that distance
 + 1e-5 relative, gradient within twice that noise + 1e-6 of max |grad|.
 """
-import ctypes
 import json
 import os
 import subprocess
@@ -19,6 +18,7 @@ import pytest
 import torch
 
 import lovasz_ref
+from loss_common import dlogits_of, dlogits_raw, poke_logits  # noqa: F401  (the child process reads T.dlogits_raw)
 from eosvos_amd import synthetic, topology
 
 pytestmark = pytest.mark.gpu
@@ -82,22 +82,6 @@ def check(tag, loss, grad, ref_loss, ref_grad, margins=None):
     assert np.array_equal(grad != 0, nz), f'{tag}: the sets of non-zero gradient entries differ'
     assert rel <= GRAD_RTOL, (tag, rel)
     assert lrel <= LOSS_RTOL, (tag, loss, ref_loss)
-
-
-def dlogits_of(eng, n):
-    return eng.debug_tensor('dlogits').reshape(-1)[:n].cpu().numpy()
-
-
-def poke_logits(eng, logits):
-    """Overwrite the engine's logits of the last forward with `logits` (a device tensor of lastB x H x W elements)."""
-    ptr, dims = ctypes.c_void_p(), (ctypes.c_int64 * 4)()
-    from eosvos_amd import _ffi
-    _ffi.check(eng.lib.eosvos_debug_tensor(eng.h, b'logits', ctypes.byref(ptr), dims))
-    assert logits.numel() == dims[0] * dims[1] * dims[2] * dims[3] and logits.is_contiguous()
-    eng.synchronize()
-    torch.cuda.synchronize()
-    rc = ctypes.CDLL('libamdhip64.so').hipMemcpy(ptr, ctypes.c_void_p(logits.data_ptr()), ctypes.c_size_t(logits.numel() * 4), 3)
-    assert rc == 0
 
 
 @pytest.mark.parametrize('scale', [3.0, 80.0])
@@ -200,18 +184,6 @@ for kind, n in (('lovasz_hinge_flat', 3 * 96 * 160), ('lovasz_hinge', 96 * 160 -
     out[kind] = [int(loss.cpu().numpy().view(np.uint32)[0]), hashlib.sha256(ptr_grad.tobytes()).hexdigest()]
 print(json.dumps(out))
 '''
-
-
-def dlogits_raw(eng, n):
-    """dlogits before any forward (debug_tensor reports one image then): the first n floats of the buffer."""
-    from eosvos_amd import _ffi
-    ptr, dims = ctypes.c_void_p(), (ctypes.c_int64 * 4)()
-    _ffi.check(eng.lib.eosvos_debug_tensor(eng.h, b'dlogits', ctypes.byref(ptr), dims))
-    out = torch.empty(n, device=DEV)
-    eng.synchronize()
-    rc = ctypes.CDLL('libamdhip64.so').hipMemcpy(ctypes.c_void_p(out.data_ptr()), ptr, ctypes.c_size_t(n * 4), 3)
-    assert rc == 0
-    return out.cpu().numpy()
 
 
 def test_nan_filled_buffers_give_the_same_bits():
