@@ -230,6 +230,8 @@ struct eosvos_engine {
   int bootstrap_q = 16384;              // eosvos_set_loss_bootstrap: round(fraction * 65536), default 0.25
   float* boundary_scratch = nullptr;    // per-pixel maps and partials of the boundary-F kinds, allocated like lovasz_scratch
   int boundary_radius = 0;              // eosvos_set_loss_boundary: 1 .. 16, 0 = the frame-size default
+  float* surface_scratch = nullptr;     // distance words and partials of the surface loss, allocated like lovasz_scratch
+  int surface_cap = 0;                  // eosvos_set_loss_surface: 1 .. 4095, 0 = the frame-size default
   // weighted sums of kinds (eosvos_set_loss_sum / eosvos_loss_sum*): a gradient slice of maxB * H * W floats per term, allocated
   // when a sum first needs that many terms; sum_vals: the terms' values as evaluated [0, 4) and of the last whole sum [4, 8)
   float* sum_slice[EOSVOS_LOSS_MAX_TERMS] = {nullptr, nullptr, nullptr, nullptr};
@@ -2345,8 +2347,10 @@ namespace {
 inline bool lovasz_kind(int kind) { return kind == EOSVOS_LOSS_LOVASZ_HINGE || kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT; }
 inline bool bootstrap_kind(int kind) { return kind == EOSVOS_LOSS_BOOTSTRAPPED_BCE; }
 inline bool boundary_kind(int kind) { return kind == EOSVOS_LOSS_BOUNDARY_F || kind == EOSVOS_LOSS_BCE_AND_BOUNDARY_F; }
+inline bool surface_kind(int kind) { return kind == EOSVOS_LOSS_SURFACE; }
+inline bool frame_shape_kind(int kind) { return boundary_kind(kind) || surface_kind(kind); }   // an image is the engine's H x W
 // (7 is unassigned on purpose, see include/eosvos.h)
-inline bool loss_kind_ok(int kind) { return (kind >= EOSVOS_LOSS_BCE && kind <= EOSVOS_LOSS_BOOTSTRAPPED_BCE) || boundary_kind(kind); }
+inline bool loss_kind_ok(int kind) { return (kind >= EOSVOS_LOSS_BCE && kind <= EOSVOS_LOSS_BOOTSTRAPPED_BCE) || frame_shape_kind(kind); }
 // a void label (null: none) is a finite value no target can take; 0 when it is one
 int ignore_check(const float* v) {
   if (v && !(std::isfinite(*v) && (*v < 0.f || *v > 1.f))) return fail("the ignore label must be finite and outside [0, 1]");
@@ -2355,7 +2359,8 @@ int ignore_check(const float* v) {
 constexpr int PROP_MAX_FRAMES = 1024;
 // The scratch some kinds need beside the gradient, sized for the engine's largest batch and allocated when such a kind is
 // first selected or used: the Lovasz kinds' sort buffers, the bootstrapped BCE's histograms, state and partials (for maxB
-// sets; their size does not depend on the number of pixels), the boundary-F kinds' per-pixel maps and partials.
+// sets; their size does not depend on the number of pixels), the boundary-F kinds' per-pixel maps and partials, the surface
+// loss's distance words (4 bytes per pixel of the largest batch) and partials.
 const struct {
   bool (*uses)(int kind);
   float* eosvos_engine::*buf;
@@ -2377,6 +2382,10 @@ const struct {
      [](const eosvos_engine* e) { return (int64_t)boundary_scratch_floats((int64_t)e->maxB * e->H * e->W, e->maxB); },
      [](const eosvos_engine* e) { return (int64_t)e->H * e->W; }, (int64_t)1 << 31,
      "boundary_f: an image must have fewer than 2^31 pixels", "boundary_f: out of device memory for the boundary maps"},
+    {surface_kind, &eosvos_engine::surface_scratch,
+     [](const eosvos_engine* e) { return (int64_t)surface_scratch_floats((int64_t)e->maxB * e->H * e->W, e->maxB); },
+     [](const eosvos_engine* e) { return (int64_t)std::max(e->H, e->W); }, (int64_t)4097,
+     "surface: frames larger than 4096 pixels a side are not supported", "surface: out of device memory for the distance words"},
 };
 // the scratch of `kind`, if it needs one: called wherever a kind is about to be used or is selected; 0 on success
 int loss_scratch_ensure(eosvos_engine* e, int kind) {
@@ -2404,12 +2413,16 @@ void boundary_eval(eosvos_engine* e, bool combined, const float* logits, const f
   launch_boundary_f(logits, masks, dlogits, loss, e->boundary_scratch, H, W, images, radius ? radius : boundary_default_radius(H, W),
                     combined ? 1 : 0, ignore, e->s);
 }
+// max(1, min(H, W) / 4), at most 4095: a quarter of the frame's short side.  Untuned.
+inline int surface_default_cap(int H, int W) { return std::min(4095, std::max(1, std::min(H, W) / 4)); }
 // Loss `kind` (checked by the caller) of `images` maps of n_per_image pixels -- the Lovasz kinds: per map, or with `flat` over
 // all of them as one set -- with its gradient, into the device pointers loss / dlogits.  `ignore`: the void label, or null.
 int loss_eval(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n_per_image, int images, int flat,
               const float* ignore, float* dlogits, float* loss) {
   if (boundary_kind(kind) && n_per_image != (int64_t)e->H * e->W)      // needs the frame's shape: an image is the engine's H x W
     return fail("boundary_f: the loss needs the frame's shape, so n must be the engine's H * W (one image); use eosvos_boundary_f for another shape");
+  if (surface_kind(kind) && n_per_image != (int64_t)e->H * e->W)
+    return fail("surface: the loss needs the frame's shape, so n must be the engine's H * W (one image); use eosvos_surface_loss for another shape");
   if (loss_scratch_ensure(e, kind)) return 1;
   if (lovasz_kind(kind)) {
     launch_lovasz(logits, masks, dlogits, loss, e->lovasz_scratch, n_per_image, images, flat, ignore, e->s);
@@ -2419,6 +2432,9 @@ int loss_eval(eosvos_engine* e, int kind, const float* logits, const float* mask
                          flat ? 1 : images, e->bootstrap_q, ignore, e->s);
   } else if (boundary_kind(kind)) {
     boundary_eval(e, kind == EOSVOS_LOSS_BCE_AND_BOUNDARY_F, logits, masks, e->H, e->W, images, e->boundary_radius, ignore, dlogits, loss);
+  } else if (surface_kind(kind)) {
+    launch_surface(logits, masks, dlogits, loss, e->surface_scratch, e->H, e->W, images,
+                   e->surface_cap ? e->surface_cap : surface_default_cap(e->H, e->W), ignore, e->s);
   } else {
     launch_loss(kind, logits, masks, dlogits, loss, e->bce_partial, n_per_image * images, ignore, e->s);
   }
@@ -3261,6 +3277,48 @@ int eosvos_adapt_targets(eosvos_engine* e, const float* probs, const float* anch
                      scratch_at(e, L.eroded), scratch_at(e, L.count_e), scratch_at(e, L.n_pos), targets, e->s);
   HIPOK(hipGetLastError());
   return read_counts(e, L.n_pos, n_frames, n_pos);             // the round's one host read (32-bit counters on the device)
+}
+
+// ---- the surface loss on caller tensors of any frame shape, and its distance / weight maps -------------------------------
+static int surface_check(const char* who, int images, int height, int width, int cap, const float* ignore) {
+  const std::string w(who);
+  if (images < 1 || images > 65535) return fail(w + ": between 1 and 65535 images per call");
+  if (height < 1 || height > 4096 || width < 1 || width > 4096) return fail(w + ": frames of 1 .. 4096 pixels a side");
+  if (cap < 0 || cap > 4095) return fail(w + ": the cap must be 1 .. 4095, or 0 for the frame-size default");
+  return ignore_check(ignore);
+}
+int eosvos_set_loss_surface(eosvos_engine* e, int cap) {
+  if (!e) return fail("null engine");
+  if (cap < 0 || cap > 4095) return fail("the surface cap must be 1 .. 4095, or 0 for the frame-size default");
+  e->surface_cap = cap;
+  return 0;
+}
+int eosvos_surface_loss(eosvos_engine* e, const float* logits, const float* masks, int images, int height, int width, int cap,
+                        const float* ignore, float* loss_out, float* dlogits_out) {
+  if (!e || !logits || !masks || !loss_out) return fail("surface_loss: null argument");
+  if (surface_check("surface_loss", images, height, width, cap, ignore)) return 1;
+  const SurfaceLayout L(images, (size_t)images * height * width, 2 * SURFACE_BLOCKS + 1);
+  if (scratch_for(e, "surface_loss", L, images)) return 1;
+  const int l = cap ? cap : surface_default_cap(height, width);
+  launch_surface_distance(masks, images, height, width, l, ignore, scratch_at(e, L.g), (int32_t*)scratch_at(e, L.g), e->s);
+  launch_surface_loss(logits, masks, (const int32_t*)scratch_at(e, L.g), dlogits_out, loss_out, scratch_at(e, L.partial), height, width,
+                      images, l, ignore, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+int eosvos_surface_weights(eosvos_engine* e, const float* masks, int images, int height, int width, int cap, const float* ignore,
+                           int32_t* c_out, float* w_out) {
+  if (!e || !masks || (!c_out && !w_out)) return fail("surface_weights: null argument");
+  if (surface_check("surface_weights", images, height, width, cap, ignore)) return 1;
+  const size_t np = (size_t)images * height * width;
+  const SurfaceLayout L(images, np, 0);
+  if (scratch_for(e, "surface_weights", L, images)) return 1;
+  const int l = cap ? cap : surface_default_cap(height, width);
+  int32_t* const c = c_out ? c_out : (int32_t*)scratch_at(e, L.g);
+  launch_surface_distance(masks, images, height, width, l, ignore, scratch_at(e, L.g), c, e->s);
+  if (w_out) launch_surface_weights(c, w_out, (int64_t)np, l, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
 }
 
 int eosvos_meta_task_begin(eosvos_engine* e) {

@@ -474,6 +474,25 @@ constexpr int BOUNDARY_BLOCKS = 1024;            // cap of the grid per image (2
 int64_t boundary_scratch_floats(int64_t n_total, int max_images);
 void launch_boundary_f(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int H, int W, int images,
                        int radius, int add, const float* ignore, hipStream_t s);
+// Distance-weighted surface loss (surface_kernels.hip; the definition: include/eosvos.h at EOSVOS_LOSS_SURFACE): `images` maps
+// of H x W pixels (H, W <= 4096, images <= 65535), cap in [1, 4095].  No atomics, fixed-order sums: bit-reproducible.  Every
+// word of g, c and the partials that a launch reads is written by a launch before it.
+//   launch_surface_distance  2 launches: c [image][H][W] int32 = min(D^2 to the other class, cap^2 + 1), 0 at void pixels;
+//                            g: [image][H][W] 32-bit scratch, which c may alias
+//   launch_surface_weights   1 launch: w = (c > cap^2 ? cap : sqrt(c)) / cap over n elements
+//   launch_surface_loss      2 launches, 3 with dlogits: the mean over the images of sum_V w e / |V|, and its gradient;
+//                            partial: images * (2 * SURFACE_BLOCKS + 1) words
+//   launch_surface           all of it on one scratch of surface_scratch_floats(images * H * W, images) words: c over g, then
+//                            the partials
+constexpr int SURFACE_BLOCKS = 256;              // cap of the partial grid per image (256 threads each)
+int64_t surface_scratch_floats(int64_t n_total, int max_images);
+void launch_surface_distance(const float* gt, int images, int H, int W, int cap, const float* ignore, uint32_t* g, int32_t* c,
+                             hipStream_t s);
+void launch_surface_weights(const int32_t* c, float* w, int64_t n, int cap, hipStream_t s);
+void launch_surface_loss(const float* logits, const float* gt, const int32_t* c, float* dlogits, float* loss, float* partial, int H,
+                         int W, int images, int cap, const float* ignore, hipStream_t s);
+void launch_surface(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int H, int W, int images,
+                    int cap, const float* ignore, hipStream_t s);
 // Weighted sum of n_terms (1 .. EOSVOS_LOSS_MAX_TERMS) evaluated losses (misc_kernels.hip; the rule: include/eosvos.h at
 // eosvos_set_loss_sum): out[i] = w0 * g0[i] (+ w1 * g1[i] ...) over n elements, *loss the same expression of vals[0 .. n_terms),
 // which are copied unweighted to terms[0 .. n_terms).  grads / weights: host arrays; vals, out, loss, terms: device.  Every

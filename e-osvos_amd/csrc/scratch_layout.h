@@ -81,6 +81,14 @@ struct AdaptTargetsLayout : ScratchLayout {                    // only the count
   ScratchAt<uint8_t> eroded;
   AdaptTargetsLayout(size_t n, size_t np, bool erode) : n(n), np(np), eroded(take<uint8_t>("eroded", erode ? np : 0)) { clear(0, g.at); }
 };
+// n = images, np = their pixels: the 32-bit words of the two vertical-distance planes, which the capped distances overwrite
+// in place (first, so 16-byte aligned), then the partial sums, counts and per-image scales of the loss (partial_words per
+// image: 2 * SURFACE_BLOCKS + 1 of kernels.h); nothing needs clearing
+struct SurfaceLayout : ScratchLayout {
+  ScratchAt<uint32_t> g;
+  ScratchAt<float> partial;
+  SurfaceLayout(size_t n, size_t np, size_t partial_words) : g(take<uint32_t>("g", np)), partial(take<float>("partial", n * partial_words)) {}
+};
 struct LucidLayersLayout : ScratchLayout {                     // the visible-pixel counts [n][8 layers] start out as 0
   ScratchAt<int> counts;
   explicit LucidLayersLayout(size_t n) : counts(take<int>("counts", n * 8)) { clear(0, end); }

@@ -10,8 +10,8 @@ import functools
 
 import torch
 
-from . import _ffi, bootstrap, boundary, loss_sum
-from .loss_names import LOSS_KINDS, resolve_loss, resolve_radius  # noqa: F401  (their home; callers import them from here)
+from . import _ffi, bootstrap, boundary, loss_sum, surface
+from .loss_names import LOSS_KINDS, resolve_cap, resolve_loss, resolve_radius  # noqa: F401  (their home; callers import them from here)
 from .topology import ARCH_ID, norm_layers, trainable
 
 
@@ -67,24 +67,26 @@ def _touched(*tensors):
 
 LR_LEVELS = {'NEURON': 0, 'TENSOR': 1, 'SINGLE': 2, 'PARAM': 3}      # include/eosvos.h EOSVOS_LR_*
 # One resolved `loss_func`: the ctypes arrays of its n kinds and weights, whether the engine combines them (a spelling with
-# '+' or '*') or runs kinds[0]'s own launches alone, and the fraction / radius the spelling or its keyword carries (None: the
-# engine's current value stays).
-LossSpec = collections.namedtuple('LossSpec', 'n kinds weights combine fraction radius')
+# '+' or '*') or runs kinds[0]'s own launches alone, and the fraction / radius / cap the spelling or its keyword carries (None:
+# the engine's current value stays).
+LossSpec = collections.namedtuple('LossSpec', 'n kinds weights combine fraction radius cap')
 
 
 @functools.lru_cache(maxsize=64, typed=True)
-def _resolve(name, fraction, radius):
-    """A sum spelling (`loss_sum.resolve`) or a plain name (`resolve_loss` / `resolve_radius`, one term of weight 1) as a
+def _resolve(name, fraction, radius, cap=None):
+    """A sum spelling (`loss_sum.resolve`, `loss_sum.resolve_cap`) or a plain name (`resolve_loss` / `resolve_radius` /
+    `resolve_cap`, one term of weight 1) as a
     LossSpec, kept per spelling: splitting and checking one takes ~10 us on the host, which a loss whose launches take 30 us
     would otherwise pay on every evaluation (`profiles/loss_sum_time.txt`); a spelling that raises is not kept."""
     combine = loss_sum.is_sum(name)
     if combine:
         kinds, weights, _, f, r = loss_sum.resolve(name, fraction, radius)
+        c = loss_sum.resolve_cap(name, cap)
     else:
-        kind, f = resolve_loss(name, fraction, radius)
-        kinds, weights, r = [kind], [1.0], resolve_radius(name, radius)
+        kind, f = resolve_loss(name, fraction, radius, cap)
+        kinds, weights, r, c = [kind], [1.0], resolve_radius(name, radius), resolve_cap(name, cap)
     n = len(kinds)
-    return LossSpec(n, (ctypes.c_int * n)(*kinds), (ctypes.c_float * n)(*weights), combine, f, r)
+    return LossSpec(n, (ctypes.c_int * n)(*kinds), (ctypes.c_float * n)(*weights), combine, f, r, c)
 
 
 def check_ignore(ignore):
@@ -223,13 +225,14 @@ class Engine:
         self.lr_level, self.lr_log, self.n_lr_store = level, bool(use_log), n
         self.synchronize()
 
-    def set_loss(self, name, ignore=None, fraction=None, radius=None):
+    def set_loss(self, name, ignore=None, fraction=None, radius=None, cap=None):
         """Loss of finetune_step / meta_grad (`loss_func`, helper_func.py:28-56) and its void label (None: every pixel counts).
         `bootstrapped_cross_entropy_<P>` or `fraction=` also set the engine's bootstrap fraction, `boundary_f_<r>` /
-        `cross_entropy_and_boundary_f_<r>` or `radius=` its boundary radius (see `_loss_spec`).  A sum spelling
-        (`0.5*lovasz_hinge+boundary_f_4`, `loss_sum.py`) selects `eosvos_set_loss_sum`; a single name returns to one kind."""
+        `cross_entropy_and_boundary_f_<r>` or `radius=` its boundary radius, `surface_<L>` or `cap=` its surface cap (see
+        `_loss_spec`).  A sum spelling (`0.5*lovasz_hinge+boundary_f_4`, `loss_sum.py`) selects `eosvos_set_loss_sum`; a
+        single name returns to one kind."""
         try:
-            spec = self._loss_spec(name, fraction, radius)
+            spec = self._loss_spec(name, fraction, radius, cap)
         except KeyError:
             raise NotImplementedError(name) from None   # helper_func.py:55-56
         v = None if ignore is None else check_ignore(ignore)
@@ -251,10 +254,18 @@ class Engine:
         _ffi.check(self.lib.eosvos_set_loss_boundary(self.h, 0 if radius == 0 and not isinstance(radius, bool)
                                                      else boundary.check_radius(radius)))
 
-    def _loss_spec(self, name, fraction=None, radius=None):
-        """The LossSpec of a spelled `loss_func` (`_resolve`); a fraction or radius carried by the spelling or the keyword
+    def set_loss_surface(self, cap):
+        """The distance cap of `surface` for every later evaluation on this engine (`eosvos_set_loss_surface`): 1 .. 4095, or
+        0 for the frame-size default `surface.default_cap(H, W)`, which a new engine has.  The default is untuned."""
+        _ffi.check(self.lib.eosvos_set_loss_surface(self.h, 0 if cap == 0 and not isinstance(cap, bool)
+                                                    else surface.check_cap(cap)))
+
+    def _loss_spec(self, name, fraction=None, radius=None, cap=None):
+        """The LossSpec of a spelled `loss_func` (`_resolve`); a fraction, radius or cap carried by the spelling or the keyword
         becomes the engine's before the call that follows."""
-        spec = _resolve(name, fraction, radius)
+        spec = _resolve(name, fraction, radius, cap)
+        if spec.cap is not None:
+            self.set_loss_surface(spec.cap)
         if spec.fraction is not None:
             self.set_loss_bootstrap(spec.fraction)
         if spec.radius is not None:
@@ -503,12 +514,13 @@ class Engine:
             self._chk_masks, self._chk_kind, self._chk_ignore = masks, 'cross_entropy', None
         return loss
 
-    def loss(self, kind, masks, ignore=None, fraction=None, radius=None):
+    def loss(self, kind, masks, ignore=None, fraction=None, radius=None, cap=None):
         """kind: a compute_loss name (helper_func.py:28-56, see LOSS_KINDS); leaves dL/dlogits.  `ignore`: the void label --
         pixels whose mask equals it are in no sum, count or ranking and get gradient 0 (`eosvos_loss_ignore`).  `fraction`:
-        of `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, as in `set_loss`.  A sum spelling evaluates the
-        weighted sum of its terms (`eosvos_loss_sum`); `last_loss_terms` then gives the terms' own values."""
-        spec = self._loss_spec(kind, fraction, radius)
+        of `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, `cap`: of `surface`, as in `set_loss`.  A sum
+        spelling evaluates the weighted sum of its terms (`eosvos_loss_sum`); `last_loss_terms` then gives the terms' own
+        values."""
+        spec = self._loss_spec(kind, fraction, radius, cap)
         ignore = None if ignore is None else check_ignore(ignore)
         assert masks.is_cuda and masks.dtype == torch.float32 and masks.is_contiguous()
         out = torch.empty(1, device=self.device)
@@ -517,19 +529,20 @@ class Engine:
             self._chk_masks, self._chk_kind, self._chk_ignore = masks, kind, ignore
         return out
 
-    def loss_of(self, kind, logits, masks, ignore=None, fraction=None, radius=None):
+    def loss_of(self, kind, logits, masks, ignore=None, fraction=None, radius=None, cap=None):
         """Value of a compute_loss loss on arbitrary device tensors (one sample of a batch for
         `batch_average: False`); no gradient is kept.  `ignore`: as in `loss` (`eosvos_loss_tensors_ignore`); `fraction`: of
-        `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, as in `set_loss`.  The boundary kinds need the frame's
-        shape: they take one image of the engine's H * W elements only (`boundary_f` below takes any shape)."""
+        `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, `cap`: of `surface`, as in `set_loss`.  The boundary
+        kinds and `surface` need the frame's shape: they take one image of the engine's H * W elements only (`boundary_f` and
+        `surface_loss` below take any shape)."""
         logits, masks = logits.contiguous(), masks.contiguous()
         assert logits.is_cuda and masks.is_cuda and logits.numel() == masks.numel()
         out = torch.empty(1, device=self.device)
-        self._loss_on_tensors(self._loss_spec(kind, fraction, radius), logits, masks,
+        self._loss_on_tensors(self._loss_spec(kind, fraction, radius, cap), logits, masks,
                               None if ignore is None else check_ignore(ignore), out)
         return out
 
-    def loss_grad_of(self, name, logits, masks, ignore=None, fraction=None, radius=None):
+    def loss_grad_of(self, name, logits, masks, ignore=None, fraction=None, radius=None, cap=None):
         """(loss, dL/dlogits of the logits' shape) of a single kind or a sum on arbitrary device tensors, the elements one set
         as in `loss_of` (`eosvos_loss_sum_tensors`; a single kind is the sum of one term of weight 1, which has that kind's
         bits).  At most the engine's largest batch of pixels; the engine's own gradient is untouched."""
@@ -539,7 +552,7 @@ class Engine:
         v = None if ignore is None else check_ignore(ignore)
         out, grad = torch.empty(1, device=self.device), torch.empty_like(logits)
         try:
-            spec = self._loss_spec(name, fraction, radius)
+            spec = self._loss_spec(name, fraction, radius, cap)
         except KeyError:
             raise NotImplementedError(f"loss_func='{name}'") from None
         self._loss_on_tensors(spec, logits, masks, v, out, grad)
@@ -569,6 +582,34 @@ class Engine:
                                               0 if radius is None else boundary.check_radius(radius), int(bool(combined)),
                                               int(v is not None), v or 0.0, _ptr(out), _ptr(grad)))
         return out, grad
+
+    def _surface_args(self, masks, cap, ignore):
+        """(images, H, W, the cap as the library takes it, the void label as a ctypes pointer or None) of (B, H, W) / (H, W)."""
+        assert masks.is_cuda and masks.dtype == torch.float32 and masks.is_contiguous() and masks.dim() in (2, 3)
+        v = None if ignore is None else ctypes.byref(ctypes.c_float(check_ignore(ignore)))
+        return (masks.shape[0] if masks.dim() == 3 else 1, *masks.shape[-2:], 0 if cap is None else surface.check_cap(cap), v)
+
+    def surface_loss(self, logits, masks, cap=None, ignore=None):
+        """`surface` of device tensors (B, H, W) or (H, W) of any frame size up to 4096 a side (`eosvos_surface_loss`); `cap`
+        None: that shape's default `surface.default_cap(H, W)`.  Returns (loss, dL/dlogits of the logits' shape); the
+        engine's own gradient is untouched."""
+        self._check_stream()
+        logits, masks = logits.contiguous(), masks.contiguous()
+        assert logits.is_cuda and logits.dtype == torch.float32 and logits.shape == masks.shape
+        b, h, w, cap, v = self._surface_args(masks, cap, ignore)
+        out, grad = torch.empty(1, device=self.device), torch.empty_like(logits)
+        _ffi.check(self.lib.eosvos_surface_loss(self.h, _ptr(logits), _ptr(masks), b, h, w, cap, v, _ptr(out), _ptr(grad)))
+        return out, grad
+
+    def surface_weights(self, masks, cap=None, ignore=None):
+        """(c, w) of rules 1 and 2 of `surface.py` for device targets (B, H, W) or (H, W) (`eosvos_surface_weights`): the capped
+        squared distances to the other class as int32 and the weights as float32, of the targets' shape."""
+        self._check_stream()
+        masks = masks.contiguous()
+        b, h, w, cap, v = self._surface_args(masks, cap, ignore)
+        c, wt = torch.empty(masks.shape, dtype=torch.int32, device=self.device), torch.empty_like(masks)
+        _ffi.check(self.lib.eosvos_surface_weights(self.h, _ptr(masks), b, h, w, cap, v, _ptr(c), _ptr(wt)))
+        return c, wt
 
     def propagation_targets(self, probs, lo, hi, ignore, counts=True):
         """Pseudo-label targets of online adaptation with an uncertainty band (`eosvos_propagation_targets`): probs (F, ...)

@@ -18,6 +18,9 @@ pixels: the engine's fraction (0.25 by default), `bootstrapped_cross_entropy_<P>
 `boundary_f` / `cross_entropy_and_boundary_f` (`boundary.py`; not in the reference) are the soft boundary-F loss and its sum
 with `cross_entropy`: the engine's window radius (by default the DAVIS tolerance of the frame size), `boundary_f_<r>` for
 r pixels, or `loss_kwargs={'radius': r}`.
+`surface` (`surface.py`; not in the reference) weights every pixel's error by its distance to the target's boundary, capped at
+the engine's cap (by default a quarter of the frame's short side, untuned), `surface_<L>` for L pixels, or
+`loss_kwargs={'cap': L}`; it is meant as a term of a sum, e.g. `dice+0.5*surface_64`.
 A `loss_func` with a '+' or a '*' is a weighted sum of up to four of these (`loss_sum.py`), e.g. `0.5*lovasz_hinge+boundary_f_4`.
 """
 import random
@@ -39,6 +42,7 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
     # a plain name is the sum of one term here (the engine still runs it as that one kind); unknown names and bad suffixes:
     # NotImplementedError; a keyword without a term of its family, out of range or against a suffix: ValueError
     names = loss_sum.resolve(loss_func, loss_kwargs.get('fraction'), loss_kwargs.get('radius'), per_image)[2]
+    loss_sum.resolve_cap(loss_func, loss_kwargs.get('cap'))
     if 'class_balanced_cross_entropy' in names and not loss_kwargs.get('size_average', True):
         raise NotImplementedError('class_balanced_cross_entropy with size_average=False')
     if not per_image:
@@ -48,7 +52,7 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
         raise RuntimeError('compute_loss needs logits produced by eosvos_amd.networks.DeepLabV3Plus '
                            '(there is no CPU/eager path)')
     gts = gts.contiguous().float()
-    kw = {k: loss_kwargs[k] for k in ('ignore', 'fraction', 'radius') if loss_kwargs.get(k) is not None}
+    kw = {k: loss_kwargs[k] for k in ('ignore', 'fraction', 'radius', 'cap') if loss_kwargs.get(k) is not None}
     if loss_kwargs.get('batch_average', True):
         loss = eng.loss(loss_func, gts, **kw).view(())      # also leaves dL/dlogits in the engine
         loss._eosvos_engine = eng

@@ -15,6 +15,10 @@ BOUNDARY_COMBINED = 'cross_entropy_and_boundary_f'
 # the kinds that need the frame's shape (include/eosvos.h; 7 stays unassigned)
 BOUNDARY_KINDS = {BOUNDARY_F: 8, BOUNDARY_COMBINED: 9}
 MAX_RADIUS = 16
+SURFACE = 'surface'
+# the distance-weighted surface loss (surface.py); it needs the frame's shape too.  A third table: the two above stay as they are
+SURFACE_KINDS = {SURFACE: 10}
+MAX_CAP = 4095
 
 
 def parse_suffix(name, bases, hi):
@@ -49,6 +53,13 @@ def parse_boundary(name):
     return parse_suffix(name, (BOUNDARY_COMBINED, BOUNDARY_F), MAX_RADIUS)
 
 
+def parse_surface(name):
+    """`surface` -> (name, None): the engine's cap; `surface_<L>`, L an integer 1 .. 4095 without a leading zero -> (name, L).
+    A name that does not start with `surface` is returned as (name, None); anything else under the prefix raises
+    NotImplementedError like an unknown loss name."""
+    return parse_suffix(name, (SURFACE,), MAX_CAP)
+
+
 def check_fraction(fraction):
     """The fraction as the float the library receives: in (0, 1]."""
     f = float(np.float32(fraction))
@@ -70,18 +81,32 @@ def check_radius(radius):
     return int(radius)
 
 
-def resolve_loss(name, fraction=None, radius=None):
+def check_cap(cap):
+    """The cap as the int the library receives: a whole number 1 .. 4095."""
+    if isinstance(cap, bool) or not isinstance(cap, (int, float)) or not math.isfinite(cap) or cap != int(cap) \
+            or not 1 <= int(cap) <= MAX_CAP:
+        raise ValueError(f'cap={cap!r}: the surface cap must be a whole number in 1 .. {MAX_CAP}')
+    return int(cap)
+
+
+def resolve_loss(name, fraction=None, radius=None, cap=None):
     """A spelled loss name -> (kind id, fraction or None).  `bootstrapped_cross_entropy_<P>` carries P percent; `fraction`
     is the keyword form, for that kind only; the two may not disagree.  None: the engine's current fraction stays.  A bad
     spelling under the bootstrap prefix raises NotImplementedError, any other unknown name KeyError.  The kinds that need the
     frame's shape (BOUNDARY_KINDS) are consulted after LOSS_KINDS and give (kind id, None); their radius, from the name
-    or `radius=`, is `resolve_radius`'s, which this call checks too."""
+    or `radius=`, is `resolve_radius`'s, which this call checks too.  SURFACE_KINDS is consulted last, in the same way, its cap
+    (`resolve_cap`) checked here too."""
     radius = resolve_radius(name, radius)
+    cap = resolve_cap(name, cap)
     base, f = parse_bootstrap(name)
     if base not in LOSS_KINDS and parse_boundary(name)[0] in BOUNDARY_KINDS:
         if fraction is not None:
             raise ValueError(f"fraction= belongs to '{BOOTSTRAP}', not to '{name}'")
         return BOUNDARY_KINDS[parse_boundary(name)[0]], None
+    if base not in LOSS_KINDS and parse_surface(name)[0] in SURFACE_KINDS:
+        if fraction is not None:
+            raise ValueError(f"fraction= belongs to '{BOOTSTRAP}', not to '{name}'")
+        return SURFACE_KINDS[parse_surface(name)[0]], None
     kind = LOSS_KINDS[base]
     if fraction is not None:
         if base != BOOTSTRAP:
@@ -104,3 +129,17 @@ def resolve_radius(name, radius=None):
             raise ValueError(f"loss_func='{name}' and radius={radius!r} disagree")
         r = radius
     return r
+
+
+def resolve_cap(name, cap=None):
+    """The distance cap a spelled loss name asks for: `surface_<L>` carries L, `cap` is the keyword form, for that kind only; the
+    two may not disagree.  None: the engine's current cap stays."""
+    base, c = parse_surface(name)
+    if cap is not None:
+        if base not in SURFACE_KINDS:
+            raise ValueError(f"cap= belongs to '{SURFACE}', not to '{name}'")
+        cap = check_cap(cap)
+        if c is not None and c != cap:
+            raise ValueError(f"loss_func='{name}' and cap={cap!r} disagree")
+        c = cap
+    return c

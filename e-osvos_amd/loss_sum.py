@@ -17,7 +17,9 @@ from fractions import Fraction
 
 import numpy as np
 
-from .loss_names import BOOTSTRAP, BOUNDARY_KINDS, parse_boundary, parse_bootstrap, resolve_loss, resolve_radius
+from .loss_names import (BOOTSTRAP, BOUNDARY_KINDS, SURFACE, SURFACE_KINDS, parse_boundary, parse_bootstrap, parse_surface,
+                         resolve_loss, resolve_radius)
+from .loss_names import resolve_cap as _term_cap
 
 MAX_TERMS = 4                           # EOSVOS_LOSS_MAX_TERMS of include/eosvos.h
 _WEIGHT = re.compile(r'[0-9]+(\.[0-9]+)?\Z')
@@ -99,6 +101,18 @@ def resolve(name, fraction=None, radius=None, per_image=True):
     f = resolve_loss(bootstrap_terms[0], fraction)[1] if bootstrap_terms else None
     r = resolve_radius(boundary_terms[0], radius) if boundary_terms else None
     return kinds, [w for w, _ in terms], names, f, r
+
+
+def resolve_cap(name, cap=None):
+    """The distance cap a spelled sum (or single name) carries, or None: `cap` belongs to the one `surface` term, as `fraction`
+    and `radius` belong to theirs in `resolve`: without such a term, or against a disagreeing suffix, ValueError; the term named
+    twice is a ValueError too.  A `surface` term beside a boundary kind is allowed: the cap and the radius are separate."""
+    surface_terms = [t for _, t in parse(name) if parse_surface(t)[0] in SURFACE_KINDS]
+    if len(surface_terms) > 1:
+        raise ValueError(f"loss_func='{name}' names a loss twice")
+    if cap is not None and not surface_terms:
+        raise ValueError(f"cap= belongs to '{SURFACE}', which is no term of '{name}'")
+    return _term_cap(surface_terms[0], cap) if surface_terms else None
 
 
 def combine_host(values, grads, weights):

@@ -258,6 +258,41 @@ int eosvos_set_loss_boundary(eosvos_engine* e, int radius);
  * dlogits_out or, when that is null, to the engine's own gradient scratch (a pending eosvos_loss* gradient is then lost). */
 int eosvos_boundary_f(eosvos_engine* e, const float* logits, const float* masks, int batch, int height, int width, int radius,
                       int combined, int ignore_on, float ignore, float* loss_out, float* dlogits_out);
+/* Distance-weighted surface loss, `surface`: every pixel's error weighted by its distance to the target's boundary (Kervadec
+ * et al., "Boundary loss for highly unbalanced segmentation", MIDL 2019).  Not in the reference.  Meant as a term beside a
+ * region loss (`dice+0.5*surface_64`).  Per image of H x W pixels, z the logits, y the targets, v the void label:
+ *   V = {y != v};  F = {i in V : y_i >= 0.5};  B = V \ F.  A void pixel is in neither set and never a source of a distance.
+ *   1. D2_i = the least dy^2 + dx^2 to a pixel of the OTHER class (B for i in F, F for i in B), infinite if that class is
+ *      empty;  c_i = min(D2_i, L^2 + 1) as int32, the capped form of eosvos_distance_sq;  c_i = 0 at a void pixel.
+ *   2. d_i = L if c_i > L^2, else sqrt(float(c_i));  w_i = d_i / float(L), in (0, 1] on V: correctly rounded IEEE fp32
+ *      operations, so the numpy float32 expression reproduces w bit for bit.
+ *   3. p = sigmoid(z);  e_i = 1 - p_i on F, p_i on B;  image loss = sum_V w e / |V|, 0 without a valid pixel;  loss = the mean
+ *      over the images.  It is Kervadec's sum p phi up to a constant that makes it >= 0, and 0 for a perfect prediction.  An empty
+ *      (or full) target gives w = 1 everywhere: the mean foreground (background) probability, no special case.
+ *   4. dL/dz_i = s_i w_i p_i (1 - p_i) / (|V| images), s = -1 on F and +1 on B; exactly +0 at a void pixel, whose logit never
+ *      reaches the result.
+ * The cap L is per engine (eosvos_set_loss_surface), a whole number of pixels in [1, 4095]; by default max(1, min(H, W) / 4)
+ * (integer division), 120 at 480 x 854.  It is untuned: no J&F figure exists for it.  The kind needs the frame's shape, as the
+ * boundary kinds do: through eosvos_loss* and the fused entry points an image is the engine's H x W; eosvos_loss_tensors* accept
+ * n == H * W only, as one image; frames of at most 4096 pixels a side.  Five launches (the two passes of the transform, the
+ * partial sums, their fixed-order reduction, the gradient), no atomics: loss and gradient are bit-identical from run to run.
+ * The first use allocates a scratch of 4 bytes per pixel of the engine's largest batch (plus 2 KB per image) once; a failed
+ * allocation is reported and leaves the engine usable with the other kinds. */
+#define EOSVOS_LOSS_SURFACE 10
+/* The cap of EOSVOS_LOSS_SURFACE for every evaluation on this engine: 1 .. 4095, or 0 for the frame-size default; anything
+ * else is an error and changes nothing.  Per engine, like the boundary radius. */
+int eosvos_set_loss_surface(eosvos_engine* e, int cap);
+/* The surface loss on caller tensors with an explicit shape: `images` (1 .. 65535) maps of height x width, each side in
+ * [1, 4096], DEVICE pointers.  cap 1 .. 4095, or 0 for this shape's default; `ignore`: null, or a HOST pointer to the void
+ * label.  The loss goes to loss_out (a device float), the gradient to dlogits_out, which may be null (none is formed).  The
+ * scratch (4 bytes per pixel) comes from the arena of the evaluation-stage entry points, under its 512 MB cap per call.  Bad
+ * arguments return non-zero before any launch: the outputs stay untouched. */
+int eosvos_surface_loss(eosvos_engine* e, const float* logits, const float* masks, int images, int height, int width, int cap,
+                        const float* ignore, float* loss_out, float* dlogits_out);
+/* Rules 1 and 2 alone, with the arguments and limits of eosvos_surface_loss: c_out [image][H][W] int32 and / or w_out
+ * [image][H][W] fp32, DEVICE pointers; either may be null, not both. */
+int eosvos_surface_weights(eosvos_engine* e, const float* masks, int images, int height, int width, int cap, const float* ignore,
+                           int32_t* c_out, float* w_out);
 /* eosvos_loss_bce for any kind (the forms of one evaluation, see there). */
 int eosvos_loss(eosvos_engine* e, int kind, const float* masks, int batch, float* loss_out);
 /* The value of the last loss evaluated by eosvos_loss* / eosvos_finetune_step / eosvos_meta_grad*, copied to a DEVICE
