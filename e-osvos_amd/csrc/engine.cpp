@@ -232,6 +232,10 @@ struct eosvos_engine {
   int boundary_radius = 0;              // eosvos_set_loss_boundary: 1 .. 16, 0 = the frame-size default
   float* surface_scratch = nullptr;     // distance words and partials of the surface loss, allocated like lovasz_scratch
   int surface_cap = 0;                  // eosvos_set_loss_surface: 1 .. 4095, 0 = the frame-size default
+  // eosvos_set_loss_potts: the pairwise loss's window radius, dilation and sigmas, 0 = the default (3, 2, radius * dilation, 0.1);
+  // it has no buffer of its own: its partials live in the scratch arena, its frames are xpad
+  int potts_window = 0, potts_dilation = 0;
+  float potts_sigma_xy = 0.f, potts_sigma_rgb = 0.f;
   // weighted sums of kinds (eosvos_set_loss_sum / eosvos_loss_sum*): a gradient slice of maxB * H * W floats per term, allocated
   // when a sum first needs that many terms; sum_vals: the terms' values as evaluated [0, 4) and of the last whole sum [4, 8)
   float* sum_slice[EOSVOS_LOSS_MAX_TERMS] = {nullptr, nullptr, nullptr, nullptr};
@@ -2343,14 +2347,18 @@ int eosvos_forward(eosvos_engine* e, const float* images, int batch, float* logi
     HIPOK(hipMemcpyAsync(logits_out, e->logits, (size_t)batch * e->H * e->W * 4, hipMemcpyDeviceToDevice, e->s));
   return 0;
 }
+static int scratch_for(eosvos_engine* e, const char* who, const ScratchLayout& L, int n_frames, bool capped);   // the arena, below
 namespace {
 inline bool lovasz_kind(int kind) { return kind == EOSVOS_LOSS_LOVASZ_HINGE || kind == EOSVOS_LOSS_LOVASZ_HINGE_FLAT; }
 inline bool bootstrap_kind(int kind) { return kind == EOSVOS_LOSS_BOOTSTRAPPED_BCE; }
 inline bool boundary_kind(int kind) { return kind == EOSVOS_LOSS_BOUNDARY_F || kind == EOSVOS_LOSS_BCE_AND_BOUNDARY_F; }
 inline bool surface_kind(int kind) { return kind == EOSVOS_LOSS_SURFACE; }
 inline bool frame_shape_kind(int kind) { return boundary_kind(kind) || surface_kind(kind); }   // an image is the engine's H x W
-// (7 is unassigned on purpose, see include/eosvos.h)
-inline bool loss_kind_ok(int kind) { return (kind >= EOSVOS_LOSS_BCE && kind <= EOSVOS_LOSS_BOOTSTRAPPED_BCE) || frame_shape_kind(kind); }
+inline bool potts_kind(int kind) { return kind == EOSVOS_LOSS_POTTS; }                         // ... and reads the last forward's frames
+// (7 and 11 are unassigned on purpose, see include/eosvos.h)
+inline bool loss_kind_ok(int kind) {
+  return (kind >= EOSVOS_LOSS_BCE && kind <= EOSVOS_LOSS_BOOTSTRAPPED_BCE) || frame_shape_kind(kind) || potts_kind(kind);
+}
 // a void label (null: none) is a finite value no target can take; 0 when it is one
 int ignore_check(const float* v) {
   if (v && !(std::isfinite(*v) && (*v < 0.f || *v > 1.f))) return fail("the ignore label must be finite and outside [0, 1]");
@@ -2415,6 +2423,29 @@ void boundary_eval(eosvos_engine* e, bool combined, const float* logits, const f
 }
 // max(1, min(H, W) / 4), at most 4095: a quarter of the frame's short side.  Untuned.
 inline int surface_default_cap(int H, int W) { return std::min(4095, std::max(1, std::min(H, W) / 4)); }
+// The pairwise loss's window and sigmas with 0 read as the default (radius 3, dilation 2, sigma_xy = radius * dilation,
+// sigma_rgb 0.1; untuned), checked against the CRF's limits; 0 on success
+struct PottsParams { int r, d; float sigma_xy, sigma_rgb; };
+int potts_params(const char* who, int window, int dilation, float sigma_xy, float sigma_rgb, PottsParams* out) {
+  const std::string w(who);
+  if (window < 0 || window > 7) return fail(w + ": the window radius must be 1 .. 7, or 0 for the default");
+  if (dilation < 0 || dilation > 4) return fail(w + ": the dilation must be 1 .. 4, or 0 for the default");
+  const int r = window ? window : 3, d = dilation ? dilation : 2;
+  if (r * d > 16) return fail(w + ": window radius * dilation must be at most 16");
+  if (!(std::isfinite(sigma_xy) && sigma_xy >= 0.f)) return fail(w + ": sigma_xy must be finite and > 0, or 0 for the default");
+  if (!(std::isfinite(sigma_rgb) && sigma_rgb >= 0.f)) return fail(w + ": sigma_rgb must be finite and > 0, or 0 for the default");
+  if (out) *out = {r, d, sigma_xy > 0.f ? sigma_xy : (float)(r * d), sigma_rgb > 0.f ? sigma_rgb : 0.1f};
+  return 0;
+}
+// the pairwise loss of `images` maps of H x W logits against `frames` (launch_potts's two layouts), its partials in the arena
+int potts_eval(eosvos_engine* e, const char* who, const PottsParams& q, const float* logits, const float* frames, int pad, int H, int W,
+               int images, float* dlogits, float* loss) {
+  const PottsLayout L((size_t)potts_scratch_floats(H, W, images));
+  if (scratch_for(e, who, L, images, true)) return 1;
+  launch_potts(logits, frames, pad, dlogits, loss, (float*)((char*)e->scratch + L.partial.at), H, W, images, q.r, q.d, q.sigma_xy,
+               q.sigma_rgb, e->s);
+  return 0;
+}
 // Loss `kind` (checked by the caller) of `images` maps of n_per_image pixels -- the Lovasz kinds: per map, or with `flat` over
 // all of them as one set -- with its gradient, into the device pointers loss / dlogits.  `ignore`: the void label, or null.
 int loss_eval(eosvos_engine* e, int kind, const float* logits, const float* masks, int64_t n_per_image, int images, int flat,
@@ -2423,6 +2454,15 @@ int loss_eval(eosvos_engine* e, int kind, const float* logits, const float* mask
     return fail("boundary_f: the loss needs the frame's shape, so n must be the engine's H * W (one image); use eosvos_boundary_f for another shape");
   if (surface_kind(kind) && n_per_image != (int64_t)e->H * e->W)
     return fail("surface: the loss needs the frame's shape, so n must be the engine's H * W (one image); use eosvos_surface_loss for another shape");
+  if (potts_kind(kind)) {                // on the logits of the last forward only: its frames are the engine's copy of that forward's
+    PottsParams q;
+    if (logits != e->logits || e->lastB < 1 || images > e->lastB || n_per_image != (int64_t)e->H * e->W)
+      return fail("potts: the loss reads the frames of the last forward; use eosvos_potts_loss (Engine.potts_loss) for caller tensors");
+    if (potts_params("potts", e->potts_window, e->potts_dilation, e->potts_sigma_xy, e->potts_sigma_rgb, &q)) return 1;
+    if (potts_eval(e, "potts", q, logits, e->xpad, 3, e->H, e->W, images, dlogits, loss)) return 1;
+    HIPOK(hipGetLastError());
+    return 0;
+  }
   if (loss_scratch_ensure(e, kind)) return 1;
   if (lovasz_kind(kind)) {
     launch_lovasz(logits, masks, dlogits, loss, e->lovasz_scratch, n_per_image, images, flat, ignore, e->s);
@@ -2496,10 +2536,19 @@ int loss_spec_eval(eosvos_engine* e, const LossSpec& spec, const float* logits, 
   e->sum_last_terms = spec.n;
   return 0;
 }
+inline bool spec_has_potts(const LossSpec& spec) {
+  for (int i = 0; i < spec.n && i < EOSVOS_LOSS_MAX_TERMS; ++i)
+    if (potts_kind(spec.kinds[i])) return true;
+  return false;
+}
 // on the logits of the last forward: leaves dL/dlogits for eosvos_backward_step, and none after a failed evaluation
 int loss_on_forward(eosvos_engine* e, const LossSpec& spec, const float* masks, int batch, const float* ignore, float* loss_out) {
   if (!e || !masks) return fail("null argument");
   if (loss_spec_ok(spec) || ignore_check(ignore)) return 1;
+  if (e->lastB < 1 && spec_has_potts(spec)) {
+    e->have_loss_grad = false;
+    return fail("potts: the loss reads the frames of the last forward, and there has been none on this engine");
+  }
   if (batch != e->lastB) return fail("loss batch differs from the last forward");
   e->have_loss_grad = false;
   if (loss_spec_eval(e, spec, e->logits, masks, (int64_t)e->H * e->W, batch, false, ignore, e->dlogits, e->loss_dev)) return 1;
@@ -2519,6 +2568,8 @@ int loss_on_tensors(eosvos_engine* e, const LossSpec& spec, const float* logits,
                     float* loss_out, float* dlogits_out) {
   if (!e || !logits || !masks || !loss_out || n < 1) return fail("bad argument");
   if (loss_spec_ok(spec) || ignore_check(ignore)) return 1;
+  if (spec_has_potts(spec))              // no frames travel with caller tensors through these entry points
+    return fail("potts: the loss needs the frames; on caller tensors use eosvos_potts_loss (Engine.potts_loss), which takes them");
   if (!spec.combine && !dlogits_out && n > (int64_t)e->maxB * e->H * e->W) return fail("n exceeds the engine's scratch");
   return loss_spec_eval(e, spec, logits, masks, n, 1, true, ignore, grad_target(e, dlogits_out), loss_out);
 }
@@ -3317,6 +3368,28 @@ int eosvos_surface_weights(eosvos_engine* e, const float* masks, int images, int
   int32_t* const c = c_out ? c_out : (int32_t*)scratch_at(e, L.g);
   launch_surface_distance(masks, images, height, width, l, ignore, scratch_at(e, L.g), c, e->s);
   if (w_out) launch_surface_weights(c, w_out, (int64_t)np, l, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+
+// ---- the pairwise (Potts) loss: its parameters on the engine, and the loss on caller tensors with their frames --------------
+int eosvos_set_loss_potts(eosvos_engine* e, int window, int dilation, float sigma_xy, float sigma_rgb) {
+  if (!e) return fail("null engine");
+  if (potts_params("set_loss_potts", window, dilation, sigma_xy, sigma_rgb, nullptr)) return 1;
+  e->potts_window = window;
+  e->potts_dilation = dilation;
+  e->potts_sigma_xy = sigma_xy;
+  e->potts_sigma_rgb = sigma_rgb;
+  return 0;
+}
+int eosvos_potts_loss(eosvos_engine* e, const float* logits, const float* frames, int images, int height, int width, int window,
+                      int dilation, float sigma_xy, float sigma_rgb, float* loss_out, float* dlogits_out) {
+  if (!e || !logits || !frames || !loss_out) return fail("potts_loss: null argument");
+  if (images < 1 || images > 65535) return fail("potts_loss: between 1 and 65535 images per call");
+  if (height < 1 || height > 4096 || width < 1 || width > 4096) return fail("potts_loss: frames of 1 .. 4096 pixels a side");
+  PottsParams q;
+  if (potts_params("potts_loss", window, dilation, sigma_xy, sigma_rgb, &q)) return 1;
+  if (potts_eval(e, "potts_loss", q, logits, frames, 0, height, width, images, dlogits_out, loss_out)) return 1;
   HIPOK(hipGetLastError());
   return 0;
 }

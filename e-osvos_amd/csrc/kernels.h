@@ -529,6 +529,17 @@ void launch_crf_prepare(const float* probs, int n_frames, int n_obj, int64_t n_p
 void launch_crf_iteration(const float* images, const float* unary, const float* q_in, float* q_out, uint8_t* labels,
                           int n_frames, int n_lab, int H, int W, int r, int d, float w_a, float w_s, float theta_beta,
                           const CrfTables& tab, hipStream_t s);
+// Image-aware pairwise (Potts) loss (potts_kernels.hip; the rule: include/eosvos.h at EOSVOS_LOSS_POTTS): `images` maps of
+// H x W logits (H, W <= 4096, images <= 65535) against their frames, the CRF's window limits (1 <= r <= 7, 1 <= d <= 4,
+// r * d <= 16), sigma_xy, sigma_rgb finite and > 0.  `frames`: with pad > 0 fp32 [image][H + 2 pad][W + 2 pad][3] (the
+// engine's copy of the last forward's frames), with pad 0 fp32 [image][3][H][W]; both give the same bits.  Three launches
+// (two without dlogits, which may be null), no atomics, fixed-order sums: bit-reproducible.  scratch: potts_scratch_floats
+// words (two partials per 32 x 8 tile and one scale per image), all written before they are read.
+struct PottsTable { float w[CRF_MAX_SIDE * CRF_MAX_SIDE]; };    // exp(-d^2 (dy^2 + dx^2) / (2 sigma_xy^2)), [(dy + r) * (2r + 1) + dx + r]
+void potts_fill_table(PottsTable& tab, int r, int d, float sigma_xy);
+int64_t potts_scratch_floats(int H, int W, int images);
+void launch_potts(const float* logits, const float* frames, int pad, float* dlogits, float* loss, float* scratch, int H, int W,
+                  int images, int r, int d, float sigma_xy, float sigma_rgb, hipStream_t s);
 
 // Connected components of uint8 label maps and the component filter (ccl_kernels.hip; the rules: include/eosvos.h,
 // eosvos_label_components / eosvos_filter_components).  Maps are [frame][H][W]; H, W <= 4096, H * W < 2^24, frames <= 65535.

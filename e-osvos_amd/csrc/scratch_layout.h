@@ -89,6 +89,12 @@ struct SurfaceLayout : ScratchLayout {
   ScratchAt<float> partial;
   SurfaceLayout(size_t n, size_t np, size_t partial_words) : g(take<uint32_t>("g", np)), partial(take<float>("partial", n * partial_words)) {}
 };
+// words = potts_scratch_floats of kernels.h: the pairwise loss's two partials per tile and one scale per image; every word is
+// written before it is read, so nothing needs clearing
+struct PottsLayout : ScratchLayout {
+  ScratchAt<float> partial;
+  explicit PottsLayout(size_t words) : partial(take<float>("partial", words)) {}
+};
 struct LucidLayersLayout : ScratchLayout {                     // the visible-pixel counts [n][8 layers] start out as 0
   ScratchAt<int> counts;
   explicit LucidLayersLayout(size_t n) : counts(take<int>("counts", n * 8)) { clear(0, end); }

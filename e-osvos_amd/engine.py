@@ -10,7 +10,7 @@ import functools
 
 import torch
 
-from . import _ffi, bootstrap, boundary, loss_sum, surface
+from . import _ffi, bootstrap, boundary, loss_sum, potts, surface
 from .loss_names import LOSS_KINDS, resolve_cap, resolve_loss, resolve_radius  # noqa: F401  (their home; callers import them from here)
 from .topology import ARCH_ID, norm_layers, trainable
 
@@ -68,12 +68,12 @@ def _touched(*tensors):
 LR_LEVELS = {'NEURON': 0, 'TENSOR': 1, 'SINGLE': 2, 'PARAM': 3}      # include/eosvos.h EOSVOS_LR_*
 # One resolved `loss_func`: the ctypes arrays of its n kinds and weights, whether the engine combines them (a spelling with
 # '+' or '*') or runs kinds[0]'s own launches alone, and the fraction / radius / cap the spelling or its keyword carries (None:
-# the engine's current value stays).
-LossSpec = collections.namedtuple('LossSpec', 'n kinds weights combine fraction radius cap')
+# the engine's current value stays), and the (radius or None, dilation or None) of a `potts` term (None without one).
+LossSpec = collections.namedtuple('LossSpec', 'n kinds weights combine fraction radius cap window')
 
 
 @functools.lru_cache(maxsize=64, typed=True)
-def _resolve(name, fraction, radius, cap=None):
+def _resolve(name, fraction, radius, cap=None, window=None):
     """A sum spelling (`loss_sum.resolve`, `loss_sum.resolve_cap`) or a plain name (`resolve_loss` / `resolve_radius` /
     `resolve_cap`, one term of weight 1) as a
     LossSpec, kept per spelling: splitting and checking one takes ~10 us on the host, which a loss whose launches take 30 us
@@ -81,12 +81,12 @@ def _resolve(name, fraction, radius, cap=None):
     combine = loss_sum.is_sum(name)
     if combine:
         kinds, weights, _, f, r = loss_sum.resolve(name, fraction, radius)
-        c = loss_sum.resolve_cap(name, cap)
+        c, w = loss_sum.resolve_cap(name, cap), loss_sum.resolve_window(name, window)
     else:
-        kind, f = resolve_loss(name, fraction, radius, cap)
-        kinds, weights, r, c = [kind], [1.0], resolve_radius(name, radius), resolve_cap(name, cap)
+        kind, f = resolve_loss(name, fraction, radius, cap, window)
+        kinds, weights, r, c, w = [kind], [1.0], resolve_radius(name, radius), resolve_cap(name, cap), potts.resolve_window(name, window)
     n = len(kinds)
-    return LossSpec(n, (ctypes.c_int * n)(*kinds), (ctypes.c_float * n)(*weights), combine, f, r, c)
+    return LossSpec(n, (ctypes.c_int * n)(*kinds), (ctypes.c_float * n)(*weights), combine, f, r, c, w)
 
 
 def check_ignore(ignore):
@@ -225,14 +225,14 @@ class Engine:
         self.lr_level, self.lr_log, self.n_lr_store = level, bool(use_log), n
         self.synchronize()
 
-    def set_loss(self, name, ignore=None, fraction=None, radius=None, cap=None):
+    def set_loss(self, name, ignore=None, fraction=None, radius=None, cap=None, window=None):
         """Loss of finetune_step / meta_grad (`loss_func`, helper_func.py:28-56) and its void label (None: every pixel counts).
         `bootstrapped_cross_entropy_<P>` or `fraction=` also set the engine's bootstrap fraction, `boundary_f_<r>` /
-        `cross_entropy_and_boundary_f_<r>` or `radius=` its boundary radius, `surface_<L>` or `cap=` its surface cap (see
-        `_loss_spec`).  A sum spelling (`0.5*lovasz_hinge+boundary_f_4`, `loss_sum.py`) selects `eosvos_set_loss_sum`; a
-        single name returns to one kind."""
+        `cross_entropy_and_boundary_f_<r>` or `radius=` its boundary radius, `surface_<L>` or `cap=` its surface cap,
+        `potts_<r>` / `potts_<r>x<d>` or `window=` its potts window (see `_loss_spec`).  A sum spelling
+        (`0.5*lovasz_hinge+boundary_f_4`, `loss_sum.py`) selects `eosvos_set_loss_sum`; a single name returns to one kind."""
         try:
-            spec = self._loss_spec(name, fraction, radius, cap)
+            spec = self._loss_spec(name, fraction, radius, cap, window)
         except KeyError:
             raise NotImplementedError(name) from None   # helper_func.py:55-56
         v = None if ignore is None else check_ignore(ignore)
@@ -260,10 +260,32 @@ class Engine:
         _ffi.check(self.lib.eosvos_set_loss_surface(self.h, 0 if cap == 0 and not isinstance(cap, bool)
                                                     else surface.check_cap(cap)))
 
-    def _loss_spec(self, name, fraction=None, radius=None, cap=None):
-        """The LossSpec of a spelled `loss_func` (`_resolve`); a fraction, radius or cap carried by the spelling or the keyword
-        becomes the engine's before the call that follows."""
-        spec = _resolve(name, fraction, radius, cap)
+    def set_loss_potts(self, window=None, dilation=None, sigma_xy=None, sigma_rgb=None):
+        """Window radius (1 .. 7), dilation (1 .. 4, radius * dilation <= 16) and sigmas (finite, > 0) of `potts` for every
+        later evaluation on this engine (`eosvos_set_loss_potts`).  None keeps what the engine has, 0 returns to the default
+        (3, 2, radius * dilation, 0.1), which a new engine has.  The defaults are untuned."""
+        now = dict(getattr(self, '_potts', None) or {'window': 0, 'dilation': 0, 'sigma_xy': 0.0, 'sigma_rgb': 0.0})
+        for key, v in (('window', window), ('dilation', dilation), ('sigma_xy', sigma_xy), ('sigma_rgb', sigma_rgb)):
+            if v is None:
+                continue
+            if v == 0 and not isinstance(v, bool):
+                now[key] = 0
+            elif key == 'window':
+                now[key] = potts.check_window(v)
+            elif key == 'dilation':
+                now[key] = potts.check_window(1, v)[1]
+            else:
+                now[key] = potts.check_sigma(key, v)
+        potts.check_window(now['window'] or potts.DEFAULT_WINDOW, now['dilation'] or potts.DEFAULT_DILATION)
+        _ffi.check(self.lib.eosvos_set_loss_potts(self.h, now['window'], now['dilation'], now['sigma_xy'], now['sigma_rgb']))
+        self._potts = now
+
+    def _loss_spec(self, name, fraction=None, radius=None, cap=None, window=None):
+        """The LossSpec of a spelled `loss_func` (`_resolve`); a fraction, radius, cap or window carried by the spelling or the
+        keyword becomes the engine's before the call that follows."""
+        spec = _resolve(name, fraction, radius, cap, window)
+        if spec.window is not None and spec.window != (None, None):
+            self.set_loss_potts(*spec.window)
         if spec.cap is not None:
             self.set_loss_surface(spec.cap)
         if spec.fraction is not None:
@@ -514,13 +536,13 @@ class Engine:
             self._chk_masks, self._chk_kind, self._chk_ignore = masks, 'cross_entropy', None
         return loss
 
-    def loss(self, kind, masks, ignore=None, fraction=None, radius=None, cap=None):
+    def loss(self, kind, masks, ignore=None, fraction=None, radius=None, cap=None, window=None):
         """kind: a compute_loss name (helper_func.py:28-56, see LOSS_KINDS); leaves dL/dlogits.  `ignore`: the void label --
         pixels whose mask equals it are in no sum, count or ranking and get gradient 0 (`eosvos_loss_ignore`).  `fraction`:
-        of `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, `cap`: of `surface`, as in `set_loss`.  A sum
-        spelling evaluates the weighted sum of its terms (`eosvos_loss_sum`); `last_loss_terms` then gives the terms' own
-        values."""
-        spec = self._loss_spec(kind, fraction, radius, cap)
+        of `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, `cap`: of `surface`, `window`: of `potts` (which
+        reads the frames of the last forward and not the masks), as in `set_loss`.  A sum spelling evaluates the weighted sum
+        of its terms (`eosvos_loss_sum`); `last_loss_terms` then gives the terms' own values."""
+        spec = self._loss_spec(kind, fraction, radius, cap, window)
         ignore = None if ignore is None else check_ignore(ignore)
         assert masks.is_cuda and masks.dtype == torch.float32 and masks.is_contiguous()
         out = torch.empty(1, device=self.device)
@@ -534,7 +556,7 @@ class Engine:
         `batch_average: False`); no gradient is kept.  `ignore`: as in `loss` (`eosvos_loss_tensors_ignore`); `fraction`: of
         `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, `cap`: of `surface`, as in `set_loss`.  The boundary
         kinds and `surface` need the frame's shape: they take one image of the engine's H * W elements only (`boundary_f` and
-        `surface_loss` below take any shape)."""
+        `surface_loss` below take any shape).  `potts` is refused: no frames travel with the tensors (`potts_loss` takes them)."""
         logits, masks = logits.contiguous(), masks.contiguous()
         assert logits.is_cuda and masks.is_cuda and logits.numel() == masks.numel()
         out = torch.empty(1, device=self.device)
@@ -545,7 +567,8 @@ class Engine:
     def loss_grad_of(self, name, logits, masks, ignore=None, fraction=None, radius=None, cap=None):
         """(loss, dL/dlogits of the logits' shape) of a single kind or a sum on arbitrary device tensors, the elements one set
         as in `loss_of` (`eosvos_loss_sum_tensors`; a single kind is the sum of one term of weight 1, which has that kind's
-        bits).  At most the engine's largest batch of pixels; the engine's own gradient is untouched."""
+        bits).  At most the engine's largest batch of pixels; the engine's own gradient is untouched.  A `potts` term is refused
+        as in `loss_of`."""
         logits, masks = logits.contiguous(), masks.contiguous()
         assert logits.is_cuda and masks.is_cuda and logits.dtype == masks.dtype == torch.float32
         assert logits.numel() == masks.numel()
@@ -610,6 +633,44 @@ class Engine:
         c, wt = torch.empty(masks.shape, dtype=torch.int32, device=self.device), torch.empty_like(masks)
         _ffi.check(self.lib.eosvos_surface_weights(self.h, _ptr(masks), b, h, w, cap, v, _ptr(c), _ptr(wt)))
         return c, wt
+
+    def potts_loss(self, logits, frames, window=None, dilation=None, sigma_xy=None, sigma_rgb=None):
+        """`potts` of device logits (B, H, W) or (H, W) against their frames (B, 3, H, W) or (3, H, W), any frame size up to
+        4096 a side (`eosvos_potts_loss`).  None: the defaults of `potts.py` (3, 2, window * dilation, 0.1; untuned), not the
+        engine's own settings.  Returns (loss, dL/dlogits of the logits' shape); the engine's own gradient is untouched."""
+        self._check_stream()
+        logits, frames = logits.contiguous(), frames.contiguous()
+        assert logits.is_cuda and frames.is_cuda and logits.dtype == frames.dtype == torch.float32 and logits.dim() in (2, 3)
+        b = logits.shape[0] if logits.dim() == 3 else 1
+        h, w = logits.shape[-2:]
+        assert frames.numel() == 3 * logits.numel() and tuple(frames.shape[-3:]) == (3, h, w)
+        r, d = potts.check_window(potts.DEFAULT_WINDOW if window is None else window,
+                                  potts.DEFAULT_DILATION if dilation is None else dilation)
+        sxy = 0.0 if sigma_xy is None else potts.check_sigma('sigma_xy', sigma_xy)
+        srgb = 0.0 if sigma_rgb is None else potts.check_sigma('sigma_rgb', sigma_rgb)
+        out, grad = torch.empty(1, device=self.device), torch.empty_like(logits)
+        _ffi.check(self.lib.eosvos_potts_loss(self.h, _ptr(logits), _ptr(frames), b, h, w, r, d, sxy, srgb, _ptr(out), _ptr(grad)))
+        return out, grad
+
+    def loss_of_framed(self, name, logits, masks, frames, ignore=None):
+        """`loss_of` for callers that hold the frames of their logits (`run_frames`' per-frame metric): a spelling without a
+        `potts` term goes to `loss_of` as it is.  With one, every other term is `loss_of`'s, the `potts` term is `potts_loss`
+        on `frames` (N, 3, H, W) with the engine's window and sigmas (a suffix sets them first, as everywhere), and the values
+        are combined by the sum's rule (`loss_sum.py`: fp32 products and sums, in spelled order)."""
+        terms = loss_sum.parse(name)
+        if not any(potts.parse(t)[0] in potts.KINDS for _, t in terms):
+            return self.loss_of(name, logits, masks, ignore=ignore)
+        self._loss_spec(name)
+        q = {k: (v or None) for k, v in (getattr(self, '_potts', None) or {}).items()}
+        acc = None
+        for w, t in terms:
+            if potts.parse(t)[0] in potts.KINDS:
+                v = self.potts_loss(logits.reshape(-1, *frames.shape[-2:]), frames, **q)[0]
+            else:
+                v = self.loss_of(t, logits, masks, ignore=ignore)
+            v = v * torch.tensor(w, dtype=torch.float32, device=v.device)
+            acc = v if acc is None else acc + v
+        return acc
 
     def propagation_targets(self, probs, lo, hi, ignore, counts=True):
         """Pseudo-label targets of online adaptation with an uncertainty band (`eosvos_propagation_targets`): probs (F, ...)

@@ -21,6 +21,10 @@ r pixels, or `loss_kwargs={'radius': r}`.
 `surface` (`surface.py`; not in the reference) weights every pixel's error by its distance to the target's boundary, capped at
 the engine's cap (by default a quarter of the frame's short side, untuned), `surface_<L>` for L pixels, or
 `loss_kwargs={'cap': L}`; it is meant as a term of a sum, e.g. `dice+0.5*surface_64`.
+`potts` (`potts.py`; not in the reference) is the image-aware pairwise loss: it reads the frames of the last forward and no
+target (void pixels get its gradient too), on the engine's window (radius 3, dilation 2 by default, untuned), `potts_<r>` /
+`potts_<r>x<d>` for another, or `loss_kwargs={'window': r}`; it is meant as a term of a sum, e.g. `cross_entropy+0.1*potts_3x2`,
+and has no per-sample form (`batch_average: False`), which carries no frames.
 A `loss_func` with a '+' or a '*' is a weighted sum of up to four of these (`loss_sum.py`), e.g. `0.5*lovasz_hinge+boundary_f_4`.
 """
 import random
@@ -43,6 +47,7 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
     # NotImplementedError; a keyword without a term of its family, out of range or against a suffix: ValueError
     names = loss_sum.resolve(loss_func, loss_kwargs.get('fraction'), loss_kwargs.get('radius'), per_image)[2]
     loss_sum.resolve_cap(loss_func, loss_kwargs.get('cap'))
+    loss_sum.resolve_window(loss_func, loss_kwargs.get('window'))
     if 'class_balanced_cross_entropy' in names and not loss_kwargs.get('size_average', True):
         raise NotImplementedError('class_balanced_cross_entropy with size_average=False')
     if not per_image:
@@ -52,7 +57,7 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
         raise RuntimeError('compute_loss needs logits produced by eosvos_amd.networks.DeepLabV3Plus '
                            '(there is no CPU/eager path)')
     gts = gts.contiguous().float()
-    kw = {k: loss_kwargs[k] for k in ('ignore', 'fraction', 'radius', 'cap') if loss_kwargs.get(k) is not None}
+    kw = {k: loss_kwargs[k] for k in ('ignore', 'fraction', 'radius', 'cap', 'window') if loss_kwargs.get(k) is not None}
     if loss_kwargs.get('batch_average', True):
         loss = eng.loss(loss_func, gts, **kw).view(())      # also leaves dL/dlogits in the engine
         loss._eosvos_engine = eng
@@ -96,6 +101,7 @@ def run_frames(model, frames, gts=None, loss_func='cross_entropy', tta=None, zoo
     use_tta = tta_views.active(tta)
     use_zoom = zoom_pass.active(zoom)
     view_set = refiner = None
+    framed = gts is not None and isinstance(loss_func, str) and 'potts' in loss_func      # (a bad spelling fails in the engine, as before)
     for i in range(frames.shape[0]):
         x = frames[i:i + 1].contiguous()
         eng = model._ensure_engine(x.shape[2], x.shape[3], 1)
@@ -113,7 +119,10 @@ def run_frames(model, frames, gts=None, loss_func='cross_entropy', tta=None, zoo
         probs.append(p)
         if gts is not None:
             logits = torch.logit(p, eps=1e-7) if use_tta or use_zoom else eng.debug_tensor('logits')[:1]
-            losses.append(eng.loss_of(loss_func, logits, gts[i:i + 1].contiguous()))
+            if framed:                                        # a `potts` term reads the frame
+                losses.append(eng.loss_of_framed(loss_func, logits, gts[i:i + 1].contiguous(), x))
+            else:
+                losses.append(eng.loss_of(loss_func, logits, gts[i:i + 1].contiguous()))
             pred = p.ge(0.5)
             accs.append(pred.eq(gts[i:i + 1].bool()).float().mean().view(1))
     probs = torch.cat(probs)

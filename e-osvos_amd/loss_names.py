@@ -3,6 +3,7 @@ engine.  Host only and a leaf: importing this module needs neither torch nor the
 package.  `bootstrap.py`, `boundary.py` and `engine.py` re-export what callers know under their names; sums of names are
 `loss_sum.py`."""
 import math
+import re
 
 import numpy as np
 
@@ -19,6 +20,12 @@ SURFACE = 'surface'
 # the distance-weighted surface loss (surface.py); it needs the frame's shape too.  A third table: the two above stay as they are
 SURFACE_KINDS = {SURFACE: 10}
 MAX_CAP = 4095
+POTTS = 'potts'
+# the image-aware pairwise loss (potts.py); it reads the frames of the last forward and no target.  A fourth table with id 12: the
+# three above stay as they are, and 11 stays unassigned like 7
+POTTS_KINDS = {POTTS: 12}
+MAX_WINDOW, MAX_DILATION, MAX_HALO = 7, 4, 16      # the CRF's limits: radius, dilation, radius * dilation
+_POTTS_SUFFIX = re.compile(r'_([1-9][0-9]*)(?:x([1-9][0-9]*))?\Z', re.ASCII)
 
 
 def parse_suffix(name, bases, hi):
@@ -60,6 +67,22 @@ def parse_surface(name):
     return parse_suffix(name, (SURFACE,), MAX_CAP)
 
 
+def parse_potts(name):
+    """`potts` -> (name, None, None): the engine's window; `potts_<r>` -> (name, r, None): radius r, the engine's dilation;
+    `potts_<r>x<d>` -> (name, r, d).  Integers without a leading zero, r in 1 .. 7, d in 1 .. 4, r * d <= 16.  A name that does
+    not start with `potts` is returned as (name, None, None); anything else under the prefix raises NotImplementedError like
+    an unknown loss name."""
+    if not isinstance(name, str) or not name.startswith(POTTS):
+        return name, None, None
+    if name == POTTS:
+        return POTTS, None, None
+    m = _POTTS_SUFFIX.match(name[len(POTTS):])
+    r, d = (int(m.group(1)), None if m.group(2) is None else int(m.group(2))) if m else (0, None)
+    if not 1 <= r <= MAX_WINDOW or (d is not None and (not 1 <= d <= MAX_DILATION or r * d > MAX_HALO)):
+        raise NotImplementedError(f"loss_func='{name}'")
+    return POTTS, r, d
+
+
 def check_fraction(fraction):
     """The fraction as the float the library receives: in (0, 1]."""
     f = float(np.float32(fraction))
@@ -89,15 +112,32 @@ def check_cap(cap):
     return int(cap)
 
 
-def resolve_loss(name, fraction=None, radius=None, cap=None):
+def check_window(window, dilation=None):
+    """The window radius (and with it the dilation) as the ints the library receives: whole numbers, 1 .. 7 and 1 .. 4, their
+    product at most 16."""
+    def whole(v, lo, hi):
+        return not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v) and v == int(v) and lo <= int(v) <= hi
+    if not whole(window, 1, MAX_WINDOW):
+        raise ValueError(f'window={window!r}: the potts window radius must be a whole number in 1 .. {MAX_WINDOW}')
+    if dilation is None:
+        return int(window)
+    if not whole(dilation, 1, MAX_DILATION):
+        raise ValueError(f'dilation={dilation!r}: the potts dilation must be a whole number in 1 .. {MAX_DILATION}')
+    if int(window) * int(dilation) > MAX_HALO:
+        raise ValueError(f'window={window!r}, dilation={dilation!r}: their product must be at most {MAX_HALO}')
+    return int(window), int(dilation)
+
+
+def resolve_loss(name, fraction=None, radius=None, cap=None, window=None):
     """A spelled loss name -> (kind id, fraction or None).  `bootstrapped_cross_entropy_<P>` carries P percent; `fraction`
     is the keyword form, for that kind only; the two may not disagree.  None: the engine's current fraction stays.  A bad
     spelling under the bootstrap prefix raises NotImplementedError, any other unknown name KeyError.  The kinds that need the
     frame's shape (BOUNDARY_KINDS) are consulted after LOSS_KINDS and give (kind id, None); their radius, from the name
     or `radius=`, is `resolve_radius`'s, which this call checks too.  SURFACE_KINDS is consulted last, in the same way, its cap
-    (`resolve_cap`) checked here too."""
+    (`resolve_cap`) checked here too.  POTTS_KINDS comes after it, its window (`resolve_window`) checked here too."""
     radius = resolve_radius(name, radius)
     cap = resolve_cap(name, cap)
+    window = resolve_window(name, window)
     base, f = parse_bootstrap(name)
     if base not in LOSS_KINDS and parse_boundary(name)[0] in BOUNDARY_KINDS:
         if fraction is not None:
@@ -107,6 +147,10 @@ def resolve_loss(name, fraction=None, radius=None, cap=None):
         if fraction is not None:
             raise ValueError(f"fraction= belongs to '{BOOTSTRAP}', not to '{name}'")
         return SURFACE_KINDS[parse_surface(name)[0]], None
+    if base not in LOSS_KINDS and parse_potts(name)[0] in POTTS_KINDS:
+        if fraction is not None:
+            raise ValueError(f"fraction= belongs to '{BOOTSTRAP}', not to '{name}'")
+        return POTTS_KINDS[POTTS], None
     kind = LOSS_KINDS[base]
     if fraction is not None:
         if base != BOOTSTRAP:
@@ -143,3 +187,22 @@ def resolve_cap(name, cap=None):
             raise ValueError(f"loss_func='{name}' and cap={cap!r} disagree")
         c = cap
     return c
+
+
+def resolve_window(name, window=None):
+    """The window a spelled loss name asks for, as (radius or None, dilation or None), or None for a name that is no `potts`:
+    `potts_<r>` / `potts_<r>x<d>` carry r (and d), `window` is the keyword form of r, for that kind only; the two may not
+    disagree.  None in a place: the engine's current value stays."""
+    base, r, d = parse_potts(name)
+    if base not in POTTS_KINDS:
+        if window is not None:
+            raise ValueError(f"window= belongs to '{POTTS}', not to '{name}'")
+        return None
+    if window is not None:
+        window = check_window(window)
+        if r is not None and r != window:
+            raise ValueError(f"loss_func='{name}' and window={window!r} disagree")
+        if d is not None and window * d > MAX_HALO:
+            raise ValueError(f"loss_func='{name}' and window={window!r}: radius * dilation must be at most {MAX_HALO}")
+        r = window
+    return r, d

@@ -17,9 +17,10 @@ from fractions import Fraction
 
 import numpy as np
 
-from .loss_names import (BOOTSTRAP, BOUNDARY_KINDS, SURFACE, SURFACE_KINDS, parse_boundary, parse_bootstrap, parse_surface,
-                         resolve_loss, resolve_radius)
+from .loss_names import (BOOTSTRAP, BOUNDARY_KINDS, POTTS, POTTS_KINDS, SURFACE, SURFACE_KINDS, parse_boundary, parse_bootstrap,
+                         parse_potts, parse_surface, resolve_loss, resolve_radius)
 from .loss_names import resolve_cap as _term_cap
+from .loss_names import resolve_window as _term_window
 
 MAX_TERMS = 4                           # EOSVOS_LOSS_MAX_TERMS of include/eosvos.h
 _WEIGHT = re.compile(r'[0-9]+(\.[0-9]+)?\Z')
@@ -113,6 +114,18 @@ def resolve_cap(name, cap=None):
     if cap is not None and not surface_terms:
         raise ValueError(f"cap= belongs to '{SURFACE}', which is no term of '{name}'")
     return _term_cap(surface_terms[0], cap) if surface_terms else None
+
+
+def resolve_window(name, window=None):
+    """The window a spelled sum (or single name) carries, as (radius or None, dilation or None), or None without a `potts`
+    term: `window` belongs to the one `potts` term as `cap` belongs to `surface` in `resolve_cap`: without such a term, or
+    against a disagreeing suffix, ValueError; two `potts` terms (they share the engine's one window) are a ValueError too."""
+    potts_terms = [t for _, t in parse(name) if parse_potts(t)[0] in POTTS_KINDS]
+    if len(potts_terms) > 1:
+        raise ValueError(f"loss_func='{name}' names a loss twice")
+    if window is not None and not potts_terms:
+        raise ValueError(f"window= belongs to '{POTTS}', which is no term of '{name}'")
+    return _term_window(potts_terms[0], window) if potts_terms else None
 
 
 def combine_host(values, grads, weights):

@@ -293,6 +293,44 @@ int eosvos_surface_loss(eosvos_engine* e, const float* logits, const float* mask
  * [image][H][W] fp32, DEVICE pointers; either may be null, not both. */
 int eosvos_surface_weights(eosvos_engine* e, const float* masks, int images, int height, int width, int cap, const float* ignore,
                            int32_t* c_out, float* w_out);
+/* Image-aware pairwise loss, `potts`: neighbouring pixels of similar colour are pulled to the same label (the relaxed Potts /
+ * dense-CRF regulariser evaluated as a loss: Tang et al., "On Regularized Losses for Weakly-supervised CNN Segmentation",
+ * ECCV 2018; the local-window form of Obukhov et al., "Gated CRF Loss", 2019).  Not in the reference.  Meant as a term beside a
+ * supervised loss (`cross_entropy+0.1*potts`).  Per image of H x W pixels, z the logits, p = sigmoid(z), I the frame as the
+ * engine received it (3 channels, any offset: only differences are used), window radius r taps, dilation d; the neighbours
+ * N(i) of pixel i are the pixels i + d (dy, dx), dy, dx in [-r, r], (dy, dx) != (0, 0), inside the frame:
+ *   k_ij = exp(-d^2 (dy^2 + dx^2) / (2 sigma_xy^2)) exp(-|I_i - I_j|^2 / (2 sigma_rgb^2))
+ *   S_i = sum_{j in N(i)} k_ij;   M_i = sum_{j in N(i)} k_ij p_j;   E = sum_i p_i (S_i - M_i);   Z = sum_i S_i
+ * Every pair counts once in each direction, so E holds p_i (1 - p_j) + p_j (1 - p_i) per pair.  Image loss = E / Z, 0 when
+ * Z = 0 (a one-pixel image, kernels that underflow); loss = the mean over the images.  Window and kernel are symmetric, so
+ *   dL/dz_i = (S_i - 2 M_i) p_i (1 - p_i) / (Z images).
+ * THE TERM READS NO TARGET: `masks` are accepted and not read, the void label changes nothing, and void pixels receive this
+ * term's gradient like every other pixel -- that is its purpose: under eval_online_adapt.min_prop = [lo, hi] the band around
+ * the contour is void for every other loss, and this term is what spreads the labelled pixels into it along the frame's edges.
+ * A NaN logit makes the loss NaN.
+ * Limits: r in [1, 7], d in [1, 4], r d <= 16 (the CRF's, so its table size fits), the sigmas finite and > 0, sides <= 4096.
+ * Engine defaults: r = 3, d = 2, sigma_xy = r d, sigma_rgb = 0.1 with colours in units of the frame's [0, 1] range --
+ * Obukhov's values rescaled; they are UNTUNED and no J&F figure exists.
+ * The frame is the engine's copy of the last forward's input (kept for the stem's weight gradient), so the kind is evaluated
+ * on the logits of the last forward only: by eosvos_loss / eosvos_loss_ignore / eosvos_loss_sum (at most one such term) and
+ * the fused entry points.  eosvos_loss_tensors* and eosvos_loss_sum_tensors carry no frames and refuse the kind; on caller
+ * tensors use eosvos_potts_loss.  An evaluation on an engine that has run no forward fails and leaves no gradient.
+ * Three launches (the stencil over 32 x 8 pixel tiles, which writes the unscaled gradient and one partial of E and of Z per
+ * tile; the fixed-order sum of the partials; the scaling of the gradient), no atomics: loss and gradient are bit-identical
+ * from run to run.  Scratch: two words per tile and one per image, from the arena of the evaluation-stage entry points. */
+#define EOSVOS_LOSS_POTTS 12            /* (11 is unassigned, like 7) */
+/* Window radius, dilation and sigmas of EOSVOS_LOSS_POTTS for every later evaluation on this engine; 0 for any of the four
+ * selects its default (3, 2, radius * dilation, 0.1).  Out of the limits above (negative or non-finite sigmas included): an
+ * error, nothing changes. */
+int eosvos_set_loss_potts(eosvos_engine* e, int window, int dilation, float sigma_xy, float sigma_rgb);
+/* The pairwise loss on caller tensors with their frames: `images` (1 .. 65535) maps of height x width logits, each side in
+ * [1, 4096], and frames fp32 [image][3][height][width]; DEVICE pointers.  0 for window, dilation or a sigma selects the
+ * default above (the engine's own settings are not used).  The loss goes to loss_out (a device float), the gradient to
+ * dlogits_out, which may be null (none is formed).  The same kernel body as on the engine, which reads its padded copy of the
+ * frames through another accessor: the same frames and logits give the same bits either way.  Bad arguments return non-zero
+ * before any launch: the outputs stay untouched. */
+int eosvos_potts_loss(eosvos_engine* e, const float* logits, const float* frames, int images, int height, int width, int window,
+                      int dilation, float sigma_xy, float sigma_rgb, float* loss_out, float* dlogits_out);
 /* eosvos_loss_bce for any kind (the forms of one evaluation, see there). */
 int eosvos_loss(eosvos_engine* e, int kind, const float* masks, int batch, float* loss_out);
 /* The value of the last loss evaluated by eosvos_loss* / eosvos_finetune_step / eosvos_meta_grad*, copied to a DEVICE
