@@ -86,6 +86,11 @@ _SIGNATURES = {
     'eosvos_set_loss_potts': (ctypes.c_int, [_E, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float]),
     'eosvos_potts_loss': (ctypes.c_int, [_E, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p]),
+    'eosvos_set_loss_cldice': (ctypes.c_int, [_E, ctypes.c_int]),
+    'eosvos_cldice_loss': (ctypes.c_int, [_E, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_float), c_float_p, c_float_p]),
+    'eosvos_soft_skeleton': (ctypes.c_int, [_E, c_float_p, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(ctypes.c_float), c_float_p]),
     'eosvos_propagation_targets': (ctypes.c_int, [_E, c_float_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_float,
                                                   ctypes.c_float, c_float_p, ctypes.POINTER(ctypes.c_int64)]),
     'eosvos_warp_affine': (ctypes.c_int, [_E, c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,

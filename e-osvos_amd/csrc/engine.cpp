@@ -232,6 +232,11 @@ struct eosvos_engine {
   int boundary_radius = 0;              // eosvos_set_loss_boundary: 1 .. 16, 0 = the frame-size default
   float* surface_scratch = nullptr;     // distance words and partials of the surface loss, allocated like lovasz_scratch
   int surface_cap = 0;                  // eosvos_set_loss_surface: 1 .. 4095, 0 = the frame-size default
+  // the centreline loss's planes, per-level increments and routing codes, allocated like lovasz_scratch for the depth in use
+  // (cldice_levels_held levels; a deeper evaluation gives the buffer back and takes a larger one)
+  float* cldice_scratch = nullptr;
+  int cldice_levels_held = 0;
+  int cldice_depth = 0;                 // eosvos_set_loss_cldice: 1 .. 16, 0 = the frame-size default
   // eosvos_set_loss_potts: the pairwise loss's window radius, dilation and sigmas, 0 = the default (3, 2, radius * dilation, 0.1);
   // it has no buffer of its own: its partials live in the scratch arena, its frames are xpad
   int potts_window = 0, potts_dilation = 0;
@@ -382,6 +387,16 @@ struct eosvos_engine {
     if (fill) { (void)hipMemsetD32((hipDeviceptr_t)p, (int)strtoul(fill, nullptr, 16), (size_t)n); (void)hipDeviceSynchronize(); }
     allocs.push_back(p);
     return (float*)p;
+  }
+  // a buffer of falloc given back before the engine closes
+  void ffree(float* q) {
+    if (!q) return;
+    void* p = q;
+    for (auto it = guarded.begin(); it != guarded.end(); ++it)
+      if ((float*)it->first + GUARD == q) { p = it->first; guarded.erase(it); break; }
+    const auto it = std::find(allocs.begin(), allocs.end(), p);
+    if (it != allocs.end()) allocs.erase(it);
+    (void)hipFree(p);
   }
   float* W_(int ci) { return Wp + t.convs[ci].poff; }
   bool gn() const { return norm_mode == EOSVOS_NORM_GN16; }
@@ -2353,9 +2368,10 @@ inline bool lovasz_kind(int kind) { return kind == EOSVOS_LOSS_LOVASZ_HINGE || k
 inline bool bootstrap_kind(int kind) { return kind == EOSVOS_LOSS_BOOTSTRAPPED_BCE; }
 inline bool boundary_kind(int kind) { return kind == EOSVOS_LOSS_BOUNDARY_F || kind == EOSVOS_LOSS_BCE_AND_BOUNDARY_F; }
 inline bool surface_kind(int kind) { return kind == EOSVOS_LOSS_SURFACE; }
-inline bool frame_shape_kind(int kind) { return boundary_kind(kind) || surface_kind(kind); }   // an image is the engine's H x W
+inline bool cldice_kind(int kind) { return kind == EOSVOS_LOSS_CLDICE; }
+inline bool frame_shape_kind(int kind) { return boundary_kind(kind) || surface_kind(kind) || cldice_kind(kind); }   // an image is the engine's H x W
 inline bool potts_kind(int kind) { return kind == EOSVOS_LOSS_POTTS; }                         // ... and reads the last forward's frames
-// (7 and 11 are unassigned on purpose, see include/eosvos.h)
+// (7 and 11 are unassigned on purpose, see include/eosvos.h; 14 and up are unknown)
 inline bool loss_kind_ok(int kind) {
   return (kind >= EOSVOS_LOSS_BCE && kind <= EOSVOS_LOSS_BOOTSTRAPPED_BCE) || frame_shape_kind(kind) || potts_kind(kind);
 }
@@ -2365,10 +2381,14 @@ int ignore_check(const float* v) {
   return 0;
 }
 constexpr int PROP_MAX_FRAMES = 1024;
+// clamp((min(H, W) + 48) / 96, 1, 16): one erosion per 96 pixels of the frame's short side, 5 at 480 x 854.  Untuned.
+inline int cldice_default_depth(int H, int W) { return std::min(CLDICE_MAX_DEPTH, std::max(1, (std::min(H, W) + 48) / 96)); }
+inline int cldice_depth_of(const eosvos_engine* e) { return e->cldice_depth ? e->cldice_depth : cldice_default_depth(e->H, e->W); }
 // The scratch some kinds need beside the gradient, sized for the engine's largest batch and allocated when such a kind is
 // first selected or used: the Lovasz kinds' sort buffers, the bootstrapped BCE's histograms, state and partials (for maxB
 // sets; their size does not depend on the number of pixels), the boundary-F kinds' per-pixel maps and partials, the surface
-// loss's distance words (4 bytes per pixel of the largest batch) and partials.
+// loss's distance words (4 bytes per pixel of the largest batch) and partials, the centreline loss's planes and levels
+// (6 (depth + 1) + 24 bytes per pixel of the largest batch, for the depth in use when it is allocated: loss_eval).
 const struct {
   bool (*uses)(int kind);
   float* eosvos_engine::*buf;
@@ -2394,6 +2414,10 @@ const struct {
      [](const eosvos_engine* e) { return (int64_t)surface_scratch_floats((int64_t)e->maxB * e->H * e->W, e->maxB); },
      [](const eosvos_engine* e) { return (int64_t)std::max(e->H, e->W); }, (int64_t)4097,
      "surface: frames larger than 4096 pixels a side are not supported", "surface: out of device memory for the distance words"},
+    {cldice_kind, &eosvos_engine::cldice_scratch,
+     [](const eosvos_engine* e) { return (int64_t)cldice_scratch_floats((int64_t)e->maxB * e->H * e->W, e->maxB, cldice_depth_of(e)); },
+     [](const eosvos_engine* e) { return (int64_t)std::max(e->H, e->W); }, (int64_t)4097,
+     "cldice: frames larger than 4096 pixels a side are not supported", "cldice: out of device memory for the skeleton levels"},
 };
 // the scratch of `kind`, if it needs one: called wherever a kind is about to be used or is selected; 0 on success
 int loss_scratch_ensure(eosvos_engine* e, int kind) {
@@ -2405,6 +2429,7 @@ int loss_scratch_ensure(eosvos_engine* e, int kind) {
       (void)hipGetLastError();              // the failed hipMalloc must not surface in a later call's launch check
       return fail(s.no_memory);
     }
+    if (cldice_kind(kind)) e->cldice_levels_held = cldice_depth_of(e) + 1;
   }
   return 0;
 }
@@ -2454,6 +2479,16 @@ int loss_eval(eosvos_engine* e, int kind, const float* logits, const float* mask
     return fail("boundary_f: the loss needs the frame's shape, so n must be the engine's H * W (one image); use eosvos_boundary_f for another shape");
   if (surface_kind(kind) && n_per_image != (int64_t)e->H * e->W)
     return fail("surface: the loss needs the frame's shape, so n must be the engine's H * W (one image); use eosvos_surface_loss for another shape");
+  if (cldice_kind(kind)) {
+    if (n_per_image != (int64_t)e->H * e->W)
+      return fail("cldice: the loss needs the frame's shape, so n must be the engine's H * W (one image); use eosvos_cldice_loss for another shape");
+    if (e->cldice_scratch && cldice_depth_of(e) + 1 > e->cldice_levels_held) {     // deeper than the buffer holds: a larger one
+      HIPOK(hipStreamSynchronize(e->s));                                           // earlier launches may still read the old one
+      e->ffree(e->cldice_scratch);
+      e->cldice_scratch = nullptr;
+      e->cldice_levels_held = 0;
+    }
+  }
   if (potts_kind(kind)) {                // on the logits of the last forward only: its frames are the engine's copy of that forward's
     PottsParams q;
     if (logits != e->logits || e->lastB < 1 || images > e->lastB || n_per_image != (int64_t)e->H * e->W)
@@ -2475,6 +2510,8 @@ int loss_eval(eosvos_engine* e, int kind, const float* logits, const float* mask
   } else if (surface_kind(kind)) {
     launch_surface(logits, masks, dlogits, loss, e->surface_scratch, e->H, e->W, images,
                    e->surface_cap ? e->surface_cap : surface_default_cap(e->H, e->W), ignore, e->s);
+  } else if (cldice_kind(kind)) {
+    launch_cldice(logits, masks, dlogits, loss, e->cldice_scratch, e->H, e->W, images, cldice_depth_of(e), ignore, e->s);
   } else {
     launch_loss(kind, logits, masks, dlogits, loss, e->bce_partial, n_per_image * images, ignore, e->s);
   }
@@ -3368,6 +3405,43 @@ int eosvos_surface_weights(eosvos_engine* e, const float* masks, int images, int
   int32_t* const c = c_out ? c_out : (int32_t*)scratch_at(e, L.g);
   launch_surface_distance(masks, images, height, width, l, ignore, scratch_at(e, L.g), c, e->s);
   if (w_out) launch_surface_weights(c, w_out, (int64_t)np, l, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+
+// ---- the centreline loss: its depth on the engine, the loss and the soft skeleton on caller tensors of any frame shape -------
+static int cldice_check(const char* who, int images, int height, int width, int depth, const float* ignore) {
+  const std::string w(who);
+  if (images < 1 || images > 65535) return fail(w + ": between 1 and 65535 images per call");
+  if (height < 1 || height > 4096 || width < 1 || width > 4096) return fail(w + ": frames of 1 .. 4096 pixels a side");
+  if (depth < 0 || depth > CLDICE_MAX_DEPTH) return fail(w + ": the depth must be 1 .. 16, or 0 for the frame-size default");
+  return ignore_check(ignore);
+}
+int eosvos_set_loss_cldice(eosvos_engine* e, int depth) {
+  if (!e) return fail("null engine");
+  if (depth < 0 || depth > CLDICE_MAX_DEPTH) return fail("the cldice depth must be 1 .. 16, or 0 for the frame-size default");
+  e->cldice_depth = depth;
+  return 0;
+}
+int eosvos_cldice_loss(eosvos_engine* e, const float* logits, const float* masks, int images, int height, int width, int depth,
+                       const float* ignore, float* loss_out, float* dlogits_out) {
+  if (!e || !logits || !masks || !loss_out) return fail("cldice_loss: null argument");
+  if (cldice_check("cldice_loss", images, height, width, depth, ignore)) return 1;
+  const int k = depth ? depth : cldice_default_depth(height, width);
+  const CldiceLayout L((size_t)cldice_scratch_floats((int64_t)images * height * width, images, k));
+  if (scratch_for(e, "cldice_loss", L, images)) return 1;
+  launch_cldice(logits, masks, dlogits_out, loss_out, (float*)scratch_at(e, L.words), height, width, images, k, ignore, e->s);
+  HIPOK(hipGetLastError());
+  return 0;
+}
+int eosvos_soft_skeleton(eosvos_engine* e, const float* maps, const float* masks, int images, int height, int width, int depth,
+                         const float* ignore, float* out) {
+  if (!e || !maps || !out) return fail("soft_skeleton: null argument");
+  if (cldice_check("soft_skeleton", images, height, width, depth, ignore)) return 1;
+  const int k = depth ? depth : cldice_default_depth(height, width);
+  const CldiceLayout L((size_t)cldice_skeleton_scratch_floats((int64_t)images * height * width));
+  if (scratch_for(e, "soft_skeleton", L, images)) return 1;
+  launch_cldice_skeleton(maps, masks, out, (float*)scratch_at(e, L.words), height, width, images, k, ignore, e->s);
   HIPOK(hipGetLastError());
   return 0;
 }

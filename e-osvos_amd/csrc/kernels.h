@@ -493,6 +493,22 @@ void launch_surface_loss(const float* logits, const float* gt, const int32_t* c,
                          int W, int images, int cap, const float* ignore, hipStream_t s);
 void launch_surface(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int H, int W, int images,
                     int cap, const float* ignore, hipStream_t s);
+// Topology-aware centreline loss (cldice_kernels.hip; the definition: include/eosvos.h at EOSVOS_LOSS_CLDICE): `images` maps of
+// H x W pixels (H, W <= 4096, images <= 65535), depth in [1, CLDICE_MAX_DEPTH].  No atomics, fixed-order sums, exact selections:
+// bit-reproducible.  Every word of the scratch that a launch reads is written by a launch of the same call before it.
+//   launch_cldice            3 depth + 8 launches (2 depth + 5 without dlogits, which may be null): the mean over the images of
+//                            1 - 2 Tp Ts / (Tp + Ts), and its gradient; scratch: cldice_scratch_floats(images * H * W, images,
+//                            depth) words, 6 (depth + 1) + 24 bytes per pixel and the partials, 8-byte aligned
+//   launch_cldice_skeleton   2 depth + 3 launches: out [image][H][W] = the soft skeleton S of maps in [0, 1], 0 where `masks`
+//                            (null: the maps themselves) hold the void label; scratch: two planes
+constexpr int CLDICE_MAX_DEPTH = 16;
+constexpr int CLDICE_BLOCKS = 1024;              // cap of the grid per image (256 threads each; more pixels: grid-stride)
+int64_t cldice_scratch_floats(int64_t n_total, int max_images, int depth);
+int64_t cldice_skeleton_scratch_floats(int64_t n_total);
+void launch_cldice(const float* logits, const float* gt, float* dlogits, float* loss, float* scratch, int H, int W, int images,
+                   int depth, const float* ignore, hipStream_t s);
+void launch_cldice_skeleton(const float* maps, const float* masks, float* out, float* scratch, int H, int W, int images, int depth,
+                            const float* ignore, hipStream_t s);
 // Weighted sum of n_terms (1 .. EOSVOS_LOSS_MAX_TERMS) evaluated losses (misc_kernels.hip; the rule: include/eosvos.h at
 // eosvos_set_loss_sum): out[i] = w0 * g0[i] (+ w1 * g1[i] ...) over n elements, *loss the same expression of vals[0 .. n_terms),
 // which are copied unweighted to terms[0 .. n_terms).  grads / weights: host arrays; vals, out, loss, terms: device.  Every

@@ -95,6 +95,12 @@ struct PottsLayout : ScratchLayout {
   ScratchAt<float> partial;
   explicit PottsLayout(size_t words) : partial(take<float>("partial", words)) {}
 };
+// words = cldice_scratch_floats / cldice_skeleton_scratch_floats of kernels.h: the centreline loss's fp64 partials (first, so
+// the region is taken as 8-byte words), planes, per-level increments and codes; every word is written before it is read
+struct CldiceLayout : ScratchLayout {
+  ScratchAt<double> words;
+  explicit CldiceLayout(size_t floats) : words(take<double>("words", (floats + 1) / 2)) {}
+};
 struct LucidLayersLayout : ScratchLayout {                     // the visible-pixel counts [n][8 layers] start out as 0
   ScratchAt<int> counts;
   explicit LucidLayersLayout(size_t n) : counts(take<int>("counts", n * 8)) { clear(0, end); }

@@ -10,7 +10,7 @@ import functools
 
 import torch
 
-from . import _ffi, bootstrap, boundary, loss_sum, potts, surface
+from . import _ffi, bootstrap, boundary, cldice, loss_sum, potts, surface
 from .loss_names import LOSS_KINDS, resolve_cap, resolve_loss, resolve_radius  # noqa: F401  (their home; callers import them from here)
 from .topology import ARCH_ID, norm_layers, trainable
 
@@ -68,12 +68,13 @@ def _touched(*tensors):
 LR_LEVELS = {'NEURON': 0, 'TENSOR': 1, 'SINGLE': 2, 'PARAM': 3}      # include/eosvos.h EOSVOS_LR_*
 # One resolved `loss_func`: the ctypes arrays of its n kinds and weights, whether the engine combines them (a spelling with
 # '+' or '*') or runs kinds[0]'s own launches alone, and the fraction / radius / cap the spelling or its keyword carries (None:
-# the engine's current value stays), and the (radius or None, dilation or None) of a `potts` term (None without one).
-LossSpec = collections.namedtuple('LossSpec', 'n kinds weights combine fraction radius cap window')
+# the engine's current value stays), the (radius or None, dilation or None) of a `potts` term (None without one), and the depth a
+# `cldice` term carries (None: the engine's stays).
+LossSpec = collections.namedtuple('LossSpec', 'n kinds weights combine fraction radius cap window depth')
 
 
 @functools.lru_cache(maxsize=64, typed=True)
-def _resolve(name, fraction, radius, cap=None, window=None):
+def _resolve(name, fraction, radius, cap=None, window=None, depth=None):
     """A sum spelling (`loss_sum.resolve`, `loss_sum.resolve_cap`) or a plain name (`resolve_loss` / `resolve_radius` /
     `resolve_cap`, one term of weight 1) as a
     LossSpec, kept per spelling: splitting and checking one takes ~10 us on the host, which a loss whose launches take 30 us
@@ -81,12 +82,13 @@ def _resolve(name, fraction, radius, cap=None, window=None):
     combine = loss_sum.is_sum(name)
     if combine:
         kinds, weights, _, f, r = loss_sum.resolve(name, fraction, radius)
-        c, w = loss_sum.resolve_cap(name, cap), loss_sum.resolve_window(name, window)
+        c, w, k = loss_sum.resolve_cap(name, cap), loss_sum.resolve_window(name, window), loss_sum.resolve_depth(name, depth)
     else:
-        kind, f = resolve_loss(name, fraction, radius, cap, window)
+        kind, f = resolve_loss(name, fraction, radius, cap, window, depth)
         kinds, weights, r, c, w = [kind], [1.0], resolve_radius(name, radius), resolve_cap(name, cap), potts.resolve_window(name, window)
+        k = cldice.resolve_depth(name, depth)
     n = len(kinds)
-    return LossSpec(n, (ctypes.c_int * n)(*kinds), (ctypes.c_float * n)(*weights), combine, f, r, c, w)
+    return LossSpec(n, (ctypes.c_int * n)(*kinds), (ctypes.c_float * n)(*weights), combine, f, r, c, w, k)
 
 
 def check_ignore(ignore):
@@ -225,14 +227,15 @@ class Engine:
         self.lr_level, self.lr_log, self.n_lr_store = level, bool(use_log), n
         self.synchronize()
 
-    def set_loss(self, name, ignore=None, fraction=None, radius=None, cap=None, window=None):
+    def set_loss(self, name, ignore=None, fraction=None, radius=None, cap=None, window=None, depth=None):
         """Loss of finetune_step / meta_grad (`loss_func`, helper_func.py:28-56) and its void label (None: every pixel counts).
         `bootstrapped_cross_entropy_<P>` or `fraction=` also set the engine's bootstrap fraction, `boundary_f_<r>` /
         `cross_entropy_and_boundary_f_<r>` or `radius=` its boundary radius, `surface_<L>` or `cap=` its surface cap,
-        `potts_<r>` / `potts_<r>x<d>` or `window=` its potts window (see `_loss_spec`).  A sum spelling
+        `potts_<r>` / `potts_<r>x<d>` or `window=` its potts window, `cldice_<k>` or `depth=` its cldice depth (see
+        `_loss_spec`).  A sum spelling
         (`0.5*lovasz_hinge+boundary_f_4`, `loss_sum.py`) selects `eosvos_set_loss_sum`; a single name returns to one kind."""
         try:
-            spec = self._loss_spec(name, fraction, radius, cap, window)
+            spec = self._loss_spec(name, fraction, radius, cap, window, depth)
         except KeyError:
             raise NotImplementedError(name) from None   # helper_func.py:55-56
         v = None if ignore is None else check_ignore(ignore)
@@ -260,6 +263,13 @@ class Engine:
         _ffi.check(self.lib.eosvos_set_loss_surface(self.h, 0 if cap == 0 and not isinstance(cap, bool)
                                                     else surface.check_cap(cap)))
 
+    def set_loss_cldice(self, depth):
+        """The depth (the number of erosions of the soft skeleton) of `cldice` for every later evaluation on this engine
+        (`eosvos_set_loss_cldice`): 1 .. 16, or 0 for the frame-size default `cldice.default_depth(H, W)`, which a new engine
+        has.  The default is untuned."""
+        _ffi.check(self.lib.eosvos_set_loss_cldice(self.h, 0 if depth == 0 and not isinstance(depth, bool)
+                                                   else cldice.check_depth(depth)))
+
     def set_loss_potts(self, window=None, dilation=None, sigma_xy=None, sigma_rgb=None):
         """Window radius (1 .. 7), dilation (1 .. 4, radius * dilation <= 16) and sigmas (finite, > 0) of `potts` for every
         later evaluation on this engine (`eosvos_set_loss_potts`).  None keeps what the engine has, 0 returns to the default
@@ -280,10 +290,12 @@ class Engine:
         _ffi.check(self.lib.eosvos_set_loss_potts(self.h, now['window'], now['dilation'], now['sigma_xy'], now['sigma_rgb']))
         self._potts = now
 
-    def _loss_spec(self, name, fraction=None, radius=None, cap=None, window=None):
-        """The LossSpec of a spelled `loss_func` (`_resolve`); a fraction, radius, cap or window carried by the spelling or the
-        keyword becomes the engine's before the call that follows."""
-        spec = _resolve(name, fraction, radius, cap, window)
+    def _loss_spec(self, name, fraction=None, radius=None, cap=None, window=None, depth=None):
+        """The LossSpec of a spelled `loss_func` (`_resolve`); a fraction, radius, cap, window or depth carried by the spelling or
+        the keyword becomes the engine's before the call that follows."""
+        spec = _resolve(name, fraction, radius, cap, window, depth)
+        if spec.depth is not None:
+            self.set_loss_cldice(spec.depth)
         if spec.window is not None and spec.window != (None, None):
             self.set_loss_potts(*spec.window)
         if spec.cap is not None:
@@ -536,13 +548,13 @@ class Engine:
             self._chk_masks, self._chk_kind, self._chk_ignore = masks, 'cross_entropy', None
         return loss
 
-    def loss(self, kind, masks, ignore=None, fraction=None, radius=None, cap=None, window=None):
+    def loss(self, kind, masks, ignore=None, fraction=None, radius=None, cap=None, window=None, depth=None):
         """kind: a compute_loss name (helper_func.py:28-56, see LOSS_KINDS); leaves dL/dlogits.  `ignore`: the void label --
         pixels whose mask equals it are in no sum, count or ranking and get gradient 0 (`eosvos_loss_ignore`).  `fraction`:
         of `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, `cap`: of `surface`, `window`: of `potts` (which
-        reads the frames of the last forward and not the masks), as in `set_loss`.  A sum spelling evaluates the weighted sum
-        of its terms (`eosvos_loss_sum`); `last_loss_terms` then gives the terms' own values."""
-        spec = self._loss_spec(kind, fraction, radius, cap, window)
+        reads the frames of the last forward and not the masks), `depth`: of `cldice`, as in `set_loss`.  A sum spelling
+        evaluates the weighted sum of its terms (`eosvos_loss_sum`); `last_loss_terms` then gives the terms' own values."""
+        spec = self._loss_spec(kind, fraction, radius, cap, window, depth)
         ignore = None if ignore is None else check_ignore(ignore)
         assert masks.is_cuda and masks.dtype == torch.float32 and masks.is_contiguous()
         out = torch.empty(1, device=self.device)
@@ -551,20 +563,20 @@ class Engine:
             self._chk_masks, self._chk_kind, self._chk_ignore = masks, kind, ignore
         return out
 
-    def loss_of(self, kind, logits, masks, ignore=None, fraction=None, radius=None, cap=None):
+    def loss_of(self, kind, logits, masks, ignore=None, fraction=None, radius=None, cap=None, depth=None):
         """Value of a compute_loss loss on arbitrary device tensors (one sample of a batch for
         `batch_average: False`); no gradient is kept.  `ignore`: as in `loss` (`eosvos_loss_tensors_ignore`); `fraction`: of
-        `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, `cap`: of `surface`, as in `set_loss`.  The boundary
-        kinds and `surface` need the frame's shape: they take one image of the engine's H * W elements only (`boundary_f` and
-        `surface_loss` below take any shape).  `potts` is refused: no frames travel with the tensors (`potts_loss` takes them)."""
+        `bootstrapped_cross_entropy`, `radius`: of the boundary kinds, `cap`: of `surface`, `depth`: of `cldice`, as in `set_loss`.  The
+        boundary kinds, `surface` and `cldice` need the frame's shape: they take one image of the engine's H * W elements only
+        (`boundary_f`, `surface_loss` and `cldice_loss` below take any shape).  `potts` is refused: no frames travel with the tensors (`potts_loss` takes them)."""
         logits, masks = logits.contiguous(), masks.contiguous()
         assert logits.is_cuda and masks.is_cuda and logits.numel() == masks.numel()
         out = torch.empty(1, device=self.device)
-        self._loss_on_tensors(self._loss_spec(kind, fraction, radius, cap), logits, masks,
+        self._loss_on_tensors(self._loss_spec(kind, fraction, radius, cap, None, depth), logits, masks,
                               None if ignore is None else check_ignore(ignore), out)
         return out
 
-    def loss_grad_of(self, name, logits, masks, ignore=None, fraction=None, radius=None, cap=None):
+    def loss_grad_of(self, name, logits, masks, ignore=None, fraction=None, radius=None, cap=None, depth=None):
         """(loss, dL/dlogits of the logits' shape) of a single kind or a sum on arbitrary device tensors, the elements one set
         as in `loss_of` (`eosvos_loss_sum_tensors`; a single kind is the sum of one term of weight 1, which has that kind's
         bits).  At most the engine's largest batch of pixels; the engine's own gradient is untouched.  A `potts` term is refused
@@ -575,7 +587,7 @@ class Engine:
         v = None if ignore is None else check_ignore(ignore)
         out, grad = torch.empty(1, device=self.device), torch.empty_like(logits)
         try:
-            spec = self._loss_spec(name, fraction, radius, cap)
+            spec = self._loss_spec(name, fraction, radius, cap, None, depth)
         except KeyError:
             raise NotImplementedError(f"loss_func='{name}'") from None
         self._loss_on_tensors(spec, logits, masks, v, out, grad)
@@ -633,6 +645,39 @@ class Engine:
         c, wt = torch.empty(masks.shape, dtype=torch.int32, device=self.device), torch.empty_like(masks)
         _ffi.check(self.lib.eosvos_surface_weights(self.h, _ptr(masks), b, h, w, cap, v, _ptr(c), _ptr(wt)))
         return c, wt
+
+    def _cldice_args(self, maps, depth, ignore):
+        """(images, H, W, the depth as the library takes it, the void label as a ctypes pointer or None) of (B, H, W) / (H, W)."""
+        assert maps.is_cuda and maps.dtype == torch.float32 and maps.is_contiguous() and maps.dim() in (2, 3)
+        v = None if ignore is None else ctypes.byref(ctypes.c_float(check_ignore(ignore)))
+        return (maps.shape[0] if maps.dim() == 3 else 1, *maps.shape[-2:], 0 if depth is None else cldice.check_depth(depth), v)
+
+    def cldice_loss(self, logits, masks, depth=None, ignore=None):
+        """`cldice` of device tensors (B, H, W) or (H, W) of any frame size up to 4096 a side (`eosvos_cldice_loss`); `depth`
+        None: that shape's default `cldice.default_depth(H, W)` (untuned).  Returns (loss, dL/dlogits of the logits' shape);
+        the engine's own gradient is untouched."""
+        self._check_stream()
+        logits, masks = logits.contiguous(), masks.contiguous()
+        assert logits.is_cuda and logits.dtype == torch.float32 and logits.shape == masks.shape
+        b, h, w, depth, v = self._cldice_args(masks, depth, ignore)
+        out, grad = torch.empty(1, device=self.device), torch.empty_like(logits)
+        _ffi.check(self.lib.eosvos_cldice_loss(self.h, _ptr(logits), _ptr(masks), b, h, w, depth, v, _ptr(out), _ptr(grad)))
+        return out, grad
+
+    def soft_skeleton(self, maps, depth, ignore=None, masks=None):
+        """The soft skeleton S (rules 1 and 2 of `cldice.py`) of device maps in [0, 1], (B, H, W) or (H, W)
+        (`eosvos_soft_skeleton`), of the maps' shape: 0 at void pixels, which are where `masks` (None: the maps themselves)
+        equal `ignore`.  The debugging and visualisation view of the selection chain."""
+        self._check_stream()
+        maps = maps.contiguous()
+        b, h, w, depth, v = self._cldice_args(maps, depth, ignore)
+        if masks is not None:
+            masks = masks.contiguous()
+            assert masks.is_cuda and masks.dtype == torch.float32 and masks.shape == maps.shape
+        out = torch.empty_like(maps)
+        _ffi.check(self.lib.eosvos_soft_skeleton(self.h, _ptr(maps), None if masks is None else _ptr(masks), b, h, w, depth, v,
+                                                 _ptr(out)))
+        return out
 
     def potts_loss(self, logits, frames, window=None, dilation=None, sigma_xy=None, sigma_rgb=None):
         """`potts` of device logits (B, H, W) or (H, W) against their frames (B, 3, H, W) or (3, H, W), any frame size up to

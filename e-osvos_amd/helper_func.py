@@ -25,6 +25,10 @@ the engine's cap (by default a quarter of the frame's short side, untuned), `sur
 target (void pixels get its gradient too), on the engine's window (radius 3, dilation 2 by default, untuned), `potts_<r>` /
 `potts_<r>x<d>` for another, or `loss_kwargs={'window': r}`; it is meant as a term of a sum, e.g. `cross_entropy+0.1*potts_3x2`,
 and has no per-sample form (`batch_average: False`), which carries no frames.
+`cldice` (`cldice.py`; not in the reference) is the topology-aware centreline loss (soft clDice): how much of each map's soft
+skeleton lies inside the other map, so a cut through a thin part costs far more than the same pixels off a blob's edge; the
+engine's depth (by default one erosion per 96 pixels of the frame's short side, untuned), `cldice_<k>` for k erosions, or
+`loss_kwargs={'depth': k}`; it is meant as a term of a sum, e.g. `dice+0.5*cldice_5`.
 A `loss_func` with a '+' or a '*' is a weighted sum of up to four of these (`loss_sum.py`), e.g. `0.5*lovasz_hinge+boundary_f_4`.
 """
 import random
@@ -48,6 +52,7 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
     names = loss_sum.resolve(loss_func, loss_kwargs.get('fraction'), loss_kwargs.get('radius'), per_image)[2]
     loss_sum.resolve_cap(loss_func, loss_kwargs.get('cap'))
     loss_sum.resolve_window(loss_func, loss_kwargs.get('window'))
+    loss_sum.resolve_depth(loss_func, loss_kwargs.get('depth'))
     if 'class_balanced_cross_entropy' in names and not loss_kwargs.get('size_average', True):
         raise NotImplementedError('class_balanced_cross_entropy with size_average=False')
     if not per_image:
@@ -57,7 +62,7 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
         raise RuntimeError('compute_loss needs logits produced by eosvos_amd.networks.DeepLabV3Plus '
                            '(there is no CPU/eager path)')
     gts = gts.contiguous().float()
-    kw = {k: loss_kwargs[k] for k in ('ignore', 'fraction', 'radius', 'cap', 'window') if loss_kwargs.get(k) is not None}
+    kw = {k: loss_kwargs[k] for k in ('ignore', 'fraction', 'radius', 'cap', 'window', 'depth') if loss_kwargs.get(k) is not None}
     if loss_kwargs.get('batch_average', True):
         loss = eng.loss(loss_func, gts, **kw).view(())      # also leaves dL/dlogits in the engine
         loss._eosvos_engine = eng

@@ -25,6 +25,11 @@ POTTS = 'potts'
 # three above stay as they are, and 11 stays unassigned like 7
 POTTS_KINDS = {POTTS: 12}
 MAX_WINDOW, MAX_DILATION, MAX_HALO = 7, 4, 16      # the CRF's limits: radius, dilation, radius * dilation
+CLDICE = 'cldice'
+# the topology-aware centreline loss (cldice.py); it needs the frame's shape like the boundary kinds and `surface`.  A fifth table
+# with id 13: the four above stay as they are, 7 and 11 stay unassigned and 14 is unknown
+CLDICE_KINDS = {CLDICE: 13}
+MAX_DEPTH = 16
 _POTTS_SUFFIX = re.compile(r'_([1-9][0-9]*)(?:x([1-9][0-9]*))?\Z', re.ASCII)
 
 
@@ -83,6 +88,13 @@ def parse_potts(name):
     return POTTS, r, d
 
 
+def parse_cldice(name):
+    """`cldice` -> (name, None): the engine's depth; `cldice_<k>`, k an integer 1 .. 16 without a leading zero -> (name, k).  A
+    name that does not start with `cldice` is returned as (name, None); anything else under the prefix raises
+    NotImplementedError like an unknown loss name."""
+    return parse_suffix(name, (CLDICE,), MAX_DEPTH)
+
+
 def check_fraction(fraction):
     """The fraction as the float the library receives: in (0, 1]."""
     f = float(np.float32(fraction))
@@ -128,16 +140,26 @@ def check_window(window, dilation=None):
     return int(window), int(dilation)
 
 
-def resolve_loss(name, fraction=None, radius=None, cap=None, window=None):
+def check_depth(depth):
+    """The depth (the number of erosions of the soft skeleton) as the int the library receives: a whole number 1 .. 16."""
+    if isinstance(depth, bool) or not isinstance(depth, (int, float)) or not math.isfinite(depth) or depth != int(depth) \
+            or not 1 <= int(depth) <= MAX_DEPTH:
+        raise ValueError(f'depth={depth!r}: the cldice depth must be a whole number in 1 .. {MAX_DEPTH}')
+    return int(depth)
+
+
+def resolve_loss(name, fraction=None, radius=None, cap=None, window=None, depth=None):
     """A spelled loss name -> (kind id, fraction or None).  `bootstrapped_cross_entropy_<P>` carries P percent; `fraction`
     is the keyword form, for that kind only; the two may not disagree.  None: the engine's current fraction stays.  A bad
     spelling under the bootstrap prefix raises NotImplementedError, any other unknown name KeyError.  The kinds that need the
     frame's shape (BOUNDARY_KINDS) are consulted after LOSS_KINDS and give (kind id, None); their radius, from the name
     or `radius=`, is `resolve_radius`'s, which this call checks too.  SURFACE_KINDS is consulted last, in the same way, its cap
-    (`resolve_cap`) checked here too.  POTTS_KINDS comes after it, its window (`resolve_window`) checked here too."""
+    (`resolve_cap`) checked here too.  POTTS_KINDS comes after it, its window (`resolve_window`) checked here too, and
+    CLDICE_KINDS after that with its depth (`resolve_depth`)."""
     radius = resolve_radius(name, radius)
     cap = resolve_cap(name, cap)
     window = resolve_window(name, window)
+    depth = resolve_depth(name, depth)
     base, f = parse_bootstrap(name)
     if base not in LOSS_KINDS and parse_boundary(name)[0] in BOUNDARY_KINDS:
         if fraction is not None:
@@ -151,6 +173,10 @@ def resolve_loss(name, fraction=None, radius=None, cap=None, window=None):
         if fraction is not None:
             raise ValueError(f"fraction= belongs to '{BOOTSTRAP}', not to '{name}'")
         return POTTS_KINDS[POTTS], None
+    if base not in LOSS_KINDS and parse_cldice(name)[0] in CLDICE_KINDS:
+        if fraction is not None:
+            raise ValueError(f"fraction= belongs to '{BOOTSTRAP}', not to '{name}'")
+        return CLDICE_KINDS[CLDICE], None
     kind = LOSS_KINDS[base]
     if fraction is not None:
         if base != BOOTSTRAP:
@@ -206,3 +232,17 @@ def resolve_window(name, window=None):
             raise ValueError(f"loss_func='{name}' and window={window!r}: radius * dilation must be at most {MAX_HALO}")
         r = window
     return r, d
+
+
+def resolve_depth(name, depth=None):
+    """The depth a spelled loss name asks for: `cldice_<k>` carries k, `depth` is the keyword form, for that kind only; the two
+    may not disagree.  None: the engine's current depth stays."""
+    base, k = parse_cldice(name)
+    if depth is not None:
+        if base not in CLDICE_KINDS:
+            raise ValueError(f"depth= belongs to '{CLDICE}', not to '{name}'")
+        depth = check_depth(depth)
+        if k is not None and k != depth:
+            raise ValueError(f"loss_func='{name}' and depth={depth!r} disagree")
+        k = depth
+    return k

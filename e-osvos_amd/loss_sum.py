@@ -17,8 +17,9 @@ from fractions import Fraction
 
 import numpy as np
 
-from .loss_names import (BOOTSTRAP, BOUNDARY_KINDS, POTTS, POTTS_KINDS, SURFACE, SURFACE_KINDS, parse_boundary, parse_bootstrap,
-                         parse_potts, parse_surface, resolve_loss, resolve_radius)
+from .loss_names import (BOOTSTRAP, BOUNDARY_KINDS, CLDICE, CLDICE_KINDS, POTTS, POTTS_KINDS, SURFACE, SURFACE_KINDS, parse_boundary,
+                         parse_bootstrap, parse_cldice, parse_potts, parse_surface, resolve_loss, resolve_radius)
+from .loss_names import resolve_depth as _term_depth
 from .loss_names import resolve_cap as _term_cap
 from .loss_names import resolve_window as _term_window
 
@@ -126,6 +127,18 @@ def resolve_window(name, window=None):
     if window is not None and not potts_terms:
         raise ValueError(f"window= belongs to '{POTTS}', which is no term of '{name}'")
     return _term_window(potts_terms[0], window) if potts_terms else None
+
+
+def resolve_depth(name, depth=None):
+    """The depth a spelled sum (or single name) carries, or None: `depth` belongs to the one `cldice` term as `cap` belongs to
+    `surface` in `resolve_cap`: without such a term, or against a disagreeing suffix, ValueError; two `cldice` terms (they share
+    the engine's one depth) are a ValueError too."""
+    cldice_terms = [t for _, t in parse(name) if parse_cldice(t)[0] in CLDICE_KINDS]
+    if len(cldice_terms) > 1:
+        raise ValueError(f"loss_func='{name}' names a loss twice")
+    if depth is not None and not cldice_terms:
+        raise ValueError(f"depth= belongs to '{CLDICE}', which is no term of '{name}'")
+    return _term_depth(cldice_terms[0], depth) if cldice_terms else None
 
 
 def combine_host(values, grads, weights):

@@ -331,6 +331,54 @@ int eosvos_set_loss_potts(eosvos_engine* e, int window, int dilation, float sigm
  * before any launch: the outputs stay untouched. */
 int eosvos_potts_loss(eosvos_engine* e, const float* logits, const float* frames, int images, int height, int width, int window,
                       int dilation, float sigma_xy, float sigma_rgb, float* loss_out, float* dlogits_out);
+/* Topology-aware centreline loss, `cldice`: the soft centreline Dice of Shit et al., "clDice -- a Novel Topology-Preserving Loss
+ * Function for Tubular Structure Segmentation" (CVPR 2021).  Not in the reference.  No other kind sees connectivity: a cut
+ * through a thin part removes skeleton and costs far more here than the same number of pixels shaved off a blob's edge.  Meant
+ * as a term beside a region loss (`dice+0.5*cldice_5`).  Per image of H x W pixels, z the logits, y the targets in [0, 1], v
+ * the void label, V = {y != v}, p = sigmoid(z).  Every window is clipped to the frame and ranges over pixels of V only; a void
+ * pixel is in no window, no sum and no ranking.  For a map x (p, or y), x_0 = x, and the levels j = 0 .. k (k the depth):
+ *   1. v_j(i) = the first minimum of x_j over (up, centre, down);  h_j(i) = the first minimum over (left, centre, right);
+ *      x_{j+1}(i) = min(v_j, h_j);  o_j(i) = the first maximum of x_{j+1} over the 3 x 3 window in row-major order;
+ *      d_j(i) = max(x_j(i) - o_j(i), 0).
+ *   2. u = 1, then u = u (1 - d_j) for j = 0 .. k in ascending order, every difference and product rounded on its own;
+ *      S(x) = 1 - u: the published recurrence skel + relu(delta - skel delta) in closed form.  The selections are exact, so the
+ *      numpy float32 expression reproduces the x_j and S planes bit for bit.
+ *   3. Tp = (sum_V S(p) y + 1) / (sum_V S(p) + 1);  Ts = (sum_V S(y) p + 1) / (sum_V S(y) + 1);  image loss =
+ *      1 - 2 Tp Ts / (Tp + Ts), 0 without a valid pixel;  loss = the mean over the images.  An empty or a full target is no
+ *      special case; a NaN logit at a valid pixel makes the loss NaN.
+ *   4. The gradient follows the selections (torch's CPU rules for the published max_pool2d / torch.min form): a window routes to
+ *      its first extremum in row-major order; min(v, h) routes to v's pixel if v < h, to h's if h < v, half to each if v = h.
+ *      S(y) carries none.  With Bq = sum_V S(p) + 1, Sy = sum_V S(y) + 1, cP = -2 Ts^2 / (Tp + Ts)^2, cS = -2 Tp^2 / (Tp + Ts)^2:
+ *      g_S(i) = cP (y_i - Tp) / Bq;  Gd_j(i) = [d_j(i) > 0] g_S(i) prod_{m != j} (1 - d_m(i)), the product in ascending m from 1;
+ *      T_{k+1}(q) = -sum_{i in N3x3(q), arg o_k(i) = q} Gd_k(i);
+ *      T_j(q) = Gd_j(q) + sum_{i in cross(q)} w_j(i -> q) T_{j+1}(i) - [j >= 1] sum_{i in N3x3(q), arg o_{j-1}(i) = q} Gd_{j-1}(i),
+ *      w in {0, 1/2, 1} from the erosion's routing, both gathers in row-major order of i, the cross first;
+ *      dL/dz = (T_0 + cS S(y) / Sy) p (1 - p) / images; exactly +0 at a void pixel, whose logit never reaches the result.
+ * The depth k is per engine (eosvos_set_loss_cldice), a whole number in [1, 16]; by default clamp((min(H, W) + 48) / 96, 1, 16)
+ * (integer division), 5 at 480 x 854.  It is untuned: no J&F figure exists for it.  The kind needs the frame's shape, as the
+ * boundary kinds and the surface loss do: through eosvos_loss* and the fused entry points an image is the engine's H x W;
+ * eosvos_loss_tensors* accept n == H * W only, as one image; frames of at most 4096 pixels a side.  3 k + 8 launches (p; an
+ * erosion and a dilation per level for p and y together; the partial sums; their fixed-order fp64 reduction; the Gd_j; one
+ * backward launch for T_{k+1} and one per level, the last writing dL/dz), no atomics: loss and gradient are bit-identical from
+ * run to run.  The first use allocates a scratch of 6 (k + 1) + 24 bytes per pixel of the engine's largest batch (d_j in fp32
+ * and a 16-bit routing code per level; p, S(y), two planes each for x and T) plus 40 KB per image; a deeper evaluation later
+ * replaces it by a larger one.  A failed allocation is reported and leaves the engine usable with the other kinds. */
+#define EOSVOS_LOSS_CLDICE 13           /* (14 and up are unknown) */
+/* The depth of EOSVOS_LOSS_CLDICE for every evaluation on this engine: 1 .. 16, or 0 for the frame-size default; anything
+ * else is an error and changes nothing.  Per engine, like the boundary radius. */
+int eosvos_set_loss_cldice(eosvos_engine* e, int depth);
+/* The centreline loss on caller tensors with an explicit shape: `images` (1 .. 65535) maps of height x width, each side in
+ * [1, 4096], DEVICE pointers.  depth 1 .. 16, or 0 for this shape's default; `ignore`: null, or a HOST pointer to the void
+ * label.  The loss goes to loss_out (a device float), the gradient to dlogits_out, which may be null (none is formed).  The
+ * scratch comes from the arena of the evaluation-stage entry points, under its 512 MB cap per call.  Bad arguments return
+ * non-zero before any launch: the outputs stay untouched. */
+int eosvos_cldice_loss(eosvos_engine* e, const float* logits, const float* masks, int images, int height, int width, int depth,
+                       const float* ignore, float* loss_out, float* dlogits_out);
+/* Rules 1 and 2 alone, with the arguments and limits of eosvos_cldice_loss: out [image][H][W] fp32 = S of `maps` (values in
+ * [0, 1]), 0 at void pixels, which are where `masks` -- null: the maps themselves -- equal the void label.  The debugging and
+ * visualisation view of the selection chain. */
+int eosvos_soft_skeleton(eosvos_engine* e, const float* maps, const float* masks, int images, int height, int width, int depth,
+                         const float* ignore, float* out);
 /* eosvos_loss_bce for any kind (the forms of one evaluation, see there). */
 int eosvos_loss(eosvos_engine* e, int kind, const float* masks, int batch, float* loss_out);
 /* The value of the last loss evaluated by eosvos_loss* / eosvos_finetune_step / eosvos_meta_grad*, copied to a DEVICE
