@@ -3967,6 +3967,11 @@ int eosvos_debug_tensor(eosvos_engine* e, const char* name, float** ptr, int64_t
     for (const auto& kv : named)
       if (k == kv.first && kv.second) return tensor(kv.second);
   }
+  // GroupNorm mode, "z<ci>": the raw output of normalised conv ci after a forward, its gradient after a backward
+  if (n.size() > 1 && n.size() <= 5 && n[0] == 'z' && n.find_first_not_of("0123456789", 1) == std::string::npos) {
+    const int ci = atoi(n.c_str() + 1);
+    if (ci < (int)e->zbuf.size() && e->zbuf[ci]) return tensor(e->zbuf[ci]);
+  }
   return fail("unknown debug tensor " + n);
 }
 

@@ -1082,7 +1082,11 @@ int eosvos_mfma_probe(eosvos_engine* e, int iters, float* ms_host, double* flops
  * (the mean of layer4's output over the pixels, C = 2048), "poolout" (the branch's conv + norm + ReLU of it, C = 256), "gp"
  * (the gradient of the loss w.r.t. the pre-ReLU "poolout": the pixel sum of "g_cat"[:, 1024:1280]) and "gvec" (w.r.t. "vec");
  * "ccl_scratch": the one grow-only scratch arena that every
- * evaluation-stage entry point shares, as dims4[3] 32-bit words (null before its first use). */
+ * evaluation-stage entry point shares, as dims4[3] 32-bit words (null before its first use);
+ * "z<ci>" (decimal conv index in eosvos_num_convs order, e.g. "z0", "z17"), GroupNorm engines only: the dense
+ * {B,Ho,Wo,cout} buffer of normalised conv ci that holds its raw (pre-norm) output z after a forward and, overwritten
+ * in place, dL/dz after a backward.  On a frozen-BatchNorm engine, or for a conv without a norm layer (the classifier),
+ * the name fails like any unknown name. */
 /* Measurement aid: HIP events around every launch of the matrix-core kernels, on the stream each one runs on.
  * profile_read returns, per kernel symbol (names: max_kernels x 64 chars), launches, summed duration (ms) and summed
  * executed fp32-equivalent FLOPs since profile_launches(e, 1).  bench.py's roofline (dominant kernel by time). */

@@ -7,15 +7,19 @@ other: no ReLU gate flips anywhere, because every mask is taken from the activat
 * gradient convention: every `g_*` buffer is dL/d(post-norm, pre-ReLU output) of the layer that wrote the activation; the
   gradient on the conv side of a frozen norm is `a * g`, `a` the folded scale gamma / sqrt(var + eps) per output channel;
 * a WEIGHT link (one per conv): dW = wgrad(x, a * g), OIHW; the classifier's bias gradient is the pixel sum of its g;
-* a DATA link: one `g_*` buffer (or `gp` / `gvec` of the image-pooling branch) from the gradients and weights it is made of.
+* a DATA link: one `g_*` buffer (or `gp` / `gvec` of the image-pooling branch) from the gradients and weights it is made of;
+* GroupNorm mode (`Net(encoder, 'gn')`): same convention for `g_*`.  Every normalised conv ci keeps its raw output z in one
+  buffer (`z<ci>` after the forward pass) that the backward pass overwrites with dL/dz (here `dz<ci>`: the same engine buffer,
+  read after the step).  A GN FORWARD link recomputes the stored activation from z, a GN BACKWARD link recomputes dz from z
+  and the conv's g (a whole buffer or its channel slice); the weight and data links read dz where the frozen form reads
+  `a * g`, with no scale.
 
 Everything here is dtype-generic (fp64 for the reference, fp32 for torch's own error on the same operands), runs on the
 CPU and makes no engine call.  tests/test_backward_links_host.py proves every function against autograd on the oracle
 network; tests/test_gpu_backward_links.py feeds them the engine's buffers.
 
-Scope: DeepLabV3+ on ResNet-50 with frozen BatchNorm.  Not covered: GroupNorm mode (it overwrites the stored raw outputs
-with dz and exposes neither), resnet101, plain DeepLabV3.  The accumulating (`gsum`) meta path and the trainable boundary:
-tests/meta_links_ref.py.
+Scope: DeepLabV3+ on ResNet-50 / ResNet-101, frozen BatchNorm or GroupNorm.  Not covered: plain DeepLabV3.  The accumulating
+(`gsum`) meta path and the trainable boundary: tests/meta_links_ref.py.
 """
 from collections import namedtuple
 
@@ -31,12 +35,18 @@ WeightLink = namedtuple('WeightLink', 'ci stage x g g_c0')       # dW[ci] = wgra
 # gradient is zero wherever that activation is <= 0; convs: the convs whose data gradient it holds; misc: the kind of a
 # link that is no convolution (a key of test_gpu_misc_ops.FLOOR, or 'maxpool_bwd')
 DataLink = namedtuple('DataLink', 'out stage fn mask convs misc')
+# GroupNorm links of conv ci: T[out][:, out_c0:out_c0 + cout] = relu?(gn(T[z<ci>]) (+ T[res])); dz = d(sum(g * gn(z))) / dz with
+# g = T[g][:, g_c0:g_c0 + cout]
+GNLink = namedtuple('GNLink', 'ci stage out out_c0 res relu g g_c0')
+GN_GROUPS, GN_EPS = 16, 1e-5
 
 
 class Net:
     """Indices of the graph's convs (`topology.conv_infos` order, the engine's) and its bottleneck blocks."""
 
-    def __init__(self, encoder='resnet50'):
+    def __init__(self, encoder='resnet50', norm='bn'):
+        assert norm in ('bn', 'gn'), norm
+        self.encoder, self.gn = encoder, norm == 'gn'
         self.convs = topology.conv_infos(encoder)
         idx = {c.name: i for i, c in enumerate(self.convs)}
         self.blocks = []
@@ -100,6 +110,27 @@ def scaled(g, a):
     return g if a is None else g * a.view(1, -1, 1, 1)
 
 
+def conv_side(net, ci, g, T, A):
+    """The gradient on the conv side of conv ci's norm layer: a * g (frozen BatchNorm; g itself for the classifier), or the
+    engine's dz (GroupNorm)."""
+    if net.gn and net.convs[ci].norm:
+        return T[f'dz{ci}']
+    return scaled(g, A[ci])
+
+
+def gn_fwd(z, gamma, beta, res=None, relu=True):
+    y = F.group_norm(z, GN_GROUPS, gamma, beta, GN_EPS)
+    if res is not None:
+        y = y + res
+    return F.relu(y) if relu else y
+
+
+def gn_bwd(z, g, gamma):
+    """d(sum(g * group_norm(z))) / dz (the shift does not enter)."""
+    z = z.detach().clone().requires_grad_(True)
+    return torch.autograd.grad(F.group_norm(z, GN_GROUPS, gamma, None, GN_EPS), z, g)[0]
+
+
 def relumask(act):
     return (act > 0).to(act.dtype)
 
@@ -146,7 +177,7 @@ def weight_links(net):
 def weight_link(net, link, T, A):
     """(dW OIHW, dbias or None) of one conv from the buffers T (name -> NCHW tensor) and the per-conv scales A."""
     c = net.convs[link.ci]
-    g = scaled(T[link.g][:, link.g_c0:link.g_c0 + c.cout], A[link.ci])
+    g = conv_side(net, link.ci, T[link.g][:, link.g_c0:link.g_c0 + c.cout], T, A)
     return wgrad(T[link.x], g, c), (g.sum(dim=(0, 2, 3)) if c.bias else None)
 
 
@@ -162,7 +193,7 @@ def data_links(net):
     L = []
 
     def conv_dg(ci, g, T, W, A, in_hw):
-        return dgrad(scaled(g, A[ci]), W[ci][0], cv[ci], in_hw)
+        return dgrad(conv_side(net, ci, g, T, A), W[ci][0], cv[ci], in_hw)
 
     L.append(DataLink('g_low', 'decoder', lambda T, W, A: resize_bwd(T['dlogits'], _hw(T['d2']), False), None, (), 'resize_bwd'))
     L.append(DataLink('g_d2', 'decoder', lambda T, W, A: relumask(T['d2']) * conv_dg(net.last, T['g_low'], T, W, A, _hw(T['d2'])),
@@ -217,12 +248,59 @@ def data_links(net):
     return L
 
 
+def gn_links(net):
+    """One GNLink per normalised conv, in conv order."""
+    L = {0: GNLink(0, 'stem', 'c1', 0, None, True, 'g_c1', 0)}
+    for i, b in enumerate(net.blocks):
+        st = b['stage']
+        L[b['c1']] = GNLink(b['c1'], st, f'blk{i}.t1', 0, None, True, f'blk{i}.g_t1', 0)
+        L[b['c2']] = GNLink(b['c2'], st, f'blk{i}.t2', 0, None, True, f'blk{i}.g_t2', 0)
+        L[b['c3']] = GNLink(b['c3'], st, f'blk{i}.out', 0, f'blk{i}.dsb' if b['ds'] >= 0 else net.xin(i), True, f'blk{i}.g_out', 0)
+        if b['ds'] >= 0:
+            L[b['ds']] = GNLink(b['ds'], st, f'blk{i}.dsb', 0, None, False, f'blk{i}.g_out', 0)
+    for j, ci in enumerate(net.aspp):
+        L[ci] = GNLink(ci, 'aspp', 'cat', 256 * j, None, True, 'g_cat', 256 * j)
+    L[net.pool] = GNLink(net.pool, 'aspp', 'poolout', 0, None, True, 'gp', 0)
+    L[net.project] = GNLink(net.project, 'aspp', 'proj', 0, None, True, 'g_proj', 0)
+    L[net.dec1] = GNLink(net.dec1, 'decoder', 'dcat', 256, None, True, 'g_dcat', 256)
+    L[net.dec_a] = GNLink(net.dec_a, 'decoder', 'd1', 0, None, True, 'g_d1', 0)
+    L[net.dec_b] = GNLink(net.dec_b, 'decoder', 'd2', 0, None, True, 'g_d2', 0)
+    assert sorted(L) == [ci for ci, c in enumerate(net.convs) if c.norm]
+    return [L[ci] for ci in sorted(L)]
+
+
+def gn_fwd_link(net, l, T, GB):
+    """(recomputed, stored) activation of GN link l; GB: per conv (gamma, beta)."""
+    cout = net.convs[l.ci].cout
+    y = gn_fwd(T[f'z{l.ci}'], GB[l.ci][0], GB[l.ci][1], T[l.res] if l.res else None, l.relu)
+    return y, T[l.out][:, l.out_c0:l.out_c0 + cout]
+
+
+def gn_bwd_link(net, l, T, GB):
+    """(recomputed, stored) dz of GN link l."""
+    cout = net.convs[l.ci].cout
+    return gn_bwd(T[f'z{l.ci}'], T[l.g][:, l.g_c0:l.g_c0 + cout], GB[l.ci][0]), T[f'dz{l.ci}']
+
+
+def affines(net, state, dtype):
+    """Per conv (gamma, beta) of its norm layer from a model state dict, None for the classifier."""
+    return [(state[c.norm + '.weight'].to(dtype), state[c.norm + '.bias'].to(dtype)) if c.norm else None for c in net.convs]
+
+
+def z_names(net):
+    """The engine's names (`z<ci>`) of the raw-output buffers of a GroupNorm engine."""
+    return [f'z{ci}' for ci, c in enumerate(net.convs) if c.norm]
+
+
 def buffer_names(net):
-    """Every named buffer the links read or recompute, the input frame ('x') aside."""
+    """Every named buffer the links read or recompute, the input frame ('x') and the z / dz buffers of a GroupNorm engine
+    (`z_names`) aside."""
     names = ['c1', 'p1', 'g_c1', 'g_p1', 'cat', 'g_cat', 'vec', 'gvec', 'poolout', 'gp', 'proj', 'g_proj', 'dcat', 'g_dcat',
              'd1', 'd2', 'g_d1', 'g_d2', 'g_low', 'dlogits']
     for i in range(len(net.blocks)):
         names += [f'blk{i}.{k}' for k in ('t1', 't2', 'out', 'g_t1', 'g_t2', 'g_out')]
+        if net.gn and net.blocks[i]['ds'] >= 0:
+            names.append(f'blk{i}.dsb')                     # the shortcut's output: the residual of the block's last GroupNorm
     return names
 
 
