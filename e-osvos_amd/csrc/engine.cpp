@@ -3944,6 +3944,11 @@ int eosvos_debug_tensor(eosvos_engine* e, const char* name, float** ptr, int64_t
   const std::pair<const char*, Tensor*> named[] = {{"c1", e->c1}, {"p1", e->p1}, {"g_c1", e->g_c1}, {"g_p1", e->g_p1}, {"cat", e->cat},
       {"g_cat", e->g_cat}, {"proj", e->proj}, {"g_proj", e->g_proj}, {"dcat", e->dcat}, {"g_dcat", e->g_dcat}, {"d1", e->d1}, {"d2", e->d2},
       {"g_d1", e->g_d1}, {"g_d2", e->g_d2}};
+  // plain DeepLabV3 has no decoder: its head (t.head3) writes "d1" / "g_d1" and the classifier "lowlog" / "g_low" on the ASPP
+  // map (e->h16 x e->w16 = its stride-8 map), dense from the start of buffers that are sized for the stride-4 map
+  const int hl = e->t.v3 ? e->h16 : e->h4, wl = e->t.v3 ? e->w16 : e->w4;
+  if (e->t.v3 && (n == "d1" || n == "g_d1")) return set(n == "d1" ? e->d1->p : e->g_d1->p, hl, wl, 256);
+  if (e->t.v3 && (n == "dcat" || n == "g_dcat" || n == "d2" || n == "g_d2")) return fail("unknown debug tensor " + n + " (plain DeepLabV3 has no decoder)");
   for (const auto& kv : named)
     if (n == kv.first) return tensor(kv.second);
   // image-pooling branch of the ASPP: one vector per image
@@ -3951,8 +3956,8 @@ int eosvos_debug_tensor(eosvos_engine* e, const char* name, float** ptr, int64_t
   if (n == "gvec") return set(e->gvec, 1, 1, 2048);
   if (n == "poolout") return set(e->poolout, 1, 1, 256);
   if (n == "gp") return set(e->gp, 1, 1, 256);
-  if (n == "lowlog") return set(e->lowlog, e->h4, e->w4, 1);
-  if (n == "g_low") return set(e->g_low, e->h4, e->w4, 1);
+  if (n == "lowlog") return set(e->lowlog, hl, wl, 1);
+  if (n == "g_low") return set(e->g_low, hl, wl, 1);
   if (n == "logits") return set(e->logits, e->H, e->W, 1);
   if (n == "dlogits") return set(e->dlogits, e->H, e->W, 1);
   if (n.rfind("blk", 0) == 0) {

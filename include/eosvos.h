@@ -1086,7 +1086,10 @@ int eosvos_mfma_probe(eosvos_engine* e, int iters, float* ms_host, double* flops
  * "z<ci>" (decimal conv index in eosvos_num_convs order, e.g. "z0", "z17"), GroupNorm engines only: the dense
  * {B,Ho,Wo,cout} buffer of normalised conv ci that holds its raw (pre-norm) output z after a forward and, overwritten
  * in place, dL/dz after a backward.  On a frozen-BatchNorm engine, or for a conv without a norm layer (the classifier),
- * the name fails like any unknown name. */
+ * the name fails like any unknown name.
+ * Plain DeepLabV3 engines have no decoder: "d1" / "g_d1" are the output of the head's 3x3 conv (classifier.1) and its
+ * gradient, "lowlog" / "g_low" the classifier's, all on the ASPP map (stride 8: {B,h8,w8,256} and {B,h8,w8,1}); "dcat",
+ * "d2" and their gradients are unknown names there. */
 /* Measurement aid: HIP events around every launch of the matrix-core kernels, on the stream each one runs on.
  * profile_read returns, per kernel symbol (names: max_kernels x 64 chars), launches, summed duration (ms) and summed
  * executed fp32-equivalent FLOPs since profile_launches(e, 1).  bench.py's roofline (dominant kernel by time). */

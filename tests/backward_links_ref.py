@@ -18,7 +18,8 @@ Everything here is dtype-generic (fp64 for the reference, fp32 for torch's own e
 CPU and makes no engine call.  tests/test_backward_links_host.py proves every function against autograd on the oracle
 network; tests/test_gpu_backward_links.py feeds them the engine's buffers.
 
-Scope: DeepLabV3+ on ResNet-50 / ResNet-101, frozen BatchNorm or GroupNorm.  Not covered: plain DeepLabV3.  The accumulating
+Scope: DeepLabV3+ on ResNet-50 / ResNet-101, frozen BatchNorm or GroupNorm.  Not covered: the backward pass of plain
+DeepLabV3 (`Net` describes its graph for the forward links, tests/forward_links_ref.py).  The accumulating
 (`gsum`) meta path and the trainable boundary: tests/meta_links_ref.py.
 """
 from collections import namedtuple
@@ -46,7 +47,8 @@ class Net:
 
     def __init__(self, encoder='resnet50', norm='bn'):
         assert norm in ('bn', 'gn'), norm
-        self.encoder, self.gn = encoder, norm == 'gn'
+        self.encoder, self.gn, self.v3 = encoder, norm == 'gn', topology.is_v3(encoder)
+        assert not (self.v3 and self.gn), 'plain DeepLabV3 has no GroupNorm variant'
         self.convs = topology.conv_infos(encoder)
         idx = {c.name: i for i, c in enumerate(self.convs)}
         self.blocks = []
@@ -59,8 +61,12 @@ class Net:
         a = 'classifier.0'
         self.aspp = [idx[f'{a}.convs.{j}.0'] for j in range(4)]
         self.pool, self.project = idx[a + '.convs.4.1'], idx[a + '.project.0']
-        self.dec1, self.dec_a = idx['decoder.conv1'], idx['decoder.last_conv.0']
-        self.dec_b, self.last = idx['decoder.last_conv.4'], idx['decoder.last_conv.8']
+        if self.v3:             # plain DeepLabV3: no decoder; DeepLabHead's 3x3 conv and classifier on the ASPP map
+            self.dec1 = self.dec_a = self.dec_b = -1
+            self.head3, self.last = idx['classifier.1'], idx['classifier.4']
+        else:
+            self.dec1, self.dec_a = idx['decoder.conv1'], idx['decoder.last_conv.0']
+            self.dec_b, self.last, self.head3 = idx['decoder.last_conv.4'], idx['decoder.last_conv.8'], -1
         self.poff, self.lroff, self.noff = [], [], []
         p = l = n = 0
         for c in self.convs:
@@ -93,7 +99,8 @@ class Net:
         return out
 
     def scales(self, norm_a):
-        """Per conv: its slice of the concatenated folded norm scales (norm-layer order), None for the classifier."""
+        """Per conv: its slice of the concatenated folded norm scales (norm-layer order), None for the classifier.  The folded
+        shifts `norm_b` have the same layout and are sliced the same way."""
         return [norm_a[o:o + c.cout] if c.norm else None for c, o in zip(self.convs, self.noff)]
 
 
@@ -152,6 +159,7 @@ def maxpool_bwd(c1, g):
 
 # ---- weight links -----------------------------------------------------------------------------------------------------------
 def weight_links(net):
+    assert not net.v3, 'the backward links cover DeepLabV3+ only'
     L = [None] * len(net.convs)
     L[0] = WeightLink(0, 'stem', 'x', 'g_c1', 0)
     for i, b in enumerate(net.blocks):
@@ -189,6 +197,7 @@ def _hw(t):
 def data_links(net):
     """Every data link, in the order `backward_impl` runs them.  fn(T, W, A) -> the link's buffer; T: name -> NCHW tensor,
     W: per conv (weight, bias), A: per conv scale."""
+    assert not net.v3, 'the backward links cover DeepLabV3+ only'
     cv = net.convs
     L = []
 

@@ -27,10 +27,14 @@ GN_K, GN_CAP = 4, 1e-4                  # the GroupNorm links' K and the cap on 
 GN_GPU_FRAMES = [(65, 97, 1, 12), (65, 97, 3, 14), (257, 261, 1, 41), (65, 97, 3, 31), (65, 97, 1, 32)]
 
 
-def capture(h, w, batch, encoder='resnet50', norm='bn', seed=7, engine_state=False):
+def capture(h, w, batch, encoder='resnet50', norm='bn', seed=7, engine_state=False, fwd=None):
     """(net, buffers under the engine's names, weights, scales, autograd's weight gradients, (gamma, beta) per conv) of one
-    forward + loss + backward.  engine_state: the float32 state the GPU tests load, cast to float64."""
+    forward + loss + backward.  engine_state: the float32 state the GPU tests load, cast to float64.  fwd: a dict that
+    receives what the forward links (tests/forward_links_ref.py) read beyond that: 'S', the folded shift per conv, and 'T',
+    the forward buffers no backward link names (`blk<i>.dsb` under a frozen norm, `lowlog`, `logits`).  Plain DeepLabV3
+    has no backward links: it needs fwd, and the result holds its forward buffers only and None for the weight gradients."""
     net = R.Net(encoder, norm)
+    assert fwd is not None or not net.v3, 'plain DeepLabV3 has forward links only: pass fwd'
     if engine_state:
         sd = {k: (v.double() if v.is_floating_point() else v) for k, v in synthetic.synthetic_state(encoder).items()}
     else:
@@ -79,8 +83,22 @@ def capture(h, w, batch, encoder='resnet50', norm='bn', seed=7, engine_state=Fal
             assert torch.equal(N[b['ds']].grad, N[b['c3']].grad)
             if net.gn:
                 T[f'blk{i}.dsb'] = N[b['ds']]
-    assert X[net.dec1] is X[net.blocks[net.tap + 1]['c1']]
+            elif fwd is not None:
+                fwd.setdefault('T', {})[f'blk{i}.dsb'] = N[b['ds']].detach()
     cat = X[net.project]
+    if fwd is not None:
+        fwd.setdefault('T', {}).update(lowlog=taps['low_logits'].detach(), logits=logits.detach())
+        fwd['S'] = [None] * len(net.convs) if net.gn else [
+            (P[c.norm + '.bias'] - P[c.norm + '.running_mean'] * P[c.norm + '.weight'].detach() / torch.sqrt(P[c.norm + '.running_var'] + deeplab.EPS)).detach()
+            if c.norm else None for c in net.convs]
+    if net.v3:
+        T = {k: v for k, v in T.items() if not k.split('.')[-1].startswith('g')}
+        T.update({'cat': cat, 'vec': X[net.pool], 'poolout': F.relu(N[net.pool]), 'proj': F.relu(N[net.project]), 'd1': X[net.last]})
+        T = {k: v.detach() for k, v in T.items()}
+        Wt = [(P[c.name + '.weight'].detach(), P[c.name + '.bias'].detach() if c.bias else None) for c in net.convs]
+        A = [P[c.norm + '.weight'].detach() / torch.sqrt(P[c.norm + '.running_var'] + deeplab.EPS) if c.norm else None for c in net.convs]
+        return net, T, Wt, A, None, R.affines(net, sd, torch.float64)
+    assert X[net.dec1] is X[net.blocks[net.tap + 1]['c1']]
     T.update({'cat': cat, 'g_cat': R.relumask(cat) * cat.grad, 'vec': X[net.pool], 'gvec': X[net.pool].grad,
               'poolout': F.relu(N[net.pool]), 'gp': N[net.pool].grad, 'proj': F.relu(N[net.project]), 'g_proj': N[net.project].grad,
               'dcat': X[net.dec_a], 'g_dcat': torch.cat((X[net.dec_a].grad[:, :256], N[net.dec1].grad), dim=1),

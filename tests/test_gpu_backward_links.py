@@ -32,7 +32,8 @@ the frames used here, and every GN link asserts it on the engine's operands befo
 
 One MARGIN line per link group (profiles/backward_links_margins.txt holds a run's lines).
 
-Not covered: plain DeepLabV3 (its own head graph, no GroupNorm variant).
+Not covered: the backward pass of plain DeepLabV3 (its own head graph, no GroupNorm variant).
+The forward pass these links start from, plain DeepLabV3's included: tests/test_gpu_forward_links.py.
 The accumulating (`gsum`) meta path and the trainable boundary: tests/test_gpu_meta_links.py.
 """
 import functools
@@ -217,14 +218,15 @@ def _audit_data(run, label, stage, cx=BN50):
     assert not bad, (label, bad)
 
 
-def _audit_gn(run, label, stages=None, forward=True, cx=GN50):
-    """GN links of a captured GroupNorm step (of the convs of `stages`, default all): the backward links, and the forward links
-    unless forward=False.  Each asserts the cap on torch32's own error on the engine's operands, then the bound."""
+def _audit_gn(run, label, stages=None, forward=True, cx=GN50, backward=True):
+    """GN links of a captured GroupNorm step (of the convs of `stages`, default all): the backward links unless backward=False
+    (a capture of a forward alone), and the forward links unless forward=False.  Each asserts the cap on torch32's own error on
+    the engine's operands, then the bound; a forward link with a ReLU also that no output is negative."""
     net = cx.net
     T64, T32 = R.Cast(run['T'], torch.float64), R.Cast(run['T'], torch.float32)
     GB64, GB32 = R.affines(net, _state(cx.encoder), torch.float64), R.affines(net, _state(cx.encoder), torch.float32)
     for kind, fn in (('gn_fwd', R.gn_fwd_link), ('gn_bwd', R.gn_bwd_link)):
-        if kind == 'gn_fwd' and not forward:
+        if not (forward if kind == 'gn_fwd' else backward):
             continue
         rows, bad = [], []
         for l in cx.gnlinks:
@@ -239,6 +241,8 @@ def _audit_gn(run, label, stages=None, forward=True, cx=GN50):
             rows.append((eg / bound, name, eg, e32, bound))
             if not eg <= bound:
                 bad.append(f'{name}: {eg:.3e} > {bound:.3e} (torch32 {e32:.2e}) at {_where(got, r64)}')
+            if kind == 'gn_fwd' and l.relu and not bool((got >= 0).all()):
+                bad.append(f'{name}: {int((got < 0).sum())} negative ReLU outputs')
         worst = max(rows)
         print(f'MARGIN {label} {kind} links ({len(rows)}): worst {worst[1]} {worst[2]:.2e} (torch32 {worst[3]:.2e}, bound {worst[4]:.2e})')
         assert not bad, (label, kind, bad)
