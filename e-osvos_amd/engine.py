@@ -11,7 +11,8 @@ import functools
 import torch
 
 from . import _ffi, bootstrap, boundary, cldice, loss_sum, potts, surface
-from .loss_names import LOSS_KINDS, resolve_cap, resolve_loss, resolve_radius  # noqa: F401  (their home; callers import them from here)
+from .loss_names import (BY_KEYWORD, FAMILIES, LOSS_KINDS, resolve_cap, resolve_loss,  # noqa: F401  (their home; callers import them
+                         resolve_name, resolve_radius)                                  # from here)
 from .topology import ARCH_ID, norm_layers, trainable
 
 
@@ -75,20 +76,21 @@ LossSpec = collections.namedtuple('LossSpec', 'n kinds weights combine fraction 
 
 @functools.lru_cache(maxsize=64, typed=True)
 def _resolve(name, fraction, radius, cap=None, window=None, depth=None):
-    """A sum spelling (`loss_sum.resolve`, `loss_sum.resolve_cap`) or a plain name (`resolve_loss` / `resolve_radius` /
-    `resolve_cap`, one term of weight 1) as a
+    """A sum spelling (`loss_sum.resolve_terms`) or a plain name (`loss_names.resolve_name`, one term of weight 1) as a
     LossSpec, kept per spelling: splitting and checking one takes ~10 us on the host, which a loss whose launches take 30 us
     would otherwise pay on every evaluation (`profiles/loss_sum_time.txt`); a spelling that raises is not kept."""
     combine = loss_sum.is_sum(name)
     if combine:
-        kinds, weights, _, f, r = loss_sum.resolve(name, fraction, radius)
-        c, w, k = loss_sum.resolve_cap(name, cap), loss_sum.resolve_window(name, window), loss_sum.resolve_depth(name, depth)
+        kinds, weights, _, knobs = loss_sum.resolve_terms(name, fraction=fraction, radius=radius, cap=cap, window=window, depth=depth)
     else:
-        kind, f = resolve_loss(name, fraction, radius, cap, window, depth)
-        kinds, weights, r, c, w = [kind], [1.0], resolve_radius(name, radius), resolve_cap(name, cap), potts.resolve_window(name, window)
-        k = cldice.resolve_depth(name, depth)
+        kind, knobs = resolve_name(name, fraction, radius, cap, window, depth)
+        kinds, weights = [kind], [1.0]
     n = len(kinds)
-    return LossSpec(n, (ctypes.c_int * n)(*kinds), (ctypes.c_float * n)(*weights), combine, f, r, c, w, k)
+    return LossSpec(n, (ctypes.c_int * n)(*kinds), (ctypes.c_float * n)(*weights), combine, *knobs)
+
+
+# the order `_loss_spec` has always applied a spelling's knobs in: depth, window, cap, fraction, radius
+_APPLIED = (*reversed(FAMILIES[2:]), *FAMILIES[:2])
 
 
 def check_ignore(ignore):
@@ -250,25 +252,29 @@ class Engine:
         0.25 on a new engine)."""
         _ffi.check(self.lib.eosvos_set_loss_bootstrap(self.h, bootstrap.check_fraction(fraction)))
 
+    def _set_whole(self, keyword, value):
+        """A whole-number knob for every later evaluation on this engine, by its family's entry point: 0 for the frame-size
+        default, otherwise what the family's check lets through (a bool is no 0)."""
+        family = BY_KEYWORD[keyword]
+        _ffi.check(getattr(self.lib, 'eosvos_' + family.setter)(self.h, 0 if value == 0 and not isinstance(value, bool)
+                                                                 else family.check(value)))
+
     def set_loss_boundary(self, radius):
         """The window radius of `boundary_f` / `cross_entropy_and_boundary_f` for every later evaluation on this engine
         (`eosvos_set_loss_boundary`): 1 .. 16, or 0 for the frame-size default `boundary.default_radius(H, W)`, which a new
         engine has."""
-        _ffi.check(self.lib.eosvos_set_loss_boundary(self.h, 0 if radius == 0 and not isinstance(radius, bool)
-                                                     else boundary.check_radius(radius)))
+        self._set_whole('radius', radius)
 
     def set_loss_surface(self, cap):
         """The distance cap of `surface` for every later evaluation on this engine (`eosvos_set_loss_surface`): 1 .. 4095, or
         0 for the frame-size default `surface.default_cap(H, W)`, which a new engine has.  The default is untuned."""
-        _ffi.check(self.lib.eosvos_set_loss_surface(self.h, 0 if cap == 0 and not isinstance(cap, bool)
-                                                    else surface.check_cap(cap)))
+        self._set_whole('cap', cap)
 
     def set_loss_cldice(self, depth):
         """The depth (the number of erosions of the soft skeleton) of `cldice` for every later evaluation on this engine
         (`eosvos_set_loss_cldice`): 1 .. 16, or 0 for the frame-size default `cldice.default_depth(H, W)`, which a new engine
         has.  The default is untuned."""
-        _ffi.check(self.lib.eosvos_set_loss_cldice(self.h, 0 if depth == 0 and not isinstance(depth, bool)
-                                                   else cldice.check_depth(depth)))
+        self._set_whole('depth', depth)
 
     def set_loss_potts(self, window=None, dilation=None, sigma_xy=None, sigma_rgb=None):
         """Window radius (1 .. 7), dilation (1 .. 4, radius * dilation <= 16) and sigmas (finite, > 0) of `potts` for every
@@ -294,16 +300,11 @@ class Engine:
         """The LossSpec of a spelled `loss_func` (`_resolve`); a fraction, radius, cap, window or depth carried by the spelling or
         the keyword becomes the engine's before the call that follows."""
         spec = _resolve(name, fraction, radius, cap, window, depth)
-        if spec.depth is not None:
-            self.set_loss_cldice(spec.depth)
-        if spec.window is not None and spec.window != (None, None):
-            self.set_loss_potts(*spec.window)
-        if spec.cap is not None:
-            self.set_loss_surface(spec.cap)
-        if spec.fraction is not None:
-            self.set_loss_bootstrap(spec.fraction)
-        if spec.radius is not None:
-            self.set_loss_boundary(spec.radius)
+        for family in _APPLIED:
+            knob = getattr(spec, family.keyword)
+            args = knob if isinstance(knob, tuple) else (knob,)      # (potts carries a pair; (None, None) asks for nothing)
+            if any(a is not None for a in args):
+                getattr(self, family.setter)(*args)
         return spec
 
     def _loss_on_forward(self, spec, masks, ignore, out):
@@ -618,11 +619,12 @@ class Engine:
                                               int(v is not None), v or 0.0, _ptr(out), _ptr(grad)))
         return out, grad
 
-    def _surface_args(self, masks, cap, ignore):
-        """(images, H, W, the cap as the library takes it, the void label as a ctypes pointer or None) of (B, H, W) / (H, W)."""
-        assert masks.is_cuda and masks.dtype == torch.float32 and masks.is_contiguous() and masks.dim() in (2, 3)
+    def _frame_args(self, maps, keyword, value, ignore):
+        """(images, H, W, the family's knob as the library takes it (0: the shape's default), the void label as a ctypes pointer
+        or None) of (B, H, W) / (H, W)."""
+        assert maps.is_cuda and maps.dtype == torch.float32 and maps.is_contiguous() and maps.dim() in (2, 3)
         v = None if ignore is None else ctypes.byref(ctypes.c_float(check_ignore(ignore)))
-        return (masks.shape[0] if masks.dim() == 3 else 1, *masks.shape[-2:], 0 if cap is None else surface.check_cap(cap), v)
+        return (maps.shape[0] if maps.dim() == 3 else 1, *maps.shape[-2:], 0 if value is None else BY_KEYWORD[keyword].check(value), v)
 
     def surface_loss(self, logits, masks, cap=None, ignore=None):
         """`surface` of device tensors (B, H, W) or (H, W) of any frame size up to 4096 a side (`eosvos_surface_loss`); `cap`
@@ -631,7 +633,7 @@ class Engine:
         self._check_stream()
         logits, masks = logits.contiguous(), masks.contiguous()
         assert logits.is_cuda and logits.dtype == torch.float32 and logits.shape == masks.shape
-        b, h, w, cap, v = self._surface_args(masks, cap, ignore)
+        b, h, w, cap, v = self._frame_args(masks, 'cap', cap, ignore)
         out, grad = torch.empty(1, device=self.device), torch.empty_like(logits)
         _ffi.check(self.lib.eosvos_surface_loss(self.h, _ptr(logits), _ptr(masks), b, h, w, cap, v, _ptr(out), _ptr(grad)))
         return out, grad
@@ -641,16 +643,10 @@ class Engine:
         squared distances to the other class as int32 and the weights as float32, of the targets' shape."""
         self._check_stream()
         masks = masks.contiguous()
-        b, h, w, cap, v = self._surface_args(masks, cap, ignore)
+        b, h, w, cap, v = self._frame_args(masks, 'cap', cap, ignore)
         c, wt = torch.empty(masks.shape, dtype=torch.int32, device=self.device), torch.empty_like(masks)
         _ffi.check(self.lib.eosvos_surface_weights(self.h, _ptr(masks), b, h, w, cap, v, _ptr(c), _ptr(wt)))
         return c, wt
-
-    def _cldice_args(self, maps, depth, ignore):
-        """(images, H, W, the depth as the library takes it, the void label as a ctypes pointer or None) of (B, H, W) / (H, W)."""
-        assert maps.is_cuda and maps.dtype == torch.float32 and maps.is_contiguous() and maps.dim() in (2, 3)
-        v = None if ignore is None else ctypes.byref(ctypes.c_float(check_ignore(ignore)))
-        return (maps.shape[0] if maps.dim() == 3 else 1, *maps.shape[-2:], 0 if depth is None else cldice.check_depth(depth), v)
 
     def cldice_loss(self, logits, masks, depth=None, ignore=None):
         """`cldice` of device tensors (B, H, W) or (H, W) of any frame size up to 4096 a side (`eosvos_cldice_loss`); `depth`
@@ -659,7 +655,7 @@ class Engine:
         self._check_stream()
         logits, masks = logits.contiguous(), masks.contiguous()
         assert logits.is_cuda and logits.dtype == torch.float32 and logits.shape == masks.shape
-        b, h, w, depth, v = self._cldice_args(masks, depth, ignore)
+        b, h, w, depth, v = self._frame_args(masks, 'depth', depth, ignore)
         out, grad = torch.empty(1, device=self.device), torch.empty_like(logits)
         _ffi.check(self.lib.eosvos_cldice_loss(self.h, _ptr(logits), _ptr(masks), b, h, w, depth, v, _ptr(out), _ptr(grad)))
         return out, grad
@@ -670,7 +666,7 @@ class Engine:
         equal `ignore`.  The debugging and visualisation view of the selection chain."""
         self._check_stream()
         maps = maps.contiguous()
-        b, h, w, depth, v = self._cldice_args(maps, depth, ignore)
+        b, h, w, depth, v = self._frame_args(maps, 'depth', depth, ignore)
         if masks is not None:
             masks = masks.contiguous()
             assert masks.is_cuda and masks.dtype == torch.float32 and masks.shape == maps.shape

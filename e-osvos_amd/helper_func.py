@@ -39,6 +39,7 @@ import torch
 from . import loss_sum
 from . import tta as tta_views
 from . import zoom as zoom_pass
+from .loss_names import KEYWORDS
 from .networks import DeepLabV3, DeepLabV3Plus
 
 
@@ -49,10 +50,7 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
     per_image = loss_kwargs.get('per_image', True)
     # a plain name is the sum of one term here (the engine still runs it as that one kind); unknown names and bad suffixes:
     # NotImplementedError; a keyword without a term of its family, out of range or against a suffix: ValueError
-    names = loss_sum.resolve(loss_func, loss_kwargs.get('fraction'), loss_kwargs.get('radius'), per_image)[2]
-    loss_sum.resolve_cap(loss_func, loss_kwargs.get('cap'))
-    loss_sum.resolve_window(loss_func, loss_kwargs.get('window'))
-    loss_sum.resolve_depth(loss_func, loss_kwargs.get('depth'))
+    names = loss_sum.resolve_terms(loss_func, per_image, **{k: loss_kwargs.get(k) for k in KEYWORDS})[2]
     if 'class_balanced_cross_entropy' in names and not loss_kwargs.get('size_average', True):
         raise NotImplementedError('class_balanced_cross_entropy with size_average=False')
     if not per_image:
@@ -62,7 +60,7 @@ def compute_loss(loss_func, outputs, gts, loss_kwargs=None):
         raise RuntimeError('compute_loss needs logits produced by eosvos_amd.networks.DeepLabV3Plus '
                            '(there is no CPU/eager path)')
     gts = gts.contiguous().float()
-    kw = {k: loss_kwargs[k] for k in ('ignore', 'fraction', 'radius', 'cap', 'window', 'depth') if loss_kwargs.get(k) is not None}
+    kw = {k: loss_kwargs[k] for k in ('ignore', *KEYWORDS) if loss_kwargs.get(k) is not None}
     if loss_kwargs.get('batch_average', True):
         loss = eng.loss(loss_func, gts, **kw).view(())      # also leaves dL/dlogits in the engine
         loss._eosvos_engine = eng

@@ -17,11 +17,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from .loss_names import (BOOTSTRAP, BOUNDARY_KINDS, CLDICE, CLDICE_KINDS, POTTS, POTTS_KINDS, SURFACE, SURFACE_KINDS, parse_boundary,
-                         parse_bootstrap, parse_cldice, parse_potts, parse_surface, resolve_loss, resolve_radius)
-from .loss_names import resolve_depth as _term_depth
-from .loss_names import resolve_cap as _term_cap
-from .loss_names import resolve_window as _term_window
+from .loss_names import FAMILIES, LOSS_KINDS, belongs, kind_of, resolve_knob
 
 MAX_TERMS = 4                           # EOSVOS_LOSS_MAX_TERMS of include/eosvos.h
 _WEIGHT = re.compile(r'[0-9]+(\.[0-9]+)?\Z')
@@ -45,11 +41,9 @@ def _weight(literal):
     return float(best) if best > 0 else None
 
 
-def parse(name):
-    """A spelled sum -> [(weight, term name), ...] in spelled order; a single name is the sum of one term of weight 1.  The
-    weight is the fp32 value nearest to its literal, as a float.  The split happens before any term reaches `bootstrap.parse`
-    / `boundary.parse`; each term name is then checked by `loss_names.resolve_loss`.  Anything outside the grammar, an unknown
-    term name and a bad suffix under a known prefix raise NotImplementedError like an unknown loss name."""
+def _split(name):
+    """A spelled sum -> [(weight, term name, kind id, the term's family or None), ...] in spelled order: `parse`, with what
+    `loss_names.kind_of` found when it checked each term."""
     bad = NotImplementedError(f"loss_func='{name}'")
     if not isinstance(name, str) or name == '' or any(c.isspace() for c in name):
         raise bad
@@ -65,11 +59,18 @@ def parse(name):
         if w is None or term == '' or '*' in weight:
             raise bad
         try:
-            resolve_loss(term)
+            terms.append((w, term, *kind_of(term)))
         except (KeyError, NotImplementedError):
             raise bad from None
-        terms.append((w, term))
     return terms
+
+
+def parse(name):
+    """A spelled sum -> [(weight, term name), ...] in spelled order; a single name is the sum of one term of weight 1.  The
+    weight is the fp32 value nearest to its literal, as a float.  The split happens before any term reaches `loss_names`; each
+    term name is then checked by `loss_names.kind_of`.  Anything outside the grammar, an unknown term name and a bad suffix
+    under a known prefix raise NotImplementedError like an unknown loss name."""
+    return [(w, term) for w, term, _, _ in _split(name)]
 
 
 def flat_spelling(name):
@@ -81,64 +82,59 @@ def flat_spelling(name):
     return '+'.join(pieces)
 
 
-def resolve(name, fraction=None, radius=None, per_image=True):
-    """A spelled sum with the keyword forms -> (kinds, weights, term names, fraction or None, radius or None).  `fraction` /
-    `radius` belong to the one term of their family: without such a term, or against a disagreeing suffix, ValueError.  The
-    returned fraction / radius are what the name or the keyword carries (None: the engine's current value stays).  `per_image`
-    False turns a `lovasz_hinge` term into `lovasz_hinge_flat`.  The same kind twice, or both boundary kinds (they share the
-    engine's one radius), is a ValueError."""
-    terms = [(w, 'lovasz_hinge_flat' if t == 'lovasz_hinge' and not per_image else t) for w, t in parse(name)]
-    names = [t for _, t in terms]
-    kinds = [resolve_loss(t)[0] for t in names]
-    if len(set(kinds)) != len(kinds):
+# `fraction` and `radius` are refused together before either is resolved, as `resolve` has always done; each later knob on its own
+_ROUNDS = (FAMILIES[:2],) + tuple((family,) for family in FAMILIES[2:])
+
+
+def resolve_terms(name, per_image=True, distinct=True, **given):
+    """The one resolution of a spelled sum (or single name): split once, then for every family whose keyword is in `given`
+    (`cap=None` asks for the cap the spelling carries) its one term's knob.  A keyword belongs to the one term of its family:
+    without such a term, or against a disagreeing suffix, ValueError; two terms of one family (they share the engine's one
+    value) are a ValueError too, and with `distinct` so is any kind named twice.  `per_image` False turns a `lovasz_hinge` term
+    into `lovasz_hinge_flat`.  Returns (kinds, weights, term names, the knobs asked for in FAMILIES' order: what the name or the
+    keyword carries; None: the engine's value stays)."""
+    terms = [(w, 'lovasz_hinge_flat', LOSS_KINDS['lovasz_hinge_flat'], f) if t == 'lovasz_hinge' and not per_image else (w, t, k, f)
+             for w, t, k, f in _split(name)]
+    kinds = [k for _, _, k, _ in terms]
+    if distinct and len(set(kinds)) != len(kinds):
         raise ValueError(f"loss_func='{name}' names a loss twice")
-    boundary_terms = [t for t in names if parse_boundary(t)[0] in BOUNDARY_KINDS]
-    if len(boundary_terms) > 1:
-        raise ValueError(f"loss_func='{name}' holds both boundary kinds; they share the engine's one radius")
-    bootstrap_terms = [t for t in names if parse_bootstrap(t)[0] == BOOTSTRAP]
-    if fraction is not None and not bootstrap_terms:
-        raise ValueError(f"fraction= belongs to '{BOOTSTRAP}', which is no term of '{name}'")
-    if radius is not None and not boundary_terms:
-        raise ValueError(f"radius= belongs to {' / '.join(repr(k) for k in BOUNDARY_KINDS)}, neither is a term of '{name}'")
-    f = resolve_loss(bootstrap_terms[0], fraction)[1] if bootstrap_terms else None
-    r = resolve_radius(boundary_terms[0], radius) if boundary_terms else None
-    return kinds, [w for w, _ in terms], names, f, r
+    mine = {family.keyword: [t for _, t, _, f in terms if f is family] for family in FAMILIES if family.keyword in given}
+    knobs = {}
+    for families in _ROUNDS:
+        families = [family for family in families if family.keyword in given]
+        for family in families:
+            if len(mine[family.keyword]) > 1:
+                raise ValueError(f"loss_func='{name}' holds both boundary kinds; they share the engine's one radius"
+                                 if family.keyword == 'radius' else f"loss_func='{name}' names a loss twice")
+        for family in families:
+            if given[family.keyword] is not None and not mine[family.keyword]:
+                raise belongs(family, f"{'neither is a' if len(family.kinds) > 1 else 'which is no'} term of '{name}'")
+        for family in families:
+            term = mine[family.keyword]
+            knobs[family.keyword] = resolve_knob(family, term[0], given[family.keyword]) if term else None
+    return kinds, [w for w, _, _, _ in terms], [t for _, t, _, _ in terms], list(knobs.values())
+
+
+def resolve(name, fraction=None, radius=None, per_image=True):
+    """`resolve_terms` for `fraction` and `radius` -> (kinds, weights, term names, fraction or None, radius or None)."""
+    kinds, weights, names, knobs = resolve_terms(name, per_image, fraction=fraction, radius=radius)
+    return kinds, weights, names, *knobs
 
 
 def resolve_cap(name, cap=None):
-    """The distance cap a spelled sum (or single name) carries, or None: `cap` belongs to the one `surface` term, as `fraction`
-    and `radius` belong to theirs in `resolve`: without such a term, or against a disagreeing suffix, ValueError; the term named
-    twice is a ValueError too.  A `surface` term beside a boundary kind is allowed: the cap and the radius are separate."""
-    surface_terms = [t for _, t in parse(name) if parse_surface(t)[0] in SURFACE_KINDS]
-    if len(surface_terms) > 1:
-        raise ValueError(f"loss_func='{name}' names a loss twice")
-    if cap is not None and not surface_terms:
-        raise ValueError(f"cap= belongs to '{SURFACE}', which is no term of '{name}'")
-    return _term_cap(surface_terms[0], cap) if surface_terms else None
+    """The distance cap a spelled sum (or single name) carries, or None.  A `surface` term beside a boundary kind is allowed: the
+    cap and the radius are separate."""
+    return resolve_terms(name, distinct=False, cap=cap)[3][0]
 
 
 def resolve_window(name, window=None):
-    """The window a spelled sum (or single name) carries, as (radius or None, dilation or None), or None without a `potts`
-    term: `window` belongs to the one `potts` term as `cap` belongs to `surface` in `resolve_cap`: without such a term, or
-    against a disagreeing suffix, ValueError; two `potts` terms (they share the engine's one window) are a ValueError too."""
-    potts_terms = [t for _, t in parse(name) if parse_potts(t)[0] in POTTS_KINDS]
-    if len(potts_terms) > 1:
-        raise ValueError(f"loss_func='{name}' names a loss twice")
-    if window is not None and not potts_terms:
-        raise ValueError(f"window= belongs to '{POTTS}', which is no term of '{name}'")
-    return _term_window(potts_terms[0], window) if potts_terms else None
+    """The window a spelled sum (or single name) carries, as (radius or None, dilation or None), or None without a `potts` term."""
+    return resolve_terms(name, distinct=False, window=window)[3][0]
 
 
 def resolve_depth(name, depth=None):
-    """The depth a spelled sum (or single name) carries, or None: `depth` belongs to the one `cldice` term as `cap` belongs to
-    `surface` in `resolve_cap`: without such a term, or against a disagreeing suffix, ValueError; two `cldice` terms (they share
-    the engine's one depth) are a ValueError too."""
-    cldice_terms = [t for _, t in parse(name) if parse_cldice(t)[0] in CLDICE_KINDS]
-    if len(cldice_terms) > 1:
-        raise ValueError(f"loss_func='{name}' names a loss twice")
-    if depth is not None and not cldice_terms:
-        raise ValueError(f"depth= belongs to '{CLDICE}', which is no term of '{name}'")
-    return _term_depth(cldice_terms[0], depth) if cldice_terms else None
+    """The depth a spelled sum (or single name) carries, or None."""
+    return resolve_terms(name, distinct=False, depth=depth)[3][0]
 
 
 def combine_host(values, grads, weights):
